@@ -9,9 +9,15 @@ proofs per step (independent units, no data-path collective) -> weak scaling; va
 `python bench.py --gpus N` without a launcher starts the N rank processes itself (fresh children, before this process touches
 the GPU); under torch.distributed.run it reads RANK / WORLD_SIZE.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline` and `cpu_baseline`; the other half of the metric
-is the object `r1cs_prove` (configs[2]: 256 provers x (16 x 64 bit)), with its own `roofline` and `cpu_baseline`, and
-`shuffle_2e14` (configs[3] on one GPU).
+Prints ONE JSON line on rank 0.  A plain run measures the headline only: it sets up, warms up, times --steps steps, writes
+the last step's outputs if --dump-outputs is given and prints the line (`value`, `ms_per_step`, ...).  --full adds every
+other measurement: `roofline` and `cpu_baseline`, the replay of one batch, the kernel timing regions, the secondary
+verification legs, the other half of the metric -- the object `r1cs_prove` (configs[2]: 256 provers x (16 x 64 bit)), with
+its own `roofline` and `cpu_baseline` -- and `shuffle_2e14` (configs[3] on one GPU); in a plain run those keys are null.
+
+--dump-outputs DIR: after the timed steps, the per-proof accept bits of the timed region's last step (what a caller of
+bpgpu_r1cs_verify_batch_dev receives) as DIR/accept_bits.npy, float32 (DIR/accept_bits_rank<r>.npy on rank r > 0).  The
+workload is generated from fixed seeds, so the same arguments give the same inputs and the same last batch in every run.
 """
 import argparse
 import hashlib
@@ -429,16 +435,24 @@ def main():
                     help="number of DIFFERENT batches of proofs the workload holds; the timed region (and the one-call legs) cycle "
                          "through them, so the fixed-base table rows a step gathers (110 MB of a 57 GB table) are never the rows of "
                          "a recent step: 256 batches touch 28 GB of rows per cycle against 256 MiB of Infinity Cache")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-combined", action="store_true", help="skip the secondary verification measurements (one-call stream, H2D-"
-                                                               "inclusive, device transcript, wire format, combined batch check, single batch)")
-    ap.add_argument("--no-prover", action="store_true", help="skip the R1CS prover measurements (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement: CPU baselines, the one-batch replay, kernel timing "
+                         "(rooflines), the secondary verification legs, the prover and the shuffle (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the accept bits of the timed region's last step to DIR/accept_bits.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-combined", action="store_true", help="with --full: skip the secondary verification measurements (one-call "
+                                                               "stream, H2D-inclusive, device transcript, wire format, combined batch "
+                                                               "check, single batch)")
+    ap.add_argument("--no-prover", action="store_true", help="with --full: skip the R1CS prover measurements (N = 1 only)")
     ap.add_argument("--prover-threads", type=int, default=3, help="worker threads (one context each) of the prover stream")
     ap.add_argument("--prover-batches", type=int, default=12, help="batches of 256 provers in the timed prover stream")
     ap.add_argument("--workload-cache", default=None,
                     help="pickle of the generated workload (written if absent); lets a profiled run skip the fork pool")
     ap.add_argument("--one-call-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.one_call_child:
         _one_call_child(a.one_call_child, a.window_bits)
         return
@@ -486,7 +500,7 @@ def main():
         wl = pickle.load(f)
     cpu = cpu1 = cpu_prove = None
     pool = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         pool = mp.get_context("fork").Pool(ncpu)
         cpu, cpu1, cpu_prove = _cpu_baseline(pool, ncpu, wl, nb)
     n1, n2, k, m = wl["dims"]
@@ -494,7 +508,7 @@ def main():
     pts, sc, ch = wl["points"], wl["scalars"], wl["challenges"]
     # ---- secondary: the one-call entry point, measured in a fresh process BEFORE this one takes the GPU (one after the other)
     one_call = None
-    if rank == 0 and world == 1 and not a.no_combined and nb == 1024:
+    if a.full and rank == 0 and world == 1 and not a.no_combined and nb == 1024:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-call-child", cache, "--window-bits", str(a.window_bits)],
                            capture_output=True, text=True, timeout=600, env={k_: v for k_, v in os.environ.items() if k_ != "GPU_MAX_HW_QUEUES"})
         if r.returncode != 0:      # a secondary leg: reported in its place (and on stderr), the headline line survives
@@ -624,11 +638,22 @@ def main():
     counter[0] = 0
     # ======== the timed region: no event timing inside it
     dt = timed(lambda i: step(), a.steps)
-    for c, d in zip(ctxs, d_oks):
-        assert c.download(d, 4 * nb) == all_ok
+    last = (counter[0] - 1) % len(ctxs)          # the context of the timed region's last step
+    for j, (c, d) in enumerate(zip(ctxs, d_oks)):
+        got = c.download(d, 4 * nb)
+        assert got == all_ok
+        if j == last:
+            last_ok = got
+    if a.dump_outputs:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "accept_bits.npy" if rank == 0 else f"accept_bits_rank{rank}.npy"),
+                np.frombuffer(last_ok, dtype="<u4").astype(np.float32))
     # the same region REPLAYING one batch (what rounds 1-3 reported): its 110 MB of table rows stay in the Infinity Cache
-    counter[0] = 0
-    dt_same = timed(lambda i: step_same(), a.steps)
+    dt_same = None
+    if a.full:
+        counter[0] = 0
+        dt_same = timed(lambda i: step_same(), a.steps)
 
     # ======== kernel timing, measured live with HIP events on the launch streams (bpgpu_profile_*), in two further regions:
     #   (1) the same K steps (at most 256) REPLAYED with an event pair around every launch of every context: the union of the
@@ -636,7 +661,7 @@ def main():
     #       can exceed the wall clock; the plain averages ("residency") are what a launch lasts among its neighbours;
     #   (2) a few un-pipelined steps on one context: each kernel's SOLO duration -- what rocprofv3 of a solo run measures
     #       (profiles/, tools/profile_all.sh) and the only duration that belongs to the kernel alone.  `roofline` uses it.
-    noprof = bool(os.environ.get("BPGPU_BENCH_NOPROF"))
+    noprof = not a.full or bool(os.environ.get("BPGPU_BENCH_NOPROF"))
     replay = solo = None
     if not noprof:
         def all_on():
@@ -678,7 +703,7 @@ def main():
         assert gpu.download(d_oks[0], 4 * nb) == all_ok
 
     fs = wire = comb = h2d = single = None
-    if not a.no_combined:
+    if a.full and not a.no_combined:
         # ---- secondary: ONE batch at a time (no pipelining): the latency of a batch's kernel chain
         lat = []
         ctxs[0].set_latency_mode(True)      # the context-level hint for un-pipelined callers (include/bpgpu.h)
@@ -789,7 +814,7 @@ def main():
     # mirror of the reference API over the C ABI.  A stream of batches on `prover_threads` worker threads, one context each.
     prove = shuffle = None
     steps_in_flight = len(ctxs)
-    if world == 1 and not a.no_prover:
+    if a.full and world == 1 and not a.no_prover:
         # the verification legs are done: their contexts (20 streams with hardware queues of their own) go, so that the prover's worker
         # contexts do not share queues with them; ctxs[0] keeps the circuit and the tables alive until the end
         steps_in_flight = len(ctxs)
@@ -956,7 +981,7 @@ def main():
     # ======== N > 1: configs[3] in its sharded form -- ONE 2^14-shuffle proof split over the ranks (every multi-scalar multiplication
     # by generator / point range, partial points all-gathered over RCCL and added: SURVEY 8e.2), proved and verified on all of them
     shuffle_sharded = None
-    if world > 1 and not a.no_prover and not os.environ.get("BPGPU_BENCH_NO_SHUFFLE"):
+    if a.full and world > 1 and not a.no_prover and not os.environ.get("BPGPU_BENCH_NO_SHUFFLE"):
         import ctypes as C
         from mpc_bulletproof_amd import sharding
         host = C.CDLL(os.path.join(ROOT, "tests", "host", "libbph_capi.so"))
@@ -1110,7 +1135,7 @@ def main():
                                            "synchronisation) after the continuous warm-up: a short run is a burst, and the clocks settle on the load pattern "
                                            "(profiles/r04_burst_precondition.log)" if a.steps <= 256 and int(os.environ.get('BPGPU_WARM_BURSTS', '8')) else
                                            "one un-timed step per context right up to the opening fence, after the continuous warm-up"),
-                       "value_replaying_one_batch": world * nb * a.steps / dt_same,
+                       "value_replaying_one_batch": (world * nb * a.steps / dt_same if dt_same else None),
                        "second_metric": ({"name": "R1CS constraints/s of the prover (configs[2]: 256 provers x (16 x 64 bit))", "value": prove.get("value"),
                                           "unit": "R1CS constraints/s", "cpu_baseline": (cpu_prove or {}).get("value")} if prove else None),
                        "h2d_inclusive_value": (h2d or {}).get("value"),
@@ -1121,9 +1146,10 @@ def main():
             "roofline": roof,
             "roofline_valu_issue": valu,
             "roofline_valu_issue_stale": pmc_stale,
-            "value_replaying_one_batch": {"value": world * nb * a.steps / dt_same, "unit": "verifications/s", "ms_per_step": dt_same / a.steps * 1e3,
-                                          "note": "the same timed region verifying ONE batch over and over (rounds 1-3's figure): its 110 MB of fixed-base "
-                                                  "table rows stay in the 256 MiB Infinity Cache; `value` cycles through distinct batches"},
+            "value_replaying_one_batch": ({"value": world * nb * a.steps / dt_same, "unit": "verifications/s", "ms_per_step": dt_same / a.steps * 1e3,
+                                           "note": "the same timed region verifying ONE batch over and over (rounds 1-3's figure): its 110 MB of fixed-base "
+                                                   "table rows stay in the 256 MiB Infinity Cache; `value` cycles through distinct batches"}
+                                          if dt_same else None),
             "r1cs_constraints_per_s": (prove or {}).get("value"),
             "roofline_int": {"bound": "valu_int (v_mad_u64_u32)", "scope": "variable-base + fixed-base halves of one step's mega_check MSMs / wall time per step",
                              "achieved": (fp_var + fp_fixed) * 94 / step_s / 1e12, "peak": MAD_PEAK_TOPS, "unit": "Tmad/s",
@@ -1145,8 +1171,9 @@ def main():
                              "note": f"the {nb} proofs of this workload, proved in lock-step by the GPU prover while it was generated "
                                      "(wall clock incl. host circuit building and transcripts)"} if wl.get("prove_seconds") else None),
         }
+        out["full"] = a.full
         if cpu is None:
-            out["cpu_baseline_reason"] = "--no-cpu-baseline"
+            out["cpu_baseline_reason"] = "--no-cpu-baseline" if a.full else "measured with --full only"
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
