@@ -483,6 +483,49 @@ int bpgpu_r1cs_verify_screened_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const
                                       const void *init_states_dev, const void *points_dev, const void *scalars_dev, const void *rho_dev,
                                       void *ok_dev, size_t *fallback_batches);
 
+/* MIXED queues: proofs of SEVERAL circuits in one call (NOT a reference API; a verifier service receives wallet updates, match
+ * settlements, range gadgets of several widths and shuffles at once).  One group per run of proofs of one circuit; the layouts of a
+ * group's operands are those of bpgpu_r1cs_verify_batch for its circuit (gadget_challenges: nb x nchi x 32 B for a circuit of
+ * bpgpu_circuit_create_param, NULL otherwise; rho: nb x 32 B random non-zero weights from the caller's CSPRNG; ok: nb int32
+ * verdicts of the screened calls, ignored by the combined calls).  Two groups may share a circuit handle.
+ *   _combined : sum over all groups and proofs of rho_p * mega_check_p as ONE point (64 zero bytes: every proof is valid).  For one
+ *               group of a one-phase circuit it is the point bpgpu_r1cs_verify_combined returns; it all-gathers the same way.  The
+ *               generator halves of all proofs share ONE fixed-base MSM (the generators are a prefix chain: a group of padded n
+ *               uses G_0..G_{n-1}, H_0..H_{n-1}), the proof points ONE bucket-method MSM.  A malformed operand (off-curve or
+ *               non-canonical point, non-canonical scalar, challenge, gadget challenge or weight) gives the POISON encoding (64
+ *               bytes 0xFF, not a point; bpgpu_points_sum rejects it) and raises the input flag; the call itself succeeds.
+ *   _screened : ok[] of every group equals what bpgpu_r1cs_verify_batch (bpgpu_r1cs_verify_batch_param for a parametric circuit)
+ *               returns for it, up to the 2^-250 chance that random weights cancel an invalid proof: the concatenated queue is cut
+ *               into checks of at most BPGPU_OPT_SCREEN_BATCH proofs, 2^16 proof points and BPGPU_MIXED_MAX_SEGMENTS runs of one
+ *               group (a check may span several groups and split one), the combined check of every one runs over the lanes of
+ *               BPGPU_OPT_STREAM_LANES, and only a check whose point is not the identity, that holds a malformed operand or a zero
+ *               weight takes the per-proof path, group run by group run.  fallback_batches (optional): how many checks did.
+ *   _dev      : operand pointers, ok[] and partial_xy_dev in HBM; asynchronous until bpgpu_sync (the screened call waits once,
+ *               between its two phases, like bpgpu_r1cs_verify_screened_dev).
+ * Shape errors fail the whole call before anything is launched: BPGPU_E_LEN (k >= 32, n1 > n, padded n = 2^k not the circuit's),
+ * BPGPU_E_GENS (2^k above the generators' capacity), BPGPU_E_ARG (a null pointer, gadget challenges given to a one-phase circuit or
+ * missing for a parametric one, ngroups > BPGPU_MIXED_MAX_GROUPS).  ngroups == 0 or only empty groups: BPGPU_OK, the identity.
+ * Device transcripts (init_states) and wire-format proofs are not taken here: challenges come from the host's transcript replay, the
+ * route a Rust host already has. */
+#define BPGPU_MIXED_MAX_GROUPS 64
+#define BPGPU_MIXED_MAX_SEGMENTS 16
+typedef struct bpgpu_verify_group {
+  const bpgpu_circuit *circuit;        /* one-phase, or parametric (bpgpu_circuit_create_param) */
+  size_t nb, n1, k;                    /* proofs in this group, phase-1 multipliers, padded_n = 2^k */
+  const void *points, *scalars, *challenges;
+  const void *gadget_challenges;       /* nb x nchi x 32 B for a parametric circuit, NULL otherwise */
+  const void *rho;                     /* nb x 32 B random non-zero weights */
+  void *ok;                            /* nb int32 verdicts (screened calls) */
+} bpgpu_verify_group;
+int bpgpu_r1cs_verify_mixed_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     uint8_t partial_xy[64]);
+int bpgpu_r1cs_verify_mixed_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         void *partial_xy_dev);
+int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     size_t *fallback_batches);
+int bpgpu_r1cs_verify_mixed_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         size_t *fallback_batches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2110,6 +2110,261 @@ int bpgpu_r1cs_verify_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
   return BPGPU_OK;
 }
 
+/* ---------------------------------------------------------------- mixed queues: proofs of several circuits in one call
+ * The groups' proofs are concatenated (group after group) and cut into checks; a check is a list of runs ("segments") of one group's
+ * consecutive proofs.  Each check is ONE ragged combined check (k_mixed.hip); the screened call re-verifies a failing check per
+ * proof, segment by segment, on each segment's own circuit. */
+namespace {
+struct MixSeg { size_t gi, lo, cnt; };
+struct MixCheck { size_t first, nseg; };   // a range of the plan's segment list
+}
+// shape checks of every group before anything is launched (the codes of the one-circuit calls); screened: ok[] must be given
+static int mixed_validate(const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, bool screened) {
+  if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
+  for (size_t i = 0; i < ngroups; i++) {
+    const bpgpu_verify_group &x = G[i];
+    const bpgpu_circuit *c = x.circuit;
+    if (!c) return BPGPU_E_ARG;
+    if (x.nb && (!x.points || !x.scalars || !x.challenges || !x.rho || (screened && !x.ok))) return BPGPU_E_ARG;
+    if ((c->nchi != 0) != (x.gadget_challenges != nullptr)) return BPGPU_E_ARG;
+    if (x.k >= 32) return BPGPU_E_LEN;
+    const size_t np = (size_t)1 << x.k, n = c->n;
+    if (n > np || x.n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;
+    if (np > g->cap) return BPGPU_E_GENS;
+  }
+  return BPGPU_OK;
+}
+static size_t mixed_nvar(const bpgpu_verify_group &x) { return 11 + x.circuit->m + 2 * x.k; }
+// cut the concatenated queue into checks of at most max_proofs proofs, max_points proof points (a single proof may exceed it) and
+// BPGPU_MIXED_MAX_SEGMENTS segments
+static void mixed_plan(const bpgpu_verify_group *G, size_t ngroups, size_t max_proofs, size_t max_points, std::vector<MixSeg> &segs,
+                       std::vector<MixCheck> &checks) {
+  size_t cp = 0, cpts = 0;
+  auto close = [&]() { if (!checks.empty() && checks.back().nseg) { checks.push_back(MixCheck{segs.size(), 0}); } cp = cpts = 0; };
+  checks.push_back(MixCheck{0, 0});
+  for (size_t gi = 0; gi < ngroups; gi++) {
+    const size_t nvar = mixed_nvar(G[gi]);
+    size_t lo = 0;
+    while (lo < G[gi].nb) {
+      if (checks.back().nseg == BPGPU_MIXED_MAX_SEGMENTS) close();
+      size_t room = max_proofs - cp, fit = cpts < max_points ? (max_points - cpts) / nvar : 0;
+      if (fit < room) room = fit;
+      if (!room) {
+        if (cp) { close(); continue; }
+        room = 1;      // one proof larger than the point budget: a check of its own
+      }
+      const size_t cnt = G[gi].nb - lo < room ? G[gi].nb - lo : room;
+      segs.push_back(MixSeg{gi, lo, cnt});
+      checks.back().nseg++;
+      cp += cnt; cpts += cnt * nvar; lo += cnt;
+      if (cp >= max_proofs || cpts >= max_points) close();
+    }
+  }
+  if (!checks.back().nseg) checks.pop_back();
+}
+// ONE ragged combined check on `ln`'s stream: partial_xy (HBM) = sum over the check's proofs of rho_p * mega_check_p.  The caller
+// resets ln's input flag; zero_rho (optional) is raised for a zero weight.
+static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group *G, const MixSeg *segs, size_t nseg,
+                              void *partial_xy, int *zero_rho) {
+  MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
+  for (size_t s = 0; s < nseg; s++) {
+    const bpgpu_verify_group &x = G[segs[s].gi];
+    const bpgpu_circuit *c = x.circuit;
+    const size_t lo = segs[s].lo, nvar = mixed_nvar(x), np = (size_t)1 << x.k;
+    MixSegIn &v = in[s];
+    v.circ = circuit_dev(c);
+    v.d = VerifyDims{segs[s].cnt, x.n1, c->n, np, x.k, c->m,
+                     c->nchi ? (const Words8 *)x.gadget_challenges + lo * c->nchi : nullptr, (size_t)ln->opt[BPGPU_OPT_VS_LARGE_MIN]};
+    v.nvar = nvar; v.nchi = c->nchi;
+    v.points = (const Words8 *)x.points + lo * nvar * 2;
+    v.proof_scalars = (const Words8 *)x.scalars + lo * 5;
+    v.challenges = (const Words8 *)x.challenges + lo * (6 + x.k);
+    v.rho = (const Words8 *)x.rho + lo;
+  }
+  void *scr;
+  CK(ws_get(ln, 14, verify_mixed_scratch_bytes(in, nseg, g->c), &scr));
+  MixedArgs a{in, nseg, scr, g->table, g->cap, g->c, ln->d_flag, zero_rho, (Words8 *)partial_xy, ln->prof ? &prof_mark_cb : nullptr, ln};
+  verify_mixed(ln->st, a);
+  return launch_ok(ln);
+}
+static int mixed_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, void *partial_xy) try {
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<MixSeg> segs;
+  std::vector<MixCheck> checks;
+  mixed_plan(G, ngroups, (size_t)-1, (size_t)-1, segs, checks);   // (checks cut at the segment cap only; each picks its own MSM route)
+  CK(flag_reset(ctx));
+  if (checks.empty()) { HIPCK(ctx, hipMemsetAsync(partial_xy, 0, 64, ctx->st)); return BPGPU_OK; }
+  void *dpart = partial_xy;
+  if (checks.size() > 1) CK(ws_get(ctx, 26, checks.size() * 64, &dpart));
+  for (size_t ci = 0; ci < checks.size(); ci++)
+    CK(mixed_check_locked(ctx, g, G, segs.data() + checks[ci].first, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
+  int *dbad2;
+  if (checks.size() > 1) {       // the checks' partials are valid points: their sum cannot raise the flag (a separate one all the same)
+    CK(ws_get(ctx, 27, 256, (void **)&dbad2));
+    points_sum(ctx->st, (const Words8 *)dpart, checks.size(), (Words8 *)partial_xy, dbad2);
+  }
+  mixed_poison(ctx->st, ctx->d_flag, (Words8 *)partial_xy);
+  return launch_ok(ctx);
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+// the per-proof path for one segment on lane ln: bpgpu_r1cs_verify_batch(_param)'s verdicts into the group's ok[] (HBM)
+static int mixed_per_proof_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group &x, size_t lo, size_t cnt) {
+  const bpgpu_circuit *c = x.circuit;
+  const size_t nvar = mixed_nvar(x);
+  const Words8 *chi = c->nchi ? (const Words8 *)x.gadget_challenges + lo * c->nchi : nullptr;
+  int32_t *ok = (int32_t *)x.ok + lo;
+  void *dchibad = nullptr;
+  if (chi) {        // a non-canonical gadget challenge rejects ITS proof, as in bpgpu_r1cs_verify_batch_param
+    CK(ws_get(ln, 18, cnt * 4, &dchibad));
+    HIPCK(ln, hipMemsetAsync(dchibad, 0, cnt * 4, ln->st));
+    scalars_check_proof(ln->st, chi, cnt * c->nchi, c->nchi, ln->d_flag, (int32_t *)dchibad);
+  }
+  CK(verify_batch_dev_locked(ln, g, c, cnt, x.n1, x.k, (const uint8_t *)x.points + lo * nvar * 64, (const uint8_t *)x.scalars + lo * 160,
+                             (const uint8_t *)x.challenges + lo * (6 + x.k) * 32, ok, nullptr, nullptr, chi));
+  if (dchibad) and_not(ln->st, ok, (const int32_t *)dchibad, cnt);
+  return launch_ok(ln);
+}
+static int mixed_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, size_t *fallback_batches) try {
+  if (fallback_batches) *fallback_batches = 0;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<MixSeg> segs;
+  std::vector<MixCheck> checks;
+  // proofs per check: BPGPU_OPT_SCREEN_BATCH, and at most 2^16 proof points (the one-instance bucket pipeline of k_pip2.hip)
+  mixed_plan(G, ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, segs, checks);
+  const size_t nchecks = checks.size();
+  if (!nchecks) return BPGPU_OK;
+  const size_t nlanes_opt = (size_t)ctx->opt[BPGPU_OPT_STREAM_LANES], nl = nchecks < nlanes_opt ? nchecks : nlanes_opt;
+  CK(stream_lanes(ctx, nl));
+  void *dpart, *dflag;
+  CK(ws_get(ctx, 26, nchecks * 64, &dpart));
+  CK(ws_get(ctx, 27, nchecks * 4, &dflag));
+  std::vector<uint8_t> hpart(nchecks * 64);
+  std::vector<int> hflag(nchecks);
+  auto fork = [&]() -> int {
+    HIPCK(ctx, hipEventRecord(ctx->lane_ev, ctx->st));
+    for (size_t l = 0; l < nl; l++) HIPCK(ctx, hipStreamWaitEvent(ctx->lanes[l]->st, ctx->lane_ev, 0));
+    return BPGPU_OK;
+  };
+  auto join = [&](int rc) -> int {
+    for (size_t l = 0; l < nl; l++)
+      if (hipEventRecord(ctx->lanes[l]->ev1, ctx->lanes[l]->st) != hipSuccess || hipStreamWaitEvent(ctx->st, ctx->lanes[l]->ev1, 0) != hipSuccess)
+        if (rc == BPGPU_OK) { ctx->err = "bpgpu_r1cs_verify_mixed_screened: joining the lanes failed"; rc = BPGPU_E_DEVICE; }
+    return rc;
+  };
+  // ---- phase 1: one ragged combined check per check; its flag holds malformed input and zero weights
+  CK(fork());
+  int rc = BPGPU_OK;
+  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
+    bpgpu_ctx *ln = ctx->lanes[ci % nl];
+    (void)((rc = flag_reset(ln)) ||
+           (rc = mixed_check_locked(ln, g, G, segs.data() + checks[ci].first, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, ln->d_flag)));
+    if (rc == BPGPU_OK && hipMemcpyAsync((int *)dflag + ci, ln->d_flag, 4, hipMemcpyDeviceToDevice, ln->st) != hipSuccess) rc = BPGPU_E_DEVICE;
+    if (rc) ctx->err = ln->err;
+  }
+  rc = join(rc);
+  if (rc) return rc;
+  CK(d2h(ctx, hpart.data(), dpart, nchecks * 64));
+  CK(d2h(ctx, hflag.data(), dflag, nchecks * 4));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  // ---- phase 2: all-accept for the checks that passed, the per-proof path segment by segment for the others
+  size_t nfall = 0;
+  CK(fork());
+  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
+    bool pass = hflag[ci] == 0;
+    for (size_t i = 0; i < 64 && pass; i++) pass = hpart[64 * ci + i] == 0;
+    const MixSeg *sg = segs.data() + checks[ci].first;
+    if (pass) {
+      for (size_t s = 0; s < checks[ci].nseg && rc == BPGPU_OK; s++)
+        if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) rc = BPGPU_E_DEVICE;
+      continue;
+    }
+    bpgpu_ctx *ln = ctx->lanes[nfall++ % nl];
+    for (size_t s = 0; s < checks[ci].nseg && rc == BPGPU_OK; s++) rc = mixed_per_proof_locked(ln, g, G[sg[s].gi], sg[s].lo, sg[s].cnt);
+    if (rc) ctx->err = ln->err;
+  }
+  rc = join(rc);
+  if (fallback_batches) *fallback_batches = nfall;
+  return rc;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+// host forms: every group's operands go up once (one staging buffer), the device form runs, the verdicts come back
+static int mixed_stage_locked(bpgpu_ctx *ctx, const bpgpu_verify_group *G, size_t ngroups, std::vector<bpgpu_verify_group> &D) {
+  size_t tot = 0;
+  auto sizes = [](const bpgpu_verify_group &x, size_t *b) {
+    const size_t nvar = mixed_nvar(x);
+    b[0] = x.nb * nvar * 64; b[1] = x.nb * 160; b[2] = x.nb * (6 + x.k) * 32; b[3] = x.gadget_challenges ? x.nb * x.circuit->nchi * 32 : 0;
+    b[4] = x.nb * 32; b[5] = x.nb * 4;
+  };
+  for (size_t i = 0; i < ngroups; i++) { size_t b[6]; sizes(G[i], b); for (size_t j : b) tot += (j + 255) / 256 * 256; }
+  void *base;
+  CK(ws_get(ctx, 29, tot, &base));
+  uint8_t *q = (uint8_t *)base;
+  D.assign(G, G + ngroups);
+  for (size_t i = 0; i < ngroups; i++) {
+    size_t b[6];
+    sizes(G[i], b);
+    const void *src[5] = {G[i].points, G[i].scalars, G[i].challenges, G[i].gadget_challenges, G[i].rho};
+    const void **dst[5] = {&D[i].points, &D[i].scalars, &D[i].challenges, &D[i].gadget_challenges, &D[i].rho};
+    for (int j = 0; j < 5; j++) {
+      if (src[j]) { CK(h2d(ctx, q, src[j], b[j])); *dst[j] = q; }
+      q += (b[j] + 255) / 256 * 256;
+    }
+    D[i].ok = q;
+    q += (b[5] + 255) / 256 * 256;
+  }
+  return BPGPU_OK;
+}
+int bpgpu_r1cs_verify_mixed_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         void *partial_xy_dev) {
+  if (!ctx || !partial_xy_dev) return BPGPU_E_ARG;
+  CK(mixed_validate(g, groups, ngroups, false));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return mixed_combined_locked(ctx, g, groups, ngroups, partial_xy_dev);
+}
+int bpgpu_r1cs_verify_mixed_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     uint8_t partial_xy[64]) try {
+  if (!ctx || !partial_xy) return BPGPU_E_ARG;
+  CK(mixed_validate(g, groups, ngroups, false));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_verify_group> D;
+  CK(mixed_stage_locked(ctx, groups, ngroups, D));
+  void *dout;
+  CK(ws_get(ctx, 4, 64, &dout));
+  CK(mixed_combined_locked(ctx, g, D.data(), ngroups, dout));
+  CK(d2h(ctx, partial_xy, dout, 64));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+int bpgpu_r1cs_verify_mixed_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         size_t *fallback_batches) {
+  if (fallback_batches) *fallback_batches = 0;
+  if (!ctx) return BPGPU_E_ARG;
+  CK(mixed_validate(g, groups, ngroups, true));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return mixed_screened_locked(ctx, g, groups, ngroups, fallback_batches);
+}
+int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     size_t *fallback_batches) try {
+  if (fallback_batches) *fallback_batches = 0;
+  if (!ctx) return BPGPU_E_ARG;
+  CK(mixed_validate(g, groups, ngroups, true));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_verify_group> D;
+  CK(mixed_stage_locked(ctx, groups, ngroups, D));
+  CK(mixed_screened_locked(ctx, g, D.data(), ngroups, fallback_batches));
+  for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+
 /* ---------------------------------------------------------------- IPP prover session */
 // (ctx->mu held) the session's buffers go back to the context's pool
 static void ipp_free_all(bpgpu_ctx *ctx, bpgpu_ipp *s) {

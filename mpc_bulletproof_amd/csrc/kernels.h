@@ -276,6 +276,31 @@ size_t verify_combined2_scratch_bytes(size_t nb, size_t nvar, size_t nfix);
 bool verify_combined2_supported(size_t nb, size_t nvar, int c, size_t padded_n);
 void verify_combined2(hipStream_t st, const CombinedArgs &a);
 
+// ---- ragged combined check (k_mixed.hip): sum_p rho_p * mega_check_p over proofs of SEVERAL circuits as ONE boundary point.
+// A segment is a run of consecutive proofs of one circuit; a check holds up to MIX_SEG_MAX of them.  The generator half sums into
+// the common layout [B, B_blinding, G_0..G_{N-1}, H_0..H_{N-1}], N = the largest padded n of the check's segments.
+constexpr size_t MIX_SEG_MAX = 16;
+struct MixSegIn {
+  CircuitDev circ; VerifyDims d;     // d.nb = the segment's proofs; d.chi = their gadget challenges (nb x nchi) or nullptr
+  size_t nvar, nchi;
+  const Words8 *points, *proof_scalars, *challenges, *rho;   // ABI bytes in HBM, from the segment's first proof on
+};
+struct MixedArgs {
+  const MixSegIn *seg; size_t nseg;  // host array, nseg <= MIX_SEG_MAX
+  void *scratch;                     // verify_mixed_scratch_bytes
+  const AffDev *table; size_t cap; int c;   // resident generator tables
+  int *bad;                          // malformed point, non-canonical scalar / challenge / gadget challenge / weight
+  int *zero_rho;                     // optional: set when a weight is zero (the screened call voids such a check)
+  Words8 *partial_xy;                // out: 64 boundary bytes
+  ProfMarkFn prof; void *prof_ctx;
+};
+size_t verify_mixed_scratch_bytes(const MixSegIn *seg, size_t nseg, int c /* the generator tables' window */);
+// front, one scalar assembly per segment, K1 and the k_pip2.hip tail (profiling slots 12, 13, 15) when the check fits the
+// one-instance bucket pipeline; otherwise the same front and column sum, then k_fixed.hip's and k_pip.hip's MSMs (all on `st`)
+void verify_mixed(hipStream_t st, const MixedArgs &a);
+// *bad != 0: out_xy := 64 bytes 0xFF (not a point; bpgpu_points_sum rejects it) -- the combined entry points' verdict on malformed input
+void mixed_poison(hipStream_t st, const int *bad, Words8 *out_xy);
+
 // the prover's blinding vectors drawn on the device from per-prover keys (k_transcript.hip, "BlindVec v1"):
 // sL / sR [p * stride + off + i] for i < cnt, plain canonical words
 void blind_vectors(hipStream_t st, const Words8 *keys, size_t nb, size_t cnt, Words8 *sL, Words8 *sR, size_t stride, size_t off);

@@ -16,8 +16,27 @@ SYMBOLS = [
     "bpgpu_r1cs_verify_batch", "bpgpu_r1cs_verify_batch_dev", "bpgpu_r1cs_verify_stream", "bpgpu_r1cs_verify_stream_dev", "bpgpu_r1cs_verify_screened", "bpgpu_r1cs_verify_screened_dev", "bpgpu_r1cs_verify_screened_fs_dev", "bpgpu_r1cs_verify_combined",
     "bpgpu_r1cs_verify_combined_dev", "bpgpu_r1cs_verify_batch_fs", "bpgpu_r1cs_verify_batch_fs_dev",
     "bpgpu_r1cs_verify_batch_wire", "bpgpu_r1cs_verify_batch_wire_dev", "bpgpu_r1cs_verify_batch_param", "bpgpu_r1cs_verify_batch_fs2",
-    "bpgpu_r1cs_verify_batch_fs2_dev",
+    "bpgpu_r1cs_verify_batch_fs2_dev", "bpgpu_r1cs_verify_mixed_combined", "bpgpu_r1cs_verify_mixed_combined_dev",
+    "bpgpu_r1cs_verify_mixed_screened", "bpgpu_r1cs_verify_mixed_screened_dev",
 ]
+
+
+MIXED_MAX_GROUPS = 64       # BPGPU_MIXED_MAX_GROUPS
+MIXED_MAX_SEGMENTS = 16     # BPGPU_MIXED_MAX_SEGMENTS
+
+
+class VerifyGroup(C.Structure):
+    """bpgpu_verify_group: one circuit's run of proofs in a mixed verification call (include/bpgpu.h)"""
+    _fields_ = [("circuit", C.c_void_p), ("nb", C.c_size_t), ("n1", C.c_size_t), ("k", C.c_size_t),
+                ("points", C.c_void_p), ("scalars", C.c_void_p), ("challenges", C.c_void_p),
+                ("gadget_challenges", C.c_void_p), ("rho", C.c_void_p), ("ok", C.c_void_p)]
+
+
+def _ptr(x):
+    """a device pointer (c_void_p / int / None) as an integer address or None"""
+    if x is None:
+        return None
+    return x.value if isinstance(x, C.c_void_p) else int(x)
 
 
 class BpGpuError(RuntimeError):
@@ -547,6 +566,60 @@ class BpGpu:
     def r1cs_verify_combined_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_out):
         self._ck(_lib.bpgpu_r1cs_verify_combined_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
                                                      d_points, d_scalars, d_challenges, d_rho, d_out))
+
+    # ---- mixed queues: groups of proofs of several circuits in one call.  A group is a dict with keys circuit, nb, n1, k, points,
+    # scalars, challenges, rho and, for a parametric circuit, gadget_challenges (the layouts of r1cs_verify_batch); the host forms
+    # take bytes, the _dev forms device pointers (and ok: the group's nb int32 verdicts in HBM for the screened call).
+    @staticmethod
+    def _groups(groups, dev):
+        arr = (VerifyGroup * max(len(groups), 1))()
+        keep, oks = [], []
+        for i, gr in enumerate(groups):
+            g = arr[i]
+            g.circuit = _ptr(gr["circuit"])
+            g.nb, g.n1, g.k = gr["nb"], gr["n1"], gr["k"]
+            for f in ("points", "scalars", "challenges", "gadget_challenges", "rho"):
+                v = gr.get(f)
+                if v is None:
+                    setattr(g, f, None)
+                elif dev:
+                    setattr(g, f, _ptr(v))
+                else:
+                    b = C.create_string_buffer(bytes(v), max(len(v), 1))
+                    keep.append(b)
+                    setattr(g, f, C.cast(b, C.c_void_p).value)
+            if dev:
+                g.ok = _ptr(gr.get("ok"))
+            else:
+                ok = (C.c_int32 * max(gr["nb"], 1))()
+                oks.append(ok)
+                g.ok = C.cast(ok, C.c_void_p).value
+        return arr, keep, oks
+
+    def r1cs_verify_mixed_combined(self, gens, groups):
+        """sum over all groups and proofs of rho_p * mega_check_p (64 bytes; all zero: every proof valid; 0xFF x 64: malformed input)"""
+        arr, keep, _ = self._groups(groups, False)
+        o = _out(64)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined(self.ctx, gens, arr, C.c_size_t(len(groups)), o))
+        return bytes(o)[:64]
+
+    def r1cs_verify_mixed_combined_dev(self, gens, groups, d_out):
+        arr, _, _ = self._groups(groups, True)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined_dev(self.ctx, gens, arr, C.c_size_t(len(groups)), d_out))
+
+    def r1cs_verify_mixed_screened(self, gens, groups):
+        """-> ([ok list per group], number of checks that took the per-proof path)"""
+        arr, keep, oks = self._groups(groups, False)
+        nf = C.c_size_t(0)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened(self.ctx, gens, arr, C.c_size_t(len(groups)), C.byref(nf)))
+        return [list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value
+
+    def r1cs_verify_mixed_screened_dev(self, gens, groups):
+        """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
+        arr, _, _ = self._groups(groups, True)
+        nf = C.c_size_t(0)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened_dev(self.ctx, gens, arr, C.c_size_t(len(groups)), C.byref(nf)))
+        return nf.value
 
     def set_shard(self, rank, world):
         """this context's share of ONE large proof split over the GPUs of a node (include/bpgpu.h bpgpu_set_shard)"""
