@@ -331,6 +331,59 @@ int bpgpu_r1cs_prover_session_polys(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu
  * once per circuit shape; a prover of the 2^14-shuffle no longer builds and uploads 65 533 constraint rows per proof. */
 int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *session, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                           const uint8_t *gadget_challenges, uint8_t *t_coeffs, uint8_t *wV);
+/* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
+ * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
+ * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step
+ * needs the party index or alpha: a public constant is added to c only; a public factor scales all three planes; two values add plane
+ * by plane; a product a b of two shared values uses a triple (x, y, z = x y): the parties open d = a - x and e = b - y, then the
+ * product's planes are z_k + d y_k + e x_k (k = share, MAC, modifier) plus d e on the modifier plane.  A point (an MSM over a plane)
+ * opens as the sum of the parties' share points plus the modifier point.  (A host whose library keeps public constants inside party
+ * 0's share maps onto this at the boundary: INTEGRATION.md.)
+ * Encodings: every share, MAC, modifier, triple, masked and opened value -- inputs and outputs -- is in ark-ff Montgomery form
+ * (x 2^256 mod n, 4 little-endian u64), which is additive, so a host adds the parties' masked planes without converting them;
+ * challenges y, z, x, u, w, the IPP's u and u^-1 and the gadget challenges are 32-byte canonical little endian, once per proof (the
+ * library broadcasts them to the planes); points are 64-byte x || y; wV is canonical little endian (public).
+ * Layouts, proof-major; "3" is the plane (share, MAC, modifier), len the length of the step's vectors:
+ *   operand vectors  nb x 3 x n_new                 blindings      nb x 3 x 3 (i, o, s blinding)
+ *   triples          nb x J x 3 (x, y, z) x 3 x len  masked         nb x J x 2 (d, e) x 3 x len     opened   nb x J x 2 (d, e) x len
+ *   where J = 6 products of the polynomial build (l1 r1, l2 r1, l3 r1, l1 r3, l2 r3, l3 r3; len = n) or 2 of an IPP round (c_L =
+ *   <a_L, b_R>, c_R = <a_R, b_L>; len = bpgpu_ipp_len / 2); an opened value is d (or e) summed over both parties' share planes plus
+ *   the modifier plane.
+ * Each call ends where the reference opens something over the network.  Shape errors (a missing pointer, s_L / s_R, gadget challenges
+ * given to a numeric circuit or missing for a parametric one, a call out of order, a context after bpgpu_set_shard) give BPGPU_E_ARG,
+ * a circuit whose multipliers are not the session's BPGPU_E_LEN, before anything is launched; a non-canonical limb in any input
+ * gives BPGPU_E_ARG as the single-party session calls do.  The single-party calls refuse these sessions (BPGPU_E_ARG):
+ * bpgpu_r1cs_prover_commit / _eval / _session_polys(_param) / _ipp_begin, bpgpu_ipp_round and bpgpu_ipp_run_fs.
+ *
+ * bpgpu_mpc_prover_commit -- mpc_prover.rs:621-657 (first call, *session == NULL) and :717-750 (second call: the n_new phase-2
+ *   multipliers): the authenticated bpgpu_r1cs_prover_commit.  s_L, s_R explicit (blinding vector keys have no place: the fabric
+ *   deals shared blindings).  commitments out: nb x 3 x 3 x 64 B (proof, plane, A_I A_O S).
+ * bpgpu_mpc_prover_polys_mask -- mpc_prover.rs:783-829 and the masking half of authenticated_poly.rs:143-164: y^-1, the flattened
+ *   constraints, l1 = a_L + y^-i wR, l2 = a_O, l3 = s_L, r0 = wO - y^i (public), r1 = y^i a_R + wL, r3 = y^i s_R per plane (public
+ *   terms on the modifier plane), and masked (nb x 6 x 2 x 3 x n) for the six shared x shared products from triples (nb x 6 x 3 x 3
+ *   x n: 6n triples per proof).  gadget_challenges: nb x nchi x 32 B for a circuit of bpgpu_circuit_create_param, else NULL.
+ * bpgpu_mpc_prover_polys_finish -- the combine half of special_inner_product and mpc_prover.rs:836-864: opened (nb x 6 x 2 x n) ->
+ *   t_coeffs out nb x 3 x 6 (proof, plane, t1..t6), the products with the public r0 computed locally; t_blindings nb x 3 x 5 (tb1,
+ *   tb3, tb4, tb5, tb6) -> T out nb x 3 x 5 x 64 B (T_1, T_3..T_6 per plane); wV out nb x m (canonical) for the host's t_2_blinding.
+ * bpgpu_mpc_prover_ipp_begin -- mpc_prover.rs:901-917 and the set-up of SharedInnerProductProof::create: l(x), r(x) per plane (the
+ *   -y^i padding on the modifier plane), G / H factors, Q = w B over the resident generators.  x, u, w: nb x 32 B.
+ * Per round while bpgpu_ipp_len(ipp) > 1 (mpc_inner_product.rs:52-228):
+ *   bpgpu_mpc_ipp_mask  -- triples nb x 2 x 3 x 3 x h -> masked nb x 2 x 2 x 3 x h for c_L, c_R   (h = bpgpu_ipp_len / 2)
+ *   bpgpu_mpc_ipp_round -- opened nb x 2 x 2 x h -> L, R: nb x 3 x 64 B each (c_L Q, c_R Q from the Beaver combine)
+ *   bpgpu_ipp_fold      -- u, u^-1: nb x 32 B (once per proof), applied to all planes
+ * then bpgpu_ipp_finish -> a, b: nb x 3 x 32 B each, ark-ff Montgomery form.  2 (padded_n - 1) triples per proof over all rounds. */
+int bpgpu_mpc_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new, const uint8_t *a_L,
+                            const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *blindings,
+                            uint8_t *commitments);
+int bpgpu_mpc_prover_polys_mask(bpgpu_ctx *ctx, bpgpu_prover *session, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
+                                const uint8_t *gadget_challenges, const uint8_t *triples, uint8_t *masked);
+int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *session, const uint8_t *opened, const uint8_t *t_blindings,
+                                  uint8_t *t_coeffs, uint8_t *T, uint8_t *wV);
+int bpgpu_mpc_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *session, const bpgpu_gens *g, size_t padded_n, size_t n1, const uint8_t *x,
+                               const uint8_t *u, const uint8_t *w, bpgpu_ipp **out);
+int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *ipp, const uint8_t *triples, uint8_t *masked);
+int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *ipp, const uint8_t *opened, uint8_t *L, uint8_t *R);
+
 /* out[i] = scalars[i] * (curve generator) -- GeneratorsChain::next (generators.rs:112-124),
  * Q = w * B (prover.rs:687), PedersenGens::commit with B = B_blinding (generators.rs:41-43,61-70) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out);

@@ -114,6 +114,9 @@ struct bpgpu_ipp {
   Words8 *cG = nullptr, *cH = nullptr, *w = nullptr;               //   coefficient vectors nb x n0 and Q = w * B
   size_t slo = 0, shi = (size_t)-1;                                // bpgpu_set_shard at session start: the generators whose terms this
   bool with_q = true;                                              //   rank's L, R carry (the c Q term belongs to rank 0)
+  int planes = 1;                                                  // 3: authenticated session of bpgpu_mpc_prover_ipp_begin (nb = 3 x proofs)
+  Words8 *trip = nullptr;                                          //   its round's Beaver triples (bpgpu_mpc_ipp_mask -> _round)
+  bool masked = false;
 };
 struct bpgpu_circuit {
   size_t q = 0, n = 0, m = 0, nnz = 0, nchi = 0;   // nchi: gadget challenges the coefficients are affine in (kernels.h CircuitDev)
@@ -2369,7 +2372,7 @@ int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const 
 // (ctx->mu held) the session's buffers go back to the context's pool
 static void ipp_free_all(bpgpu_ctx *ctx, bpgpu_ipp *s) {
   void *all[] = {s->a[0], s->a[1], s->b[0], s->b[1], s->G[0], s->G[1], s->H[0], s->H[1], s->Q, s->Gf, s->Hf, s->t1, s->t2, s->t3, s->t4,
-                 s->cLR, s->uu, s->res, s->sums, s->out_xy, s->mpts, s->msc, s->cG, s->cH, s->w};
+                 s->cLR, s->uu, s->res, s->sums, s->out_xy, s->mpts, s->msc, s->cG, s->cH, s->w, s->trip};
   for (void *p : all) pool_release(ctx, p);
   delete s;
 }
@@ -2510,13 +2513,16 @@ size_t bpgpu_ipp_len(const bpgpu_ipp *s) { return s ? s->n : 0; }
 
 /* c_L, c_R and the two MSMs of one round -- inner_product_proof.rs:87-114 (first) / :156-172.
  * Device part: out_xy[2p], out_xy[2p + 1] = L_p, R_p in boundary form (2 Words8 per point). */
-static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy) {
+// beaver: cLR already holds c_L, c_R (an authenticated session's Beaver combine, bpgpu_mpc_ipp_round)
+static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy, bool beaver = false) {
   hipStream_t st = ctx->st;
   const size_t nb = s->nb, n = s->n, h = n / 2, seg = 2 * h + 1;
   Words8 *a = s->a[s->cur], *b = s->b[s->cur];
   if (s->gens) {   // resident generators: two table-lookup MSMs over the original generators per proof
-    sc_dot_batched(st, nb, h, a, n, b + h, n, s->cLR, 2);        // c_L = <a_L, b_R>
-    sc_dot_batched(st, nb, h, a + h, n, b, n, s->cLR + 1, 2);    // c_R = <a_R, b_L>
+    if (!beaver) {
+      sc_dot_batched(st, nb, h, a, n, b + h, n, s->cLR, 2);        // c_L = <a_L, b_R>
+      sc_dot_batched(st, nb, h, a + h, n, b, n, s->cLR + 1, 2);    // c_R = <a_R, b_L>
+    }
     ipp_gens_scalars(st, nb, s->n0, n, a, b, s->cG, s->cH, s->cLR, s->w, s->msc, s->slo, s->shi, s->with_q);
     {
       size_t chunks = fixed_msm_ipp_chunks(s->gens->c, s->n0, nb * 2);
@@ -2576,7 +2582,7 @@ static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy) {
   return launch_ok(ctx);
 }
 int bpgpu_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *L, uint8_t *R) try {
-  if (!ctx || !s || !L || !R) return BPGPU_E_ARG;
+  if (!ctx || !s || !L || !R || s->planes != 1) return BPGPU_E_ARG;   // (shares: c_L, c_R need Beaver triples, bpgpu_mpc_ipp_round)
   if (s->n < 2) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -2639,7 +2645,13 @@ static int ipp_fold_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *du, Words8 *dui) {
   s->cur = nxt; s->n = h; s->first = false;
   return launch_ok(ctx);
 }
-int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t *u_inv) {
+// per-proof 32-byte values repeated for the three planes of each proof (authenticated sessions)
+static std::vector<uint8_t> bcast3(const uint8_t *src, size_t nproofs) {
+  std::vector<uint8_t> out(nproofs * 3 * 32);
+  for (size_t v = 0; v < 3 * nproofs; v++) memcpy(&out[32 * v], src + 32 * (v / 3), 32);
+  return out;
+}
+int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t *u_inv) try {
   if (!ctx || !s || !u || !u_inv) return BPGPU_E_ARG;
   if (s->n < 2) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2647,20 +2659,31 @@ int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t
   const size_t nb = s->nb;
   Words8 *du = s->uu, *dui = s->uu + nb;
   CK(flag_reset(ctx));
-  CK(h2d(ctx, du, u, nb * 32));
-  CK(h2d(ctx, dui, u_inv, nb * 32));
+  std::vector<uint8_t> b3;
+  if (s->planes != 1) {   // authenticated session: one challenge per proof, broadcast to its three planes
+    if (s->masked) return BPGPU_E_ARG;     // a masked round has not been completed by bpgpu_mpc_ipp_round
+    b3 = bcast3(u, nb / 3);
+    const std::vector<uint8_t> bi = bcast3(u_inv, nb / 3);
+    b3.insert(b3.end(), bi.begin(), bi.end());
+    CK(h2d(ctx, du, b3.data(), 2 * nb * 32));   // (du, dui adjacent; flag_read below waits for the copy)
+  } else {
+    CK(h2d(ctx, du, u, nb * 32));
+    CK(h2d(ctx, dui, u_inv, nb * 32));
+  }
   scalars_check(ctx->st, s->uu, 2 * nb, ctx->d_flag);
   int bad = 0;
   CK(flag_read(ctx, &bad));
   if (bad) return BPGPU_E_ARG;        // checked before the session state advances
   return ipp_fold_dev(ctx, s, du, dui);
+} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
+  return BPGPU_E_OOM;
 }
 /* InnerProductProof::create's whole round loop on the device (SURVEY 8f N1 applied to the prover): per round the
  * L, R MSMs, transcript.append_point("L"), ("R"), challenge_scalar("u") (inner_product_proof.rs:119-123,177-181)
  * with the keccak hash chain in a kernel, u^-1 and the fold -- no host round trip between rounds. */
 int bpgpu_ipp_run_fs(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *states_in, uint8_t *L_out, uint8_t *R_out,
                      uint8_t *a_out, uint8_t *b_out, uint8_t *states_out) try {
-  if (!ctx || !s || !states_in || !a_out || !b_out) return BPGPU_E_ARG;
+  if (!ctx || !s || !states_in || !a_out || !b_out || s->planes != 1) return BPGPU_E_ARG;
   if (s->shi != (size_t)-1) return BPGPU_E_ARG;    // a sharded session's L, R are partial sums: its rounds need the ranks' exchange
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -2733,6 +2756,18 @@ int bpgpu_ipp_finish(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *a_out, uint8_t *b_ou
   if (!ctx || !s || !a_out || !b_out) return BPGPU_E_ARG;
   if (s->n != 1) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  if (s->planes != 1) {   // authenticated planes leave in ark-ff Montgomery form, as every share of the two-party calls
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    Words8 *t = s->out_xy;   // nb x 2 points = 4 nb words: room for a and b
+    CK(flag_reset(ctx));
+    scalars_to_ark(ctx->st, s->a[s->cur], t, s->nb, ctx->d_flag);
+    scalars_to_ark(ctx->st, s->b[s->cur], t + s->nb, s->nb, ctx->d_flag);
+    CK(launch_ok(ctx));
+    CK(d2h(ctx, a_out, t, s->nb * 32));
+    CK(d2h(ctx, b_out, t + s->nb, s->nb * 32));
+    HIPCK(ctx, hipStreamSynchronize(ctx->st));
+    return BPGPU_OK;
+  }
   CK(d2h(ctx, a_out, s->a[s->cur], s->nb * 32));
   CK(d2h(ctx, b_out, s->b[s->cur], s->nb * 32));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
@@ -2752,9 +2787,14 @@ struct bpgpu_prover {
   size_t wn = 0;
   Words8 *aL = nullptr, *aR = nullptr, *aO = nullptr, *sL = nullptr, *sR = nullptr;
   Words8 *yinv = nullptr;     // nb (set by bpgpu_r1cs_prover_session_polys)
+  // authenticated sessions (bpgpu_mpc_prover_commit): nb above counts VIRTUAL provers, 3 per proof (share, MAC, modifier planes)
+  int planes = 1;
+  const bpgpu_gens *g = nullptr;        // the generators of the commitments (T points of bpgpu_mpc_prover_polys_finish)
+  Words8 *trip = nullptr, *wv = nullptr; // the polynomial build's Beaver triples (plain) and wV (proofs x m), mask -> finish
+  bool finished = false;
 };
 static void prover_free_all(bpgpu_ctx *ctx, bpgpu_prover *s) {   // ctx->mu held
-  void *all[] = {s->polys, s->y, s->aL, s->aR, s->aO, s->sL, s->sR, s->yinv};
+  void *all[] = {s->polys, s->y, s->aL, s->aR, s->aO, s->sL, s->sR, s->yinv, s->trip, s->wv};
   for (void *p : all) pool_release(ctx, p);
   delete s;
 }
@@ -2818,7 +2858,7 @@ int bpgpu_r1cs_prover_polys_ark(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t n
 }
 int bpgpu_r1cs_prover_eval(bpgpu_ctx *ctx, bpgpu_prover *s, size_t padded_n, const uint8_t *x, uint8_t *l_vec,
                            uint8_t *r_vec) {
-  if (!ctx || !s || !x || !l_vec || !r_vec) return BPGPU_E_ARG;
+  if (!ctx || !s || !x || !l_vec || !r_vec || s->planes != 1) return BPGPU_E_ARG;
   if (padded_n < s->n || (padded_n & (padded_n - 1))) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -2842,10 +2882,10 @@ int bpgpu_r1cs_prover_eval(bpgpu_ctx *ctx, bpgpu_prover *s, size_t padded_n, con
 }
 /* prover.rs:659-708 without leaving the device: l(x), r(x) with their padding, the G/H factors and the
  * resident-generator IPP session that consumes them */
-int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
-                                const uint8_t *x, const uint8_t *u, const uint8_t *y_inv, const uint8_t *w,
-                                bpgpu_ipp **out) {
-  if (!ctx || !ps || !g || !x || !u || (!y_inv && !ps->yinv) || !w || !out || !ps->polys) return BPGPU_E_ARG;
+// (x, u, w: one per virtual prover; an authenticated session (planes 3) evaluates with k_mpc_eval and takes its own y^-1)
+static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
+                                 const uint8_t *x, const uint8_t *u, const uint8_t *y_inv, const uint8_t *w,
+                                 bpgpu_ipp **out) {
   if (!padded_n || padded_n < ps->n || (padded_n & (padded_n - 1)) || n1 > ps->n) return BPGPU_E_LEN;
   if (padded_n > g->cap) return BPGPU_E_GENS;
   *out = nullptr;
@@ -2854,7 +2894,7 @@ int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_ge
   const size_t nb = ps->nb, n = padded_n;
   bpgpu_ipp *s = new (std::nothrow) bpgpu_ipp();
   if (!s) return BPGPU_E_OOM;
-  s->nb = nb; s->n0 = s->n = n; s->gens = g;
+  s->nb = nb; s->n0 = s->n = n; s->gens = g; s->planes = ps->planes;
   if (ctx->shard_world > 1) { shard_bounds(n, ctx->shard_rank, ctx->shard_world, &s->slo, &s->shi); s->with_q = ctx->shard_rank == 0; }
   size_t tot = nb * n, half = nb * (n > 1 ? n / 2 : 1);
   bool okk = true;
@@ -2864,6 +2904,7 @@ int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_ge
   M((void **)&s->cLR, nb * 2 * 32); M((void **)&s->uu, nb * 2 * 32);
   M((void **)&s->sums, nb * 2 * sizeof(JacRaw)); M((void **)&s->out_xy, nb * 2 * 64);
   M((void **)&s->msc, nb * 2 * (2 + 2 * n) * 32);
+  if (ps->planes != 1) M((void **)&s->trip, (nb / 3) * 2 * 9 * (n / 2 ? n / 2 : 1) * 32);   // the first round's triples, the largest
   if (!okk) { ipp_free_all(ctx, s); return BPGPU_E_OOM; }
   int rc = BPGPU_OK;
   do {
@@ -2877,7 +2918,8 @@ int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_ge
     ProfSpan span(ctx, 19, ctx->st);
     scalars_check(ctx->st, dx, 3 * nb, ctx->d_flag);
     scalars_check(ctx->st, s->w, nb, ctx->d_flag);
-    prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+    if (ps->planes != 1) mpc_eval(ctx->st, nb / 3, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+    else prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
     ipp_r1cs_factors(ctx->st, nb, n, n1, du, dyi, s->cG, s->cH);
     span.close();
     if ((rc = launch_ok(ctx))) break;
@@ -2889,6 +2931,12 @@ int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_ge
   *out = s;
   return BPGPU_OK;
 }
+int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
+                                const uint8_t *x, const uint8_t *u, const uint8_t *y_inv, const uint8_t *w,
+                                bpgpu_ipp **out) {
+  if (!ctx || !ps || !g || !x || !u || (!y_inv && !ps->yinv) || !w || !out || !ps->polys || ps->planes != 1) return BPGPU_E_ARG;
+  return prover_ipp_begin_impl(ctx, ps, g, padded_n, n1, x, u, y_inv, w, out);
+}
 void bpgpu_prover_destroy(bpgpu_ctx *ctx, bpgpu_prover *s) {
   if (!s || !ctx) return;        // (a session belongs to the context it was opened on)
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2898,10 +2946,12 @@ void bpgpu_prover_destroy(bpgpu_ctx *ctx, bpgpu_prover *s) {
 
 /* ---- resident-witness prover sessions: prover.rs:457-494 / :519-565 (phase commitments) and :587-619 (polynomials) with the
  * witness uploaded ONCE and the blinding vectors optionally drawn on the device ------------------------------------------ */
-int bpgpu_r1cs_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new,
-                             const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
-                             const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments) {
+// planes = 3: an authenticated session (bpgpu_mpc_prover_commit), nb = 3 x proofs virtual provers
+static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new,
+                              const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
+                              const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments, int planes) {
   if (!ctx || !g || !session || !nb || !blindings || !commitments) return BPGPU_E_ARG;
+  if (*session && (*session)->planes != planes) return BPGPU_E_ARG;   // no mixing of single-party and authenticated calls
   if (n_new && (!a_L || !a_R || !a_O)) return BPGPU_E_ARG;
   const bool explicit_vec = s_L && s_R;
   if (n_new && (explicit_vec == (vector_keys != nullptr) || (!s_L) != (!s_R))) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
@@ -2915,7 +2965,7 @@ int bpgpu_r1cs_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover *
   if (fresh) {
     s = new (std::nothrow) bpgpu_prover();
     if (!s) return BPGPU_E_OOM;
-    s->nb = nb;
+    s->nb = nb; s->planes = planes; s->g = g;
   }
   auto fail = [&](int rc) { if (fresh) prover_free_all(ctx, s); return rc; };
   // new planes of nb x wn; the multipliers of the earlier phase are carried over
@@ -2977,17 +3027,22 @@ int bpgpu_r1cs_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover *
   *session = s;
   return BPGPU_OK;
 }
+int bpgpu_r1cs_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new,
+                             const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
+                             const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments) {
+  return prover_commit_impl(ctx, g, session, nb, n_new, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, commitments, 1);
+}
 static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                        const uint8_t *chi, uint8_t *t_coeffs, uint8_t *wV);
 int bpgpu_r1cs_prover_session_polys(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                     uint8_t *t_coeffs, uint8_t *wV) {
-  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV)) return BPGPU_E_ARG;
+  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1) return BPGPU_E_ARG;
   if (c->nchi) return BPGPU_E_ARG;
   return prover_session_polys_locked(ctx, s, c, y, z, nullptr, t_coeffs, wV);
 }
 int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                           const uint8_t *gadget_challenges, uint8_t *t_coeffs, uint8_t *wV) {
-  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV)) return BPGPU_E_ARG;
+  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1) return BPGPU_E_ARG;
   if (!c->nchi || !gadget_challenges) return BPGPU_E_ARG;
   return prover_session_polys_locked(ctx, s, c, y, z, gadget_challenges, t_coeffs, wV);
 }
@@ -3067,6 +3122,167 @@ int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_
   CK(d2h(ctx, out, dout, n * 64));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
   return BPGPU_OK;
+}
+
+/* ---- two-party prover: one party's local arithmetic (src/r1cs_mpc/ of the reference; include/bpgpu.h, k_mpc.hip).  A session of nb
+ * proofs holds 3 nb virtual provers v = 3 p + k (k = 0 share, 1 MAC share, 2 public modifier): the linear steps are the single-party
+ * launches over them, the products of two shared values go through the host's Beaver triples. ---------------------------------- */
+int bpgpu_mpc_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new, const uint8_t *a_L,
+                            const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *blindings,
+                            uint8_t *commitments) {
+  if (!ctx || !g || !session || !nb || !blindings || !commitments) return BPGPU_E_ARG;
+  if (n_new && (!a_L || !a_R || !a_O || !s_L || !s_R)) return BPGPU_E_ARG;   // blinding vectors come shared from the fabric: explicit only
+  if (ctx->shard_world > 1) return BPGPU_E_ARG;
+  if (*session && ((*session)->planes != 3 || (*session)->polys)) return BPGPU_E_ARG;
+  if (*session && (*session)->nb != 3 * nb) return BPGPU_E_LEN;
+  return prover_commit_impl(ctx, g, session, 3 * nb, n_new, a_L, a_R, a_O, s_L, s_R, nullptr, blindings, commitments, 3);
+}
+int bpgpu_mpc_prover_polys_mask(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
+                                const uint8_t *gadget_challenges, const uint8_t *triples, uint8_t *masked) try {
+  if (!ctx || !s || !c || !y || !z || !triples || !masked || s->planes != 3) return BPGPU_E_ARG;
+  if ((c->nchi != 0) != (gadget_challenges != nullptr) || ctx->shard_world > 1) return BPGPU_E_ARG;
+  if (c->n != s->wn || s->polys) return BPGPU_E_LEN;     // the circuit's multipliers are the session's; one polynomial build per session
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t NB = s->nb, nb = NB / 3, n = c->n, m = c->m, ntrip = nb * 6 * 9 * n, nmask = nb * 6 * 6 * n;
+  bool okk = true;
+  for (auto pp : {std::make_pair((void **)&s->polys, 6 * NB * (n ? n : 1) * 9 * 4), std::make_pair((void **)&s->y, NB * 32),
+                  std::make_pair((void **)&s->yinv, NB * 32), std::make_pair((void **)&s->trip, ntrip * 32), std::make_pair((void **)&s->wv, nb * m * 32)})
+    okk = okk && pool_alloc(ctx, pp.first, pp.second);
+  auto fail = [&](int rc) {   // the session stays where it was: the call may be repeated
+    for (void **p : {(void **)&s->polys, (void **)&s->y, (void **)&s->yinv, (void **)&s->trip, (void **)&s->wv}) { pool_release(ctx, *p); *p = nullptr; }
+    return rc;
+  };
+  if (!okk) return fail(BPGPU_E_OOM);
+  void *dz, *dzp, *dm, *dchi = nullptr;
+  const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);
+  int rc;
+  if ((rc = ws_get(ctx, 0, nb * 32, &dz)) || (rc = ws_get(ctx, 6, nb * qz * 9 * 4, &dzp)) || (rc = ws_get(ctx, 23, nmask * 32, &dm)) ||
+      (c->nchi && (rc = ws_get(ctx, 21, nb * c->nchi * 32, &dchi))))
+    return fail(rc);
+  const std::vector<uint8_t> y3 = bcast3(y, nb);
+  if ((rc = flag_reset(ctx)) || (rc = h2d(ctx, s->y, y3.data(), NB * 32)) || (rc = h2d(ctx, dz, z, nb * 32)) ||
+      (rc = h2d(ctx, s->trip, triples, ntrip * 32)) || (c->nchi && (rc = h2d(ctx, dchi, gadget_challenges, nb * c->nchi * 32))))
+    return fail(rc);
+  scalars_check(ctx->st, s->y, NB, ctx->d_flag);
+  scalars_check(ctx->st, (const Words8 *)dz, nb, ctx->d_flag);
+  if (c->nchi) scalars_check(ctx->st, (const Words8 *)dchi, nb * c->nchi, ctx->d_flag);
+  scalars_from_ark(ctx->st, s->trip, s->trip, ntrip, ctx->d_flag);
+  ProfSpan span(ctx, 17, ctx->st);
+  if (hipMemcpyAsync(s->yinv, s->y, NB * 32, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
+  batch_inverse(ctx->st, s->yinv, NB, ctx->d_flag);        // y^-1 (a zero challenge raises the flag: E_ARG)
+  zpow_table(ctx->st, nb, c->q, (const Words8 *)dz, 8, (int32_t *)dzp, c->nchi, (const Words8 *)dchi);
+  mpc_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, (const int32_t *)dzp, s->polys, s->wv, s->trip,
+            (Words8 *)dm);
+  scalars_to_ark(ctx->st, (const Words8 *)dm, (Words8 *)dm, nmask, ctx->d_flag);
+  span.close();
+  if ((rc = launch_ok(ctx))) return fail(rc);
+  int bad = 0;
+  if ((rc = flag_read(ctx, &bad))) return fail(rc);
+  if (bad) return fail(BPGPU_E_ARG);
+  if ((rc = d2h(ctx, masked, dm, nmask * 32))) return fail(rc);
+  if (hipStreamSynchronize(ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
+  s->n = n; s->m = m;
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
+  return BPGPU_E_OOM;
+}
+int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *s, const uint8_t *opened, const uint8_t *t_blindings, uint8_t *t_coeffs,
+                                  uint8_t *T, uint8_t *wV) {
+  if (!ctx || !s || !opened || !t_blindings || !t_coeffs || !T || s->planes != 3) return BPGPU_E_ARG;
+  if (!s->polys || s->finished || (s->m && !wV)) return BPGPU_E_ARG;   // after bpgpu_mpc_prover_polys_mask, once
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t NB = s->nb, nb = NB / 3, n = s->n, nop = nb * 6 * 2 * n;
+  void *dop, *dsc, *dres, *dout;
+  CK(ws_get(ctx, 23, nop * 32, &dop));
+  CK(ws_get(ctx, 0, NB * (5 + 6 + 10) * 32, &dsc));
+  CK(ws_get(ctx, 4, NB * 5 * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, 5, NB * 5 * 64, &dout));
+  Words8 *dtb = (Words8 *)dsc, *dt = dtb + NB * 5, *rows = dt + NB * 6;
+  CK(flag_reset(ctx));
+  CK(h2d(ctx, dop, opened, nop * 32));
+  CK(h2d(ctx, dtb, t_blindings, NB * 5 * 32));
+  scalars_from_ark(ctx->st, (const Words8 *)dop, (Words8 *)dop, nop, ctx->d_flag);
+  scalars_from_ark(ctx->st, dtb, dtb, NB * 5, ctx->d_flag);
+  ProfSpan span(ctx, 17, ctx->st);
+  mpc_tcoeffs(ctx->st, nb, n, s->polys, (const Words8 *)dop, s->trip, dt);
+  mpc_t_rows(ctx->st, NB, dt, dtb, rows);
+  CK(msm_gens_dev(ctx, s->g, NB * 5, 0, (const uint32_t *)rows, (JacRaw *)dres, ctx->st));   // commit_shared, mpc_prover.rs:836-856
+  jac_to_boundary(ctx->st, (const JacRaw *)dres, (Words8 *)dout, NB * 5);
+  scalars_to_ark(ctx->st, dt, dt, NB * 6, ctx->d_flag);
+  span.close();
+  CK(launch_ok(ctx));
+  int bad = 0;
+  CK(flag_read(ctx, &bad));
+  if (bad) return BPGPU_E_ARG;
+  CK(d2h(ctx, t_coeffs, dt, NB * 6 * 32));
+  CK(d2h(ctx, T, dout, NB * 5 * 64));
+  if (s->m) CK(d2h(ctx, wV, s->wv, nb * s->m * 32));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  s->finished = true;
+  return BPGPU_OK;
+}
+int bpgpu_mpc_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1, const uint8_t *x,
+                               const uint8_t *u, const uint8_t *w, bpgpu_ipp **out) try {
+  if (!ctx || !ps || !g || !x || !u || !w || !out || ps->planes != 3 || !ps->finished || ctx->shard_world > 1) return BPGPU_E_ARG;
+  const size_t nb = ps->nb / 3;
+  const std::vector<uint8_t> x3 = bcast3(x, nb), u3 = bcast3(u, nb), w3 = bcast3(w, nb);
+  return prover_ipp_begin_impl(ctx, ps, g, padded_n, n1, x3.data(), u3.data(), nullptr, w3.data(), out);
+} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
+  return BPGPU_E_OOM;
+}
+int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *triples, uint8_t *masked) {
+  if (!ctx || !s || !triples || !masked || s->planes != 3) return BPGPU_E_ARG;
+  if (s->n < 2) return BPGPU_E_LEN;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t nb = s->nb / 3, h = s->n / 2, ntrip = nb * 2 * 9 * h, nmask = nb * 2 * 6 * h;
+  void *dm;
+  CK(ws_get(ctx, 23, nmask * 32, &dm));
+  CK(flag_reset(ctx));
+  CK(h2d(ctx, s->trip, triples, ntrip * 32));
+  ProfSpan span(ctx, 20, ctx->st);
+  scalars_from_ark(ctx->st, s->trip, s->trip, ntrip, ctx->d_flag);
+  mpc_ipp_mask(ctx->st, nb, h, s->a[s->cur], s->b[s->cur], s->trip, (Words8 *)dm);
+  scalars_to_ark(ctx->st, (const Words8 *)dm, (Words8 *)dm, nmask, ctx->d_flag);
+  span.close();
+  CK(launch_ok(ctx));
+  int bad = 0;
+  CK(flag_read(ctx, &bad));
+  if (bad) return BPGPU_E_ARG;
+  CK(d2h(ctx, masked, dm, nmask * 32));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  s->masked = true;
+  return BPGPU_OK;
+}
+int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *opened, uint8_t *L, uint8_t *R) try {
+  if (!ctx || !s || !opened || !L || !R || s->planes != 3 || !s->masked) return BPGPU_E_ARG;
+  if (s->n < 2) return BPGPU_E_LEN;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t NB = s->nb, nb = NB / 3, h = s->n / 2, nop = nb * 2 * 2 * h;
+  void *dop;
+  CK(ws_get(ctx, 23, nop * 32, &dop));
+  CK(flag_reset(ctx));
+  CK(h2d(ctx, dop, opened, nop * 32));
+  scalars_from_ark(ctx->st, (const Words8 *)dop, (Words8 *)dop, nop, ctx->d_flag);
+  int bad = 0;
+  CK(flag_read(ctx, &bad));
+  if (bad) return BPGPU_E_ARG;        // checked before the session state advances
+  {
+    ProfSpan span(ctx, 20, ctx->st);
+    mpc_ipp_combine(ctx->st, nb, h, (const Words8 *)dop, s->trip, s->cLR);   // c_L, c_R per plane: mpc_inner_product.rs:142-155
+    CK(ipp_round_dev(ctx, s, s->out_xy, true));
+  }
+  std::vector<uint8_t> tmp(NB * 128);
+  CK(d2h(ctx, tmp.data(), s->out_xy, NB * 128));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  for (size_t v = 0; v < NB; v++) { memcpy(L + 64 * v, &tmp[128 * v], 64); memcpy(R + 64 * v, &tmp[128 * v + 64], 64); }
+  s->masked = false;
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
+  return BPGPU_E_OOM;
 }
 
 #pragma GCC visibility pop

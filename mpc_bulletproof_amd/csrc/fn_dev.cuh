@@ -60,4 +60,20 @@ __device__ __forceinline__ Fn wave_sum(Fn x) {
   return x;
 }
 
+// one flattened constraint weight: output o of the column-major circuit against a proof's z-power table (flattened_constraints,
+// prover.rs:342-379; w_V and w_c carry the reference's minus sign)
+__device__ __forceinline__ Fn flatten_column(const CircuitDev &c, size_t o, const int32_t *zp) {
+  Fn acc = fe_zero<FN>();
+  uint32_t cnt = 0;
+  for (uint32_t t = c.col_ptr[o]; t < c.col_ptr[o + 1]; t++) {
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
+    acc = add(acc, mul(unpack<FN>(w), raw_get(zp + (size_t)c.row[t] * NL)));
+    if ((++cnt & 15) == 0) acc = fn_reduce(acc);
+  }
+  if (o >= 3 * c.n) acc = neg(acc);
+  return acc;
+}
+
 }  // namespace bpk

@@ -480,19 +480,6 @@ __global__ void __launch_bounds__(256) k_zpow(const Words8 *z, size_t z_stride, 
   raw_put(zpow + (b * qz + r) * NL, zr);
   for (size_t j = 0; j < nchi; j++) raw_put(zpow + (b * qz + (j + 1) * q + r) * NL, mul(zr, load_plain(&chi[b * nchi + j])));
 }
-__device__ __forceinline__ Fn flatten_column(const CircuitDev &c, size_t o, const int32_t *zp) {
-  Fn acc = fe_zero<FN>();
-  uint32_t cnt = 0;
-  for (uint32_t t = c.col_ptr[o]; t < c.col_ptr[o + 1]; t++) {
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
-    acc = add(acc, mul(unpack<FN>(w), raw_get(zp + (size_t)c.row[t] * NL)));
-    if ((++cnt & 15) == 0) acc = fn_reduce(acc);
-  }
-  if (o >= 3 * c.n) acc = neg(acc);
-  return acc;
-}
 __global__ void __launch_bounds__(256) k_flatten(CircuitDev c, const int32_t *zpow, Words8 *wL, Words8 *wR, Words8 *wO,
                                                  Words8 *wV, Words8 *wc) {
   size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -320,6 +320,23 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
 // wave-cooperative Keccak, u and u^-1
 void ipp_round_tail(hipStream_t st, size_t nb, const JacRaw *sums, uint64_t *states, Words8 *lr_xy, Words8 *u_out, Words8 *uinv_out, const JacRaw *partials = nullptr, size_t chunks = 0 /* > 1: sums[2p + s] = sum of partials[(2p + s) * chunks + i], added up here */);
 
+// ---- two-party prover, one party's local arithmetic (k_mpc.hip): 3 nb virtual provers v = 3 p + k (k = 0 share, 1 MAC, 2 public
+// modifier); triples [p][j][x, y, z][k][i], masked [p][j][d, e][k][i], opened [p][j][d, e][i] (plain canonical words)
+// polys [6][3 nb][n][9] as prover_polys (r0 holds the public value on every plane); y, y_inv: 3 nb; wV_out: nb x m; j < 6
+void mpc_polys(hipStream_t st, const CircuitDev &c, size_t nb, const Words8 *y, const Words8 *y_inv, const Words8 *a_L,
+               const Words8 *a_R, const Words8 *a_O, const Words8 *s_L, const Words8 *s_R, const int32_t *zpow, int32_t *polys,
+               Words8 *wV_out, const Words8 *trip, Words8 *masked);
+// t_out[3 nb][6]: t1..t6 per plane from the Beaver combine of the six products and the local products with r0
+void mpc_tcoeffs(hipStream_t st, size_t nb, size_t n, const int32_t *polys, const Words8 *opened, const Words8 *trip, Words8 *t_out);
+// rows[(5 v + j) * 2 ..]: [t, t_blinding] of T_1, T_3..T_6 over [B, B_blinding] (t: nvirt x 6, tb: nvirt x 5)
+void mpc_t_rows(hipStream_t st, size_t nvirt, const Words8 *t, const Words8 *tb, Words8 *rows);
+// l_vec, r_vec[3 nb][padded_n]: l(x), r(x) per plane, r0 and the -y^i padding on the modifier plane (x, y: 3 nb)
+void mpc_eval(hipStream_t st, size_t nb, size_t n, size_t padded_n, const Words8 *x, const Words8 *y, const int32_t *polys, Words8 *l_vec,
+              Words8 *r_vec);
+// IPP round: masked values of c_L = <a_L, b_R>, c_R = <a_R, b_L> (j = 0, 1; a, b: 3 nb x 2h), then their combine into cLR[2 v + j]
+void mpc_ipp_mask(hipStream_t st, size_t nb, size_t h, const Words8 *a, const Words8 *b, const Words8 *trip, Words8 *masked);
+void mpc_ipp_combine(hipStream_t st, size_t nb, size_t h, const Words8 *opened, const Words8 *trip, Words8 *cLR);
+
 // ---- wire codec of points (k_codec.hip): 32-byte compressed <-> 64-byte affine boundary form ------
 size_t sqrt_table_bytes();
 void sqrt_tables_build(hipStream_t st, void *tab /* sqrt_table_bytes() */);

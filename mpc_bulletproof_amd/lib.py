@@ -18,6 +18,8 @@ SYMBOLS = [
     "bpgpu_r1cs_verify_batch_wire", "bpgpu_r1cs_verify_batch_wire_dev", "bpgpu_r1cs_verify_batch_param", "bpgpu_r1cs_verify_batch_fs2",
     "bpgpu_r1cs_verify_batch_fs2_dev", "bpgpu_r1cs_verify_mixed_combined", "bpgpu_r1cs_verify_mixed_combined_dev",
     "bpgpu_r1cs_verify_mixed_screened", "bpgpu_r1cs_verify_mixed_screened_dev",
+    "bpgpu_mpc_prover_commit", "bpgpu_mpc_prover_polys_mask", "bpgpu_mpc_prover_polys_finish", "bpgpu_mpc_prover_ipp_begin",
+    "bpgpu_mpc_ipp_mask", "bpgpu_mpc_ipp_round",
 ]
 
 
@@ -471,6 +473,13 @@ class BpGpu:
                                                opt(a_O), opt(s_L), opt(s_R), opt(vector_keys), _buf(blindings), out))
         return h, bytes(out)[:64 * 3 * nb]
 
+    def r1cs_prover_ipp_begin(self, session, gens, padded_n, n1, x, u, y_inv, w):
+        """prover.rs:659-708 on the device: l(x), r(x), G / H factors and the resident-generator IPP session (y_inv None: the session's)"""
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_r1cs_prover_ipp_begin(self.ctx, session, gens, C.c_size_t(padded_n), C.c_size_t(n1), _buf(x), _buf(u),
+                                                  _buf(y_inv) if y_inv is not None else None, _buf(w), C.byref(h)))
+        return h
+
     def r1cs_prover_session_polys(self, session, circuit, nb, m, y, z):
         """prover.rs:587-619 on the session's planes -> (t_coeffs nb x 6 x 32 B, wV nb x m x 32 B); y, z canonical LE"""
         t, wv = _out(32 * 6 * nb), _out(32 * nb * max(m, 1))
@@ -479,6 +488,50 @@ class BpGpu:
 
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
+
+    # ---- two-party prover, one party's local work (include/bpgpu.h: three planes share | MAC | modifier per scalar, every share in
+    # ark-ff Montgomery form, challenges canonical LE once per proof)
+    def mpc_prover_commit(self, gens, session, nb, n_new, a_L, a_R, a_O, s_L, s_R, blindings):
+        """mpc_prover.rs:621-657 / :717-750 -> (session, A_I A_O S as nb x 3 planes x 3 x 64 B); operands nb x 3 x n_new, blindings nb x 3 x 3"""
+        h = session if session is not None else C.c_void_p()
+        out = _out(64 * 9 * nb)
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_mpc_prover_commit(self.ctx, gens, C.byref(h), C.c_size_t(nb), C.c_size_t(n_new), opt(a_L), opt(a_R), opt(a_O),
+                                              opt(s_L), opt(s_R), _buf(blindings), out))
+        return h, bytes(out)[:64 * 9 * nb]
+
+    def mpc_prover_polys_mask(self, session, circuit, nb, n, y, z, triples, gadget_challenges=None):
+        """mpc_prover.rs:783-829: triples nb x 6 x 3 x 3 x n -> masked d, e (nb x 6 x 2 x 3 x n)"""
+        out = _out(32 * nb * 36 * max(n, 1))
+        self._ck(_lib.bpgpu_mpc_prover_polys_mask(self.ctx, session, circuit, _buf(y), _buf(z),
+                                                  _buf(gadget_challenges) if gadget_challenges is not None else None, _buf(triples), out))
+        return bytes(out)[:32 * nb * 36 * n]
+
+    def mpc_prover_polys_finish(self, session, nb, m, opened, t_blindings):
+        """opened d, e (nb x 6 x 2 x n), t_blindings (nb x 3 x 5) -> (t_coeffs nb x 3 x 6, T nb x 3 x 5 x 64 B, wV nb x m canonical)"""
+        t, T, wv = _out(32 * 18 * nb), _out(64 * 15 * nb), _out(32 * nb * max(m, 1))
+        self._ck(_lib.bpgpu_mpc_prover_polys_finish(self.ctx, session, _buf(opened), _buf(t_blindings), t, T, wv))
+        return bytes(t)[:32 * 18 * nb], bytes(T)[:64 * 15 * nb], bytes(wv)[:32 * nb * m]
+
+    def mpc_prover_ipp_begin(self, session, gens, padded_n, n1, x, u, w):
+        """mpc_prover.rs:901-917 + the SharedInnerProductProof set-up -> IPP session of 3 planes per proof"""
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_mpc_prover_ipp_begin(self.ctx, session, gens, C.c_size_t(padded_n), C.c_size_t(n1), _buf(x), _buf(u), _buf(w),
+                                                 C.byref(h)))
+        return h
+
+    def mpc_ipp_mask(self, s, nb, triples):
+        """triples nb x 2 x 3 x 3 x h -> masked nb x 2 x 2 x 3 x h (c_L, c_R)"""
+        h = self.ipp_len(s) // 2
+        out = _out(32 * nb * 12 * max(h, 1))
+        self._ck(_lib.bpgpu_mpc_ipp_mask(self.ctx, s, _buf(triples), out))
+        return bytes(out)[:32 * nb * 12 * h]
+
+    def mpc_ipp_round(self, s, nb, opened):
+        """opened nb x 2 x 2 x h -> (L, R) nb x 3 planes x 64 B each"""
+        L, R = _out(64 * 3 * nb), _out(64 * 3 * nb)
+        self._ck(_lib.bpgpu_mpc_ipp_round(self.ctx, s, _buf(opened), L, R))
+        return bytes(L)[:192 * nb], bytes(R)[:192 * nb]
 
     def r1cs_verify_batch(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, want_mega=True,
                           want_scalars=False):
