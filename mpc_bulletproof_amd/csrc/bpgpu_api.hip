@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -19,6 +20,39 @@ namespace {
 
 struct Slot { void *p = nullptr; size_t cap = 0; };
 
+// Workspace slots (bpgpu_ctx::ws), one grow-only device buffer each.  ws_get may free and reallocate a slot, so no function ws_gets
+// a slot that one of its callers still holds.
+enum WsSlot : int {
+  // an entry point's operands, results and small scratch (host staging, a lane's batch); the cores below an entry point take the
+  // ones it leaves free (msm_batch_dev_locked: 2-4 under msm_batch_locked's 0, 1, 5; verify_wire_locked: 0-2 under the host form's 3-5)
+  WS_ARG0, WS_ARG1, WS_ARG2, WS_ARG3, WS_ARG4, WS_ARG5,
+  WS_ZPOW,          // z-power tables: flatten, prover polynomials, the verifier's scalar assembly
+  WS_VPTS,          // verifier: converted proof points
+  WS_VFIX,          // verifier: generator-half scalars; bpgpu_msm_shared: point replicas
+  WS_VVAR,          // verifier: proof-point scalars
+  WS_VVRES,         // verifier: proof-point sums; combined check: weighted generator column sums
+  WS_VFRES,         // verifier: generator-half sums; combined check: the two halves
+  WS_MSM,           // window-parallel scratch, fixed-base chunk partials (msm_gens_dev), second Straus scratch, msm_core_locked's terms
+  WS_STRAUS,        // Straus tables (straus_ws)
+  WS_PIP,           // bucket-method and combined-check pipelines (k_pip.hip, k_pip2.hip, k_mixed.hip)
+  WS_VAUX,          // wire format / decode bits (verify_wire_locked); combined check: final sum
+  WS_FS_STAGE,      // transcript host forms: challenges out, wire verdicts; bpgpu_ipp_run_fs: transcript states
+  WS_FS_CH,         // device transcript: challenges; bpgpu_ipp_run_fs: L, R
+  WS_PROOF_BAD,     // per-proof rejects: transcript identity points, non-canonical gadget challenges; bpgpu_ipp_run_fs: zero flag
+  WS_SCHED,         // device transcript schedule (bpgpu_ctx::sched_key)
+  WS_VBITS,         // verifier: per-proof malformed scalar | point bits (bpgpu_r1cs_verify_shard gets the same buffer before it calls in)
+  WS_CHI,           // gadget challenges: uploaded, or derived by the device transcript
+  WS_CHI_OUT,       // bpgpu_r1cs_verify_batch_fs(2): gadget challenges out
+  WS_MSM2,          // fixed-base chunk partials under a caller that holds WS_MSM (verifier); two-party masked and opened values
+  WS_WP_PTS,        // msm_wp_batch: padded points
+  WS_WP_SC,         // msm_wp_batch: padded scalars
+  WS_SCREEN_PART,   // screened calls: one partial point per check; mixed combined call: the checks' partials
+  WS_SCREEN_FLAG,   // screened calls: one input flag per check; mixed combined call: the partials' sum flag
+  WS_WP_RED,        // msm_wp_batch: scratch of the reduced instances
+  WS_MIXED_STAGE,   // mixed host forms: every group's operands
+  WS_COUNT
+};
+
 }  // namespace
 
 struct bpgpu_ctx {
@@ -30,7 +64,7 @@ struct bpgpu_ctx {
   int *d_flag = nullptr;          // device int: bad-input flag
   void *sqrt_tab = nullptr;       // F_p square-root tables of the point codec (built on first use)
   struct bpgpu_gens *gen_tab = nullptr;   // 16-bit-window table of the curve generator (bpgpu_generator_mul)
-  Slot ws[30];                    // grow-only workspace slots
+  Slot ws[WS_COUNT];              // grow-only workspace slots
   // optional per-kernel HIP-event timing (bench.py roofline): kind -> list of (start, stop)
   bool prof = false;
   bool latency_mode = false;      // bpgpu_set_latency_mode
@@ -51,9 +85,9 @@ struct bpgpu_ctx {
   // of one call over; created on first use, owned by the parent
   std::vector<bpgpu_ctx *> lanes;
   hipEvent_t lane_ev = nullptr;   // fork / join marker of a stream call
-  void *pinned = nullptr;         // page-locked staging for the verdicts of a host-memory stream call (grow-only)
+  void *pinned = nullptr;         // page-locked staging for the verdicts of a host-memory stream or screened call (pinned_verdicts)
   size_t pinned_cap = 0;
-  // device-transcript schedule cache (m, k, padded_n) -> steps already resident in ws slot 15
+  // device-transcript schedule cache (m, k, padded_n) -> steps already resident in WS_SCHED
   size_t sched_key[3] = {(size_t)-1, (size_t)-1, (size_t)-1};
   int sched_len = 0;
 };
@@ -175,7 +209,7 @@ static void pool_release(bpgpu_ctx *ctx, void *p) {
     ctx->pool.erase(ctx->pool.begin() + (long)largest);
   }
 }
-static int ws_get(bpgpu_ctx *ctx, int slot, size_t bytes, void **out) {
+static int ws_get(bpgpu_ctx *ctx, WsSlot slot, size_t bytes, void **out) {
   Slot &s = ctx->ws[slot];
   if (bytes < 256) bytes = 256;
   if (s.cap < bytes) {
@@ -188,7 +222,7 @@ static int ws_get(bpgpu_ctx *ctx, int slot, size_t bytes, void **out) {
   return BPGPU_OK;
 }
 // scratch for the per-lane Straus tables; launches on ctx->st are in order, so they share it
-static int straus_ws(bpgpu_ctx *ctx, int np, size_t n, void **out) { return ws_get(ctx, 13, straus_scratch_bytes(np, n), out); }
+static int straus_ws(bpgpu_ctx *ctx, int np, size_t n, void **out) { return ws_get(ctx, WS_STRAUS, straus_scratch_bytes(np, n), out); }
 static int flag_reset(bpgpu_ctx *ctx) { HIPCK(ctx, hipMemsetAsync(ctx->d_flag, 0, sizeof(int), ctx->st)); return BPGPU_OK; }
 static int flag_read(bpgpu_ctx *ctx, int *v) {
   HIPCK(ctx, hipMemcpyAsync(v, ctx->d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->st));
@@ -204,6 +238,18 @@ static int d2h(bpgpu_ctx *ctx, void *h, const void *d, size_t n) {
   return BPGPU_OK;
 }
 static int launch_ok(bpgpu_ctx *ctx) { HIPCK(ctx, hipGetLastError()); return BPGPU_OK; }
+// the end of an entry point whose launches validate into ctx->d_flag: the launch check, the flag (a host-side wait), BPGPU_E_ARG
+// before anything is downloaded when it is raised, then the downloads and the wait for them
+struct D2H { void *host; const void *dev; size_t bytes; };
+static int checked_download(bpgpu_ctx *ctx, std::initializer_list<D2H> outs) {
+  CK(launch_ok(ctx));
+  int bad = 0;
+  CK(flag_read(ctx, &bad));
+  if (bad) return BPGPU_E_ARG;
+  for (const D2H &o : outs) CK(d2h(ctx, o.host, o.dev, o.bytes));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+}
 // One launch that brings a batch's three operand arrays from page-locked host memory into the lane's buffers: wide, coalesced reads
 // over the bus by 256 waves (no DMA command, no cross-engine dependency), so that the chain's latency-bound kernels -- the table
 // lanes, the scalar assembly -- read HBM, not the bus.  Sizes in 16-byte words.
@@ -250,7 +296,7 @@ __global__ void k_coeff_ark_to_mont(Words8 *io, size_t n, int *bad) {
   for (int j = 0; j < 8; j++) io[i].w[j] = w[j];
 }
 static int msm_gens_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, const uint32_t *dsc, JacRaw *dres,
-                        hipStream_t st, int part_slot = 12, int lpm = 0, int kinds = 0) {
+                        hipStream_t st, WsSlot part_slot = WS_MSM, int lpm = 0, int kinds = 0) {
   size_t chunks = fixed_msm_chunks(g->c, n, nb, kinds);
   void *dpart = nullptr;
   if (chunks > 1) CK(ws_get(ctx, part_slot, nb * chunks * sizeof(JacRaw), &dpart));
@@ -562,41 +608,29 @@ int bpgpu_batch_inverse(bpgpu_ctx *ctx, uint8_t *scalars, size_t n) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *d;
-  CK(ws_get(ctx, 0, n * 32, &d));
+  CK(ws_get(ctx, WS_ARG0, n * 32, &d));
   CK(flag_reset(ctx));
   CK(h2d(ctx, d, scalars, n * 32));
   scalars_check(ctx->st, (Words8 *)d, n, ctx->d_flag);
   batch_inverse(ctx->st, (Words8 *)d, n, ctx->d_flag);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, scalars, d, n * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{scalars, d, n * 32}});
 }
 int bpgpu_inner_product(bpgpu_ctx *ctx, const uint8_t *a, const uint8_t *b, size_t n, uint8_t out[32]) {
   if (!ctx || !out || (n && (!a || !b))) return BPGPU_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *da, *db, *dout, *scr;
-  CK(ws_get(ctx, 0, n * 32, &da));
-  CK(ws_get(ctx, 1, n * 32, &db));
-  CK(ws_get(ctx, 2, 32, &dout));
-  CK(ws_get(ctx, 3, inner_product_scratch_bytes(n), &scr));
+  CK(ws_get(ctx, WS_ARG0, n * 32, &da));
+  CK(ws_get(ctx, WS_ARG1, n * 32, &db));
+  CK(ws_get(ctx, WS_ARG2, 32, &dout));
+  CK(ws_get(ctx, WS_ARG3, inner_product_scratch_bytes(n), &scr));
   CK(flag_reset(ctx));
   CK(h2d(ctx, da, a, n * 32));
   CK(h2d(ctx, db, b, n * 32));
   scalars_check(ctx->st, (Words8 *)da, n, ctx->d_flag);
   scalars_check(ctx->st, (Words8 *)db, n, ctx->d_flag);
   inner_product(ctx->st, (Words8 *)da, (Words8 *)db, n, (Words8 *)dout, scr);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, 32}});
 }
 
 // MSMs of up to 2^15 terms as a batch of independent <= 32-point sums through the window-parallel launches of the verifier
@@ -627,8 +661,8 @@ static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, co
   const void *sc = dsc, *pts = points;
   if (np != n) {   // ragged tails: identity points with zero scalars -- 64 zero bytes are the identity in either form
     void *dp, *ds;
-    CK(ws_get(ctx, 24, nb * np * 64, &dp));     // (slots of their own: the verifier calls this with its slot-7 / slot-9 buffers as operands)
-    CK(ws_get(ctx, 25, nb * np * 32, &ds));
+    CK(ws_get(ctx, WS_WP_PTS, nb * np * 64, &dp));
+    CK(ws_get(ctx, WS_WP_SC, nb * np * 32, &ds));
     HIPCK(ctx, hipMemsetAsync(dp, 0, nb * np * 64, ctx->st));
     HIPCK(ctx, hipMemsetAsync(ds, 0, nb * np * 32, ctx->st));
     HIPCK(ctx, hipMemcpy2DAsync(dp, np * 64, points, n * 64, n * 64, nb, hipMemcpyDeviceToDevice, ctx->st));
@@ -636,7 +670,7 @@ static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, co
     pts = dp; sc = ds;
   }
   void *dwp;
-  CK(ws_get(ctx, 12, verify_wp_scratch_bytes(ng, G), &dwp));
+  CK(ws_get(ctx, WS_MSM, verify_wp_scratch_bytes(ng, G), &dwp));
   VerifyWp v{(const AffDev *)pts, ng, G, dwp, bad ? bad : ctx->d_flag, nullptr, true, converted};
   wp_options(ctx, v);
   if (!verify_wp_layout_fits(v)) { ctx->err = "internal: window-parallel scratch layout exceeds its buffer (msm)"; return BPGPU_E_DEVICE; }
@@ -650,7 +684,7 @@ static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, co
   } else {
     // the instances' window sums are added up first: ONE pair of Horner stages per MSM (not per instance, with a sum of `per` points behind it)
     void *dwp2;
-    CK(ws_get(ctx, 28, verify_wp_scratch_bytes(nb, G), &dwp2));
+    CK(ws_get(ctx, WS_WP_RED, verify_wp_scratch_bytes(nb, G), &dwp2));
     VerifyWp v2 = v;
     v2.nb = nb;
     v2.scratch = dwp2;
@@ -668,9 +702,9 @@ static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, co
 static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, const void *dxy, void *dout) {
   size_t tot = nb * n;
   void *dpts, *dres, *dsum;
-  CK(ws_get(ctx, 2, tot * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, 3, tot * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 4, nb * sizeof(JacRaw), &dsum));
+  CK(ws_get(ctx, WS_ARG2, tot * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_ARG3, tot * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG4, nb * sizeof(JacRaw), &dsum));
   const size_t pip_min = (size_t)ctx->opt[BPGPU_OPT_PIPPENGER_MIN];
   if (n >= pip_min) {
     // 32-bit bucket ids, sorted entries (term index | sign bit) and offsets: reject what they cannot address
@@ -692,7 +726,7 @@ static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void 
   if (pip2_single && nb == 1 && n >= pip_min && pippenger2_supported(n)) {   // one mid-size instance: seven launches (k_pip2.hip)
     const int c2 = pippenger2_window(n);
     void *dpip;
-    CK(ws_get(ctx, 14, pippenger2_scratch_bytes(n, c2), &dpip));
+    CK(ws_get(ctx, WS_PIP, pippenger2_scratch_bytes(n, c2), &dpip));
     pippenger2_boundary(ctx->st, (const Words8 *)dxy, (const Words8 *)dsc, n, c2, (Words8 *)dout, (AffDev *)dpts, dpip, ctx->d_flag);
     return launch_ok(ctx);
   }
@@ -702,10 +736,10 @@ static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void 
     int c = pippenger_window(n);
     void *dpip;
     if (nb == 1) {
-      CK(ws_get(ctx, 14, pippenger_scratch_bytes(n, c), &dpip));
+      CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes(n, c), &dpip));
       pippenger(ctx->st, (AffDev *)dpts, (const uint32_t *)dsc, n, c, (JacRaw *)dsum, dpip);
     } else {
-      CK(ws_get(ctx, 14, pippenger_scratch_bytes_batch(nb, n, c), &dpip));
+      CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nb, n, c), &dpip));
       pippenger_batch(ctx->st, (AffDev *)dpts, (const uint32_t *)dsc, nb, n, c, (JacRaw *)dsum, 1, dpip);
     }
   } else {
@@ -727,9 +761,9 @@ static int msm_batch_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *
   if (!nb) return BPGPU_OK;
   if (!n) { memset(out, 0, nb * 64); return BPGPU_OK; }
   void *dsc, *dxy, *dout;
-  CK(ws_get(ctx, 0, tot * 32, &dsc));
-  CK(ws_get(ctx, 1, tot * 64, &dxy));
-  CK(ws_get(ctx, 5, nb * 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, tot * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG1, tot * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG5, nb * 64, &dout));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dsc, scalars, tot * 32));
   CK(h2d(ctx, dxy, points, tot * 64));
@@ -774,18 +808,18 @@ static int msm_core_locked(bpgpu_ctx *ctx, size_t n, const uint32_t *dsc, const 
   const bool pip2_single = ctx->opt[BPGPU_OPT_MSM_PIP2_SINGLE] != 0;
   if (pip2_single && n >= pip_min && pippenger2_supported(n)) {
     const int c2 = pippenger2_window(n);
-    CK(ws_get(ctx, 14, pippenger2_scratch_bytes(n, c2), &dpip));
+    CK(ws_get(ctx, WS_PIP, pippenger2_scratch_bytes(n, c2), &dpip));
     pippenger2(ctx->st, dpts, dsc, n, c2, dsum, dpip, ctx->d_flag);
   } else if (n >= pip_min) {
     const int c = pippenger_window(n);
     const size_t cW = 252 / (size_t)c + 1;
     if (n >= ((size_t)1 << 31) || cW * ((size_t)1 << (c - 1)) >= ((size_t)1 << 31) || n * cW >= ((size_t)1 << 32)) return BPGPU_E_LEN;
-    CK(ws_get(ctx, 14, pippenger_scratch_bytes(n, c), &dpip));
+    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes(n, c), &dpip));
     pippenger(ctx->st, dpts, dsc, n, c, dsum, dpip);
   } else {
     void *dres, *dstr;
-    CK(ws_get(ctx, 13, straus_scratch_bytes(1, n), &dstr));
-    CK(ws_get(ctx, 12, n * sizeof(JacRaw), &dres));
+    CK(ws_get(ctx, WS_STRAUS, straus_scratch_bytes(1, n), &dstr));
+    CK(ws_get(ctx, WS_MSM, n * sizeof(JacRaw), &dres));
     StrausArgs sa{};
     sa.pts[0] = dpts; sa.pt_stride[0] = 1;
     sa.sc[0] = dsc; sa.sc_stride[0] = 8;
@@ -799,12 +833,12 @@ int bpgpu_msm_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, const uint8_t *po
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *dsc, *dpj, *daff, *djac, *dsum, *dout;
-  CK(ws_get(ctx, 0, (n ? n : 1) * 32, &dsc));
-  CK(ws_get(ctx, 1, (n ? n : 1) * 96, &dpj));
-  CK(ws_get(ctx, 2, (n ? n : 1) * sizeof(AffDev), &daff));
-  CK(ws_get(ctx, 3, (n ? n : 1) * sizeof(JacRaw), &djac));
-  CK(ws_get(ctx, 4, sizeof(JacRaw), &dsum));
-  CK(ws_get(ctx, 5, 96, &dout));
+  CK(ws_get(ctx, WS_ARG0, (n ? n : 1) * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG1, (n ? n : 1) * 96, &dpj));
+  CK(ws_get(ctx, WS_ARG2, (n ? n : 1) * sizeof(AffDev), &daff));
+  CK(ws_get(ctx, WS_ARG3, (n ? n : 1) * sizeof(JacRaw), &djac));
+  CK(ws_get(ctx, WS_ARG4, sizeof(JacRaw), &dsum));
+  CK(ws_get(ctx, WS_ARG5, 96, &dout));
   CK(flag_reset(ctx));
   if (n) {
     CK(h2d(ctx, dsc, scalars_mont, n * 32));
@@ -817,23 +851,17 @@ int bpgpu_msm_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, const uint8_t *po
     HIPCK(ctx, hipMemsetAsync(dsum, 0, sizeof(JacRaw), ctx->st));                                  // Z = 0: the identity
   }
   points_to_ark(ctx->st, (const JacRaw *)dsum, (Words8 *)dout, 1);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out_jac_mont, dout, 96));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out_jac_mont, dout, 96}});
 }
 static int ark_convert_locked(bpgpu_ctx *ctx, int what, const uint8_t *in, size_t n, uint8_t *out) {
   static const size_t in_sz[4] = {32, 32, 96, 64}, out_sz[4] = {32, 32, 64, 96};
   if (!n) return BPGPU_OK;
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *din, *dout, *djac, *daff;
-  CK(ws_get(ctx, 0, n * in_sz[what], &din));
-  CK(ws_get(ctx, 1, n * out_sz[what], &dout));
-  CK(ws_get(ctx, 3, n * sizeof(JacRaw), &djac));
-  CK(ws_get(ctx, 2, n * sizeof(AffDev), &daff));
+  CK(ws_get(ctx, WS_ARG0, n * in_sz[what], &din));
+  CK(ws_get(ctx, WS_ARG1, n * out_sz[what], &dout));
+  CK(ws_get(ctx, WS_ARG3, n * sizeof(JacRaw), &djac));
+  CK(ws_get(ctx, WS_ARG2, n * sizeof(AffDev), &daff));
   CK(flag_reset(ctx));
   CK(h2d(ctx, din, in, n * in_sz[what]));
   switch (what) {
@@ -849,13 +877,7 @@ static int ark_convert_locked(bpgpu_ctx *ctx, int what, const uint8_t *in, size_
       points_to_ark(ctx->st, (const JacRaw *)djac, (Words8 *)dout, n);
       break;
   }
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, n * out_sz[what]));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, n * out_sz[what]}});
 }
 int bpgpu_scalars_from_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, size_t n, uint8_t *scalars_le) {
   if (!ctx || (n && (!scalars_mont || !scalars_le))) return BPGPU_E_ARG;
@@ -883,18 +905,12 @@ int bpgpu_points_sum(bpgpu_ctx *ctx, const uint8_t *points, size_t n, uint8_t ou
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *dxy, *dout;
-  CK(ws_get(ctx, 0, n * 64, &dxy));
-  CK(ws_get(ctx, 4, 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, n * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG4, 64, &dout));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dxy, points, n * 64));
   points_sum(ctx->st, (const Words8 *)dxy, n, (Words8 *)dout, ctx->d_flag);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, 64}});
 }
 int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scalars, const uint8_t *points,
                      uint8_t *out) {
@@ -905,14 +921,14 @@ int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scal
   if (!n) { memset(out, 0, nsets * 64); return BPGPU_OK; }
   const size_t tot = nsets * n;
   void *dsc, *dxy, *dpts, *dres, *dsum, *dout;
-  CK(ws_get(ctx, 0, tot * 32, &dsc));
-  CK(ws_get(ctx, 1, n * 64, &dxy));
-  CK(ws_get(ctx, 3, tot * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 4, nsets * sizeof(JacRaw), &dsum));
-  CK(ws_get(ctx, 5, nsets * 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, tot * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG1, n * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG3, tot * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG4, nsets * sizeof(JacRaw), &dsum));
+  CK(ws_get(ctx, WS_ARG5, nsets * 64, &dout));
   const size_t pip_min = (size_t)ctx->opt[BPGPU_OPT_PIPPENGER_MIN];
   const bool bucket = n >= pip_min;
-  CK(ws_get(ctx, 2, (bucket ? tot + n : n) * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_ARG2, (bucket ? tot + n : n) * sizeof(AffDev), &dpts));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dsc, scalars, tot * 32));
   CK(h2d(ctx, dxy, points, n * 64));
@@ -921,7 +937,7 @@ int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scal
   bool wp_done = false;
   if (!bucket || n <= ((size_t)1 << 15)) {   // window-parallel launches over replicas of the converted points (msm_wp_batch)
     void *drep;
-    CK(ws_get(ctx, 8, tot * sizeof(AffDev), &drep));
+    CK(ws_get(ctx, WS_VFIX, tot * sizeof(AffDev), &drep));
     gather_points(ctx->st, (AffDev *)dpts, 0, n, nsets, (AffDev *)drep, n);
     CK(msm_wp_batch(ctx, nsets, n, dsc, drep, true, (JacRaw *)dsum, &wp_done));
   }
@@ -931,7 +947,7 @@ int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scal
     gather_points(ctx->st, (AffDev *)dpts, 0, n, nsets, rep, n);
     int c = pippenger_window(n);
     void *dpip;
-    CK(ws_get(ctx, 14, pippenger_scratch_bytes_batch(nsets, n, c), &dpip));
+    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nsets, n, c), &dpip));
     pippenger_batch(ctx->st, rep, (const uint32_t *)dsc, nsets, n, c, (JacRaw *)dsum, 1, dpip);
   } else {        // one Straus lane per (set, term), the sets share the point array
     StrausArgs a{};
@@ -944,13 +960,7 @@ int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scal
     segmented_sum(ctx->st, (JacRaw *)dres, (JacRaw *)dsum, nsets, n);
   }
   jac_to_boundary(ctx->st, (JacRaw *)dsum, (Words8 *)dout, nsets);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, nsets * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, nsets * 64}});
 }
 
 /* ---------------------------------------------------------------- point wire codec */
@@ -966,9 +976,9 @@ int bpgpu_points_decompress(bpgpu_ctx *ctx, const uint8_t *compressed, size_t n,
     ctx->sqrt_tab = t;
   }
   void *din, *dxy, *dok;
-  CK(ws_get(ctx, 0, n * 32, &din));
-  CK(ws_get(ctx, 1, n * 64, &dxy));
-  CK(ws_get(ctx, 5, n * 4, &dok));
+  CK(ws_get(ctx, WS_ARG0, n * 32, &din));
+  CK(ws_get(ctx, WS_ARG1, n * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG5, n * 4, &dok));
   CK(h2d(ctx, din, compressed, n * 32));
   points_decompress(ctx->st, (const Words8 *)din, (Words8 *)dxy, (int32_t *)dok, n, ctx->sqrt_tab);
   CK(launch_ok(ctx));
@@ -983,20 +993,14 @@ int bpgpu_points_compress(bpgpu_ctx *ctx, const uint8_t *xy, size_t n, uint8_t *
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *dxy, *dpts, *dout;
-  CK(ws_get(ctx, 1, n * 64, &dxy));
-  CK(ws_get(ctx, 2, n * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, 0, n * 32, &dout));
+  CK(ws_get(ctx, WS_ARG1, n * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG2, n * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_ARG0, n * 32, &dout));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dxy, xy, n * 64));
   points_from_boundary(ctx->st, (const Words8 *)dxy, (AffDev *)dpts, n, ctx->d_flag);   // canonical + on-curve checks
   points_compress(ctx->st, (const Words8 *)dxy, (Words8 *)dout, n);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, compressed, dout, n * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{compressed, dout, n * 32}});
 }
 
 /* ---------------------------------------------------------------- resident generators */
@@ -1077,9 +1081,9 @@ static int msm_gens_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t 
   HIPCK(ctx, hipSetDevice(ctx->device));
   size_t per = 2 + 2 * n, tot = nb * per;
   void *dsc, *dres, *dout;
-  CK(ws_get(ctx, 0, tot * 32, &dsc));
-  CK(ws_get(ctx, 4, nb * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 5, nb * 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, tot * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG4, nb * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG5, nb * 64, &dout));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dsc, scalars, tot * 32));
   ProfSpan span(ctx, 18, ctx->st);
@@ -1088,13 +1092,7 @@ static int msm_gens_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t 
   CK(msm_gens_dev(ctx, g, nb, n, (uint32_t *)dsc, (JacRaw *)dres, ctx->st));
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, nb);
   span.close();
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, nb * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, nb * 64}});
 }
 int bpgpu_msm_gens(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, const uint8_t *scalars, uint8_t *out) {
   return msm_gens_impl(ctx, g, nb, n, scalars, out, false);
@@ -1111,14 +1109,14 @@ int bpgpu_fold_witness(bpgpu_ctx *ctx, size_t n, const uint8_t u[32], const uint
   if (!n) return BPGPU_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  // slot 0: scalars u, u_inv, a[2n], b[2n], a_out[n], b_out[n]
+  // scalars: u, u_inv, a[2n], b[2n], a_out[n], b_out[n]
   void *dsc, *dxy, *dpts, *dres, *dout;
   size_t nsc = 2 + 4 * n + 2 * n;
-  CK(ws_get(ctx, 0, nsc * 32, &dsc));
-  CK(ws_get(ctx, 1, 4 * n * 64, &dxy));
-  CK(ws_get(ctx, 2, 4 * n * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, 3, 2 * n * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 5, 2 * n * 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, nsc * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG1, 4 * n * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG2, 4 * n * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_ARG3, 2 * n * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG5, 2 * n * 64, &dout));
   Words8 *w = (Words8 *)dsc;
   Words8 *du = w, *dui = w + 1, *da = w + 2, *db = w + 2 + 2 * n, *dao = w + 2 + 4 * n, *dbo = w + 2 + 5 * n;
   CK(flag_reset(ctx));
@@ -1143,16 +1141,7 @@ int bpgpu_fold_witness(bpgpu_ctx *ctx, size_t n, const uint8_t u[32], const uint
   sh.sc[0] = (uint32_t *)du; sh.sc[1] = (uint32_t *)dui; sh.sc_stride[0] = sh.sc_stride[1] = 0;
   straus(ctx->st, 2, sh, (JacRaw *)dres + n, n, dstr);
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, 2 * n);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, a_out, dao, n * 32));
-  CK(d2h(ctx, b_out, dbo, n * 32));
-  CK(d2h(ctx, G_out, dout, n * 64));
-  CK(d2h(ctx, H_out, (uint8_t *)dout + n * 64, n * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{a_out, dao, n * 32}, {b_out, dbo, n * 32}, {G_out, dout, n * 64}, {H_out, (uint8_t *)dout + n * 64, n * 64}});
 }
 int bpgpu_verification_scalars(bpgpu_ctx *ctx, const uint8_t *challenges, size_t k, size_t n, uint8_t *u_sq,
                                uint8_t *u_inv_sq, uint8_t *s) {
@@ -1161,21 +1150,13 @@ int bpgpu_verification_scalars(bpgpu_ctx *ctx, const uint8_t *challenges, size_t
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *d;
-  CK(ws_get(ctx, 0, (3 * k + n + 1) * 32, &d));
+  CK(ws_get(ctx, WS_ARG0, (3 * k + n + 1) * 32, &d));
   Words8 *w = (Words8 *)d;
   CK(flag_reset(ctx));
   CK(h2d(ctx, w, challenges, k * 32));
   scalars_check(ctx->st, w, k, ctx->d_flag);
   verification_scalars(ctx->st, w, k, n, w + k, w + 2 * k, w + 3 * k);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, u_sq, w + k, k * 32));
-  CK(d2h(ctx, u_inv_sq, w + 2 * k, k * 32));
-  CK(d2h(ctx, s, w + 3 * k, n * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{u_sq, w + k, k * 32}, {u_inv_sq, w + 2 * k, k * 32}, {s, w + 3 * k, n * 32}});
 }
 
 /* ---------------------------------------------------------------- R1CS */
@@ -1206,8 +1187,8 @@ static int circuit_create_impl(bpgpu_ctx *ctx, size_t q_real, size_t nchi, const
   c->row = (uint32_t *)((uint8_t *)c->coeff + b_coeff + b_col);
   void *drp, *dkd, *dix, *dcf, *dfill;
   int rc;
-  if ((rc = ws_get(ctx, 0, (q + 1) * 4, &drp)) || (rc = ws_get(ctx, 1, (nnz ? nnz : 1) * 4, &dkd)) || (rc = ws_get(ctx, 2, (nnz ? nnz : 1) * 4, &dix)) ||
-      (rc = ws_get(ctx, 3, (nnz ? nnz : 1) * 32, &dcf)) || (rc = ws_get(ctx, 4, nout * 4, &dfill)))
+  if ((rc = ws_get(ctx, WS_ARG0, (q + 1) * 4, &drp)) || (rc = ws_get(ctx, WS_ARG1, (nnz ? nnz : 1) * 4, &dkd)) || (rc = ws_get(ctx, WS_ARG2, (nnz ? nnz : 1) * 4, &dix)) ||
+      (rc = ws_get(ctx, WS_ARG3, (nnz ? nnz : 1) * 32, &dcf)) || (rc = ws_get(ctx, WS_ARG4, nout * 4, &dfill)))
     return fail(rc);
   if (hipMemsetAsync(ctx->d_flag, 0, sizeof(int), ctx->st) != hipSuccess ||
       hipMemcpyAsync(drp, row_ptr, (q + 1) * 4, hipMemcpyHostToDevice, ctx->st) != hipSuccess ||
@@ -1262,26 +1243,16 @@ int bpgpu_flatten_constraints(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb,
   HIPCK(ctx, hipSetDevice(ctx->device));
   size_t n = c->n, m = c->m;
   void *dz, *dw, *dzp;
-  CK(ws_get(ctx, 0, nb * 32, &dz));
-  CK(ws_get(ctx, 1, nb * (3 * n + m + 1) * 32, &dw));
-  CK(ws_get(ctx, 6, nb * (c->q ? c->q : 1) * 9 * 4, &dzp));
+  CK(ws_get(ctx, WS_ARG0, nb * 32, &dz));
+  CK(ws_get(ctx, WS_ARG1, nb * (3 * n + m + 1) * 32, &dw));
+  CK(ws_get(ctx, WS_ZPOW, nb * (c->q ? c->q : 1) * 9 * 4, &dzp));
   Words8 *w = (Words8 *)dw;
   Words8 *dL = w, *dR = w + nb * n, *dO = w + 2 * nb * n, *dV = w + 3 * nb * n, *dC = w + 3 * nb * n + nb * m;
   CK(flag_reset(ctx));
   CK(h2d(ctx, dz, z, nb * 32));
   scalars_check(ctx->st, (Words8 *)dz, nb, ctx->d_flag);
   flatten(ctx->st, circuit_dev(c), nb, (Words8 *)dz, 8, dL, dR, dO, dV, dC, (int32_t *)dzp);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, wL, dL, nb * n * 32));
-  CK(d2h(ctx, wR, dR, nb * n * 32));
-  CK(d2h(ctx, wO, dO, nb * n * 32));
-  CK(d2h(ctx, wV, dV, nb * m * 32));
-  if (wc) CK(d2h(ctx, wc, dC, nb * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{wL, dL, nb * n * 32}, {wR, dR, nb * n * 32}, {wO, dO, nb * n * 32}, {wV, dV, nb * m * 32}, {wc, dC, wc ? nb * 32 : 0}});
 }
 
 static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
@@ -1299,12 +1270,12 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
   HIPCK(ctx, hipSetDevice(ctx->device));
   size_t nvar = 11 + m + 2 * k, nfix = 2 + 2 * np;
   void *dpts, *dfix, *dvar, *dzp, *dvres, *dfres;
-  CK(ws_get(ctx, 7, nb * nvar * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, 8, nb * nfix * 32, &dfix));
-  CK(ws_get(ctx, 9, nb * nvar * 32, &dvar));
+  CK(ws_get(ctx, WS_VPTS, nb * nvar * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_VFIX, nb * nfix * 32, &dfix));
+  CK(ws_get(ctx, WS_VVAR, nb * nvar * 32, &dvar));
   VerifyDims d{nb, n1, n, np, k, m, (const Words8 *)chi, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
-  CK(ws_get(ctx, 6, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
-  CK(ws_get(ctx, 10, nb * nvar * sizeof(JacRaw), &dvres));
+  CK(ws_get(ctx, WS_ZPOW, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
+  CK(ws_get(ctx, WS_VVRES, nb * nvar * sizeof(JacRaw), &dvres));
   // (nb x parts partial sums when the generator half is walked a proof per lane: BPGPU_OPT_FIXED_CHUNK_GENS)
   size_t fparts = 1;
   if (fixed_msm_chunks(g->c, np, nb) == 1 && verify_wp_supported(nb, nvar, g->c, np)) {
@@ -1314,12 +1285,12 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
     wp_options(ctx, vt);
     fparts = verify_wp_fixed_parts(vt, np);
   }
-  CK(ws_get(ctx, 11, nb * fparts * sizeof(JacRaw), &dfres));
+  CK(ws_get(ctx, WS_VFRES, nb * fparts * sizeof(JacRaw), &dfres));
   void *dstr;
   CK(straus_ws(ctx, 4, nb * nvar, &dstr));
   // per-proof canonicity bits of the scalar assembly (every entry is written by the kernel: no reset)
   void *dbadsc;
-  CK(ws_get(ctx, 20, 2 * nb * sizeof(int32_t), &dbadsc));
+  CK(ws_get(ctx, WS_VBITS, 2 * nb * sizeof(int32_t), &dbadsc));
   int32_t *dbadpt = (int32_t *)dbadsc + nb;   // per-proof malformed-point bits of the Straus / separate-launch paths
   // default: window-parallel variable-base part -- front [tables | inversion pass], scalars, windows, groups,
   // back [Horner | fixed-base MSMs], verdict (k_ec.hip).  Every launch is on ctx->st.
@@ -1332,7 +1303,7 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
   const bool fused_fixed = fixed_msm_chunks(g->c, np, nb) == 1 && verify_wp_supported(nb, nvar, g->c, np);
   if (!no_fuse && !no_wp && nvar && (fused_fixed || nvar <= 256)) {
     void *dwp;
-    CK(ws_get(ctx, 12, verify_wp_scratch_bytes(nb, nvar), &dwp));
+    CK(ws_get(ctx, WS_MSM, verify_wp_scratch_bytes(nb, nvar), &dwp));
     VerifyWp v{(const AffDev *)points, nb, nvar, dwp, ctx->d_flag, (const int32_t *)dbadsc, ctx->latency_mode, false, (int)ctx->opt[BPGPU_OPT_TABLE_NP]};
     wp_options(ctx, v);
     if (!verify_wp_layout_fits(v)) { ctx->err = "internal: window-parallel scratch layout exceeds its buffer (verify)"; return BPGPU_E_DEVICE; }
@@ -1360,7 +1331,7 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
       HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
       HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
       { ProfScope ps(ctx, 1, ctx->st2);
-        CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, 23, 64)); }
+        CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, WS_MSM2, 64)); }
       HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
     }
     { ProfScope ps(ctx, 7, ctx->st);
@@ -1368,7 +1339,7 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
     { ProfScope ps(ctx, 9, ctx->st);
       verify_wp_groups(ctx->st, v); }
     if (!fused_fixed) { ProfScope ps(ctx, 1, ctx->st);
-      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st, 23)); }
+      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st, WS_MSM2)); }
     { ProfScope ps(ctx, 10, ctx->st);
       verify_wp_back(ctx->st, v, g->c, fused_fixed && !side ? g->table : nullptr, np, g->cap, (const uint32_t *)dfix, (2 + 2 * np) * 8, (JacRaw *)dfres); }
     if (side) HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0));
@@ -1415,7 +1386,7 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
     HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
     HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
     { ProfScope ps(ctx, 1, ctx->st2);
-      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, 23)); }
+      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, WS_MSM2)); }
     HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
     bool done = false;
     { ProfScope ps(ctx, 3, ctx->st);
@@ -1444,7 +1415,7 @@ static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
       bf.pts[0] = (const AffDev *)points + vnp * lanes;
       bf.from_boundary = 1; bf.bad = ctx->d_flag; bf.bad_inner = dbadpt;
       void *dstr2;
-      CK(ws_get(ctx, 12, straus_scratch_bytes(1, nb * rem), &dstr2));
+      CK(ws_get(ctx, WS_MSM, straus_scratch_bytes(1, nb * rem), &dstr2));
       straus(ctx->st, 1, bf, (JacRaw *)dvres + lanes, nb * rem, dstr2);
     }
   }
@@ -1492,25 +1463,25 @@ int bpgpu_r1cs_verify_shard(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t m = c->m, nvar = 11 + m + 2 * k;
   void *dP, *dS, *dC, *dok, *dmega, *dchi = nullptr;
-  CK(ws_get(ctx, 0, nvar * 64, &dP));
-  CK(ws_get(ctx, 1, 5 * 32, &dS));
-  CK(ws_get(ctx, 2, (6 + k) * 32, &dC));
-  CK(ws_get(ctx, 3, 4, &dok));
-  CK(ws_get(ctx, 4, 64, &dmega));
-  if (c->nchi) { CK(ws_get(ctx, 21, c->nchi * 32, &dchi)); CK(h2d(ctx, dchi, gadget_challenges, c->nchi * 32)); }
+  CK(ws_get(ctx, WS_ARG0, nvar * 64, &dP));
+  CK(ws_get(ctx, WS_ARG1, 5 * 32, &dS));
+  CK(ws_get(ctx, WS_ARG2, (6 + k) * 32, &dC));
+  CK(ws_get(ctx, WS_ARG3, 4, &dok));
+  CK(ws_get(ctx, WS_ARG4, 64, &dmega));
+  if (c->nchi) { CK(ws_get(ctx, WS_CHI, c->nchi * 32, &dchi)); CK(h2d(ctx, dchi, gadget_challenges, c->nchi * 32)); }
   CK(flag_reset(ctx));
   CK(h2d(ctx, dP, points, nvar * 64));
   CK(h2d(ctx, dS, scalars, 5 * 32));
   CK(h2d(ctx, dC, challenges, (6 + k) * 32));
   if (dchi) scalars_check(ctx->st, (const Words8 *)dchi, c->nchi, ctx->d_flag);
   const size_t shard[2] = {rank, world};
-  void *dbits;                       // the proof's malformed-scalar | malformed-point bits (slot 20 of verify_batch_dev_locked, nb = 1)
-  CK(ws_get(ctx, 20, 2 * sizeof(int32_t), &dbits));
+  void *dbits;                       // the proof's malformed-scalar | malformed-point bits (verify_batch_dev_locked's, nb = 1)
+  CK(ws_get(ctx, WS_VBITS, 2 * sizeof(int32_t), &dbits));
   HIPCK(ctx, hipMemsetAsync(dbits, 0, 2 * sizeof(int32_t), ctx->st));
   CK(verify_batch_dev_locked(ctx, g, c, 1, n1, k, dP, dS, dC, dok, dmega, nullptr, dchi, shard));
   // A malformed operand (off-curve / non-canonical point, non-canonical scalar or challenge) is seen only by the rank whose share
   // holds it: the context flag, or -- on the large-proof route, which validates this rank's slice of the points into the proof's
-  // own bits -- the per-proof bits of workspace slot 20 (scalars | points).  The verdict must be COLLECTIVE: this rank returns
+  // own bits -- the per-proof bits of WS_VBITS (scalars | points).  The verdict must be COLLECTIVE: this rank returns
   // BPGPU_OK with the poison encoding (64 bytes 0xFF: not a point), and bpgpu_points_sum over the gathered partials fails with
   // BPGPU_E_ARG on every rank alike.  (An error code on one rank only would leave the others waiting in their all-gather.)
   int bad = 0;
@@ -1522,33 +1493,48 @@ int bpgpu_r1cs_verify_shard(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
   if (bad || bits[0] || bits[1]) memset(partial_xy, 0xFF, 64);
   return BPGPU_OK;
 }
+// bpgpu_r1cs_verify_batch(_param) after their argument checks: the operands go up, the verdicts come back
+static int verify_batch_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
+                             const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *gadget_challenges,
+                             int32_t *ok, uint8_t *mega, uint8_t *msm_scalars) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  size_t np = (size_t)1 << k, m = c->m, nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
+  void *dP, *dS, *dC, *dok, *dmega, *dfull = nullptr, *dchi = nullptr;
+  CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
+  CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
+  CK(ws_get(ctx, WS_ARG2, nb * (6 + k) * 32, &dC));
+  CK(ws_get(ctx, WS_ARG3, nb * 4, &dok));
+  CK(ws_get(ctx, WS_ARG4, nb * 64, &dmega));
+  if (msm_scalars) CK(ws_get(ctx, WS_ARG5, nb * nterms * 32, &dfull));
+  if (c->nchi && gadget_challenges) { CK(ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi)); CK(h2d(ctx, dchi, gadget_challenges, nb * c->nchi * 32)); }
+  CK(h2d(ctx, dP, points, nb * nvar * 64));
+  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
+  CK(h2d(ctx, dC, challenges, nb * (6 + k) * 32));
+  // a malformed proof (off-curve / non-canonical point, non-canonical scalar or challenge) is rejected on its own:
+  // ok[p] = 0, the other verdicts stand (the reference's per-proof FormatError / VerificationError); so is a proof with a
+  // non-canonical gadget challenge
+  void *dchibad = nullptr;
+  if (dchi) {
+    CK(ws_get(ctx, WS_PROOF_BAD, nb * 4, &dchibad));
+    HIPCK(ctx, hipMemsetAsync(dchibad, 0, nb * 4, ctx->st));
+    scalars_check_proof(ctx->st, (const Words8 *)dchi, nb * c->nchi, c->nchi, ctx->d_flag, (int32_t *)dchibad);
+  }
+  CK(verify_batch_dev_locked(ctx, g, c, nb, n1, k, dP, dS, dC, dok, mega ? dmega : nullptr, dfull, dchi));
+  if (dchibad) and_not(ctx->st, (int32_t *)dok, (const int32_t *)dchibad, nb);
+  CK(d2h(ctx, ok, dok, nb * 4));
+  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
+  if (msm_scalars) CK(d2h(ctx, msm_scalars, dfull, nb * nterms * 32));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+}
 int bpgpu_r1cs_verify_batch(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                             size_t k, const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges,
                             int32_t *ok, uint8_t *mega, uint8_t *msm_scalars) {
   if (!ctx || !g || !c || (nb && (!points || !scalars || !challenges || !ok))) return BPGPU_E_ARG;
   if (k >= 32) return BPGPU_E_LEN;
   if (!nb) return BPGPU_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t np = (size_t)1 << k, m = c->m, nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
-  void *dP, *dS, *dC, *dok, *dmega, *dfull = nullptr;
-  CK(ws_get(ctx, 0, nb * nvar * 64, &dP));
-  CK(ws_get(ctx, 1, nb * 5 * 32, &dS));
-  CK(ws_get(ctx, 2, nb * (6 + k) * 32, &dC));
-  CK(ws_get(ctx, 3, nb * 4, &dok));
-  CK(ws_get(ctx, 4, nb * 64, &dmega));
-  if (msm_scalars) CK(ws_get(ctx, 5, nb * nterms * 32, &dfull));
-  CK(h2d(ctx, dP, points, nb * nvar * 64));
-  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
-  CK(h2d(ctx, dC, challenges, nb * (6 + k) * 32));
-  // a malformed proof (off-curve / non-canonical point, non-canonical scalar or challenge) is rejected on its own:
-  // ok[p] = 0, the other verdicts stand (the reference's per-proof FormatError / VerificationError)
-  CK(verify_batch_dev_locked(ctx, g, c, nb, n1, k, dP, dS, dC, dok, mega ? dmega : nullptr, dfull));
-  CK(d2h(ctx, ok, dok, nb * 4));
-  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
-  if (msm_scalars) CK(d2h(ctx, msm_scalars, dfull, nb * nterms * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return verify_batch_host(ctx, g, c, nb, n1, k, points, scalars, challenges, nullptr, ok, mega, msm_scalars);
 }
 
 /* A STREAM of verification batches in one call: the proofs are cut into batches of `batch` proofs (default 1024) that take turns
@@ -1570,6 +1556,29 @@ static int stream_lanes(bpgpu_ctx *ctx, size_t want) {
   }
   return BPGPU_OK;
 }
+static int lanes_fork(bpgpu_ctx *ctx, size_t nl) {
+  HIPCK(ctx, hipEventRecord(ctx->lane_ev, ctx->st));
+  for (size_t l = 0; l < nl; l++) HIPCK(ctx, hipStreamWaitEvent(ctx->lanes[l]->st, ctx->lane_ev, 0));
+  return BPGPU_OK;
+}
+// the join runs on the way out of an error (rc) too: the batches already submitted keep running, and nothing the caller does next
+// on this context may overtake them: ctx->st -- and with it bpgpu_sync / the caller's next call -- waits for every lane
+static int lanes_join(bpgpu_ctx *ctx, size_t nl, int rc, const char *what) {
+  for (size_t l = 0; l < nl; l++)
+    if (hipEventRecord(ctx->lanes[l]->ev1, ctx->lanes[l]->st) != hipSuccess || hipStreamWaitEvent(ctx->st, ctx->lanes[l]->ev1, 0) != hipSuccess)
+      if (rc == BPGPU_OK) { ctx->err = std::string(what) + ": joining the lanes failed"; rc = BPGPU_E_DEVICE; }
+  return rc;
+}
+// page-locked staging for the verdicts of a host-memory stream or screened call (grow-only): an asynchronous copy into the caller's
+// (pageable) array would make every batch's download a host-side wait for its lane -- and serialise the lanes
+static int pinned_verdicts(bpgpu_ctx *ctx, size_t nb) {
+  if (ctx->pinned_cap < nb * 4) {
+    if (ctx->pinned) { HIPCK(ctx, hipStreamSynchronize(ctx->st)); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; ctx->pinned_cap = 0; }
+    HIPCK(ctx, hipHostMalloc(&ctx->pinned, nb * 4 + nb, hipHostMallocDefault));
+    ctx->pinned_cap = nb * 4 + nb;
+  }
+  return BPGPU_OK;
+}
 static int verify_stream_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                 const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, uint8_t *ok, int on_host) {
   // on_host: 0 = operands and verdicts resident; 1 = pageable host memory (staged copies on the lane's stream); 2 = device-mapped
@@ -1581,8 +1590,7 @@ static int verify_stream_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
   const size_t nchunks = (nb + batch - 1) / batch, nl = nchunks < nlanes_opt ? nchunks : nlanes_opt;
   CK(stream_lanes(ctx, nl));
   const size_t m = c->m, nvar = 11 + m + 2 * k, nch = 6 + k;
-  HIPCK(ctx, hipEventRecord(ctx->lane_ev, ctx->st));
-  for (size_t l = 0; l < nl; l++) HIPCK(ctx, hipStreamWaitEvent(ctx->lanes[l]->st, ctx->lane_ev, 0));
+  CK(lanes_fork(ctx, nl));
   int rc = BPGPU_OK;
   for (size_t ci = 0; ci < nchunks && rc == BPGPU_OK; ci++) {
     bpgpu_ctx *ln = ctx->lanes[ci % nl];
@@ -1591,29 +1599,22 @@ static int verify_stream_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
     uint8_t *O = ok + lo * 4;
     if (on_host == 2) {
       void *dP, *dS, *dC;
-      if (!(rc = ws_get(ln, 0, batch * nvar * 64, &dP)) && !(rc = ws_get(ln, 1, batch * 5 * 32, &dS)) && !(rc = ws_get(ln, 2, batch * nch * 32, &dC))) {
+      if (!(rc = ws_get(ln, WS_ARG0, batch * nvar * 64, &dP)) && !(rc = ws_get(ln, WS_ARG1, batch * 5 * 32, &dS)) && !(rc = ws_get(ln, WS_ARG2, batch * nch * 32, &dC))) {
         hipLaunchKernelGGL(k_fetch3, dim3(64), dim3(256), 0, ln->st, (const uint4 *)P, (uint4 *)dP, cnt * nvar * 4, (const uint4 *)S, (uint4 *)dS, cnt * 10,
                            (const uint4 *)Cc, (uint4 *)dC, cnt * nch * 2);
         rc = verify_batch_dev_locked(ln, g, c, cnt, n1, k, dP, dS, dC, O, nullptr, nullptr);
       }
     } else if (on_host) {       // operands and verdicts in pageable host memory: staged through the lane's own buffers
       void *dP, *dS, *dC, *dok;
-      (void)((rc = ws_get(ln, 0, batch * nvar * 64, &dP)) || (rc = ws_get(ln, 1, batch * 5 * 32, &dS)) ||
-             (rc = ws_get(ln, 2, batch * nch * 32, &dC)) || (rc = ws_get(ln, 3, batch * 4, &dok)) ||
+      (void)((rc = ws_get(ln, WS_ARG0, batch * nvar * 64, &dP)) || (rc = ws_get(ln, WS_ARG1, batch * 5 * 32, &dS)) ||
+             (rc = ws_get(ln, WS_ARG2, batch * nch * 32, &dC)) || (rc = ws_get(ln, WS_ARG3, batch * 4, &dok)) ||
              (rc = h2d(ln, dP, P, cnt * nvar * 64)) || (rc = h2d(ln, dS, S, cnt * 5 * 32)) || (rc = h2d(ln, dC, Cc, cnt * nch * 32)) ||
              (rc = verify_batch_dev_locked(ln, g, c, cnt, n1, k, dP, dS, dC, dok, nullptr, nullptr)) ||
              (rc = d2h(ln, O, dok, cnt * 4)));
     } else rc = verify_batch_dev_locked(ln, g, c, cnt, n1, k, P, S, Cc, O, nullptr, nullptr);
     if (rc) ctx->err = ln->err;
   }
-  // join (also on the way out of an error: the batches already submitted keep running, and nothing the caller does next on this
-  // context may overtake them): ctx->st -- and with it bpgpu_sync / the caller's next call -- waits for every lane
-  for (size_t l = 0; l < nl; l++) {
-    if (hipEventRecord(ctx->lanes[l]->ev1, ctx->lanes[l]->st) != hipSuccess || hipStreamWaitEvent(ctx->st, ctx->lanes[l]->ev1, 0) != hipSuccess) {
-      if (rc == BPGPU_OK) { ctx->err = "bpgpu_r1cs_verify_stream: joining the lanes failed"; rc = BPGPU_E_DEVICE; }
-    }
-  }
-  return rc;
+  return lanes_join(ctx, nl, rc, "bpgpu_r1cs_verify_stream");
 }
 int bpgpu_r1cs_verify_stream_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                  const void *points_dev, const void *scalars_dev, const void *challenges_dev, void *ok_dev) {
@@ -1629,14 +1630,8 @@ int bpgpu_r1cs_verify_stream(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_ci
   if (c->nchi) return BPGPU_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!nb) return BPGPU_OK;
-  // the verdicts come back through page-locked staging: an asynchronous copy into the caller's (pageable) array would make every
-  // batch's download a host-side wait for its lane -- and serialise the lanes
   HIPCK(ctx, hipSetDevice(ctx->device));
-  if (ctx->pinned_cap < nb * 4) {
-    if (ctx->pinned) { HIPCK(ctx, hipStreamSynchronize(ctx->st)); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; ctx->pinned_cap = 0; }
-    HIPCK(ctx, hipHostMalloc(&ctx->pinned, nb * 4 + nb, hipHostMallocDefault));
-    ctx->pinned_cap = nb * 4 + nb;
-  }
+  CK(pinned_verdicts(ctx, nb));
   // Operands in PAGE-LOCKED host memory (bpgpu_host_alloc, hipHostMalloc, hipHostRegister) are fetched by ONE kernel launch per batch
   // on its lane (k_fetch3: wide coalesced reads over the bus -- 2 080 bytes per proof, 8 GB/s at 4 M proofs/s) and the verdicts are
   // written straight into the page-locked staging.  No copy command is enqueued at all: the per-batch H2D / D2H copies on 20 lanes
@@ -1666,10 +1661,10 @@ static int fs_transcript_locked(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t n
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t m = c->m, np = (size_t)1 << k, nchi = c->nchi;
   void *dsteps, *dch, *dbad, *dchi = nullptr;
-  if (nchi) { if (chi_out) dchi = chi_out; else CK(ws_get(ctx, 21, nb * nchi * 32, &dchi)); }
-  CK(ws_get(ctx, 19, transcript_schedule_max(m, k) * sizeof(TrStep) + 64, &dsteps));
-  CK(ws_get(ctx, 17, nb * (6 + k) * 32, &dch));
-  CK(ws_get(ctx, 18, nb * 4, &dbad));
+  if (nchi) { if (chi_out) dchi = chi_out; else CK(ws_get(ctx, WS_CHI, nb * nchi * 32, &dchi)); }
+  CK(ws_get(ctx, WS_SCHED, transcript_schedule_max(m, k) * sizeof(TrStep) + 64, &dsteps));
+  CK(ws_get(ctx, WS_FS_CH, nb * (6 + k) * 32, &dch));
+  CK(ws_get(ctx, WS_PROOF_BAD, nb * 4, &dbad));
   if (ctx->sched_key[0] != m || ctx->sched_key[1] != k || ctx->sched_key[2] != np + (nchi << 40)) {
     std::vector<TrStep> steps(transcript_schedule_max(m, k));
     ctx->sched_len = transcript_schedule(steps.data(), m, k, np, nchi);
@@ -1706,31 +1701,39 @@ int bpgpu_r1cs_verify_batch_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
   std::lock_guard<std::mutex> lk(ctx->mu);
   return verify_fs_locked(ctx, g, c, nb, n1, k, init_states, points, scalars, ok, mega, challenges_out);
 }
+// bpgpu_r1cs_verify_batch_fs(2) after their argument checks: the operands go up, the verdicts and challenges come back
+static int verify_fs_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
+                          const uint8_t *init_states, const uint8_t *gadget_label, const uint8_t *points, const uint8_t *scalars,
+                          int32_t *ok, uint8_t *mega, uint8_t *challenges_out, uint8_t *gadget_challenges_out) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  size_t m = c->m, nvar = 11 + m + 2 * k;
+  void *dP, *dS, *dI, *dok, *dmega, *dcho, *dchi;
+  CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
+  CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
+  CK(ws_get(ctx, WS_ARG2, nb * 32, &dI));
+  CK(ws_get(ctx, WS_ARG3, nb * 4 + nb * 64, &dok));
+  dmega = (uint8_t *)dok + ((nb * 4 + 63) / 64) * 64;
+  CK(ws_get(ctx, WS_FS_STAGE, nb * (6 + k) * 32, &dcho));
+  CK(ws_get(ctx, WS_CHI_OUT, nb * (c->nchi ? c->nchi : 1) * 32, &dchi));
+  CK(h2d(ctx, dP, points, nb * nvar * 64));
+  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
+  CK(h2d(ctx, dI, init_states, nb * 32));
+  CK(verify_fs_locked(ctx, g, c, nb, n1, k, dI, dP, dS, dok, mega ? dmega : nullptr, dcho, gadget_label, c->nchi ? dchi : nullptr));
+  CK(d2h(ctx, ok, dok, nb * 4));
+  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
+  if (challenges_out) CK(d2h(ctx, challenges_out, dcho, nb * (6 + k) * 32));
+  if (gadget_challenges_out && c->nchi) CK(d2h(ctx, gadget_challenges_out, dchi, nb * c->nchi * 32));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+}
 int bpgpu_r1cs_verify_batch_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                const uint8_t *init_states, const uint8_t *points, const uint8_t *scalars, int32_t *ok,
                                uint8_t *mega, uint8_t *challenges_out) {
   if (!ctx || !g || !c || (nb && (!init_states || !points || !scalars || !ok))) return BPGPU_E_ARG;
   if (k >= 32) return BPGPU_E_LEN;
   if (!nb) return BPGPU_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t m = c->m, nvar = 11 + m + 2 * k;
-  void *dP, *dS, *dI, *dok, *dmega, *dcho;
-  CK(ws_get(ctx, 0, nb * nvar * 64, &dP));
-  CK(ws_get(ctx, 1, nb * 5 * 32, &dS));
-  CK(ws_get(ctx, 2, nb * 32, &dI));
-  CK(ws_get(ctx, 3, nb * 4 + nb * 64, &dok));
-  dmega = (uint8_t *)dok + ((nb * 4 + 63) / 64) * 64;
-  CK(ws_get(ctx, 16, nb * (6 + k) * 32, &dcho));
-  CK(h2d(ctx, dP, points, nb * nvar * 64));
-  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
-  CK(h2d(ctx, dI, init_states, nb * 32));
-  CK(verify_fs_locked(ctx, g, c, nb, n1, k, dI, dP, dS, dok, mega ? dmega : nullptr, dcho));
-  CK(d2h(ctx, ok, dok, nb * 4));
-  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
-  if (challenges_out) CK(d2h(ctx, challenges_out, dcho, nb * (6 + k) * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return verify_fs_host(ctx, g, c, nb, n1, k, init_states, nullptr, points, scalars, ok, mega, challenges_out, nullptr);
 }
 
 /* two-phase circuits (parametric constraint weights): host challenges + gadget challenges, or the transcript on the device */
@@ -1740,34 +1743,7 @@ int bpgpu_r1cs_verify_batch_param(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   if (!ctx || !g || !c || (nb && (!points || !scalars || !challenges || !ok)) || (c && c->nchi && !gadget_challenges)) return BPGPU_E_ARG;
   if (k >= 32) return BPGPU_E_LEN;
   if (!nb) return BPGPU_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t np = (size_t)1 << k, m = c->m, nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
-  void *dP, *dS, *dC, *dok, *dmega, *dfull = nullptr, *dchi = nullptr;
-  CK(ws_get(ctx, 0, nb * nvar * 64, &dP));
-  CK(ws_get(ctx, 1, nb * 5 * 32, &dS));
-  CK(ws_get(ctx, 2, nb * (6 + k) * 32, &dC));
-  CK(ws_get(ctx, 3, nb * 4, &dok));
-  CK(ws_get(ctx, 4, nb * 64, &dmega));
-  if (msm_scalars) CK(ws_get(ctx, 5, nb * nterms * 32, &dfull));
-  if (c->nchi) { CK(ws_get(ctx, 21, nb * c->nchi * 32, &dchi)); CK(h2d(ctx, dchi, gadget_challenges, nb * c->nchi * 32)); }
-  CK(h2d(ctx, dP, points, nb * nvar * 64));
-  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
-  CK(h2d(ctx, dC, challenges, nb * (6 + k) * 32));
-  // a non-canonical gadget challenge rejects ITS proof (ok[p] = 0), like any other non-canonical scalar or challenge
-  void *dchibad = nullptr;
-  if (dchi) {
-    CK(ws_get(ctx, 18, nb * 4, &dchibad));
-    HIPCK(ctx, hipMemsetAsync(dchibad, 0, nb * 4, ctx->st));
-    scalars_check_proof(ctx->st, (const Words8 *)dchi, nb * c->nchi, c->nchi, ctx->d_flag, (int32_t *)dchibad);
-  }
-  CK(verify_batch_dev_locked(ctx, g, c, nb, n1, k, dP, dS, dC, dok, mega ? dmega : nullptr, dfull, dchi));
-  if (dchibad) and_not(ctx->st, (int32_t *)dok, (const int32_t *)dchibad, nb);
-  CK(d2h(ctx, ok, dok, nb * 4));
-  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
-  if (msm_scalars) CK(d2h(ctx, msm_scalars, dfull, nb * nterms * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return verify_batch_host(ctx, g, c, nb, n1, k, points, scalars, challenges, gadget_challenges, ok, mega, msm_scalars);
 }
 int bpgpu_r1cs_verify_batch_fs2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                     const void *init_states, const uint8_t gadget_label[32], const void *points, const void *scalars,
@@ -1783,27 +1759,7 @@ int bpgpu_r1cs_verify_batch_fs2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
   if (!ctx || !g || !c || (nb && (!init_states || !points || !scalars || !ok))) return BPGPU_E_ARG;
   if (k >= 32) return BPGPU_E_LEN;
   if (!nb) return BPGPU_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t m = c->m, nvar = 11 + m + 2 * k;
-  void *dP, *dS, *dI, *dok, *dmega, *dcho, *dchi;
-  CK(ws_get(ctx, 0, nb * nvar * 64, &dP));
-  CK(ws_get(ctx, 1, nb * 5 * 32, &dS));
-  CK(ws_get(ctx, 2, nb * 32, &dI));
-  CK(ws_get(ctx, 3, nb * 4 + nb * 64, &dok));
-  dmega = (uint8_t *)dok + ((nb * 4 + 63) / 64) * 64;
-  CK(ws_get(ctx, 16, nb * (6 + k) * 32, &dcho));
-  CK(ws_get(ctx, 22, nb * (c->nchi ? c->nchi : 1) * 32, &dchi));
-  CK(h2d(ctx, dP, points, nb * nvar * 64));
-  CK(h2d(ctx, dS, scalars, nb * 5 * 32));
-  CK(h2d(ctx, dI, init_states, nb * 32));
-  CK(verify_fs_locked(ctx, g, c, nb, n1, k, dI, dP, dS, dok, mega ? dmega : nullptr, dcho, gadget_label, c->nchi ? dchi : nullptr));
-  CK(d2h(ctx, ok, dok, nb * 4));
-  if (mega) CK(d2h(ctx, mega, dmega, nb * 64));
-  if (challenges_out) CK(d2h(ctx, challenges_out, dcho, nb * (6 + k) * 32));
-  if (gadget_challenges_out && c->nchi) CK(d2h(ctx, gadget_challenges_out, dchi, nb * c->nchi * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return verify_fs_host(ctx, g, c, nb, n1, k, init_states, gadget_label, points, scalars, ok, mega, challenges_out, gadget_challenges_out);
 }
 
 /* ---------------------------------------------------------------- Verifier::verify from wire-format proofs */
@@ -1831,10 +1787,10 @@ static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_c
   }
   const size_t m = c->m, nvar = 11 + m + 2 * k;
   void *dcomp, *dxy, *dsc, *dfmt;
-  CK(ws_get(ctx, 0, nb * nvar * 32, &dcomp));
-  CK(ws_get(ctx, 1, nb * nvar * 64, &dxy));
-  CK(ws_get(ctx, 2, nb * 5 * 32, &dsc));
-  CK(ws_get(ctx, 15, nb * 4 + nb * nvar * 4, &dfmt));
+  CK(ws_get(ctx, WS_ARG0, nb * nvar * 32, &dcomp));
+  CK(ws_get(ctx, WS_ARG1, nb * nvar * 64, &dxy));
+  CK(ws_get(ctx, WS_ARG2, nb * 5 * 32, &dsc));
+  CK(ws_get(ctx, WS_VAUX, nb * 4 + nb * nvar * 4, &dfmt));
   int32_t *fmt_ok = (int32_t *)dfmt, *dec_ok = fmt_ok + nb;
   wire_unpack(ctx->st, (const uint8_t *)proofs, proof_len, (const uint8_t *)commitments, nb, m, k, two_phase,
               (Words8 *)dcomp, (Words8 *)dsc, fmt_ok);
@@ -1860,10 +1816,10 @@ int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t m = c->m;
   void *dP, *dC, *dI, *dok;
-  CK(ws_get(ctx, 3, nb * proof_len + 64, &dP));
-  CK(ws_get(ctx, 4, nb * (m ? m : 1) * 32, &dC));
-  CK(ws_get(ctx, 5, nb * 32, &dI));
-  CK(ws_get(ctx, 16, nb * 4, &dok));
+  CK(ws_get(ctx, WS_ARG3, nb * proof_len + 64, &dP));
+  CK(ws_get(ctx, WS_ARG4, nb * (m ? m : 1) * 32, &dC));
+  CK(ws_get(ctx, WS_ARG5, nb * 32, &dI));
+  CK(ws_get(ctx, WS_FS_STAGE, nb * 4, &dok));
   CK(h2d(ctx, dP, proofs, nb * proof_len));
   if (m) CK(h2d(ctx, dC, commitments, nb * m * 32));
   CK(h2d(ctx, dI, init_states, nb * 32));
@@ -1890,27 +1846,27 @@ static int verify_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   HIPCK(ctx, hipSetDevice(ctx->device));
   size_t nvar = 11 + m + 2 * k, nfix = 2 + 2 * np, tot = nb * nvar;
   void *dpts, *dfix, *dvar, *dzp, *dfsum, *dtwo, *dsum, *dpip;
-  int cw = pippenger_window(tot);
-  CK(ws_get(ctx, 7, tot * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, 8, nb * nfix * 32, &dfix));
-  CK(ws_get(ctx, 9, tot * 32, &dvar));
+  CK(ws_get(ctx, WS_VPTS, tot * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_VFIX, nb * nfix * 32, &dfix));
+  CK(ws_get(ctx, WS_VVAR, tot * 32, &dvar));
   if (c->nchi) return BPGPU_E_ARG;
   VerifyDims d{nb, n1, n, np, k, m, nullptr, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
-  CK(ws_get(ctx, 6, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
-  CK(ws_get(ctx, 10, nfix * 32, &dfsum));
-  CK(ws_get(ctx, 11, 2 * sizeof(JacRaw), &dtwo));
-  CK(ws_get(ctx, 15, sizeof(JacRaw), &dsum));
-  CK(ws_get(ctx, 14, pippenger_scratch_bytes(tot, cw), &dpip));
+  CK(ws_get(ctx, WS_ZPOW, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
+  CK(ws_get(ctx, WS_VVRES, nfix * 32, &dfsum));
+  CK(ws_get(ctx, WS_VFRES, 2 * sizeof(JacRaw), &dtwo));
+  CK(ws_get(ctx, WS_VAUX, sizeof(JacRaw), &dsum));
   CK(flag_reset(ctx));
   if (verify_combined2_supported(nb, nvar, g->c, np)) {   // eight launches on one stream (k_pip2.hip)
     void *dc2;
-    CK(ws_get(ctx, 14, verify_combined2_scratch_bytes(nb, nvar, nfix), &dc2));
+    CK(ws_get(ctx, WS_PIP, verify_combined2_scratch_bytes(nb, nvar, nfix), &dc2));
     CombinedArgs ca{circuit_dev(c), d, nvar, (const Words8 *)points, (const Words8 *)scalars, (const Words8 *)challenges,
                     (const Words8 *)rho, (Words8 *)dfix, (Words8 *)dvar, (int32_t *)dzp, g->table, g->cap, g->c, dc2, ctx->d_flag,
                     (Words8 *)partial_xy, ctx->prof ? &prof_mark_cb : nullptr, ctx};
     verify_combined2(ctx->st, ca);
     return launch_ok(ctx);
   }
+  const int cw = pippenger_window(tot);
+  CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes(tot, cw), &dpip));
   // (canonicity of the scalars and challenges is checked inside verify_scalars)
   scalars_check(ctx->st, (const Words8 *)rho, nb, ctx->d_flag);
   verify_scalars(ctx->st, circuit_dev(c), d, (const Words8 *)challenges, (const Words8 *)scalars, (Words8 *)dfix,
@@ -1947,11 +1903,11 @@ int bpgpu_r1cs_verify_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
   HIPCK(ctx, hipSetDevice(ctx->device));
   size_t m = c->m, nvar = 11 + m + 2 * k;
   void *dP, *dS, *dC, *dR, *dout;
-  CK(ws_get(ctx, 0, nb * nvar * 64, &dP));
-  CK(ws_get(ctx, 1, nb * 5 * 32, &dS));
-  CK(ws_get(ctx, 2, nb * (6 + k) * 32, &dC));
-  CK(ws_get(ctx, 3, nb * 32, &dR));
-  CK(ws_get(ctx, 4, 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
+  CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
+  CK(ws_get(ctx, WS_ARG2, nb * (6 + k) * 32, &dC));
+  CK(ws_get(ctx, WS_ARG3, nb * 32, &dR));
+  CK(ws_get(ctx, WS_ARG4, 64, &dout));
   CK(h2d(ctx, dP, points, nb * nvar * 64));
   CK(h2d(ctx, dS, scalars, nb * 5 * 32));
   CK(h2d(ctx, dC, challenges, nb * (6 + k) * 32));
@@ -1965,14 +1921,58 @@ int bpgpu_r1cs_verify_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
   return BPGPU_OK;
 }
 
+/* The two phases of a screened call over `nchecks` checks, each forked over the lanes and joined.  Phase 1: check(ln, ci, partial) on
+ * lane ci % nl writes check ci's point to `partial` (HBM) and leaves its malformed-input flag in ln->d_flag, which is copied beside
+ * it; the host reads every point and flag at once.  Phase 2: a check passes when its flag is 0 and its point is the identity (64
+ * zero bytes): accept(ci) marks its proofs valid; the others go to fallback(ln, ci), round-robin over the lanes. */
+extern "C++" {   // (a template, in the middle of the C ABI)
+template <class Check, class Accept, class Fallback>
+static int screen_locked(bpgpu_ctx *ctx, size_t nchecks, const char *what, size_t *fallback_batches, Check check, Accept accept,
+                         Fallback fallback) try {
+  const size_t nlanes_opt = (size_t)ctx->opt[BPGPU_OPT_STREAM_LANES], nl = nchecks < nlanes_opt ? nchecks : nlanes_opt;
+  CK(stream_lanes(ctx, nl));
+  void *dpart, *dflag;
+  CK(ws_get(ctx, WS_SCREEN_PART, nchecks * 64, &dpart));
+  CK(ws_get(ctx, WS_SCREEN_FLAG, nchecks * 4, &dflag));
+  std::vector<uint8_t> hpart(nchecks * 64);
+  std::vector<int> hflag(nchecks);
+  CK(lanes_fork(ctx, nl));
+  int rc = BPGPU_OK;
+  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
+    bpgpu_ctx *ln = ctx->lanes[ci % nl];
+    rc = check(ln, ci, (uint8_t *)dpart + 64 * ci);
+    if (rc == BPGPU_OK && hipMemcpyAsync((int *)dflag + ci, ln->d_flag, 4, hipMemcpyDeviceToDevice, ln->st) != hipSuccess) rc = BPGPU_E_DEVICE;
+    if (rc) ctx->err = ln->err;
+  }
+  CK(lanes_join(ctx, nl, rc, what));
+  CK(d2h(ctx, hpart.data(), dpart, nchecks * 64));
+  CK(d2h(ctx, hflag.data(), dflag, nchecks * 4));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  size_t nfall = 0;
+  CK(lanes_fork(ctx, nl));
+  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
+    bool pass = hflag[ci] == 0;
+    for (size_t i = 0; i < 64 && pass; i++) pass = hpart[64 * ci + i] == 0;
+    if (pass) { rc = accept(ci); continue; }
+    bpgpu_ctx *ln = ctx->lanes[nfall++ % nl];
+    rc = fallback(ln, ci);
+    if (rc) ctx->err = ln->err;
+  }
+  rc = lanes_join(ctx, nl, rc, what);
+  if (fallback_batches) *fallback_batches = nfall;
+  return rc;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+}  // extern "C++"
+
 /* Screened stream: the combined check of every batch first (one point per batch), the per-proof path only for the batches whose
- * point is not the identity (or that hold a malformed input).  Phase 1 and phase 2 each fork over the lanes and join; between them
- * the host reads 68 bytes per batch. */
+ * point is not the identity (or that hold a malformed input). */
 // init_states != null: the transcript is replayed on the device (challenges unused): per batch k_verify_transcript first, and a proof
 // whose transcript replay fails (a validated point is the identity) sends its batch to the per-proof path like any other failure
 static int verify_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                   const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *rho,
-                                  uint8_t *ok, bool on_host, size_t *fallback_batches, const uint8_t *init_states = nullptr) try {
+                                  uint8_t *ok, bool on_host, size_t *fallback_batches, const uint8_t *init_states = nullptr) {
   if (k >= 32) return BPGPU_E_LEN;
   if (fallback_batches) *fallback_batches = 0;
   if (!nb) return BPGPU_OK;
@@ -1984,25 +1984,8 @@ static int verify_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   size_t batch = (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH];
   const size_t fit = ((size_t)1 << 16) / nvar / 64 * 64;          // proof points of one check <= 2^16
   if (fit >= 256 && batch > fit) batch = fit;
-  const size_t nlanes_opt = (size_t)ctx->opt[BPGPU_OPT_STREAM_LANES];
-  const size_t nchunks = (nb + batch - 1) / batch, nl = nchunks < nlanes_opt ? nchunks : nlanes_opt;
-  CK(stream_lanes(ctx, nl));
-  void *dpart, *dflag;
-  CK(ws_get(ctx, 26, nchunks * 64, &dpart));
-  CK(ws_get(ctx, 27, nchunks * 4, &dflag));
-  std::vector<uint8_t> hpart(nchunks * 64);
-  std::vector<int> hflag(nchunks);
-  auto fork = [&]() -> int {
-    HIPCK(ctx, hipEventRecord(ctx->lane_ev, ctx->st));
-    for (size_t l = 0; l < nl; l++) HIPCK(ctx, hipStreamWaitEvent(ctx->lanes[l]->st, ctx->lane_ev, 0));
-    return BPGPU_OK;
-  };
-  auto join = [&](int rc) -> int {
-    for (size_t l = 0; l < nl; l++)
-      if (hipEventRecord(ctx->lanes[l]->ev1, ctx->lanes[l]->st) != hipSuccess || hipStreamWaitEvent(ctx->st, ctx->lanes[l]->ev1, 0) != hipSuccess)
-        if (rc == BPGPU_OK) { ctx->err = "bpgpu_r1cs_verify_screened: joining the lanes failed"; rc = BPGPU_E_DEVICE; }
-    return rc;
-  };
+  const size_t nchunks = (nb + batch - 1) / batch;
+  auto count = [&](size_t lo) { return nb - lo < batch ? nb - lo : batch; };
   // stage a batch's operands on its lane (host variant); returns device pointers either way
   // (*Cc = the challenges, or with a device transcript the batch's 32-byte initial states)
   const uint8_t *third = init_states ? init_states : challenges;
@@ -2014,66 +1997,45 @@ static int verify_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
     }
     void *dP, *dS, *dC, *dR;
     int rc;
-    if ((rc = ws_get(ln, 0, batch * nvar * 64, &dP)) || (rc = ws_get(ln, 1, batch * 5 * 32, &dS)) || (rc = ws_get(ln, 2, batch * third_bytes, &dC)) ||
-        (rc = ws_get(ln, 3, batch * 32, &dR)) || (rc = ws_get(ln, 4, batch * 4, dok)) ||
+    if ((rc = ws_get(ln, WS_ARG0, batch * nvar * 64, &dP)) || (rc = ws_get(ln, WS_ARG1, batch * 5 * 32, &dS)) || (rc = ws_get(ln, WS_ARG2, batch * third_bytes, &dC)) ||
+        (rc = ws_get(ln, WS_ARG3, batch * 32, &dR)) || (rc = ws_get(ln, WS_ARG4, batch * 4, dok)) ||
         (rc = h2d(ln, dP, points + lo * nvar * 64, cnt * nvar * 64)) || (rc = h2d(ln, dS, scalars + lo * 5 * 32, cnt * 5 * 32)) ||
         (rc = h2d(ln, dC, third + lo * third_bytes, cnt * third_bytes)) || (rc = h2d(ln, dR, rho + lo * 32, cnt * 32)))
       return rc;
     *P = dP; *S = dS; *Cc = dC; *R = dR;
     return BPGPU_OK;
   };
-  // ---- phase 1: one combined check per batch
-  CK(fork());
-  int rc = BPGPU_OK;
-  for (size_t ci = 0; ci < nchunks && rc == BPGPU_OK; ci++) {
-    bpgpu_ctx *ln = ctx->lanes[ci % nl];
-    const size_t lo = ci * batch, cnt = nb - lo < batch ? nb - lo : batch;
+  auto check = [&](bpgpu_ctx *ln, size_t ci, void *partial) -> int {
+    const size_t lo = ci * batch, cnt = count(lo);
     const void *P, *S, *Cc, *R;
-    void *dok;
-    rc = operands(ln, lo, cnt, &P, &S, &Cc, &R, &dok);
-    void *dbad = nullptr, *dchi = nullptr;
-    if (rc == BPGPU_OK && init_states) {       // the batch's challenges from the device transcript
+    void *dok, *dbad = nullptr, *dchi = nullptr;
+    CK(operands(ln, lo, cnt, &P, &S, &Cc, &R, &dok));
+    if (init_states) {       // the batch's challenges from the device transcript
       Words8 *chp = nullptr;
-      rc = fs_transcript_locked(ln, c, cnt, k, Cc, P, S, nullptr, nullptr, nullptr, &chp, &dbad, &dchi);
+      CK(fs_transcript_locked(ln, c, cnt, k, Cc, P, S, nullptr, nullptr, nullptr, &chp, &dbad, &dchi));
       Cc = chp;
     }
-    if (rc == BPGPU_OK) rc = verify_combined_locked(ln, g, c, cnt, n1, k, P, S, Cc, R, (uint8_t *)dpart + 64 * ci);
-    if (rc == BPGPU_OK && dbad) or_flag(ln->st, (const int32_t *)dbad, cnt, ln->d_flag);      // (after the combined check: it resets the flag)
-    if (rc == BPGPU_OK) zero_flag(ln->st, (const Words8 *)R, cnt, ln->d_flag);                // a zero weight voids the check for its batch
-    if (rc == BPGPU_OK && hipMemcpyAsync((int *)dflag + ci, ln->d_flag, 4, hipMemcpyDeviceToDevice, ln->st) != hipSuccess) rc = BPGPU_E_DEVICE;
-    if (rc) ctx->err = ln->err;
-  }
-  rc = join(rc);
-  if (rc) return rc;
-  CK(d2h(ctx, hpart.data(), dpart, nchunks * 64));
-  CK(d2h(ctx, hflag.data(), dflag, nchunks * 4));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  // ---- phase 2: all-accept for the batches that passed, the per-proof verification for the others
-  size_t nfall = 0;
-  CK(fork());
-  for (size_t ci = 0; ci < nchunks && rc == BPGPU_OK; ci++) {
-    const size_t lo = ci * batch, cnt = nb - lo < batch ? nb - lo : batch;
-    bool pass = hflag[ci] == 0;
-    for (size_t i = 0; i < 64 && pass; i++) pass = hpart[64 * ci + i] == 0;
-    if (pass) {
-      if (on_host) for (size_t i = 0; i < cnt; i++) ((int32_t *)ok)[lo + i] = 1;
-      else if (hipMemsetD32Async((hipDeviceptr_t)(ok + lo * 4), 1, cnt, ctx->st) != hipSuccess) rc = BPGPU_E_DEVICE;
-      continue;
-    }
-    bpgpu_ctx *ln = ctx->lanes[nfall++ % nl];
+    CK(verify_combined_locked(ln, g, c, cnt, n1, k, P, S, Cc, R, partial));
+    if (dbad) or_flag(ln->st, (const int32_t *)dbad, cnt, ln->d_flag);      // (after the combined check: it resets the flag)
+    zero_flag(ln->st, (const Words8 *)R, cnt, ln->d_flag);                   // a zero weight voids the check for its batch
+    return BPGPU_OK;
+  };
+  auto accept = [&](size_t ci) -> int {
+    const size_t lo = ci * batch, cnt = count(lo);
+    if (on_host) for (size_t i = 0; i < cnt; i++) ((int32_t *)ok)[lo + i] = 1;
+    else if (hipMemsetD32Async((hipDeviceptr_t)(ok + lo * 4), 1, cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
+    return BPGPU_OK;
+  };
+  auto fallback = [&](bpgpu_ctx *ln, size_t ci) -> int {
+    const size_t lo = ci * batch, cnt = count(lo);
     const void *P, *S, *Cc, *R;
     void *dok;
-    (void)((rc = operands(ln, lo, cnt, &P, &S, &Cc, &R, &dok)) ||
-           (rc = init_states ? verify_fs_locked(ln, g, c, cnt, n1, k, Cc, P, S, dok, nullptr, nullptr)
-                             : verify_batch_dev_locked(ln, g, c, cnt, n1, k, P, S, Cc, dok, nullptr, nullptr)) ||
-           (on_host && (rc = d2h(ln, ok + lo * 4, dok, cnt * 4))));
-    if (rc) ctx->err = ln->err;
-  }
-  rc = join(rc);
-  if (fallback_batches) *fallback_batches = nfall;
-  return rc;
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
+    CK(operands(ln, lo, cnt, &P, &S, &Cc, &R, &dok));
+    CK(init_states ? verify_fs_locked(ln, g, c, cnt, n1, k, Cc, P, S, dok, nullptr, nullptr)
+                   : verify_batch_dev_locked(ln, g, c, cnt, n1, k, P, S, Cc, dok, nullptr, nullptr));
+    return on_host ? d2h(ln, ok + lo * 4, dok, cnt * 4) : BPGPU_OK;
+  };
+  return screen_locked(ctx, nchunks, "bpgpu_r1cs_verify_screened", fallback_batches, check, accept, fallback);
 }
 int bpgpu_r1cs_verify_screened_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                                       const void *init_states_dev, const void *points_dev, const void *scalars_dev, const void *rho_dev,
@@ -2102,11 +2064,7 @@ int bpgpu_r1cs_verify_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
   if (fallback_batches) *fallback_batches = 0;
   if (!nb) return BPGPU_OK;
   HIPCK(ctx, hipSetDevice(ctx->device));
-  if (ctx->pinned_cap < nb * 4) {       // verdicts of the fallback batches come back through page-locked staging (bpgpu_r1cs_verify_stream)
-    if (ctx->pinned) { HIPCK(ctx, hipStreamSynchronize(ctx->st)); (void)hipHostFree(ctx->pinned); ctx->pinned = nullptr; ctx->pinned_cap = 0; }
-    HIPCK(ctx, hipHostMalloc(&ctx->pinned, nb * 4 + nb, hipHostMallocDefault));
-    ctx->pinned_cap = nb * 4 + nb;
-  }
+  CK(pinned_verdicts(ctx, nb));
   CK(verify_screened_locked(ctx, g, c, nb, n1, k, points, scalars, challenges, rho, (uint8_t *)ctx->pinned, true, fallback_batches));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
   memcpy(ok, ctx->pinned, nb * 4);
@@ -2185,7 +2143,7 @@ static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_ve
     v.rho = (const Words8 *)x.rho + lo;
   }
   void *scr;
-  CK(ws_get(ln, 14, verify_mixed_scratch_bytes(in, nseg, g->c), &scr));
+  CK(ws_get(ln, WS_PIP, verify_mixed_scratch_bytes(in, nseg, g->c), &scr));
   MixedArgs a{in, nseg, scr, g->table, g->cap, g->c, ln->d_flag, zero_rho, (Words8 *)partial_xy, ln->prof ? &prof_mark_cb : nullptr, ln};
   verify_mixed(ln->st, a);
   return launch_ok(ln);
@@ -2198,12 +2156,12 @@ static int mixed_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
   CK(flag_reset(ctx));
   if (checks.empty()) { HIPCK(ctx, hipMemsetAsync(partial_xy, 0, 64, ctx->st)); return BPGPU_OK; }
   void *dpart = partial_xy;
-  if (checks.size() > 1) CK(ws_get(ctx, 26, checks.size() * 64, &dpart));
+  if (checks.size() > 1) CK(ws_get(ctx, WS_SCREEN_PART, checks.size() * 64, &dpart));
   for (size_t ci = 0; ci < checks.size(); ci++)
     CK(mixed_check_locked(ctx, g, G, segs.data() + checks[ci].first, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
   int *dbad2;
   if (checks.size() > 1) {       // the checks' partials are valid points: their sum cannot raise the flag (a separate one all the same)
-    CK(ws_get(ctx, 27, 256, (void **)&dbad2));
+    CK(ws_get(ctx, WS_SCREEN_FLAG, 256, (void **)&dbad2));
     points_sum(ctx->st, (const Words8 *)dpart, checks.size(), (Words8 *)partial_xy, dbad2);
   }
   mixed_poison(ctx->st, ctx->d_flag, (Words8 *)partial_xy);
@@ -2219,7 +2177,7 @@ static int mixed_per_proof_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgp
   int32_t *ok = (int32_t *)x.ok + lo;
   void *dchibad = nullptr;
   if (chi) {        // a non-canonical gadget challenge rejects ITS proof, as in bpgpu_r1cs_verify_batch_param
-    CK(ws_get(ln, 18, cnt * 4, &dchibad));
+    CK(ws_get(ln, WS_PROOF_BAD, cnt * 4, &dchibad));
     HIPCK(ln, hipMemsetAsync(dchibad, 0, cnt * 4, ln->st));
     scalars_check_proof(ln->st, chi, cnt * c->nchi, c->nchi, ln->d_flag, (int32_t *)dchibad);
   }
@@ -2235,60 +2193,24 @@ static int mixed_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
   std::vector<MixCheck> checks;
   // proofs per check: BPGPU_OPT_SCREEN_BATCH, and at most 2^16 proof points (the one-instance bucket pipeline of k_pip2.hip)
   mixed_plan(G, ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, segs, checks);
-  const size_t nchecks = checks.size();
-  if (!nchecks) return BPGPU_OK;
-  const size_t nlanes_opt = (size_t)ctx->opt[BPGPU_OPT_STREAM_LANES], nl = nchecks < nlanes_opt ? nchecks : nlanes_opt;
-  CK(stream_lanes(ctx, nl));
-  void *dpart, *dflag;
-  CK(ws_get(ctx, 26, nchecks * 64, &dpart));
-  CK(ws_get(ctx, 27, nchecks * 4, &dflag));
-  std::vector<uint8_t> hpart(nchecks * 64);
-  std::vector<int> hflag(nchecks);
-  auto fork = [&]() -> int {
-    HIPCK(ctx, hipEventRecord(ctx->lane_ev, ctx->st));
-    for (size_t l = 0; l < nl; l++) HIPCK(ctx, hipStreamWaitEvent(ctx->lanes[l]->st, ctx->lane_ev, 0));
+  if (checks.empty()) return BPGPU_OK;
+  // a check's flag holds malformed input and zero weights; a failing check takes the per-proof path segment by segment
+  auto check = [&](bpgpu_ctx *ln, size_t ci, void *partial) -> int {
+    CK(flag_reset(ln));
+    return mixed_check_locked(ln, g, G, segs.data() + checks[ci].first, checks[ci].nseg, partial, ln->d_flag);
+  };
+  auto accept = [&](size_t ci) -> int {
+    const MixSeg *sg = segs.data() + checks[ci].first;
+    for (size_t s = 0; s < checks[ci].nseg; s++)
+      if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
     return BPGPU_OK;
   };
-  auto join = [&](int rc) -> int {
-    for (size_t l = 0; l < nl; l++)
-      if (hipEventRecord(ctx->lanes[l]->ev1, ctx->lanes[l]->st) != hipSuccess || hipStreamWaitEvent(ctx->st, ctx->lanes[l]->ev1, 0) != hipSuccess)
-        if (rc == BPGPU_OK) { ctx->err = "bpgpu_r1cs_verify_mixed_screened: joining the lanes failed"; rc = BPGPU_E_DEVICE; }
-    return rc;
-  };
-  // ---- phase 1: one ragged combined check per check; its flag holds malformed input and zero weights
-  CK(fork());
-  int rc = BPGPU_OK;
-  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
-    bpgpu_ctx *ln = ctx->lanes[ci % nl];
-    (void)((rc = flag_reset(ln)) ||
-           (rc = mixed_check_locked(ln, g, G, segs.data() + checks[ci].first, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, ln->d_flag)));
-    if (rc == BPGPU_OK && hipMemcpyAsync((int *)dflag + ci, ln->d_flag, 4, hipMemcpyDeviceToDevice, ln->st) != hipSuccess) rc = BPGPU_E_DEVICE;
-    if (rc) ctx->err = ln->err;
-  }
-  rc = join(rc);
-  if (rc) return rc;
-  CK(d2h(ctx, hpart.data(), dpart, nchecks * 64));
-  CK(d2h(ctx, hflag.data(), dflag, nchecks * 4));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  // ---- phase 2: all-accept for the checks that passed, the per-proof path segment by segment for the others
-  size_t nfall = 0;
-  CK(fork());
-  for (size_t ci = 0; ci < nchecks && rc == BPGPU_OK; ci++) {
-    bool pass = hflag[ci] == 0;
-    for (size_t i = 0; i < 64 && pass; i++) pass = hpart[64 * ci + i] == 0;
+  auto fallback = [&](bpgpu_ctx *ln, size_t ci) -> int {
     const MixSeg *sg = segs.data() + checks[ci].first;
-    if (pass) {
-      for (size_t s = 0; s < checks[ci].nseg && rc == BPGPU_OK; s++)
-        if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) rc = BPGPU_E_DEVICE;
-      continue;
-    }
-    bpgpu_ctx *ln = ctx->lanes[nfall++ % nl];
-    for (size_t s = 0; s < checks[ci].nseg && rc == BPGPU_OK; s++) rc = mixed_per_proof_locked(ln, g, G[sg[s].gi], sg[s].lo, sg[s].cnt);
-    if (rc) ctx->err = ln->err;
-  }
-  rc = join(rc);
-  if (fallback_batches) *fallback_batches = nfall;
-  return rc;
+    for (size_t s = 0; s < checks[ci].nseg; s++) CK(mixed_per_proof_locked(ln, g, G[sg[s].gi], sg[s].lo, sg[s].cnt));
+    return BPGPU_OK;
+  };
+  return screen_locked(ctx, checks.size(), "bpgpu_r1cs_verify_mixed_screened", fallback_batches, check, accept, fallback);
 } catch (const std::bad_alloc &) {
   return BPGPU_E_OOM;
 }
@@ -2302,7 +2224,7 @@ static int mixed_stage_locked(bpgpu_ctx *ctx, const bpgpu_verify_group *G, size_
   };
   for (size_t i = 0; i < ngroups; i++) { size_t b[6]; sizes(G[i], b); for (size_t j : b) tot += (j + 255) / 256 * 256; }
   void *base;
-  CK(ws_get(ctx, 29, tot, &base));
+  CK(ws_get(ctx, WS_MIXED_STAGE, tot, &base));
   uint8_t *q = (uint8_t *)base;
   D.assign(G, G + ngroups);
   for (size_t i = 0; i < ngroups; i++) {
@@ -2335,7 +2257,7 @@ int bpgpu_r1cs_verify_mixed_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const 
   std::vector<bpgpu_verify_group> D;
   CK(mixed_stage_locked(ctx, groups, ngroups, D));
   void *dout;
-  CK(ws_get(ctx, 4, 64, &dout));
+  CK(ws_get(ctx, WS_ARG4, 64, &dout));
   CK(mixed_combined_locked(ctx, g, D.data(), ngroups, dout));
   CK(d2h(ctx, partial_xy, dout, 64));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
@@ -2527,7 +2449,7 @@ static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy, bool beav
     {
       size_t chunks = fixed_msm_ipp_chunks(s->gens->c, s->n0, nb * 2);
       void *dpart = nullptr;
-      if (chunks > 1) CK(ws_get(ctx, 12, nb * 2 * chunks * sizeof(JacRaw), &dpart));
+      if (chunks > 1) CK(ws_get(ctx, WS_MSM, nb * 2 * chunks * sizeof(JacRaw), &dpart));
       ProfScope ps(ctx, 21, st);
       // (out_xy == nullptr: the caller's fused round tail sums the chunk partials and converts the points itself)
       const bool tail_sums = !out_xy && chunks > 1 && chunks <= 256;
@@ -2568,7 +2490,7 @@ static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy, bool beav
   if (seg >= pip_min) {   // bucket method, one batched launch for all instances
     int cw = pippenger_window(seg);
     void *dpip;
-    CK(ws_get(ctx, 14, pippenger_scratch_bytes_batch(nb * 2, seg, cw), &dpip));
+    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nb * 2, seg, cw), &dpip));
     pippenger_batch(st, s->mpts, (const uint32_t *)s->msc, nb * 2, seg, cw, s->sums, 1, dpip);
   } else {                // short rounds: one Straus lane per term (a single launch), then a tree sum per instance
     StrausArgs x{};
@@ -2630,7 +2552,7 @@ static int ipp_fold_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *du, Words8 *dui) {
   // the G and the H fold are independent 252-doubling chains: run them side by side on the context's two streams
   void *dstr, *dstr2;
   CK(straus_ws(ctx, 2, nb * h, &dstr));
-  CK(ws_get(ctx, 12, straus_scratch_bytes(2, nb * h), &dstr2));
+  CK(ws_get(ctx, WS_MSM, straus_scratch_bytes(2, nb * h), &dstr2));
   hipStream_t st2 = ctx->st2;
   HIPCK(ctx, hipEventRecord(ctx->ev1, st));
   HIPCK(ctx, hipStreamWaitEvent(st2, ctx->ev1, 0));
@@ -2692,9 +2614,9 @@ int bpgpu_ipp_run_fs(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *states_in, uin
   for (size_t t = s->n; t > 1; t >>= 1) k++;
   if (k && (!L_out || !R_out)) return BPGPU_E_ARG;
   void *dstates, *dlr, *dzero;
-  CK(ws_get(ctx, 16, nb * 32, &dstates));
-  CK(ws_get(ctx, 17, (k ? k : 1) * nb * 128, &dlr));
-  CK(ws_get(ctx, 18, 4, &dzero));
+  CK(ws_get(ctx, WS_FS_STAGE, nb * 32, &dstates));
+  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
+  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
   CK(h2d(ctx, dstates, states_in, nb * 32));
   Words8 *du = s->uu, *dui = s->uu + nb;
   ProfSpan span(ctx, 20, ctx->st);
@@ -2818,8 +2740,8 @@ static int prover_polys_impl(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, 
   void *din, *dzp, *dout;
   size_t tot = nb * n;
   int rc;
-  if ((rc = ws_get(ctx, 0, (3 * nb + 5 * tot) * 32, &din)) || (rc = ws_get(ctx, 6, nb * (c->q ? c->q : 1) * 9 * 4, &dzp)) ||
-      (rc = ws_get(ctx, 1, (nb * 6 + nb * m) * 32, &dout)))
+  if ((rc = ws_get(ctx, WS_ARG0, (3 * nb + 5 * tot) * 32, &din)) || (rc = ws_get(ctx, WS_ZPOW, nb * (c->q ? c->q : 1) * 9 * 4, &dzp)) ||
+      (rc = ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout)))
     return fail(rc);
   Words8 *w = (Words8 *)din;
   Words8 *dy = w, *dyi = w + nb, *dz = w + 2 * nb, *dL = w + 3 * nb, *dR = dL + tot, *dO = dR + tot, *dsL = dO + tot, *dsR = dsL + tot;
@@ -2864,21 +2786,14 @@ int bpgpu_r1cs_prover_eval(bpgpu_ctx *ctx, bpgpu_prover *s, size_t padded_n, con
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *dx, *dout;
   size_t nb = s->nb;
-  CK(ws_get(ctx, 0, nb * 32, &dx));
-  CK(ws_get(ctx, 1, 2 * nb * padded_n * 32, &dout));
+  CK(ws_get(ctx, WS_ARG0, nb * 32, &dx));
+  CK(ws_get(ctx, WS_ARG1, 2 * nb * padded_n * 32, &dout));
   Words8 *dl = (Words8 *)dout, *dr = dl + nb * padded_n;
   CK(flag_reset(ctx));
   CK(h2d(ctx, dx, x, nb * 32));
   scalars_check(ctx->st, (Words8 *)dx, nb, ctx->d_flag);
   prover_eval(ctx->st, nb, s->n, padded_n, (Words8 *)dx, s->y, s->polys, dl, dr);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, l_vec, dl, nb * padded_n * 32));
-  CK(d2h(ctx, r_vec, dr, nb * padded_n * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{l_vec, dl, nb * padded_n * 32}, {r_vec, dr, nb * padded_n * 32}});
 }
 /* prover.rs:659-708 without leaving the device: l(x), r(x) with their padding, the G/H factors and the
  * resident-generator IPP session that consumes them */
@@ -2909,7 +2824,7 @@ static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_g
   int rc = BPGPU_OK;
   do {
     void *din;
-    if ((rc = ws_get(ctx, 0, 3 * nb * 32, &din))) break;
+    if ((rc = ws_get(ctx, WS_ARG0, 3 * nb * 32, &din))) break;
     Words8 *dx = (Words8 *)din, *du = dx + nb, *dyi = du + nb;
     if ((rc = flag_reset(ctx))) break;
     if ((rc = h2d(ctx, dx, x, nb * 32)) || (rc = h2d(ctx, du, u, nb * 32)) || (rc = h2d(ctx, s->w, w, nb * 32))) break;
@@ -2974,8 +2889,8 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   const size_t tot_new = nb * n_new;
   void *din = nullptr, *drows = nullptr, *dres = nullptr, *dout = nullptr;
   int rc;
-  if ((rc = ws_get(ctx, 0, (5 * tot_new + 4 * nb) * 32, &din)) || (rc = ws_get(ctx, 1, nb * 3 * (2 + 2 * wn) * 32, &drows)) ||
-      (rc = ws_get(ctx, 4, nb * 3 * sizeof(JacRaw), &dres)) || (rc = ws_get(ctx, 5, nb * 3 * 64, &dout)))
+  if ((rc = ws_get(ctx, WS_ARG0, (5 * tot_new + 4 * nb) * 32, &din)) || (rc = ws_get(ctx, WS_ARG1, nb * 3 * (2 + 2 * wn) * 32, &drows)) ||
+      (rc = ws_get(ctx, WS_ARG4, nb * 3 * sizeof(JacRaw), &dres)) || (rc = ws_get(ctx, WS_ARG5, nb * 3 * 64, &dout)))
     return fail(rc);
   if (n_new) {
     bool okk = true;
@@ -3015,7 +2930,7 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   if (ctx->shard_world > 1) shard_bounds(wn, ctx->shard_rank, ctx->shard_world, &slo, &shi);   // this rank's generators: partial commitments
   commit_rows(ctx->st, nb, wn, wn0, wn, s->aL, s->aR, s->aO, s->sL, s->sR, dbl, (Words8 *)drows, slo, shi, ctx->shard_rank == 0);
   // (three classes of rows per prover -- A_I, A_O: bit vectors; S: dense -- so that a wave of the MSM-per-lane walk holds one class)
-  if ((rc = msm_gens_dev(ctx, g, nb * 3, wn, (const uint32_t *)drows, (JacRaw *)dres, ctx->st, 12, 0, 3))) return fail(rc);
+  if ((rc = msm_gens_dev(ctx, g, nb * 3, wn, (const uint32_t *)drows, (JacRaw *)dres, ctx->st, WS_MSM, 0, 3))) return fail(rc);
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, nb * 3);
   span.close();
   if ((rc = launch_ok(ctx))) return fail(rc);
@@ -3061,10 +2976,10 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
   s->n = n; s->m = m;
   void *din, *dzp, *dout, *dchi = nullptr;
   const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);    // a parametric circuit's z-power table carries one block per gadget challenge
-  CK(ws_get(ctx, 0, 2 * nb * 32, &din));
-  CK(ws_get(ctx, 6, nb * qz * 9 * 4, &dzp));
-  CK(ws_get(ctx, 1, (nb * 6 + nb * m) * 32, &dout));
-  if (c->nchi) CK(ws_get(ctx, 21, nb * c->nchi * 32, &dchi));
+  CK(ws_get(ctx, WS_ARG0, 2 * nb * 32, &din));
+  CK(ws_get(ctx, WS_ZPOW, nb * qz * 9 * 4, &dzp));
+  CK(ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout));
+  if (c->nchi) CK(ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi));
   Words8 *dz = (Words8 *)din, *dt = (Words8 *)dout, *dwV = dt + nb * 6;
   CK(flag_reset(ctx));
   CK(h2d(ctx, s->y, y, nb * 32));
@@ -3079,14 +2994,7 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
   prover_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, (const int32_t *)dzp, s->polys, dwV);
   prover_tcoeffs(ctx->st, nb, n, s->polys, dt);
   span.close();
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, t_coeffs, dt, nb * 6 * 32));
-  if (m) CK(d2h(ctx, wV, dwV, nb * m * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{t_coeffs, dt, nb * 6 * 32}, {wV, dwV, nb * m * 32}});
 }
 /* scalars[i] * (curve generator): GeneratorsChain::next (generators.rs:112-124), Q = w * B (prover.rs:687) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out) {
@@ -3107,21 +3015,15 @@ int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   void *dsc, *dres, *dout;
-  CK(ws_get(ctx, 0, n * 32, &dsc));
-  CK(ws_get(ctx, 3, n * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 5, n * 64, &dout));
+  CK(ws_get(ctx, WS_ARG0, n * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG3, n * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG5, n * 64, &dout));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dsc, scalars, n * 32));
   scalars_check(ctx->st, (Words8 *)dsc, n, ctx->d_flag);
   fixed_single16(ctx->st, ctx->gen_tab->table, (const uint32_t *)dsc, (JacRaw *)dres, n);   // 16 table additions per scalar
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, n);
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, n * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, n * 64}});
 }
 
 /* ---- two-party prover: one party's local arithmetic (src/r1cs_mpc/ of the reference; include/bpgpu.h, k_mpc.hip).  A session of nb
@@ -3157,8 +3059,8 @@ int bpgpu_mpc_prover_polys_mask(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_cir
   void *dz, *dzp, *dm, *dchi = nullptr;
   const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);
   int rc;
-  if ((rc = ws_get(ctx, 0, nb * 32, &dz)) || (rc = ws_get(ctx, 6, nb * qz * 9 * 4, &dzp)) || (rc = ws_get(ctx, 23, nmask * 32, &dm)) ||
-      (c->nchi && (rc = ws_get(ctx, 21, nb * c->nchi * 32, &dchi))))
+  if ((rc = ws_get(ctx, WS_ARG0, nb * 32, &dz)) || (rc = ws_get(ctx, WS_ZPOW, nb * qz * 9 * 4, &dzp)) || (rc = ws_get(ctx, WS_MSM2, nmask * 32, &dm)) ||
+      (c->nchi && (rc = ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi))))
     return fail(rc);
   const std::vector<uint8_t> y3 = bcast3(y, nb);
   if ((rc = flag_reset(ctx)) || (rc = h2d(ctx, s->y, y3.data(), NB * 32)) || (rc = h2d(ctx, dz, z, nb * 32)) ||
@@ -3195,10 +3097,10 @@ int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *s, const uint8_t
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t NB = s->nb, nb = NB / 3, n = s->n, nop = nb * 6 * 2 * n;
   void *dop, *dsc, *dres, *dout;
-  CK(ws_get(ctx, 23, nop * 32, &dop));
-  CK(ws_get(ctx, 0, NB * (5 + 6 + 10) * 32, &dsc));
-  CK(ws_get(ctx, 4, NB * 5 * sizeof(JacRaw), &dres));
-  CK(ws_get(ctx, 5, NB * 5 * 64, &dout));
+  CK(ws_get(ctx, WS_MSM2, nop * 32, &dop));
+  CK(ws_get(ctx, WS_ARG0, NB * (5 + 6 + 10) * 32, &dsc));
+  CK(ws_get(ctx, WS_ARG4, NB * 5 * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG5, NB * 5 * 64, &dout));
   Words8 *dtb = (Words8 *)dsc, *dt = dtb + NB * 5, *rows = dt + NB * 6;
   CK(flag_reset(ctx));
   CK(h2d(ctx, dop, opened, nop * 32));
@@ -3212,14 +3114,7 @@ int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *s, const uint8_t
   jac_to_boundary(ctx->st, (const JacRaw *)dres, (Words8 *)dout, NB * 5);
   scalars_to_ark(ctx->st, dt, dt, NB * 6, ctx->d_flag);
   span.close();
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, t_coeffs, dt, NB * 6 * 32));
-  CK(d2h(ctx, T, dout, NB * 5 * 64));
-  if (s->m) CK(d2h(ctx, wV, s->wv, nb * s->m * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  CK(checked_download(ctx, {{t_coeffs, dt, NB * 6 * 32}, {T, dout, NB * 5 * 64}, {wV, s->wv, nb * s->m * 32}}));
   s->finished = true;
   return BPGPU_OK;
 }
@@ -3239,7 +3134,7 @@ int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *triples, uin
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t nb = s->nb / 3, h = s->n / 2, ntrip = nb * 2 * 9 * h, nmask = nb * 2 * 6 * h;
   void *dm;
-  CK(ws_get(ctx, 23, nmask * 32, &dm));
+  CK(ws_get(ctx, WS_MSM2, nmask * 32, &dm));
   CK(flag_reset(ctx));
   CK(h2d(ctx, s->trip, triples, ntrip * 32));
   ProfSpan span(ctx, 20, ctx->st);
@@ -3247,12 +3142,7 @@ int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *triples, uin
   mpc_ipp_mask(ctx->st, nb, h, s->a[s->cur], s->b[s->cur], s->trip, (Words8 *)dm);
   scalars_to_ark(ctx->st, (const Words8 *)dm, (Words8 *)dm, nmask, ctx->d_flag);
   span.close();
-  CK(launch_ok(ctx));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, masked, dm, nmask * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  CK(checked_download(ctx, {{masked, dm, nmask * 32}}));
   s->masked = true;
   return BPGPU_OK;
 }
@@ -3263,7 +3153,7 @@ int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *opened, uin
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t NB = s->nb, nb = NB / 3, h = s->n / 2, nop = nb * 2 * 2 * h;
   void *dop;
-  CK(ws_get(ctx, 23, nop * 32, &dop));
+  CK(ws_get(ctx, WS_MSM2, nop * 32, &dop));
   CK(flag_reset(ctx));
   CK(h2d(ctx, dop, opened, nop * 32));
   scalars_from_ark(ctx->st, (const Words8 *)dop, (Words8 *)dop, nop, ctx->d_flag);
