@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -24,7 +25,9 @@ struct Slot { void *p = nullptr; size_t cap = 0; };
 // a slot that one of its callers still holds.
 enum WsSlot : int {
   // an entry point's operands, results and small scratch (host staging, a lane's batch); the cores below an entry point take the
-  // ones it leaves free (msm_batch_dev_locked: 2-4 under msm_batch_locked's 0, 1, 5; verify_wire_locked: 0-2 under the host form's 3-5)
+  // ones it leaves free (msm_batch_dev_locked: 2-4 under msm_batch_locked's 0, 1, 5; verify_wire_locked: 0-2 under the host form's 3-5;
+  // session_polys_begin: 0 for z, besides WS_CHI).  The helpers of the variable-base MSMs and of the polynomial build take none of
+  // these: msm_tail WS_PIP or WS_STRAUS, zpow_build WS_ZPOW.
   WS_ARG0, WS_ARG1, WS_ARG2, WS_ARG3, WS_ARG4, WS_ARG5,
   WS_ZPOW,          // z-power tables: flatten, prover polynomials, the verifier's scalar assembly
   WS_VPTS,          // verifier: converted proof points
@@ -209,6 +212,18 @@ static void pool_release(bpgpu_ctx *ctx, void *p) {
     ctx->pool.erase(ctx->pool.begin() + (long)largest);
   }
 }
+// the buffers of a session under construction, one after the other: the first failure sticks, and the session's owner gives back
+// what was taken (slot: the address of a device pointer of the session)
+struct PoolTake {
+  bpgpu_ctx *ctx;
+  bool ok = true;
+  template <class T> void operator()(T **slot, size_t bytes) { ok = ok && pool_alloc(ctx, (void **)slot, bytes); }
+};
+// No exception crosses the C ABI: an entry point that stages on the host (std::vector) runs its body in here, and an allocation
+// that fails is BPGPU_E_OOM.
+template <class Body> static int noexcept_abi(Body body) {
+  try { return body(); } catch (const std::bad_alloc &) { return BPGPU_E_OOM; }
+}
 static int ws_get(bpgpu_ctx *ctx, WsSlot slot, size_t bytes, void **out) {
   Slot &s = ctx->ws[slot];
   if (bytes < 256) bytes = 256;
@@ -229,6 +244,7 @@ static int flag_read(bpgpu_ctx *ctx, int *v) {
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
   return BPGPU_OK;
 }
+// (n == 0 copies nothing and touches neither pointer: the upload / download lists below pass an absent optional operand that way)
 static int h2d(bpgpu_ctx *ctx, void *d, const void *h, size_t n) {
   if (n) HIPCK(ctx, hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, ctx->st));
   return BPGPU_OK;
@@ -238,16 +254,42 @@ static int d2h(bpgpu_ctx *ctx, void *h, const void *d, size_t n) {
   return BPGPU_OK;
 }
 static int launch_ok(bpgpu_ctx *ctx) { HIPCK(ctx, hipGetLastError()); return BPGPU_OK; }
-// the end of an entry point whose launches validate into ctx->d_flag: the launch check, the flag (a host-side wait), BPGPU_E_ARG
-// before anything is downloaded when it is raised, then the downloads and the wait for them
-struct D2H { void *host; const void *dev; size_t bytes; };
-static int checked_download(bpgpu_ctx *ctx, std::initializer_list<D2H> outs) {
+// the head of an entry point whose launches validate into ctx->d_flag: the flag cleared, then the operands' uploads in order
+struct H2D { void *dev; const void *host; size_t bytes; };
+static int upload_inputs(bpgpu_ctx *ctx, std::initializer_list<H2D> ins) {
+  CK(flag_reset(ctx));
+  for (const H2D &i : ins) CK(h2d(ctx, i.dev, i.host, i.bytes));
+  return BPGPU_OK;
+}
+// the end of the uploads of an entry point whose launches validate into ctx->d_flag: the launch check, the flag (a host-side wait),
+// BPGPU_E_ARG when it is raised
+static int checked_inputs(bpgpu_ctx *ctx) {
   CK(launch_ok(ctx));
   int bad = 0;
   CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
+  return bad ? BPGPU_E_ARG : BPGPU_OK;
+}
+// the same at the end of an entry point, before anything is downloaded; then the downloads and the wait for them
+struct D2H { void *host; const void *dev; size_t bytes; };
+static int checked_download(bpgpu_ctx *ctx, std::initializer_list<D2H> outs) {
+  CK(checked_inputs(ctx));
   for (const D2H &o : outs) CK(d2h(ctx, o.host, o.dev, o.bytes));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+}
+// rounds x count pairs of points (64 B each: the L, R of IPP rounds, a session's folded G', H'), interleaved and round-major in HBM, into
+// two host arrays, item-major: out0[i][r], out1[i][r].  `also` are downloads that ride on the same wait.
+static int download_pairs(bpgpu_ctx *ctx, const void *dev, size_t count, size_t rounds, uint8_t *out0, uint8_t *out1,
+                          std::initializer_list<D2H> also = {}) {
+  std::vector<uint8_t> tmp(rounds * count * 128);
+  CK(d2h(ctx, tmp.data(), dev, tmp.size()));
+  for (const D2H &o : also) CK(d2h(ctx, o.host, o.dev, o.bytes));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  for (size_t i = 0; i < count; i++)
+    for (size_t r = 0; r < rounds; r++) {
+      memcpy(out0 + (i * rounds + r) * 64, &tmp[(r * count + i) * 128], 64);
+      memcpy(out1 + (i * rounds + r) * 64, &tmp[(r * count + i) * 128 + 64], 64);
+    }
   return BPGPU_OK;
 }
 // One launch that brings a batch's three operand arrays from page-locked host memory into the lane's buffers: wide, coalesced reads
@@ -698,6 +740,37 @@ static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, co
   return BPGPU_OK;
 }
 /* ---------------------------------------------------------------- MSM (general points) */
+// 32-bit bucket ids, sorted entries (term index | sign bit) and offsets: what the bucket method cannot address is BPGPU_E_LEN
+static bool pippenger_addressable(size_t nb, size_t n) {
+  const int c = pippenger_window(n);
+  const size_t cW = 252 / (size_t)c + 1, chalf = (size_t)1 << (c - 1);
+  return n < ((size_t)1 << 31) / nb && nb * cW * chalf < ((size_t)1 << 31) && nb * n * cW < ((size_t)1 << 32);
+}
+// one Straus lane per term of dense instances: term i reads pts[i], sc[i]
+static StrausArgs straus_dense(const AffDev *pts, const uint32_t *sc) {
+  StrausArgs a{};
+  a.pts[0] = pts; a.pt_stride[0] = 1;
+  a.sc[0] = sc; a.sc_stride[0] = 8;
+  return a;
+}
+// The common end of the variable-base routes, nb validated instances of n terms -> dsum[nb].  From pip_min terms on: the bucket method,
+// one batched launch chain over dense instances (pts, sc: nb x n; pippenger() is the same chain for one instance).  Below: one Straus
+// lane per term, addressed by `lanes` (results in dres, nb x n), and a tree sum per instance.  Takes WS_PIP or WS_STRAUS.
+static int msm_tail(bpgpu_ctx *ctx, size_t nb, size_t n, size_t pip_min, const AffDev *pts, const uint32_t *sc, const StrausArgs &lanes,
+                    JacRaw *dres, JacRaw *dsum) {
+  if (n >= pip_min) {
+    const int c = pippenger_window(n);
+    void *dpip;
+    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nb, n, c), &dpip));
+    pippenger_batch(ctx->st, pts, sc, nb, n, c, dsum, 1, dpip);
+  } else {
+    void *dstr;
+    CK(straus_ws(ctx, 1, nb * n, &dstr));
+    straus(ctx->st, 1, lanes, dres, nb * n, dstr);
+    segmented_sum(ctx->st, dres, dsum, nb, n);
+  }
+  return BPGPU_OK;
+}
 // device-resident core: dsc / dxy hold the boundary encodings in HBM, dout receives nb x 64 B; asynchronous on ctx->st
 static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, const void *dxy, void *dout) {
   size_t tot = nb * n;
@@ -706,11 +779,7 @@ static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void 
   CK(ws_get(ctx, WS_ARG3, tot * sizeof(JacRaw), &dres));
   CK(ws_get(ctx, WS_ARG4, nb * sizeof(JacRaw), &dsum));
   const size_t pip_min = (size_t)ctx->opt[BPGPU_OPT_PIPPENGER_MIN];
-  if (n >= pip_min) {
-    // 32-bit bucket ids, sorted entries (term index | sign bit) and offsets: reject what they cannot address
-    const size_t cW = 252 / (size_t)pippenger_window(n) + 1, chalf = (size_t)1 << (pippenger_window(n) - 1);
-    if (n >= ((size_t)1 << 31) / nb || nb * cW * chalf >= ((size_t)1 << 31) || tot * cW >= ((size_t)1 << 32)) return BPGPU_E_LEN;
-  }
+  if (n >= pip_min && !pippenger_addressable(nb, n)) return BPGPU_E_LEN;
   {
     bool done = false;
     scalars_check(ctx->st, (const Words8 *)dsc, tot, ctx->d_flag);
@@ -732,25 +801,8 @@ static int msm_batch_dev_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const void 
   }
   scalars_check(ctx->st, (const Words8 *)dsc, tot, ctx->d_flag);
   points_from_boundary(ctx->st, (const Words8 *)dxy, (AffDev *)dpts, tot, ctx->d_flag);
-  if (n >= pip_min) {   // bucket method
-    int c = pippenger_window(n);
-    void *dpip;
-    if (nb == 1) {
-      CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes(n, c), &dpip));
-      pippenger(ctx->st, (AffDev *)dpts, (const uint32_t *)dsc, n, c, (JacRaw *)dsum, dpip);
-    } else {
-      CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nb, n, c), &dpip));
-      pippenger_batch(ctx->st, (AffDev *)dpts, (const uint32_t *)dsc, nb, n, c, (JacRaw *)dsum, 1, dpip);
-    }
-  } else {
-    StrausArgs a{};
-    a.pts[0] = (AffDev *)dpts; a.pt_stride[0] = 1;
-    a.sc[0] = (const uint32_t *)dsc; a.sc_stride[0] = 8;
-    void *dstr;
-    CK(straus_ws(ctx, 1, tot, &dstr));
-    straus(ctx->st, 1, a, (JacRaw *)dres, tot, dstr);
-    segmented_sum(ctx->st, (JacRaw *)dres, (JacRaw *)dsum, nb, n);
-  }
+  CK(msm_tail(ctx, nb, n, pip_min, (const AffDev *)dpts, (const uint32_t *)dsc, straus_dense((const AffDev *)dpts, (const uint32_t *)dsc),
+              (JacRaw *)dres, (JacRaw *)dsum));
   jac_to_boundary(ctx->st, (JacRaw *)dsum, (Words8 *)dout, nb);
   return launch_ok(ctx);
 }
@@ -768,12 +820,7 @@ static int msm_batch_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *
   CK(h2d(ctx, dsc, scalars, tot * 32));
   CK(h2d(ctx, dxy, points, tot * 64));
   CK(msm_batch_dev_locked(ctx, nb, n, dsc, dxy, dout));
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;
-  CK(d2h(ctx, out, dout, nb * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
+  return checked_download(ctx, {{out, dout, nb * 64}});
 }
 int bpgpu_msm_batch_dev(bpgpu_ctx *ctx, size_t nb, size_t n, const void *scalars_dev, const void *points_dev, void *out_dev) {
   if (!ctx || (nb && !out_dev) || (nb && n && (!scalars_dev || !points_dev))) return BPGPU_E_ARG;
@@ -796,7 +843,6 @@ int bpgpu_msm_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *scalars,
   return msm_batch_locked(ctx, nb, n, scalars, points, out);
 }
 
-/* nsets MSMs over ONE point vector (the share / MAC / public-modifier MSMs of msm_authenticated_iter) */
 /* ---------------------------------------------------------------- arkworks in-memory forms (k_ark.hip) */
 // sum_i scalars[i] * pts[i] for validated device operands (plain canonical scalars, Montgomery affine points) -> one JacRaw
 static int msm_core_locked(bpgpu_ctx *ctx, size_t n, const uint32_t *dsc, const AffDev *dpts, JacRaw *dsum) {
@@ -804,29 +850,18 @@ static int msm_core_locked(bpgpu_ctx *ctx, size_t n, const uint32_t *dsc, const 
   bool done = false;
   CK(msm_wp_batch(ctx, 1, n, dsc, dpts, true, dsum, &done));
   if (done) return BPGPU_OK;
-  void *dpip;
   const bool pip2_single = ctx->opt[BPGPU_OPT_MSM_PIP2_SINGLE] != 0;
   if (pip2_single && n >= pip_min && pippenger2_supported(n)) {
     const int c2 = pippenger2_window(n);
+    void *dpip;
     CK(ws_get(ctx, WS_PIP, pippenger2_scratch_bytes(n, c2), &dpip));
     pippenger2(ctx->st, dpts, dsc, n, c2, dsum, dpip, ctx->d_flag);
-  } else if (n >= pip_min) {
-    const int c = pippenger_window(n);
-    const size_t cW = 252 / (size_t)c + 1;
-    if (n >= ((size_t)1 << 31) || cW * ((size_t)1 << (c - 1)) >= ((size_t)1 << 31) || n * cW >= ((size_t)1 << 32)) return BPGPU_E_LEN;
-    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes(n, c), &dpip));
-    pippenger(ctx->st, dpts, dsc, n, c, dsum, dpip);
-  } else {
-    void *dres, *dstr;
-    CK(ws_get(ctx, WS_STRAUS, straus_scratch_bytes(1, n), &dstr));
-    CK(ws_get(ctx, WS_MSM, n * sizeof(JacRaw), &dres));
-    StrausArgs sa{};
-    sa.pts[0] = dpts; sa.pt_stride[0] = 1;
-    sa.sc[0] = dsc; sa.sc_stride[0] = 8;
-    straus(ctx->st, 1, sa, (JacRaw *)dres, n, dstr);
-    segmented_sum(ctx->st, (JacRaw *)dres, dsum, 1, n);
+    return BPGPU_OK;
   }
-  return BPGPU_OK;
+  if (n >= pip_min && !pippenger_addressable(1, n)) return BPGPU_E_LEN;
+  void *dres = nullptr;   // the Straus lanes' results: WS_MSM (the caller holds WS_ARG0..5)
+  if (n < pip_min) CK(ws_get(ctx, WS_MSM, n * sizeof(JacRaw), &dres));
+  return msm_tail(ctx, 1, n, pip_min, dpts, dsc, straus_dense(dpts, dsc), (JacRaw *)dres, dsum);
 }
 int bpgpu_msm_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, const uint8_t *points_jac_mont, size_t n, uint8_t out_jac_mont[96]) {
   if (!ctx || !out_jac_mont || (n && (!scalars_mont || !points_jac_mont))) return BPGPU_E_ARG;
@@ -912,6 +947,7 @@ int bpgpu_points_sum(bpgpu_ctx *ctx, const uint8_t *points, size_t n, uint8_t ou
   points_sum(ctx->st, (const Words8 *)dxy, n, (Words8 *)dout, ctx->d_flag);
   return checked_download(ctx, {{out, dout, 64}});
 }
+/* nsets MSMs over ONE point vector (the share / MAC / public-modifier MSMs of msm_authenticated_iter) */
 int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scalars, const uint8_t *points,
                      uint8_t *out) {
   if (!ctx || (nsets && !out) || (nsets && n && (!scalars || !points))) return BPGPU_E_ARG;
@@ -941,23 +977,14 @@ int bpgpu_msm_shared(bpgpu_ctx *ctx, size_t nsets, size_t n, const uint8_t *scal
     gather_points(ctx->st, (AffDev *)dpts, 0, n, nsets, (AffDev *)drep, n);
     CK(msm_wp_batch(ctx, nsets, n, dsc, drep, true, (JacRaw *)dsum, &wp_done));
   }
-  if (wp_done) {
-  } else if (bucket) {   // one batched bucket-method launch; the instances read replicas of the converted points
-    AffDev *rep = (AffDev *)dpts + n;
-    gather_points(ctx->st, (AffDev *)dpts, 0, n, nsets, rep, n);
-    int c = pippenger_window(n);
-    void *dpip;
-    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nsets, n, c), &dpip));
-    pippenger_batch(ctx->st, rep, (const uint32_t *)dsc, nsets, n, c, (JacRaw *)dsum, 1, dpip);
-  } else {        // one Straus lane per (set, term), the sets share the point array
-    StrausArgs a{};
-    a.pts[0] = (AffDev *)dpts; a.pt_stride[0] = 1; a.pt_outer[0] = 0;
-    a.sc[0] = (uint32_t *)dsc; a.sc_stride[0] = 8; a.sc_outer[0] = n * 8;
+  if (!wp_done) {
+    // the bucket method's instances read replicas of the converted points; the Straus lanes (set, term) share the one point array
+    AffDev *rep = (AffDev *)dpts + n;   // (behind the n converted points; there, and read, only when bucket)
+    if (bucket) gather_points(ctx->st, (AffDev *)dpts, 0, n, nsets, rep, n);
+    StrausArgs a = straus_dense((const AffDev *)dpts, (const uint32_t *)dsc);
+    a.pt_outer[0] = 0; a.sc_outer[0] = n * 8;
     a.inner = n;
-    void *dstr;
-    CK(straus_ws(ctx, 1, tot, &dstr));
-    straus(ctx->st, 1, a, (JacRaw *)dres, tot, dstr);
-    segmented_sum(ctx->st, (JacRaw *)dres, (JacRaw *)dsum, nsets, n);
+    CK(msm_tail(ctx, nsets, n, pip_min, rep, (const uint32_t *)dsc, a, (JacRaw *)dres, (JacRaw *)dsum));
   }
   jac_to_boundary(ctx->st, (JacRaw *)dsum, (Words8 *)dout, nsets);
   return checked_download(ctx, {{out, dout, nsets * 64}});
@@ -2298,6 +2325,28 @@ static void ipp_free_all(bpgpu_ctx *ctx, bpgpu_ipp *s) {
   for (void *p : all) pool_release(ctx, p);
   delete s;
 }
+// a session under construction: freed on the way out of its entry point (under the lock that entry point holds) unless it is
+// released to the caller
+namespace { struct IppFree { bpgpu_ctx *ctx; void operator()(bpgpu_ipp *s) const { ipp_free_all(ctx, s); } }; }
+using IppOwner = std::unique_ptr<bpgpu_ipp, IppFree>;
+// A resident-generator session of nb proofs of length n (planes 3: nb counts the virtual provers of an authenticated one): its fields,
+// this rank's shard, its buffers.  `own` holds whatever was allocated, also on failure.
+static int ipp_gens_session(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, int planes, IppOwner &own) {
+  bpgpu_ipp *s = new (std::nothrow) bpgpu_ipp();
+  if (!s) return BPGPU_E_OOM;
+  own.reset(s);
+  s->nb = nb; s->n0 = s->n = n; s->gens = g; s->planes = planes;
+  if (ctx->shard_world > 1) { shard_bounds(n, ctx->shard_rank, ctx->shard_world, &s->slo, &s->shi); s->with_q = ctx->shard_rank == 0; }
+  const size_t tot = nb * n, half = nb * (n > 1 ? n / 2 : 1);
+  PoolTake M{ctx};
+  M(&s->a[0], tot * 32); M(&s->b[0], tot * 32); M(&s->a[1], half * 32); M(&s->b[1], half * 32);
+  M(&s->cG, tot * 32); M(&s->cH, tot * 32); M(&s->w, nb * 32);
+  M(&s->cLR, nb * 2 * 32); M(&s->uu, nb * 2 * 32);
+  M(&s->sums, nb * 2 * sizeof(JacRaw)); M(&s->out_xy, nb * 2 * 64);
+  M(&s->msc, nb * 2 * (2 + 2 * n) * 32);
+  if (planes != 1) M(&s->trip, (nb / 3) * 2 * 9 * (n / 2 ? n / 2 : 1) * 32);   // the first round's triples, the largest
+  return M.ok ? BPGPU_OK : BPGPU_E_OOM;
+}
 int bpgpu_ipp_begin(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *Q, const uint8_t *G_factors,
                     const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int shared_gens, const uint8_t *a,
                     const uint8_t *b, bpgpu_ipp **out) {
@@ -2312,10 +2361,7 @@ int bpgpu_ipp_begin(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *Q, const
   // n = 1024, 32 KB at c = 4 above: 2 GB at n = 2^15) and their build grows with n, so the route is bounded: n <=
   // BPGPU_OPT_IPP_TABLE_MAX_N (default 2^16), tables + staging within half of the free device memory, and a table build that
   // runs out of memory falls back to the literal schedule, whose footprint is O(n).
-  int64_t literal = 0, table_max_n = 0;
-  (void)bpgpu_get_option(ctx, BPGPU_OPT_IPP_LITERAL, &literal);
-  (void)bpgpu_get_option(ctx, BPGPU_OPT_IPP_TABLE_MAX_N, &table_max_n);
-  if (nb == 1 && n >= 2 && !literal && n <= (size_t)table_max_n) {
+  if (nb == 1 && n >= 2) {
     const int c = n <= 1024 ? 8 : 4;
     const size_t per_gen = (252 / c + 1) * ((size_t)1 << (c - 1)), ng = 2 + 2 * n;
     size_t stage_gens = ((size_t)8 << 30) / ((per_gen + 252 / c + 1) * sizeof(JacRaw));
@@ -2324,7 +2370,8 @@ int bpgpu_ipp_begin(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *Q, const
     size_t free_b = 0, total_b = 0;
     bool fits = false;
     { std::lock_guard<std::mutex> lk(ctx->mu);
-      fits = hipSetDevice(ctx->device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2; }
+      fits = !ctx->opt[BPGPU_OPT_IPP_LITERAL] && n <= (size_t)ctx->opt[BPGPU_OPT_IPP_TABLE_MAX_N] &&
+             hipSetDevice(ctx->device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2; }
     if (fits) {
       bpgpu_gens *g = nullptr;
       int rc = bpgpu_gens_create(ctx, G, H, n, Q, Q, c, &g);
@@ -2339,48 +2386,41 @@ int bpgpu_ipp_begin(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *Q, const
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  bpgpu_ipp *s = new (std::nothrow) bpgpu_ipp();
+  IppOwner own(new (std::nothrow) bpgpu_ipp(), IppFree{ctx});
+  bpgpu_ipp *s = own.get();
   if (!s) return BPGPU_E_OOM;
   s->nb = nb; s->n0 = s->n = n; s->shared_gens = shared_gens != 0;
   size_t tot = nb * n, gtot = shared_gens ? n : tot, half = nb * (n > 1 ? n / 2 : 1);
-  void *stage = nullptr;
-  bool okk = true;
-  auto M = [&](void **p, size_t bytes) { if (okk && !pool_alloc(ctx, p, bytes)) okk = false; };
-  M((void **)&s->a[0], tot * 32); M((void **)&s->b[0], tot * 32); M((void **)&s->a[1], half * 32); M((void **)&s->b[1], half * 32);
-  M((void **)&s->G[0], (gtot > half ? gtot : half) * sizeof(AffDev)); M((void **)&s->H[0], (gtot > half ? gtot : half) * sizeof(AffDev));
-  M((void **)&s->G[1], half * sizeof(AffDev)); M((void **)&s->H[1], half * sizeof(AffDev));
-  M((void **)&s->Q, nb * sizeof(AffDev)); M((void **)&s->Gf, tot * 32); M((void **)&s->Hf, tot * 32);
-  M((void **)&s->t1, half * 32); M((void **)&s->t2, half * 32); M((void **)&s->t3, half * 32); M((void **)&s->t4, half * 32);
-  M((void **)&s->cLR, nb * 2 * 32); M((void **)&s->uu, nb * 2 * 32);
-  M((void **)&s->res, nb * 2 * (n + 1) * sizeof(JacRaw)); M((void **)&s->sums, nb * 2 * sizeof(JacRaw));
-  M((void **)&s->out_xy, nb * 2 * 64);
-  M((void **)&s->mpts, nb * 2 * (n + 1) * sizeof(AffDev)); M((void **)&s->msc, nb * 2 * (n + 1) * 32);
-  M(&stage, (2 * gtot + nb) * 64);
-  if (!okk) { pool_release(ctx, stage); ipp_free_all(ctx, s); return BPGPU_E_OOM; }
-  int rc = BPGPU_OK;
-  do {
-    if ((rc = flag_reset(ctx))) break;
-    if ((rc = h2d(ctx, s->a[0], a, tot * 32)) || (rc = h2d(ctx, s->b[0], b, tot * 32)) ||
-        (rc = h2d(ctx, s->Gf, G_factors, tot * 32)) || (rc = h2d(ctx, s->Hf, H_factors, tot * 32))) break;
-    uint8_t *st8 = (uint8_t *)stage;
-    if ((rc = h2d(ctx, st8, G, gtot * 64)) || (rc = h2d(ctx, st8 + gtot * 64, H, gtot * 64)) ||
-        (rc = h2d(ctx, st8 + 2 * gtot * 64, Q, nb * 64))) break;
-    scalars_check(ctx->st, s->a[0], tot, ctx->d_flag);
-    scalars_check(ctx->st, s->b[0], tot, ctx->d_flag);
-    scalars_check(ctx->st, s->Gf, tot, ctx->d_flag);
-    scalars_check(ctx->st, s->Hf, tot, ctx->d_flag);
-    points_from_boundary(ctx->st, (Words8 *)st8, s->G[0], gtot, ctx->d_flag);
-    points_from_boundary(ctx->st, (Words8 *)(st8 + gtot * 64), s->H[0], gtot, ctx->d_flag);
-    points_from_boundary(ctx->st, (Words8 *)(st8 + 2 * gtot * 64), s->Q, nb, ctx->d_flag);
-    if ((rc = launch_ok(ctx))) break;
-    int bad = 0;
-    if ((rc = flag_read(ctx, &bad))) break;
-    if (bad) rc = BPGPU_E_ARG;
-  } while (0);
-  (void)hipStreamSynchronize(ctx->st);   // the staging buffer goes back to the pool: its conversion launches have completed
-  pool_release(ctx, stage);
-  if (rc) { ipp_free_all(ctx, s); return rc; }
-  *out = s;
+  // the points' boundary form; the staging buffer goes back to the pool once its conversion launches have completed
+  struct Stage {
+    bpgpu_ctx *ctx;
+    uint8_t *p;
+    ~Stage() { (void)hipStreamSynchronize(ctx->st); pool_release(ctx, p); }
+  } stage{ctx, nullptr};
+  PoolTake M{ctx};
+  M(&s->a[0], tot * 32); M(&s->b[0], tot * 32); M(&s->a[1], half * 32); M(&s->b[1], half * 32);
+  M(&s->G[0], (gtot > half ? gtot : half) * sizeof(AffDev)); M(&s->H[0], (gtot > half ? gtot : half) * sizeof(AffDev));
+  M(&s->G[1], half * sizeof(AffDev)); M(&s->H[1], half * sizeof(AffDev));
+  M(&s->Q, nb * sizeof(AffDev)); M(&s->Gf, tot * 32); M(&s->Hf, tot * 32);
+  M(&s->t1, half * 32); M(&s->t2, half * 32); M(&s->t3, half * 32); M(&s->t4, half * 32);
+  M(&s->cLR, nb * 2 * 32); M(&s->uu, nb * 2 * 32);
+  M(&s->res, nb * 2 * (n + 1) * sizeof(JacRaw)); M(&s->sums, nb * 2 * sizeof(JacRaw));
+  M(&s->out_xy, nb * 2 * 64);
+  M(&s->mpts, nb * 2 * (n + 1) * sizeof(AffDev)); M(&s->msc, nb * 2 * (n + 1) * 32);
+  M(&stage.p, (2 * gtot + nb) * 64);
+  if (!M.ok) return BPGPU_E_OOM;
+  uint8_t *dG = stage.p, *dH = dG + gtot * 64, *dQ = dH + gtot * 64;
+  CK(upload_inputs(ctx, {{s->a[0], a, tot * 32}, {s->b[0], b, tot * 32}, {s->Gf, G_factors, tot * 32}, {s->Hf, H_factors, tot * 32},
+                         {dG, G, gtot * 64}, {dH, H, gtot * 64}, {dQ, Q, nb * 64}}));
+  scalars_check(ctx->st, s->a[0], tot, ctx->d_flag);
+  scalars_check(ctx->st, s->b[0], tot, ctx->d_flag);
+  scalars_check(ctx->st, s->Gf, tot, ctx->d_flag);
+  scalars_check(ctx->st, s->Hf, tot, ctx->d_flag);
+  points_from_boundary(ctx->st, (Words8 *)dG, s->G[0], gtot, ctx->d_flag);
+  points_from_boundary(ctx->st, (Words8 *)dH, s->H[0], gtot, ctx->d_flag);
+  points_from_boundary(ctx->st, (Words8 *)dQ, s->Q, nb, ctx->d_flag);
+  CK(checked_inputs(ctx));
+  *out = own.release();
   return BPGPU_OK;
 }
 int bpgpu_ipp_begin_gens(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, const uint8_t *w,
@@ -2392,37 +2432,19 @@ int bpgpu_ipp_begin_gens(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t 
   *out = nullptr;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  bpgpu_ipp *s = new (std::nothrow) bpgpu_ipp();
-  if (!s) return BPGPU_E_OOM;
-  s->nb = nb; s->n0 = s->n = n; s->gens = g;
-  if (ctx->shard_world > 1) { shard_bounds(n, ctx->shard_rank, ctx->shard_world, &s->slo, &s->shi); s->with_q = ctx->shard_rank == 0; }
-  size_t tot = nb * n, half = nb * (n > 1 ? n / 2 : 1);
-  bool okk = true;
-  auto M = [&](void **p, size_t bytes) { if (okk && !pool_alloc(ctx, p, bytes)) okk = false; };
-  M((void **)&s->a[0], tot * 32); M((void **)&s->b[0], tot * 32); M((void **)&s->a[1], half * 32); M((void **)&s->b[1], half * 32);
-  M((void **)&s->cG, tot * 32); M((void **)&s->cH, tot * 32); M((void **)&s->w, nb * 32);
-  M((void **)&s->cLR, nb * 2 * 32); M((void **)&s->uu, nb * 2 * 32);
-  M((void **)&s->sums, nb * 2 * sizeof(JacRaw)); M((void **)&s->out_xy, nb * 2 * 64);
-  M((void **)&s->msc, nb * 2 * (2 + 2 * n) * 32);
-  if (!okk) { ipp_free_all(ctx, s); return BPGPU_E_OOM; }
-  int rc = BPGPU_OK;
-  do {
-    if ((rc = flag_reset(ctx))) break;
-    if ((rc = h2d(ctx, s->a[0], a, tot * 32)) || (rc = h2d(ctx, s->b[0], b, tot * 32)) ||
-        (rc = h2d(ctx, s->cG, G_factors, tot * 32)) || (rc = h2d(ctx, s->cH, H_factors, tot * 32)) ||
-        (rc = h2d(ctx, s->w, w, nb * 32))) break;
-    scalars_check(ctx->st, s->a[0], tot, ctx->d_flag);
-    scalars_check(ctx->st, s->b[0], tot, ctx->d_flag);
-    scalars_check(ctx->st, s->cG, tot, ctx->d_flag);
-    scalars_check(ctx->st, s->cH, tot, ctx->d_flag);
-    scalars_check(ctx->st, s->w, nb, ctx->d_flag);
-    if ((rc = launch_ok(ctx))) break;
-    int bad = 0;
-    if ((rc = flag_read(ctx, &bad))) break;
-    if (bad) rc = BPGPU_E_ARG;
-  } while (0);
-  if (rc) { ipp_free_all(ctx, s); return rc; }
-  *out = s;
+  IppOwner own(nullptr, IppFree{ctx});
+  CK(ipp_gens_session(ctx, g, nb, n, 1, own));
+  bpgpu_ipp *s = own.get();
+  const size_t tot = nb * n;
+  CK(upload_inputs(ctx, {{s->a[0], a, tot * 32}, {s->b[0], b, tot * 32}, {s->cG, G_factors, tot * 32}, {s->cH, H_factors, tot * 32},
+                         {s->w, w, nb * 32}}));
+  scalars_check(ctx->st, s->a[0], tot, ctx->d_flag);
+  scalars_check(ctx->st, s->b[0], tot, ctx->d_flag);
+  scalars_check(ctx->st, s->cG, tot, ctx->d_flag);
+  scalars_check(ctx->st, s->cH, tot, ctx->d_flag);
+  scalars_check(ctx->st, s->w, nb, ctx->d_flag);
+  CK(checked_inputs(ctx));
+  *out = own.release();
   return BPGPU_OK;
 }
 void bpgpu_ipp_destroy(bpgpu_ctx *ctx, bpgpu_ipp *s) {
@@ -2463,8 +2485,6 @@ static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy, bool beav
   const AffDev *G = s->G[s->cur], *H = s->H[s->cur];
   const bool shared = s->first && s->shared_gens;
   const size_t gouter = shared ? 0 : n;
-  void *dstr;
-  CK(straus_ws(ctx, 1, nb * h, &dstr));
   sc_dot_batched(st, nb, h, a, n, b + h, n, s->cLR, 2);        // c_L = <a_L, b_R>
   sc_dot_batched(st, nb, h, a + h, n, b, n, s->cLR + 1, 2);    // c_R = <a_R, b_L>
   const Words8 *sLa = a, *sLb = b + h, *sRa = a + h, *sRb = b;
@@ -2487,36 +2507,21 @@ static int ipp_round_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *out_xy, bool beav
     gather_points(st, H + h, gouter, h, nb, s->mpts + seg + h, io);  gather_scalars(st, sRb, so, h, nb, s->msc + seg + h, io);
     gather_points(st, s->Q, 1, 1, nb, s->mpts + seg + 2 * h, io);    gather_scalars(st, s->cLR + 1, 2, 1, nb, s->msc + seg + 2 * h, io);
   }
-  if (seg >= pip_min) {   // bucket method, one batched launch for all instances
-    int cw = pippenger_window(seg);
-    void *dpip;
-    CK(ws_get(ctx, WS_PIP, pippenger_scratch_bytes_batch(nb * 2, seg, cw), &dpip));
-    pippenger_batch(st, s->mpts, (const uint32_t *)s->msc, nb * 2, seg, cw, s->sums, 1, dpip);
-  } else {                // short rounds: one Straus lane per term (a single launch), then a tree sum per instance
-    StrausArgs x{};
-    x.pts[0] = s->mpts; x.pt_stride[0] = 1;
-    x.sc[0] = (const uint32_t *)s->msc; x.sc_stride[0] = 8;
-    CK(straus_ws(ctx, 1, nb * 2 * seg, &dstr));
-    straus(st, 1, x, s->res, nb * 2 * seg, dstr);
-    segmented_sum(st, s->res, s->sums, nb * 2, seg);
-  }
+  // long rounds: the bucket method, one batched launch chain for all instances; short ones: a Straus lane per term and a sum per instance
+  const uint32_t *msc = (const uint32_t *)s->msc;
+  CK(msm_tail(ctx, nb * 2, seg, pip_min, s->mpts, msc, straus_dense(s->mpts, msc), s->res, s->sums));
   jac_to_boundary(st, s->sums, out_xy, nb * 2);
   return launch_ok(ctx);
 }
-int bpgpu_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *L, uint8_t *R) try {
-  if (!ctx || !s || !L || !R || s->planes != 1) return BPGPU_E_ARG;   // (shares: c_L, c_R need Beaver triples, bpgpu_mpc_ipp_round)
-  if (s->n < 2) return BPGPU_E_LEN;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t nb = s->nb;
-  CK(ipp_round_dev(ctx, s, s->out_xy));
-  std::vector<uint8_t> tmp(nb * 128);
-  CK(d2h(ctx, tmp.data(), s->out_xy, nb * 128));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  for (size_t p = 0; p < nb; p++) { memcpy(L + 64 * p, &tmp[128 * p], 64); memcpy(R + 64 * p, &tmp[128 * p + 64], 64); }
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+int bpgpu_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *L, uint8_t *R) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !L || !R || s->planes != 1) return BPGPU_E_ARG;   // (shares: c_L, c_R need Beaver triples, bpgpu_mpc_ipp_round)
+    if (s->n < 2) return BPGPU_E_LEN;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    CK(ipp_round_dev(ctx, s, s->out_xy));
+    return download_pairs(ctx, s->out_xy, s->nb, 1, L, R);
+  });
 }
 /* fold_witness with the round's challenges -- inner_product_proof.rs:125-146 (first) / :183-184 */
 // device part of the fold: du / dui = the round's challenges and their inverses (nb each) already in HBM
@@ -2573,106 +2578,91 @@ static std::vector<uint8_t> bcast3(const uint8_t *src, size_t nproofs) {
   for (size_t v = 0; v < 3 * nproofs; v++) memcpy(&out[32 * v], src + 32 * (v / 3), 32);
   return out;
 }
-int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t *u_inv) try {
-  if (!ctx || !s || !u || !u_inv) return BPGPU_E_ARG;
-  if (s->n < 2) return BPGPU_E_LEN;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t nb = s->nb;
-  Words8 *du = s->uu, *dui = s->uu + nb;
-  CK(flag_reset(ctx));
-  std::vector<uint8_t> b3;
-  if (s->planes != 1) {   // authenticated session: one challenge per proof, broadcast to its three planes
-    if (s->masked) return BPGPU_E_ARG;     // a masked round has not been completed by bpgpu_mpc_ipp_round
-    b3 = bcast3(u, nb / 3);
-    const std::vector<uint8_t> bi = bcast3(u_inv, nb / 3);
-    b3.insert(b3.end(), bi.begin(), bi.end());
-    CK(h2d(ctx, du, b3.data(), 2 * nb * 32));   // (du, dui adjacent; flag_read below waits for the copy)
-  } else {
-    CK(h2d(ctx, du, u, nb * 32));
-    CK(h2d(ctx, dui, u_inv, nb * 32));
-  }
-  scalars_check(ctx->st, s->uu, 2 * nb, ctx->d_flag);
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;        // checked before the session state advances
-  return ipp_fold_dev(ctx, s, du, dui);
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t *u_inv) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !u || !u_inv) return BPGPU_E_ARG;
+    if (s->n < 2) return BPGPU_E_LEN;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = s->nb;
+    Words8 *du = s->uu, *dui = s->uu + nb;
+    CK(flag_reset(ctx));
+    std::vector<uint8_t> b3;
+    if (s->planes != 1) {   // authenticated session: one challenge per proof, broadcast to its three planes
+      if (s->masked) return BPGPU_E_ARG;     // a masked round has not been completed by bpgpu_mpc_ipp_round
+      b3 = bcast3(u, nb / 3);
+      const std::vector<uint8_t> bi = bcast3(u_inv, nb / 3);
+      b3.insert(b3.end(), bi.begin(), bi.end());
+      CK(h2d(ctx, du, b3.data(), 2 * nb * 32));   // (du, dui adjacent; the flag's read below waits for the copy)
+    } else {
+      CK(h2d(ctx, du, u, nb * 32));
+      CK(h2d(ctx, dui, u_inv, nb * 32));
+    }
+    scalars_check(ctx->st, s->uu, 2 * nb, ctx->d_flag);
+    CK(checked_inputs(ctx));            // before the session state advances
+    return ipp_fold_dev(ctx, s, du, dui);
+  });
 }
 /* InnerProductProof::create's whole round loop on the device (SURVEY 8f N1 applied to the prover): per round the
  * L, R MSMs, transcript.append_point("L"), ("R"), challenge_scalar("u") (inner_product_proof.rs:119-123,177-181)
  * with the keccak hash chain in a kernel, u^-1 and the fold -- no host round trip between rounds. */
 int bpgpu_ipp_run_fs(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *states_in, uint8_t *L_out, uint8_t *R_out,
-                     uint8_t *a_out, uint8_t *b_out, uint8_t *states_out) try {
-  if (!ctx || !s || !states_in || !a_out || !b_out || s->planes != 1) return BPGPU_E_ARG;
-  if (s->shi != (size_t)-1) return BPGPU_E_ARG;    // a sharded session's L, R are partial sums: its rounds need the ranks' exchange
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t nb = s->nb;
-  size_t k = 0;
-  for (size_t t = s->n; t > 1; t >>= 1) k++;
-  if (k && (!L_out || !R_out)) return BPGPU_E_ARG;
-  void *dstates, *dlr, *dzero;
-  CK(ws_get(ctx, WS_FS_STAGE, nb * 32, &dstates));
-  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
-  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
-  CK(h2d(ctx, dstates, states_in, nb * 32));
-  Words8 *du = s->uu, *dui = s->uu + nb;
-  ProfSpan span(ctx, 20, ctx->st);
-  for (size_t r = 0; r < k; r++) {
-    Words8 *lr = (Words8 *)dlr + r * nb * 4;             // 2 points x 2 Words8 per proof
-    if (s->gens) {   // resident generators: point conversion, the three transcript steps and u^-1 in ONE launch (k_ipp_round_tail)
-      CK(ipp_round_dev(ctx, s, nullptr));
-      ipp_round_tail(ctx->st, nb, s->sums, (uint64_t *)dstates, lr, du, dui, s->tail_partials, s->tail_chunks);
-    } else {
-      CK(ipp_round_dev(ctx, s, lr));
-      ipp_round_challenge(ctx->st, nb, (uint64_t *)dstates, lr, du);
-      HIPCK(ctx, hipMemcpyAsync(dui, du, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
-      batch_inverse(ctx->st, dui, nb, (int *)dzero);       // challenges are non-zero up to 2^-252
-    }
-    CK(ipp_fold_dev(ctx, s, du, dui));
-  }
-  span.close();
-  std::vector<uint8_t> tmp(k * nb * 128);
-  if (k) CK(d2h(ctx, tmp.data(), dlr, k * nb * 128));
-  CK(d2h(ctx, a_out, s->a[s->cur], nb * 32));
-  CK(d2h(ctx, b_out, s->b[s->cur], nb * 32));
-  if (states_out) CK(d2h(ctx, states_out, dstates, nb * 32));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  for (size_t p = 0; p < nb; p++)       // proof-major outputs: L_out[p][r], R_out[p][r]
+                     uint8_t *a_out, uint8_t *b_out, uint8_t *states_out) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !states_in || !a_out || !b_out || s->planes != 1) return BPGPU_E_ARG;
+    if (s->shi != (size_t)-1) return BPGPU_E_ARG;    // a sharded session's L, R are partial sums: its rounds need the ranks' exchange
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = s->nb;
+    size_t k = 0;
+    for (size_t t = s->n; t > 1; t >>= 1) k++;
+    if (k && (!L_out || !R_out)) return BPGPU_E_ARG;
+    void *dstates, *dlr, *dzero;
+    CK(ws_get(ctx, WS_FS_STAGE, nb * 32, &dstates));
+    CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
+    CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
+    CK(h2d(ctx, dstates, states_in, nb * 32));
+    Words8 *du = s->uu, *dui = s->uu + nb;
+    ProfSpan span(ctx, 20, ctx->st);
     for (size_t r = 0; r < k; r++) {
-      memcpy(L_out + (p * k + r) * 64, &tmp[(r * nb + p) * 128], 64);
-      memcpy(R_out + (p * k + r) * 64, &tmp[(r * nb + p) * 128 + 64], 64);
+      Words8 *lr = (Words8 *)dlr + r * nb * 4;             // 2 points x 2 Words8 per proof
+      if (s->gens) {   // resident generators: point conversion, the three transcript steps and u^-1 in ONE launch (k_ipp_round_tail)
+        CK(ipp_round_dev(ctx, s, nullptr));
+        ipp_round_tail(ctx->st, nb, s->sums, (uint64_t *)dstates, lr, du, dui, s->tail_partials, s->tail_chunks);
+      } else {
+        CK(ipp_round_dev(ctx, s, lr));
+        ipp_round_challenge(ctx->st, nb, (uint64_t *)dstates, lr, du);
+        HIPCK(ctx, hipMemcpyAsync(dui, du, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+        batch_inverse(ctx->st, dui, nb, (int *)dzero);       // challenges are non-zero up to 2^-252
+      }
+      CK(ipp_fold_dev(ctx, s, du, dui));
     }
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+    span.close();
+    // proof-major outputs: L_out[p][r], R_out[p][r]
+    return download_pairs(ctx, dlr, nb, k, L_out, R_out,
+                          {{a_out, s->a[s->cur], nb * 32}, {b_out, s->b[s->cur], nb * 32}, {states_out, dstates, states_out ? nb * 32 : 0}});
+  });
 }
 /* final a, b -- inner_product_proof.rs:187-192 */
 // The generators a resident-generator session has folded SO FAR, as points: G'_t = sum_{i = t mod n} cG[i] G_i (and H'), n = the
 // session's current length.  For n == 1 this is the pair (G', H') the remaining state (a, b) refers to -- what a rank of a
 // vector-sharded IPP (sharding.sharded_ipp_create: SURVEY 8e.2) hands to the final log2(ranks) rounds.  Only n == 1 is exposed.
-int bpgpu_ipp_folded_gens(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *G_out, uint8_t *H_out) try {
-  if (!ctx || !s || !G_out || !H_out || !s->gens) return BPGPU_E_ARG;
-  if (s->n != 1) return BPGPU_E_LEN;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t nb = s->nb, n0 = s->n0, per = 2 + 2 * n0;
-  // MSM 2p over [B, Bb, G.., H..]: scalars cG[p] on the G block; MSM 2p + 1: cH[p] on the H block
-  HIPCK(ctx, hipMemsetAsync(s->msc, 0, nb * 2 * per * 32, ctx->st));
-  HIPCK(ctx, hipMemcpy2DAsync((uint8_t *)s->msc + 2 * 32, 2 * per * 32, s->cG, n0 * 32, n0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st));
-  HIPCK(ctx, hipMemcpy2DAsync((uint8_t *)s->msc + (per + 2 + n0) * 32, 2 * per * 32, s->cH, n0 * 32, n0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st));
-  CK(msm_gens_dev(ctx, s->gens, 2 * nb, n0, (const uint32_t *)s->msc, s->sums, ctx->st));
-  jac_to_boundary(ctx->st, s->sums, s->out_xy, 2 * nb);
-  CK(launch_ok(ctx));
-  std::vector<uint8_t> tmp(nb * 2 * 64);
-  CK(d2h(ctx, tmp.data(), s->out_xy, nb * 2 * 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  for (size_t p = 0; p < nb; p++) { memcpy(G_out + 64 * p, &tmp[128 * p], 64); memcpy(H_out + 64 * p, &tmp[128 * p + 64], 64); }
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+int bpgpu_ipp_folded_gens(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *G_out, uint8_t *H_out) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !G_out || !H_out || !s->gens) return BPGPU_E_ARG;
+    if (s->n != 1) return BPGPU_E_LEN;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = s->nb, n0 = s->n0, per = 2 + 2 * n0;
+    // MSM 2p over [B, Bb, G.., H..]: scalars cG[p] on the G block; MSM 2p + 1: cH[p] on the H block
+    HIPCK(ctx, hipMemsetAsync(s->msc, 0, nb * 2 * per * 32, ctx->st));
+    HIPCK(ctx, hipMemcpy2DAsync((uint8_t *)s->msc + 2 * 32, 2 * per * 32, s->cG, n0 * 32, n0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st));
+    HIPCK(ctx, hipMemcpy2DAsync((uint8_t *)s->msc + (per + 2 + n0) * 32, 2 * per * 32, s->cH, n0 * 32, n0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st));
+    CK(msm_gens_dev(ctx, s->gens, 2 * nb, n0, (const uint32_t *)s->msc, s->sums, ctx->st));
+    jac_to_boundary(ctx->st, s->sums, s->out_xy, 2 * nb);
+    CK(launch_ok(ctx));
+    return download_pairs(ctx, s->out_xy, nb, 1, G_out, H_out);
+  });
 }
 int bpgpu_ipp_finish(bpgpu_ctx *ctx, bpgpu_ipp *s, uint8_t *a_out, uint8_t *b_out) {
   if (!ctx || !s || !a_out || !b_out) return BPGPU_E_ARG;
@@ -2720,6 +2710,63 @@ static void prover_free_all(bpgpu_ctx *ctx, bpgpu_prover *s) {   // ctx->mu held
   for (void *p : all) pool_release(ctx, p);
   delete s;
 }
+namespace { struct ProverFree { bpgpu_ctx *ctx; void operator()(bpgpu_prover *s) const { prover_free_all(ctx, s); } }; }
+using ProverOwner = std::unique_ptr<bpgpu_prover, ProverFree>;   // a session under construction (as IppOwner)
+
+/* ---- what the three polynomial builds share (prover_polys_impl: staged witness; prover_session_polys_locked and
+ * bpgpu_mpc_prover_polys_mask: resident witness) --------------------------------------------------------------------------- */
+// polys and y of the session's s->nb (virtual) provers, from the pool
+static int polys_alloc(bpgpu_ctx *ctx, bpgpu_prover *s, size_t n) {
+  PoolTake M{ctx};
+  M(&s->polys, (6 * s->nb * (n ? n : 1) * 9) * 4); M(&s->y, s->nb * 32);
+  return M.ok ? BPGPU_OK : BPGPU_E_OOM;
+}
+// the z-power table of nb proofs into WS_ZPOW (a parametric circuit's carries one block per gadget challenge); dz, dchi: validated
+static int zpow_build(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const Words8 *dz, const Words8 *dchi, const int32_t **dzp) {
+  const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);
+  void *p;
+  CK(ws_get(ctx, WS_ZPOW, nb * qz * 9 * 4, &p));
+  zpow_table(ctx->st, nb, c->q, dz, 8, (int32_t *)p, c->nchi, dchi);
+  *dzp = (const int32_t *)p;
+  return BPGPU_OK;
+}
+// A build on a resident-witness session (ctx->mu held): until it is kept, what it allocated goes back to the pool on the way out and
+// the session stays where it was -- the call may be repeated.
+namespace {
+struct PolysBuild {
+  bpgpu_ctx *ctx;
+  bpgpu_prover *s;
+  bool kept = false;
+  ~PolysBuild() {
+    if (kept) return;
+    for (void **p : {(void **)&s->polys, (void **)&s->y, (void **)&s->yinv, (void **)&s->trip, (void **)&s->wv}) { pool_release(ctx, *p); *p = nullptr; }
+  }
+};
+}  // namespace
+// Its head: polys, y, y^-1 from the pool; y (one per virtual prover) into the session, z and the gadget challenges (one set per proof)
+// into WS_ARG0 / WS_CHI; all of them validated.
+struct PolyChallenges { const Words8 *z, *chi; };
+static int session_polys_begin(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z, const uint8_t *chi,
+                               PolyChallenges *ch) {
+  const size_t nv = s->nb, nb = nv / (size_t)s->planes;
+  CK(polys_alloc(ctx, s, c->n));
+  if (!pool_alloc(ctx, (void **)&s->yinv, nv * 32)) return BPGPU_E_OOM;
+  void *dz, *dchi = nullptr;
+  CK(ws_get(ctx, WS_ARG0, nb * 32, &dz));
+  if (c->nchi) CK(ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi));
+  CK(upload_inputs(ctx, {{s->y, y, nv * 32}, {dz, z, nb * 32}, {dchi, chi, nb * c->nchi * 32}}));
+  scalars_check(ctx->st, s->y, nv, ctx->d_flag);
+  scalars_check(ctx->st, (const Words8 *)dz, nb, ctx->d_flag);
+  if (c->nchi) scalars_check(ctx->st, (const Words8 *)dchi, nb * c->nchi, ctx->d_flag);
+  ch->z = (const Words8 *)dz; ch->chi = (const Words8 *)dchi;
+  return BPGPU_OK;
+}
+// ... and what its polynomial kernel reads besides the witness: y^-1 (prover.rs:593; a zero challenge raises the flag: E_ARG), z powers
+static int session_polys_powers(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const PolyChallenges &ch, const int32_t **dzp) {
+  HIPCK(ctx, hipMemcpyAsync(s->yinv, s->y, s->nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+  batch_inverse(ctx->st, s->yinv, s->nb, ctx->d_flag);
+  return zpow_build(ctx, c, s->nb / (size_t)s->planes, ch.z, ch.chi, dzp);
+}
 static int prover_polys_impl(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *y, const uint8_t *y_inv,
                              const uint8_t *z, const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
                              const uint8_t *s_L, const uint8_t *s_R, uint8_t *t_coeffs, uint8_t *wV,
@@ -2731,39 +2778,30 @@ static int prover_polys_impl(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, 
   *out = nullptr;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
+  ProverOwner own(new (std::nothrow) bpgpu_prover(), ProverFree{ctx});
+  bpgpu_prover *s = own.get();
   if (!s) return BPGPU_E_OOM;
   s->nb = nb; s->n = n; s->m = m;
-  auto fail = [&](int rc) { prover_free_all(ctx, s); return rc; };
-  if (!pool_alloc(ctx, (void **)&s->polys, (6 * nb * (n ? n : 1) * 9) * 4) || !pool_alloc(ctx, (void **)&s->y, nb * 32))
-    return fail(BPGPU_E_OOM);
-  void *din, *dzp, *dout;
+  CK(polys_alloc(ctx, s, n));
+  // y, y^-1 and z arrive with the witness, in the witness's form: one staging block, one validation (or conversion) launch
+  void *din, *dout;
   size_t tot = nb * n;
-  int rc;
-  if ((rc = ws_get(ctx, WS_ARG0, (3 * nb + 5 * tot) * 32, &din)) || (rc = ws_get(ctx, WS_ZPOW, nb * (c->q ? c->q : 1) * 9 * 4, &dzp)) ||
-      (rc = ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout)))
-    return fail(rc);
+  CK(ws_get(ctx, WS_ARG0, (3 * nb + 5 * tot) * 32, &din));
+  CK(ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout));
   Words8 *w = (Words8 *)din;
   Words8 *dy = w, *dyi = w + nb, *dz = w + 2 * nb, *dL = w + 3 * nb, *dR = dL + tot, *dO = dR + tot, *dsL = dO + tot, *dsR = dsL + tot;
   Words8 *dt = (Words8 *)dout, *dwV = dt + nb * 6;
-  if ((rc = flag_reset(ctx)) || (rc = h2d(ctx, dy, y, nb * 32)) || (rc = h2d(ctx, dyi, y_inv, nb * 32)) ||
-      (rc = h2d(ctx, dz, z, nb * 32)) || (rc = h2d(ctx, dL, a_L, tot * 32)) || (rc = h2d(ctx, dR, a_R, tot * 32)) ||
-      (rc = h2d(ctx, dO, a_O, tot * 32)) || (rc = h2d(ctx, dsL, s_L, tot * 32)) || (rc = h2d(ctx, dsR, s_R, tot * 32)))
-    return fail(rc);
+  CK(upload_inputs(ctx, {{dy, y, nb * 32}, {dyi, y_inv, nb * 32}, {dz, z, nb * 32}, {dL, a_L, tot * 32}, {dR, a_R, tot * 32},
+                         {dO, a_O, tot * 32}, {dsL, s_L, tot * 32}, {dsR, s_R, tot * 32}}));
   if (ark) scalars_from_ark(ctx->st, w, w, 3 * nb + 5 * tot, ctx->d_flag);
   else scalars_check(ctx->st, w, 3 * nb + 5 * tot, ctx->d_flag);
-  if (hipMemcpyAsync(s->y, dy, nb * 32, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
-  CircuitDev cd = circuit_dev(c);
-  zpow_table(ctx->st, nb, c->q, dz, 8, (int32_t *)dzp);   // (parametric circuits are rejected above: the prover builds numeric rows)
-  prover_polys(ctx->st, cd, nb, dy, dyi, dL, dR, dO, dsL, dsR, (const int32_t *)dzp, s->polys, dwV);
+  HIPCK(ctx, hipMemcpyAsync(s->y, dy, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+  const int32_t *dzp;
+  CK(zpow_build(ctx, c, nb, dz, nullptr, &dzp));   // (parametric circuits are rejected above: the prover builds numeric rows)
+  prover_polys(ctx->st, circuit_dev(c), nb, dy, dyi, dL, dR, dO, dsL, dsR, dzp, s->polys, dwV);
   prover_tcoeffs(ctx->st, nb, n, s->polys, dt);
-  if ((rc = launch_ok(ctx))) return fail(rc);
-  int bad = 0;
-  if ((rc = flag_read(ctx, &bad))) return fail(rc);
-  if (bad) return fail(BPGPU_E_ARG);
-  if ((rc = d2h(ctx, t_coeffs, dt, nb * 6 * 32)) || (m && (rc = d2h(ctx, wV, dwV, nb * m * 32)))) return fail(rc);
-  if (hipStreamSynchronize(ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
-  *out = s;
+  CK(checked_download(ctx, {{t_coeffs, dt, nb * 6 * 32}, {wV, dwV, nb * m * 32}}));
+  *out = own.release();
   return BPGPU_OK;
 }
 int bpgpu_r1cs_prover_polys(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *y, const uint8_t *y_inv,
@@ -2807,43 +2845,24 @@ static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_g
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t nb = ps->nb, n = padded_n;
-  bpgpu_ipp *s = new (std::nothrow) bpgpu_ipp();
-  if (!s) return BPGPU_E_OOM;
-  s->nb = nb; s->n0 = s->n = n; s->gens = g; s->planes = ps->planes;
-  if (ctx->shard_world > 1) { shard_bounds(n, ctx->shard_rank, ctx->shard_world, &s->slo, &s->shi); s->with_q = ctx->shard_rank == 0; }
-  size_t tot = nb * n, half = nb * (n > 1 ? n / 2 : 1);
-  bool okk = true;
-  auto M = [&](void **p, size_t bytes) { if (okk && !pool_alloc(ctx, p, bytes)) okk = false; };
-  M((void **)&s->a[0], tot * 32); M((void **)&s->b[0], tot * 32); M((void **)&s->a[1], half * 32); M((void **)&s->b[1], half * 32);
-  M((void **)&s->cG, tot * 32); M((void **)&s->cH, tot * 32); M((void **)&s->w, nb * 32);
-  M((void **)&s->cLR, nb * 2 * 32); M((void **)&s->uu, nb * 2 * 32);
-  M((void **)&s->sums, nb * 2 * sizeof(JacRaw)); M((void **)&s->out_xy, nb * 2 * 64);
-  M((void **)&s->msc, nb * 2 * (2 + 2 * n) * 32);
-  if (ps->planes != 1) M((void **)&s->trip, (nb / 3) * 2 * 9 * (n / 2 ? n / 2 : 1) * 32);   // the first round's triples, the largest
-  if (!okk) { ipp_free_all(ctx, s); return BPGPU_E_OOM; }
-  int rc = BPGPU_OK;
-  do {
-    void *din;
-    if ((rc = ws_get(ctx, WS_ARG0, 3 * nb * 32, &din))) break;
-    Words8 *dx = (Words8 *)din, *du = dx + nb, *dyi = du + nb;
-    if ((rc = flag_reset(ctx))) break;
-    if ((rc = h2d(ctx, dx, x, nb * 32)) || (rc = h2d(ctx, du, u, nb * 32)) || (rc = h2d(ctx, s->w, w, nb * 32))) break;
-    if (y_inv) { if ((rc = h2d(ctx, dyi, y_inv, nb * 32))) break; }
-    else if (hipMemcpyAsync(dyi, ps->yinv, nb * 32, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) { rc = BPGPU_E_DEVICE; break; }
-    ProfSpan span(ctx, 19, ctx->st);
-    scalars_check(ctx->st, dx, 3 * nb, ctx->d_flag);
-    scalars_check(ctx->st, s->w, nb, ctx->d_flag);
-    if (ps->planes != 1) mpc_eval(ctx->st, nb / 3, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
-    else prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
-    ipp_r1cs_factors(ctx->st, nb, n, n1, du, dyi, s->cG, s->cH);
-    span.close();
-    if ((rc = launch_ok(ctx))) break;
-    int bad = 0;
-    if ((rc = flag_read(ctx, &bad))) break;
-    if (bad) rc = BPGPU_E_ARG;
-  } while (0);
-  if (rc) { ipp_free_all(ctx, s); return rc; }
-  *out = s;
+  IppOwner own(nullptr, IppFree{ctx});
+  CK(ipp_gens_session(ctx, g, nb, n, ps->planes, own));
+  bpgpu_ipp *s = own.get();
+  void *din;
+  CK(ws_get(ctx, WS_ARG0, 3 * nb * 32, &din));
+  Words8 *dx = (Words8 *)din, *du = dx + nb, *dyi = du + nb;
+  CK(upload_inputs(ctx, {{dx, x, nb * 32}, {du, u, nb * 32}, {s->w, w, nb * 32}}));
+  if (y_inv) CK(h2d(ctx, dyi, y_inv, nb * 32));
+  else HIPCK(ctx, hipMemcpyAsync(dyi, ps->yinv, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+  ProfSpan span(ctx, 19, ctx->st);
+  scalars_check(ctx->st, dx, 3 * nb, ctx->d_flag);
+  scalars_check(ctx->st, s->w, nb, ctx->d_flag);
+  if (ps->planes != 1) mpc_eval(ctx->st, nb / 3, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+  else prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+  ipp_r1cs_factors(ctx->st, nb, n, n1, du, dyi, s->cG, s->cH);
+  span.close();
+  CK(checked_inputs(ctx));
+  *out = own.release();
   return BPGPU_OK;
 }
 int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
@@ -2882,25 +2901,23 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
     if (!s) return BPGPU_E_OOM;
     s->nb = nb; s->planes = planes; s->g = g;
   }
-  auto fail = [&](int rc) { if (fresh) prover_free_all(ctx, s); return rc; };
+  ProverOwner own(fresh ? s : nullptr, ProverFree{ctx});   // only a fresh session is freed on failure
   // new planes of nb x wn; the multipliers of the earlier phase are carried over
   Words8 *pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   Words8 **old[5] = {&s->aL, &s->aR, &s->aO, &s->sL, &s->sR};
   const size_t tot_new = nb * n_new;
   void *din = nullptr, *drows = nullptr, *dres = nullptr, *dout = nullptr;
-  int rc;
-  if ((rc = ws_get(ctx, WS_ARG0, (5 * tot_new + 4 * nb) * 32, &din)) || (rc = ws_get(ctx, WS_ARG1, nb * 3 * (2 + 2 * wn) * 32, &drows)) ||
-      (rc = ws_get(ctx, WS_ARG4, nb * 3 * sizeof(JacRaw), &dres)) || (rc = ws_get(ctx, WS_ARG5, nb * 3 * 64, &dout)))
-    return fail(rc);
+  CK(ws_get(ctx, WS_ARG0, (5 * tot_new + 4 * nb) * 32, &din));
+  CK(ws_get(ctx, WS_ARG1, nb * 3 * (2 + 2 * wn) * 32, &drows));
+  CK(ws_get(ctx, WS_ARG4, nb * 3 * sizeof(JacRaw), &dres));
+  CK(ws_get(ctx, WS_ARG5, nb * 3 * 64, &dout));
   if (n_new) {
-    bool okk = true;
-    for (int i = 0; i < 5; i++) okk = okk && pool_alloc(ctx, (void **)&pl[i], nb * wn * 32);
-    if (!okk) { for (auto p : pl) pool_release(ctx, p); return fail(BPGPU_E_OOM); }
+    auto drop = [&](int rc) { for (auto p : pl) pool_release(ctx, p); return rc; };   // (until the session takes the new planes)
+    PoolTake M{ctx};
+    for (int i = 0; i < 5; i++) M(&pl[i], nb * wn * 32);
+    if (!M.ok) return drop(BPGPU_E_OOM);
     if (wn0) for (int i = 0; i < 5; i++)
-      if (hipMemcpy2DAsync(pl[i], wn * 32, *old[i], wn0 * 32, wn0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) {
-        for (auto p : pl) pool_release(ctx, p);
-        return fail(BPGPU_E_DEVICE);
-      }
+      if (hipMemcpy2DAsync(pl[i], wn * 32, *old[i], wn0 * 32, wn0 * 32, nb, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) return drop(BPGPU_E_DEVICE);
     for (int i = 0; i < 5; i++) { pool_release(ctx, *old[i]); *old[i] = pl[i]; }   // (stream-ordered: any reuse runs after the copies)
     s->wn = wn;
   }
@@ -2909,10 +2926,10 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   const size_t nvec = explicit_vec ? 5 : 3;
   Words8 *dbl = w + nvec * tot_new, *dkeys = dbl + 3 * nb;
   const uint8_t *src[5] = {a_L, a_R, a_O, s_L, s_R};
-  if ((rc = flag_reset(ctx))) return fail(rc);
-  for (size_t i = 0; i < nvec && n_new; i++) if ((rc = h2d(ctx, w + i * tot_new, src[i], tot_new * 32))) return fail(rc);
-  if ((rc = h2d(ctx, dbl, blindings, nb * 3 * 32))) return fail(rc);
-  if (n_new && !explicit_vec && (rc = h2d(ctx, dkeys, vector_keys, nb * 32))) return fail(rc);
+  CK(flag_reset(ctx));
+  for (size_t i = 0; i < nvec && n_new; i++) CK(h2d(ctx, w + i * tot_new, src[i], tot_new * 32));
+  CK(h2d(ctx, dbl, blindings, nb * 3 * 32));
+  if (n_new && !explicit_vec) CK(h2d(ctx, dkeys, vector_keys, nb * 32));
   ProfSpan span(ctx, 16, ctx->st);
   if (n_new) {
     if (wn0 == 0) {          // contiguous planes: convert straight into them
@@ -2920,8 +2937,7 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
     } else {
       scalars_from_ark(ctx->st, w, w, nvec * tot_new, ctx->d_flag);
       for (size_t i = 0; i < nvec; i++)
-        if (hipMemcpy2DAsync(*old[i] + wn0, wn * 32, w + i * tot_new, n_new * 32, n_new * 32, nb, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess)
-          return fail(BPGPU_E_DEVICE);
+        HIPCK(ctx, hipMemcpy2DAsync(*old[i] + wn0, wn * 32, w + i * tot_new, n_new * 32, n_new * 32, nb, hipMemcpyDeviceToDevice, ctx->st));
     }
     if (!explicit_vec) blind_vectors(ctx->st, dkeys, nb, n_new, s->sL, s->sR, wn, wn0);
   }
@@ -2930,15 +2946,11 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   if (ctx->shard_world > 1) shard_bounds(wn, ctx->shard_rank, ctx->shard_world, &slo, &shi);   // this rank's generators: partial commitments
   commit_rows(ctx->st, nb, wn, wn0, wn, s->aL, s->aR, s->aO, s->sL, s->sR, dbl, (Words8 *)drows, slo, shi, ctx->shard_rank == 0);
   // (three classes of rows per prover -- A_I, A_O: bit vectors; S: dense -- so that a wave of the MSM-per-lane walk holds one class)
-  if ((rc = msm_gens_dev(ctx, g, nb * 3, wn, (const uint32_t *)drows, (JacRaw *)dres, ctx->st, WS_MSM, 0, 3))) return fail(rc);
+  CK(msm_gens_dev(ctx, g, nb * 3, wn, (const uint32_t *)drows, (JacRaw *)dres, ctx->st, WS_MSM, 0, 3));
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, nb * 3);
   span.close();
-  if ((rc = launch_ok(ctx))) return fail(rc);
-  int bad = 0;
-  if ((rc = flag_read(ctx, &bad))) return fail(rc);
-  if (bad) return fail(BPGPU_E_ARG);
-  if ((rc = d2h(ctx, commitments, dout, nb * 3 * 64))) return fail(rc);
-  if (hipStreamSynchronize(ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
+  CK(checked_download(ctx, {{commitments, dout, nb * 3 * 64}}));
+  (void)own.release();
   *session = s;
   return BPGPU_OK;
 }
@@ -2967,34 +2979,22 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t nb = s->nb, n = c->n, m = c->m;
-  if (!pool_alloc(ctx, (void **)&s->polys, (6 * nb * (n ? n : 1) * 9) * 4) || !pool_alloc(ctx, (void **)&s->y, nb * 32) ||
-      !pool_alloc(ctx, (void **)&s->yinv, nb * 32)) {
-    pool_release(ctx, s->polys); pool_release(ctx, s->y); pool_release(ctx, s->yinv);
-    s->polys = nullptr; s->y = s->yinv = nullptr;
-    return BPGPU_E_OOM;
-  }
-  s->n = n; s->m = m;
-  void *din, *dzp, *dout, *dchi = nullptr;
-  const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);    // a parametric circuit's z-power table carries one block per gadget challenge
-  CK(ws_get(ctx, WS_ARG0, 2 * nb * 32, &din));
-  CK(ws_get(ctx, WS_ZPOW, nb * qz * 9 * 4, &dzp));
+  PolysBuild build{ctx, s};
+  void *dout;
   CK(ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout));
-  if (c->nchi) CK(ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi));
-  Words8 *dz = (Words8 *)din, *dt = (Words8 *)dout, *dwV = dt + nb * 6;
-  CK(flag_reset(ctx));
-  CK(h2d(ctx, s->y, y, nb * 32));
-  CK(h2d(ctx, dz, z, nb * 32));
-  if (c->nchi) { CK(h2d(ctx, dchi, chi, nb * c->nchi * 32)); scalars_check(ctx->st, (const Words8 *)dchi, nb * c->nchi, ctx->d_flag); }
-  scalars_check(ctx->st, s->y, nb, ctx->d_flag);
-  scalars_check(ctx->st, dz, nb, ctx->d_flag);
+  Words8 *dt = (Words8 *)dout, *dwV = dt + nb * 6;
+  PolyChallenges ch;
+  CK(session_polys_begin(ctx, s, c, y, z, chi, &ch));
   ProfSpan span(ctx, 17, ctx->st);
-  HIPCK(ctx, hipMemcpyAsync(s->yinv, s->y, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
-  batch_inverse(ctx->st, s->yinv, nb, ctx->d_flag);       // y^-1, prover.rs:593 (a zero challenge raises the flag: E_ARG)
-  zpow_table(ctx->st, nb, c->q, dz, 8, (int32_t *)dzp, c->nchi, (const Words8 *)dchi);
-  prover_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, (const int32_t *)dzp, s->polys, dwV);
+  const int32_t *dzp;
+  CK(session_polys_powers(ctx, s, c, ch, &dzp));
+  prover_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, dzp, s->polys, dwV);
   prover_tcoeffs(ctx->st, nb, n, s->polys, dt);
   span.close();
-  return checked_download(ctx, {{t_coeffs, dt, nb * 6 * 32}, {wV, dwV, nb * m * 32}});
+  CK(checked_download(ctx, {{t_coeffs, dt, nb * 6 * 32}, {wV, dwV, nb * m * 32}}));
+  build.kept = true;
+  s->n = n; s->m = m;
+  return BPGPU_OK;
 }
 /* scalars[i] * (curve generator): GeneratorsChain::next (generators.rs:112-124), Q = w * B (prover.rs:687) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out) {
@@ -3040,54 +3040,36 @@ int bpgpu_mpc_prover_commit(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **
   return prover_commit_impl(ctx, g, session, 3 * nb, n_new, a_L, a_R, a_O, s_L, s_R, nullptr, blindings, commitments, 3);
 }
 int bpgpu_mpc_prover_polys_mask(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
-                                const uint8_t *gadget_challenges, const uint8_t *triples, uint8_t *masked) try {
-  if (!ctx || !s || !c || !y || !z || !triples || !masked || s->planes != 3) return BPGPU_E_ARG;
-  if ((c->nchi != 0) != (gadget_challenges != nullptr) || ctx->shard_world > 1) return BPGPU_E_ARG;
-  if (c->n != s->wn || s->polys) return BPGPU_E_LEN;     // the circuit's multipliers are the session's; one polynomial build per session
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t NB = s->nb, nb = NB / 3, n = c->n, m = c->m, ntrip = nb * 6 * 9 * n, nmask = nb * 6 * 6 * n;
-  bool okk = true;
-  for (auto pp : {std::make_pair((void **)&s->polys, 6 * NB * (n ? n : 1) * 9 * 4), std::make_pair((void **)&s->y, NB * 32),
-                  std::make_pair((void **)&s->yinv, NB * 32), std::make_pair((void **)&s->trip, ntrip * 32), std::make_pair((void **)&s->wv, nb * m * 32)})
-    okk = okk && pool_alloc(ctx, pp.first, pp.second);
-  auto fail = [&](int rc) {   // the session stays where it was: the call may be repeated
-    for (void **p : {(void **)&s->polys, (void **)&s->y, (void **)&s->yinv, (void **)&s->trip, (void **)&s->wv}) { pool_release(ctx, *p); *p = nullptr; }
-    return rc;
-  };
-  if (!okk) return fail(BPGPU_E_OOM);
-  void *dz, *dzp, *dm, *dchi = nullptr;
-  const size_t qz = (1 + c->nchi) * (c->q ? c->q : 1);
-  int rc;
-  if ((rc = ws_get(ctx, WS_ARG0, nb * 32, &dz)) || (rc = ws_get(ctx, WS_ZPOW, nb * qz * 9 * 4, &dzp)) || (rc = ws_get(ctx, WS_MSM2, nmask * 32, &dm)) ||
-      (c->nchi && (rc = ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi))))
-    return fail(rc);
-  const std::vector<uint8_t> y3 = bcast3(y, nb);
-  if ((rc = flag_reset(ctx)) || (rc = h2d(ctx, s->y, y3.data(), NB * 32)) || (rc = h2d(ctx, dz, z, nb * 32)) ||
-      (rc = h2d(ctx, s->trip, triples, ntrip * 32)) || (c->nchi && (rc = h2d(ctx, dchi, gadget_challenges, nb * c->nchi * 32))))
-    return fail(rc);
-  scalars_check(ctx->st, s->y, NB, ctx->d_flag);
-  scalars_check(ctx->st, (const Words8 *)dz, nb, ctx->d_flag);
-  if (c->nchi) scalars_check(ctx->st, (const Words8 *)dchi, nb * c->nchi, ctx->d_flag);
-  scalars_from_ark(ctx->st, s->trip, s->trip, ntrip, ctx->d_flag);
-  ProfSpan span(ctx, 17, ctx->st);
-  if (hipMemcpyAsync(s->yinv, s->y, NB * 32, hipMemcpyDeviceToDevice, ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
-  batch_inverse(ctx->st, s->yinv, NB, ctx->d_flag);        // y^-1 (a zero challenge raises the flag: E_ARG)
-  zpow_table(ctx->st, nb, c->q, (const Words8 *)dz, 8, (int32_t *)dzp, c->nchi, (const Words8 *)dchi);
-  mpc_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, (const int32_t *)dzp, s->polys, s->wv, s->trip,
-            (Words8 *)dm);
-  scalars_to_ark(ctx->st, (const Words8 *)dm, (Words8 *)dm, nmask, ctx->d_flag);
-  span.close();
-  if ((rc = launch_ok(ctx))) return fail(rc);
-  int bad = 0;
-  if ((rc = flag_read(ctx, &bad))) return fail(rc);
-  if (bad) return fail(BPGPU_E_ARG);
-  if ((rc = d2h(ctx, masked, dm, nmask * 32))) return fail(rc);
-  if (hipStreamSynchronize(ctx->st) != hipSuccess) return fail(BPGPU_E_DEVICE);
-  s->n = n; s->m = m;
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+                                const uint8_t *gadget_challenges, const uint8_t *triples, uint8_t *masked) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !c || !y || !z || !triples || !masked || s->planes != 3) return BPGPU_E_ARG;
+    if ((c->nchi != 0) != (gadget_challenges != nullptr) || ctx->shard_world > 1) return BPGPU_E_ARG;
+    if (c->n != s->wn || s->polys) return BPGPU_E_LEN;     // the circuit's multipliers are the session's; one polynomial build per session
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = s->nb / 3, n = c->n, m = c->m, ntrip = nb * 6 * 9 * n, nmask = nb * 6 * 6 * n;
+    const std::vector<uint8_t> y3 = bcast3(y, nb);
+    PolysBuild build{ctx, s};
+    void *dm;
+    CK(ws_get(ctx, WS_MSM2, nmask * 32, &dm));
+    PolyChallenges ch;
+    CK(session_polys_begin(ctx, s, c, y3.data(), z, gadget_challenges, &ch));
+    PoolTake M{ctx};
+    M(&s->trip, ntrip * 32); M(&s->wv, nb * m * 32);
+    if (!M.ok) return BPGPU_E_OOM;
+    CK(h2d(ctx, s->trip, triples, ntrip * 32));
+    scalars_from_ark(ctx->st, s->trip, s->trip, ntrip, ctx->d_flag);
+    ProfSpan span(ctx, 17, ctx->st);
+    const int32_t *dzp;
+    CK(session_polys_powers(ctx, s, c, ch, &dzp));
+    mpc_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, dzp, s->polys, s->wv, s->trip, (Words8 *)dm);
+    scalars_to_ark(ctx->st, (const Words8 *)dm, (Words8 *)dm, nmask, ctx->d_flag);
+    span.close();
+    CK(checked_download(ctx, {{masked, dm, nmask * 32}}));
+    build.kept = true;
+    s->n = n; s->m = m;
+    return BPGPU_OK;
+  });
 }
 int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *s, const uint8_t *opened, const uint8_t *t_blindings, uint8_t *t_coeffs,
                                   uint8_t *T, uint8_t *wV) {
@@ -3119,13 +3101,13 @@ int bpgpu_mpc_prover_polys_finish(bpgpu_ctx *ctx, bpgpu_prover *s, const uint8_t
   return BPGPU_OK;
 }
 int bpgpu_mpc_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1, const uint8_t *x,
-                               const uint8_t *u, const uint8_t *w, bpgpu_ipp **out) try {
-  if (!ctx || !ps || !g || !x || !u || !w || !out || ps->planes != 3 || !ps->finished || ctx->shard_world > 1) return BPGPU_E_ARG;
-  const size_t nb = ps->nb / 3;
-  const std::vector<uint8_t> x3 = bcast3(x, nb), u3 = bcast3(u, nb), w3 = bcast3(w, nb);
-  return prover_ipp_begin_impl(ctx, ps, g, padded_n, n1, x3.data(), u3.data(), nullptr, w3.data(), out);
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+                               const uint8_t *u, const uint8_t *w, bpgpu_ipp **out) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !ps || !g || !x || !u || !w || !out || ps->planes != 3 || !ps->finished || ctx->shard_world > 1) return BPGPU_E_ARG;
+    const size_t nb = ps->nb / 3;
+    const std::vector<uint8_t> x3 = bcast3(x, nb), u3 = bcast3(u, nb), w3 = bcast3(w, nb);
+    return prover_ipp_begin_impl(ctx, ps, g, padded_n, n1, x3.data(), u3.data(), nullptr, w3.data(), out);
+  });
 }
 int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *triples, uint8_t *masked) {
   if (!ctx || !s || !triples || !masked || s->planes != 3) return BPGPU_E_ARG;
@@ -3146,33 +3128,28 @@ int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *triples, uin
   s->masked = true;
   return BPGPU_OK;
 }
-int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *opened, uint8_t *L, uint8_t *R) try {
-  if (!ctx || !s || !opened || !L || !R || s->planes != 3 || !s->masked) return BPGPU_E_ARG;
-  if (s->n < 2) return BPGPU_E_LEN;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t NB = s->nb, nb = NB / 3, h = s->n / 2, nop = nb * 2 * 2 * h;
-  void *dop;
-  CK(ws_get(ctx, WS_MSM2, nop * 32, &dop));
-  CK(flag_reset(ctx));
-  CK(h2d(ctx, dop, opened, nop * 32));
-  scalars_from_ark(ctx->st, (const Words8 *)dop, (Words8 *)dop, nop, ctx->d_flag);
-  int bad = 0;
-  CK(flag_read(ctx, &bad));
-  if (bad) return BPGPU_E_ARG;        // checked before the session state advances
-  {
-    ProfSpan span(ctx, 20, ctx->st);
-    mpc_ipp_combine(ctx->st, nb, h, (const Words8 *)dop, s->trip, s->cLR);   // c_L, c_R per plane: mpc_inner_product.rs:142-155
-    CK(ipp_round_dev(ctx, s, s->out_xy, true));
-  }
-  std::vector<uint8_t> tmp(NB * 128);
-  CK(d2h(ctx, tmp.data(), s->out_xy, NB * 128));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  for (size_t v = 0; v < NB; v++) { memcpy(L + 64 * v, &tmp[128 * v], 64); memcpy(R + 64 * v, &tmp[128 * v + 64], 64); }
-  s->masked = false;
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
-  return BPGPU_E_OOM;
+int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *opened, uint8_t *L, uint8_t *R) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !s || !opened || !L || !R || s->planes != 3 || !s->masked) return BPGPU_E_ARG;
+    if (s->n < 2) return BPGPU_E_LEN;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = s->nb / 3, h = s->n / 2, nop = nb * 2 * 2 * h;
+    void *dop;
+    CK(ws_get(ctx, WS_MSM2, nop * 32, &dop));
+    CK(flag_reset(ctx));
+    CK(h2d(ctx, dop, opened, nop * 32));
+    scalars_from_ark(ctx->st, (const Words8 *)dop, (Words8 *)dop, nop, ctx->d_flag);
+    CK(checked_inputs(ctx));            // before the session state advances
+    {
+      ProfSpan span(ctx, 20, ctx->st);
+      mpc_ipp_combine(ctx->st, nb, h, (const Words8 *)dop, s->trip, s->cLR);   // c_L, c_R per plane: mpc_inner_product.rs:142-155
+      CK(ipp_round_dev(ctx, s, s->out_xy, true));
+    }
+    CK(download_pairs(ctx, s->out_xy, s->nb, 1, L, R));
+    s->masked = false;
+    return BPGPU_OK;
+  });
 }
 
 #pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers of the HIP kernels (k_ec.hip, k_scalar.hip).
+// kernels.h -- host-callable launchers of the HIP kernels (the k_*.hip files; each section below names its file).
 // All pointers are device pointers; every launcher enqueues on `st` and returns immediately.
 #pragma once
 #include <hip/hip_runtime.h>
