@@ -486,6 +486,12 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_prover_session_polys(self.ctx, session, circuit, _buf(y), _buf(z), t, wv))
         return bytes(t)[:32 * 6 * nb], bytes(wv)[:32 * nb * m]
 
+    def r1cs_prover_session_polys_param(self, session, circuit, nb, m, y, z, gadget_challenges):
+        """the same for a circuit of circuit_create_param; gadget_challenges nb x nchi x 32 B canonical LE"""
+        t, wv = _out(32 * 6 * nb), _out(32 * nb * max(m, 1))
+        self._ck(_lib.bpgpu_r1cs_prover_session_polys_param(self.ctx, session, circuit, _buf(y), _buf(z), _buf(gadget_challenges), t, wv))
+        return bytes(t)[:32 * 6 * nb], bytes(wv)[:32 * nb * m]
+
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
 

@@ -68,6 +68,30 @@ extern "C" {
 int h29_fp(int op, const uint8_t *a, const uint8_t *b, uint8_t *out) { return binop<FP>(op, a, b, out); }
 int h29_fn(int op, const uint8_t *a, const uint8_t *b, uint8_t *out) { return binop<FN>(op, a, b, out); }
 
+// The lazy column sum of flatten_column (fn_dev.cuh) on raw values: acc += mul(a, b) for k terms with the reduction mul(acc, R mod n)
+// after every 16th, then the UNREDUCED sum as an operand of a product, out = acc * y / R mod n.  a, b, y: the limbs' values themselves
+// (no Montgomery conversion); b is lifted by lift * n (|lift| <= 1) to the ends of the range a product returns.  acc_limbs: the
+// nine limbs of the sum that went into the last product (the header's contract: |value| < 2^256).
+int h29_fn_lazy_sum(int k, int lift, const uint8_t *a, const uint8_t *b, const uint8_t *y, int32_t *acc_limbs, uint8_t *out) {
+  uint32_t wa[8], wb[8], wy[8];
+  load_words(wa, a); load_words(wb, b); load_words(wy, y);
+  if (!words_lt_mod<FN>(wa) || !words_lt_mod<FN>(wb) || !words_lt_mod<FN>(wy) || lift < -1 || lift > 1) return -1;
+  constexpr int32_t MOD[NL] = FN_MOD;
+  Fn A = unpack<FN>(wa), B = unpack<FN>(wb), Y = unpack<FN>(wy);
+  for (int j = 0; j < NL; j++) B.v[j] += lift * MOD[j];
+  B = norm(B);
+  Fn acc = fe_zero<FN>();
+  for (int t = 1; t <= k; t++) {
+    acc = add(acc, mul(A, B));
+    if ((t & 15) == 0) acc = mul(acc, fe_one<FN>());
+  }
+  for (int j = 0; j < NL; j++) acc_limbs[j] = acc.v[j];
+  uint32_t w[8];
+  pack(w, canon(mul(acc, Y)));
+  memcpy(out, w, 32);
+  return 0;
+}
+
 // op 0: madd(a, b)  1: add(jac a, jac b') with b' rescaled by a random-ish Z  2: dbl(a)
 // op 3: the same sum through the extended-Jacobian accumulator: ((identity + a) + b) by xyzz_madd, back through xyzz_to_jac
 // op 4: (a rescaled to a non-trivial ZZ / ZZZ) + b by xyzz_madd_nzq (b must not be the identity)

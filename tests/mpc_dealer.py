@@ -97,15 +97,22 @@ def pack(rows):
     return b"".join(pack(r) for r in rows)
 
 
-def circuit_rows(constraints, param=False):
+def circuit_rows(constraints, param=False, nchi=None):
     """CSR rows (row_ptr, kind, idx, coeff) of the model's constraints; param: the shuffle's (1 + 1) q rows with every `One` term
-    -chi moved to the chi block as -1 (include/bpgpu.h bpgpu_circuit_create_param), and chi"""
+    -chi moved to the chi block as -1 (include/bpgpu.h bpgpu_circuit_create_param), and chi.
+    A constraint is the model's dict, or a list of (var, coeff) terms kept as they are: repeated variables and zero coefficients
+    stay separate terms.  nchi: the (1 + nchi) q rows of a circuit whose coefficients may be tuples (c0, c1, .., c_nchi) standing
+    for c0 + sum_j chi_j c_j -- part j goes to block j, None parts to none (tests/circuit_gen.py)."""
     q = len(constraints)
-    blocks = [[[] for _ in range(q)] for _ in range(2 if param else 1)]
+    blocks = [[[] for _ in range(q)] for _ in range(1 + nchi if nchi is not None else (2 if param else 1))]
     chi = None
     for r, lc in enumerate(constraints):
-        for var, c in lc.items():
-            if param and var[0] == "1":
+        for var, c in (lc.items() if isinstance(lc, dict) else lc):
+            if isinstance(c, tuple):
+                for j, cj in enumerate(c):
+                    if cj is not None:
+                        blocks[j][r].append((KIND[var[0]], var[1] if len(var) > 1 else 0, cj % N))
+            elif param and var[0] == "1":
                 assert chi is None or chi == (-c) % N
                 chi = (-c) % N
                 blocks[1][r].append((4, 0, N - 1))

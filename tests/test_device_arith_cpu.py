@@ -124,3 +124,30 @@ def test_fp_sqrt_against_model(h):
         r = int.from_bytes(bytes(out), "little")
         assert r * r % P == a
     assert h.h29_sqrt(buf(le(c)), out) == 0        # the Sylow generator itself is a non-residue
+
+
+@pytest.mark.parametrize("k", [15, 16, 31])
+def test_unreduced_column_sum_as_a_product_operand(h, k):
+    """fe29.cuh: "every mul input must satisfy |v| < 2^256".  flatten_column (fn_dev.cuh) adds products lazily, reduces after every
+    16th and hands the sum to a product as it is, so 15 products past the start or past a reduction is the most it ever holds.  Each
+    product here is as large as one gets: the stored coefficient n - 1 times a z power at either end of the range a product returns
+    (lifted by -n, 0, +n), chosen so that the product is n - 1, the largest residue.  The sum must stay inside the contract and the
+    product that consumes it must be exact."""
+    R = 1 << 261
+    RI = pow(R, -1, N)
+    rnd = random.Random(61 + k)
+    limbs = (C.c_int32 * 9)()
+    out = (C.c_uint8 * 32)()
+    biggest = 0
+    for target in (N - 1, 1, (N + 1) // 2, rnd.randrange(N)):
+        a = N - 1
+        b = target * R * pow(a, -1, N) % N                  # a b / R = target (mod n)
+        for lift in (-1, 0, 1):
+            for y in (N - 1, 1, rnd.randrange(N)):
+                assert h.h29_fn_lazy_sum(k, lift, buf(le(a)), buf(le(b)), buf(le(y)), limbs, out) == 0
+                acc = sum(v << (29 * j) for j, v in enumerate(limbs))
+                assert abs(acc) < 1 << 256, (hex(target), lift)
+                assert acc % N == k * target % N
+                assert int.from_bytes(bytes(out), "little") == k * target * y * RI % N, (hex(target), lift, hex(y))
+                biggest = max(biggest, abs(acc))
+    assert biggest > (15 * (N - 1) if k != 16 else N - 1) - N      # the cases reach the largest sum this cadence allows
