@@ -210,6 +210,40 @@ int bpgpu_fold_witness(bpgpu_ctx *ctx, size_t n, const uint8_t u[32], const uint
  * (the transcript replay of :271-278 stays on the host). */
 int bpgpu_verification_scalars(bpgpu_ctx *ctx, const uint8_t *challenges, size_t k, size_t n,
                                uint8_t *u_sq, uint8_t *u_inv_sq, uint8_t *s);
+/* InnerProductProof::verify -- src/inner_product_proof.rs:317-372 -- for nb proofs of one length n = 2^k in one call:
+ *   expect_P = a b Q + sum_i a s_i Gf_i G_i + sum_i b s_{n-1-i} Hf_i H_i - sum_j u_j^2 L_j - sum_j u_j^-2 R_j ;  ok[p] = 1 iff expect_P == P
+ * (the vector s of :280-309 stays on the device and is never stored).
+ * Q, P: nb x 64 B; G_factors, H_factors: nb x n x 32 B; G, H: n x 64 B shared by all proofs (shared_gens = 1) or nb x n x 64 B;
+ * L, R: nb x k x 64 B (proof-major); ab: nb x 2 x 32 B (a, b); challenges: nb x k x 32 B, u_1..u_k in creation order, from the
+ * host's transcript replay (:269-278).  ok: nb int32.  expect_P (optional): nb x 64 B, for accepted and rejected proofs alike.
+ * G_factors and H_factors hold exactly n entries per proof: the reference's .take(G.len()) over a longer iterator is not
+ * reproduced.  k >= 32 or n != 2^k: BPGPU_E_LEN (:259-267); a null operand: BPGPU_E_ARG (L, R, challenges may be null when k = 0);
+ * a size one of the MSM routes cannot address: BPGPU_E_LEN, as bpgpu_msm_batch; nb == 0: BPGPU_OK.  A non-canonical scalar or an
+ * off-curve / non-canonical point is BPGPU_E_ARG.  A wrong proof is never an error: ok[p] = 0; so is one with a zero challenge
+ * (the reference's batch inversion has no inverse to give). */
+int bpgpu_ipp_verify_batch(bpgpu_ctx *ctx, size_t nb, size_t n, size_t k, const uint8_t *Q, const uint8_t *G_factors,
+                           const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int shared_gens, const uint8_t *P,
+                           const uint8_t *L, const uint8_t *R, const uint8_t *ab, const uint8_t *challenges, int32_t *ok,
+                           uint8_t *expect_P);
+/* The same on device pointers (bpgpu_malloc), asynchronous on the context's stream: results are valid after bpgpu_sync, and a
+ * malformed operand raises bpgpu_input_flag instead of an error code (the verdicts of such a call mean nothing). */
+int bpgpu_ipp_verify_batch_dev(bpgpu_ctx *ctx, size_t nb, size_t n, size_t k, const void *Q, const void *G_factors,
+                               const void *H_factors, const void *G, const void *H, int shared_gens, const void *P, const void *L,
+                               const void *R, const void *ab, const void *challenges, void *ok, void *expect_P);
+/* Over RESIDENT generators: G, H = the first n of `g`, Q = w * B with B = g's Pedersen base (w: nb x 32 B), as
+ * bpgpu_ipp_begin_gens; the generator half is a table walk.  n above g's capacity: BPGPU_E_GENS. */
+int bpgpu_ipp_verify_gens(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, const uint8_t *w,
+                          const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *P, const uint8_t *L, const uint8_t *R,
+                          const uint8_t *ab, const uint8_t *challenges, int32_t *ok, uint8_t *expect_P);
+/* With the transcript replay on the DEVICE: per proof k x (validate_and_append_point "L", "R"; challenge_scalar "u") from
+ * states_in, the nb 32-byte hash-chain states after innerproduct_domain_sep (the convention of bpgpu_ipp_run_fs); states_out
+ * (optional): the states afterwards.  An identity L or R rejects its proof (transcript.rs validate_and_append_point): ok[p] = 0,
+ * not an error.  g == NULL: Q_or_w = Q and G, H, shared_gens as in bpgpu_ipp_verify_batch; otherwise resident generators and
+ * Q_or_w = w (G, H ignored).  The hash chain is the build's stand-in for merlin's. */
+int bpgpu_ipp_verify_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, const uint8_t *Q_or_w,
+                        const uint8_t *G_factors, const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int shared_gens,
+                        const uint8_t *P, const uint8_t *L, const uint8_t *R, const uint8_t *ab, const uint8_t *states_in,
+                        int32_t *ok, uint8_t *states_out);
 
 /* InnerProductProof::create -- src/inner_product_proof.rs:49-193 -- split at the Fiat-Shamir transcript
  * (which stays on the host) for nb independent proofs advancing in lock-step; all state stays in HBM

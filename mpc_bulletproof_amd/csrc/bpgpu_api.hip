@@ -53,6 +53,12 @@ enum WsSlot : int {
   WS_SCREEN_FLAG,   // screened calls: one input flag per check; mixed combined call: the partials' sum flag
   WS_WP_RED,        // msm_wp_batch: scratch of the reduced instances
   WS_MIXED_STAGE,   // mixed host forms: every group's operands
+  WS_IPPV_STAGE,    // bpgpu_ipp_verify_*: the host forms' operands and results
+  WS_IPPV_HDR,      // ... per-proof header values, reject marks
+  WS_IPPV_SC,       // ... MSM scalars: dense instances, or the generator half over resident generators
+  WS_IPPV_VSC,      // ... resident generators: the scalars of L, R
+  WS_IPPV_PTS,      // ... converted points in instance layout
+  WS_IPPV_SUM,      // ... MSM sums, expect_P when the caller does not ask for it
   WS_COUNT
 };
 
@@ -844,24 +850,25 @@ int bpgpu_msm_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *scalars,
 }
 
 /* ---------------------------------------------------------------- arkworks in-memory forms (k_ark.hip) */
-// sum_i scalars[i] * pts[i] for validated device operands (plain canonical scalars, Montgomery affine points) -> one JacRaw
-static int msm_core_locked(bpgpu_ctx *ctx, size_t n, const uint32_t *dsc, const AffDev *dpts, JacRaw *dsum) {
+// nb dense instances of sum_i scalars[i] * pts[i] for validated device operands (plain canonical scalars, Montgomery affine points,
+// instance-major) -> nb JacRaw
+static int msm_core_locked(bpgpu_ctx *ctx, size_t nb, size_t n, const uint32_t *dsc, const AffDev *dpts, JacRaw *dsum) {
   const size_t pip_min = (size_t)ctx->opt[BPGPU_OPT_PIPPENGER_MIN];
   bool done = false;
-  CK(msm_wp_batch(ctx, 1, n, dsc, dpts, true, dsum, &done));
+  CK(msm_wp_batch(ctx, nb, n, dsc, dpts, true, dsum, &done));
   if (done) return BPGPU_OK;
   const bool pip2_single = ctx->opt[BPGPU_OPT_MSM_PIP2_SINGLE] != 0;
-  if (pip2_single && n >= pip_min && pippenger2_supported(n)) {
+  if (pip2_single && nb == 1 && n >= pip_min && pippenger2_supported(n)) {
     const int c2 = pippenger2_window(n);
     void *dpip;
     CK(ws_get(ctx, WS_PIP, pippenger2_scratch_bytes(n, c2), &dpip));
     pippenger2(ctx->st, dpts, dsc, n, c2, dsum, dpip, ctx->d_flag);
     return BPGPU_OK;
   }
-  if (n >= pip_min && !pippenger_addressable(1, n)) return BPGPU_E_LEN;
+  if (n >= pip_min && !pippenger_addressable(nb, n)) return BPGPU_E_LEN;
   void *dres = nullptr;   // the Straus lanes' results: WS_MSM (the caller holds WS_ARG0..5)
-  if (n < pip_min) CK(ws_get(ctx, WS_MSM, n * sizeof(JacRaw), &dres));
-  return msm_tail(ctx, 1, n, pip_min, dpts, dsc, straus_dense(dpts, dsc), (JacRaw *)dres, dsum);
+  if (n < pip_min) CK(ws_get(ctx, WS_MSM, nb * n * sizeof(JacRaw), &dres));
+  return msm_tail(ctx, nb, n, pip_min, dpts, dsc, straus_dense(dpts, dsc), (JacRaw *)dres, dsum);
 }
 int bpgpu_msm_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, const uint8_t *points_jac_mont, size_t n, uint8_t out_jac_mont[96]) {
   if (!ctx || !out_jac_mont || (n && (!scalars_mont || !points_jac_mont))) return BPGPU_E_ARG;
@@ -881,7 +888,7 @@ int bpgpu_msm_ark(bpgpu_ctx *ctx, const uint8_t *scalars_mont, const uint8_t *po
     scalars_from_ark(ctx->st, (const Words8 *)dsc, (Words8 *)dsc, n, ctx->d_flag);                 // in place
     points_from_ark(ctx->st, (const Words8 *)dpj, (JacRaw *)djac, n, ctx->d_flag);
     batch_normalize(ctx->st, (const JacRaw *)djac, (AffDev *)daff, n, 8);
-    CK(msm_core_locked(ctx, n, (const uint32_t *)dsc, (const AffDev *)daff, (JacRaw *)dsum));
+    CK(msm_core_locked(ctx, 1, n, (const uint32_t *)dsc, (const AffDev *)daff, (JacRaw *)dsum));
   } else {
     HIPCK(ctx, hipMemsetAsync(dsum, 0, sizeof(JacRaw), ctx->st));                                  // Z = 0: the identity
   }
@@ -1184,6 +1191,138 @@ int bpgpu_verification_scalars(bpgpu_ctx *ctx, const uint8_t *challenges, size_t
   scalars_check(ctx->st, w, k, ctx->d_flag);
   verification_scalars(ctx->st, w, k, n, w + k, w + 2 * k, w + 3 * k);
   return checked_download(ctx, {{u_sq, w + k, k * 32}, {u_inv_sq, w + 2 * k, k * 32}, {s, w + 3 * k, n * 32}});
+}
+
+/* ---------------------------------------------------------------- InnerProductProof::verify (k_ippv.hip) */
+namespace {
+struct IppvOps {   // device pointers; Qw: Q (nb points) or, over resident generators, w (nb scalars); ch: challenges or, fs, states_in
+  const void *Qw, *Gf, *Hf, *G, *H, *P, *L, *R, *ab, *ch;
+};
+}
+static int ippv_dims(size_t n, size_t k) { return (k >= 32 || n != ((size_t)1 << k)) ? BPGPU_E_LEN : BPGPU_OK; }   // inner_product_proof.rs:259-267
+// the instance length the variable-base routes get: above 32 terms the window-parallel launches take groups of 16, so the
+// instances are laid out padded (identity points, zero scalars) instead of being copied into a padded layout by msm_wp_batch
+static size_t ippv_stride(size_t terms) { return terms <= 32 ? terms : (terms + 15) / 16 * 16; }
+// device operands -> ok (nb int32), expect_P (optional, nb x 64 B), states_out (fs, optional); asynchronous on ctx->st, malformed
+// operands raise ctx->d_flag (reset by the caller)
+static int ippv_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, bool shared, const IppvOps &in, bool fs,
+                           void *ok, void *expect_P, void *states_out) {
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  if (!ippv_assemble_fits(nb, n)) return BPGPU_E_LEN;
+  const size_t terms = g ? 2 * k : 2 * n + 1 + 2 * k, stride = ippv_stride(terms), fixed = 2 + 2 * n;
+  void *dhdr, *dsc, *dvsc = nullptr, *dpts, *dsum, *dch = nullptr;
+  const size_t hdr_bytes = (nb * (k + 2) * bp::NL * 4 + 63) / 64 * 64;
+  CK(ws_get(ctx, WS_IPPV_HDR, hdr_bytes + nb * 4, &dhdr));
+  int32_t *dreject = (int32_t *)((uint8_t *)dhdr + hdr_bytes);
+  CK(ws_get(ctx, WS_IPPV_SC, nb * (g ? fixed : stride) * 32, &dsc));
+  if (g) CK(ws_get(ctx, WS_IPPV_VSC, nb * stride * 32, &dvsc));
+  CK(ws_get(ctx, WS_IPPV_PTS, nb * stride * sizeof(AffDev), &dpts));
+  CK(ws_get(ctx, WS_IPPV_SUM, nb * (2 * sizeof(JacRaw) + 64 + 4), &dsum));
+  JacRaw *dvar = (JacRaw *)dsum, *dfix = dvar + nb;
+  Words8 *dexp = expect_P ? (Words8 *)expect_P : (Words8 *)(dfix + nb);
+  HIPCK(ctx, hipMemsetAsync(dreject, 0, nb * 4, ctx->st));
+  const Words8 *ch = (const Words8 *)in.ch;
+  if (fs) {
+    CK(ws_get(ctx, WS_FS_CH, nb * (k ? k : 1) * 32, &dch));
+    ippv_transcript(ctx->st, nb, k, (const Words8 *)in.ch, (const Words8 *)in.L, (const Words8 *)in.R, (Words8 *)dch, dreject, (Words8 *)states_out);
+    ch = (const Words8 *)dch;
+  }
+  // scalars: [G | H | Q | L | R | padding] per dense instance; over resident generators [B, B_blinding, G.., H..] and [L | R | padding]
+  Words8 *sc = (Words8 *)dsc, *vsc = g ? (Words8 *)dvsc : sc + 2 * n + 1;
+  IppvHeader h{nb, (int)k, ch, (const Words8 *)in.ab, g ? (const Words8 *)in.Qw : nullptr, (int32_t *)dhdr,
+               g ? sc : sc + 2 * n, g ? sc + 1 : nullptr, g ? fixed : stride, vsc, vsc + k, stride, dreject, ctx->d_flag};
+  ippv_header(ctx->st, h);
+  ippv_assemble(ctx->st, nb, n, k, (const int32_t *)dhdr, (const Words8 *)in.Gf, (const Words8 *)in.Hf, g ? sc + 2 : sc, g ? sc + 2 + n : sc + n,
+                g ? fixed : stride, ctx->d_flag);
+  IppvPoints pa{};
+  int ns = 0;
+  if (!g) {
+    pa.seg[ns++] = {(const Words8 *)in.G, shared ? 0 : n, n, 0};
+    pa.seg[ns++] = {(const Words8 *)in.H, shared ? 0 : n, n, 0};
+    pa.seg[ns++] = {(const Words8 *)in.Qw, 1, 1, 0};
+  }
+  pa.seg[ns++] = {(const Words8 *)in.L, k, k, 0};
+  pa.seg[ns++] = {(const Words8 *)in.R, k, k, 0};
+  pa.seg[ns++] = {(const Words8 *)in.P, 1, 1, 1};
+  pa.nseg = ns; pa.nb = nb; pa.stride = stride; pa.used = terms; pa.extra = 1;
+  pa.dst = (AffDev *)dpts; pa.pad_sc = g ? (Words8 *)dvsc : sc; pa.bad = ctx->d_flag;
+  ippv_points(ctx->st, pa);
+  if (stride) CK(msm_core_locked(ctx, nb, stride, (const uint32_t *)(g ? dvsc : dsc), (const AffDev *)dpts, dvar));
+  if (g) {
+    CK(msm_gens_dev(ctx, g, nb, n, (const uint32_t *)dsc, dfix, ctx->st, WS_MSM2));
+    verify_finalize(ctx->st, dvar, stride ? 1 : 0, dfix, nb, (int32_t *)ok, dexp);   // ok: overwritten by the verdict below
+  } else {
+    jac_to_boundary(ctx->st, dvar, dexp, nb);
+  }
+  ippv_verdict(ctx->st, nb, dexp, (const Words8 *)in.P, dreject, (int32_t *)ok);
+  return launch_ok(ctx);
+}
+// the host-pointer forms after their argument checks: the operands go up in one staging buffer, verdicts (and expect_P /
+// states_out) come back; a malformed operand is BPGPU_E_ARG
+static int ippv_host(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, bool shared, const IppvOps &in, bool fs, int32_t *ok,
+                     uint8_t *expect_P, uint8_t *states_out) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  const size_t gtot = g ? 0 : (shared ? n : nb * n);
+  const size_t sizes[10] = {nb * (g ? 32 : 64), nb * n * 32, nb * n * 32, gtot * 64, gtot * 64, nb * 64, nb * k * 64, nb * k * 64, nb * 64,
+                            fs ? nb * 32 : nb * k * 32};
+  const void *host[10] = {in.Qw, in.Gf, in.Hf, in.G, in.H, in.P, in.L, in.R, in.ab, in.ch};
+  size_t off[11] = {0};
+  for (int i = 0; i < 10; i++) off[i + 1] = off[i] + sizes[i];
+  const size_t o_ok = off[10], o_exp = (o_ok + nb * 4 + 63) / 64 * 64, o_st = o_exp + nb * 64;
+  void *d;
+  CK(ws_get(ctx, WS_IPPV_STAGE, o_st + nb * 32, &d));
+  uint8_t *b = (uint8_t *)d;
+  CK(flag_reset(ctx));
+  for (int i = 0; i < 10; i++) CK(h2d(ctx, b + off[i], host[i], sizes[i]));
+  const IppvOps dev{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], b + off[6], b + off[7], b + off[8], b + off[9]};
+  CK(ippv_dev_locked(ctx, g, nb, n, k, shared, dev, fs, b + o_ok, expect_P ? b + o_exp : nullptr, fs && states_out ? b + o_st : nullptr));
+  return checked_download(ctx, {{ok, b + o_ok, nb * 4}, {expect_P, b + o_exp, expect_P ? nb * 64 : 0},
+                                {states_out, b + o_st, fs && states_out ? nb * 32 : 0}});
+}
+// the operands every form needs (L, R, challenges only from k = 1 on)
+static bool ippv_args(const void *Gf, const void *Hf, const void *P, const void *L, const void *R, const void *ab, const void *ch, size_t k,
+                      bool fs, const void *ok) {
+  return Gf && Hf && P && ab && ok && (fs ? ch != nullptr : (!k || ch)) && (!k || (L && R));
+}
+int bpgpu_ipp_verify_batch(bpgpu_ctx *ctx, size_t nb, size_t n, size_t k, const uint8_t *Q, const uint8_t *G_factors, const uint8_t *H_factors,
+                           const uint8_t *G, const uint8_t *H, int shared_gens, const uint8_t *P, const uint8_t *L, const uint8_t *R,
+                           const uint8_t *ab, const uint8_t *challenges, int32_t *ok, uint8_t *expect_P) {
+  if (!ctx || (nb && (!Q || !G || !H || !ippv_args(G_factors, H_factors, P, L, R, ab, challenges, k, false, ok)))) return BPGPU_E_ARG;
+  CK(ippv_dims(n, k));
+  if (!nb) return BPGPU_OK;
+  return ippv_host(ctx, nullptr, nb, n, k, shared_gens != 0, {Q, G_factors, H_factors, G, H, P, L, R, ab, challenges}, false, ok, expect_P, nullptr);
+}
+int bpgpu_ipp_verify_batch_dev(bpgpu_ctx *ctx, size_t nb, size_t n, size_t k, const void *Q, const void *G_factors, const void *H_factors,
+                               const void *G, const void *H, int shared_gens, const void *P, const void *L, const void *R, const void *ab,
+                               const void *challenges, void *ok, void *expect_P) {
+  if (!ctx || (nb && (!Q || !G || !H || !ippv_args(G_factors, H_factors, P, L, R, ab, challenges, k, false, ok)))) return BPGPU_E_ARG;
+  CK(ippv_dims(n, k));
+  if (!nb) return BPGPU_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call
+  return ippv_dev_locked(ctx, nullptr, nb, n, k, shared_gens != 0, {Q, G_factors, H_factors, G, H, P, L, R, ab, challenges}, false, ok, expect_P,
+                         nullptr);
+}
+int bpgpu_ipp_verify_gens(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, const uint8_t *w, const uint8_t *G_factors,
+                          const uint8_t *H_factors, const uint8_t *P, const uint8_t *L, const uint8_t *R, const uint8_t *ab,
+                          const uint8_t *challenges, int32_t *ok, uint8_t *expect_P) {
+  if (!ctx || !g || (nb && (!w || !ippv_args(G_factors, H_factors, P, L, R, ab, challenges, k, false, ok)))) return BPGPU_E_ARG;
+  CK(ippv_dims(n, k));
+  if (n > g->cap) return BPGPU_E_GENS;
+  if (!nb) return BPGPU_OK;
+  return ippv_host(ctx, g, nb, n, k, true, {w, G_factors, H_factors, nullptr, nullptr, P, L, R, ab, challenges}, false, ok, expect_P, nullptr);
+}
+int bpgpu_ipp_verify_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t n, size_t k, const uint8_t *Q_or_w, const uint8_t *G_factors,
+                        const uint8_t *H_factors, const uint8_t *G, const uint8_t *H, int shared_gens, const uint8_t *P, const uint8_t *L,
+                        const uint8_t *R, const uint8_t *ab, const uint8_t *states_in, int32_t *ok, uint8_t *states_out) {
+  if (!ctx || (nb && (!Q_or_w || (!g && (!G || !H)) || !ippv_args(G_factors, H_factors, P, L, R, ab, states_in, k, true, ok)))) return BPGPU_E_ARG;
+  CK(ippv_dims(n, k));
+  if (g && n > g->cap) return BPGPU_E_GENS;
+  if (!nb) return BPGPU_OK;
+  return ippv_host(ctx, g, nb, n, k, g || shared_gens != 0, {Q_or_w, G_factors, H_factors, g ? nullptr : G, g ? nullptr : H, P, L, R, ab, states_in},
+                   true, ok, nullptr, states_out);
 }
 
 /* ---------------------------------------------------------------- R1CS */

@@ -324,6 +324,37 @@ __global__ void __launch_bounds__(64) k_ipp_round_challenge(size_t nb, uint64_t 
 #pragma unroll
   for (int i = 0; i < 4; i++) states[p * 4 + i] = st[i];
 }
+// The verifier's side of the same rounds (inner_product_proof.rs:269-278), all k of them for nb proofs, one lane each: the proof's
+// L_r, R_r are absorbed through validate_and_append_point, so an identity point marks the proof rejected (its remaining
+// challenges are still drawn: the caller's kernels read them).
+__global__ void __launch_bounds__(64) k_ippv_transcript(size_t nb, size_t k, const Words8 *states_in, const Words8 *L, const Words8 *R,
+                                                        Words8 *challenges, int32_t *reject, Words8 *states_out) {
+  size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  uint64_t st[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) st[i] = (uint64_t)states_in[p].w[2 * i] | ((uint64_t)states_in[p].w[2 * i + 1] << 32);
+  bool identity = false;
+  uint64_t tail[9];
+  tail[0] = 64;
+#pragma unroll 1
+  for (size_t r = 0; r < k; r++) {
+    identity |= load64(L + (p * k + r) * 2, tail + 1);
+    chain_hash<9>(st, 0x00, TR_LABELS[LB_L], tail);
+    identity |= load64(R + (p * k + r) * 2, tail + 1);
+    chain_hash<9>(st, 0x00, TR_LABELS[LB_R], tail);
+    tr_challenge_scalar(st, TR_LABELS[LB_u], &challenges[p * k + r]);
+  }
+  if (identity) reject[p] = 1;
+  if (states_out) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { states_out[p].w[2 * i] = (uint32_t)st[i]; states_out[p].w[2 * i + 1] = (uint32_t)(st[i] >> 32); }
+  }
+}
+void ippv_transcript(hipStream_t st, size_t nb, size_t k, const Words8 *states_in, const Words8 *L, const Words8 *R, Words8 *challenges,
+                     int32_t *reject, Words8 *states_out) {
+  if (nb) hipLaunchKernelGGL(k_ippv_transcript, dim3((nb + 63) / 64), dim3(64), 0, st, nb, k, states_in, L, R, challenges, reject, states_out);
+}
 // The prover's blinding vectors s_L, s_R (r1cs/prover.rs:457-462, 519-527: n random scalars each) drawn ON THE DEVICE from a
 // 32-byte key per prover and phase that the host takes from its RNG at the point where the reference draws the vectors: "BlindVec v1",
 //   block(key, v, j) = the first 128 bytes of Keccak-f[1600] over the 48-byte message key || u64le(v) || u64le(j), padded as keccak256

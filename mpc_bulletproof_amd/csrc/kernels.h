@@ -337,6 +337,33 @@ void mpc_eval(hipStream_t st, size_t nb, size_t n, size_t padded_n, const Words8
 void mpc_ipp_mask(hipStream_t st, size_t nb, size_t h, const Words8 *a, const Words8 *b, const Words8 *trip, Words8 *masked);
 void mpc_ipp_combine(hipStream_t st, size_t nb, size_t h, const Words8 *opened, const Words8 *trip, Words8 *cLR);
 
+// ---- InnerProductProof::verify for nb proofs of one length n = 2^k (k_ippv.hip) -------------------
+// header, a lane per proof: hdr[p] = (k + 2) x 9 int32 (u_j^2, a / prod u, b / prod u: what ippv_assemble reads); the scalars of
+// Q (a b, times w[p] when w is given: Q = w B), L_j (-u_j^2) and R_j (-u_j^-2) as plain words at q_sc[p * q_stride],
+// l_sc / r_sc[p * lr_stride + j]; zero_sc (optional): [p * q_stride] := 0.  reject[p] = 1 for a zero challenge (writes 1 only);
+// *bad |= 1 for a non-canonical challenge, a, b or w.
+struct IppvHeader { size_t nb; int k; const Words8 *challenges, *ab, *w; int32_t *hdr; Words8 *q_sc, *zero_sc; size_t q_stride;
+                    Words8 *l_sc, *r_sc; size_t lr_stride; int32_t *reject; int *bad; };
+void ippv_header(hipStream_t st, const IppvHeader &h);
+// g_sc[p * sc_stride + i] = a s_i Gf[p][i], h_sc[p * sc_stride + i] = b s_{n-1-i} Hf[p][i] (s is not stored); *bad |= 1 for a
+// non-canonical factor.  ippv_assemble_fits: the launch's grid is addressable
+bool ippv_assemble_fits(size_t nb, size_t n);
+void ippv_assemble(hipStream_t st, size_t nb, size_t n, size_t k, const int32_t *hdr, const Words8 *Gf, const Words8 *Hf, Words8 *g_sc,
+                   Words8 *h_sc, size_t sc_stride, int *bad);
+// boundary points -> dst[p * stride + row]: the segments with check_only = 0 fill rows [0, used) in order (segment row q of proof p
+// reads src[p * outer + q]; outer = 0: one array for all proofs), rows [used, stride) become identity points and pad_sc there zero
+// scalars; check_only segments (`extra` rows per proof in all) are validated and not stored.  *bad |= 1 on a malformed point.
+struct IppvSeg { const Words8 *src; size_t outer, cnt; int check_only; };
+struct IppvPoints { IppvSeg seg[6]; int nseg; size_t nb, stride, used, extra; AffDev *dst; Words8 *pad_sc; int *bad; };
+void ippv_points(hipStream_t st, const IppvPoints &a);
+// ok[p] = expect_P[p] == P[p] (64 boundary bytes each) && !reject[p]
+void ippv_verdict(hipStream_t st, size_t nb, const Words8 *expect_xy, const Words8 *P_xy, const int32_t *reject, int32_t *ok);
+// the verifier's transcript replay (k_transcript.hip; inner_product_proof.rs:269-278 after the domain separator), a lane per
+// proof: k x (append_point "L", "R"; challenge_scalar "u").  L, R: nb x k points (proof-major); challenges: nb x k;
+// reject[p] = 1 for an identity L or R (validate_and_append_point; writes 1 only); states_out may alias states_in
+void ippv_transcript(hipStream_t st, size_t nb, size_t k, const Words8 *states_in, const Words8 *L, const Words8 *R, Words8 *challenges,
+                     int32_t *reject, Words8 *states_out);
+
 // ---- wire codec of points (k_codec.hip): 32-byte compressed <-> 64-byte affine boundary form ------
 size_t sqrt_table_bytes();
 void sqrt_tables_build(hipStream_t st, void *tab /* sqrt_table_bytes() */);

@@ -933,8 +933,8 @@ InnerProductProof InnerProductProof::create(Transcript &transcript, const StarkP
   return proof;
 }
 
-InnerProductProof::VerificationScalars InnerProductProof::verification_scalars(size_t n, Transcript &transcript,
-                                                                               std::vector<Scalar> *challenges_out) const {
+// the transcript replay of inner_product_proof.rs:259-278: the challenges u_1..u_k in creation order
+static std::vector<Scalar> ipp_replay(size_t n, Transcript &transcript, const std::vector<StarkPoint> &L_vec, const std::vector<StarkPoint> &R_vec) {
   size_t lg_n = L_vec.size();
   if (lg_n >= 32) throw ProofException(ProofError::VerificationError);                    // :259-264
   if (n != ((size_t)1 << lg_n)) throw ProofException(ProofError::VerificationError);      // :265-267
@@ -945,6 +945,13 @@ InnerProductProof::VerificationScalars InnerProductProof::verification_scalars(s
     transcript.validate_and_append_point("R", R_vec.at(i));
     ch.push_back(transcript.challenge_scalar("u"));
   }
+  return ch;
+}
+
+InnerProductProof::VerificationScalars InnerProductProof::verification_scalars(size_t n, Transcript &transcript,
+                                                                               std::vector<Scalar> *challenges_out) const {
+  size_t lg_n = L_vec.size();
+  std::vector<Scalar> ch = ipp_replay(n, transcript, L_vec, R_vec);
   if (challenges_out) *challenges_out = ch;
   Device &d = Device::default_device();
   auto pc = pack_scalars(ch);
@@ -957,20 +964,39 @@ InnerProductProof::VerificationScalars InnerProductProof::verification_scalars(s
   return v;
 }
 
+// The transcript replay on the host, then ONE bpgpu_ipp_verify_batch call (nb = 1): the vector s and the 2n + 2k + 1 MSM scalars
+// are formed on the device and never cross the bus.
 void InnerProductProof::verify(size_t n, Transcript &transcript, const std::vector<Scalar> &G_factors,
                                const std::vector<Scalar> &H_factors, const StarkPoint &P, const StarkPoint &Q,
                                const std::vector<StarkPoint> &G, const std::vector<StarkPoint> &H) const {
-  auto v = verification_scalars(n, transcript);
-  std::vector<Scalar> sc;
-  std::vector<StarkPoint> pts;
-  sc.push_back(a * b);
-  pts.push_back(Q);
-  for (size_t i = 0; i < n && i < G.size(); i++) { sc.push_back((a * v.s[i]) * G_factors.at(i)); pts.push_back(G[i]); }   // :336-340
-  for (size_t i = 0; i < n && i < H.size(); i++) { sc.push_back((b * v.s[n - 1 - i]) * H_factors.at(i)); pts.push_back(H[i]); }   // :343-348
-  for (size_t i = 0; i < L_vec.size(); i++) { sc.push_back(-v.u_sq[i]); pts.push_back(L_vec[i]); }
-  for (size_t i = 0; i < R_vec.size(); i++) { sc.push_back(-v.u_inv_sq[i]); pts.push_back(R_vec[i]); }
-  StarkPoint expect_P = Device::default_device().msm(sc, pts);
-  if (expect_P != P) throw ProofException(ProofError::VerificationError);
+  if (G.size() < n || H.size() < n) {   // fewer generators than n: the reference's .take(G.len()) sums over those there are, which the
+    auto v = verification_scalars(n, transcript);   // batch call does not reproduce -- the composition of the separate exports does
+    std::vector<Scalar> sc;
+    std::vector<StarkPoint> pts;
+    sc.push_back(a * b);
+    pts.push_back(Q);
+    for (size_t i = 0; i < n && i < G.size(); i++) { sc.push_back((a * v.s[i]) * G_factors.at(i)); pts.push_back(G[i]); }   // :336-340
+    for (size_t i = 0; i < n && i < H.size(); i++) { sc.push_back((b * v.s[n - 1 - i]) * H_factors.at(i)); pts.push_back(H[i]); }   // :343-348
+    for (size_t i = 0; i < L_vec.size(); i++) { sc.push_back(-v.u_sq[i]); pts.push_back(L_vec[i]); }
+    for (size_t i = 0; i < R_vec.size(); i++) { sc.push_back(-v.u_inv_sq[i]); pts.push_back(R_vec[i]); }
+    StarkPoint expect_P = Device::default_device().msm(sc, pts);
+    if (expect_P != P) throw ProofException(ProofError::VerificationError);
+    return;
+  }
+  std::vector<Scalar> ch = ipp_replay(n, transcript, L_vec, R_vec);
+  const size_t k = L_vec.size();
+  if (n) { (void)G_factors.at(n - 1); (void)H_factors.at(n - 1); }   // as the loops of :336-348 would
+  auto gf = pack_scalars(std::vector<Scalar>(G_factors.begin(), G_factors.begin() + n));
+  auto hf = pack_scalars(std::vector<Scalar>(H_factors.begin(), H_factors.begin() + n));
+  auto g = pack_points(std::vector<StarkPoint>(G.begin(), G.begin() + n)), h = pack_points(std::vector<StarkPoint>(H.begin(), H.begin() + n));
+  auto l = pack_points(L_vec), r = pack_points(std::vector<StarkPoint>(R_vec.begin(), R_vec.begin() + k));
+  auto ab = pack_scalars({a, b}), pc = pack_scalars(ch);
+  int32_t ok = 0;
+  Device &d = Device::default_device();
+  d.check(bpgpu_ipp_verify_batch(d.ctx(), 1, n, k, Q.xy.data(), gf.data(), hf.data(), g.data(), h.data(), 1, P.xy.data(), k ? l.data() : nullptr,
+                                 k ? r.data() : nullptr, ab.data(), k ? pc.data() : nullptr, &ok, nullptr),
+          "bpgpu_ipp_verify_batch");
+  if (!ok) throw ProofException(ProofError::VerificationError);
 }
 
 // ================================================================ r1cs ============================

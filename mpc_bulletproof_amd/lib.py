@@ -20,6 +20,7 @@ SYMBOLS = [
     "bpgpu_r1cs_verify_mixed_screened", "bpgpu_r1cs_verify_mixed_screened_dev",
     "bpgpu_mpc_prover_commit", "bpgpu_mpc_prover_polys_mask", "bpgpu_mpc_prover_polys_finish", "bpgpu_mpc_prover_ipp_begin",
     "bpgpu_mpc_ipp_mask", "bpgpu_mpc_ipp_round",
+    "bpgpu_ipp_verify_batch", "bpgpu_ipp_verify_batch_dev", "bpgpu_ipp_verify_gens", "bpgpu_ipp_verify_fs",
 ]
 
 
@@ -396,6 +397,43 @@ class BpGpu:
 
     def ipp_destroy(self, s):
         _lib.bpgpu_ipp_destroy(self.ctx, s)
+
+    # InnerProductProof::verify for nb proofs of one length n = 2^k (include/bpgpu.h bpgpu_ipp_verify_*)
+    @staticmethod
+    def _opt(b):
+        return _buf(b) if b else None
+
+    def ipp_verify_batch(self, nb, n, Q, Gf, Hf, G, H, shared_gens, P, L, R, ab, challenges, want_expect=False, k=None):
+        """-> accept bits [nb] (and expect_P, nb x 64 B, with want_expect).  L, R, challenges: nb x k entries, proof-major."""
+        k = n.bit_length() - 1 if k is None else k
+        ok, ex = (C.c_int32 * max(nb, 1))(), _out(64 * nb) if want_expect else None
+        self._ck(_lib.bpgpu_ipp_verify_batch(self.ctx, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(Q), _buf(Gf), _buf(Hf), _buf(G),
+                                             _buf(H), 1 if shared_gens else 0, _buf(P), self._opt(L), self._opt(R), _buf(ab),
+                                             self._opt(challenges), ok, ex))
+        return (list(ok)[:nb], bytes(ex)[:64 * nb]) if want_expect else list(ok)[:nb]
+
+    def ipp_verify_batch_dev(self, nb, n, k, d_Q, d_Gf, d_Hf, d_G, d_H, shared_gens, d_P, d_L, d_R, d_ab, d_challenges, d_ok, d_expect=None):
+        """device pointers, asynchronous: sync() before reading d_ok; malformed operands raise input_flag()"""
+        self._ck(_lib.bpgpu_ipp_verify_batch_dev(self.ctx, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), d_Q, d_Gf, d_Hf, d_G, d_H,
+                                                 1 if shared_gens else 0, d_P, d_L, d_R, d_ab, d_challenges, d_ok, d_expect))
+
+    def ipp_verify_gens(self, gens, nb, n, w, Gf, Hf, P, L, R, ab, challenges, want_expect=False):
+        """over resident generators: G, H = gens[:n], Q = w * B"""
+        k = n.bit_length() - 1
+        ok, ex = (C.c_int32 * max(nb, 1))(), _out(64 * nb) if want_expect else None
+        self._ck(_lib.bpgpu_ipp_verify_gens(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(w), _buf(Gf), _buf(Hf),
+                                            _buf(P), self._opt(L), self._opt(R), _buf(ab), self._opt(challenges), ok, ex))
+        return (list(ok)[:nb], bytes(ex)[:64 * nb]) if want_expect else list(ok)[:nb]
+
+    def ipp_verify_fs(self, gens, nb, n, Q_or_w, Gf, Hf, G, H, shared_gens, P, L, R, ab, states):
+        """transcript replay on the device from `states` (after innerproduct_domain_sep) -> (accept bits, states_out);
+        gens None: Q and G, H as ipp_verify_batch; else resident generators and w"""
+        k = n.bit_length() - 1
+        ok, so = (C.c_int32 * max(nb, 1))(), _out(32 * nb)
+        self._ck(_lib.bpgpu_ipp_verify_fs(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(Q_or_w), _buf(Gf), _buf(Hf),
+                                          self._opt(G), self._opt(H), 1 if shared_gens else 0, _buf(P), self._opt(L), self._opt(R),
+                                          _buf(ab), _buf(states), ok, so))
+        return list(ok)[:nb], bytes(so)[:32 * nb]
 
     def generator_mul(self, scalars):
         n = len(scalars) // 32

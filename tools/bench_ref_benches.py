@@ -5,15 +5,21 @@
   * benches/r1cs.rs  "prover" / "verifier"  dummy circuit of n = 2^1 .. 2^10 multiplications (benches/r1cs.rs:24-33);
   * benches/generators.rs  "BulletproofGens::new"  sizes 2 << i, i < 10 (and 2^15 for the shuffle).
 Through the host C++ mirror over the C ABI; wall clock per call after one warm-up call.  The CPU column is the oracle's
-single-thread restatement on the smaller sizes."""
+single-thread restatement on the smaller sizes.  Every ipp-prover size is checked before it is printed: byte for byte against the
+oracle up to 2^10, and above (where the oracle's create takes minutes) by bpgpu_ipp_verify_batch accepting the proof against
+P = <a, Gf o G> + <b, Hf o H> + <a, b> Q from the oracle's MSM, with the challenges of a host replay of the transcript."""
 import ctypes as C
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import oracle_lib as o   # noqa: E402
+import pymodel as pm   # noqa: E402
+import mpc_bulletproof_amd as m   # noqa: E402
 
 host = C.CDLL(os.path.join(ROOT, "tests", "host", "libbph_capi.so"))
 label = b"test"
@@ -21,6 +27,7 @@ buf = o._buf
 
 print("== inner_product / ipp-prover (random G, H, Q, factors; generators folded every round)")
 base = o.gens("G", 4096) + o.gens("H", 4096)
+gpu = m.BpGpu(0)
 for lg in range(1, 17):
     n = 1 << lg
     G = (base * ((n + 8191) // 8192))[:64 * n]
@@ -44,8 +51,23 @@ for lg in range(1, 17):
         tc = time.perf_counter() - t0
         assert (bytes(L), bytes(R), bytes(ao), bytes(bo)) == (Lo, Ro, a_o, b_o)
         line += f"   cpu-oracle 1T {tc * 1e3:9.1f} ms  x{tc / tg:6.1f}   (bytes identical)"
+    else:
+        P = o.msm(o.sc_binop(2, a, Gf) + o.sc_binop(2, b, Hf) + o.inner_product(a, b), G + H + Q)
+        t = pm.Transcript(label)
+        t.innerproduct_domain_sep(n)
+        ch = b""
+        for r in range(k):
+            t.append_message(b"L", bytes(L)[64 * r:64 * r + 64])
+            t.append_message(b"R", bytes(R)[64 * r:64 * r + 64])
+            ch += pm.s2b(t.challenge_scalar(b"u"))
+        t0 = time.perf_counter()
+        ok = gpu.ipp_verify_batch(1, n, Q, Gf, Hf, G, H, True, P, bytes(L), bytes(R), bytes(ao) + bytes(bo), ch)
+        tv = time.perf_counter() - t0
+        assert ok == [1], (lg, ok)
+        line += f"   verified on the GPU against the oracle's P ({tv * 1e3:.2f} ms)"
     print(line)
     sys.stdout.flush()
+gpu.close()
 
 print("== r1cs / prover, verifier (dummy circuit of n multiplications)")
 for lg in range(1, 11):
