@@ -22,7 +22,8 @@ namespace {
 struct Slot { void *p = nullptr; size_t cap = 0; };
 
 // Workspace slots (bpgpu_ctx::ws), one grow-only device buffer each.  ws_get may free and reallocate a slot, so no function ws_gets
-// a slot that one of its callers still holds.
+// a slot that one of its callers still holds.  (verify_plan takes the "verifier:" slots, WS_ZPOW and WS_STRAUS on behalf of
+// verify_batch_dev_locked; the launch routes under it take WS_MSM, WS_MSM2 and msm_wp_batch's.)
 enum WsSlot : int {
   // an entry point's operands, results and small scratch (host staging, a lane's batch); the cores below an entry point take the
   // ones it leaves free (msm_batch_dev_locked: 2-4 under msm_batch_locked's 0, 1, 5; verify_wire_locked: 0-2 under the host form's 3-5;
@@ -260,6 +261,15 @@ static int d2h(bpgpu_ctx *ctx, void *h, const void *d, size_t n) {
   return BPGPU_OK;
 }
 static int launch_ok(bpgpu_ctx *ctx) { HIPCK(ctx, hipGetLastError()); return BPGPU_OK; }
+// Work on the context's second stream beside ctx->st: side_fork (st2 waits for what st holds so far), the launches on st2, side_done
+// (marks the end of st2's part), more launches on st, side_join (st waits for the mark)
+static int side_fork(bpgpu_ctx *ctx) {
+  HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
+  HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
+  return BPGPU_OK;
+}
+static int side_done(bpgpu_ctx *ctx) { HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2)); return BPGPU_OK; }
+static int side_join(bpgpu_ctx *ctx) { HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0)); return BPGPU_OK; }
 // the head of an entry point whose launches validate into ctx->d_flag: the flag cleared, then the operands' uploads in order
 struct H2D { void *dev; const void *host; size_t bytes; };
 static int upload_inputs(bpgpu_ctx *ctx, std::initializer_list<H2D> ins) {
@@ -1421,193 +1431,227 @@ int bpgpu_flatten_constraints(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb,
   return checked_download(ctx, {{wL, dL, nb * n * 32}, {wR, dR, nb * n * 32}, {wO, dO, nb * n * 32}, {wV, dV, nb * m * 32}, {wc, dC, wc ? nb * 32 : 0}});
 }
 
-static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
-                                   size_t k, const void *points, const void *scalars, const void *challenges,
-                                   void *ok, void *mega, void *full_sc, const void *chi = nullptr, const size_t *shard = nullptr) {
-  // shard = {rank, world} (nb == 1): this rank's share of ONE proof's mega_check -- the generators and the proof points of its
-  // slice; `mega` receives the partial sum (the ranks all-gather and add them: SURVEY 8e.2), `ok` says whether the PARTIAL is the identity
+/* ---------------------------------------------------------------- per-proof verification: shape, plan, one function per launch route */
+static size_t verify_nvar(const bpgpu_circuit *c, size_t k) { return 11 + c->m + 2 * k; }   // proof points of one proof
+// (k < 32) padded_n = 2^k must be next_pow2(n), the first phase n1 of the n multipliers, and the generators must reach that far
+static int verify_shape(const bpgpu_circuit *c, const bpgpu_gens *g, size_t n1, size_t k) {
+  const size_t np = (size_t)1 << k, n = c->n;
+  if (n > np || n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;
+  return np > g->cap ? BPGPU_E_GENS : BPGPU_OK;
+}
+namespace {
+struct VerifyOperands { const void *points, *scalars, *challenges; void *ok, *mega, *full_sc; };
+struct VarRange { size_t lo, hi; };   // a range of one proof's points
+// What one call of verify_batch_dev_locked works with, filled once by verify_plan: the sizes, the workspace slots it holds for the
+// routes (they take WS_MSM, WS_MSM2 and msm_wp_batch's on top) and what picks the route.
+struct VerifyPlan {
+  size_t nb, np, nvar;
+  const size_t *shard;      // {rank, world} (nb == 1), or nullptr
+  VerifyDims d;
+  void *dpts, *dfix, *dvar, *dzp, *dvres, *dfres, *dstr;   // WS_VPTS, WS_VFIX, WS_VVAR, WS_ZPOW, WS_VVRES, WS_VFRES, WS_STRAUS
+  int32_t *dbadsc, *dbadpt; // WS_VBITS: per-proof canonicity bits of the scalar assembly (every entry is written by the kernel: no
+                            // reset) | per-proof malformed-point bits of the Straus / separate-launch routes
+  bool one_chunk;           // the generator half is a single chunk of the fixed-base MSM ...
+  bool fused_fixed;         // ... and rides in the window-parallel back launch: <= 16 384 (generator, window) pairs per proof
+  size_t fparts;            // partial sums per proof it leaves there (nb x parts when it is walked a proof per lane: BPGPU_OPT_FIXED_CHUNK_GENS)
+  bool no_fuse, no_wp;      // BPGPU_OPT_VERIFY_NO_FUSE != 0, BPGPU_OPT_VERIFY_WINDOW_PARALLEL == 0
+  int vnp;                  // Straus routes: points per lane, sharing one doubling chain (BPGPU_OPT_VERIFY_STRAUS_NP) ...
+  size_t lanes, rem, nres;  // ... lanes per proof, leftover points (one per lane), sums per proof = lanes + rem
+};
+}
+// shard = {rank, world} (nb == 1): this rank's share of ONE proof's mega_check -- the generators and the proof points of its
+// slice; `mega` receives the partial sum (the ranks all-gather and add them: SURVEY 8e.2), `ok` says whether the PARTIAL is the identity
+static int verify_plan(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k, const void *chi,
+                       const size_t *shard, VerifyPlan &p) {
   if (k >= 32) return BPGPU_E_LEN;
   if (shard && (nb != 1 || !shard[1] || shard[0] >= shard[1])) return BPGPU_E_ARG;
   if ((c->nchi != 0) != (chi != nullptr)) return BPGPU_E_ARG;   // a parametric circuit needs its gadget challenges, and only it
-  size_t np = (size_t)1 << k, n = c->n, m = c->m;
-  if (n > np || n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;   // padded_n = next_pow2(n)
-  if (np > g->cap) return BPGPU_E_GENS;
-  if (!nb) return BPGPU_OK;
+  CK(verify_shape(c, g, n1, k));
+  if (!nb) return BPGPU_OK;     // (nothing is planned: the caller returns before any HIP call)
   HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t nvar = 11 + m + 2 * k, nfix = 2 + 2 * np;
-  void *dpts, *dfix, *dvar, *dzp, *dvres, *dfres;
-  CK(ws_get(ctx, WS_VPTS, nb * nvar * sizeof(AffDev), &dpts));
-  CK(ws_get(ctx, WS_VFIX, nb * nfix * 32, &dfix));
-  CK(ws_get(ctx, WS_VVAR, nb * nvar * 32, &dvar));
-  VerifyDims d{nb, n1, n, np, k, m, (const Words8 *)chi, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
-  CK(ws_get(ctx, WS_ZPOW, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
-  CK(ws_get(ctx, WS_VVRES, nb * nvar * sizeof(JacRaw), &dvres));
-  // (nb x parts partial sums when the generator half is walked a proof per lane: BPGPU_OPT_FIXED_CHUNK_GENS)
-  size_t fparts = 1;
-  if (fixed_msm_chunks(g->c, np, nb) == 1 && verify_wp_supported(nb, nvar, g->c, np)) {
+  const size_t np = (size_t)1 << k, nvar = verify_nvar(c, k), nfix = 2 + 2 * np;
+  p.nb = nb; p.np = np; p.nvar = nvar; p.shard = shard;
+  CK(ws_get(ctx, WS_VPTS, nb * nvar * sizeof(AffDev), &p.dpts));
+  CK(ws_get(ctx, WS_VFIX, nb * nfix * 32, &p.dfix));
+  CK(ws_get(ctx, WS_VVAR, nb * nvar * 32, &p.dvar));
+  p.d = VerifyDims{nb, n1, c->n, np, k, c->m, (const Words8 *)chi, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
+  CK(ws_get(ctx, WS_ZPOW, verify_scalars_scratch_ints(circuit_dev(c), p.d) * 4, &p.dzp));
+  CK(ws_get(ctx, WS_VVRES, nb * nvar * sizeof(JacRaw), &p.dvres));
+  p.one_chunk = fixed_msm_chunks(g->c, np, nb) == 1;
+  p.fused_fixed = p.one_chunk && verify_wp_supported(nb, nvar, g->c, np);
+  p.fparts = 1;
+  if (p.fused_fixed) {
     VerifyWp vt{};
-    vt.nb = nb;
-    vt.latency_mode = ctx->latency_mode;
+    vt.nb = nb; vt.latency_mode = ctx->latency_mode;
     wp_options(ctx, vt);
-    fparts = verify_wp_fixed_parts(vt, np);
+    p.fparts = verify_wp_fixed_parts(vt, np);
   }
-  CK(ws_get(ctx, WS_VFRES, nb * fparts * sizeof(JacRaw), &dfres));
-  void *dstr;
-  CK(straus_ws(ctx, 4, nb * nvar, &dstr));
-  // per-proof canonicity bits of the scalar assembly (every entry is written by the kernel: no reset)
-  void *dbadsc;
-  CK(ws_get(ctx, WS_VBITS, 2 * nb * sizeof(int32_t), &dbadsc));
-  int32_t *dbadpt = (int32_t *)dbadsc + nb;   // per-proof malformed-point bits of the Straus / separate-launch paths
-  // default: window-parallel variable-base part -- front [tables | inversion pass], scalars, windows, groups,
-  // back [Horner | fixed-base MSMs], verdict (k_ec.hip).  Every launch is on ctx->st.
-  const bool no_fuse = ctx->opt[BPGPU_OPT_VERIFY_NO_FUSE] != 0;
-  const bool no_wp = ctx->opt[BPGPU_OPT_VERIFY_WINDOW_PARALLEL] == 0;
-  // The generator half rides in the back launch when it is small (<= 16 384 (generator, window) pairs per proof, one chunk);
-  // otherwise -- few proofs of a mid-size circuit, or a table window the fused kernel is not built for -- it is its own
-  // chunked launch ahead of the Horner pass.  The window kernel walks a proof's points serially in every window lane: up to
-  // 256 proof points (the 2^14-shuffle's 32 809 take the Straus launches below).
-  const bool fused_fixed = fixed_msm_chunks(g->c, np, nb) == 1 && verify_wp_supported(nb, nvar, g->c, np);
-  if (!no_fuse && !no_wp && nvar && (fused_fixed || nvar <= 256)) {
-    void *dwp;
-    CK(ws_get(ctx, WS_MSM, verify_wp_scratch_bytes(nb, nvar), &dwp));
-    VerifyWp v{(const AffDev *)points, nb, nvar, dwp, ctx->d_flag, (const int32_t *)dbadsc, ctx->latency_mode, false, (int)ctx->opt[BPGPU_OPT_TABLE_NP]};
-    wp_options(ctx, v);
-    if (!verify_wp_layout_fits(v)) { ctx->err = "internal: window-parallel scratch layout exceeds its buffer (verify)"; return BPGPU_E_DEVICE; }
-    int32_t *aux = nullptr;
-    size_t aux_stride = 0;
-    const bool fuse_prep = verify_scalars_aux(circuit_dev(c), d, (int32_t *)dzp, &aux, &aux_stride);
-    const bool fast = fuse_prep && verify_scalars_fast_shape(circuit_dev(c), d);   // wave-sized proofs: the serial part of the assembly in the front launch's lanes
-    { ProfScope ps(ctx, 8, ctx->st);
-      verify_wp_front_launch(ctx->st, v, d, (const Words8 *)challenges, aux, aux_stride, fuse_prep, fast ? (const Words8 *)scalars : nullptr,
-                             fast ? (Words8 *)dfix : nullptr, fast ? (Words8 *)dvar : nullptr, fast ? (Words8 *)full_sc : nullptr); }
-    { ProfScope ps(ctx, 0, ctx->st);
-      verify_scalars(ctx->st, circuit_dev(c), d, (const Words8 *)challenges, (const Words8 *)scalars, (Words8 *)dfix,
-                     (Words8 *)dvar, (Words8 *)full_sc, (int32_t *)dzp, ctx->d_flag, (int32_t *)dbadsc, fuse_prep, fast); }
-    if (shard) {   // a small proof: the other ranks' terms are simply zeroed
-      size_t slo, shi, vlo, vhi;
-      shard_bounds(np, shard[0], shard[1], &slo, &shi);
-      shard_bounds(nvar, shard[0], shard[1], &vlo, &vhi);
-      shard_mask(ctx->st, (Words8 *)dfix, np, slo, shi, shard[0] == 0, (Words8 *)dvar, nvar, vlo, vhi);
-    }
-    // Latency mode with a second stream: the generator half needs nothing but the scalars, so it runs BESIDE the window sums,
-    // the first Horner stage and the Horner pass instead of sharing the back launch with the wave-per-proof Horner rows (which
-    // then have the SIMDs to themselves): a lone batch's chain loses the ~0.15 ms the two halves spent taking turns.
-    const bool side = fused_fixed && ctx->latency_mode && ctx->st2 != ctx->st && !shard;
-    if (side) {
-      HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
-      HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
-      { ProfScope ps(ctx, 1, ctx->st2);
-        CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, WS_MSM2, 64)); }
-      HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
-    }
-    { ProfScope ps(ctx, 7, ctx->st);
-      verify_wp_windows(ctx->st, v, (const uint32_t *)dvar); }
-    { ProfScope ps(ctx, 9, ctx->st);
-      verify_wp_groups(ctx->st, v); }
-    if (!fused_fixed) { ProfScope ps(ctx, 1, ctx->st);
-      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st, WS_MSM2)); }
-    { ProfScope ps(ctx, 10, ctx->st);
-      verify_wp_back(ctx->st, v, g->c, fused_fixed && !side ? g->table : nullptr, np, g->cap, (const uint32_t *)dfix, (2 + 2 * np) * 8, (JacRaw *)dfres); }
-    if (side) HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0));
-    { ProfScope ps(ctx, 11, ctx->st);
-      verify_wp_verdict(ctx->st, v, (const JacRaw *)dfres, (int32_t *)ok, (Words8 *)mega, fused_fixed && !side ? verify_wp_fixed_parts(v, np) : 1); }
-    return launch_ok(ctx);
-  }
-  // scalar assembly, then fixed-base part on st2 while st runs the variable-base part
-  // (canonicity of the scalars and challenges is checked inside verify_scalars)
-  HIPCK(ctx, hipMemsetAsync(dbadpt, 0, nb * sizeof(int32_t), ctx->st));
-  {
-    ProfScope ps(ctx, 0, ctx->st);
-    verify_scalars(ctx->st, circuit_dev(c), d, (const Words8 *)challenges, (const Words8 *)scalars, (Words8 *)dfix,
-                   (Words8 *)dvar, (Words8 *)full_sc, (int32_t *)dzp, ctx->d_flag, (int32_t *)dbadsc);
-  }
-  size_t vlo = 0, vhi = nvar;
-  if (shard) {     // generator half: the other ranks' scalars are zeroed (a zero digit costs the table-lookup lanes nothing but the
-    size_t slo, shi;   // walk); proof-point half: only this rank's slice of the points is touched at all (below)
-    shard_bounds(np, shard[0], shard[1], &slo, &shi);
-    shard_bounds(nvar, shard[0], shard[1], &vlo, &vhi);
-    shard_mask(ctx->st, (Words8 *)dfix, np, slo, shi, shard[0] == 0, (Words8 *)dvar, nvar, vlo, vhi);
-  }
-  // proof points: `vnp` points per lane share one doubling chain (lanes per proof = ceil(nvar / vnp)).  Lanes
-  // are ROLE-major (lane = role * nb + proof): the 64 lanes of a wave hold the same proof element of 64 proofs,
-  // so the identity points of 1-phase proofs (A_I2, A_O2, S2) are skipped wave-uniformly inside k_straus.
+  CK(ws_get(ctx, WS_VFRES, nb * p.fparts * sizeof(JacRaw), &p.dfres));
+  CK(straus_ws(ctx, 4, nb * nvar, &p.dstr));
+  CK(ws_get(ctx, WS_VBITS, 2 * nb * sizeof(int32_t), (void **)&p.dbadsc));
+  p.dbadpt = p.dbadsc + nb;
+  p.no_fuse = ctx->opt[BPGPU_OPT_VERIFY_NO_FUSE] != 0;
+  p.no_wp = ctx->opt[BPGPU_OPT_VERIFY_WINDOW_PARALLEL] == 0;
   const int vnp_opt = (int)ctx->opt[BPGPU_OPT_VERIFY_STRAUS_NP];
-  const int vnp = vnp_opt < 1 ? 1 : (vnp_opt > 4 ? 4 : vnp_opt);
-  const size_t lanes = nvar / vnp, rem = nvar - lanes * vnp;   // `rem` leftover points run one per lane
-  const size_t nres = lanes + rem;
-  StrausArgs am{}, ar{};
-  for (int j = 0; j < vnp; j++) {
-    am.pts[j] = (AffDev *)dpts + j * lanes; am.pt_stride[j] = nvar; am.pt_outer[j] = 1;
-    am.sc[j] = (uint32_t *)dvar + j * lanes * 8; am.sc_stride[j] = nvar * 8; am.sc_outer[j] = 8;
+  p.vnp = vnp_opt < 1 ? 1 : (vnp_opt > 4 ? 4 : vnp_opt);
+  p.lanes = nvar / p.vnp; p.rem = nvar - p.lanes * p.vnp; p.nres = p.lanes + p.rem;
+  return BPGPU_OK;
+}
+// A shard's share of the proof: the other ranks' generator and proof-point scalars are zeroed (a zero digit costs the table-lookup
+// lanes nothing but the walk).  -> this rank's range of the proof points (all of them without a shard)
+static VarRange verify_shard_mask(bpgpu_ctx *ctx, const VerifyPlan &p) {
+  VarRange v{0, p.nvar};
+  if (p.shard) {
+    size_t slo, shi;
+    shard_bounds(p.np, p.shard[0], p.shard[1], &slo, &shi);
+    shard_bounds(p.nvar, p.shard[0], p.shard[1], &v.lo, &v.hi);
+    shard_mask(ctx->st, (Words8 *)p.dfix, p.np, slo, shi, p.shard[0] == 0, (Words8 *)p.dvar, p.nvar, v.lo, v.hi);
   }
-  am.inner = nb; am.out_outer = 1; am.out_stride = nres;
-  ar.pts[0] = (AffDev *)dpts + vnp * lanes; ar.pt_stride[0] = nvar; ar.pt_outer[0] = 1;
-  ar.sc[0] = (uint32_t *)dvar + vnp * lanes * 8; ar.sc_stride[0] = nvar * 8; ar.sc_outer[0] = 8;
-  ar.inner = nb; ar.out_outer = 1; ar.out_stride = nres;
-  bool fused = false;
-  if (nb == 1 && !no_wp && !no_fuse && nvar <= ((size_t)1 << 16)) {
-    // ONE large proof (the 2^14-shuffle: 32 809 proof points): its variable-base half as 16-point groups through the window-
-    // parallel launches (msm_wp_batch) instead of a Straus lane per 4 points, a one-point remainder launch and a 256-deep
-    // serial sum (1.9 + 0.9 + 1.15 ms -> 0.8 ms); the generator half runs on the second stream as below.
-    HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
-    HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
-    { ProfScope ps(ctx, 1, ctx->st2);
-      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2, WS_MSM2)); }
-    HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
-    bool done = false;
-    { ProfScope ps(ctx, 3, ctx->st);
-      if (vhi > vlo) CK(msm_wp_batch(ctx, 1, vhi - vlo, (const uint8_t *)dvar + vlo * 32, (const uint8_t *)points + vlo * 64, false, (JacRaw *)dvres, &done,
-                                     (int *)dbadpt, (size_t)1 << 16));
-      else { HIPCK(ctx, hipMemsetAsync(dvres, 0, sizeof(JacRaw), ctx->st)); done = true; }    // (zero limbs = the identity)
-    }
-    HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0));
-    if (done) {
-      ProfScope ps(ctx, 4, ctx->st);
-      verify_finalize(ctx->st, (JacRaw *)dvres, 1, (JacRaw *)dfres, nb, (int32_t *)ok, (Words8 *)mega, (const int32_t *)dbadsc, dbadpt);
-      return launch_ok(ctx);
-    }
+  return v;
+}
+// the generator half on the second stream, beside what ctx->st runs until side_join (part_slot: its chunk partials)
+static int verify_gens_on_side(bpgpu_ctx *ctx, const bpgpu_gens *g, const VerifyPlan &p, WsSlot part_slot = WS_MSM, int lpm = 0) {
+  CK(side_fork(ctx));
+  { ProfScope ps(ctx, 1, ctx->st2);
+    CK(msm_gens_dev(ctx, g, p.nb, p.np, (const uint32_t *)p.dfix, (JacRaw *)p.dfres, ctx->st2, part_slot, lpm)); }
+  return side_done(ctx);
+}
+// Default route: window-parallel variable-base part -- front [tables | inversion pass], scalars, windows, groups,
+// back [Horner | fixed-base MSMs], verdict (k_ec.hip).  Every launch is on ctx->st.
+// The generator half rides in the back launch when it is small (p.fused_fixed); otherwise -- few proofs of a mid-size circuit, or a
+// table window the fused kernel is not built for -- it is its own chunked launch ahead of the Horner pass.
+static int verify_route_wp(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const VerifyPlan &p, const VerifyOperands &o) {
+  const size_t nb = p.nb, np = p.np, nvar = p.nvar;
+  const VerifyDims &d = p.d;
+  void *dwp;
+  CK(ws_get(ctx, WS_MSM, verify_wp_scratch_bytes(nb, nvar), &dwp));
+  VerifyWp v{(const AffDev *)o.points, nb, nvar, dwp, ctx->d_flag, p.dbadsc, ctx->latency_mode, false, (int)ctx->opt[BPGPU_OPT_TABLE_NP]};
+  wp_options(ctx, v);
+  if (!verify_wp_layout_fits(v)) { ctx->err = "internal: window-parallel scratch layout exceeds its buffer (verify)"; return BPGPU_E_DEVICE; }
+  int32_t *aux = nullptr; size_t aux_stride = 0;
+  const bool fuse_prep = verify_scalars_aux(circuit_dev(c), d, (int32_t *)p.dzp, &aux, &aux_stride);
+  const bool fast = fuse_prep && verify_scalars_fast_shape(circuit_dev(c), d);   // wave-sized proofs: the serial part of the assembly in the front launch's lanes
+  { ProfScope ps(ctx, 8, ctx->st);
+    verify_wp_front_launch(ctx->st, v, d, (const Words8 *)o.challenges, aux, aux_stride, fuse_prep, fast ? (const Words8 *)o.scalars : nullptr,
+                           fast ? (Words8 *)p.dfix : nullptr, fast ? (Words8 *)p.dvar : nullptr, fast ? (Words8 *)o.full_sc : nullptr); }
+  { ProfScope ps(ctx, 0, ctx->st);
+    verify_scalars(ctx->st, circuit_dev(c), d, (const Words8 *)o.challenges, (const Words8 *)o.scalars, (Words8 *)p.dfix,
+                   (Words8 *)p.dvar, (Words8 *)o.full_sc, (int32_t *)p.dzp, ctx->d_flag, p.dbadsc, fuse_prep, fast); }
+  verify_shard_mask(ctx, p);   // a small proof: the other ranks' terms are simply zeroed (every rank walks all the points)
+  // Latency mode with a second stream: the generator half needs nothing but the scalars, so it runs BESIDE the window sums,
+  // the first Horner stage and the Horner pass instead of sharing the back launch with the wave-per-proof Horner rows (which
+  // then have the SIMDs to themselves): a lone batch's chain loses the ~0.15 ms the two halves spent taking turns.
+  const bool side = p.fused_fixed && ctx->latency_mode && ctx->st2 != ctx->st && !p.shard;
+  const bool in_back = p.fused_fixed && !side;
+  if (side) CK(verify_gens_on_side(ctx, g, p, WS_MSM2, 64));
+  { ProfScope ps(ctx, 7, ctx->st); verify_wp_windows(ctx->st, v, (const uint32_t *)p.dvar); }
+  { ProfScope ps(ctx, 9, ctx->st); verify_wp_groups(ctx->st, v); }
+  if (!p.fused_fixed) { ProfScope ps(ctx, 1, ctx->st);
+    CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)p.dfix, (JacRaw *)p.dfres, ctx->st, WS_MSM2)); }
+  { ProfScope ps(ctx, 10, ctx->st);
+    verify_wp_back(ctx->st, v, g->c, in_back ? g->table : nullptr, np, g->cap, (const uint32_t *)p.dfix, (2 + 2 * np) * 8, (JacRaw *)p.dfres); }
+  if (side) CK(side_join(ctx));
+  { ProfScope ps(ctx, 11, ctx->st);
+    verify_wp_verdict(ctx->st, v, (const JacRaw *)p.dfres, (int32_t *)o.ok, (Words8 *)o.mega, in_back ? p.fparts : 1); }
+  return BPGPU_OK;
+}
+// The head of the three routes below: scalar assembly (canonicity of the scalars and challenges is checked inside verify_scalars),
+// then the shard's mask.  -> this rank's range of the proof points
+static int verify_straus_scalars(bpgpu_ctx *ctx, const bpgpu_circuit *c, const VerifyPlan &p, const VerifyOperands &o, VarRange *var) {
+  const size_t nb = p.nb;
+  int32_t *dbadpt = p.dbadpt;
+  HIPCK(ctx, hipMemsetAsync(dbadpt, 0, nb * sizeof(int32_t), ctx->st));
+  { ProfScope ps(ctx, 0, ctx->st);
+    verify_scalars(ctx->st, circuit_dev(c), p.d, (const Words8 *)o.challenges, (const Words8 *)o.scalars, (Words8 *)p.dfix,
+                   (Words8 *)p.dvar, (Words8 *)o.full_sc, (int32_t *)p.dzp, ctx->d_flag, p.dbadsc); }
+  *var = verify_shard_mask(ctx, p);
+  return BPGPU_OK;
+}
+// ... and their tail: the nres sums of a proof's points + its generator half -> ok, mega
+static void verify_finalize_launch(bpgpu_ctx *ctx, const VerifyPlan &p, const VerifyOperands &o, size_t nres) {
+  ProfScope ps(ctx, 4, ctx->st);
+  verify_finalize(ctx->st, (JacRaw *)p.dvres, nres, (JacRaw *)p.dfres, p.nb, (int32_t *)o.ok, (Words8 *)o.mega, p.dbadsc, p.dbadpt);
+}
+// ONE large proof (the 2^14-shuffle: 32 809 proof points): its variable-base half as 16-point groups through the window-
+// parallel launches (msm_wp_batch) instead of a Straus lane per 4 points, a one-point remainder launch and a 256-deep
+// serial sum (1.9 + 0.9 + 1.15 ms -> 0.8 ms); the generator half runs on the second stream.  Only this rank's slice `var` of the
+// points is touched at all.  *done = false: msm_wp_batch declined, the Straus routes take over.
+static int verify_route_large(bpgpu_ctx *ctx, const bpgpu_gens *g, const VerifyPlan &p, const VerifyOperands &o, VarRange var, bool *done) {
+  void *dvres = p.dvres;
+  CK(verify_gens_on_side(ctx, g, p, WS_MSM2));
+  *done = false;
+  { ProfScope ps(ctx, 3, ctx->st);
+    if (var.hi > var.lo) CK(msm_wp_batch(ctx, 1, var.hi - var.lo, (const uint8_t *)p.dvar + var.lo * 32, (const uint8_t *)o.points + var.lo * 64, false,
+                                         (JacRaw *)dvres, done, (int *)p.dbadpt, (size_t)1 << 16));
+    else { HIPCK(ctx, hipMemsetAsync(dvres, 0, sizeof(JacRaw), ctx->st)); *done = true; }    // (zero limbs = the identity)
   }
-  if (!no_fuse && lanes && fixed_msm_chunks(g->c, np, nb) == 1) {
-    // one launch for both halves of the MSM, reading the proof points straight from the ABI bytes
-    StrausArgs af = am;
-    for (int j = 0; j < vnp; j++) af.pts[j] = (const AffDev *)points + j * lanes;
-    af.from_boundary = 1; af.bad = ctx->d_flag; af.bad_inner = dbadpt;
-    af.prio = 0;
-    ProfScope ps(ctx, 6, ctx->st);
-    fused = verify_msm_fused(ctx->st, vnp, af, (JacRaw *)dvres, nb * lanes, dstr, g->c, g->table, np, g->cap,
-                             (const uint32_t *)dfix, (2 + 2 * np) * 8, (JacRaw *)dfres, nb);
-    if (fused && rem) {
-      StrausArgs bf = ar;
-      bf.pts[0] = (const AffDev *)points + vnp * lanes;
-      bf.from_boundary = 1; bf.bad = ctx->d_flag; bf.bad_inner = dbadpt;
+  CK(side_join(ctx));
+  if (*done) verify_finalize_launch(ctx, p, o, 1);
+  return BPGPU_OK;
+}
+// Straus lanes over `npl` points each of every proof's points from `first` on (npl = p.vnp: the p.lanes full lanes; 1: the leftover
+// points).  Lanes are ROLE-major (lane = role * nb + proof): the 64 lanes of a wave hold the same proof element of 64 proofs, so the
+// identity points of 1-phase proofs (A_I2, A_O2, S2) are skipped wave-uniformly inside k_straus.
+// bad != nullptr: pts are the ABI bytes, validated and converted in the launch
+static StrausArgs verify_straus_args(const VerifyPlan &p, const AffDev *pts, size_t first, int npl, int *bad = nullptr) {
+  StrausArgs a{};
+  for (int j = 0; j < npl; j++) {
+    a.pts[j] = pts + first + j * p.lanes; a.pt_stride[j] = p.nvar; a.pt_outer[j] = 1;
+    a.sc[j] = (uint32_t *)p.dvar + (first + j * p.lanes) * 8; a.sc_stride[j] = p.nvar * 8; a.sc_outer[j] = 8;
+  }
+  a.inner = p.nb; a.out_outer = 1; a.out_stride = p.nres;
+  if (bad) { a.from_boundary = 1; a.bad = bad; a.bad_inner = p.dbadpt; }
+  return a;
+}
+// One launch for both halves of the MSM, reading the proof points straight from the ABI bytes (+ one for the leftover points).
+// *done = false: this (vnp, c, size) combination has no fused kernel, the separate launches take over.
+static int verify_route_fused(bpgpu_ctx *ctx, const bpgpu_gens *g, const VerifyPlan &p, const VerifyOperands &o, bool *done) {
+  const size_t nb = p.nb, np = p.np;
+  *done = false;
+  if (!p.lanes) return BPGPU_OK;
+  { ProfScope ps(ctx, 6, ctx->st);
+    *done = verify_msm_fused(ctx->st, p.vnp, verify_straus_args(p, (const AffDev *)o.points, 0, p.vnp, ctx->d_flag), (JacRaw *)p.dvres, nb * p.lanes,
+                             p.dstr, g->c, g->table, np, g->cap, (const uint32_t *)p.dfix, (2 + 2 * np) * 8, (JacRaw *)p.dfres, nb);
+    if (*done && p.rem) {
       void *dstr2;
-      CK(ws_get(ctx, WS_MSM, straus_scratch_bytes(1, nb * rem), &dstr2));
-      straus(ctx->st, 1, bf, (JacRaw *)dvres + lanes, nb * rem, dstr2);
+      CK(ws_get(ctx, WS_MSM, straus_scratch_bytes(1, nb * p.rem), &dstr2));
+      straus(ctx->st, 1, verify_straus_args(p, (const AffDev *)o.points, p.vnp * p.lanes, 1, ctx->d_flag), (JacRaw *)p.dvres + p.lanes, nb * p.rem, dstr2);
     }
   }
-  if (!fused) {
-    HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
-    HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
-    {
-      ProfScope ps(ctx, 1, ctx->st2);
-      CK(msm_gens_dev(ctx, g, nb, np, (const uint32_t *)dfix, (JacRaw *)dfres, ctx->st2));
-    }
-    HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
-    {
-      ProfScope ps(ctx, 2, ctx->st);
-      points_from_boundary(ctx->st, (const Words8 *)points, (AffDev *)dpts, nb * nvar, ctx->d_flag, dbadpt, nvar);
-    }
-    {
-      ProfScope ps(ctx, 3, ctx->st);
-      if (lanes) straus(ctx->st, vnp, am, (JacRaw *)dvres, nb * lanes, dstr);
-      if (rem) straus(ctx->st, 1, ar, (JacRaw *)dvres + lanes, nb * rem, dstr);
-    }
-    HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0));
-  }
-  {
-    ProfScope ps(ctx, 4, ctx->st);
-    verify_finalize(ctx->st, (JacRaw *)dvres, nres, (JacRaw *)dfres, nb, (int32_t *)ok, (Words8 *)mega, (const int32_t *)dbadsc, dbadpt);
-  }
+  if (*done) verify_finalize_launch(ctx, p, o, p.nres);
+  return BPGPU_OK;
+}
+// Separate launches: the fixed-base part on st2 while st converts the proof points and runs their Straus lanes
+static int verify_route_separate(bpgpu_ctx *ctx, const bpgpu_gens *g, const VerifyPlan &p, const VerifyOperands &o) {
+  const size_t nb = p.nb, nvar = p.nvar;
+  const AffDev *dpts = (const AffDev *)p.dpts;
+  CK(verify_gens_on_side(ctx, g, p));
+  { ProfScope ps(ctx, 2, ctx->st);
+    points_from_boundary(ctx->st, (const Words8 *)o.points, (AffDev *)p.dpts, nb * nvar, ctx->d_flag, p.dbadpt, nvar); }
+  { ProfScope ps(ctx, 3, ctx->st);
+    if (p.lanes) straus(ctx->st, p.vnp, verify_straus_args(p, dpts, 0, p.vnp), (JacRaw *)p.dvres, nb * p.lanes, p.dstr);
+    if (p.rem) straus(ctx->st, 1, verify_straus_args(p, dpts, p.vnp * p.lanes, 1), (JacRaw *)p.dvres + p.lanes, nb * p.rem, p.dstr); }
+  CK(side_join(ctx));
+  verify_finalize_launch(ctx, p, o, p.nres);
+  return BPGPU_OK;
+}
+static int verify_batch_dev_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                   size_t k, const void *points, const void *scalars, const void *challenges,
+                                   void *ok, void *mega, void *full_sc, const void *chi = nullptr, const size_t *shard = nullptr) {
+  VerifyPlan p;
+  CK(verify_plan(ctx, g, c, nb, n1, k, chi, shard, p));
+  if (!nb) return BPGPU_OK;
+  const VerifyOperands o{points, scalars, challenges, ok, mega, full_sc};
+  const bool wp = !p.no_fuse && !p.no_wp;
+  // The window kernel walks a proof's points serially in every window lane: up to 256 proof points, unless the generator half
+  // rides along (the 2^14-shuffle's 32 809 take the routes below)
+  if (wp && p.nvar && (p.fused_fixed || p.nvar <= 256)) { CK(verify_route_wp(ctx, g, c, p, o)); return launch_ok(ctx); }
+  VarRange var;
+  CK(verify_straus_scalars(ctx, c, p, o, &var));
+  bool done = false;
+  if (wp && nb == 1 && p.nvar <= ((size_t)1 << 16)) CK(verify_route_large(ctx, g, p, o, var, &done));
+  if (!done && !p.no_fuse && p.one_chunk) CK(verify_route_fused(ctx, g, p, o, &done));
+  if (!done) CK(verify_route_separate(ctx, g, p, o));
   return launch_ok(ctx);
 }
 int bpgpu_r1cs_verify_batch_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
@@ -1627,7 +1671,7 @@ int bpgpu_r1cs_verify_shard(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
   if (k >= 32) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t m = c->m, nvar = 11 + m + 2 * k;
+  const size_t nvar = verify_nvar(c, k);
   void *dP, *dS, *dC, *dok, *dmega, *dchi = nullptr;
   CK(ws_get(ctx, WS_ARG0, nvar * 64, &dP));
   CK(ws_get(ctx, WS_ARG1, 5 * 32, &dS));
@@ -1665,7 +1709,7 @@ static int verify_batch_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_ci
                              int32_t *ok, uint8_t *mega, uint8_t *msm_scalars) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t np = (size_t)1 << k, m = c->m, nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
+  const size_t np = (size_t)1 << k, nvar = verify_nvar(c, k), nterms = nvar + 2 + 2 * np;   // proof points + B, B_blinding, G, H
   void *dP, *dS, *dC, *dok, *dmega, *dfull = nullptr, *dchi = nullptr;
   CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
   CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
@@ -1755,7 +1799,7 @@ static int verify_stream_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
   const size_t batch = (size_t)ctx->opt[BPGPU_OPT_STREAM_BATCH], nlanes_opt = (size_t)ctx->opt[BPGPU_OPT_STREAM_LANES];
   const size_t nchunks = (nb + batch - 1) / batch, nl = nchunks < nlanes_opt ? nchunks : nlanes_opt;
   CK(stream_lanes(ctx, nl));
-  const size_t m = c->m, nvar = 11 + m + 2 * k, nch = 6 + k;
+  const size_t nvar = verify_nvar(c, k), nch = 6 + k;
   CK(lanes_fork(ctx, nl));
   int rc = BPGPU_OK;
   for (size_t ci = 0; ci < nchunks && rc == BPGPU_OK; ci++) {
@@ -1873,7 +1917,7 @@ static int verify_fs_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circu
                           int32_t *ok, uint8_t *mega, uint8_t *challenges_out, uint8_t *gadget_challenges_out) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t m = c->m, nvar = 11 + m + 2 * k;
+  const size_t nvar = verify_nvar(c, k);
   void *dP, *dS, *dI, *dok, *dmega, *dcho, *dchi;
   CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
   CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
@@ -1951,7 +1995,7 @@ static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_c
     sqrt_tables_build(ctx->st, t);
     ctx->sqrt_tab = t;
   }
-  const size_t m = c->m, nvar = 11 + m + 2 * k;
+  const size_t m = c->m, nvar = verify_nvar(c, k);
   void *dcomp, *dxy, *dsc, *dfmt;
   CK(ws_get(ctx, WS_ARG0, nb * nvar * 32, &dcomp));
   CK(ws_get(ctx, WS_ARG1, nb * nvar * 64, &dxy));
@@ -2005,18 +2049,16 @@ static int verify_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
                                   size_t k, const void *points, const void *scalars, const void *challenges,
                                   const void *rho, void *partial_xy) {
   if (k >= 32) return BPGPU_E_LEN;
-  size_t np = (size_t)1 << k, n = c->n, m = c->m;
-  if (n > np || n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;
-  if (np > g->cap) return BPGPU_E_GENS;
+  CK(verify_shape(c, g, n1, k));
   if (!nb) return BPGPU_OK;
   HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t nvar = 11 + m + 2 * k, nfix = 2 + 2 * np, tot = nb * nvar;
+  const size_t np = (size_t)1 << k, nvar = verify_nvar(c, k), nfix = 2 + 2 * np, tot = nb * nvar;
   void *dpts, *dfix, *dvar, *dzp, *dfsum, *dtwo, *dsum, *dpip;
   CK(ws_get(ctx, WS_VPTS, tot * sizeof(AffDev), &dpts));
   CK(ws_get(ctx, WS_VFIX, nb * nfix * 32, &dfix));
   CK(ws_get(ctx, WS_VVAR, tot * 32, &dvar));
   if (c->nchi) return BPGPU_E_ARG;
-  VerifyDims d{nb, n1, n, np, k, m, nullptr, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
+  VerifyDims d{nb, n1, c->n, np, k, c->m, nullptr, (size_t)ctx->opt[BPGPU_OPT_VS_LARGE_MIN]};
   CK(ws_get(ctx, WS_ZPOW, verify_scalars_scratch_ints(circuit_dev(c), d) * 4, &dzp));
   CK(ws_get(ctx, WS_VVRES, nfix * 32, &dfsum));
   CK(ws_get(ctx, WS_VFRES, 2 * sizeof(JacRaw), &dtwo));
@@ -2038,16 +2080,15 @@ static int verify_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   verify_scalars(ctx->st, circuit_dev(c), d, (const Words8 *)challenges, (const Words8 *)scalars, (Words8 *)dfix,
                  (Words8 *)dvar, nullptr, (int32_t *)dzp, ctx->d_flag);
   // generator part on stream 2: weighted column sums, then one fixed-base MSM
-  HIPCK(ctx, hipEventRecord(ctx->ev1, ctx->st));
-  HIPCK(ctx, hipStreamWaitEvent(ctx->st2, ctx->ev1, 0));
+  CK(side_fork(ctx));
   sc_weighted_colsum(ctx->st2, nb, nfix, (const Words8 *)dfix, (const Words8 *)rho, (Words8 *)dfsum);
   CK(msm_gens_dev(ctx, g, 1, np, (const uint32_t *)dfsum, (JacRaw *)dtwo, ctx->st2));
-  HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2));
+  CK(side_done(ctx));
   // proof-specific points on stream 1: scale by rho, bucket-method MSM
   points_from_boundary(ctx->st, (const Words8 *)points, (AffDev *)dpts, tot, ctx->d_flag);
   sc_scale_rows(ctx->st, nb, nvar, (Words8 *)dvar, (const Words8 *)rho);
   pippenger(ctx->st, (const AffDev *)dpts, (const uint32_t *)dvar, tot, cw, (JacRaw *)dtwo + 1, dpip);
-  HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0));
+  CK(side_join(ctx));
   segmented_sum(ctx->st, (const JacRaw *)dtwo, (JacRaw *)dsum, 1, 2);
   jac_to_boundary(ctx->st, (const JacRaw *)dsum, (Words8 *)partial_xy, 1);
   return launch_ok(ctx);
@@ -2067,7 +2108,7 @@ int bpgpu_r1cs_verify_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
   if (!nb) { memset(partial_xy, 0, 64); return BPGPU_OK; }
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  size_t m = c->m, nvar = 11 + m + 2 * k;
+  const size_t nvar = verify_nvar(c, k);
   void *dP, *dS, *dC, *dR, *dout;
   CK(ws_get(ctx, WS_ARG0, nb * nvar * 64, &dP));
   CK(ws_get(ctx, WS_ARG1, nb * 5 * 32, &dS));
@@ -2146,7 +2187,7 @@ static int verify_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   // proofs per combined check: the check is a chain of nine mostly latency-bound launches with little work per proof, so its
   // batches are larger than the per-proof path's (2560 x 24 points still fit the one-instance bucket pipeline of k_pip2.hip:
   // 11.2 M/s against 8.1 M/s at 1024); a batch that fails is re-verified proof by proof as a whole
-  const size_t m = c->m, nvar = 11 + m + 2 * k, nch = 6 + k;
+  const size_t nvar = verify_nvar(c, k), nch = 6 + k;
   size_t batch = (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH];
   const size_t fit = ((size_t)1 << 16) / nvar / 64 * 64;          // proof points of one check <= 2^16
   if (fit >= 256 && batch > fit) batch = fit;
@@ -2255,13 +2296,10 @@ static int mixed_validate(const bpgpu_gens *g, const bpgpu_verify_group *G, size
     if (x.nb && (!x.points || !x.scalars || !x.challenges || !x.rho || (screened && !x.ok))) return BPGPU_E_ARG;
     if ((c->nchi != 0) != (x.gadget_challenges != nullptr)) return BPGPU_E_ARG;
     if (x.k >= 32) return BPGPU_E_LEN;
-    const size_t np = (size_t)1 << x.k, n = c->n;
-    if (n > np || x.n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;
-    if (np > g->cap) return BPGPU_E_GENS;
+    CK(verify_shape(c, g, x.n1, x.k));
   }
   return BPGPU_OK;
 }
-static size_t mixed_nvar(const bpgpu_verify_group &x) { return 11 + x.circuit->m + 2 * x.k; }
 // cut the concatenated queue into checks of at most max_proofs proofs, max_points proof points (a single proof may exceed it) and
 // BPGPU_MIXED_MAX_SEGMENTS segments
 static void mixed_plan(const bpgpu_verify_group *G, size_t ngroups, size_t max_proofs, size_t max_points, std::vector<MixSeg> &segs,
@@ -2270,7 +2308,7 @@ static void mixed_plan(const bpgpu_verify_group *G, size_t ngroups, size_t max_p
   auto close = [&]() { if (!checks.empty() && checks.back().nseg) { checks.push_back(MixCheck{segs.size(), 0}); } cp = cpts = 0; };
   checks.push_back(MixCheck{0, 0});
   for (size_t gi = 0; gi < ngroups; gi++) {
-    const size_t nvar = mixed_nvar(G[gi]);
+    const size_t nvar = verify_nvar(G[gi].circuit, G[gi].k);
     size_t lo = 0;
     while (lo < G[gi].nb) {
       if (checks.back().nseg == BPGPU_MIXED_MAX_SEGMENTS) close();
@@ -2297,7 +2335,7 @@ static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_ve
   for (size_t s = 0; s < nseg; s++) {
     const bpgpu_verify_group &x = G[segs[s].gi];
     const bpgpu_circuit *c = x.circuit;
-    const size_t lo = segs[s].lo, nvar = mixed_nvar(x), np = (size_t)1 << x.k;
+    const size_t lo = segs[s].lo, nvar = verify_nvar(x.circuit, x.k), np = (size_t)1 << x.k;
     MixSegIn &v = in[s];
     v.circ = circuit_dev(c);
     v.d = VerifyDims{segs[s].cnt, x.n1, c->n, np, x.k, c->m,
@@ -2338,7 +2376,7 @@ static int mixed_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
 // the per-proof path for one segment on lane ln: bpgpu_r1cs_verify_batch(_param)'s verdicts into the group's ok[] (HBM)
 static int mixed_per_proof_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group &x, size_t lo, size_t cnt) {
   const bpgpu_circuit *c = x.circuit;
-  const size_t nvar = mixed_nvar(x);
+  const size_t nvar = verify_nvar(x.circuit, x.k);
   const Words8 *chi = c->nchi ? (const Words8 *)x.gadget_challenges + lo * c->nchi : nullptr;
   int32_t *ok = (int32_t *)x.ok + lo;
   void *dchibad = nullptr;
@@ -2384,7 +2422,7 @@ static int mixed_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
 static int mixed_stage_locked(bpgpu_ctx *ctx, const bpgpu_verify_group *G, size_t ngroups, std::vector<bpgpu_verify_group> &D) {
   size_t tot = 0;
   auto sizes = [](const bpgpu_verify_group &x, size_t *b) {
-    const size_t nvar = mixed_nvar(x);
+    const size_t nvar = verify_nvar(x.circuit, x.k);
     b[0] = x.nb * nvar * 64; b[1] = x.nb * 160; b[2] = x.nb * (6 + x.k) * 32; b[3] = x.gadget_challenges ? x.nb * x.circuit->nchi * 32 : 0;
     b[4] = x.nb * 32; b[5] = x.nb * 4;
   };
@@ -2698,16 +2736,15 @@ static int ipp_fold_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, Words8 *du, Words8 *dui) {
   CK(straus_ws(ctx, 2, nb * h, &dstr));
   CK(ws_get(ctx, WS_MSM, straus_scratch_bytes(2, nb * h), &dstr2));
   hipStream_t st2 = ctx->st2;
-  HIPCK(ctx, hipEventRecord(ctx->ev1, st));
-  HIPCK(ctx, hipStreamWaitEvent(st2, ctx->ev1, 0));
+  CK(side_fork(ctx));
   straus(st, 2, g, fres, nb * h, dstr);
   straus(st2, 2, hh, fres + nb * h, nb * h, dstr2);
   // when the input generators are shared the folded ones become per-proof: write them to buffer nxt
   batch_normalize(st, fres, s->G[nxt], nb * h, 8);
   batch_normalize(st2, fres + nb * h, s->H[nxt], nb * h, 8);
-  HIPCK(ctx, hipEventRecord(ctx->ev2, st2));
+  CK(side_done(ctx));
   fold_scalars_batched(st, nb, h, du, dui, s->a[cur], s->b[cur], s->a[nxt], s->b[nxt]);
-  HIPCK(ctx, hipStreamWaitEvent(st, ctx->ev2, 0));
+  CK(side_join(ctx));
   s->cur = nxt; s->n = h; s->first = false;
   return launch_ok(ctx);
 }

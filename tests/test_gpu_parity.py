@@ -837,6 +837,60 @@ def test_shard_malformed_point_is_a_collective_verdict(gpu):
             s.close()
 
 
+@pytest.mark.parametrize("route", [{"verify_window_parallel": 0}, {"verify_no_fuse": 1}], ids=["fused", "separate"])
+def test_shard_partial_sums_add_up_on_the_straus_routes(gpu, opts, route):
+    """bpgpu_r1cs_verify_shard with the window-parallel chain switched off: the other ranks' scalars are zeroed ahead of the fused
+    Straus launch (4 points per lane: the 8-bit gadget's 18 proof points leave a remainder launch) and ahead of the separate
+    launches alike, and the partial mega_check points of 2 and of 3 ranks add up to the oracle's point -- the identity for the
+    valid proof, the tampered proof's point otherwise."""
+    opts(**route)
+    recs, cap = bh.make_range_batch(8, 2, tamper={1})
+    g = _gens(gpu, cap, 8)
+    try:
+        for proof, com in recs:
+            s = o.VerifySession(o.K_RANGE, 8, b"RangeProofTest", [], com, proof, cap)
+            circ = gpu.circuit_create(*s.csr(), s.n1 + s.n2, s.m)
+            try:
+                k, pts, sc = bh.verify_inputs(proof, com)
+                assert 11 + s.m + 2 * s.k == 18
+                for world in (2, 3):
+                    parts = [gpu.r1cs_verify_shard(g, circ, s.n1, s.k, pts, sc, s.challenges(), r, world) for r in range(world)]
+                    assert gpu.points_sum(b"".join(parts)) == s.mega_check(), world
+                assert (s.mega_check() == bytes(64)) == (s.rc == 0)
+            finally:
+                gpu.circuit_destroy(circ)
+                s.close()
+    finally:
+        gpu.gens_destroy(g)
+
+
+def test_verify_one_large_proof_default_options(gpu):
+    """ONE proof of more than 256 proof points under the default options (256 x 1-bit values: 11 + 256 + 2 * 8 = 283 points): its
+    proof-point half goes through the window-parallel MSM, the generator half runs on the second stream.  Accept bit, mega_check
+    point and all MSM scalars equal the oracle's, for the proof and for a copy with a bit of t_x flipped."""
+    cap = 256
+    rc, proof, com = o.r1cs_prove(o.K_RANGE_MULTI, 1 | (256 << 16), b"RangeProofTest", [i & 1 for i in range(256)], 4242, cap)
+    assert rc == 0
+    bad = bytearray(proof)
+    bad[8 + 11 * 64 + 3] ^= 4                                  # t_x
+    g = _gens(gpu, cap, 8)
+    try:
+        for pr in (proof, bytes(bad)):
+            s = o.VerifySession(o.K_RANGE_MULTI, 1 | (256 << 16), b"RangeProofTest", [], com, pr, cap)
+            circ = gpu.circuit_create(*s.csr(), s.n1 + s.n2, s.m)
+            try:
+                k, pts, sc = bh.verify_inputs(pr, com)
+                assert 11 + s.m + 2 * s.k > 256
+                ok, mega, full = gpu.r1cs_verify_batch(g, circ, 1, s.n1, s.k, s.m, pts, sc, s.challenges(), True, True)
+                assert ok == [1 if pr is proof else 0] and (s.rc == 0) == (pr is proof)
+                assert mega == s.mega_check() and full == s.msm_terms()[0]
+            finally:
+                gpu.circuit_destroy(circ)
+                s.close()
+    finally:
+        gpu.gens_destroy(g)
+
+
 def test_options_setter_rejects_bad_values(gpu):
     import mpc_bulletproof_amd as m
     for name, bad in (("verify_straus_np", 5), ("table_np", 3), ("vs_large_min", 0), ("ipp_literal", 2), ("msm_wp_max", -1)):
