@@ -98,7 +98,9 @@ int bpgpu_input_flag(bpgpu_ctx *ctx, int *bad);
 #define BPGPU_PROF_KINDS 24
 /* Kinds 16..21 cover the prover (one pair per device phase of a call, i.e. from its first to its last launch): 16 phase commitments
  * (bpgpu_r1cs_prover_commit), 17 polynomial build, 18 bpgpu_msm_gens (T commitments), 19 IPP session set-up, 20 the IPP round
- * loop, 21 the L / R table-lookup MSM of one round (the prover's dominant kernel, nested inside 20). */
+ * loop, 21 the L / R table-lookup MSM of one round (the prover's dominant kernel, nested inside 20).
+ * Kind 22: the launches only bpgpu_r1cs_prove_fs has (its transcript slices, the scalar links between the stages, proof assembly);
+ * the stages it chains keep reporting under 16..21. */
 int bpgpu_profile_enable(bpgpu_ctx *ctx, int on);
 int bpgpu_profile_select(bpgpu_ctx *ctx, uint32_t kind_mask);
 int bpgpu_profile_read(bpgpu_ctx *ctx, double ms_sum[BPGPU_PROF_KINDS], uint64_t launches[BPGPU_PROF_KINDS]);
@@ -365,6 +367,42 @@ int bpgpu_r1cs_prover_session_polys(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu
  * once per circuit shape; a prover of the 2^14-shuffle no longer builds and uploads 65 533 constraint rows per proof. */
 int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *session, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                           const uint8_t *gadget_challenges, uint8_t *t_coeffs, uint8_t *wV);
+/* Prover::prove (r1cs/prover.rs:412-727) in ONE call, transcript included, for nb provers of one circuit WITHOUT randomized constraints
+ * (bpgpu_circuit_create / _ark): the phase commitments, y and z, the polynomial build, the T commitments, u and x, t(x) and the
+ * blindings, w, the IPP session and its k rounds run back to back on the context's stream; the Fiat-Shamir hash chain is advanced on
+ * the device between them.  It replaces the five staged calls (bpgpu_r1cs_prover_commit, _session_polys, bpgpu_msm_gens,
+ * bpgpu_r1cs_prover_ipp_begin, bpgpu_ipp_run_fs) and the host hashing, waits and copies between them.  A parametric circuit
+ * (bpgpu_circuit_create_param) is refused with BPGPU_E_ARG: the phase-2 witness of a two-phase prover depends on a challenge the host
+ * has to evaluate its gadget on, so that round trip is inherent; such provers keep the staged calls.
+ * With n = the circuit's multipliers, m its commitments, padded_n = next_pow2(n), k = lg padded_n:
+ *   states_in      nb x 32        the chain state on entry to Prover::prove (prover.rs:412): after Prover::new and every commit(),
+ *                                 i.e. the V's are already absorbed by the host
+ *   a_L, a_R, a_O  nb x n         ark-ff Montgomery form
+ *   s_L, s_R       nb x n         explicit blinding vectors, or both NULL with
+ *   vector_keys    nb x 32        "BlindVec v1" keys, as bpgpu_r1cs_prover_commit (exactly one of the two sources)
+ *   v_blinding     nb x m         ark form (prover.rs:644-648); may be NULL when m == 0
+ *   blindings      nb x 8         ark form: i_blinding o_blinding s_blinding tb1 tb3 tb4 tb5 tb6, in the order the reference draws
+ *                                 them (:457-459, :621-625); the transcript-bound RNG of :435-445 is the caller's
+ *   proof_points   nb x (11 + 2k) x 64   A_I1 A_O1 S1 A_I2 A_O2 S2 T_1 T_3 T_4 T_5 T_6 L_0..L_{k-1} R_0..R_{k-1}; A_I2, A_O2, S2 are
+ *                                 the identity (64 zero bytes) and are absorbed as such
+ *   proof_scalars  nb x 5 x 32    canonical LE: t_x t_x_blinding e_blinding a b (layout of bpgpu_r1cs_verify_batch)
+ *   wire           (optional) nb x proof_len, proof_len = 1 + 11 * 32 + (2k + 2) * 32: R1CSProof::to_bytes (proof.rs:82-109), version
+ *                                 byte 0 (which omits the three identity points)
+ *   challenges_out (optional) nb x (5 + k) x 32: y z u x w u_1..u_k;   states_out (optional) nb x 32: the chain states afterwards
+ * Refusals, before anything is launched: BPGPU_E_ARG for a null required pointer, for both or neither of explicit s_L / s_R and
+ * vector_keys, for a parametric circuit and for a context after bpgpu_set_shard(world > 1); BPGPU_E_LEN for n == 0 (the staged calls
+ * remain for such circuits); BPGPU_E_GENS for padded_n above the generators' capacity; nb == 0: BPGPU_OK.  A non-canonical ark limb
+ * gives BPGPU_E_ARG in the host form and raises bpgpu_input_flag in the `_dev` form (every operand and result a device pointer;
+ * asynchronous on the context's stream).  A failed call leaves no session or pool memory behind.  The hash chain is the build's
+ * stand-in for merlin's. */
+int bpgpu_r1cs_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const uint8_t *states_in,
+                        const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
+                        const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points,
+                        uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out);
+int bpgpu_r1cs_prove_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const void *states_in,
+                            const void *a_L, const void *a_R, const void *a_O, const void *s_L, const void *s_R,
+                            const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
+                            void *proof_scalars, void *wire, void *challenges_out, void *states_out);
 /* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
  * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
  * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step

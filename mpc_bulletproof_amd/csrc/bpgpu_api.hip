@@ -60,6 +60,11 @@ enum WsSlot : int {
   WS_IPPV_VSC,      // ... resident generators: the scalars of L, R
   WS_IPPV_PTS,      // ... converted points in instance layout
   WS_IPPV_SUM,      // ... MSM sums, expect_P when the caller does not ask for it
+  WS_PFS_STAGE,     // bpgpu_r1cs_prove_fs: the host form's operands and results
+  WS_PFS_CH,        // ... chain states, the challenge arrays y z u x w u_1..u_k
+  WS_PFS_SC,        // ... blindings and v_blinding (plain), T rows, tb2, t_x t_x_blinding e_blinding
+  WS_PFS_PTS,       // ... A_I A_O S and T_1..T_6: sums and boundary bytes
+  WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched_key)
   WS_COUNT
 };
 
@@ -100,6 +105,9 @@ struct bpgpu_ctx {
   // device-transcript schedule cache (m, k, padded_n) -> steps already resident in WS_SCHED
   size_t sched_key[3] = {(size_t)-1, (size_t)-1, (size_t)-1};
   int sched_len = 0;
+  // the prover's schedule (bpgpu_r1cs_prove_fs): (m, padded_n) -> steps resident in WS_PFS_SCHED, and its three slices
+  size_t psched_key[2] = {(size_t)-1, (size_t)-1};
+  int psched_cut[4] = {0, 0, 0, 0};
 };
 struct ProfScope {   // records start/stop events on `st` around a launch when profiling is on (events come from a per-context pool)
   bpgpu_ctx *c; int kind; hipStream_t st;
@@ -260,6 +268,11 @@ static int d2h(bpgpu_ctx *ctx, void *h, const void *d, size_t n) {
   if (n) HIPCK(ctx, hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, ctx->st));
   return BPGPU_OK;
 }
+// an operand of a core that serves host forms and device forms alike: uploaded, or copied within HBM (stream-ordered either way)
+static int copy_in(bpgpu_ctx *ctx, void *d, const void *src, size_t n, bool src_dev) {
+  if (n) HIPCK(ctx, hipMemcpyAsync(d, src, n, src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
+  return BPGPU_OK;
+}
 static int launch_ok(bpgpu_ctx *ctx) { HIPCK(ctx, hipGetLastError()); return BPGPU_OK; }
 // Work on the context's second stream beside ctx->st: side_fork (st2 waits for what st holds so far), the launches on st2, side_done
 // (marks the end of st2's part), more launches on st, side_join (st waits for the mark)
@@ -270,11 +283,14 @@ static int side_fork(bpgpu_ctx *ctx) {
 }
 static int side_done(bpgpu_ctx *ctx) { HIPCK(ctx, hipEventRecord(ctx->ev2, ctx->st2)); return BPGPU_OK; }
 static int side_join(bpgpu_ctx *ctx) { HIPCK(ctx, hipStreamWaitEvent(ctx->st, ctx->ev2, 0)); return BPGPU_OK; }
-// the head of an entry point whose launches validate into ctx->d_flag: the flag cleared, then the operands' uploads in order
+// the head of an entry point whose launches validate into ctx->d_flag: the flag cleared, then the operands' uploads in order.
+// Where the operands come from: host memory (the staged entry points) or HBM (src_dev: the one-call prover chains the same cores
+// on challenges its transcript kernel has just written, and keeps ONE flag for the whole chain: reset = false).
+struct OperandSrc { bool src_dev = false, reset = true; };
 struct H2D { void *dev; const void *host; size_t bytes; };
-static int upload_inputs(bpgpu_ctx *ctx, std::initializer_list<H2D> ins) {
-  CK(flag_reset(ctx));
-  for (const H2D &i : ins) CK(h2d(ctx, i.dev, i.host, i.bytes));
+static int upload_inputs(bpgpu_ctx *ctx, std::initializer_list<H2D> ins, OperandSrc from = {}) {
+  if (from.reset) CK(flag_reset(ctx));
+  for (const H2D &i : ins) CK(copy_in(ctx, i.dev, i.host, i.bytes, from.src_dev));
   return BPGPU_OK;
 }
 // the end of the uploads of an entry point whose launches validate into ctx->d_flag: the launch check, the flag (a host-side wait),
@@ -2782,6 +2798,28 @@ int bpgpu_ipp_fold(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *u, const uint8_t
 /* InnerProductProof::create's whole round loop on the device (SURVEY 8f N1 applied to the prover): per round the
  * L, R MSMs, transcript.append_point("L"), ("R"), challenge_scalar("u") (inner_product_proof.rs:119-123,177-181)
  * with the keccak hash chain in a kernel, u^-1 and the fold -- no host round trip between rounds. */
+// the k rounds on states, L / R and (optional) per-round challenge arrays that are already in HBM (ctx->mu held; asynchronous):
+// dlr: k x nb x (L, R) boundary points, round-major; uch: k arrays of nb, u_1..u_k (nullptr: not kept); dzero: a 4-byte scratch flag
+static int ipp_rounds_fs_dev(bpgpu_ctx *ctx, bpgpu_ipp *s, size_t k, void *dstates, void *dlr, Words8 *uch, void *dzero) {
+  const size_t nb = s->nb;
+  Words8 *dui = s->uu + nb;
+  ProfSpan span(ctx, 20, ctx->st);
+  for (size_t r = 0; r < k; r++) {
+    Words8 *lr = (Words8 *)dlr + r * nb * 4;             // 2 points x 2 Words8 per proof
+    Words8 *du = uch ? uch + r * nb : s->uu;
+    if (s->gens) {   // resident generators: point conversion, the three transcript steps and u^-1 in ONE launch (k_ipp_round_tail)
+      CK(ipp_round_dev(ctx, s, nullptr));
+      ipp_round_tail(ctx->st, nb, s->sums, (uint64_t *)dstates, lr, du, dui, s->tail_partials, s->tail_chunks);
+    } else {
+      CK(ipp_round_dev(ctx, s, lr));
+      ipp_round_challenge(ctx->st, nb, (uint64_t *)dstates, lr, du);
+      HIPCK(ctx, hipMemcpyAsync(dui, du, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+      batch_inverse(ctx->st, dui, nb, (int *)dzero);       // challenges are non-zero up to 2^-252
+    }
+    CK(ipp_fold_dev(ctx, s, du, dui));
+  }
+  return BPGPU_OK;
+}
 int bpgpu_ipp_run_fs(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *states_in, uint8_t *L_out, uint8_t *R_out,
                      uint8_t *a_out, uint8_t *b_out, uint8_t *states_out) {
   return noexcept_abi([&]() -> int {
@@ -2798,22 +2836,7 @@ int bpgpu_ipp_run_fs(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *states_in, uin
     CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
     CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
     CK(h2d(ctx, dstates, states_in, nb * 32));
-    Words8 *du = s->uu, *dui = s->uu + nb;
-    ProfSpan span(ctx, 20, ctx->st);
-    for (size_t r = 0; r < k; r++) {
-      Words8 *lr = (Words8 *)dlr + r * nb * 4;             // 2 points x 2 Words8 per proof
-      if (s->gens) {   // resident generators: point conversion, the three transcript steps and u^-1 in ONE launch (k_ipp_round_tail)
-        CK(ipp_round_dev(ctx, s, nullptr));
-        ipp_round_tail(ctx->st, nb, s->sums, (uint64_t *)dstates, lr, du, dui, s->tail_partials, s->tail_chunks);
-      } else {
-        CK(ipp_round_dev(ctx, s, lr));
-        ipp_round_challenge(ctx->st, nb, (uint64_t *)dstates, lr, du);
-        HIPCK(ctx, hipMemcpyAsync(dui, du, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
-        batch_inverse(ctx->st, dui, nb, (int *)dzero);       // challenges are non-zero up to 2^-252
-      }
-      CK(ipp_fold_dev(ctx, s, du, dui));
-    }
-    span.close();
+    CK(ipp_rounds_fs_dev(ctx, s, k, dstates, dlr, nullptr, dzero));
     // proof-major outputs: L_out[p][r], R_out[p][r]
     return download_pairs(ctx, dlr, nb, k, L_out, R_out,
                           {{a_out, s->a[s->cur], nb * 32}, {b_out, s->b[s->cur], nb * 32}, {states_out, dstates, states_out ? nb * 32 : 0}});
@@ -2923,14 +2946,14 @@ struct PolysBuild {
 // into WS_ARG0 / WS_CHI; all of them validated.
 struct PolyChallenges { const Words8 *z, *chi; };
 static int session_polys_begin(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z, const uint8_t *chi,
-                               PolyChallenges *ch) {
+                               PolyChallenges *ch, OperandSrc from = {}) {
   const size_t nv = s->nb, nb = nv / (size_t)s->planes;
   CK(polys_alloc(ctx, s, c->n));
   if (!pool_alloc(ctx, (void **)&s->yinv, nv * 32)) return BPGPU_E_OOM;
   void *dz, *dchi = nullptr;
   CK(ws_get(ctx, WS_ARG0, nb * 32, &dz));
   if (c->nchi) CK(ws_get(ctx, WS_CHI, nb * c->nchi * 32, &dchi));
-  CK(upload_inputs(ctx, {{s->y, y, nv * 32}, {dz, z, nb * 32}, {dchi, chi, nb * c->nchi * 32}}));
+  CK(upload_inputs(ctx, {{s->y, y, nv * 32}, {dz, z, nb * 32}, {dchi, chi, nb * c->nchi * 32}}, from));
   scalars_check(ctx->st, s->y, nv, ctx->d_flag);
   scalars_check(ctx->st, (const Words8 *)dz, nb, ctx->d_flag);
   if (c->nchi) scalars_check(ctx->st, (const Words8 *)dchi, nb * c->nchi, ctx->d_flag);
@@ -3012,6 +3035,26 @@ int bpgpu_r1cs_prover_eval(bpgpu_ctx *ctx, bpgpu_prover *s, size_t padded_n, con
 /* prover.rs:659-708 without leaving the device: l(x), r(x) with their padding, the G/H factors and the
  * resident-generator IPP session that consumes them */
 // (x, u, w: one per virtual prover; an authenticated session (planes 3) evaluates with k_mpc_eval and takes its own y^-1)
+// the session and its launches (ctx->mu held; no host-side wait): `own` holds the session, also on failure
+static int prover_ipp_begin_core(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1, const uint8_t *x,
+                                 const uint8_t *u, const uint8_t *y_inv, const uint8_t *w, OperandSrc from, IppOwner &own) {
+  const size_t nb = ps->nb, n = padded_n;
+  CK(ipp_gens_session(ctx, g, nb, n, ps->planes, own));
+  bpgpu_ipp *s = own.get();
+  void *din;
+  CK(ws_get(ctx, WS_ARG0, 3 * nb * 32, &din));
+  Words8 *dx = (Words8 *)din, *du = dx + nb, *dyi = du + nb;
+  CK(upload_inputs(ctx, {{dx, x, nb * 32}, {du, u, nb * 32}, {s->w, w, nb * 32}}, from));
+  if (y_inv) CK(copy_in(ctx, dyi, y_inv, nb * 32, from.src_dev));
+  else HIPCK(ctx, hipMemcpyAsync(dyi, ps->yinv, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
+  ProfSpan span(ctx, 19, ctx->st);
+  scalars_check(ctx->st, dx, 3 * nb, ctx->d_flag);
+  scalars_check(ctx->st, s->w, nb, ctx->d_flag);
+  if (ps->planes != 1) mpc_eval(ctx->st, nb / 3, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+  else prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
+  ipp_r1cs_factors(ctx->st, nb, n, n1, du, dyi, s->cG, s->cH);
+  return BPGPU_OK;
+}
 static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
                                  const uint8_t *x, const uint8_t *u, const uint8_t *y_inv, const uint8_t *w,
                                  bpgpu_ipp **out) {
@@ -3020,23 +3063,8 @@ static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_g
   *out = nullptr;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
-  const size_t nb = ps->nb, n = padded_n;
   IppOwner own(nullptr, IppFree{ctx});
-  CK(ipp_gens_session(ctx, g, nb, n, ps->planes, own));
-  bpgpu_ipp *s = own.get();
-  void *din;
-  CK(ws_get(ctx, WS_ARG0, 3 * nb * 32, &din));
-  Words8 *dx = (Words8 *)din, *du = dx + nb, *dyi = du + nb;
-  CK(upload_inputs(ctx, {{dx, x, nb * 32}, {du, u, nb * 32}, {s->w, w, nb * 32}}));
-  if (y_inv) CK(h2d(ctx, dyi, y_inv, nb * 32));
-  else HIPCK(ctx, hipMemcpyAsync(dyi, ps->yinv, nb * 32, hipMemcpyDeviceToDevice, ctx->st));
-  ProfSpan span(ctx, 19, ctx->st);
-  scalars_check(ctx->st, dx, 3 * nb, ctx->d_flag);
-  scalars_check(ctx->st, s->w, nb, ctx->d_flag);
-  if (ps->planes != 1) mpc_eval(ctx->st, nb / 3, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
-  else prover_eval(ctx->st, nb, ps->n, n, dx, ps->y, ps->polys, s->a[0], s->b[0]);
-  ipp_r1cs_factors(ctx->st, nb, n, n1, du, dyi, s->cG, s->cH);
-  span.close();
+  CK(prover_ipp_begin_core(ctx, ps, g, padded_n, n1, x, u, y_inv, w, {}, own));
   CK(checked_inputs(ctx));
   *out = own.release();
   return BPGPU_OK;
@@ -3057,27 +3085,13 @@ void bpgpu_prover_destroy(bpgpu_ctx *ctx, bpgpu_prover *s) {
 /* ---- resident-witness prover sessions: prover.rs:457-494 / :519-565 (phase commitments) and :587-619 (polynomials) with the
  * witness uploaded ONCE and the blinding vectors optionally drawn on the device ------------------------------------------ */
 // planes = 3: an authenticated session (bpgpu_mpc_prover_commit), nb = 3 x proofs virtual provers
-static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new,
-                              const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
-                              const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments, int planes) {
-  if (!ctx || !g || !session || !nb || !blindings || !commitments) return BPGPU_E_ARG;
-  if (*session && (*session)->planes != planes) return BPGPU_E_ARG;   // no mixing of single-party and authenticated calls
-  if (n_new && (!a_L || !a_R || !a_O)) return BPGPU_E_ARG;
+// the launches of one commitment phase on a session whose fields are set (ctx->mu held; no host-side wait): the operands from host
+// memory or HBM (`from`), the blindings bl_pitch bytes apart (3 x 32: the staged calls' packed triples), *dcommit = nb x 3 boundary points
+static int prover_commit_core(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover *s, size_t nb, size_t n_new, const uint8_t *a_L,
+                              const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
+                              const uint8_t *blindings, size_t bl_pitch, OperandSrc from, Words8 **dcommit) {
   const bool explicit_vec = s_L && s_R;
-  if (n_new && (explicit_vec == (vector_keys != nullptr) || (!s_L) != (!s_R))) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  bpgpu_prover *s = *session;
-  const bool fresh = s == nullptr;
-  if (!fresh && s->nb != nb) return BPGPU_E_LEN;
-  const size_t wn0 = fresh ? 0 : s->wn, wn = wn0 + n_new;
-  if (wn > g->cap) return BPGPU_E_GENS;
-  if (fresh) {
-    s = new (std::nothrow) bpgpu_prover();
-    if (!s) return BPGPU_E_OOM;
-    s->nb = nb; s->planes = planes; s->g = g;
-  }
-  ProverOwner own(fresh ? s : nullptr, ProverFree{ctx});   // only a fresh session is freed on failure
+  const size_t wn0 = s->wn, wn = wn0 + n_new;
   // new planes of nb x wn; the multipliers of the earlier phase are carried over
   Words8 *pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   Words8 **old[5] = {&s->aL, &s->aR, &s->aO, &s->sL, &s->sR};
@@ -3102,10 +3116,11 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   const size_t nvec = explicit_vec ? 5 : 3;
   Words8 *dbl = w + nvec * tot_new, *dkeys = dbl + 3 * nb;
   const uint8_t *src[5] = {a_L, a_R, a_O, s_L, s_R};
-  CK(flag_reset(ctx));
-  for (size_t i = 0; i < nvec && n_new; i++) CK(h2d(ctx, w + i * tot_new, src[i], tot_new * 32));
-  CK(h2d(ctx, dbl, blindings, nb * 3 * 32));
-  if (n_new && !explicit_vec) CK(h2d(ctx, dkeys, vector_keys, nb * 32));
+  if (from.reset) CK(flag_reset(ctx));
+  for (size_t i = 0; i < nvec && n_new; i++) CK(copy_in(ctx, w + i * tot_new, src[i], tot_new * 32, from.src_dev));
+  if (bl_pitch == 3 * 32) CK(copy_in(ctx, dbl, blindings, nb * 3 * 32, from.src_dev));
+  else HIPCK(ctx, hipMemcpy2DAsync(dbl, 3 * 32, blindings, bl_pitch, 3 * 32, nb, from.src_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->st));
+  if (n_new && !explicit_vec) CK(copy_in(ctx, dkeys, vector_keys, nb * 32, from.src_dev));
   ProfSpan span(ctx, 16, ctx->st);
   if (n_new) {
     if (wn0 == 0) {          // contiguous planes: convert straight into them
@@ -3124,7 +3139,32 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
   // (three classes of rows per prover -- A_I, A_O: bit vectors; S: dense -- so that a wave of the MSM-per-lane walk holds one class)
   CK(msm_gens_dev(ctx, g, nb * 3, wn, (const uint32_t *)drows, (JacRaw *)dres, ctx->st, WS_MSM, 0, 3));
   jac_to_boundary(ctx->st, (JacRaw *)dres, (Words8 *)dout, nb * 3);
-  span.close();
+  *dcommit = (Words8 *)dout;
+  return BPGPU_OK;
+}
+static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover **session, size_t nb, size_t n_new,
+                              const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
+                              const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments, int planes) {
+  if (!ctx || !g || !session || !nb || !blindings || !commitments) return BPGPU_E_ARG;
+  if (*session && (*session)->planes != planes) return BPGPU_E_ARG;   // no mixing of single-party and authenticated calls
+  if (n_new && (!a_L || !a_R || !a_O)) return BPGPU_E_ARG;
+  const bool explicit_vec = s_L && s_R;
+  if (n_new && (explicit_vec == (vector_keys != nullptr) || (!s_L) != (!s_R))) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  bpgpu_prover *s = *session;
+  const bool fresh = s == nullptr;
+  if (!fresh && s->nb != nb) return BPGPU_E_LEN;
+  const size_t wn0 = fresh ? 0 : s->wn, wn = wn0 + n_new;
+  if (wn > g->cap) return BPGPU_E_GENS;
+  if (fresh) {
+    s = new (std::nothrow) bpgpu_prover();
+    if (!s) return BPGPU_E_OOM;
+    s->nb = nb; s->planes = planes; s->g = g;
+  }
+  ProverOwner own(fresh ? s : nullptr, ProverFree{ctx});   // only a fresh session is freed on failure
+  Words8 *dout = nullptr;
+  CK(prover_commit_core(ctx, g, s, nb, n_new, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, 3 * 32, {}, &dout));
   CK(checked_download(ctx, {{commitments, dout, nb * 3 * 64}}));
   (void)own.release();
   *session = s;
@@ -3149,6 +3189,23 @@ int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *s, const
   if (!c->nchi || !gadget_challenges) return BPGPU_E_ARG;
   return prover_session_polys_locked(ctx, s, c, y, z, gadget_challenges, t_coeffs, wV);
 }
+// the launches of the polynomial build (ctx->mu held; no host-side wait): *dt = nb x 6 t coefficients, *dwV = nb x m, in WS_ARG1
+static int session_polys_core(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z, const uint8_t *chi,
+                              OperandSrc from, Words8 **dt_out, Words8 **dwV_out) {
+  const size_t nb = s->nb, n = c->n, m = c->m;
+  void *dout;
+  CK(ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout));
+  Words8 *dt = (Words8 *)dout, *dwV = dt + nb * 6;
+  PolyChallenges ch;
+  CK(session_polys_begin(ctx, s, c, y, z, chi, &ch, from));
+  ProfSpan span(ctx, 17, ctx->st);
+  const int32_t *dzp;
+  CK(session_polys_powers(ctx, s, c, ch, &dzp));
+  prover_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, dzp, s->polys, dwV);
+  prover_tcoeffs(ctx->st, nb, n, s->polys, dt);
+  *dt_out = dt; *dwV_out = dwV;
+  return BPGPU_OK;
+}
 static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                        const uint8_t *chi, uint8_t *t_coeffs, uint8_t *wV) {
   if (c->n != s->wn || s->polys) return BPGPU_E_LEN;     // the circuit's multipliers are the session's; one polynomial build per session
@@ -3156,21 +3213,176 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t nb = s->nb, n = c->n, m = c->m;
   PolysBuild build{ctx, s};
-  void *dout;
-  CK(ws_get(ctx, WS_ARG1, (nb * 6 + nb * m) * 32, &dout));
-  Words8 *dt = (Words8 *)dout, *dwV = dt + nb * 6;
-  PolyChallenges ch;
-  CK(session_polys_begin(ctx, s, c, y, z, chi, &ch));
-  ProfSpan span(ctx, 17, ctx->st);
-  const int32_t *dzp;
-  CK(session_polys_powers(ctx, s, c, ch, &dzp));
-  prover_polys(ctx->st, circuit_dev(c), nb, s->y, s->yinv, s->aL, s->aR, s->aO, s->sL, s->sR, dzp, s->polys, dwV);
-  prover_tcoeffs(ctx->st, nb, n, s->polys, dt);
-  span.close();
+  Words8 *dt, *dwV;
+  CK(session_polys_core(ctx, s, c, y, z, chi, {}, &dt, &dwV));
   CK(checked_download(ctx, {{t_coeffs, dt, nb * 6 * 32}, {wV, dwV, nb * m * 32}}));
   build.kept = true;
   s->n = n; s->m = m;
   return BPGPU_OK;
+}
+/* ---- Prover::prove (r1cs/prover.rs:412-727) in ONE call for nb provers of a circuit without randomized constraints: the phase
+ * commitments, the polynomial build, the T commitments, t(x) and the blindings, the IPP session and its rounds chained on the
+ * context's stream with the Fiat-Shamir transcript on the device between them (k_prover_transcript in three slices) -- the host
+ * neither hashes nor waits until the proofs are complete.  The stages are the cores of the staged entry points above, fed from
+ * HBM; what is new are the transcript slices and the links of k_prove_fs.hip. ------------------------------------------------ */
+namespace {
+struct ProveFsIo {   // every pointer in HBM
+  const uint8_t *states_in, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *v_blinding, *blindings;
+  uint8_t *proof_points, *proof_scalars, *wire, *challenges_out, *states_out;
+};
+struct ProveFsDims { size_t n, m, padded_n, k; };
+}  // namespace
+static ProveFsDims prove_fs_dims(const bpgpu_circuit *c) {
+  ProveFsDims d{c->n, c->m, 1, 0};
+  while (d.padded_n < d.n) { d.padded_n <<= 1; d.k++; }
+  return d;
+}
+// the refusals that depend on shapes alone, before anything is launched (BPGPU_OK with nb == 0: nothing to do)
+static int prove_fs_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const void *states_in, const void *a_L,
+                          const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys, const void *v_blinding,
+                          const void *blindings, const void *proof_points, const void *proof_scalars) {
+  if (!ctx || !g || !c) return BPGPU_E_ARG;
+  if (c->nchi) return BPGPU_E_ARG;       // a two-phase prover evaluates its gadget on the challenge: that round trip stays on the host
+  if (!nb) return BPGPU_OK;
+  if (!c->n) return BPGPU_E_LEN;         // (no multipliers: no IPP to speak of; the staged calls serve such circuits)
+  if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
+  if (!states_in || !a_L || !a_R || !a_O || !blindings || !proof_points || !proof_scalars || (c->m && !v_blinding)) return BPGPU_E_ARG;
+  if ((!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  return BPGPU_OK;
+}
+// ctx->mu held, shapes checked, nb > 0; asynchronous.  The sessions live until the last launch is enqueued: their buffers go back to
+// the context's pool on the way out (stream-ordered reuse), whatever the outcome.
+static int prove_fs_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const ProveFsIo &io) {
+  if (ctx->shard_world > 1) return BPGPU_E_ARG;      // partial sums cannot be hashed: a sharded proof needs the ranks' exchange
+  const ProveFsDims d = prove_fs_dims(c);
+  const size_t n = d.n, m = d.m, k = d.k;
+  hipStream_t st = ctx->st;
+  const OperandSrc dev{true, false};                 // operands in HBM; ONE input flag for the whole chain
+  void *dchs, *dscs, *dpts, *dsteps, *dlr, *dzero;
+  CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + k) * 32, &dchs));
+  CK(ws_get(ctx, WS_PFS_SC, nb * (8 + m + 10 + 1 + 3) * 32, &dscs));
+  CK(ws_get(ctx, WS_PFS_PTS, nb * 5 * (64 + sizeof(JacRaw)), &dpts));
+  CK(ws_get(ctx, WS_PFS_SCHED, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
+  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
+  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
+  uint64_t *dstates = (uint64_t *)dchs;
+  Words8 *dch = (Words8 *)dchs + nb, *duch = dch + 5 * nb;                        // y z u x w: nb each; then u_1..u_k
+  const uint8_t *cy = (const uint8_t *)dch, *cz = (const uint8_t *)(dch + nb), *cu = (const uint8_t *)(dch + 2 * nb),
+                *cx = (const uint8_t *)(dch + 3 * nb), *cw = (const uint8_t *)(dch + 4 * nb);
+  Words8 *dbl = (Words8 *)dscs, *dvb = dbl + 8 * nb, *drows = dvb + nb * m, *dtb2 = drows + 10 * nb, *dsc3 = dtb2 + nb;
+  Words8 *dT = (Words8 *)dpts;
+  JacRaw *dTres = (JacRaw *)(dT + nb * 5 * 2);
+  if (ctx->psched_key[0] != m || ctx->psched_key[1] != d.padded_n) {
+    TrStep steps[PROVER_SCHEDULE_MAX];
+    const int len = prover_transcript_schedule(steps, m, d.padded_n, ctx->psched_cut);
+    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, st));
+    HIPCK(ctx, hipStreamSynchronize(st));   // `steps` is a local
+    ctx->psched_key[0] = m; ctx->psched_key[1] = d.padded_n;
+  }
+  const TrStep *steps = (const TrStep *)dsteps;
+  const int *cut = ctx->psched_cut;
+  bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
+  if (!s) return BPGPU_E_OOM;
+  ProverOwner pown(s, ProverFree{ctx});
+  IppOwner iown(nullptr, IppFree{ctx});
+  s->nb = nb; s->planes = 1; s->g = g;
+  CK(copy_in(ctx, dstates, io.states_in, nb * 32, true));
+  {
+    ProfScope link(ctx, 22, st);
+    scalars_from_ark(st, (const Words8 *)io.blindings, dbl, 8 * nb, ctx->d_flag);
+    scalars_from_ark(st, (const Words8 *)io.v_blinding, dvb, nb * m, ctx->d_flag);
+  }
+  // prover.rs:420-585: append_u64("m"), the phase-1 commitments, the 1-phase separator, the identity phase-2 points; y, z
+  Words8 *dA;
+  CK(prover_commit_core(ctx, g, s, nb, n, io.a_L, io.a_R, io.a_O, io.s_L, io.s_R, io.vector_keys, io.blindings, 8 * 32, dev, &dA));
+  {
+    ProfScope link(ctx, 22, st);
+    prover_transcript(st, nb, steps + cut[0], cut[1] - cut[0], dstates, dA, 3, nullptr, 0, dch);
+  }
+  // :587-640: y^-1, the flattened constraints, l / r coefficients, t_1..t_6; T_i = t_i B + tb_i B_blinding; u, x
+  Words8 *dt, *dwV;
+  CK(session_polys_core(ctx, s, c, cy, cz, nullptr, dev, &dt, &dwV));
+  s->n = n; s->m = m;
+  {
+    ProfScope link(ctx, 22, st);
+    prove_fs_t_rows(st, nb, dt, dbl, drows);
+  }
+  {
+    ProfScope tmsm(ctx, 18, st);
+    CK(msm_gens_dev(ctx, g, nb * 5, 0, (const uint32_t *)drows, dTres, st));
+    jac_to_boundary(st, dTres, dT, nb * 5);
+  }
+  {
+    // :644-686: tb2 = <wV, v_blinding>, t_x, t_x_blinding, e_blinding; w; then innerproduct_domain_sep (inner_product_proof.rs:72)
+    ProfScope link(ctx, 22, st);
+    prover_transcript(st, nb, steps + cut[1], cut[2] - cut[1], dstates, dT, 5, nullptr, 0, dch);
+    const bool coop = m > PROVE_FS_DOT_LANE_MAX;
+    if (coop) sc_dot_batched(st, nb, m, dwV, m, dvb, m, dtb2, 1);
+    prove_fs_glue(st, nb, m, (const Words8 *)cx, dt, dbl, dwV, dvb, coop ? dtb2 : nullptr, dsc3);
+    prover_transcript(st, nb, steps + cut[2], cut[3] - cut[2], dstates, nullptr, 0, dsc3, 3, dch);
+  }
+  // :687-708: l(x), r(x), the G / H factors, Q = w B; the k rounds (u_j kept for challenges_out)
+  CK(prover_ipp_begin_core(ctx, s, g, d.padded_n, n, cx, cu, nullptr, cw, dev, iown));
+  bpgpu_ipp *ipp = iown.get();
+  CK(ipp_rounds_fs_dev(ctx, ipp, k, dstates, dlr, duch, dzero));
+  {
+    ProfScope link(ctx, 22, st);
+    ProveFsAssemble a{nb, k, dA, dT, (const Words8 *)dlr, dsc3, ipp->a[ipp->cur], ipp->b[ipp->cur], dch, duch, dstates,
+                      (Words8 *)io.proof_points, (Words8 *)io.proof_scalars, (Words8 *)io.challenges_out, (Words8 *)io.states_out, io.wire};
+    prove_fs_assemble(st, a);
+  }
+  return launch_ok(ctx);
+}
+int bpgpu_r1cs_prove_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const void *states_in, const void *a_L,
+                            const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
+                            const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
+                            void *challenges_out, void *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs_check(ctx, g, c, nb, states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call
+    const ProveFsIo io{(const uint8_t *)states_in, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O, (const uint8_t *)s_L,
+                       (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)v_blinding, (const uint8_t *)blindings,
+                       (uint8_t *)proof_points, (uint8_t *)proof_scalars, (uint8_t *)wire, (uint8_t *)challenges_out, (uint8_t *)states_out};
+    return prove_fs_locked(ctx, g, c, nb, io);
+  });
+}
+int bpgpu_r1cs_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const uint8_t *states_in, const uint8_t *a_L,
+                        const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
+                        const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire,
+                        uint8_t *challenges_out, uint8_t *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs_check(ctx, g, c, nb, states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const ProveFsDims d = prove_fs_dims(c);
+    const size_t tot = nb * d.n * 32, nvar = 11 + 2 * d.k, proof_len = 1 + 11 * 32 + (2 * d.k + 2) * 32;
+    // staging: the operands in the order of the argument list, then the results (the wire form, of odd length, last)
+    const size_t in_bytes[9] = {nb * 32, tot, tot, tot, s_L ? tot : 0, s_R ? tot : 0, vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32};
+    const size_t out_bytes[5] = {nb * nvar * 64, nb * 5 * 32, nb * (5 + d.k) * 32, nb * 32, wire ? nb * proof_len : 0};
+    size_t total = 0;
+    for (size_t b : in_bytes) total += b;
+    for (size_t b : out_bytes) total += b;
+    void *dstage;
+    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
+    const uint8_t *in_host[9] = {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings};
+    uint8_t *in_dev[9], *out_dev[5], *at = (uint8_t *)dstage;
+    for (int i = 0; i < 9; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
+    for (int i = 0; i < 5; i++) { out_dev[i] = at; at += out_bytes[i]; }
+    CK(flag_reset(ctx));
+    for (int i = 0; i < 9; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
+    const ProveFsIo io{in_dev[0], in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7], in_dev[8],
+                       out_dev[0], out_dev[1], wire ? out_dev[4] : nullptr, out_dev[2], out_dev[3]};
+    CK(prove_fs_locked(ctx, g, c, nb, io));
+    return checked_download(ctx, {{proof_points, out_dev[0], out_bytes[0]}, {proof_scalars, out_dev[1], out_bytes[1]},
+                                  {challenges_out, out_dev[2], challenges_out ? out_bytes[2] : 0},
+                                  {states_out, out_dev[3], states_out ? out_bytes[3] : 0}, {wire, out_dev[4], out_bytes[4]}});
+  });
 }
 /* scalars[i] * (curve generator): GeneratorsChain::next (generators.rs:112-124), Q = w * B (prover.rs:687) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out) {

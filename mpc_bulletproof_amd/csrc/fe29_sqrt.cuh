@@ -70,5 +70,14 @@ BP_HD bool words_gt(const uint32_t a[8], const uint32_t b[8]) {
   for (int j = 7; j >= 0; j--) { if (a[j] != b[j]) return a[j] > b[j]; }
   return false;
 }
+// affine boundary words (x, y; all zero = identity) -> the 32-byte compressed encoding in x: bit 7 of byte 31 = "y is the larger of
+// (y, -y)", bit 6 = point at infinity (k_codec.hip, the wire form of the fused prover)
+BP_HD void compress_xy_words(uint32_t x[8], const uint32_t y[8]) {
+  constexpr uint32_t HALF[8] = FP_HALF_W;
+  uint32_t hw[8], o = 0;
+  for (int j = 0; j < 8; j++) { hw[j] = HALF[j]; o |= x[j] | y[j]; }
+  if (o == 0) x[7] = 0x40000000u;
+  else if (words_gt(y, hw)) x[7] |= 0x80000000u;
+}
 
 }  // namespace bp

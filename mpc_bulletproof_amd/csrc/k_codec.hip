@@ -71,15 +71,10 @@ __global__ void __launch_bounds__(64) k_points_decompress(const Words8 *in, Word
 __global__ void __launch_bounds__(256) k_points_compress(const Words8 *xy, Words8 *out, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t x[8], y[8], o = 0;
+  uint32_t x[8], y[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) { x[j] = xy[2 * i].w[j]; y[j] = xy[2 * i + 1].w[j]; o |= x[j] | y[j]; }
-  constexpr uint32_t HALF[8] = FP_HALF_W;
-  uint32_t hw[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) hw[j] = HALF[j];
-  if (o == 0) x[7] = 0x40000000u;
-  else if (words_gt(y, hw)) x[7] |= 0x80000000u;
+  for (int j = 0; j < 8; j++) { x[j] = xy[2 * i].w[j]; y[j] = xy[2 * i + 1].w[j]; }
+  compress_xy_words(x, y);
 #pragma unroll
   for (int j = 0; j < 8; j++) out[i].w[j] = x[j];
 }

@@ -1,0 +1,138 @@
+// k_prove_fs.hip -- the small links between the stages of the one-call prover (bpgpu_r1cs_prove_fs: Prover::prove, r1cs/prover.rs:412-727,
+// for a circuit without randomized constraints, with the transcript on the device).  The stages themselves are the staged entry
+// points' kernels (phase commitments, polynomial build, fixed-base MSMs, the IPP session and its rounds) and the transcript slices
+// of k_transcript.hip; here: the scalar rows of the T commitments, the scalars between the x and the w challenge, proof assembly.
+// Each launch is a short link of one batch's latency chain -- a lane per proof (or per output item), nothing to tune for throughput.
+#include "fe29_sqrt.cuh"
+#include "fn_dev.cuh"
+#include "kernels.h"
+
+using namespace bp;
+
+namespace bpk {
+
+// T_j = t_j B + tb_j B_blinding for j in {1, 3, 4, 5, 6} (prover.rs:627-631) as rows of msm_gens over [B, B_blinding] (n = 0):
+// rows[(5 p + j) * 2] = (t_j, tb_j).  t: nb x 6 (t1..t6); bl: nb x 8 (i o s blinding, tb1 tb3 tb4 tb5 tb6), both plain canonical.
+__global__ void __launch_bounds__(256) k_pfs_t_rows(size_t nb, const Words8 *t, const Words8 *bl, Words8 *rows) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nb * 5) return;
+  const size_t p = r / 5, j = r % 5;
+  rows[2 * r] = t[p * 6 + (j ? j + 1 : 0)];
+  rows[2 * r + 1] = bl[p * 8 + 3 + j];
+}
+void prove_fs_t_rows(hipStream_t st, size_t nb, const Words8 *t, const Words8 *bl, Words8 *rows) {
+  if (nb) hipLaunchKernelGGL(k_pfs_t_rows, dim3((nb * 5 + 255) / 256), dim3(256), 0, st, nb, t, bl, rows);
+}
+
+// prover.rs:644-678 with n2 = 0 (no second phase: the u terms of :674-676 vanish), a lane per proof:
+//   tb2 = <wV, v_blinding>                       (:644-648; m <= PROVE_FS_DOT_LANE_MAX: here, a serial loop; above: tb2_pre, which
+//                                                 sc_dot_batched -- a block per proof, shuffle + LDS reduction -- has computed)
+//   t_x = sum_i t_i x^i, t_x_blinding = sum_i tb_i x^i  (i = 1..6, util.rs:192-194);  e_blinding = x (i_b + x (o_b + x s_b))  (:678)
+// out: nb x 3 (t_x, t_x_blinding, e_blinding), plain canonical -- the third transcript slice absorbs them from there.
+__global__ void __launch_bounds__(64) k_pfs_glue(size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV,
+                                                 const Words8 *vb, const Words8 *tb2_pre, Words8 *out) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  Fn tb2 = fe_zero<FN>();
+  if (tb2_pre) tb2 = load_plain(&tb2_pre[p]);
+  else {
+    for (size_t i = 0; i < m; i++) {
+      tb2 = add(tb2, mul(load_plain(&wV[p * m + i]), load_plain(&vb[p * m + i])));
+      if ((i & 15) == 15) tb2 = fn_reduce(tb2);
+    }
+    tb2 = fn_reduce(tb2);
+  }
+  const Fn xx = load_plain(&x[p]);
+  const Words8 *tp = t + p * 6, *bp_ = bl + p * 8;
+  Fn tx = load_plain(&tp[5]), tb = load_plain(&bp_[7]);
+#pragma unroll 1
+  for (int i = 4; i >= 0; i--) {
+    tx = add(mul(tx, xx), load_plain(&tp[i]));
+    // tb1 tb2 tb3 tb4 tb5 tb6: tb2 is not a draw, the others lie at bl[3], bl[4..7]
+    const Fn c = i == 1 ? tb2 : load_plain(&bp_[i == 0 ? 3 : 2 + i]);
+    tb = add(mul(tb, xx), c);
+  }
+  store_plain(&out[p * 3], mul(tx, xx));
+  store_plain(&out[p * 3 + 1], mul(tb, xx));
+  const Fn e = mul(xx, add(load_plain(&bp_[0]), mul(xx, add(load_plain(&bp_[1]), mul(xx, load_plain(&bp_[2]))))));
+  store_plain(&out[p * 3 + 2], e);
+}
+void prove_fs_glue(hipStream_t st, size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV, const Words8 *vb,
+                   const Words8 *tb2_pre, Words8 *out) {
+  if (nb) hipLaunchKernelGGL(k_pfs_glue, dim3((nb + 63) / 64), dim3(64), 0, st, nb, m, x, t, bl, wV, vb, tb2_pre, out);
+}
+
+// Proof assembly, a lane per output item of a proof: its 11 + 2k points, 5 scalars, 5 + k challenges and chain state.
+//   A: nb x 3 points, T: nb x 5 points, lr: k x nb x (L, R) points (round-major, as the round loop leaves them); sc3: nb x 3 (the
+//   glue's); a, b: nb; ch: 5 arrays of nb (y z u x w); uch: k arrays of nb (u_1..u_k); states: 4 x u64 per proof.
+//   proof_points  nb x (11 + 2k) x 64 B : A_I1 A_O1 S1 A_I2 A_O2 S2 (identity) T_1 T_3 T_4 T_5 T_6 L_0.. R_0..
+//   proof_scalars nb x 5 x 32 B        : t_x t_x_blinding e_blinding a b
+//   wire (optional) nb x proof_len     : R1CSProof::to_bytes, r1cs/proof.rs:82-109 -- version byte 0, A_I1 A_O1 S1 T_1..T_6 compressed,
+//                                        the three scalars big-endian, (L_j, R_j) pairs compressed, a, b big-endian
+//   challenges_out (optional) nb x (5 + k) x 32 B : y z u x w u_1..u_k;  states_out (optional) nb x 32 B
+// (ProveFsAssemble: kernels.h)
+__device__ __forceinline__ void put_bytes_le(uint8_t *dst, const uint32_t w[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    dst[4 * j] = (uint8_t)w[j]; dst[4 * j + 1] = (uint8_t)(w[j] >> 8); dst[4 * j + 2] = (uint8_t)(w[j] >> 16); dst[4 * j + 3] = (uint8_t)(w[j] >> 24);
+  }
+}
+__device__ __forceinline__ void put_bytes_be(uint8_t *dst, const uint32_t w[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    uint8_t *d = dst + 28 - 4 * j;
+    d[3] = (uint8_t)w[j]; d[2] = (uint8_t)(w[j] >> 8); d[1] = (uint8_t)(w[j] >> 16); d[0] = (uint8_t)(w[j] >> 24);
+  }
+}
+__global__ void __launch_bounds__(256) k_pfs_assemble(ProveFsAssemble o) {
+  const size_t k = o.k, nvar = 11 + 2 * k, per = nvar + 5 + (5 + k) + 1, proof_len = 1 + 11 * 32 + (2 * k + 2) * 32;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= o.nb * per) return;
+  const size_t p = t / per, s = t - p * per;
+  uint8_t *wire = o.wire ? o.wire + p * proof_len : nullptr;
+  if (s < nvar) {
+    const Words8 *src = nullptr;     // identity: A_I2 A_O2 S2
+    size_t wslot = (size_t)-1;       // 32-byte slot of the wire body, none for the identity points (version 0 omits them)
+    if (s < 3) { src = o.A + (p * 3 + s) * 2; wslot = s; }
+    else if (s >= 6 && s < 11) { src = o.T + (p * 5 + (s - 6)) * 2; wslot = s - 3; }
+    else if (s >= 11 && s < 11 + k) { src = o.lr + ((s - 11) * o.nb + p) * 4; wslot = 11 + 2 * (s - 11); }
+    else if (s >= 11 + k) { src = o.lr + ((s - 11 - k) * o.nb + p) * 4 + 2; wslot = 11 + 2 * (s - 11 - k) + 1; }
+    uint32_t x[8], y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) { x[j] = src ? src[0].w[j] : 0u; y[j] = src ? src[1].w[j] : 0u; }
+    Words8 *dst = o.proof_points + (p * nvar + s) * 2;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { dst[0].w[j] = x[j]; dst[1].w[j] = y[j]; }
+    if (wire && wslot != (size_t)-1) {
+      compress_xy_words(x, y);
+      put_bytes_le(wire + 1 + 32 * wslot, x);
+    }
+    if (wire && s == 0) wire[0] = 0;   // ONE_PHASE_COMMITMENTS
+  } else if (s < nvar + 5) {
+    const size_t q = s - nvar;
+    const Words8 *src = q < 3 ? o.sc3 + p * 3 + q : (q == 3 ? o.a + p : o.b + p);
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = src->w[j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) o.proof_scalars[p * 5 + q].w[j] = w[j];
+    if (wire) put_bytes_be(wire + 1 + 32 * (q < 3 ? 8 + q : 11 + 2 * k + (q - 3)), w);
+  } else if (s < nvar + 5 + 5 + k) {
+    if (!o.challenges_out) return;
+    const size_t c = s - nvar - 5;
+    o.challenges_out[p * (5 + k) + c] = c < 5 ? o.ch[c * o.nb + p] : o.uch[(c - 5) * o.nb + p];
+  } else if (o.states_out) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint64_t v = o.states[p * 4 + i];
+      o.states_out[p].w[2 * i] = (uint32_t)v; o.states_out[p].w[2 * i + 1] = (uint32_t)(v >> 32);
+    }
+  }
+}
+void prove_fs_assemble(hipStream_t st, const ProveFsAssemble &a) {
+  if (!a.nb) return;
+  const size_t tot = a.nb * (11 + 2 * a.k + 5 + 5 + a.k + 1);
+  hipLaunchKernelGGL(k_pfs_assemble, dim3((tot + 255) / 256), dim3(256), 0, st, a);
+}
+
+}  // namespace bpk

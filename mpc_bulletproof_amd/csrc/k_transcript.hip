@@ -553,4 +553,98 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
   hipLaunchKernelGGL(k_ipp_round_challenge, dim3((nb + 63) / 64), dim3(64), 0, st, nb, states, lr, u_out);
 }
 
+// ---- the PROVER's side of the schedule (r1cs/prover.rs:420-686 for a circuit without randomized constraints), for the one-call
+// prover (bpgpu_r1cs_prove_fs): the same step table, cut where a challenge has to exist before the next arithmetic stage runs --
+//   slice 0: append_u64("m"), A_I1 A_O1 S1, the 1-phase separator, A_I2 A_O2 S2 (identity), y, z       -> the polynomial build
+//   slice 1: T_1 T_3 T_4 T_5 T_6, u, x                                                                  -> t(x), the blindings
+//   slice 2: t_x, t_x_blinding, e_blinding, w, innerproduct_domain_sep(padded n)                        -> the IPP session
+// One lane per proof; the chain state lives in `states` (4 x u64 per proof) between the slices.  points: pt_stride points per proof,
+// a step's src indexes them (TS_SRC_IDENTITY: the 64 zero bytes of the identity); scalars: sc_stride per proof; challenges out as
+// separate arrays, challenges[src * nb + p] (each is the contiguous operand of the stage that follows).  Nothing is validated: the
+// prover appends its own points without the identity check.
+constexpr uint32_t TS_SRC_IDENTITY = 0xFFFFFFFFu;
+__global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrStep *steps, int nsteps, uint64_t *states, const Words8 *points,
+                                                          size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges) {
+  // (no raised wave priority: the note in k_verify_transcript holds for a prover batch that runs beside others)
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  uint64_t st[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) st[i] = states[p * 4 + i];
+#pragma unroll 1
+  for (int t = 0; t < nsteps; t++) {
+    const TrStep s = steps[t];
+    const Label lab = TR_LABELS[s.label];
+    switch (s.kind) {
+      case TS_DOMSEP: {
+        constexpr Label DS = mk_label("dom-sep");
+        uint64_t tail[5] = {32, lab.w[0], lab.w[1], lab.w[2], lab.w[3]};
+        chain_hash<5>(st, 0x00, DS, tail);
+        break;
+      }
+      case TS_SCALAR: {
+        const Words8 *sc = scalars + p * sc_stride + s.src;
+        uint64_t tail[5];
+        tail[0] = 32;
+#pragma unroll
+        for (int i = 0; i < 4; i++) tail[1 + i] = (uint64_t)sc->w[2 * i] | ((uint64_t)sc->w[2 * i + 1] << 32);
+        chain_hash<5>(st, 0x00, lab, tail);
+        break;
+      }
+      case TS_U64: {
+        uint64_t tail[2] = {8, s.value};
+        chain_hash<2>(st, 0x00, lab, tail);
+        break;
+      }
+      case TS_POINT: {
+        uint64_t tail[9];
+        tail[0] = 64;
+        if (s.src == TS_SRC_IDENTITY) {
+#pragma unroll
+          for (int i = 1; i < 9; i++) tail[i] = 0;
+        } else {
+          load64(points + (p * pt_stride + s.src) * 2, tail + 1);
+        }
+        chain_hash<9>(st, 0x00, lab, tail);
+        break;
+      }
+      default:
+        tr_challenge_scalar(st, lab, &challenges[(size_t)s.src * nb + p]);
+        break;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) states[p * 4 + i] = st[i];
+}
+// the step list and its three slices: slice j = steps [cut[j], cut[j + 1]).  Points are indexed within the slice's own array
+// (A_I1 A_O1 S1 | T_1 T_3 T_4 T_5 T_6), scalars as t_x t_x_blinding e_blinding, challenges as y z u x w.
+int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4]) {
+  int n = 0;
+  auto add = [&](uint8_t kind, uint8_t label, uint32_t src, uint64_t value) {
+    out[n].kind = kind; out[n].label = label; out[n].validate = 0; out[n].pad = 0; out[n].src = src; out[n].value = value; n++;
+  };
+  cut[0] = 0;
+  add(TS_U64, LB_m, 0, m);                                                                       // prover.rs:420
+  add(TS_POINT, LB_AI1, 0, 0); add(TS_POINT, LB_AO1, 1, 0); add(TS_POINT, LB_S1, 2, 0);          // :496-498
+  add(TS_DOMSEP, LB_1phase, 0, 0);                                                               // :388
+  add(TS_POINT, LB_AI2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_AO2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_S2, TS_SRC_IDENTITY, 0);   // :566-580
+  add(TS_CHALLENGE, LB_y, 0, 0); add(TS_CHALLENGE, LB_z, 1, 0);                                  // :584-585
+  cut[1] = n;
+  const uint8_t tl[5] = {LB_T1, LB_T3, LB_T4, LB_T5, LB_T6};
+  for (int j = 0; j < 5; j++) add(TS_POINT, tl[j], (uint32_t)j, 0);                              // :633-637
+  add(TS_CHALLENGE, LB_u, 2, 0); add(TS_CHALLENGE, LB_x, 3, 0);                                  // :639-640
+  cut[2] = n;
+  add(TS_SCALAR, LB_tx, 0, 0); add(TS_SCALAR, LB_txb, 1, 0); add(TS_SCALAR, LB_eb, 2, 0);        // :680-683
+  add(TS_CHALLENGE, LB_w, 4, 0);                                                                 // :686
+  add(TS_DOMSEP, LB_ipp, 0, 0); add(TS_U64, LB_n, 0, padded_n);                                  // inner_product_proof.rs:72
+  cut[3] = n;
+  return n;
+}
+void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
+                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges) {
+  if (!nb || nsteps <= 0) return;
+  hipLaunchKernelGGL(k_prover_transcript, dim3((nb + 63) / 64), dim3(64), 0, st, nb, steps_dev, nsteps, states, points, pt_stride, scalars,
+                     sc_stride, challenges);
+}
+
 }  // namespace bpk

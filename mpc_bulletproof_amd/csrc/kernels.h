@@ -320,6 +320,33 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
 // wave-cooperative Keccak, u and u^-1
 void ipp_round_tail(hipStream_t st, size_t nb, const JacRaw *sums, uint64_t *states, Words8 *lr_xy, Words8 *u_out, Words8 *uinv_out, const JacRaw *partials = nullptr, size_t chunks = 0 /* > 1: sums[2p + s] = sum of partials[(2p + s) * chunks + i], added up here */);
 
+// ---- the one-call prover (bpgpu_r1cs_prove_fs): the prover's transcript slices (k_transcript.hip) and the links between the stages
+// (k_prove_fs.hip) ------------------------------------------------------------------------------------
+// host: the prover's step list for a one-phase circuit (22 steps) and its three slices, slice j = steps [cut[j], cut[j + 1]):
+// up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator
+constexpr int PROVER_SCHEDULE_MAX = 24;
+int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4]);
+// one slice for nb provers, a lane each; states: 4 x u64 per prover, updated.  A step's src indexes points (pt_stride per prover),
+// scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p]
+void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
+                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges);
+// rows[(5 p + j) * 2 ..] = (t, t_blinding) of T_1, T_3..T_6 over [B, B_blinding]; t: nb x 6, bl: nb x 8 (i o s blinding, tb1 tb3 tb4 tb5 tb6)
+void prove_fs_t_rows(hipStream_t st, size_t nb, const Words8 *t, const Words8 *bl, Words8 *rows);
+// out[p] = (t_x, t_x_blinding, e_blinding) from x, t, bl and tb2 = <wV, v_blinding>: summed by the proof's lane for m up to
+// PROVE_FS_DOT_LANE_MAX (tb2_pre = nullptr), above it taken from tb2_pre (nb values of sc_dot_batched, a block per proof)
+constexpr size_t PROVE_FS_DOT_LANE_MAX = 16;
+void prove_fs_glue(hipStream_t st, size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV, const Words8 *vb,
+                   const Words8 *tb2_pre, Words8 *out);
+// proof assembly (layouts: k_prove_fs.hip): proof_points, proof_scalars, and the optional wire form, challenges and chain states
+struct ProveFsAssemble {
+  size_t nb, k;
+  const Words8 *A, *T, *lr, *sc3, *a, *b, *ch, *uch;
+  const uint64_t *states;
+  Words8 *proof_points, *proof_scalars, *challenges_out, *states_out;
+  uint8_t *wire;
+};
+void prove_fs_assemble(hipStream_t st, const ProveFsAssemble &a);
+
 // ---- two-party prover, one party's local arithmetic (k_mpc.hip): 3 nb virtual provers v = 3 p + k (k = 0 share, 1 MAC, 2 public
 // modifier); triples [p][j][x, y, z][k][i], masked [p][j][d, e][k][i], opened [p][j][d, e][i] (plain canonical words)
 // polys [6][3 nb][n][9] as prover_polys (r0 holds the public value on every plane); y, y_inv: 3 nb; wV_out: nb x m; j < 6

@@ -1439,10 +1439,16 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
   bpgpu_gens *gens = bp_gens.device_tables(pc);
   const size_t n1 = cs[0]->a_L.size(), m = cs[0]->v.size();
   const bool vkeys = rngs[0]->vector_keys();
+  // BPH_PROVE_FUSED: one-phase circuits take bpgpu_r1cs_prove_fs -- the whole protocol, transcript included, in ONE device call
+  // (below); everything else, and the default, is the staged sequence
+  bool fused = getenv("BPH_PROVE_FUSED") && !group && n1 >= 1 && !cs[0]->param;
+  for (size_t p = 0; p < nb && fused; p++) fused = cs[p]->deferred.empty();
+  std::vector<uint8_t> st_entry(fused ? nb * 32 : 0);
   for (size_t p = 0; p < nb; p++) {
     CsCore *c = cs[p];
     if (c->a_L.size() != n1 || c->v.size() != m) throw std::invalid_argument("prove_batch: circuits differ in shape");
     if (rngs[p]->vector_keys() != vkeys) throw std::invalid_argument("prove_batch: the provers' Rngs differ in vector_keys()");
+    if (fused) memcpy(&st_entry[32 * p], c->tr.state(), 32);                             // the device appends "m" itself
     c->tr.append_u64("m", c->v.size());                                                  // prover.rs:420
   }
   if (bp_gens.gens_capacity < n1) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :450-452
@@ -1472,6 +1478,68 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
       rngs[p]->rekey(dig.data(), dig.size());
     }
   }, 16);
+  if (fused) {
+    // Every draw up front, in the reference's order -- i_blinding o_blinding s_blinding, the vector key or s_L, s_R (:457-462), tb1
+    // tb3 tb4 tb5 tb6 (:621-625): with no second phase nothing is drawn in between, so it is the staged route's stream.
+    const size_t padded_n = next_pow2(n1), plane = nb * n1 * 32;
+    if (bp_gens.gens_capacity < padded_n) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :511-513
+    size_t k = 0;
+    for (size_t t = padded_n; t > 1; t >>= 1) k++;
+    for (size_t p = 1; p < nb; p++)
+      if (cs[p]->rows_hash[0] != cs[0]->rows_hash[0] || cs[p]->rows_hash[1] != cs[0]->rows_hash[1] || cs[p]->rows_nnz != cs[0]->rows_nnz ||
+          cs[p]->constraints.size() != cs[0]->constraints.size())
+        throw std::invalid_argument("prove_batch: constraint rows differ between provers");
+    std::vector<uint8_t> in((vkeys ? 3 : 5) * plane + nb * (32 + m * 32 + 8 * 32) + 1);
+    uint8_t *paL = in.data(), *paR = paL + plane, *paO = paR + plane, *psL = paO + plane, *psR = psL + plane;
+    uint8_t *pkey = paO + plane + (vkeys ? 0 : 2 * plane), *pvb = pkey + nb * 32, *pbl = pvb + nb * m * 32;
+    parallel_for(nb, [&](size_t p) {
+      Rng &r = *rngs[p];
+      for (int i = 0; i < 3; i++) r.scalar().to_ark_le(pbl + (p * 8 + i) * 32);
+      if (vkeys) {
+        for (int i = 0; i < 4; i++) { uint64_t w = r.next_u64(); memcpy(pkey + p * 32 + 8 * i, &w, 8); }
+      } else {
+        std::vector<Scalar> v(n1);
+        r.scalars(v.data(), n1);
+        pack_range_ark(psL + p * n1 * 32, v.data(), n1);
+        r.scalars(v.data(), n1);
+        pack_range_ark(psR + p * n1 * 32, v.data(), n1);
+      }
+      for (int i = 3; i < 8; i++) r.scalar().to_ark_le(pbl + (p * 8 + i) * 32);
+      pack_range_ark(paL + p * n1 * 32, cs[p]->a_L.data(), n1);
+      pack_range_ark(paR + p * n1 * 32, cs[p]->a_R.data(), n1);
+      pack_range_ark(paO + p * n1 * 32, cs[p]->a_O.data(), n1);
+      pack_range_ark(pvb + p * m * 32, cs[p]->v_blinding.data(), m);
+      cs[p]->create_randomized_constraints();                                              // :501 (nothing deferred: the 1-phase separator)
+    });
+    lap("prove: pack planes, draws");
+    bpgpu_circuit *circ = circuit_cache().acquire(*cs[0], n1, m);
+    struct CircuitGuard { bpgpu_circuit *c; ~CircuitGuard() { if (c) circuit_cache().release(c); } } circuit_guard{circ};
+    const size_t nvar = 11 + 2 * k;
+    std::vector<uint8_t> pts(nb * nvar * 64), sc(nb * 5 * 32), st_out(nb * 32);
+    int rc = bpgpu_r1cs_prove_fs(d.ctx(), gens, circ, nb, st_entry.data(), paL, paR, paO, vkeys ? nullptr : psL, vkeys ? nullptr : psR,
+                                 vkeys ? pkey : nullptr, m ? pvb : nullptr, pbl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
+    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
+    d.check(rc, "bpgpu_r1cs_prove_fs");
+    for (size_t p = 0; p < nb; p++) {
+      R1CSProof &pr = proofs[p];
+      const uint8_t *pp = &pts[p * nvar * 64];
+      StarkPoint *dst[11] = {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6};
+      for (int i = 0; i < 11; i++) memcpy(dst[i]->xy.data(), pp + 64 * i, 64);
+      for (size_t r = 0; r < k; r++) {
+        StarkPoint Lp, Rp;
+        memcpy(Lp.xy.data(), pp + 64 * (11 + r), 64);
+        memcpy(Rp.xy.data(), pp + 64 * (11 + k + r), 64);
+        pr.ipp_proof.L_vec.push_back(Lp);
+        pr.ipp_proof.R_vec.push_back(Rp);
+      }
+      const uint8_t *ps5 = &sc[p * 160];
+      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
+      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
+      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up, as after bpgpu_ipp_run_fs
+    }
+    lap("prove: fused device call");
+    return proofs;
+  }
   // One phase of commitments, prover.rs:457-494 (lo = 0) / :519-565 (lo = n1): blinding factors, then A_I, A_O, S over
   // [B_blinding, G_lo.., H_lo..] -- the witness planes go to the device once (bpgpu_r1cs_prover_commit keeps them in the
   // session for the polynomial build), the blinding vectors s_L, s_R either with them or, Rng::vector_keys(), as one 32-byte

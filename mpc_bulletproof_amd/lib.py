@@ -21,6 +21,7 @@ SYMBOLS = [
     "bpgpu_mpc_prover_commit", "bpgpu_mpc_prover_polys_mask", "bpgpu_mpc_prover_polys_finish", "bpgpu_mpc_prover_ipp_begin",
     "bpgpu_mpc_ipp_mask", "bpgpu_mpc_ipp_round",
     "bpgpu_ipp_verify_batch", "bpgpu_ipp_verify_batch_dev", "bpgpu_ipp_verify_gens", "bpgpu_ipp_verify_fs",
+    "bpgpu_r1cs_prove_fs", "bpgpu_r1cs_prove_fs_dev",
 ]
 
 
@@ -89,7 +90,7 @@ OPT = {"msm_wp_max": 1, "msm_pip2_single": 2, "verify_no_fuse": 3, "verify_windo
 PROF_NAMES = ["verify_scalars", "fixed_msm", "points_from_boundary", "straus", "verify_finalize", "transcript", "verify_msm",
               "verify_windows", "verify_front", "verify_groups", "verify_back", "verify_verdict", "combined_front_scalars_digits",
               "combined_sort_accum_reduce", "combined_unused", "combined_final", "prover_commit", "prover_polys", "msm_gens", "ipp_begin",
-              "ipp_rounds", "ipp_round_msm", "reserved22", "reserved23"]
+              "ipp_rounds", "ipp_round_msm", "prove_fs_links", "reserved23"]
 PROF_KINDS = len(PROF_NAMES)
 
 
@@ -529,6 +530,28 @@ class BpGpu:
         t, wv = _out(32 * 6 * nb), _out(32 * nb * max(m, 1))
         self._ck(_lib.bpgpu_r1cs_prover_session_polys_param(self.ctx, session, circuit, _buf(y), _buf(z), _buf(gadget_challenges), t, wv))
         return bytes(t)[:32 * 6 * nb], bytes(wv)[:32 * nb * m]
+
+    def r1cs_prove_fs(self, gens, circuit, nb, n, m, states, a_L, a_R, a_O, blindings, v_blinding=None, s_L=None, s_R=None,
+                      vector_keys=None, want_wire=True):
+        """Prover::prove in one call for nb provers of a one-phase circuit of n multipliers and m commitments, transcript on the
+        device (include/bpgpu.h bpgpu_r1cs_prove_fs).  Witness, v_blinding and blindings (nb x 8) in ark-ff Montgomery form, the
+        blinding vectors explicit or from vector_keys -> (proof_points nb x (11 + 2k) x 64 B, proof_scalars nb x 5 x 32 B, wire
+        nb x proof_len or None, challenges nb x (5 + k) x 32 B, states_out nb x 32 B)"""
+        k = max(n - 1, 0).bit_length()
+        nvar, plen = 11 + 2 * k, 1 + 11 * 32 + (2 * k + 2) * 32
+        pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
+        wire = _out(nb * plen) if want_wire else None
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_prove_fs(self.ctx, gens, circuit, C.c_size_t(nb), opt(states), opt(a_L), opt(a_R), opt(a_O), opt(s_L),
+                                          opt(s_R), opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so))
+        return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
+                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
+
+    def r1cs_prove_fs_dev(self, gens, circuit, nb, d_states, d_a_L, d_a_R, d_a_O, d_blindings, d_points, d_scalars, d_v_blinding=None,
+                          d_s_L=None, d_s_R=None, d_vector_keys=None, d_wire=None, d_ch=None, d_states_out=None):
+        """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
+        self._ck(_lib.bpgpu_r1cs_prove_fs_dev(self.ctx, gens, circuit, C.c_size_t(nb), d_states, d_a_L, d_a_R, d_a_O, d_s_L, d_s_R,
+                                              d_vector_keys, d_v_blinding, d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out))
 
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
