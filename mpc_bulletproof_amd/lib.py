@@ -2,28 +2,12 @@
 import ctypes as C
 import os
 
+from ._abi import PROTOS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libbpgpu.so")
 
-SYMBOLS = [
-    "bpgpu_device_count", "bpgpu_create", "bpgpu_destroy", "bpgpu_strerror", "bpgpu_last_error", "bpgpu_sync",
-    "bpgpu_stream", "bpgpu_set_latency_mode", "bpgpu_set_shard", "bpgpu_r1cs_verify_shard", "bpgpu_set_option", "bpgpu_get_option", "bpgpu_input_flag", "bpgpu_profile_enable", "bpgpu_profile_select", "bpgpu_profile_read", "bpgpu_profile_epoch", "bpgpu_profile_intervals", "bpgpu_malloc", "bpgpu_free", "bpgpu_upload", "bpgpu_download", "bpgpu_upload_async", "bpgpu_download_async", "bpgpu_host_alloc", "bpgpu_host_free",
-    "bpgpu_batch_inverse", "bpgpu_inner_product", "bpgpu_msm", "bpgpu_msm_batch", "bpgpu_msm_batch_dev", "bpgpu_points_sum", "bpgpu_msm_ark", "bpgpu_scalars_from_ark", "bpgpu_scalars_to_ark", "bpgpu_points_from_ark", "bpgpu_points_to_ark", "bpgpu_msm_shared", "bpgpu_points_decompress", "bpgpu_points_compress", "bpgpu_gens_create",
-    "bpgpu_gens_destroy", "bpgpu_gens_capacity", "bpgpu_msm_gens", "bpgpu_msm_gens_ark", "bpgpu_fold_witness",
-    "bpgpu_verification_scalars", "bpgpu_ipp_begin", "bpgpu_ipp_begin_gens", "bpgpu_ipp_destroy", "bpgpu_ipp_len", "bpgpu_ipp_round",
-    "bpgpu_ipp_fold", "bpgpu_ipp_finish", "bpgpu_ipp_folded_gens", "bpgpu_ipp_run_fs", "bpgpu_r1cs_prover_polys", "bpgpu_r1cs_prover_polys_ark", "bpgpu_r1cs_prover_eval", "bpgpu_r1cs_prover_ipp_begin", "bpgpu_prover_destroy", "bpgpu_r1cs_prover_commit", "bpgpu_r1cs_prover_session_polys", "bpgpu_r1cs_prover_session_polys_param",
-    "bpgpu_generator_mul", "bpgpu_circuit_create", "bpgpu_circuit_create_ark", "bpgpu_circuit_create_param", "bpgpu_circuit_destroy", "bpgpu_flatten_constraints",
-    "bpgpu_r1cs_verify_batch", "bpgpu_r1cs_verify_batch_dev", "bpgpu_r1cs_verify_stream", "bpgpu_r1cs_verify_stream_dev", "bpgpu_r1cs_verify_screened", "bpgpu_r1cs_verify_screened_dev", "bpgpu_r1cs_verify_screened_fs_dev", "bpgpu_r1cs_verify_combined",
-    "bpgpu_r1cs_verify_combined_dev", "bpgpu_r1cs_verify_batch_fs", "bpgpu_r1cs_verify_batch_fs_dev",
-    "bpgpu_r1cs_verify_batch_wire", "bpgpu_r1cs_verify_batch_wire_dev", "bpgpu_r1cs_verify_batch_param", "bpgpu_r1cs_verify_batch_fs2",
-    "bpgpu_r1cs_verify_batch_fs2_dev", "bpgpu_r1cs_verify_mixed_combined", "bpgpu_r1cs_verify_mixed_combined_dev",
-    "bpgpu_r1cs_verify_mixed_screened", "bpgpu_r1cs_verify_mixed_screened_dev",
-    "bpgpu_mpc_prover_commit", "bpgpu_mpc_prover_polys_mask", "bpgpu_mpc_prover_polys_finish", "bpgpu_mpc_prover_ipp_begin",
-    "bpgpu_mpc_ipp_mask", "bpgpu_mpc_ipp_round",
-    "bpgpu_ipp_verify_batch", "bpgpu_ipp_verify_batch_dev", "bpgpu_ipp_verify_gens", "bpgpu_ipp_verify_fs",
-    "bpgpu_r1cs_prove_fs", "bpgpu_r1cs_prove_fs_dev",
-]
-
+SYMBOLS = sorted(PROTOS)     # every entry point of include/bpgpu.h (_abi.py is generated from it by tools/gen_rust_sys.py)
 
 MIXED_MAX_GROUPS = 64       # BPGPU_MIXED_MAX_GROUPS
 MIXED_MAX_SEGMENTS = 16     # BPGPU_MIXED_MAX_SEGMENTS
@@ -34,13 +18,6 @@ class VerifyGroup(C.Structure):
     _fields_ = [("circuit", C.c_void_p), ("nb", C.c_size_t), ("n1", C.c_size_t), ("k", C.c_size_t),
                 ("points", C.c_void_p), ("scalars", C.c_void_p), ("challenges", C.c_void_p),
                 ("gadget_challenges", C.c_void_p), ("rho", C.c_void_p), ("ok", C.c_void_p)]
-
-
-def _ptr(x):
-    """a device pointer (c_void_p / int / None) as an integer address or None"""
-    if x is None:
-        return None
-    return x.value if isinstance(x, C.c_void_p) else int(x)
 
 
 class BpGpuError(RuntimeError):
@@ -55,23 +32,19 @@ def load():
             f"{SO_PATH} is missing: the HIP extension has not been built "
             "(run __graft_entry__.build()).  There is no CPU fallback.")
     lib = C.CDLL(SO_PATH)
-    lib.bpgpu_strerror.restype = C.c_char_p
-    lib.bpgpu_last_error.restype = C.c_char_p
-    lib.bpgpu_stream.restype = C.c_void_p
-    lib.bpgpu_gens_capacity.restype = C.c_size_t
-    lib.bpgpu_ipp_len.restype = C.c_size_t
+    for name, (restype, argtypes) in PROTOS.items():     # an integer of the wrong width is refused, never truncated
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
 _lib = load()
-_lib.bpgpu_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
-_lib.bpgpu_host_free.argtypes = [C.c_void_p]
 
 
 def host_alloc(nbytes, data=None):
     """page-locked staging memory (bpgpu_host_alloc), optionally filled with `data`; returns a c_void_p"""
     p = C.c_void_p()
-    rc = _lib.bpgpu_host_alloc(C.c_size_t(nbytes), C.byref(p))
+    rc = _lib.bpgpu_host_alloc(nbytes, C.byref(p))
     if rc or not p.value:
         raise BpGpuError(rc or E_OOM, "bpgpu_host_alloc")
     if data is not None:
@@ -81,6 +54,8 @@ def host_alloc(nbytes, data=None):
 
 def host_free(p):
     _lib.bpgpu_host_free(p)
+
+
 E_ARG, E_LEN, E_DEVICE, E_OOM, E_GENS = -1, -2, -3, -4, -5
 # bpgpu_set_option (include/bpgpu.h BPGPU_OPT_*)
 OPT = {"msm_wp_max": 1, "msm_pip2_single": 2, "verify_no_fuse": 3, "verify_window_parallel": 4, "verify_straus_np": 5,
@@ -144,11 +119,11 @@ class BpGpu:
     # ---- plumbing
     def set_option(self, name, value):
         """launch-route option of this context (OPT keys; include/bpgpu.h BPGPU_OPT_*)"""
-        self._ck(_lib.bpgpu_set_option(self.ctx, C.c_int(OPT[name]), C.c_int64(int(value))))
+        self._ck(_lib.bpgpu_set_option(self.ctx, OPT[name], int(value)))
 
     def get_option(self, name):
         v = C.c_int64()
-        self._ck(_lib.bpgpu_get_option(self.ctx, C.c_int(OPT[name]), C.byref(v)))
+        self._ck(_lib.bpgpu_get_option(self.ctx, OPT[name], C.byref(v)))
         return v.value
 
     def options(self, **kw):
@@ -176,18 +151,18 @@ class BpGpu:
 
     def malloc(self, nbytes):
         p = C.c_void_p()
-        self._ck(_lib.bpgpu_malloc(self.ctx, C.c_size_t(nbytes), C.byref(p)))
+        self._ck(_lib.bpgpu_malloc(self.ctx, nbytes, C.byref(p)))
         return p
 
     def free(self, p):
         self._ck(_lib.bpgpu_free(self.ctx, p))
 
     def upload(self, dptr, data):
-        self._ck(_lib.bpgpu_upload(self.ctx, dptr, _buf(data), C.c_size_t(len(data))))
+        self._ck(_lib.bpgpu_upload(self.ctx, dptr, _buf(data), len(data)))
 
     def upload_async(self, dptr, host_ptr, nbytes):
         """enqueue a copy from (page-locked) host memory on the context's stream; host_ptr: integer address / c_void_p"""
-        self._ck(_lib.bpgpu_upload_async(self.ctx, dptr, C.c_void_p(host_ptr if isinstance(host_ptr, int) else host_ptr.value), C.c_size_t(nbytes)))
+        self._ck(_lib.bpgpu_upload_async(self.ctx, dptr, host_ptr, nbytes))
 
     def to_device(self, data):
         p = self.malloc(len(data))
@@ -196,7 +171,7 @@ class BpGpu:
 
     def download(self, dptr, nbytes):
         o = _out(nbytes)
-        self._ck(_lib.bpgpu_download(self.ctx, o, dptr, C.c_size_t(nbytes)))
+        self._ck(_lib.bpgpu_download(self.ctx, o, dptr, nbytes))
         return bytes(o)[:nbytes]
 
     def input_flag(self):
@@ -213,7 +188,7 @@ class BpGpu:
     def profile_select(self, names=None):
         """restrict the event timing to the named kinds (PROF_NAMES); None = all"""
         mask = 0xffffffff if names is None else sum(1 << PROF_NAMES.index(n) for n in names)
-        self._ck(_lib.bpgpu_profile_select(self.ctx, C.c_uint32(mask)))
+        self._ck(_lib.bpgpu_profile_select(self.ctx, mask))
 
     def profile_read(self):
         ms = (C.c_double * PROF_KINDS)()
@@ -223,7 +198,6 @@ class BpGpu:
 
     def profile_epoch(self):
         """reference event for profile_intervals (of any context of this device); owned by the context"""
-        _lib.bpgpu_profile_epoch.restype = C.c_void_p
         e = _lib.bpgpu_profile_epoch(self.ctx)
         if not e:
             raise BpGpuError(E_DEVICE, "bpgpu_profile_epoch")
@@ -232,18 +206,18 @@ class BpGpu:
     def profile_intervals(self, epoch, cap=8192):
         """-> [(kind name, start ms, end ms)] of every timed launch since the last read, relative to `epoch`"""
         kind, a, b, n = (C.c_int32 * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), C.c_size_t(0)
-        self._ck(_lib.bpgpu_profile_intervals(self.ctx, epoch, C.c_size_t(cap), kind, a, b, C.byref(n)))
+        self._ck(_lib.bpgpu_profile_intervals(self.ctx, epoch, cap, kind, a, b, C.byref(n)))
         return [(PROF_NAMES[kind[i]], a[i], b[i]) for i in range(n.value)]
 
     # ---- scalar field
     def batch_inverse(self, scalars):
         n = len(scalars) // 32
         b = _inout(scalars)
-        self._ck(_lib.bpgpu_batch_inverse(self.ctx, b, C.c_size_t(n)))
+        self._ck(_lib.bpgpu_batch_inverse(self.ctx, b, n))
         return bytes(b)[:32 * n]
 
     def msm_batch_dev(self, nb, n, d_scalars, d_points, d_out):
-        self._ck(_lib.bpgpu_msm_batch_dev(self.ctx, C.c_size_t(nb), C.c_size_t(n), d_scalars, d_points, d_out))
+        self._ck(_lib.bpgpu_msm_batch_dev(self.ctx, nb, n, d_scalars, d_points, d_out))
 
     # ---- arkworks in-memory forms (include/bpgpu.h): scalars 32 B = x 2^256 mod n, points 96 B = Jacobian coords c 2^256 mod p
     def msm_ark(self, scalars_mont, points_jac_mont):
@@ -251,13 +225,13 @@ class BpGpu:
         if len(points_jac_mont) != 96 * n:
             raise BpGpuError(E_LEN, "msm_ark: length mismatch")
         o = _out(96)
-        self._ck(_lib.bpgpu_msm_ark(self.ctx, _buf(scalars_mont), _buf(points_jac_mont), C.c_size_t(n), o))
+        self._ck(_lib.bpgpu_msm_ark(self.ctx, _buf(scalars_mont), _buf(points_jac_mont), n, o))
         return bytes(o)
 
     def _ark(self, fn, data, isz, osz):
         n = len(data) // isz
         o = _out(osz * n)
-        self._ck(fn(self.ctx, _buf(data), C.c_size_t(n), o))
+        self._ck(fn(self.ctx, _buf(data), n, o))
         return bytes(o)[:osz * n]
 
     def scalars_from_ark(self, b):
@@ -276,33 +250,33 @@ class BpGpu:
         """sum of the 64-byte points in `points` (no scalars) -> 64 bytes"""
         n = len(points) // 64
         out = _out(64)
-        self._ck(_lib.bpgpu_points_sum(self.ctx, _buf(points), C.c_size_t(n), out))
+        self._ck(_lib.bpgpu_points_sum(self.ctx, _buf(points), n, out))
         return bytes(out)
 
     def msm_shared(self, nsets, n, scalars, points):
         """nsets MSMs over one point vector (msm_authenticated_iter's share / MAC / modifier MSMs)."""
         out = _out(64 * nsets)
-        self._ck(_lib.bpgpu_msm_shared(self.ctx, C.c_size_t(nsets), C.c_size_t(n), _buf(scalars), _buf(points), out))
+        self._ck(_lib.bpgpu_msm_shared(self.ctx, nsets, n, _buf(scalars), _buf(points), out))
         return bytes(out)[:64 * nsets]
 
     def points_decompress(self, compressed):
         """-> (xy bytes n x 64, ok list) for n x 32-byte compressed points"""
         n = len(compressed) // 32
         xy, ok = _out(64 * n), (C.c_int32 * max(n, 1))()
-        self._ck(_lib.bpgpu_points_decompress(self.ctx, _buf(compressed), C.c_size_t(n), xy, ok))
+        self._ck(_lib.bpgpu_points_decompress(self.ctx, _buf(compressed), n, xy, ok))
         return bytes(xy)[:64 * n], list(ok)[:n]
 
     def points_compress(self, xy):
         n = len(xy) // 64
         out = _out(32 * n)
-        self._ck(_lib.bpgpu_points_compress(self.ctx, _buf(xy), C.c_size_t(n), out))
+        self._ck(_lib.bpgpu_points_compress(self.ctx, _buf(xy), n, out))
         return bytes(out)[:32 * n]
 
     def inner_product(self, a, b):
         if len(a) != len(b):
             raise BpGpuError(E_LEN, "inner_product(a,b): lengths of vectors do not match")
         o = _out(32)
-        self._ck(_lib.bpgpu_inner_product(self.ctx, _buf(a), _buf(b), C.c_size_t(len(a) // 32), o))
+        self._ck(_lib.bpgpu_inner_product(self.ctx, _buf(a), _buf(b), len(a) // 32, o))
         return bytes(o)
 
     # ---- MSM
@@ -311,22 +285,21 @@ class BpGpu:
         if len(points) != 64 * n:
             raise BpGpuError(E_LEN, "msm: length mismatch")
         o = _out(64)
-        self._ck(_lib.bpgpu_msm(self.ctx, _buf(scalars), _buf(points), C.c_size_t(n), o))
+        self._ck(_lib.bpgpu_msm(self.ctx, _buf(scalars), _buf(points), n, o))
         return bytes(o)
 
     def msm_batch(self, nb, n, scalars, points):
         if len(scalars) != 32 * nb * n or len(points) != 64 * nb * n:
             raise BpGpuError(E_LEN, "msm_batch: length mismatch")
         o = _out(64 * nb)
-        self._ck(_lib.bpgpu_msm_batch(self.ctx, C.c_size_t(nb), C.c_size_t(n), _buf(scalars), _buf(points), o))
+        self._ck(_lib.bpgpu_msm_batch(self.ctx, nb, n, _buf(scalars), _buf(points), o))
         return bytes(o)[:64 * nb]
 
     # ---- generators
     def gens_create(self, G, H, B, B_blinding, window_bits=8):
         cap = len(G) // 64
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_gens_create(self.ctx, _buf(G), _buf(H), C.c_size_t(cap), _buf(B), _buf(B_blinding),
-                                        window_bits, C.byref(h)))
+        self._ck(_lib.bpgpu_gens_create(self.ctx, _buf(G), _buf(H), cap, _buf(B), _buf(B_blinding), window_bits, C.byref(h)))
         return h
 
     def gens_destroy(self, h):
@@ -336,7 +309,7 @@ class BpGpu:
         """ark=True: the scalars are ark-ff Montgomery limbs (x * 2^256 mod n), converted on the device"""
         o = _out(64 * nb)
         fn = _lib.bpgpu_msm_gens_ark if ark else _lib.bpgpu_msm_gens
-        self._ck(fn(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), _buf(scalars), o))
+        self._ck(fn(self.ctx, gens, nb, n, _buf(scalars), o))
         return bytes(o)[:64 * nb]
 
     # ---- IPP
@@ -344,28 +317,26 @@ class BpGpu:
         if not (len(a) == len(b) == 64 * n and len(G) == len(H) == 128 * n):
             raise BpGpuError(E_LEN, "fold_witness: length mismatch")
         ao, bo, Go, Ho = _out(32 * n), _out(32 * n), _out(64 * n), _out(64 * n)
-        self._ck(_lib.bpgpu_fold_witness(self.ctx, C.c_size_t(n), _buf(u), _buf(u_inv), _buf(a), _buf(b), _buf(G),
-                                         _buf(H), ao, bo, Go, Ho))
+        self._ck(_lib.bpgpu_fold_witness(self.ctx, n, _buf(u), _buf(u_inv), _buf(a), _buf(b), _buf(G), _buf(H), ao, bo, Go, Ho))
         return bytes(ao)[:32 * n], bytes(bo)[:32 * n], bytes(Go)[:64 * n], bytes(Ho)[:64 * n]
 
     def verification_scalars(self, challenges, n):
         k = len(challenges) // 32
         a, b, s = _out(32 * k), _out(32 * k), _out(32 * n)
-        self._ck(_lib.bpgpu_verification_scalars(self.ctx, _buf(challenges), C.c_size_t(k), C.c_size_t(n), a, b, s))
+        self._ck(_lib.bpgpu_verification_scalars(self.ctx, _buf(challenges), k, n, a, b, s))
         return bytes(a)[:32 * k], bytes(b)[:32 * k], bytes(s)[:32 * n]
 
     # lock-step InnerProductProof::create (transcript on the host)
     def ipp_begin(self, nb, n, Q, Gf, Hf, G, H, shared_gens, a, b):
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_ipp_begin(self.ctx, C.c_size_t(nb), C.c_size_t(n), _buf(Q), _buf(Gf), _buf(Hf), _buf(G),
-                                      _buf(H), 1 if shared_gens else 0, _buf(a), _buf(b), C.byref(h)))
+        self._ck(_lib.bpgpu_ipp_begin(self.ctx, nb, n, _buf(Q), _buf(Gf), _buf(Hf), _buf(G), _buf(H), 1 if shared_gens else 0, _buf(a), _buf(b),
+                                      C.byref(h)))
         return h
 
     def ipp_begin_gens(self, gens, nb, n, w, Gf, Hf, a, b):
         """Resident-generator session: G, H = gens[:n], Q = w * B (no generator folding on the device)."""
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_ipp_begin_gens(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), _buf(w), _buf(Gf), _buf(Hf),
-                                           _buf(a), _buf(b), C.byref(h)))
+        self._ck(_lib.bpgpu_ipp_begin_gens(self.ctx, gens, nb, n, _buf(w), _buf(Gf), _buf(Hf), _buf(a), _buf(b), C.byref(h)))
         return h
 
     def ipp_len(self, s):
@@ -408,22 +379,21 @@ class BpGpu:
         """-> accept bits [nb] (and expect_P, nb x 64 B, with want_expect).  L, R, challenges: nb x k entries, proof-major."""
         k = n.bit_length() - 1 if k is None else k
         ok, ex = (C.c_int32 * max(nb, 1))(), _out(64 * nb) if want_expect else None
-        self._ck(_lib.bpgpu_ipp_verify_batch(self.ctx, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(Q), _buf(Gf), _buf(Hf), _buf(G),
-                                             _buf(H), 1 if shared_gens else 0, _buf(P), self._opt(L), self._opt(R), _buf(ab),
-                                             self._opt(challenges), ok, ex))
+        self._ck(_lib.bpgpu_ipp_verify_batch(self.ctx, nb, n, k, _buf(Q), _buf(Gf), _buf(Hf), _buf(G), _buf(H), 1 if shared_gens else 0, _buf(P),
+                                             self._opt(L), self._opt(R), _buf(ab), self._opt(challenges), ok, ex))
         return (list(ok)[:nb], bytes(ex)[:64 * nb]) if want_expect else list(ok)[:nb]
 
     def ipp_verify_batch_dev(self, nb, n, k, d_Q, d_Gf, d_Hf, d_G, d_H, shared_gens, d_P, d_L, d_R, d_ab, d_challenges, d_ok, d_expect=None):
         """device pointers, asynchronous: sync() before reading d_ok; malformed operands raise input_flag()"""
-        self._ck(_lib.bpgpu_ipp_verify_batch_dev(self.ctx, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), d_Q, d_Gf, d_Hf, d_G, d_H,
-                                                 1 if shared_gens else 0, d_P, d_L, d_R, d_ab, d_challenges, d_ok, d_expect))
+        self._ck(_lib.bpgpu_ipp_verify_batch_dev(self.ctx, nb, n, k, d_Q, d_Gf, d_Hf, d_G, d_H, 1 if shared_gens else 0, d_P, d_L, d_R, d_ab,
+                                                 d_challenges, d_ok, d_expect))
 
     def ipp_verify_gens(self, gens, nb, n, w, Gf, Hf, P, L, R, ab, challenges, want_expect=False):
         """over resident generators: G, H = gens[:n], Q = w * B"""
         k = n.bit_length() - 1
         ok, ex = (C.c_int32 * max(nb, 1))(), _out(64 * nb) if want_expect else None
-        self._ck(_lib.bpgpu_ipp_verify_gens(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(w), _buf(Gf), _buf(Hf),
-                                            _buf(P), self._opt(L), self._opt(R), _buf(ab), self._opt(challenges), ok, ex))
+        self._ck(_lib.bpgpu_ipp_verify_gens(self.ctx, gens, nb, n, k, _buf(w), _buf(Gf), _buf(Hf), _buf(P), self._opt(L), self._opt(R), _buf(ab),
+                                            self._opt(challenges), ok, ex))
         return (list(ok)[:nb], bytes(ex)[:64 * nb]) if want_expect else list(ok)[:nb]
 
     def ipp_verify_fs(self, gens, nb, n, Q_or_w, Gf, Hf, G, H, shared_gens, P, L, R, ab, states):
@@ -431,26 +401,25 @@ class BpGpu:
         gens None: Q and G, H as ipp_verify_batch; else resident generators and w"""
         k = n.bit_length() - 1
         ok, so = (C.c_int32 * max(nb, 1))(), _out(32 * nb)
-        self._ck(_lib.bpgpu_ipp_verify_fs(self.ctx, gens, C.c_size_t(nb), C.c_size_t(n), C.c_size_t(k), _buf(Q_or_w), _buf(Gf), _buf(Hf),
-                                          self._opt(G), self._opt(H), 1 if shared_gens else 0, _buf(P), self._opt(L), self._opt(R),
-                                          _buf(ab), _buf(states), ok, so))
+        self._ck(_lib.bpgpu_ipp_verify_fs(self.ctx, gens, nb, n, k, _buf(Q_or_w), _buf(Gf), _buf(Hf), self._opt(G), self._opt(H),
+                                          1 if shared_gens else 0, _buf(P), self._opt(L), self._opt(R), _buf(ab), _buf(states), ok, so))
         return list(ok)[:nb], bytes(so)[:32 * nb]
 
     def generator_mul(self, scalars):
         n = len(scalars) // 32
         o = _out(64 * n)
-        self._ck(_lib.bpgpu_generator_mul(self.ctx, _buf(scalars), C.c_size_t(n), o))
+        self._ck(_lib.bpgpu_generator_mul(self.ctx, _buf(scalars), n, o))
         return bytes(o)[:64 * n]
 
     def prover_polys(self, circuit, nb, n, m, y, y_inv, z, a_L, a_R, a_O, s_L, s_R):
         t, wV, h = _out(32 * 6 * nb), _out(32 * nb * m), C.c_void_p()
-        self._ck(_lib.bpgpu_r1cs_prover_polys(self.ctx, circuit, C.c_size_t(nb), _buf(y), _buf(y_inv), _buf(z), _buf(a_L),
-                                              _buf(a_R), _buf(a_O), _buf(s_L), _buf(s_R), t, wV, C.byref(h)))
+        self._ck(_lib.bpgpu_r1cs_prover_polys(self.ctx, circuit, nb, _buf(y), _buf(y_inv), _buf(z), _buf(a_L), _buf(a_R), _buf(a_O), _buf(s_L),
+                                              _buf(s_R), t, wV, C.byref(h)))
         return bytes(t)[:32 * 6 * nb], bytes(wV)[:32 * nb * m], h
 
     def prover_eval(self, sess, nb, padded_n, x):
         lv, rv = _out(32 * nb * padded_n), _out(32 * nb * padded_n)
-        self._ck(_lib.bpgpu_r1cs_prover_eval(self.ctx, sess, C.c_size_t(padded_n), _buf(x), lv, rv))
+        self._ck(_lib.bpgpu_r1cs_prover_eval(self.ctx, sess, padded_n, _buf(x), lv, rv))
         return bytes(lv)[:32 * nb * padded_n], bytes(rv)[:32 * nb * padded_n]
 
     def prover_destroy(self, sess):
@@ -466,7 +435,7 @@ class BpGpu:
         kd = (C.c_uint32 * max(nnz, 1))(*kind)
         ix = (C.c_uint32 * max(nnz, 1))(*idx)
         fn = _lib.bpgpu_circuit_create_ark if ark else _lib.bpgpu_circuit_create
-        self._ck(fn(self.ctx, C.c_size_t(q), rp, kd, ix, _buf(coeff), C.c_size_t(n_mul), C.c_size_t(m), C.byref(h)))
+        self._ck(fn(self.ctx, q, rp, kd, ix, _buf(coeff), n_mul, m, C.byref(h)))
         return h
 
     def circuit_destroy(self, h):
@@ -476,8 +445,7 @@ class BpGpu:
         nb = len(z) // 32
         wL, wR, wO = _out(32 * nb * n_mul), _out(32 * nb * n_mul), _out(32 * nb * n_mul)
         wV, wc = _out(32 * nb * m), _out(32 * nb)
-        self._ck(_lib.bpgpu_flatten_constraints(self.ctx, circuit, C.c_size_t(nb), _buf(z), wL, wR, wO, wV,
-                                                wc if want_wc else None))
+        self._ck(_lib.bpgpu_flatten_constraints(self.ctx, circuit, nb, _buf(z), wL, wR, wO, wV, wc if want_wc else None))
 
         def cut(b, k):
             return bytes(b)[:32 * nb * k]
@@ -492,14 +460,13 @@ class BpGpu:
                 raise BpGpuError(E_LEN, "r1cs_prover_polys: length mismatch")
         t, wv, h = _out(32 * 6 * nb), _out(32 * nb * max(m, 1)), C.c_void_p()
         fn = _lib.bpgpu_r1cs_prover_polys_ark if ark else _lib.bpgpu_r1cs_prover_polys
-        self._ck(fn(self.ctx, circuit, C.c_size_t(nb), _buf(y), _buf(y_inv), _buf(z), _buf(a_L), _buf(a_R),
-                    _buf(a_O), _buf(s_L), _buf(s_R), t, wv, C.byref(h)))
+        self._ck(fn(self.ctx, circuit, nb, _buf(y), _buf(y_inv), _buf(z), _buf(a_L), _buf(a_R), _buf(a_O), _buf(s_L), _buf(s_R), t, wv, C.byref(h)))
         return bytes(t)[:32 * 6 * nb], bytes(wv)[:32 * nb * m], h
 
     def r1cs_prover_eval(self, prover, nb, padded_n, x):
         """prover.rs:659-672: l_vec, r_vec (nb x padded_n) = l(x), r(x) with the zero / -y^i padding"""
         lv, rv = _out(32 * nb * padded_n), _out(32 * nb * padded_n)
-        self._ck(_lib.bpgpu_r1cs_prover_eval(self.ctx, prover, C.c_size_t(padded_n), _buf(x), lv, rv))
+        self._ck(_lib.bpgpu_r1cs_prover_eval(self.ctx, prover, padded_n, _buf(x), lv, rv))
         return bytes(lv)[:32 * nb * padded_n], bytes(rv)[:32 * nb * padded_n]
 
     def r1cs_prover_commit(self, gens, session, nb, n_new, a_L, a_R, a_O, blindings, s_L=None, s_R=None, vector_keys=None):
@@ -508,15 +475,15 @@ class BpGpu:
         h = session if session is not None else C.c_void_p()
         out = _out(64 * 3 * nb)
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_prover_commit(self.ctx, gens, C.byref(h), C.c_size_t(nb), C.c_size_t(n_new), opt(a_L), opt(a_R),
-                                               opt(a_O), opt(s_L), opt(s_R), opt(vector_keys), _buf(blindings), out))
+        self._ck(_lib.bpgpu_r1cs_prover_commit(self.ctx, gens, C.byref(h), nb, n_new, opt(a_L), opt(a_R), opt(a_O), opt(s_L), opt(s_R),
+                                               opt(vector_keys), _buf(blindings), out))
         return h, bytes(out)[:64 * 3 * nb]
 
     def r1cs_prover_ipp_begin(self, session, gens, padded_n, n1, x, u, y_inv, w):
         """prover.rs:659-708 on the device: l(x), r(x), G / H factors and the resident-generator IPP session (y_inv None: the session's)"""
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_r1cs_prover_ipp_begin(self.ctx, session, gens, C.c_size_t(padded_n), C.c_size_t(n1), _buf(x), _buf(u),
-                                                  _buf(y_inv) if y_inv is not None else None, _buf(w), C.byref(h)))
+        self._ck(_lib.bpgpu_r1cs_prover_ipp_begin(self.ctx, session, gens, padded_n, n1, _buf(x), _buf(u), _buf(y_inv) if y_inv is not None else None,
+                                                  _buf(w), C.byref(h)))
         return h
 
     def r1cs_prover_session_polys(self, session, circuit, nb, m, y, z):
@@ -542,16 +509,16 @@ class BpGpu:
         pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
         wire = _out(nb * plen) if want_wire else None
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_prove_fs(self.ctx, gens, circuit, C.c_size_t(nb), opt(states), opt(a_L), opt(a_R), opt(a_O), opt(s_L),
-                                          opt(s_R), opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so))
+        self._ck(_lib.bpgpu_r1cs_prove_fs(self.ctx, gens, circuit, nb, opt(states), opt(a_L), opt(a_R), opt(a_O), opt(s_L), opt(s_R),
+                                          opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so))
         return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
                 bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
 
     def r1cs_prove_fs_dev(self, gens, circuit, nb, d_states, d_a_L, d_a_R, d_a_O, d_blindings, d_points, d_scalars, d_v_blinding=None,
                           d_s_L=None, d_s_R=None, d_vector_keys=None, d_wire=None, d_ch=None, d_states_out=None):
         """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
-        self._ck(_lib.bpgpu_r1cs_prove_fs_dev(self.ctx, gens, circuit, C.c_size_t(nb), d_states, d_a_L, d_a_R, d_a_O, d_s_L, d_s_R,
-                                              d_vector_keys, d_v_blinding, d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out))
+        self._ck(_lib.bpgpu_r1cs_prove_fs_dev(self.ctx, gens, circuit, nb, d_states, d_a_L, d_a_R, d_a_O, d_s_L, d_s_R, d_vector_keys, d_v_blinding,
+                                              d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out))
 
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
@@ -563,8 +530,8 @@ class BpGpu:
         h = session if session is not None else C.c_void_p()
         out = _out(64 * 9 * nb)
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
-        self._ck(_lib.bpgpu_mpc_prover_commit(self.ctx, gens, C.byref(h), C.c_size_t(nb), C.c_size_t(n_new), opt(a_L), opt(a_R), opt(a_O),
-                                              opt(s_L), opt(s_R), _buf(blindings), out))
+        self._ck(_lib.bpgpu_mpc_prover_commit(self.ctx, gens, C.byref(h), nb, n_new, opt(a_L), opt(a_R), opt(a_O), opt(s_L), opt(s_R),
+                                              _buf(blindings), out))
         return h, bytes(out)[:64 * 9 * nb]
 
     def mpc_prover_polys_mask(self, session, circuit, nb, n, y, z, triples, gadget_challenges=None):
@@ -583,8 +550,7 @@ class BpGpu:
     def mpc_prover_ipp_begin(self, session, gens, padded_n, n1, x, u, w):
         """mpc_prover.rs:901-917 + the SharedInnerProductProof set-up -> IPP session of 3 planes per proof"""
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_mpc_prover_ipp_begin(self.ctx, session, gens, C.c_size_t(padded_n), C.c_size_t(n1), _buf(x), _buf(u), _buf(w),
-                                                 C.byref(h)))
+        self._ck(_lib.bpgpu_mpc_prover_ipp_begin(self.ctx, session, gens, padded_n, n1, _buf(x), _buf(u), _buf(w), C.byref(h)))
         return h
 
     def mpc_ipp_mask(self, s, nb, triples):
@@ -609,8 +575,7 @@ class BpGpu:
         ok = (C.c_int32 * max(nb, 1))()
         mega = _out(64 * nb) if want_mega else None
         full = _out(32 * nb * nterms) if want_scalars else None
-        self._ck(_lib.bpgpu_r1cs_verify_batch(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                              _buf(points), _buf(scalars), _buf(challenges), ok, mega, full))
+        self._ck(_lib.bpgpu_r1cs_verify_batch(self.ctx, gens, circuit, nb, n1, k, _buf(points), _buf(scalars), _buf(challenges), ok, mega, full))
         return (list(ok)[:nb], bytes(mega)[:64 * nb] if want_mega else None,
                 bytes(full)[:32 * nb * nterms] if want_scalars else None)
 
@@ -621,8 +586,7 @@ class BpGpu:
         ok = (C.c_int32 * max(nb, 1))()
         mega = _out(64 * nb) if want_mega else None
         ch = _out(32 * nb * (6 + k))
-        self._ck(_lib.bpgpu_r1cs_verify_batch_fs(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                 _buf(init_states), _buf(points), _buf(scalars), ok, mega, ch))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_fs(self.ctx, gens, circuit, nb, n1, k, _buf(init_states), _buf(points), _buf(scalars), ok, mega, ch))
         return list(ok)[:nb], (bytes(mega)[:64 * nb] if want_mega else None), bytes(ch)[:32 * nb * (6 + k)]
 
     def circuit_create_param(self, q, nchi, row_ptr, kind, idx, coeff, n_mul, m):
@@ -632,8 +596,7 @@ class BpGpu:
         kd = (C.c_uint32 * max(nnz, 1))(*kind)
         ix = (C.c_uint32 * max(nnz, 1))(*idx)
         h = C.c_void_p()
-        self._ck(_lib.bpgpu_circuit_create_param(self.ctx, C.c_size_t(q), C.c_size_t(nchi), rp, kd, ix, _buf(coeff), C.c_size_t(n_mul),
-                                                 C.c_size_t(m), C.byref(h)))
+        self._ck(_lib.bpgpu_circuit_create_param(self.ctx, q, nchi, rp, kd, ix, _buf(coeff), n_mul, m, C.byref(h)))
         return h
 
     def r1cs_verify_batch_param(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, gadget_challenges, want_mega=True,
@@ -643,8 +606,8 @@ class BpGpu:
         ok = (C.c_int32 * max(nb, 1))()
         mega = _out(64 * nb) if want_mega else None
         full = _out(32 * nb * nterms) if want_scalars else None
-        self._ck(_lib.bpgpu_r1cs_verify_batch_param(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k), _buf(points),
-                                                    _buf(scalars), _buf(challenges), _buf(gadget_challenges), ok, mega, full))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_param(self.ctx, gens, circuit, nb, n1, k, _buf(points), _buf(scalars), _buf(challenges),
+                                                    _buf(gadget_challenges), ok, mega, full))
         return (list(ok)[:nb], bytes(mega)[:64 * nb] if want_mega else None, bytes(full)[:32 * nb * nterms] if want_scalars else None)
 
     def r1cs_verify_batch_fs2(self, gens, circuit, nb, n1, k, m, nchi, init_states, gadget_label, points, scalars, want_mega=True):
@@ -653,39 +616,35 @@ class BpGpu:
         mega = _out(64 * nb) if want_mega else None
         ch, chi = _out(32 * nb * (6 + k)), _out(32 * nb * max(nchi, 1))
         lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_verify_batch_fs2(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k), _buf(init_states),
-                                                  _buf(lab), _buf(points), _buf(scalars), ok, mega, ch, chi))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_fs2(self.ctx, gens, circuit, nb, n1, k, _buf(init_states), _buf(lab), _buf(points), _buf(scalars), ok,
+                                                  mega, ch, chi))
         return list(ok)[:nb], (bytes(mega)[:64 * nb] if want_mega else None), bytes(ch)[:32 * nb * (6 + k)], bytes(chi)[:32 * nb * nchi]
 
     def r1cs_verify_batch_fs_dev(self, gens, circuit, nb, n1, k, d_init, d_points, d_scalars, d_ok, d_mega=None, d_ch=None):
-        self._ck(_lib.bpgpu_r1cs_verify_batch_fs_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                     d_init, d_points, d_scalars, d_ok, d_mega, d_ch))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_fs_dev(self.ctx, gens, circuit, nb, n1, k, d_init, d_points, d_scalars, d_ok, d_mega, d_ch))
 
     def r1cs_verify_batch_wire(self, gens, circuit, nb, n1, proof_len, proofs, commitments, init_states):
         """wire-format proofs (R1CSProof::to_bytes) + compressed commitments -> accept bits, all on the device"""
         if len(proofs) != nb * proof_len or len(init_states) != 32 * nb:
             raise BpGpuError(E_LEN, "r1cs_verify_batch_wire: length mismatch")
         ok = (C.c_int32 * max(nb, 1))()
-        self._ck(_lib.bpgpu_r1cs_verify_batch_wire(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(proof_len),
-                                                   _buf(proofs), _buf(commitments), _buf(init_states), ok))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire(self.ctx, gens, circuit, nb, n1, proof_len, _buf(proofs), _buf(commitments), _buf(init_states),
+                                                   ok))
         return list(ok)[:nb]
 
     def r1cs_verify_batch_wire_dev(self, gens, circuit, nb, n1, proof_len, d_proofs, d_commitments, d_init, d_ok):
-        self._ck(_lib.bpgpu_r1cs_verify_batch_wire_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1),
-                                                       C.c_size_t(proof_len), d_proofs, d_commitments, d_init, d_ok))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire_dev(self.ctx, gens, circuit, nb, n1, proof_len, d_proofs, d_commitments, d_init, d_ok))
 
     def r1cs_verify_combined(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, rho):
         nvar = 11 + m + 2 * k
         if len(points) != 64 * nb * nvar or len(scalars) != 160 * nb or len(challenges) != 32 * nb * (6 + k) or len(rho) != 32 * nb:
             raise BpGpuError(E_LEN, "r1cs_verify_combined: length mismatch")
         o = _out(64)
-        self._ck(_lib.bpgpu_r1cs_verify_combined(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                 _buf(points), _buf(scalars), _buf(challenges), _buf(rho), o))
+        self._ck(_lib.bpgpu_r1cs_verify_combined(self.ctx, gens, circuit, nb, n1, k, _buf(points), _buf(scalars), _buf(challenges), _buf(rho), o))
         return bytes(o)
 
     def r1cs_verify_combined_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_out):
-        self._ck(_lib.bpgpu_r1cs_verify_combined_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                     d_points, d_scalars, d_challenges, d_rho, d_out))
+        self._ck(_lib.bpgpu_r1cs_verify_combined_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_out))
 
     # ---- mixed queues: groups of proofs of several circuits in one call.  A group is a dict with keys circuit, nb, n1, k, points,
     # scalars, challenges, rho and, for a parametric circuit, gadget_challenges (the layouts of r1cs_verify_batch); the host forms
@@ -696,20 +655,20 @@ class BpGpu:
         keep, oks = [], []
         for i, gr in enumerate(groups):
             g = arr[i]
-            g.circuit = _ptr(gr["circuit"])
+            g.circuit = gr["circuit"]
             g.nb, g.n1, g.k = gr["nb"], gr["n1"], gr["k"]
             for f in ("points", "scalars", "challenges", "gadget_challenges", "rho"):
                 v = gr.get(f)
                 if v is None:
                     setattr(g, f, None)
                 elif dev:
-                    setattr(g, f, _ptr(v))
+                    setattr(g, f, v)
                 else:
                     b = C.create_string_buffer(bytes(v), max(len(v), 1))
                     keep.append(b)
                     setattr(g, f, C.cast(b, C.c_void_p).value)
             if dev:
-                g.ok = _ptr(gr.get("ok"))
+                g.ok = gr.get("ok")
             else:
                 ok = (C.c_int32 * max(gr["nb"], 1))()
                 oks.append(ok)
@@ -720,66 +679,62 @@ class BpGpu:
         """sum over all groups and proofs of rho_p * mega_check_p (64 bytes; all zero: every proof valid; 0xFF x 64: malformed input)"""
         arr, keep, _ = self._groups(groups, False)
         o = _out(64)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined(self.ctx, gens, arr, C.c_size_t(len(groups)), o))
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined(self.ctx, gens, arr, len(groups), o))
         return bytes(o)[:64]
 
     def r1cs_verify_mixed_combined_dev(self, gens, groups, d_out):
         arr, _, _ = self._groups(groups, True)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined_dev(self.ctx, gens, arr, C.c_size_t(len(groups)), d_out))
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined_dev(self.ctx, gens, arr, len(groups), d_out))
 
     def r1cs_verify_mixed_screened(self, gens, groups):
         """-> ([ok list per group], number of checks that took the per-proof path)"""
         arr, keep, oks = self._groups(groups, False)
         nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened(self.ctx, gens, arr, C.c_size_t(len(groups)), C.byref(nf)))
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened(self.ctx, gens, arr, len(groups), C.byref(nf)))
         return [list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value
 
     def r1cs_verify_mixed_screened_dev(self, gens, groups):
         """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
         arr, _, _ = self._groups(groups, True)
         nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened_dev(self.ctx, gens, arr, C.c_size_t(len(groups)), C.byref(nf)))
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened_dev(self.ctx, gens, arr, len(groups), C.byref(nf)))
         return nf.value
 
     def set_shard(self, rank, world):
         """this context's share of ONE large proof split over the GPUs of a node (include/bpgpu.h bpgpu_set_shard)"""
-        self._ck(_lib.bpgpu_set_shard(self.ctx, C.c_size_t(rank), C.c_size_t(world)))
+        self._ck(_lib.bpgpu_set_shard(self.ctx, rank, world))
 
     def r1cs_verify_shard(self, gens, circuit, n1, k, points, scalars, challenges, rank, world, gadget_challenges=None):
         """rank's partial mega_check point of one proof (64 bytes)"""
         out = _out(64)
-        self._ck(_lib.bpgpu_r1cs_verify_shard(self.ctx, gens, circuit, C.c_size_t(n1), C.c_size_t(k), _buf(points), _buf(scalars),
-                                              _buf(challenges), _buf(gadget_challenges) if gadget_challenges is not None else None,
-                                              C.c_size_t(rank), C.c_size_t(world), out))
+        self._ck(_lib.bpgpu_r1cs_verify_shard(self.ctx, gens, circuit, n1, k, _buf(points), _buf(scalars), _buf(challenges),
+                                              _buf(gadget_challenges) if gadget_challenges is not None else None, rank, world, out))
         return bytes(out)[:64]
 
     def r1cs_verify_stream_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok):
         """any number of proofs in one call: batches over the context's ring of lanes (asynchronous; sync() waits for all)"""
-        self._ck(_lib.bpgpu_r1cs_verify_stream_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                   d_points, d_scalars, d_challenges, d_ok))
+        self._ck(_lib.bpgpu_r1cs_verify_stream_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok))
 
     def r1cs_verify_stream(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, raw=False):
         """the same from host memory (bytes, or c_void_p of page-locked memory for all three operands) -> [ok]
         (raw = True: the nb x int32 verdicts as bytes -- turning 65 536 verdicts into a Python list costs milliseconds)"""
         ok = (C.c_int32 * max(nb, 1))()
         wrap = lambda b: b if isinstance(b, C.c_void_p) else _buf(b)     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_verify_stream(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                               wrap(points), wrap(scalars), wrap(challenges), ok))
+        self._ck(_lib.bpgpu_r1cs_verify_stream(self.ctx, gens, circuit, nb, n1, k, wrap(points), wrap(scalars), wrap(challenges), ok))
         return bytes(ok)[:4 * nb] if raw else ok[:nb]
 
     def r1cs_verify_screened_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_ok):
         """combined check per batch first, per-proof path only for the batches that fail it (device-resident operands and verdicts;
         sync() before reading d_ok) -> number of batches that took the per-proof path"""
         nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_screened_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                     d_points, d_scalars, d_challenges, d_rho, d_ok, C.byref(nf)))
+        self._ck(_lib.bpgpu_r1cs_verify_screened_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_ok, C.byref(nf)))
         return nf.value
 
     def r1cs_verify_screened_fs_dev(self, gens, circuit, nb, n1, k, d_init_states, d_points, d_scalars, d_rho, d_ok):
         """the same with the transcript replayed on the device (whole Verifier::verify; 1-phase circuits) -> fallback batches"""
         nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_screened_fs_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                        d_init_states, d_points, d_scalars, d_rho, d_ok, C.byref(nf)))
+        self._ck(_lib.bpgpu_r1cs_verify_screened_fs_dev(self.ctx, gens, circuit, nb, n1, k, d_init_states, d_points, d_scalars, d_rho, d_ok,
+                                                        C.byref(nf)))
         return nf.value
 
     def r1cs_verify_screened(self, gens, circuit, nb, n1, k, points, scalars, challenges, rho):
@@ -787,12 +742,10 @@ class BpGpu:
         ok = (C.c_int32 * max(nb, 1))()
         nf = C.c_size_t(0)
         wrap = lambda b: b if isinstance(b, C.c_void_p) else _buf(b)     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_verify_screened(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1), C.c_size_t(k),
-                                                 wrap(points), wrap(scalars), wrap(challenges), wrap(rho), ok, C.byref(nf)))
+        self._ck(_lib.bpgpu_r1cs_verify_screened(self.ctx, gens, circuit, nb, n1, k, wrap(points), wrap(scalars), wrap(challenges), wrap(rho), ok,
+                                                 C.byref(nf)))
         return list(ok)[:nb], nf.value
 
     def r1cs_verify_batch_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok, d_mega=None,
                               d_full=None):
-        self._ck(_lib.bpgpu_r1cs_verify_batch_dev(self.ctx, gens, circuit, C.c_size_t(nb), C.c_size_t(n1),
-                                                  C.c_size_t(k), d_points, d_scalars, d_challenges, d_ok, d_mega,
-                                                  d_full))
+        self._ck(_lib.bpgpu_r1cs_verify_batch_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok, d_mega, d_full))
