@@ -875,6 +875,85 @@ Scalar inner_product(const std::vector<Scalar> &a, const std::vector<Scalar> &b)
   return Scalar::from_bytes_le(out);
 }
 
+// partial points of the ranks -> their sums (count points per rank, in place in `mine`)
+// Returns the first non-zero bpgpu_points_sum code AFTER every column has been tried: every rank sees the same gathered bytes, so
+// every rank gets the same code -- a partial that is not a point (the poison encoding a rank's bpgpu_r1cs_verify_shard returns
+// for a malformed operand in its share) fails the whole group together, with no rank left waiting in a collective.
+static int combine_partials_rc(Device &d, RankGroup &g, uint8_t *mine, size_t count) {
+  const size_t w = g.size();
+  std::vector<uint8_t> all(w * count * 64), col(w * 64);
+  g.all_gather(mine, count * 64, all.data());
+  int first = 0;
+  for (size_t j = 0; j < count; j++) {
+    for (size_t r = 0; r < w; r++) memcpy(&col[64 * r], &all[(r * count + j) * 64], 64);
+    const int rc = bpgpu_points_sum(d.ctx(), col.data(), w, mine + 64 * j);
+    if (rc && !first) first = rc;
+  }
+  return first;
+}
+static void combine_partials(Device &d, RankGroup &g, uint8_t *mine, size_t count) {
+  d.check(combine_partials_rc(d, g, mine, count), "bpgpu_points_sum");
+}
+
+namespace {
+size_t log2_exact(size_t pow2) { size_t k = 0; for (size_t t = pow2; t > 1; t >>= 1) k++; return k; }
+// 64-byte rows of a device result -> the named points of a proof / the end of its L_vec or R_vec
+void read_points(const uint8_t *rows, std::initializer_list<StarkPoint *> dst) { for (StarkPoint *q : dst) { memcpy(q->xy.data(), rows, 64); rows += 64; } }
+void append_points(std::vector<StarkPoint> &dst, const uint8_t *rows, size_t count) {
+  for (size_t i = 0; i < count; i++) { dst.emplace_back(); memcpy(dst.back().xy.data(), rows + 64 * i, 64); }
+}
+// Owner of a device handle (an open session, an uploaded circuit): destroyed exactly once, whichever way its scope is left
+template <class H, void (*destroy)(bpgpu_ctx *, H *)> struct Owned {
+  Device &d;
+  H *h = nullptr;
+  explicit Owned(Device &dev, H *x = nullptr) : d(dev), h(x) {}
+  Owned(const Owned &) = delete;
+  ~Owned() { if (h) destroy(d.ctx(), h); }
+};
+typedef Owned<bpgpu_ipp, bpgpu_ipp_destroy> IppSession;
+typedef Owned<bpgpu_prover, bpgpu_prover_destroy> ProverSession;
+typedef Owned<bpgpu_circuit, bpgpu_circuit_destroy> UploadedCircuit;
+
+// The rounds of an open session over its tr.size() proofs (inner_product_proof.rs:78-230): L_vec, R_vec, a, b into `out`, every
+// transcript left where the reference leaves it.  By default the k rounds run back to back on the device, hash chain included
+// (bpgpu_ipp_run_fs), and the host transcripts are advanced to the state it returns.  BPH_HOST_IPP_TRANSCRIPT, or a rank group
+// (ONE proof, whose partial L, R are summed over the ranks before they are hashed), takes the rounds one by one.
+void ipp_rounds(Device &d, IppSession &s, const std::vector<Transcript *> &tr, const std::vector<InnerProductProof *> &out, RankGroup *group) {
+  const size_t nb = tr.size();
+  std::vector<uint8_t> a(nb * 32), b(nb * 32);
+  if (!getenv("BPH_HOST_IPP_TRANSCRIPT") && !group) {
+    const size_t k = log2_exact(bpgpu_ipp_len(s.h));
+    std::vector<uint8_t> st_in(nb * 32), st_out(nb * 32), L(nb * k * 64 + 1), R(nb * k * 64 + 1);
+    for (size_t p = 0; p < nb; p++) memcpy(&st_in[32 * p], tr[p]->state(), 32);
+    d.check(bpgpu_ipp_run_fs(d.ctx(), s.h, st_in.data(), L.data(), R.data(), a.data(), b.data(), st_out.data()), "bpgpu_ipp_run_fs");
+    for (size_t p = 0; p < nb; p++) {
+      tr[p]->set_state(&st_out[32 * p]);
+      append_points(out[p]->L_vec, &L[p * k * 64], k);
+      append_points(out[p]->R_vec, &R[p * k * 64], k);
+    }
+  } else {
+    std::vector<uint8_t> LR(2 * nb * 64), ub(nb * 32), uib;
+    uint8_t *L = LR.data(), *R = L + nb * 64;
+    while (bpgpu_ipp_len(s.h) > 1) {
+      d.check(bpgpu_ipp_round(d.ctx(), s.h, L, R), "bpgpu_ipp_round");
+      if (group) combine_partials(d, *group, LR.data(), 2);       // this rank's partial L, R -> the sums over the ranks (nb == 1)
+      parallel_for(nb, [&](size_t p) {
+        append_points(out[p]->L_vec, L + 64 * p, 1);
+        append_points(out[p]->R_vec, R + 64 * p, 1);
+        tr[p]->append_point("L", out[p]->L_vec.back());                                   // :119-123 / :177-181
+        tr[p]->append_point("R", out[p]->R_vec.back());
+        tr[p]->challenge_scalar("u").to_bytes_le(&ub[32 * p]);
+      }, 64);
+      uib = ub;
+      d.check(bpgpu_batch_inverse(d.ctx(), uib.data(), nb), "bpgpu_batch_inverse");
+      d.check(bpgpu_ipp_fold(d.ctx(), s.h, ub.data(), uib.data()), "bpgpu_ipp_fold");
+    }
+    d.check(bpgpu_ipp_finish(d.ctx(), s.h, a.data(), b.data()), "bpgpu_ipp_finish");
+  }
+  for (size_t p = 0; p < nb; p++) { out[p]->a = Scalar::from_bytes_le(&a[32 * p]); out[p]->b = Scalar::from_bytes_le(&b[32 * p]); }
+}
+}  // namespace
+
 InnerProductProof InnerProductProof::create(Transcript &transcript, const StarkPoint &Q, const std::vector<Scalar> &G_factors,
                                             const std::vector<Scalar> &H_factors, std::vector<StarkPoint> G_vec,
                                             std::vector<StarkPoint> H_vec, std::vector<Scalar> a_vec, std::vector<Scalar> b_vec) {
@@ -885,51 +964,11 @@ InnerProductProof InnerProductProof::create(Transcript &transcript, const StarkP
   transcript.innerproduct_domain_sep(n);                                                  // :72
   Device &d = Device::default_device();
   InnerProductProof proof;
-  bpgpu_ipp *s = nullptr;
+  IppSession s(d);
   auto pG = pack_points(G_vec), pH = pack_points(H_vec);
   auto pa = pack_scalars(a_vec), pb = pack_scalars(b_vec), pgf = pack_scalars(G_factors), phf = pack_scalars(H_factors);
-  d.check(bpgpu_ipp_begin(d.ctx(), 1, n, Q.xy.data(), pgf.data(), phf.data(), pG.data(), pH.data(), 1, pa.data(), pb.data(), &s),
-          "bpgpu_ipp_begin");
-  try {
-    if (!getenv("BPH_HOST_IPP_TRANSCRIPT")) {   // all rounds on the device, hash chain included (bpgpu_ipp_run_fs)
-      size_t k = 0;
-      for (size_t t = n; t > 1; t >>= 1) k++;
-      std::vector<uint8_t> L(k * 64 + 1), R(k * 64 + 1);
-      uint8_t st_out[32], a[32], b[32];
-      d.check(bpgpu_ipp_run_fs(d.ctx(), s, transcript.state(), L.data(), R.data(), a, b, st_out), "bpgpu_ipp_run_fs");
-      transcript.set_state(st_out);
-      for (size_t r = 0; r < k; r++) {
-        StarkPoint Lp, Rp;
-        memcpy(Lp.xy.data(), &L[64 * r], 64);
-        memcpy(Rp.xy.data(), &R[64 * r], 64);
-        proof.L_vec.push_back(Lp);
-        proof.R_vec.push_back(Rp);
-      }
-      proof.a = Scalar::from_bytes_le(a);
-      proof.b = Scalar::from_bytes_le(b);
-      bpgpu_ipp_destroy(d.ctx(), s);
-      return proof;
-    }
-    while (bpgpu_ipp_len(s) > 1) {
-      StarkPoint L, R;
-      d.check(bpgpu_ipp_round(d.ctx(), s, L.xy.data(), R.xy.data()), "bpgpu_ipp_round");
-      proof.L_vec.push_back(L);
-      proof.R_vec.push_back(R);
-      transcript.append_point("L", L);                                                    // :119-123 / :177-181
-      transcript.append_point("R", R);
-      Scalar u = transcript.challenge_scalar("u"), u_inv = u.inverse();
-      auto bu = u.to_bytes(), bi = u_inv.to_bytes();
-      d.check(bpgpu_ipp_fold(d.ctx(), s, bu.data(), bi.data()), "bpgpu_ipp_fold");
-    }
-    uint8_t a[32], b[32];
-    d.check(bpgpu_ipp_finish(d.ctx(), s, a, b), "bpgpu_ipp_finish");
-    proof.a = Scalar::from_bytes_le(a);
-    proof.b = Scalar::from_bytes_le(b);
-  } catch (...) {
-    bpgpu_ipp_destroy(d.ctx(), s);
-    throw;
-  }
-  bpgpu_ipp_destroy(d.ctx(), s);
+  d.check(bpgpu_ipp_begin(d.ctx(), 1, n, Q.xy.data(), pgf.data(), phf.data(), pG.data(), pH.data(), 1, pa.data(), pb.data(), &s.h), "bpgpu_ipp_begin");
+  ipp_rounds(d, s, {&transcript}, {&proof}, nullptr);
   return proof;
 }
 
@@ -1384,9 +1423,6 @@ R1CSProof Prover::prove(const BulletproofGens &bp_gens, Rng &rng) {
   return prove_batch(ps, bp_gens, rs)[0];
 }
 
-// Lock-step Prover::prove (prover.rs:412-727) for nb provers of circuits with identical constraint rows
-// (1-phase gadgets, or 2-phase ones whose randomized rows happen to coincide): every device call is
-// batched over the provers; only the transcripts run per prover on the host.
 R1CSProof Prover::prove(const BulletproofGens &bp_gens, RankGroup &group, Rng *rng, Device *device) {
   std::vector<Prover *> ps{this};
   std::unique_ptr<Rng> own;
@@ -1402,167 +1438,110 @@ R1CSProof Prover::prove(const BulletproofGens &bp_gens, RankGroup &group, Rng *r
   std::vector<Rng *> rs{rng};
   return prove_batch(ps, bp_gens, rs, device, &group)[0];
 }
-// partial points of the ranks -> their sums (count points per rank, in place in `mine`)
-// Returns the first non-zero bpgpu_points_sum code AFTER every column has been tried: every rank sees the same gathered bytes, so
-// every rank gets the same code -- a partial that is not a point (the poison encoding a rank's bpgpu_r1cs_verify_shard returns
-// for a malformed operand in its share) fails the whole group together, with no rank left waiting in a collective.
-static int combine_partials_rc(Device &d, RankGroup &g, uint8_t *mine, size_t count) {
-  const size_t w = g.size();
-  std::vector<uint8_t> all(w * count * 64), col(w * 64);
-  g.all_gather(mine, count * 64, all.data());
-  int first = 0;
-  for (size_t j = 0; j < count; j++) {
-    for (size_t r = 0; r < w; r++) memcpy(&col[64 * r], &all[(r * count + j) * 64], 64);
-    const int rc = bpgpu_points_sum(d.ctx(), col.data(), w, mine + 64 * j);
-    if (rc && !first) first = rc;
-  }
-  return first;
-}
-static void combine_partials(Device &d, RankGroup &g, uint8_t *mine, size_t count) {
-  d.check(combine_partials_rc(d, g, mine, count), "bpgpu_points_sum");
-}
-std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const BulletproofGens &bp_gens,
-                                           std::vector<Rng *> &rngs, Device *device, RankGroup *group) {
-  const size_t nb = provers.size();
-  if (!nb || rngs.size() != nb) throw std::invalid_argument("prove_batch: one Rng per prover");
-  Device &d = same_gpu(device);
-  if (group && group->size() <= 1) group = nullptr;
-  if (group && nb != 1) throw std::invalid_argument("prove_batch: a rank group shards ONE proof");
-  struct ShardGuard {      // the context computes this rank's partial sums for the duration of the call
-    Device &d; bool on;
-    ~ShardGuard() { if (on) bpgpu_set_shard(d.ctx(), 0, 1); }
-  } shard_guard{d, group != nullptr};
-  if (group) d.check(bpgpu_set_shard(d.ctx(), group->rank(), group->size()), "bpgpu_set_shard");
-  std::vector<CsCore *> cs(nb);
-  for (size_t p = 0; p < nb; p++) cs[p] = provers[p]->c_.get();
-  const PedersenGens &pc = cs[0]->pc_gens;
-  bpgpu_gens *gens = bp_gens.device_tables(pc);
-  const size_t n1 = cs[0]->a_L.size(), m = cs[0]->v.size();
-  const bool vkeys = rngs[0]->vector_keys();
-  // BPH_PROVE_FUSED: one-phase circuits take bpgpu_r1cs_prove_fs -- the whole protocol, transcript included, in ONE device call
-  // (below); everything else, and the default, is the staged sequence
-  bool fused = getenv("BPH_PROVE_FUSED") && !group && n1 >= 1 && !cs[0]->param;
-  for (size_t p = 0; p < nb && fused; p++) fused = cs[p]->deferred.empty();
-  std::vector<uint8_t> st_entry(fused ? nb * 32 : 0);
-  for (size_t p = 0; p < nb; p++) {
-    CsCore *c = cs[p];
-    if (c->a_L.size() != n1 || c->v.size() != m) throw std::invalid_argument("prove_batch: circuits differ in shape");
-    if (rngs[p]->vector_keys() != vkeys) throw std::invalid_argument("prove_batch: the provers' Rngs differ in vector_keys()");
-    if (fused) memcpy(&st_entry[32 * p], c->tr.state(), 32);                             // the device appends "m" itself
-    c->tr.append_u64("m", c->v.size());                                                  // prover.rs:420
-  }
-  if (bp_gens.gens_capacity < n1) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :450-452
-  std::vector<R1CSProof> proofs(nb);
+// ---- Prover::prove_batch, stage by stage ---------------------------------------------------------------------------------
+namespace {
+// the context computes this rank's partial sums for the duration of the call
+struct ShardGuard { Device &d; bool on; ~ShardGuard() { if (on) bpgpu_set_shard(d.ctx(), 0, 1); } };
+// a reference to a circuit of the cache (a ParametricCircuit's own device copy is not one: c stays null)
+struct CircuitGuard { bpgpu_circuit *c; ~CircuitGuard() { if (c) circuit_cache().release(c); } };
+
+// Lock-step Prover::prove (prover.rs:412-727) for nb provers of circuits with identical constraint rows (1-phase gadgets, or 2-phase
+// ones whose randomized rows happen to coincide): every device call is batched over the provers; only the transcripts run per
+// prover on the host.  The members are what the stages hand to one another; Prover::prove_batch calls the stages in the
+// reference's order.
+struct ProveBatch {
+  Device &d;
+  const BulletproofGens &bp_gens;
+  const std::vector<CsCore *> cs;
+  const std::vector<Rng *> &rngs;
+  RankGroup *const group;
+  const size_t nb;
+  bpgpu_gens *gens = nullptr;
+  size_t n1 = 0, m = 0, n = 0, padded_n = 0;
+  bool vkeys = false, fused = false;
+  const ParametricCircuit *param = nullptr;
+  bpgpu_circuit *circ = nullptr;
+  std::vector<uint8_t> st_entry, chi_bytes;                      // (fused) the transcript states before "m"; the gadget challenges
+  std::vector<R1CSProof> proofs;
+  std::vector<Scalar> i_b1, o_b1, s_b1, i_b2, o_b2, s_b2;
+  std::vector<Scalar> y, z, u, x, w, t, tb, wV;                  // challenges; per prover t1..t6, their blindings, the m weights wV
   Lap lap;
-  std::vector<Scalar> i_b1(nb), o_b1(nb), s_b1(nb), i_b2(nb), o_b2(nb), s_b2(nb);
-  // prover.rs:435-445: the blinding RNG is bound to the transcript state and to the witness blindings
-  // (build_rng().rekey_with_witness_bytes("v_blinding", ..)); the OS entropy is already in an OsRng's key
-  // (many commitments -- the 2^14-shuffle has 32 768 -- are absorbed as the keccak256 digests of runs of 128 blindings, hashed
-  // on the thread pool: one rekey per blinding was 32 768 dependent permutations, 13 ms)
-  parallel_for(nb, [&](size_t p) {
-    rngs[p]->rekey(cs[p]->tr.state(), 32);
-    const auto &vb = cs[p]->v_blinding;
-    const size_t RUN = 128, runs = (vb.size() + RUN - 1) / RUN;
-    if (runs <= 1) {
-      std::vector<uint8_t> all(vb.size() * 32);
-      for (size_t i = 0; i < vb.size(); i++) vb[i].to_bytes_le(&all[32 * i]);
-      if (!all.empty()) rngs[p]->rekey(all.data(), all.size());
-    } else {
-      std::vector<uint8_t> dig(runs * 32);
-      parallel_for(runs, [&](size_t r) {
-        const size_t lo = r * RUN, hi = std::min(vb.size(), lo + RUN);
-        std::vector<uint8_t> buf((hi - lo) * 32);
-        for (size_t i = lo; i < hi; i++) vb[i].to_bytes_le(&buf[32 * (i - lo)]);
-        keccak256(buf.data(), buf.size(), &dig[32 * r]);
-      });
-      rngs[p]->rekey(dig.data(), dig.size());
-    }
-  }, 16);
-  if (fused) {
-    // Every draw up front, in the reference's order -- i_blinding o_blinding s_blinding, the vector key or s_L, s_R (:457-462), tb1
-    // tb3 tb4 tb5 tb6 (:621-625): with no second phase nothing is drawn in between, so it is the staged route's stream.
-    const size_t padded_n = next_pow2(n1), plane = nb * n1 * 32;
-    if (bp_gens.gens_capacity < padded_n) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :511-513
-    size_t k = 0;
-    for (size_t t = padded_n; t > 1; t >>= 1) k++;
-    for (size_t p = 1; p < nb; p++)
-      if (cs[p]->rows_hash[0] != cs[0]->rows_hash[0] || cs[p]->rows_hash[1] != cs[0]->rows_hash[1] || cs[p]->rows_nnz != cs[0]->rows_nnz ||
-          cs[p]->constraints.size() != cs[0]->constraints.size())
-        throw std::invalid_argument("prove_batch: constraint rows differ between provers");
-    std::vector<uint8_t> in((vkeys ? 3 : 5) * plane + nb * (32 + m * 32 + 8 * 32) + 1);
-    uint8_t *paL = in.data(), *paR = paL + plane, *paO = paR + plane, *psL = paO + plane, *psR = psL + plane;
-    uint8_t *pkey = paO + plane + (vkeys ? 0 : 2 * plane), *pvb = pkey + nb * 32, *pbl = pvb + nb * m * 32;
-    parallel_for(nb, [&](size_t p) {
-      Rng &r = *rngs[p];
-      for (int i = 0; i < 3; i++) r.scalar().to_ark_le(pbl + (p * 8 + i) * 32);
-      if (vkeys) {
-        for (int i = 0; i < 4; i++) { uint64_t w = r.next_u64(); memcpy(pkey + p * 32 + 8 * i, &w, 8); }
-      } else {
-        std::vector<Scalar> v(n1);
-        r.scalars(v.data(), n1);
-        pack_range_ark(psL + p * n1 * 32, v.data(), n1);
-        r.scalars(v.data(), n1);
-        pack_range_ark(psR + p * n1 * 32, v.data(), n1);
-      }
-      for (int i = 3; i < 8; i++) r.scalar().to_ark_le(pbl + (p * 8 + i) * 32);
-      pack_range_ark(paL + p * n1 * 32, cs[p]->a_L.data(), n1);
-      pack_range_ark(paR + p * n1 * 32, cs[p]->a_R.data(), n1);
-      pack_range_ark(paO + p * n1 * 32, cs[p]->a_O.data(), n1);
-      pack_range_ark(pvb + p * m * 32, cs[p]->v_blinding.data(), m);
-      cs[p]->create_randomized_constraints();                                              // :501 (nothing deferred: the 1-phase separator)
-    });
-    lap("prove: pack planes, draws");
-    bpgpu_circuit *circ = circuit_cache().acquire(*cs[0], n1, m);
-    struct CircuitGuard { bpgpu_circuit *c; ~CircuitGuard() { if (c) circuit_cache().release(c); } } circuit_guard{circ};
-    const size_t nvar = 11 + 2 * k;
-    std::vector<uint8_t> pts(nb * nvar * 64), sc(nb * 5 * 32), st_out(nb * 32);
-    int rc = bpgpu_r1cs_prove_fs(d.ctx(), gens, circ, nb, st_entry.data(), paL, paR, paO, vkeys ? nullptr : psL, vkeys ? nullptr : psR,
-                                 vkeys ? pkey : nullptr, m ? pvb : nullptr, pbl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
-    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
-    d.check(rc, "bpgpu_r1cs_prove_fs");
+  ShardGuard shard;                                              // released in reverse: ipp, circuit, session, shard
+  ProverSession ps;
+  CircuitGuard circuit_guard{nullptr};
+  IppSession ipp;
+
+  ProveBatch(Device &dev, const BulletproofGens &bg, std::vector<CsCore *> cores, const std::vector<Rng *> &r, RankGroup *g)
+      : d(dev), bp_gens(bg), cs(std::move(cores)), rngs(r), group(g), nb(cs.size()), proofs(nb), i_b1(nb), o_b1(nb), s_b1(nb), i_b2(nb),
+        o_b2(nb), s_b2(nb), y(nb), z(nb), u(nb), x(nb), w(nb), tb(nb * 6), shard{dev, g != nullptr}, ps(dev), ipp(dev) {}
+
+  // Shard, shapes, "m", the generator capacity and the route; then the Rngs are bound to the proof
+  void check_and_bind() {
+    if (group && nb != 1) throw std::invalid_argument("prove_batch: a rank group shards ONE proof");
+    if (group) d.check(bpgpu_set_shard(d.ctx(), group->rank(), group->size()), "bpgpu_set_shard");
+    gens = bp_gens.device_tables(cs[0]->pc_gens);
+    n1 = cs[0]->a_L.size(); m = cs[0]->v.size();
+    vkeys = rngs[0]->vector_keys();
+    // BPH_PROVE_FUSED: one-phase circuits take bpgpu_r1cs_prove_fs -- the whole protocol, transcript included, in ONE device call
+    // (prove_fused); everything else, and the default, is the staged sequence
+    fused = getenv("BPH_PROVE_FUSED") && !group && n1 >= 1 && !cs[0]->param;
+    for (size_t p = 0; p < nb && fused; p++) fused = cs[p]->deferred.empty();
+    st_entry.resize(fused ? nb * 32 : 0);
     for (size_t p = 0; p < nb; p++) {
-      R1CSProof &pr = proofs[p];
-      const uint8_t *pp = &pts[p * nvar * 64];
-      StarkPoint *dst[11] = {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6};
-      for (int i = 0; i < 11; i++) memcpy(dst[i]->xy.data(), pp + 64 * i, 64);
-      for (size_t r = 0; r < k; r++) {
-        StarkPoint Lp, Rp;
-        memcpy(Lp.xy.data(), pp + 64 * (11 + r), 64);
-        memcpy(Rp.xy.data(), pp + 64 * (11 + k + r), 64);
-        pr.ipp_proof.L_vec.push_back(Lp);
-        pr.ipp_proof.R_vec.push_back(Rp);
-      }
-      const uint8_t *ps5 = &sc[p * 160];
-      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
-      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
-      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up, as after bpgpu_ipp_run_fs
+      CsCore *c = cs[p];
+      if (c->a_L.size() != n1 || c->v.size() != m) throw std::invalid_argument("prove_batch: circuits differ in shape");
+      if (rngs[p]->vector_keys() != vkeys) throw std::invalid_argument("prove_batch: the provers' Rngs differ in vector_keys()");
+      if (fused) memcpy(&st_entry[32 * p], c->tr.state(), 32);                             // the device appends "m" itself
+      c->tr.append_u64("m", c->v.size());                                                  // prover.rs:420
     }
-    lap("prove: fused device call");
-    return proofs;
+    if (bp_gens.gens_capacity < n1) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :450-452
+    lap = Lap();
+    // prover.rs:435-445: the blinding RNG is bound to the transcript state and to the witness blindings
+    // (build_rng().rekey_with_witness_bytes("v_blinding", ..)); the OS entropy is already in an OsRng's key
+    // (many commitments -- the 2^14-shuffle has 32 768 -- are absorbed as the keccak256 digests of runs of 128 blindings, hashed
+    // on the thread pool: one rekey per blinding was 32 768 dependent permutations, 13 ms)
+    parallel_for(nb, [&](size_t p) {
+      rngs[p]->rekey(cs[p]->tr.state(), 32);
+      const auto &vb = cs[p]->v_blinding;
+      const size_t RUN = 128, runs = (vb.size() + RUN - 1) / RUN;
+      if (runs <= 1) {
+        std::vector<uint8_t> all(vb.size() * 32);
+        for (size_t i = 0; i < vb.size(); i++) vb[i].to_bytes_le(&all[32 * i]);
+        if (!all.empty()) rngs[p]->rekey(all.data(), all.size());
+      } else {
+        std::vector<uint8_t> dig(runs * 32);
+        parallel_for(runs, [&](size_t r) {
+          const size_t lo = r * RUN, hi = std::min(vb.size(), lo + RUN);
+          std::vector<uint8_t> buf((hi - lo) * 32);
+          for (size_t i = lo; i < hi; i++) vb[i].to_bytes_le(&buf[32 * (i - lo)]);
+          keccak256(buf.data(), buf.size(), &dig[32 * r]);
+        });
+        rngs[p]->rekey(dig.data(), dig.size());
+      }
+    }, 16);
   }
-  // One phase of commitments, prover.rs:457-494 (lo = 0) / :519-565 (lo = n1): blinding factors, then A_I, A_O, S over
-  // [B_blinding, G_lo.., H_lo..] -- the witness planes go to the device once (bpgpu_r1cs_prover_commit keeps them in the
-  // session for the polynomial build), the blinding vectors s_L, s_R either with them or, Rng::vector_keys(), as one 32-byte
-  // key per prover that the device expands
-  bpgpu_prover *ps = nullptr;
-  struct SessionGuard { Device &d; bpgpu_prover *&ps; ~SessionGuard() { if (ps) bpgpu_prover_destroy(d.ctx(), ps); } } session_guard{d, ps};
-  auto commit_phase = [&](size_t lo, size_t hi, std::vector<Scalar> &ib, std::vector<Scalar> &ob, std::vector<Scalar> &sb, int which_phase) {
+
+  // The operands of one phase of commitments, as draw_and_pack lays them out in the caller's buffer of planes_size() bytes: nb x cnt
+  // witness scalars each, the blinding vectors likewise or nb 32-byte keys in their place, nb x nbl blinding factors
+  struct Planes { const uint8_t *aL, *aR, *aO; uint8_t *sL, *sR, *key, *bl; };
+  size_t planes_size(size_t cnt, size_t nbl) const { return (vkeys ? 3 : 5) * nb * cnt * 32 + nb * nbl * 32 + nb * 32; }
+  // The draws of one phase in the reference's order, prover.rs:457-462 (lo = 0) / :519-527 (lo = n1) -- i_blinding o_blinding
+  // s_blinding (kept in ib, ob, sb), then the vector key or s_L, s_R -- and the witness a_L a_R a_O [lo, hi) packed beside them.  The
+  // one-call route has nothing to wait for between these and the blindings of T_1 T_3 T_4 T_5 T_6 (:621-625): nbl = 8 draws those
+  // five too, into the slots behind the first three.
+  Planes draw_and_pack(size_t lo, size_t hi, uint8_t *base, size_t nbl, std::vector<Scalar> &ib, std::vector<Scalar> &ob, std::vector<Scalar> &sb) {
     const size_t cnt = hi - lo, plane = nb * cnt * 32;
-    static thread_local RawBuf buf;
-    uint8_t *base = buf.ensure((vkeys ? 3 : 5) * plane + nb * 3 * 32 + nb * 32 + 1);
-    const uint8_t *paL = base, *paR = base + plane, *paO = base + 2 * plane;
-    uint8_t *psL = base + 3 * plane, *psR = base + 4 * plane;
-    uint8_t *pbl = base + (vkeys ? 3 : 5) * plane, *pkey = pbl + nb * 3 * 32;
+    Planes pl{base, base + plane, base + 2 * plane, base + 3 * plane, base + 4 * plane, nullptr, base + (vkeys ? 3 : 5) * plane};
+    pl.key = pl.bl + nb * nbl * 32;
     // one prover: its witness vectors already lie in memory as the planes the call takes (a Scalar IS its four Montgomery words)
     static_assert(sizeof(Scalar) == 32, "Scalar must be its 32 in-memory bytes");
     const bool direct = nb == 1 && cnt > 0;
-    if (direct) {
-      paL = (const uint8_t *)(cs[0]->a_L.data() + lo); paR = (const uint8_t *)(cs[0]->a_R.data() + lo); paO = (const uint8_t *)(cs[0]->a_O.data() + lo);
-    }
+    if (direct) { pl.aL = (const uint8_t *)(cs[0]->a_L.data() + lo); pl.aR = (const uint8_t *)(cs[0]->a_R.data() + lo); pl.aO = (const uint8_t *)(cs[0]->a_O.data() + lo); }
     parallel_for(nb, [&](size_t p) {
       Rng &r = *rngs[p];
       ib[p] = r.scalar(); ob[p] = r.scalar(); sb[p] = r.scalar();                         // :457-459 / :519-521
-      ib[p].to_ark_le(pbl + (p * 3) * 32); ob[p].to_ark_le(pbl + (p * 3 + 1) * 32); sb[p].to_ark_le(pbl + (p * 3 + 2) * 32);
+      uint8_t *bl = pl.bl + p * nbl * 32;
+      ib[p].to_ark_le(bl); ob[p].to_ark_le(bl + 32); sb[p].to_ark_le(bl + 64);
       if (!direct) {
         pack_range_ark(base + p * cnt * 32, cs[p]->a_L.data() + lo, cnt);
         pack_range_ark(base + plane + p * cnt * 32, cs[p]->a_R.data() + lo, cnt);
@@ -1570,94 +1549,146 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
       }
       if (!cnt) return;
       if (vkeys) {                                                                        // :461-462 / :526-527, as a key
-        for (int i = 0; i < 4; i++) { uint64_t w = r.next_u64(); memcpy(pkey + p * 32 + 8 * i, &w, 8); }   // little-endian host
+        for (int i = 0; i < 4; i++) { uint64_t w64 = r.next_u64(); memcpy(pl.key + p * 32 + 8 * i, &w64, 8); }   // little-endian host
       } else {                                                 // (inside a running loop, i.e. for nb >= 2, the inner loop runs serially)
         std::vector<Scalar> v(cnt);
         r.scalars(v.data(), cnt);
-        pack_range_ark(psL + p * cnt * 32, v.data(), cnt);
+        pack_range_ark(pl.sL + p * cnt * 32, v.data(), cnt);
         r.scalars(v.data(), cnt);
-        pack_range_ark(psR + p * cnt * 32, v.data(), cnt);
+        pack_range_ark(pl.sR + p * cnt * 32, v.data(), cnt);
       }
+      for (size_t i = 3; i < nbl; i++) r.scalar().to_ark_le(bl + 32 * i);
     });
-    lap("prove:   pack planes");
-    std::vector<uint8_t> o(nb * 3 * 64);
-    int rc = bpgpu_r1cs_prover_commit(d.ctx(), gens, &ps, nb, cnt, paL, paR, paO, vkeys ? nullptr : psL, vkeys ? nullptr : psR,
-                                      vkeys && cnt ? pkey : nullptr, pbl, o.data());
-    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
-    d.check(rc, "bpgpu_r1cs_prover_commit");
-    if (group) combine_partials(d, *group, o.data(), 3);
-    for (size_t p = 0; p < nb; p++) {
-      StarkPoint *dst[3] = {which_phase == 1 ? &proofs[p].A_I1 : &proofs[p].A_I2, which_phase == 1 ? &proofs[p].A_O1 : &proofs[p].A_O2,
-                            which_phase == 1 ? &proofs[p].S1 : &proofs[p].S2};
-      for (int k = 0; k < 3; k++) memcpy(dst[k]->xy.data(), &o[(p * 3 + k) * 64], 64);
-    }
-  };
-  commit_phase(0, n1, i_b1, o_b1, s_b1, 1);
-  lap("prove: phase-1 commit");
-  parallel_for(nb, [&](size_t p) {
-    cs[p]->tr.append_point("A_I1", proofs[p].A_I1);
-    cs[p]->tr.append_point("A_O1", proofs[p].A_O1);
-    cs[p]->tr.append_point("S1", proofs[p].S1);
-    cs[p]->create_randomized_constraints();                                              // :501
-  });
-  lap("prove: randomized constraints");
-  const size_t n = cs[0]->a_L.size(), n2 = n - n1, padded_n = next_pow2(n);
-  for (auto *c : cs) if (c->a_L.size() != n) throw std::invalid_argument("prove_batch: circuits differ after randomization");
-  if (bp_gens.gens_capacity < padded_n) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :511-513
-  if (n2 > 0) commit_phase(n1, n, i_b2, o_b2, s_b2, 2);                                    // else identity, :566-576
-  lap("prove: phase-2 commit");
-  std::vector<Scalar> y(nb), z(nb);
-  parallel_for(nb, [&](size_t p) {
-    cs[p]->tr.append_point("A_I2", proofs[p].A_I2);
-    cs[p]->tr.append_point("A_O2", proofs[p].A_O2);
-    cs[p]->tr.append_point("S2", proofs[p].S2);
-    y[p] = cs[p]->tr.challenge_scalar("y");                                               // :584-585
-    z[p] = cs[p]->tr.challenge_scalar("z");
-  });
-  // device: flattened constraints, l/r coefficient vectors, t_1..t_6 -- :587-619 (y^-1, :593, on the device too).  One
-  // circuit for all provers: the constraint rows must coincide (their running hashes; BPH_CHECK_ROWS=1: row by row).
-  const ParametricCircuit *param = cs[0]->param;
-  for (size_t p = 1; p < nb; p++) if (cs[p]->param != param) throw std::invalid_argument("prove_batch: provers of different circuits");
-  std::vector<uint8_t> chi_bytes;
-  if (param) {
-    // the provers were bound to a ParametricCircuit: its device circuit serves all of them; what must agree is the shape the
-    // gadgets produced (multipliers per phase, commitments, rows, challenges drawn) and the circuit's
-    const size_t nchi = param->challenge_labels().size();
-    for (size_t p = 0; p < nb; p++)
-      if (n != param->n() || n1 != param->n1() || m != param->m() || cs[p]->chi_drawn.size() != nchi || cs[p]->rows_dropped != param->num_constraints())
-        throw std::invalid_argument("prove_batch: the gadgets built on a prover do not match its ParametricCircuit");
-    chi_bytes.resize(nb * nchi * 32);
-    for (size_t p = 0; p < nb; p++) for (size_t j = 0; j < nchi; j++) cs[p]->chi_drawn[j].to_bytes_le(&chi_bytes[(p * nchi + j) * 32]);
-  } else {
+    return pl;
+  }
+
+  // One circuit serves all provers: their constraint rows must coincide (their running hashes)
+  void check_same_rows() const {
     for (size_t p = 1; p < nb; p++)
       if (cs[p]->rows_hash[0] != cs[0]->rows_hash[0] || cs[p]->rows_hash[1] != cs[0]->rows_hash[1] || cs[p]->rows_nnz != cs[0]->rows_nnz ||
           cs[p]->constraints.size() != cs[0]->constraints.size())
         throw std::invalid_argument("prove_batch: constraint rows differ between provers");
-    if (getenv("BPH_CHECK_ROWS"))
-      parallel_for(nb, [&](size_t p) {
-        if (p && !cs[p]->same_rows(*cs[0])) throw std::invalid_argument("prove_batch: constraint rows differ between provers");
-      });
   }
-  lap("prove: transcript y z, rows");
-  bpgpu_circuit *circ = param ? param->device_circuit() : circuit_cache().acquire(*cs[0], n, m);
-  struct CircuitGuard { bpgpu_circuit *c; ~CircuitGuard() { if (c) circuit_cache().release(c); } } circuit_guard{param ? nullptr : circ};
-  lap("prove: circuit");
-  if (!ps) {   // a circuit without multipliers in either phase cannot happen after the phase-1 call; kept for clarity
-    throw std::logic_error("prove_batch: no prover session");
+
+  // BPH_PROVE_FUSED: every draw up front -- with no second phase nothing is drawn between the vectors and the T blindings, so it is
+  // the staged route's stream --, then bpgpu_r1cs_prove_fs
+  void prove_fused() {
+    padded_n = next_pow2(n1);
+    if (bp_gens.gens_capacity < padded_n) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :511-513
+    const size_t k = log2_exact(padded_n);
+    check_same_rows();
+    std::vector<uint8_t> in(planes_size(n1, 8) + nb * m * 32 + 1);
+    uint8_t *pvb = in.data() + planes_size(n1, 8);
+    const Planes pl = draw_and_pack(0, n1, in.data(), 8, i_b1, o_b1, s_b1);
+    parallel_for(nb, [&](size_t p) {
+      pack_range_ark(pvb + p * m * 32, cs[p]->v_blinding.data(), m);
+      cs[p]->create_randomized_constraints();                                              // :501 (nothing deferred: the 1-phase separator)
+    });
+    lap("prove: pack planes, draws");
+    circ = circuit_guard.c = circuit_cache().acquire(*cs[0], n1, m);
+    const size_t nvar = 11 + 2 * k;
+    std::vector<uint8_t> pts(nb * nvar * 64), sc(nb * 5 * 32), st_out(nb * 32);
+    int rc = bpgpu_r1cs_prove_fs(d.ctx(), gens, circ, nb, st_entry.data(), pl.aL, pl.aR, pl.aO, vkeys ? nullptr : pl.sL, vkeys ? nullptr : pl.sR,
+                                 vkeys ? pl.key : nullptr, m ? pvb : nullptr, pl.bl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
+    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
+    d.check(rc, "bpgpu_r1cs_prove_fs");
+    for (size_t p = 0; p < nb; p++) {
+      R1CSProof &pr = proofs[p];
+      const uint8_t *pp = &pts[p * nvar * 64], *ps5 = &sc[p * 160];
+      read_points(pp, {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6});
+      append_points(pr.ipp_proof.L_vec, pp + 64 * 11, k);
+      append_points(pr.ipp_proof.R_vec, pp + 64 * (11 + k), k);
+      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
+      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
+      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up, as after bpgpu_ipp_run_fs
+    }
+    lap("prove: fused device call");
   }
-  std::vector<uint8_t> tco(nb * 6 * 32), wVb(nb * m * 32 + 1);
-  {
+
+  // One phase of commitments, prover.rs:457-494 (lo = 0) / :519-565 (lo = n1): blinding factors, then A_I, A_O, S over
+  // [B_blinding, G_lo.., H_lo..] -- the witness planes go to the device once (bpgpu_r1cs_prover_commit keeps them in the
+  // session for the polynomial build), the blinding vectors s_L, s_R either with them or, Rng::vector_keys(), as one 32-byte
+  // key per prover that the device expands
+  void commit_phase(size_t lo, size_t hi, int which_phase) {
+    const size_t cnt = hi - lo;
+    const bool one = which_phase == 1;
+    static thread_local RawBuf buf;
+    const Planes pl = draw_and_pack(lo, hi, buf.ensure(planes_size(cnt, 3) + 1), 3, one ? i_b1 : i_b2, one ? o_b1 : o_b2, one ? s_b1 : s_b2);
+    lap("prove:   pack planes");
+    std::vector<uint8_t> o(nb * 3 * 64);
+    int rc = bpgpu_r1cs_prover_commit(d.ctx(), gens, &ps.h, nb, cnt, pl.aL, pl.aR, pl.aO, vkeys ? nullptr : pl.sL, vkeys ? nullptr : pl.sR,
+                                      vkeys && cnt ? pl.key : nullptr, pl.bl, o.data());
+    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
+    d.check(rc, "bpgpu_r1cs_prover_commit");
+    if (group) combine_partials(d, *group, o.data(), 3);
+    for (size_t p = 0; p < nb; p++) {
+      R1CSProof &pr = proofs[p];
+      if (one) read_points(&o[p * 192], {&pr.A_I1, &pr.A_O1, &pr.S1}); else read_points(&o[p * 192], {&pr.A_I2, &pr.A_O2, &pr.S2});
+    }
+  }
+
+  // Between the phases: A_I1 A_O1 S1 into the transcripts, the gadgets' second phase (:496-513)
+  void randomize_constraints() {
+    parallel_for(nb, [&](size_t p) {
+      cs[p]->tr.append_point("A_I1", proofs[p].A_I1);
+      cs[p]->tr.append_point("A_O1", proofs[p].A_O1);
+      cs[p]->tr.append_point("S1", proofs[p].S1);
+      cs[p]->create_randomized_constraints();                                              // :501
+    });
+    lap("prove: randomized constraints");
+    n = cs[0]->a_L.size(); padded_n = next_pow2(n);
+    for (auto *c : cs) if (c->a_L.size() != n) throw std::invalid_argument("prove_batch: circuits differ after randomization");
+    if (bp_gens.gens_capacity < padded_n) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :511-513
+  }
+
+  // A_I2 A_O2 S2 -> y, z (:578-585); then the circuit that serves all provers, whose rows or parametric shape must be theirs
+  void challenges_y_z_and_circuit() {
+    parallel_for(nb, [&](size_t p) {
+      cs[p]->tr.append_point("A_I2", proofs[p].A_I2);
+      cs[p]->tr.append_point("A_O2", proofs[p].A_O2);
+      cs[p]->tr.append_point("S2", proofs[p].S2);
+      y[p] = cs[p]->tr.challenge_scalar("y");                                               // :584-585
+      z[p] = cs[p]->tr.challenge_scalar("z");
+    });
+    param = cs[0]->param;
+    for (size_t p = 1; p < nb; p++) if (cs[p]->param != param) throw std::invalid_argument("prove_batch: provers of different circuits");
+    if (param) {
+      // the provers were bound to a ParametricCircuit: its device circuit serves all of them; what must agree is the shape the
+      // gadgets produced (multipliers per phase, commitments, rows, challenges drawn) and the circuit's
+      const size_t nchi = param->challenge_labels().size();
+      for (size_t p = 0; p < nb; p++)
+        if (n != param->n() || n1 != param->n1() || m != param->m() || cs[p]->chi_drawn.size() != nchi || cs[p]->rows_dropped != param->num_constraints())
+          throw std::invalid_argument("prove_batch: the gadgets built on a prover do not match its ParametricCircuit");
+      chi_bytes.resize(nb * nchi * 32);
+      for (size_t p = 0; p < nb; p++) for (size_t j = 0; j < nchi; j++) cs[p]->chi_drawn[j].to_bytes_le(&chi_bytes[(p * nchi + j) * 32]);
+    } else {
+      check_same_rows();
+      if (getenv("BPH_CHECK_ROWS"))   // row by row
+        parallel_for(nb, [&](size_t p) {
+          if (p && !cs[p]->same_rows(*cs[0])) throw std::invalid_argument("prove_batch: constraint rows differ between provers");
+        });
+    }
+    lap("prove: transcript y z, rows");
+    circ = param ? param->device_circuit() : (circuit_guard.c = circuit_cache().acquire(*cs[0], n, m));
+    lap("prove: circuit");
+  }
+
+  // device: flattened constraints, l/r coefficient vectors, t_1..t_6 -- :587-619 (y^-1, :593, on the device too)
+  void polynomials() {
+    if (!ps.h) throw std::logic_error("prove_batch: no prover session");   // (cannot happen after the phase-1 call; kept for clarity)
+    std::vector<uint8_t> tco(nb * 6 * 32), wVb(nb * m * 32 + 1);
     auto by = pack_scalars(y), bz = pack_scalars(z);
-    if (param) d.check(bpgpu_r1cs_prover_session_polys_param(d.ctx(), ps, circ, by.data(), bz.data(), chi_bytes.data(), tco.data(), wVb.data()),
+    if (param) d.check(bpgpu_r1cs_prover_session_polys_param(d.ctx(), ps.h, circ, by.data(), bz.data(), chi_bytes.data(), tco.data(), wVb.data()),
                        "bpgpu_r1cs_prover_session_polys_param");
-    else d.check(bpgpu_r1cs_prover_session_polys(d.ctx(), ps, circ, by.data(), bz.data(), tco.data(), wVb.data()),
+    else d.check(bpgpu_r1cs_prover_session_polys(d.ctx(), ps.h, circ, by.data(), bz.data(), tco.data(), wVb.data()),
                  "bpgpu_r1cs_prover_session_polys");
+    lap("prove: prover_polys");
+    t = unpack_scalars(tco.data(), nb * 6);   // per prover: t1 t2 t3 t4 t5 t6
+    wV = unpack_scalars(wVb.data(), nb * m);
   }
-  lap("prove: prover_polys");
-  auto t = unpack_scalars(tco.data(), nb * 6);   // per prover: t1 t2 t3 t4 t5 t6
-  auto wV = unpack_scalars(wVb.data(), nb * m);
-  std::vector<Scalar> tb(nb * 6);                                                         // :621-625 (tb2 filled below)
-  {   // T_1, T_3, T_4, T_5, T_6 = commit(t_i, tb_i): 5 nb two-term MSMs over (B, B_blinding) -- :627-631
+
+  // T_1, T_3, T_4, T_5, T_6 = commit(t_i, tb_i): 5 nb two-term MSMs over (B, B_blinding) -- :621-631 (tb2: the next stage)
+  void commit_T() {
     std::vector<Scalar> vec(nb * 5 * 2);
     const int idx[5] = {0, 2, 3, 4, 5};
     parallel_for(nb, [&](size_t p) {
@@ -1670,62 +1701,60 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
     auto bytes = pack_scalars(vec);
     std::vector<uint8_t> o(nb * 5 * 64);
     d.check(bpgpu_msm_gens(d.ctx(), gens, nb * 5, 0, bytes.data(), o.data()), "bpgpu_msm_gens");
-    for (size_t p = 0; p < nb; p++) {
-      StarkPoint *dst[5] = {&proofs[p].T_1, &proofs[p].T_3, &proofs[p].T_4, &proofs[p].T_5, &proofs[p].T_6};
-      for (int k = 0; k < 5; k++) memcpy(dst[k]->xy.data(), &o[(p * 5 + k) * 64], 64);
-    }
+    for (size_t p = 0; p < nb; p++) read_points(&o[p * 5 * 64], {&proofs[p].T_1, &proofs[p].T_3, &proofs[p].T_4, &proofs[p].T_5, &proofs[p].T_6});
   }
-  std::vector<Scalar> u(nb), x(nb), w(nb);
-  parallel_for(nb, [&](size_t p) {
-    Transcript &tr = cs[p]->tr;
-    tr.append_point("T_1", proofs[p].T_1);
-    tr.append_point("T_3", proofs[p].T_3);
-    tr.append_point("T_4", proofs[p].T_4);
-    tr.append_point("T_5", proofs[p].T_5);
-    tr.append_point("T_6", proofs[p].T_6);
-    u[p] = tr.challenge_scalar("u");                                                      // :639-640
-    x[p] = tr.challenge_scalar("x");
-    Scalar tb2;
-    if (m >= 4096) {                                                                      // :644-648 (32 768 terms for the 2^14-shuffle)
-      std::vector<Scalar> part(64);
-      parallel_for(64, [&](size_t c) {
-        Scalar acc;
-        for (size_t i = m * c / 64; i < m * (c + 1) / 64; i++) acc += wV[p * m + i] * cs[p]->v_blinding[i];
-        part[c] = acc;
-      });
-      for (auto &x : part) tb2 += x;
-    } else {
-      for (size_t i = 0; i < m; i++) tb2 += wV[p * m + i] * cs[p]->v_blinding[i];
-    }
-    tb[p * 6 + 1] = tb2;
-    auto poly6 = [&](const Scalar *c6) {                                                  // util.rs:192-194
-      return x[p] * (c6[0] + x[p] * (c6[1] + x[p] * (c6[2] + x[p] * (c6[3] + x[p] * (c6[4] + x[p] * c6[5])))));
-    };
-    proofs[p].t_x = poly6(&t[p * 6]);                                                     // :659-660
-    proofs[p].t_x_blinding = poly6(&tb[p * 6]);
-    Scalar i_b = i_b1[p] + u[p] * i_b2[p], o_b = o_b1[p] + u[p] * o_b2[p], s_b = s_b1[p] + u[p] * s_b2[p];   // :674-676
-    proofs[p].e_blinding = x[p] * (i_b + x[p] * (o_b + x[p] * s_b));                      // :678
-    tr.append_scalar("t_x", proofs[p].t_x);
-    tr.append_scalar("t_x_blinding", proofs[p].t_x_blinding);
-    tr.append_scalar("e_blinding", proofs[p].e_blinding);
-    w[p] = tr.challenge_scalar("w");                                                      // :686
-  }, 8);
-  lap("prove: T commits, x, blindings");
-  bpgpu_ipp *ipp = nullptr;
-  for (size_t p = 0; p < nb; p++) cs[p]->tr.innerproduct_domain_sep(padded_n);              // inner_product_proof.rs:72
-  if (!getenv("BPH_IPP_FOLD_GENERATORS")) {
-    // l(x), r(x), the G/H factors (:661-672, 689-697) and the IPP operands never leave the device; Q_p = w_p * B
-    // (:687) and G, H = bp_gens are resident: the session runs over the generator tables
+
+  // T_i -> u, x (:633-640); t(x) and the blindings at x (:642-678); t_x t_x_blinding e_blinding -> w (:680-686)
+  void challenges_u_x_w() {
+    parallel_for(nb, [&](size_t p) {
+      Transcript &tr = cs[p]->tr;
+      tr.append_point("T_1", proofs[p].T_1);
+      tr.append_point("T_3", proofs[p].T_3);
+      tr.append_point("T_4", proofs[p].T_4);
+      tr.append_point("T_5", proofs[p].T_5);
+      tr.append_point("T_6", proofs[p].T_6);
+      u[p] = tr.challenge_scalar("u");                                                      // :639-640
+      x[p] = tr.challenge_scalar("x");
+      Scalar tb2;
+      if (m >= 4096) {                                                                      // :644-648 (32 768 terms for the 2^14-shuffle)
+        std::vector<Scalar> part(64);
+        parallel_for(64, [&](size_t c) {
+          Scalar acc;
+          for (size_t i = m * c / 64; i < m * (c + 1) / 64; i++) acc += wV[p * m + i] * cs[p]->v_blinding[i];
+          part[c] = acc;
+        });
+        for (auto &s : part) tb2 += s;
+      } else {
+        for (size_t i = 0; i < m; i++) tb2 += wV[p * m + i] * cs[p]->v_blinding[i];
+      }
+      tb[p * 6 + 1] = tb2;
+      auto poly6 = [&](const Scalar *c6) {                                                  // util.rs:192-194
+        return x[p] * (c6[0] + x[p] * (c6[1] + x[p] * (c6[2] + x[p] * (c6[3] + x[p] * (c6[4] + x[p] * c6[5])))));
+      };
+      proofs[p].t_x = poly6(&t[p * 6]);                                                     // :659-660
+      proofs[p].t_x_blinding = poly6(&tb[p * 6]);
+      Scalar i_b = i_b1[p] + u[p] * i_b2[p], o_b = o_b1[p] + u[p] * o_b2[p], s_b = s_b1[p] + u[p] * s_b2[p];   // :674-676
+      proofs[p].e_blinding = x[p] * (i_b + x[p] * (o_b + x[p] * s_b));                      // :678
+      tr.append_scalar("t_x", proofs[p].t_x);
+      tr.append_scalar("t_x_blinding", proofs[p].t_x_blinding);
+      tr.append_scalar("e_blinding", proofs[p].e_blinding);
+      w[p] = tr.challenge_scalar("w");                                                      // :686
+    }, 8);
+    lap("prove: T commits, x, blindings");
+  }
+
+  // The inner-product session, default form: l(x), r(x), the G/H factors (:661-672, 689-697) and the IPP operands never leave the
+  // device; Q_p = w_p * B (:687) and G, H = bp_gens are resident: the session runs over the generator tables
+  void ipp_begin_resident() {
     auto bx = pack_scalars(x), bu = pack_scalars(u), bw = pack_scalars(w);
-    int rc = bpgpu_r1cs_prover_ipp_begin(d.ctx(), ps, gens, padded_n, n1, bx.data(), bu.data(), nullptr /* the session's y^-1 */, bw.data(), &ipp);
+    int rc = bpgpu_r1cs_prover_ipp_begin(d.ctx(), ps.h, gens, padded_n, n1, bx.data(), bu.data(), nullptr /* the session's y^-1 */, bw.data(), &ipp.h);
     d.check(rc, "bpgpu_r1cs_prover_ipp_begin");
-  } else {   // the reference's literal schedule (operands through the host, generators folded every round), for A/B runs
+  }
+  // BPH_IPP_FOLD_GENERATORS: the reference's literal schedule (operands through the host, generators folded every round), for A/B runs
+  void ipp_begin_fold_generators() {
     std::vector<uint8_t> lv(nb * padded_n * 32), rv(nb * padded_n * 32);
-    {
-      auto bx = pack_scalars(x);
-      int rc = bpgpu_r1cs_prover_eval(d.ctx(), ps, padded_n, bx.data(), lv.data(), rv.data());   // :661-672
-      d.check(rc, "bpgpu_r1cs_prover_eval");
-    }
+    auto bx = pack_scalars(x);
+    d.check(bpgpu_r1cs_prover_eval(d.ctx(), ps.h, padded_n, bx.data(), lv.data(), rv.data()), "bpgpu_r1cs_prover_eval");   // :661-672
     std::vector<Scalar> Gf(nb * padded_n), Hf(nb * padded_n);
     parallel_for(nb, [&](size_t p) {
       auto exp_y_inv = util::exp_iter(y[p].inverse(), padded_n);
@@ -1741,69 +1770,46 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
     auto bytes = pack_scalars(vec);
     d.check(bpgpu_msm_gens(d.ctx(), gens, nb, 0, bytes.data(), Qb.data()), "bpgpu_msm_gens");
     auto pG = pack_points(bp_gens.share(0).G(padded_n)), pH = pack_points(bp_gens.share(0).H(padded_n));
-    d.check(bpgpu_ipp_begin(d.ctx(), nb, padded_n, Qb.data(), pgf.data(), phf.data(), pG.data(), pH.data(), 1, lv.data(), rv.data(), &ipp),
+    d.check(bpgpu_ipp_begin(d.ctx(), nb, padded_n, Qb.data(), pgf.data(), phf.data(), pG.data(), pH.data(), 1, lv.data(), rv.data(), &ipp.h),
             "bpgpu_ipp_begin");
   }
-  lap("prove: ipp_begin");
-  try {
-    if (!getenv("BPH_HOST_IPP_TRANSCRIPT") && !group) {
-      // the k rounds back to back on the device, hash chain included (bpgpu_ipp_run_fs); the host transcripts are
-      // advanced to the same state afterwards
-      size_t k = 0;
-      for (size_t t = padded_n; t > 1; t >>= 1) k++;
-      std::vector<uint8_t> st_in(nb * 32), st_out(nb * 32), L(nb * k * 64 + 1), R(nb * k * 64 + 1), a(nb * 32), b(nb * 32);
-      for (size_t p = 0; p < nb; p++) memcpy(&st_in[32 * p], cs[p]->tr.state(), 32);
-      d.check(bpgpu_ipp_run_fs(d.ctx(), ipp, st_in.data(), L.data(), R.data(), a.data(), b.data(), st_out.data()), "bpgpu_ipp_run_fs");
-      for (size_t p = 0; p < nb; p++) {
-        cs[p]->tr.set_state(&st_out[32 * p]);
-        for (size_t r = 0; r < k; r++) {
-          StarkPoint Lp, Rp;
-          memcpy(Lp.xy.data(), &L[(p * k + r) * 64], 64);
-          memcpy(Rp.xy.data(), &R[(p * k + r) * 64], 64);
-          proofs[p].ipp_proof.L_vec.push_back(Lp);
-          proofs[p].ipp_proof.R_vec.push_back(Rp);
-        }
-        proofs[p].ipp_proof.a = Scalar::from_bytes_le(&a[32 * p]);
-        proofs[p].ipp_proof.b = Scalar::from_bytes_le(&b[32 * p]);
-      }
-    } else {
-    std::vector<uint8_t> L(nb * 64), R(nb * 64), ub(nb * 32), uib(nb * 32);
-    while (bpgpu_ipp_len(ipp) > 1) {
-      d.check(bpgpu_ipp_round(d.ctx(), ipp, L.data(), R.data()), "bpgpu_ipp_round");
-      if (group) {       // this rank's partial L, R -> the sums over the ranks (nb == 1)
-        uint8_t lr[128];
-        memcpy(lr, L.data(), 64); memcpy(lr + 64, R.data(), 64);
-        combine_partials(d, *group, lr, 2);
-        memcpy(L.data(), lr, 64); memcpy(R.data(), lr + 64, 64);
-      }
-      parallel_for(nb, [&](size_t p) {
-        StarkPoint Lp, Rp;
-        memcpy(Lp.xy.data(), &L[64 * p], 64);
-        memcpy(Rp.xy.data(), &R[64 * p], 64);
-        proofs[p].ipp_proof.L_vec.push_back(Lp);
-        proofs[p].ipp_proof.R_vec.push_back(Rp);
-        cs[p]->tr.append_point("L", Lp);                                                  // :119-123 / :177-181
-        cs[p]->tr.append_point("R", Rp);
-        cs[p]->tr.challenge_scalar("u").to_bytes_le(&ub[32 * p]);
-      }, 64);
-      uib = ub;
-      d.check(bpgpu_batch_inverse(d.ctx(), uib.data(), nb), "bpgpu_batch_inverse");
-      d.check(bpgpu_ipp_fold(d.ctx(), ipp, ub.data(), uib.data()), "bpgpu_ipp_fold");
-    }
-    std::vector<uint8_t> a(nb * 32), b(nb * 32);
-    d.check(bpgpu_ipp_finish(d.ctx(), ipp, a.data(), b.data()), "bpgpu_ipp_finish");
+
+  // :699-712: the inner-product argument over l(x), r(x)
+  void inner_product() {
+    std::vector<Transcript *> tr(nb);
+    std::vector<InnerProductProof *> out(nb);
     for (size_t p = 0; p < nb; p++) {
-      proofs[p].ipp_proof.a = Scalar::from_bytes_le(&a[32 * p]);
-      proofs[p].ipp_proof.b = Scalar::from_bytes_le(&b[32 * p]);
+      tr[p] = &cs[p]->tr; out[p] = &proofs[p].ipp_proof;
+      tr[p]->innerproduct_domain_sep(padded_n);                                             // inner_product_proof.rs:72
     }
-    }
-  } catch (...) {
-    bpgpu_ipp_destroy(d.ctx(), ipp);
-    throw;
+    if (getenv("BPH_IPP_FOLD_GENERATORS")) ipp_begin_fold_generators(); else ipp_begin_resident();
+    lap("prove: ipp_begin");
+    ipp_rounds(d, ipp, tr, out, group);
+    lap("prove: ipp rounds");
   }
-  bpgpu_ipp_destroy(d.ctx(), ipp);
-  lap("prove: ipp rounds");
-  return proofs;
+};
+}  // namespace
+
+std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const BulletproofGens &bp_gens,
+                                           std::vector<Rng *> &rngs, Device *device, RankGroup *group) {
+  const size_t nb = provers.size();
+  if (!nb || rngs.size() != nb) throw std::invalid_argument("prove_batch: one Rng per prover");
+  std::vector<CsCore *> cs(nb);
+  for (size_t p = 0; p < nb; p++) cs[p] = provers[p]->c_.get();
+  ProveBatch b(same_gpu(device), bp_gens, std::move(cs), rngs, group && group->size() > 1 ? group : nullptr);
+  b.check_and_bind();                                                                     // prover.rs:420-452
+  if (b.fused) { b.prove_fused(); return std::move(b.proofs); }
+  b.commit_phase(0, b.n1, 1);                                                             // :457-494
+  b.lap("prove: phase-1 commit");
+  b.randomize_constraints();                                                              // :496-513
+  if (b.n > b.n1) b.commit_phase(b.n1, b.n, 2);                                           // :519-565; else identity, :566-576
+  b.lap("prove: phase-2 commit");
+  b.challenges_y_z_and_circuit();                                                         // :578-585
+  b.polynomials();                                                                        // :587-619
+  b.commit_T();                                                                           // :621-631
+  b.challenges_u_x_w();                                                                   // :633-686
+  b.inner_product();                                                                      // :687-712
+  return std::move(b.proofs);
 }
 
 // ---- Verifier --------------------------------------------------------------------------------------
@@ -1914,46 +1920,50 @@ Verifier::BatchInputs Verifier::replay(const R1CSProof &proof, const Bulletproof
   return in;
 }
 
-void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens, RankGroup &group, Device *device) {
-  if (group.size() <= 1) { verify(proof, bp_gens); return; }
-  CsCore &c = *c_;
-  BatchInputs in = transcript_replay(proof, bp_gens);          // (every rank replays the transcript: sequential hashing, no shares)
-  Device &d = same_gpu(device);
-  bpgpu_gens *gens = bp_gens.device_tables(c.pc_gens);
-  bpgpu_circuit *circ = c.upload_circuit(in.n, in.m);
-  uint8_t part[64];
-  int rc = bpgpu_r1cs_verify_shard(d.ctx(), gens, circ, in.n1, in.k, in.points.data(), in.scalars.data(), in.challenges.data(), nullptr,
-                                   group.rank(), group.size(), part);
-  bpgpu_circuit_destroy(d.ctx(), circ);
-  // E_GENS / E_LEN depend on the shapes only, which every rank holds alike: all ranks throw here together.  A malformed point or
-  // scalar is seen by the rank whose share holds it: that rank's partial is the poison encoding, and the sum fails on ALL ranks.
-  if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
-  d.check(rc, "bpgpu_r1cs_verify_shard");
-  const int rc2 = combine_partials_rc(d, group, part, 1);
-  if (rc2 == BPGPU_E_ARG) throw R1CSException(R1CSError::FormatError);
-  d.check(rc2, "bpgpu_points_sum");
-  memcpy(c.mega.xy.data(), part, 64);
-  if (!c.mega.is_identity()) throw R1CSException(R1CSError::VerificationError);      // :549-551
-}
-void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens) {
+// Verifier::verify (verifier.rs:393-554) in its four forms: against the rows this verifier's gadgets built (uploaded for the call)
+// or a ParametricCircuit `pc`; in one device call, or with the mega_check's terms split over the ranks of `group`, each computing
+// a partial point (every rank replays the transcript: sequential hashing, no shares).
+void Verifier::verify_core(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit *pc, RankGroup *group, Device *device) {
+  if (group && group->size() <= 1) group = nullptr;
   CsCore &c = *c_;
   Lap lap;
-  BatchInputs in = transcript_replay(proof, bp_gens);
-  lap("verify: transcript replay");
+  const std::string tag = pc ? "verify (parametric): " : "verify: ";
+  std::vector<uint8_t> chi;
+  BatchInputs in = replay(proof, bp_gens, pc, pc ? &chi : nullptr);
+  lap((tag + "transcript replay").c_str());
   // device: flatten, inversions, scalar assembly, mega_check MSM, identity test -- :457-553
-  Device &d = Device::default_device();
+  Device &d = group ? same_gpu(device) : Device::default_device();
   bpgpu_gens *gens = bp_gens.device_tables(c.pc_gens);
-  bpgpu_circuit *circ = c.upload_circuit(in.n, in.m);
-  lap("verify: upload_circuit");
+  const char *what = group ? "bpgpu_r1cs_verify_shard" : pc ? "bpgpu_r1cs_verify_batch_param" : "bpgpu_r1cs_verify_batch";
   int32_t ok = 0;
-  int rc = bpgpu_r1cs_verify_batch(d.ctx(), gens, circ, 1, in.n1, in.k, in.points.data(), in.scalars.data(),
-                                   in.challenges.data(), &ok, c.mega.xy.data(), nullptr);
-  lap("verify: bpgpu_r1cs_verify_batch");
-  bpgpu_circuit_destroy(d.ctx(), circ);
+  uint8_t part[64];
+  int rc;
+  {
+    UploadedCircuit own(d, pc ? nullptr : c.upload_circuit(in.n, in.m));
+    bpgpu_circuit *circ = pc ? pc->device_circuit() : own.h;
+    if (!pc) lap("verify: upload_circuit");
+    const uint8_t *pts = in.points.data(), *sc = in.scalars.data(), *ch = in.challenges.data();
+    if (group) rc = bpgpu_r1cs_verify_shard(d.ctx(), gens, circ, in.n1, in.k, pts, sc, ch, pc ? chi.data() : nullptr, group->rank(), group->size(), part);
+    else if (pc) rc = bpgpu_r1cs_verify_batch_param(d.ctx(), gens, circ, 1, in.n1, in.k, pts, sc, ch, chi.data(), &ok, c.mega.xy.data(), nullptr);
+    else rc = bpgpu_r1cs_verify_batch(d.ctx(), gens, circ, 1, in.n1, in.k, pts, sc, ch, &ok, c.mega.xy.data(), nullptr);
+    lap((tag + what).c_str());
+  }
   if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
+  if (group) {
+    // E_GENS / E_LEN depend on the shapes only, which every rank holds alike: all ranks throw here together.  A malformed point or
+    // scalar is seen by the rank whose share holds it: that rank's partial is the poison encoding, and the sum fails on ALL ranks.
+    d.check(rc, what);
+    rc = combine_partials_rc(d, *group, part, 1);
+    what = "bpgpu_points_sum";
+  }
   if (rc == BPGPU_E_ARG) throw R1CSException(R1CSError::FormatError);
-  d.check(rc, "bpgpu_r1cs_verify_batch");
+  d.check(rc, what);
+  if (group) { memcpy(c.mega.xy.data(), part, 64); ok = c.mega.is_identity(); }
   if (!ok) throw R1CSException(R1CSError::VerificationError);                           // :549-551
+}
+void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens) { verify_core(proof, bp_gens, nullptr, nullptr, nullptr); }
+void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens, RankGroup &group, Device *device) {
+  verify_core(proof, bp_gens, nullptr, &group, device);
 }
 
 // ---- ParametricCircuit --------------------------------------------------------------------------------------------------
@@ -2039,40 +2049,11 @@ ParametricCircuit::ParametricCircuit(size_t m, const std::function<void(Verifier
 }
 ParametricCircuit::~ParametricCircuit() { if (circ_) bpgpu_circuit_destroy(Device::default_device().ctx(), circ_); }
 
-void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit &circuit, RankGroup &group, Device *device) {
-  if (group.size() <= 1) { verify(proof, bp_gens, circuit); return; }
-  CsCore &c = *c_;
-  std::vector<uint8_t> chi;
-  BatchInputs in = replay(proof, bp_gens, &circuit, &chi);
-  Device &d = same_gpu(device);
-  bpgpu_gens *gens = bp_gens.device_tables(c.pc_gens);
-  uint8_t part[64];
-  int rc = bpgpu_r1cs_verify_shard(d.ctx(), gens, circuit.device_circuit(), in.n1, in.k, in.points.data(), in.scalars.data(), in.challenges.data(),
-                                   chi.data(), group.rank(), group.size(), part);
-  if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
-  d.check(rc, "bpgpu_r1cs_verify_shard");
-  const int rc2 = combine_partials_rc(d, group, part, 1);      // (a malformed operand: the poison partial fails every rank together)
-  if (rc2 == BPGPU_E_ARG) throw R1CSException(R1CSError::FormatError);
-  d.check(rc2, "bpgpu_points_sum");
-  memcpy(c.mega.xy.data(), part, 64);
-  if (!c.mega.is_identity()) throw R1CSException(R1CSError::VerificationError);
-}
 void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit &circuit) {
-  CsCore &c = *c_;
-  Lap lap;
-  std::vector<uint8_t> chi;
-  BatchInputs in = replay(proof, bp_gens, &circuit, &chi);
-  lap("verify (parametric): transcript replay");
-  Device &d = Device::default_device();
-  bpgpu_gens *gens = bp_gens.device_tables(c.pc_gens);
-  int32_t ok = 0;
-  int rc = bpgpu_r1cs_verify_batch_param(d.ctx(), gens, circuit.device_circuit(), 1, in.n1, in.k, in.points.data(), in.scalars.data(),
-                                         in.challenges.data(), chi.data(), &ok, c.mega.xy.data(), nullptr);
-  lap("verify (parametric): bpgpu_r1cs_verify_batch_param");
-  if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
-  if (rc == BPGPU_E_ARG) throw R1CSException(R1CSError::FormatError);
-  d.check(rc, "bpgpu_r1cs_verify_batch_param");
-  if (!ok) throw R1CSException(R1CSError::VerificationError);                           // :549-551
+  verify_core(proof, bp_gens, &circuit, nullptr, nullptr);
+}
+void Verifier::verify(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit &circuit, RankGroup &group, Device *device) {
+  verify_core(proof, bp_gens, &circuit, &group, device);
 }
 
 }  // namespace r1cs

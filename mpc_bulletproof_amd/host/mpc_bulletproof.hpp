@@ -481,6 +481,7 @@ class Verifier : public RandomizedConstraintSystem {
  private:
   friend class ParametricCircuit;
   BatchInputs replay(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit *pc, std::vector<uint8_t> *chi);
+  void verify_core(const R1CSProof &proof, const BulletproofGens &bp_gens, const ParametricCircuit *pc, RankGroup *group, Device *device);
   std::unique_ptr<CsCore> c_;
 };
 

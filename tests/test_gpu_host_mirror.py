@@ -406,3 +406,69 @@ def test_shuffle_verified_against_a_parametric_circuit(host, lgk):
         assert verify_param(bytes(t), com) == rc_bad                # VerificationError either way
         swapped = com[64:128] + com[:64] + com[128:]
         assert verify_param(proof, swapped) == rc_bad
+
+
+# ------------------------------------------------------------------ the environment switches of Prover::prove_batch's IPP stages
+IPP_SWITCHES = [("BPH_HOST_IPP_TRANSCRIPT",), ("BPH_IPP_FOLD_GENERATORS",), ("BPH_HOST_IPP_TRANSCRIPT", "BPH_IPP_FOLD_GENERATORS")]
+
+
+@pytest.mark.parametrize("switches", IPP_SWITCHES, ids="+".join)
+def test_ipp_switches_give_the_oracle_bytes(host, monkeypatch, switches):
+    """BPH_HOST_IPP_TRANSCRIPT (the IPP rounds one by one, their transcript on the host) and BPH_IPP_FOLD_GENERATORS (the reference's
+    literal schedule: operands through the host, explicit G / H factors) change how Prover::prove_batch drives the inner-product
+    argument, never what it proves: proof and commitment bytes are the oracle's, in both blinding modes.  The smallest shapes at which
+    each branch differs from the default: k = 3 rounds, an n that is no power of two (the u / y^-i factors of the padding are live),
+    several values, a two-phase circuit (two commit phases), the dummy circuit."""
+    import random
+    for name in switches:
+        monkeypatch.setenv(name, "1")
+    rnd = random.Random(20261017)
+    cases = [(o.K_RANGE, w, [rnd.getrandbits(w)]) for w in (7, 33)]
+    cases.append((o.K_RANGE_MULTI, 8 | (3 << 16), [rnd.getrandbits(8) for _ in range(3)]))
+    xs = [rnd.getrandbits(64) for _ in range(3)]
+    cases.append((o.K_SHUFFLE, 3, xs + xs[::-1]))
+    cases.append((o.K_DUMMY, 3, []))
+    for vkeys in (0, 1):
+        host.bph_set_seeded_vector_keys(vkeys)
+        try:
+            for kind, param, values in cases:
+                seed, cap, label = rnd.getrandbits(48), 128, b"ipp switches %d" % param
+                rc_o, proof_o, com_o = o.r1cs_prove(kind, param, label, values, seed, cap, vector_keys=bool(vkeys))
+                rc, proof, com = _prove(host, kind, param, label, values, seed, cap)
+                assert rc == rc_o == 0 and proof == proof_o and com == com_o, (kind, param, vkeys)
+        finally:
+            host.bph_set_seeded_vector_keys(0)
+
+
+@pytest.mark.parametrize("switches", IPP_SWITCHES, ids="+".join)
+def test_ipp_switches_in_lockstep_batches(host, monkeypatch, switches):
+    """The same switches with several provers in lock-step (test_prove_batch_lockstep_matches_oracle's small shape): every per-prover
+    stride of the round loop and of the literal schedule's operands is live only from two provers on."""
+    for name in switches:
+        monkeypatch.setenv(name, "1")
+    nb, nvals, n_bits = 3, 4, 8
+    cap = nvals * n_bits
+    vals = [(17 * (i + 1) + 101 * p) % (1 << n_bits) for p in range(nb) for i in range(nvals)]
+    arr = (C.c_uint64 * len(vals))(*vals)
+    proofs = (C.c_uint8 * (nb * 8192))()
+    plen = C.c_size_t(0)
+    com = (C.c_uint8 * (nb * nvals * 64))()
+    rc = host.bph_range_prove_batch(C.c_size_t(nb), C.c_size_t(nvals), C.c_size_t(n_bits), o._buf(b"RangeProofTest"),
+                                    C.c_size_t(14), arr, C.c_uint64(500), C.c_size_t(cap), proofs, C.byref(plen), com)
+    assert rc == 0
+    L = plen.value
+    param = n_bits | (nvals << 16)
+    for p in range(nb):
+        rc_o, proof_o, com_o = o.r1cs_prove(o.K_RANGE_MULTI, param, b"RangeProofTest", vals[p * nvals:(p + 1) * nvals], 500 + p, cap)
+        assert rc_o == 0
+        assert bytes(proofs)[p * L:(p + 1) * L] == proof_o
+        assert bytes(com)[p * nvals * 64:(p + 1) * nvals * 64] == com_o
+
+
+def test_reference_tests_restated_in_cpp_with_the_host_ipp_transcript():
+    """host_tests once more, in a process of its own with BPH_HOST_IPP_TRANSCRIPT set: InnerProductProof::create then runs its rounds
+    one by one with the transcript on the host."""
+    exe = os.path.join(ROOT, "tests", "host", "host_tests")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, BPH_HOST_IPP_TRANSCRIPT="1"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all passed" in r.stdout
