@@ -99,8 +99,8 @@ int bpgpu_input_flag(bpgpu_ctx *ctx, int *bad);
 /* Kinds 16..21 cover the prover (one pair per device phase of a call, i.e. from its first to its last launch): 16 phase commitments
  * (bpgpu_r1cs_prover_commit), 17 polynomial build, 18 bpgpu_msm_gens (T commitments), 19 IPP session set-up, 20 the IPP round
  * loop, 21 the L / R table-lookup MSM of one round (the prover's dominant kernel, nested inside 20).
- * Kind 22: the launches only bpgpu_r1cs_prove_fs has (its transcript slices, the scalar links between the stages, proof assembly);
- * the stages it chains keep reporting under 16..21. */
+ * Kind 22: the launches only bpgpu_r1cs_prove_fs and bpgpu_r1cs_prove_fs2_begin / _finish have (their transcript slices, the scalar
+ * links between the stages, proof assembly); the stages they chain keep reporting under 16..21. */
 int bpgpu_profile_enable(bpgpu_ctx *ctx, int on);
 int bpgpu_profile_select(bpgpu_ctx *ctx, uint32_t kind_mask);
 int bpgpu_profile_read(bpgpu_ctx *ctx, double ms_sum[BPGPU_PROF_KINDS], uint64_t launches[BPGPU_PROF_KINDS]);
@@ -403,6 +403,60 @@ int bpgpu_r1cs_prove_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
                             const void *a_L, const void *a_R, const void *a_O, const void *s_L, const void *s_R,
                             const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
                             void *proof_scalars, void *wire, void *challenges_out, void *states_out);
+/* Prover::prove for nb provers of ONE two-phase circuit (bpgpu_circuit_create_param with nchi == 1) in TWO calls around the gadget: the
+ * phase-2 witness depends on a challenge the host evaluates its gadget on, and that is the only round trip left.  The Fiat-Shamir hash
+ * chain runs on the device in both calls; they replace bpgpu_r1cs_prover_commit (twice), _session_polys_param, bpgpu_msm_gens,
+ * bpgpu_r1cs_prover_ipp_begin, bpgpu_ipp_run_fs and the host hashing between them.  With n = the circuit's multipliers, n1 those of
+ * phase 1, n2 = n - n1 >= 1, m its commitments, padded_n = next_pow2(n), k = lg padded_n:
+ * _begin (prover.rs:420-501): append_u64("m"), the phase-1 commitments (n1 == 0 commits the blindings alone), A_I1 A_O1 S1 absorbed,
+ * the 2-phase separator, challenge_scalar(gadget_label) -- the label zero-padded to 32 bytes as in bpgpu_r1cs_verify_batch_fs2.
+ *   states_in      nb x 32        the chain state on entry to Prover::prove, as bpgpu_r1cs_prove_fs
+ *   a_L, a_R, a_O  nb x n1        ark form; s_L, s_R nb x n1 or vector_keys nb x 32: exactly one source when n1 > 0; all may be NULL
+ *                                 when n1 == 0
+ *   blindings      nb x 3         ark form: i_blinding1 o_blinding1 s_blinding1 (:457-459)
+ *   session        in: *session == NULL; out: the open session.  It keeps on the device the chain state, the gadget challenge, the
+ *                                 phase-1 blinding factors and commitments and the witness planes
+ *   commitments    (optional) nb x 3 x 64: A_I1 A_O1 S1;   gadget_challenges_out (optional) nb x 32 canonical LE;
+ *   states_out     (optional) nb x 32: the chain after the gadget challenge
+ * _finish (:515-727): the phase-2 commitments over G[n1..n), H[n1..n), A_I2 A_O2 S2 absorbed, y, z, the polynomial build with the
+ * parametric weights taken from the session's own gadget challenge, the T commitments, u, x, tb2, t_x, t_x_blinding,
+ * e_blinding = x((i1 + u i2) + x((o1 + u o2) + x(s1 + u s2))), w, the IPP session with G_factors = [1; n1] ++ [u; n2 + pad], its k
+ * rounds, proof assembly -- without a host wait in between.
+ *   a_L, a_R, a_O  nb x n2        ark form; s_L, s_R nb x n2 or vector_keys nb x 32 (exactly one of the two sources)
+ *   v_blinding     nb x m         ark form; may be NULL when m == 0
+ *   blindings      nb x 8         ark form: i_blinding2 o_blinding2 s_blinding2 tb1 tb3 tb4 tb5 tb6 (draw order of :519-523, :621-625)
+ *   proof_points   nb x (11 + 2k) x 64   A_I1 A_O1 S1 A_I2 A_O2 S2 T_1 T_3 T_4 T_5 T_6 L_0..L_{k-1} R_0..R_{k-1}, all real points
+ *   proof_scalars  nb x 5 x 32    canonical LE: t_x t_x_blinding e_blinding a b
+ *   wire           (optional) nb x proof_len, proof_len = 1 + 14 * 32 + (2k + 2) * 32: R1CSProof::to_bytes with version byte 1 and all
+ *                                 14 points
+ *   challenges_out (optional) nb x (5 + k) x 32: y z u x w u_1..u_k;   states_out (optional) nb x 32
+ * Sessions: _finish consumes the session and sets *session = NULL once anything has been launched, whatever it then returns; a
+ * refusal on shapes or arguments leaves it open; bpgpu_prover_destroy frees an abandoned one.  The staged calls (_commit,
+ * _session_polys(_param), _eval, _ipp_begin) refuse a session opened by _begin with BPGPU_E_ARG; _finish refuses a session that _begin
+ * did not open, and a circuit handle other than the one _begin was given.
+ * Refusals, before anything is launched: BPGPU_E_ARG for a null required pointer, for *session != NULL on _begin, for a numeric
+ * circuit or nchi != 1, for both or neither source of a phase's blinding vectors when that phase has multipliers, and for a context
+ * after bpgpu_set_shard(world > 1); BPGPU_E_LEN for n1 >= n (no second-phase commitments: the staged calls remain for that case);
+ * BPGPU_E_GENS for padded_n above the generators' capacity; nb == 0: BPGPU_OK with *session left NULL.  A non-canonical ark limb gives
+ * BPGPU_E_ARG in the host forms and raises bpgpu_input_flag in the `_dev` forms (every operand and result a device pointer;
+ * asynchronous on the context's stream: _finish_dev may be enqueued right after _begin_dev, without a synchronise, by a host whose
+ * phase-2 witness is already resident).  A failed call leaves no pool memory behind. */
+int bpgpu_r1cs_prove_fs2_begin(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const uint8_t *states_in,
+                               const uint8_t gadget_label[32], const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
+                               const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *blindings,
+                               bpgpu_prover **session, uint8_t *commitments, uint8_t *gadget_challenges_out, uint8_t *states_out);
+int bpgpu_r1cs_prove_fs2_begin_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
+                                   const uint8_t gadget_label[32], const void *a_L, const void *a_R, const void *a_O, const void *s_L,
+                                   const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session,
+                                   void *commitments, void *gadget_challenges_out, void *states_out);
+int bpgpu_r1cs_prove_fs2_finish(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const uint8_t *a_L,
+                                const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
+                                const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points, uint8_t *proof_scalars,
+                                uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out);
+int bpgpu_r1cs_prove_fs2_finish_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const void *a_L,
+                                    const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
+                                    const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
+                                    void *challenges_out, void *states_out);
 /* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
  * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
  * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step
@@ -533,6 +587,16 @@ int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
 int bpgpu_r1cs_verify_batch_wire_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                      size_t proof_len, const void *proofs_dev, const void *commitments_dev,
                                      const void *init_states_dev, void *ok_dev);
+
+/* bpgpu_r1cs_verify_batch_wire for ONE two-phase circuit (bpgpu_circuit_create_param, nchi == 1): the same call with the gadget's
+ * challenge label (32 bytes, zero-padded, as bpgpu_r1cs_verify_batch_fs2), so that a version-1 proof decodes, decompresses, replays
+ * and verifies on the device. */
+int bpgpu_r1cs_verify_batch_wire2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                  size_t proof_len, const uint8_t gadget_label[32], const uint8_t *proofs, const uint8_t *commitments,
+                                  const uint8_t *init_states, int32_t *ok);
+int bpgpu_r1cs_verify_batch_wire2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                      size_t proof_len, const uint8_t gadget_label[32], const void *proofs_dev,
+                                      const void *commitments_dev, const void *init_states_dev, void *ok_dev);
 
 /* Verifier::verify for nb proofs of ONE two-phase circuit (bpgpu_circuit_create_param).  _param: as bpgpu_r1cs_verify_batch with the
  * gadget challenges (nb x nchi x 32 B, in the order the gadget drew them) beside the usual 6 + k challenges.  _fs2: as

@@ -65,6 +65,7 @@ enum WsSlot : int {
   WS_PFS_SC,        // ... blindings and v_blinding (plain), T rows, tb2, t_x t_x_blinding e_blinding
   WS_PFS_PTS,       // ... A_I A_O S and T_1..T_6: sums and boundary bytes
   WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched_key)
+  WS_PFS_SCHED2,    // bpgpu_r1cs_prove_fs2_begin / _finish: the two-phase schedule (bpgpu_ctx::psched2_key)
   WS_COUNT
 };
 
@@ -108,6 +109,9 @@ struct bpgpu_ctx {
   // the prover's schedule (bpgpu_r1cs_prove_fs): (m, padded_n) -> steps resident in WS_PFS_SCHED, and its three slices
   size_t psched_key[2] = {(size_t)-1, (size_t)-1};
   int psched_cut[4] = {0, 0, 0, 0};
+  // ... and the two-phase one (bpgpu_r1cs_prove_fs2_begin / _finish) in WS_PFS_SCHED2, with its four slices
+  size_t psched2_key[2] = {(size_t)-1, (size_t)-1};
+  int psched2_cut[5] = {0, 0, 0, 0, 0};
 };
 struct ProfScope {   // records start/stop events on `st` around a launch when profiling is on (events come from a per-context pool)
   bpgpu_ctx *c; int kind; hipStream_t st;
@@ -1999,7 +2003,7 @@ static bool wire_dims(size_t proof_len, int *two_phase, size_t *k) {
 }
 static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                               size_t proof_len, const void *proofs, const void *commitments, const void *init_states,
-                              void *ok) {
+                              void *ok, const uint8_t *gadget_label = nullptr) {
   int two_phase = 0;
   size_t k = 0;
   if (!wire_dims(proof_len, &two_phase, &k)) return BPGPU_E_LEN;
@@ -2022,20 +2026,32 @@ static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_c
               (Words8 *)dcomp, (Words8 *)dsc, fmt_ok);
   points_decompress(ctx->st, (const Words8 *)dcomp, (Words8 *)dxy, dec_ok, nb * nvar, ctx->sqrt_tab);
   // undecodable points come out as the identity: the transcript / MSM run on them, the verdict is forced to 0 below
-  CK(verify_fs_locked(ctx, g, c, nb, n1, k, init_states, dxy, dsc, ok, nullptr, nullptr));
+  CK(verify_fs_locked(ctx, g, c, nb, n1, k, init_states, dxy, dsc, ok, nullptr, nullptr, gadget_label));
   wire_and_ok(ctx->st, (int32_t *)ok, fmt_ok, dec_ok, nb, nvar);
   return launch_ok(ctx);
+}
+// (gadget_label: null for the entry points without one -- a parametric circuit is then refused by the transcript half)
+static int verify_wire_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t proof_len,
+                           const uint8_t *gadget_label, const void *proofs_dev, const void *commitments_dev, const void *init_states_dev,
+                           void *ok_dev) {
+  if (!ctx || !g || !c || (nb && (!proofs_dev || !init_states_dev || !ok_dev || (c->m && !commitments_dev)))) return BPGPU_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return verify_wire_locked(ctx, g, c, nb, n1, proof_len, proofs_dev, commitments_dev, init_states_dev, ok_dev, gadget_label);
 }
 int bpgpu_r1cs_verify_batch_wire_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                      size_t proof_len, const void *proofs_dev, const void *commitments_dev,
                                      const void *init_states_dev, void *ok_dev) {
-  if (!ctx || !g || !c || (nb && (!proofs_dev || !init_states_dev || !ok_dev || (c->m && !commitments_dev)))) return BPGPU_E_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return verify_wire_locked(ctx, g, c, nb, n1, proof_len, proofs_dev, commitments_dev, init_states_dev, ok_dev);
+  return verify_wire_dev(ctx, g, c, nb, n1, proof_len, nullptr, proofs_dev, commitments_dev, init_states_dev, ok_dev);
 }
-int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
-                                 size_t proof_len, const uint8_t *proofs, const uint8_t *commitments,
-                                 const uint8_t *init_states, int32_t *ok) {
+int bpgpu_r1cs_verify_batch_wire2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                      size_t proof_len, const uint8_t gadget_label[32], const void *proofs_dev,
+                                      const void *commitments_dev, const void *init_states_dev, void *ok_dev) {
+  if (!gadget_label) return BPGPU_E_ARG;
+  return verify_wire_dev(ctx, g, c, nb, n1, proof_len, gadget_label, proofs_dev, commitments_dev, init_states_dev, ok_dev);
+}
+static int verify_wire_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t proof_len,
+                            const uint8_t *gadget_label, const uint8_t *proofs, const uint8_t *commitments, const uint8_t *init_states,
+                            int32_t *ok) {
   if (!ctx || !g || !c || (nb && (!proofs || !init_states || !ok || (c->m && !commitments)))) return BPGPU_E_ARG;
   if (!nb) return BPGPU_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2049,10 +2065,21 @@ int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
   CK(h2d(ctx, dP, proofs, nb * proof_len));
   if (m) CK(h2d(ctx, dC, commitments, nb * m * 32));
   CK(h2d(ctx, dI, init_states, nb * 32));
-  CK(verify_wire_locked(ctx, g, c, nb, n1, proof_len, dP, dC, dI, dok));
+  CK(verify_wire_locked(ctx, g, c, nb, n1, proof_len, dP, dC, dI, dok, gadget_label));
   CK(d2h(ctx, ok, dok, nb * 4));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
   return BPGPU_OK;
+}
+int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                 size_t proof_len, const uint8_t *proofs, const uint8_t *commitments,
+                                 const uint8_t *init_states, int32_t *ok) {
+  return verify_wire_host(ctx, g, c, nb, n1, proof_len, nullptr, proofs, commitments, init_states, ok);
+}
+int bpgpu_r1cs_verify_batch_wire2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                  size_t proof_len, const uint8_t gadget_label[32], const uint8_t *proofs, const uint8_t *commitments,
+                                  const uint8_t *init_states, int32_t *ok) {
+  if (!gadget_label) return BPGPU_E_ARG;
+  return verify_wire_host(ctx, g, c, nb, n1, proof_len, gadget_label, proofs, commitments, init_states, ok);
 }
 
 /* ---------------------------------------------------------------- combined batch check
@@ -2903,9 +2930,13 @@ struct bpgpu_prover {
   const bpgpu_gens *g = nullptr;        // the generators of the commitments (T points of bpgpu_mpc_prover_polys_finish)
   Words8 *trip = nullptr, *wv = nullptr; // the polynomial build's Beaver triples (plain) and wV (proofs x m), mask -> finish
   bool finished = false;
+  // a session of bpgpu_r1cs_prove_fs2_begin, until _finish consumes it: four arrays over the nb provers -- the chain states after the
+  // gadget challenge (32 B each), the gadget challenges, the phase-1 blinding factors (3 each, plain), A_I1 A_O1 S1 (3 x 64 B each)
+  Words8 *fs2 = nullptr;
+  const bpgpu_circuit *fs2_c = nullptr;   // the circuit _begin was given
 };
 static void prover_free_all(bpgpu_ctx *ctx, bpgpu_prover *s) {   // ctx->mu held
-  void *all[] = {s->polys, s->y, s->aL, s->aR, s->aO, s->sL, s->sR, s->yinv, s->trip, s->wv};
+  void *all[] = {s->polys, s->y, s->aL, s->aR, s->aO, s->sL, s->sR, s->yinv, s->trip, s->wv, s->fs2};
   for (void *p : all) pool_release(ctx, p);
   delete s;
 }
@@ -3017,7 +3048,7 @@ int bpgpu_r1cs_prover_polys_ark(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t n
 }
 int bpgpu_r1cs_prover_eval(bpgpu_ctx *ctx, bpgpu_prover *s, size_t padded_n, const uint8_t *x, uint8_t *l_vec,
                            uint8_t *r_vec) {
-  if (!ctx || !s || !x || !l_vec || !r_vec || s->planes != 1) return BPGPU_E_ARG;
+  if (!ctx || !s || !x || !l_vec || !r_vec || s->planes != 1 || s->fs2) return BPGPU_E_ARG;   // (fs2: _finish owns such a session's rest)
   if (padded_n < s->n || (padded_n & (padded_n - 1))) return BPGPU_E_LEN;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCK(ctx, hipSetDevice(ctx->device));
@@ -3072,7 +3103,7 @@ static int prover_ipp_begin_impl(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_g
 int bpgpu_r1cs_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *ps, const bpgpu_gens *g, size_t padded_n, size_t n1,
                                 const uint8_t *x, const uint8_t *u, const uint8_t *y_inv, const uint8_t *w,
                                 bpgpu_ipp **out) {
-  if (!ctx || !ps || !g || !x || !u || (!y_inv && !ps->yinv) || !w || !out || !ps->polys || ps->planes != 1) return BPGPU_E_ARG;
+  if (!ctx || !ps || !g || !x || !u || (!y_inv && !ps->yinv) || !w || !out || !ps->polys || ps->planes != 1 || ps->fs2) return BPGPU_E_ARG;
   return prover_ipp_begin_impl(ctx, ps, g, padded_n, n1, x, u, y_inv, w, out);
 }
 void bpgpu_prover_destroy(bpgpu_ctx *ctx, bpgpu_prover *s) {
@@ -3147,6 +3178,7 @@ static int prover_commit_impl(bpgpu_ctx *ctx, const bpgpu_gens *g, bpgpu_prover 
                               const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *commitments, int planes) {
   if (!ctx || !g || !session || !nb || !blindings || !commitments) return BPGPU_E_ARG;
   if (*session && (*session)->planes != planes) return BPGPU_E_ARG;   // no mixing of single-party and authenticated calls
+  if (*session && (*session)->fs2) return BPGPU_E_ARG;                // opened by bpgpu_r1cs_prove_fs2_begin: _finish commits its phase 2
   if (n_new && (!a_L || !a_R || !a_O)) return BPGPU_E_ARG;
   const bool explicit_vec = s_L && s_R;
   if (n_new && (explicit_vec == (vector_keys != nullptr) || (!s_L) != (!s_R))) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
@@ -3179,13 +3211,13 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
                                        const uint8_t *chi, uint8_t *t_coeffs, uint8_t *wV);
 int bpgpu_r1cs_prover_session_polys(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                     uint8_t *t_coeffs, uint8_t *wV) {
-  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1) return BPGPU_E_ARG;
+  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1 || s->fs2) return BPGPU_E_ARG;
   if (c->nchi) return BPGPU_E_ARG;
   return prover_session_polys_locked(ctx, s, c, y, z, nullptr, t_coeffs, wV);
 }
 int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *s, const bpgpu_circuit *c, const uint8_t *y, const uint8_t *z,
                                           const uint8_t *gadget_challenges, uint8_t *t_coeffs, uint8_t *wV) {
-  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1) return BPGPU_E_ARG;
+  if (!ctx || !s || !c || !y || !z || !t_coeffs || (c->m && !wV) || s->planes != 1 || s->fs2) return BPGPU_E_ARG;
   if (!c->nchi || !gadget_challenges) return BPGPU_E_ARG;
   return prover_session_polys_locked(ctx, s, c, y, z, gadget_challenges, t_coeffs, wV);
 }
@@ -3379,6 +3411,273 @@ int bpgpu_r1cs_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit
     const ProveFsIo io{in_dev[0], in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7], in_dev[8],
                        out_dev[0], out_dev[1], wire ? out_dev[4] : nullptr, out_dev[2], out_dev[3]};
     CK(prove_fs_locked(ctx, g, c, nb, io));
+    return checked_download(ctx, {{proof_points, out_dev[0], out_bytes[0]}, {proof_scalars, out_dev[1], out_bytes[1]},
+                                  {challenges_out, out_dev[2], challenges_out ? out_bytes[2] : 0},
+                                  {states_out, out_dev[3], states_out ? out_bytes[3] : 0}, {wire, out_dev[4], out_bytes[4]}});
+  });
+}
+/* ---- Prover::prove for a TWO-PHASE circuit (one gadget challenge) in two calls around the host's gadget: _begin = prover.rs:420-501
+ * (phase-1 commitments, the chain up to the gadget challenge), _finish = :515-727 (everything else, as prove_fs_locked with a second
+ * commitment phase).  The session carries the chain state, the challenge, the phase-1 blinding factors and commitments from the one
+ * to the other in HBM: _finish_dev may follow _begin_dev on the stream without a wait. -------------------------------------------- */
+namespace {
+struct ProveFs2BeginIo {   // every pointer in HBM but the label
+  const uint8_t *states_in, *gadget_label, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *blindings;
+  uint8_t *commitments, *chi_out, *states_out;
+};
+struct Fs2Arrays { uint64_t *states; Words8 *chi, *bl1, *A1; };
+}  // namespace
+static Fs2Arrays fs2_arrays(const bpgpu_prover *s) { return {(uint64_t *)s->fs2, s->fs2 + s->nb, s->fs2 + 2 * s->nb, s->fs2 + 5 * s->nb}; }
+// the two-phase schedule of (m, padded_n), resident in WS_PFS_SCHED2 (ctx->mu held)
+static int prove_fs2_schedule(bpgpu_ctx *ctx, size_t m, size_t padded_n, const TrStep **steps_out) {
+  void *dsteps;
+  CK(ws_get(ctx, WS_PFS_SCHED2, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
+  if (ctx->psched2_key[0] != m || ctx->psched2_key[1] != padded_n) {
+    TrStep steps[PROVER_SCHEDULE_MAX];
+    const int len = prover_transcript_schedule2(steps, m, padded_n, ctx->psched2_cut);
+    static_assert(PROVER_SCHEDULE_MAX >= 24, "the two-phase schedule has 24 steps");
+    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
+    HIPCK(ctx, hipStreamSynchronize(ctx->st));   // `steps` is a local
+    ctx->psched2_key[0] = m; ctx->psched2_key[1] = padded_n;
+  }
+  *steps_out = (const TrStep *)dsteps;
+  return BPGPU_OK;
+}
+// the refusals that depend on shapes and arguments alone (BPGPU_OK with nb == 0: nothing to do)
+static int prove_fs2_begin_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
+                                 const uint8_t *gadget_label, const void *a_L, const void *a_R, const void *a_O, const void *s_L,
+                                 const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session) {
+  if (!ctx || !g || !c || !session || *session) return BPGPU_E_ARG;
+  if (c->nchi != 1) return BPGPU_E_ARG;      // a numeric circuit has no gadget challenge (bpgpu_r1cs_prove_fs); one label per schedule
+  if (!nb) return BPGPU_OK;
+  if (n1 >= c->n) return BPGPU_E_LEN;        // (no second-phase commitments: the staged calls serve such provers)
+  if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
+  if (!states_in || !gadget_label || !blindings) return BPGPU_E_ARG;
+  if (n1 && (!a_L || !a_R || !a_O || (!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr))) return BPGPU_E_ARG;
+  return BPGPU_OK;
+}
+// ctx->mu held, shapes checked, nb > 0; asynchronous.  `own` holds the session, also on failure.
+static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const ProveFs2BeginIo &io,
+                                  ProverOwner &own) {
+  const ProveFsDims d = prove_fs_dims(c);
+  hipStream_t st = ctx->st;
+  const OperandSrc dev{true, false};                 // operands in HBM; the caller has reset the input flag
+  const TrStep *steps;
+  CK(prove_fs2_schedule(ctx, d.m, d.padded_n, &steps));
+  const int *cut = ctx->psched2_cut;
+  bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
+  if (!s) return BPGPU_E_OOM;
+  own.reset(s);
+  s->nb = nb; s->planes = 1; s->g = g; s->fs2_c = c;
+  if (!pool_alloc(ctx, (void **)&s->fs2, nb * 11 * 32)) return BPGPU_E_OOM;
+  const Fs2Arrays f = fs2_arrays(s);
+  CK(copy_in(ctx, f.states, io.states_in, nb * 32, true));
+  {
+    ProfScope link(ctx, 22, st);
+    scalars_from_ark(st, (const Words8 *)io.blindings, f.bl1, 3 * nb, ctx->d_flag);
+  }
+  // prover.rs:420-501: append_u64("m"), the phase-1 commitments, the 2-phase separator, the gadget's challenge
+  const bool keys = n1 && !io.s_L;
+  Words8 *dA;
+  CK(prover_commit_core(ctx, g, s, nb, n1, io.a_L, io.a_R, io.a_O, n1 ? io.s_L : nullptr, n1 ? io.s_R : nullptr,
+                        keys ? io.vector_keys : nullptr, io.blindings, 3 * 32, dev, &dA));
+  {
+    ProfScope link(ctx, 22, st);
+    prover_transcript(st, nb, steps + cut[0], cut[1] - cut[0], f.states, dA, 3, nullptr, 0, nullptr, io.gadget_label, f.chi);
+  }
+  HIPCK(ctx, hipMemcpyAsync(f.A1, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
+  if (io.commitments) HIPCK(ctx, hipMemcpyAsync(io.commitments, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
+  if (io.chi_out) HIPCK(ctx, hipMemcpyAsync(io.chi_out, f.chi, nb * 32, hipMemcpyDeviceToDevice, st));
+  if (io.states_out) HIPCK(ctx, hipMemcpyAsync(io.states_out, f.states, nb * 32, hipMemcpyDeviceToDevice, st));   // (little-endian words)
+  return launch_ok(ctx);
+}
+int bpgpu_r1cs_prove_fs2_begin_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
+                                   const uint8_t gadget_label[32], const void *a_L, const void *a_R, const void *a_O, const void *s_L,
+                                   const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session,
+                                   void *commitments, void *gadget_challenges_out, void *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs2_begin_check(ctx, g, c, nb, n1, states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, session));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;    // partial sums cannot be hashed
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call; _finish_dev adds to it: one flag for the pair
+    const ProveFs2BeginIo io{(const uint8_t *)states_in, gadget_label, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O,
+                             (const uint8_t *)s_L, (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)blindings,
+                             (uint8_t *)commitments, (uint8_t *)gadget_challenges_out, (uint8_t *)states_out};
+    ProverOwner own(nullptr, ProverFree{ctx});
+    CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, io, own));
+    *session = own.release();
+    return BPGPU_OK;
+  });
+}
+int bpgpu_r1cs_prove_fs2_begin(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const uint8_t *states_in,
+                               const uint8_t gadget_label[32], const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
+                               const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *blindings,
+                               bpgpu_prover **session, uint8_t *commitments, uint8_t *gadget_challenges_out, uint8_t *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs2_begin_check(ctx, g, c, nb, n1, states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, session));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t tot = nb * n1 * 32;
+    // staging: the operands in the order of the argument list, then the results
+    const size_t in_bytes[8] = {nb * 32, tot, tot, tot, n1 && s_L ? tot : 0, n1 && s_R ? tot : 0, n1 && vector_keys ? nb * 32 : 0, nb * 3 * 32};
+    const size_t out_bytes[3] = {nb * 3 * 64, nb * 32, nb * 32};
+    size_t total = 0;
+    for (size_t b : in_bytes) total += b;
+    for (size_t b : out_bytes) total += b;
+    void *dstage;
+    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
+    const uint8_t *in_host[8] = {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings};
+    uint8_t *in_dev[8], *out_dev[3], *at = (uint8_t *)dstage;
+    for (int i = 0; i < 8; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
+    for (int i = 0; i < 3; i++) { out_dev[i] = at; at += out_bytes[i]; }
+    CK(flag_reset(ctx));
+    for (int i = 0; i < 8; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
+    const ProveFs2BeginIo io{in_dev[0], gadget_label, in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7],
+                             out_dev[0], out_dev[1], out_dev[2]};
+    ProverOwner own(nullptr, ProverFree{ctx});
+    CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, io, own));
+    CK(checked_download(ctx, {{commitments, out_dev[0], commitments ? out_bytes[0] : 0},
+                              {gadget_challenges_out, out_dev[1], gadget_challenges_out ? out_bytes[1] : 0},
+                              {states_out, out_dev[2], states_out ? out_bytes[2] : 0}}));
+    *session = own.release();
+    return BPGPU_OK;
+  });
+}
+// _finish's refusals: they leave the session open
+static int prove_fs2_finish_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const void *a_L,
+                                  const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
+                                  const void *v_blinding, const void *blindings, const void *proof_points, const void *proof_scalars) {
+  if (!ctx || !g || !c || !session || !*session) return BPGPU_E_ARG;
+  const bpgpu_prover *s = *session;
+  if (!s->fs2 || s->fs2_c != c || s->g != g) return BPGPU_E_ARG;   // opened by _begin, on this circuit and these generators
+  if (!a_L || !a_R || !a_O || !blindings || !proof_points || !proof_scalars || (c->m && !v_blinding)) return BPGPU_E_ARG;
+  if ((!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  return BPGPU_OK;
+}
+// ctx->mu held, arguments checked; asynchronous.  The session is `pown`'s: its buffers, and the IPP session's, go back to the
+// context's pool on the way out (stream-ordered reuse), whatever the outcome.
+static int prove_fs2_finish_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, ProverOwner &pown, const ProveFsIo &io) {
+  bpgpu_prover *s = pown.get();
+  const ProveFsDims d = prove_fs_dims(c);
+  const size_t nb = s->nb, n = d.n, m = d.m, k = d.k, n1 = s->wn, n2 = n - n1;
+  hipStream_t st = ctx->st;
+  const OperandSrc dev{true, false};                 // operands in HBM; ONE input flag for the whole chain
+  const TrStep *steps;
+  CK(prove_fs2_schedule(ctx, m, d.padded_n, &steps));
+  const int *cut = ctx->psched2_cut;
+  void *dchs, *dscs, *dpts, *dlr, *dzero;
+  CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + k) * 32, &dchs));
+  CK(ws_get(ctx, WS_PFS_SC, nb * (8 + m + 10 + 1 + 3) * 32, &dscs));
+  CK(ws_get(ctx, WS_PFS_PTS, nb * 5 * (64 + sizeof(JacRaw)), &dpts));
+  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
+  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
+  const Fs2Arrays f = fs2_arrays(s);
+  Words8 *dch = (Words8 *)dchs + nb, *duch = dch + 5 * nb;                        // y z u x w: nb each; then u_1..u_k
+  const uint8_t *cy = (const uint8_t *)dch, *cz = (const uint8_t *)(dch + nb), *cu = (const uint8_t *)(dch + 2 * nb),
+                *cx = (const uint8_t *)(dch + 3 * nb), *cw = (const uint8_t *)(dch + 4 * nb);
+  Words8 *dbl = (Words8 *)dscs, *dvb = dbl + 8 * nb, *drows = dvb + nb * m, *dtb2 = drows + 10 * nb, *dsc3 = dtb2 + nb;
+  Words8 *dT = (Words8 *)dpts;
+  JacRaw *dTres = (JacRaw *)(dT + nb * 5 * 2);
+  IppOwner iown(nullptr, IppFree{ctx});
+  {
+    ProfScope link(ctx, 22, st);
+    scalars_from_ark(st, (const Words8 *)io.blindings, dbl, 8 * nb, ctx->d_flag);
+    scalars_from_ark(st, (const Words8 *)io.v_blinding, dvb, nb * m, ctx->d_flag);
+  }
+  // prover.rs:515-585: the phase-2 commitments over G[n1..n), H[n1..n); A_I2 A_O2 S2; y, z
+  Words8 *dA2;
+  CK(prover_commit_core(ctx, g, s, nb, n2, io.a_L, io.a_R, io.a_O, io.s_L, io.s_R, io.vector_keys, io.blindings, 8 * 32, dev, &dA2));
+  {
+    ProfScope link(ctx, 22, st);
+    prover_transcript(st, nb, steps + cut[1], cut[2] - cut[1], f.states, dA2, 3, nullptr, 0, dch);
+  }
+  // :587-640: the polynomial build on the session's own gadget challenge; T_i = t_i B + tb_i B_blinding; u, x
+  Words8 *dt, *dwV;
+  CK(session_polys_core(ctx, s, c, cy, cz, (const uint8_t *)f.chi, dev, &dt, &dwV));
+  s->n = n; s->m = m;
+  {
+    ProfScope link(ctx, 22, st);
+    prove_fs_t_rows(st, nb, dt, dbl, drows);
+  }
+  {
+    ProfScope tmsm(ctx, 18, st);
+    CK(msm_gens_dev(ctx, g, nb * 5, 0, (const uint32_t *)drows, dTres, st));
+    jac_to_boundary(st, dTres, dT, nb * 5);
+  }
+  {
+    // :644-686: tb2, t_x, t_x_blinding, e_blinding over both phases' blinding factors; w; then innerproduct_domain_sep
+    ProfScope link(ctx, 22, st);
+    prover_transcript(st, nb, steps + cut[2], cut[3] - cut[2], f.states, dT, 5, nullptr, 0, dch);
+    const bool coop = m > PROVE_FS_DOT_LANE_MAX;
+    if (coop) sc_dot_batched(st, nb, m, dwV, m, dvb, m, dtb2, 1);
+    prove_fs_glue(st, nb, m, (const Words8 *)cx, dt, dbl, dwV, dvb, coop ? dtb2 : nullptr, dsc3, (const Words8 *)cu, f.bl1);
+    prover_transcript(st, nb, steps + cut[3], cut[4] - cut[3], f.states, nullptr, 0, dsc3, 3, dch);
+  }
+  // :687-708: l(x), r(x), G_factors = [1; n1] ++ [u; n2 + pad], Q = w B; the k rounds (u_j kept for challenges_out)
+  CK(prover_ipp_begin_core(ctx, s, g, d.padded_n, n1, cx, cu, nullptr, cw, dev, iown));
+  bpgpu_ipp *ipp = iown.get();
+  CK(ipp_rounds_fs_dev(ctx, ipp, k, f.states, dlr, duch, dzero));
+  {
+    ProfScope link(ctx, 22, st);
+    ProveFsAssemble a{nb, k, f.A1, dT, (const Words8 *)dlr, dsc3, ipp->a[ipp->cur], ipp->b[ipp->cur], dch, duch, f.states,
+                      (Words8 *)io.proof_points, (Words8 *)io.proof_scalars, (Words8 *)io.challenges_out, (Words8 *)io.states_out, io.wire,
+                      dA2};
+    prove_fs_assemble(st, a);
+  }
+  return launch_ok(ctx);
+}
+int bpgpu_r1cs_prove_fs2_finish_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const void *a_L,
+                                    const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
+                                    const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
+                                    void *challenges_out, void *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs2_finish_check(ctx, g, c, session, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    ProverOwner pown(*session, ProverFree{ctx});   // from here on the session is consumed
+    *session = nullptr;
+    // (no flag reset: what _begin_dev's operands raised stays raised -- the flag reports on the pair)
+    const ProveFsIo io{nullptr, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O, (const uint8_t *)s_L,
+                       (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)v_blinding, (const uint8_t *)blindings,
+                       (uint8_t *)proof_points, (uint8_t *)proof_scalars, (uint8_t *)wire, (uint8_t *)challenges_out, (uint8_t *)states_out};
+    return prove_fs2_finish_locked(ctx, g, c, pown, io);
+  });
+}
+int bpgpu_r1cs_prove_fs2_finish(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const uint8_t *a_L,
+                                const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
+                                const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points, uint8_t *proof_scalars,
+                                uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs2_finish_check(ctx, g, c, session, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const ProveFsDims d = prove_fs_dims(c);
+    const size_t nb = (*session)->nb, tot = nb * (d.n - (*session)->wn) * 32, nvar = 11 + 2 * d.k, proof_len = 1 + 14 * 32 + (2 * d.k + 2) * 32;
+    // staging: the operands in the order of the argument list, then the results (the wire form, of odd length, last)
+    const size_t in_bytes[8] = {tot, tot, tot, s_L ? tot : 0, s_R ? tot : 0, vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32};
+    const size_t out_bytes[5] = {nb * nvar * 64, nb * 5 * 32, nb * (5 + d.k) * 32, nb * 32, wire ? nb * proof_len : 0};
+    size_t total = 0;
+    for (size_t b : in_bytes) total += b;
+    for (size_t b : out_bytes) total += b;
+    void *dstage;
+    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
+    ProverOwner pown(*session, ProverFree{ctx});   // from here on the session is consumed
+    *session = nullptr;
+    const uint8_t *in_host[8] = {a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings};
+    uint8_t *in_dev[8], *out_dev[5], *at = (uint8_t *)dstage;
+    for (int i = 0; i < 8; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
+    for (int i = 0; i < 5; i++) { out_dev[i] = at; at += out_bytes[i]; }
+    CK(flag_reset(ctx));
+    for (int i = 0; i < 8; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
+    const ProveFsIo io{nullptr, in_dev[0], in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7],
+                       out_dev[0], out_dev[1], wire ? out_dev[4] : nullptr, out_dev[2], out_dev[3]};
+    CK(prove_fs2_finish_locked(ctx, g, c, pown, io));
     return checked_download(ctx, {{proof_points, out_dev[0], out_bytes[0]}, {proof_scalars, out_dev[1], out_bytes[1]},
                                   {challenges_out, out_dev[2], challenges_out ? out_bytes[2] : 0},
                                   {states_out, out_dev[3], states_out ? out_bytes[3] : 0}, {wire, out_dev[4], out_bytes[4]}});

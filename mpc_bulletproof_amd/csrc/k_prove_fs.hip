@@ -2,6 +2,8 @@
 // for a circuit without randomized constraints, with the transcript on the device).  The stages themselves are the staged entry
 // points' kernels (phase commitments, polynomial build, fixed-base MSMs, the IPP session and its rounds) and the transcript slices
 // of k_transcript.hip; here: the scalar rows of the T commitments, the scalars between the x and the w challenge, proof assembly.
+// The two calls of a two-phase prover (bpgpu_r1cs_prove_fs2_begin / _finish) use the same links: the glue with the second phase's
+// blinding factors and u, the assembly with a second commitment triple.
 // Each launch is a short link of one batch's latency chain -- a lane per proof (or per output item), nothing to tune for throughput.
 #include "fe29_sqrt.cuh"
 #include "fn_dev.cuh"
@@ -24,13 +26,14 @@ void prove_fs_t_rows(hipStream_t st, size_t nb, const Words8 *t, const Words8 *b
   if (nb) hipLaunchKernelGGL(k_pfs_t_rows, dim3((nb * 5 + 255) / 256), dim3(256), 0, st, nb, t, bl, rows);
 }
 
-// prover.rs:644-678 with n2 = 0 (no second phase: the u terms of :674-676 vanish), a lane per proof:
+// prover.rs:644-678, a lane per proof (u = nullptr: n2 = 0, no second phase -- the u terms of :674-676 vanish):
 //   tb2 = <wV, v_blinding>                       (:644-648; m <= PROVE_FS_DOT_LANE_MAX: here, a serial loop; above: tb2_pre, which
 //                                                 sc_dot_batched -- a block per proof, shuffle + LDS reduction -- has computed)
 //   t_x = sum_i t_i x^i, t_x_blinding = sum_i tb_i x^i  (i = 1..6, util.rs:192-194);  e_blinding = x (i_b + x (o_b + x s_b))  (:678)
+//   with i_b = i1 + u i2 etc. (:674-676) for two phases: bl's first three are then i2 o2 s2, bl1 (nb x 3) holds i1 o1 s1
 // out: nb x 3 (t_x, t_x_blinding, e_blinding), plain canonical -- the third transcript slice absorbs them from there.
 __global__ void __launch_bounds__(64) k_pfs_glue(size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV,
-                                                 const Words8 *vb, const Words8 *tb2_pre, Words8 *out) {
+                                                 const Words8 *vb, const Words8 *tb2_pre, Words8 *out, const Words8 *u, const Words8 *bl1) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nb) return;
   Fn tb2 = fe_zero<FN>();
@@ -54,21 +57,30 @@ __global__ void __launch_bounds__(64) k_pfs_glue(size_t nb, size_t m, const Word
   }
   store_plain(&out[p * 3], mul(tx, xx));
   store_plain(&out[p * 3 + 1], mul(tb, xx));
-  const Fn e = mul(xx, add(load_plain(&bp_[0]), mul(xx, add(load_plain(&bp_[1]), mul(xx, load_plain(&bp_[2]))))));
+  // the blinding factors of A_I, A_O, S: one phase: bl's first three; two (:674-676): i1 + u i2 etc., the first phase's from bl1
+  Fn ib = load_plain(&bp_[0]), ob = load_plain(&bp_[1]), sb = load_plain(&bp_[2]);
+  if (u) {
+    const Fn uu = load_plain(&u[p]);
+    ib = add(load_plain(&bl1[p * 3]), mul(uu, ib));
+    ob = add(load_plain(&bl1[p * 3 + 1]), mul(uu, ob));
+    sb = add(load_plain(&bl1[p * 3 + 2]), mul(uu, sb));
+  }
+  const Fn e = mul(xx, add(ib, mul(xx, add(ob, mul(xx, sb)))));
   store_plain(&out[p * 3 + 2], e);
 }
 void prove_fs_glue(hipStream_t st, size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV, const Words8 *vb,
-                   const Words8 *tb2_pre, Words8 *out) {
-  if (nb) hipLaunchKernelGGL(k_pfs_glue, dim3((nb + 63) / 64), dim3(64), 0, st, nb, m, x, t, bl, wV, vb, tb2_pre, out);
+                   const Words8 *tb2_pre, Words8 *out, const Words8 *u, const Words8 *bl1) {
+  if (nb) hipLaunchKernelGGL(k_pfs_glue, dim3((nb + 63) / 64), dim3(64), 0, st, nb, m, x, t, bl, wV, vb, tb2_pre, out, u, bl1);
 }
 
 // Proof assembly, a lane per output item of a proof: its 11 + 2k points, 5 scalars, 5 + k challenges and chain state.
 //   A: nb x 3 points, T: nb x 5 points, lr: k x nb x (L, R) points (round-major, as the round loop leaves them); sc3: nb x 3 (the
 //   glue's); a, b: nb; ch: 5 arrays of nb (y z u x w); uch: k arrays of nb (u_1..u_k); states: 4 x u64 per proof.
-//   proof_points  nb x (11 + 2k) x 64 B : A_I1 A_O1 S1 A_I2 A_O2 S2 (identity) T_1 T_3 T_4 T_5 T_6 L_0.. R_0..
+//   proof_points  nb x (11 + 2k) x 64 B : A_I1 A_O1 S1 A_I2 A_O2 S2 (identity, or A2: nb x 3 points) T_1 T_3 T_4 T_5 T_6 L_0.. R_0..
 //   proof_scalars nb x 5 x 32 B        : t_x t_x_blinding e_blinding a b
 //   wire (optional) nb x proof_len     : R1CSProof::to_bytes, r1cs/proof.rs:82-109 -- version byte 0, A_I1 A_O1 S1 T_1..T_6 compressed,
-//                                        the three scalars big-endian, (L_j, R_j) pairs compressed, a, b big-endian
+//                                        the three scalars big-endian, (L_j, R_j) pairs compressed, a, b big-endian; with A2: version
+//                                        byte 1, A_I2 A_O2 S2 behind S1 (14 points), every later slot three further on
 //   challenges_out (optional) nb x (5 + k) x 32 B : y z u x w u_1..u_k;  states_out (optional) nb x 32 B
 // (ProveFsAssemble: kernels.h)
 __device__ __forceinline__ void put_bytes_le(uint8_t *dst, const uint32_t w[8]) {
@@ -85,18 +97,20 @@ __device__ __forceinline__ void put_bytes_be(uint8_t *dst, const uint32_t w[8]) 
   }
 }
 __global__ void __launch_bounds__(256) k_pfs_assemble(ProveFsAssemble o) {
-  const size_t k = o.k, nvar = 11 + 2 * k, per = nvar + 5 + (5 + k) + 1, proof_len = 1 + 11 * 32 + (2 * k + 2) * 32;
+  // sh: the wire slots that A_I2 A_O2 S2 take when there is a second phase (version 1 carries all 14 points)
+  const size_t k = o.k, nvar = 11 + 2 * k, per = nvar + 5 + (5 + k) + 1, sh = o.A2 ? 3 : 0, proof_len = 1 + (11 + sh) * 32 + (2 * k + 2) * 32;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= o.nb * per) return;
   const size_t p = t / per, s = t - p * per;
   uint8_t *wire = o.wire ? o.wire + p * proof_len : nullptr;
   if (s < nvar) {
-    const Words8 *src = nullptr;     // identity: A_I2 A_O2 S2
+    const Words8 *src = nullptr;     // identity: A_I2 A_O2 S2 of a one-phase proof
     size_t wslot = (size_t)-1;       // 32-byte slot of the wire body, none for the identity points (version 0 omits them)
     if (s < 3) { src = o.A + (p * 3 + s) * 2; wslot = s; }
-    else if (s >= 6 && s < 11) { src = o.T + (p * 5 + (s - 6)) * 2; wslot = s - 3; }
-    else if (s >= 11 && s < 11 + k) { src = o.lr + ((s - 11) * o.nb + p) * 4; wslot = 11 + 2 * (s - 11); }
-    else if (s >= 11 + k) { src = o.lr + ((s - 11 - k) * o.nb + p) * 4 + 2; wslot = 11 + 2 * (s - 11 - k) + 1; }
+    else if (s < 6) { if (o.A2) { src = o.A2 + (p * 3 + (s - 3)) * 2; wslot = s; } }
+    else if (s < 11) { src = o.T + (p * 5 + (s - 6)) * 2; wslot = s - 3 + sh; }
+    else if (s < 11 + k) { src = o.lr + ((s - 11) * o.nb + p) * 4; wslot = 11 + sh + 2 * (s - 11); }
+    else { src = o.lr + ((s - 11 - k) * o.nb + p) * 4 + 2; wslot = 11 + sh + 2 * (s - 11 - k) + 1; }
     uint32_t x[8], y[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) { x[j] = src ? src[0].w[j] : 0u; y[j] = src ? src[1].w[j] : 0u; }
@@ -107,7 +121,7 @@ __global__ void __launch_bounds__(256) k_pfs_assemble(ProveFsAssemble o) {
       compress_xy_words(x, y);
       put_bytes_le(wire + 1 + 32 * wslot, x);
     }
-    if (wire && s == 0) wire[0] = 0;   // ONE_PHASE_COMMITMENTS
+    if (wire && s == 0) wire[0] = o.A2 ? 1 : 0;   // TWO_PHASE_COMMITMENTS : ONE_PHASE_COMMITMENTS
   } else if (s < nvar + 5) {
     const size_t q = s - nvar;
     const Words8 *src = q < 3 ? o.sc3 + p * 3 + q : (q == 3 ? o.a + p : o.b + p);
@@ -116,7 +130,7 @@ __global__ void __launch_bounds__(256) k_pfs_assemble(ProveFsAssemble o) {
     for (int j = 0; j < 8; j++) w[j] = src->w[j];
 #pragma unroll
     for (int j = 0; j < 8; j++) o.proof_scalars[p * 5 + q].w[j] = w[j];
-    if (wire) put_bytes_be(wire + 1 + 32 * (q < 3 ? 8 + q : 11 + 2 * k + (q - 3)), w);
+    if (wire) put_bytes_be(wire + 1 + 32 * (sh + (q < 3 ? 8 + q : 11 + 2 * k + (q - 3))), w);
   } else if (s < nvar + 5 + 5 + k) {
     if (!o.challenges_out) return;
     const size_t c = s - nvar - 5;

@@ -564,7 +564,8 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
 // prover appends its own points without the identity check.
 constexpr uint32_t TS_SRC_IDENTITY = 0xFFFFFFFFu;
 __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrStep *steps, int nsteps, uint64_t *states, const Words8 *points,
-                                                          size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges) {
+                                                          size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges,
+                                                          Label gadget_label, Words8 *chi) {
   // (no raised wave priority: the note in k_verify_transcript holds for a prover batch that runs beside others)
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nb) return;
@@ -608,6 +609,9 @@ __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrSte
         chain_hash<9>(st, 0x00, lab, tail);
         break;
       }
+      case TS_GADGET_CHALLENGE:   // cs.challenge_scalar(gadget label) inside the randomized-constraints callback (prover.rs:393-408)
+        tr_challenge_scalar(st, gadget_label, &chi[p]);
+        break;
       default:
         tr_challenge_scalar(st, lab, &challenges[(size_t)s.src * nb + p]);
         break;
@@ -640,11 +644,42 @@ int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4
   cut[3] = n;
   return n;
 }
+// The same for a circuit WITH randomized constraints and one gadget challenge (bpgpu_r1cs_prove_fs2_begin / _finish), in four slices:
+//   slice 0: append_u64("m"), A_I1 A_O1 S1, the 2-phase separator, the gadget challenge (into chi[p])   -> the host's gadget
+//   slice 1: A_I2 A_O2 S2 (the second commitment's output, indexed 0..2), y, z                          -> the polynomial build
+//   slice 2, 3: as slices 1, 2 above
+int prover_transcript_schedule2(TrStep *out, size_t m, size_t padded_n, int cut[5]) {
+  int n = 0;
+  auto add = [&](uint8_t kind, uint8_t label, uint32_t src, uint64_t value) {
+    out[n].kind = kind; out[n].label = label; out[n].validate = 0; out[n].pad = 0; out[n].src = src; out[n].value = value; n++;
+  };
+  cut[0] = 0;
+  add(TS_U64, LB_m, 0, m);                                                                       // prover.rs:420
+  add(TS_POINT, LB_AI1, 0, 0); add(TS_POINT, LB_AO1, 1, 0); add(TS_POINT, LB_S1, 2, 0);          // :496-498
+  add(TS_DOMSEP, LB_2phase, 0, 0);                                                               // :391
+  add(TS_GADGET_CHALLENGE, LB_z, 0, 0);                                                          // :393-408 (the label is the launch's)
+  cut[1] = n;
+  add(TS_POINT, LB_AI2, 0, 0); add(TS_POINT, LB_AO2, 1, 0); add(TS_POINT, LB_S2, 2, 0);          // :578-580
+  add(TS_CHALLENGE, LB_y, 0, 0); add(TS_CHALLENGE, LB_z, 1, 0);                                  // :584-585
+  cut[2] = n;
+  const uint8_t tl[5] = {LB_T1, LB_T3, LB_T4, LB_T5, LB_T6};
+  for (int j = 0; j < 5; j++) add(TS_POINT, tl[j], (uint32_t)j, 0);                              // :633-637
+  add(TS_CHALLENGE, LB_u, 2, 0); add(TS_CHALLENGE, LB_x, 3, 0);                                  // :639-640
+  cut[3] = n;
+  add(TS_SCALAR, LB_tx, 0, 0); add(TS_SCALAR, LB_txb, 1, 0); add(TS_SCALAR, LB_eb, 2, 0);        // :680-683
+  add(TS_CHALLENGE, LB_w, 4, 0);                                                                 // :686
+  add(TS_DOMSEP, LB_ipp, 0, 0); add(TS_U64, LB_n, 0, padded_n);                                  // inner_product_proof.rs:72
+  cut[4] = n;
+  return n;
+}
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
-                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges) {
+                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges, const uint8_t *gadget_label,
+                       Words8 *chi) {
   if (!nb || nsteps <= 0) return;
+  Label gl{{0, 0, 0, 0}};
+  if (gadget_label) for (int i = 0; i < 32; i++) gl.w[i >> 3] |= (uint64_t)gadget_label[i] << (8 * (i & 7));
   hipLaunchKernelGGL(k_prover_transcript, dim3((nb + 63) / 64), dim3(64), 0, st, nb, steps_dev, nsteps, states, points, pt_stride, scalars,
-                     sc_stride, challenges);
+                     sc_stride, challenges, gl, chi);
 }
 
 }  // namespace bpk

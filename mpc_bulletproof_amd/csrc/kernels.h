@@ -326,17 +326,24 @@ void ipp_round_tail(hipStream_t st, size_t nb, const JacRaw *sums, uint64_t *sta
 // up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator
 constexpr int PROVER_SCHEDULE_MAX = 24;
 int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4]);
+// ... and for a two-phase circuit with one gadget challenge (24 steps), in four slices: up to the gadget challenge | A_I2 A_O2 S2, y, z |
+// T points, u, x | the three scalars, w, the IPP separator
+int prover_transcript_schedule2(TrStep *out, size_t m, size_t padded_n, int cut[5]);
 // one slice for nb provers, a lane each; states: 4 x u64 per prover, updated.  A step's src indexes points (pt_stride per prover),
-// scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p]
+// scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p].  A TS_GADGET_CHALLENGE step draws under
+// gadget_label (32 bytes, zero-padded, host memory) into chi[p]
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
-                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges);
+                       size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges, const uint8_t *gadget_label = nullptr,
+                       Words8 *chi = nullptr);
 // rows[(5 p + j) * 2 ..] = (t, t_blinding) of T_1, T_3..T_6 over [B, B_blinding]; t: nb x 6, bl: nb x 8 (i o s blinding, tb1 tb3 tb4 tb5 tb6)
 void prove_fs_t_rows(hipStream_t st, size_t nb, const Words8 *t, const Words8 *bl, Words8 *rows);
 // out[p] = (t_x, t_x_blinding, e_blinding) from x, t, bl and tb2 = <wV, v_blinding>: summed by the proof's lane for m up to
 // PROVE_FS_DOT_LANE_MAX (tb2_pre = nullptr), above it taken from tb2_pre (nb values of sc_dot_batched, a block per proof)
 constexpr size_t PROVE_FS_DOT_LANE_MAX = 16;
+// two phases (u, bl1 non-null): bl's first three are the SECOND phase's blinding factors, bl1 (nb x 3) the first's, and
+// e_blinding = x ((i1 + u i2) + x ((o1 + u o2) + x (s1 + u s2)))
 void prove_fs_glue(hipStream_t st, size_t nb, size_t m, const Words8 *x, const Words8 *t, const Words8 *bl, const Words8 *wV, const Words8 *vb,
-                   const Words8 *tb2_pre, Words8 *out);
+                   const Words8 *tb2_pre, Words8 *out, const Words8 *u = nullptr, const Words8 *bl1 = nullptr);
 // proof assembly (layouts: k_prove_fs.hip): proof_points, proof_scalars, and the optional wire form, challenges and chain states
 struct ProveFsAssemble {
   size_t nb, k;
@@ -344,6 +351,7 @@ struct ProveFsAssemble {
   const uint64_t *states;
   Words8 *proof_points, *proof_scalars, *challenges_out, *states_out;
   uint8_t *wire;
+  const Words8 *A2 = nullptr;   // two phases: nb x 3 points A_I2 A_O2 S2 (nullptr: the identity, wire version 0)
 };
 void prove_fs_assemble(hipStream_t st, const ProveFsAssemble &a);
 

@@ -1458,7 +1458,7 @@ struct ProveBatch {
   const size_t nb;
   bpgpu_gens *gens = nullptr;
   size_t n1 = 0, m = 0, n = 0, padded_n = 0;
-  bool vkeys = false, fused = false;
+  bool vkeys = false, fused = false, fused2 = false;
   const ParametricCircuit *param = nullptr;
   bpgpu_circuit *circ = nullptr;
   std::vector<uint8_t> st_entry, chi_bytes;                      // (fused) the transcript states before "m"; the gadget challenges
@@ -1486,12 +1486,18 @@ struct ProveBatch {
     // (prove_fused); everything else, and the default, is the staged sequence
     fused = getenv("BPH_PROVE_FUSED") && !group && n1 >= 1 && !cs[0]->param;
     for (size_t p = 0; p < nb && fused; p++) fused = cs[p]->deferred.empty();
-    st_entry.resize(fused ? nb * 32 : 0);
+    // ... and provers bound to ONE ParametricCircuit with one challenge label and a second phase take the two calls around their
+    // gadget, bpgpu_r1cs_prove_fs2_begin / _finish (prove_fused2)
+    const ParametricCircuit *pc = cs[0]->param;
+    fused2 = getenv("BPH_PROVE_FUSED") && !group && pc && pc->challenge_labels().size() == 1 && pc->n() > pc->n1() && pc->n1() == n1 &&
+             pc->m() == m;
+    for (size_t p = 0; p < nb && fused2; p++) fused2 = cs[p]->param == pc;
+    st_entry.resize(fused || fused2 ? nb * 32 : 0);
     for (size_t p = 0; p < nb; p++) {
       CsCore *c = cs[p];
       if (c->a_L.size() != n1 || c->v.size() != m) throw std::invalid_argument("prove_batch: circuits differ in shape");
       if (rngs[p]->vector_keys() != vkeys) throw std::invalid_argument("prove_batch: the provers' Rngs differ in vector_keys()");
-      if (fused) memcpy(&st_entry[32 * p], c->tr.state(), 32);                             // the device appends "m" itself
+      if (fused || fused2) memcpy(&st_entry[32 * p], c->tr.state(), 32);                             // the device appends "m" itself
       c->tr.append_u64("m", c->v.size());                                                  // prover.rs:420
     }
     if (bp_gens.gens_capacity < n1) throw R1CSException(R1CSError::InvalidGeneratorsLength);   // :450-452
@@ -1603,6 +1609,56 @@ struct ProveBatch {
       cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up, as after bpgpu_ipp_run_fs
     }
     lap("prove: fused device call");
+  }
+
+  // BPH_PROVE_FUSED for a two-phase ParametricCircuit: the draws in the staged route's order (three, the vector or key; then three,
+  // the vector or key, five), the device transcript on both sides of the gadget, which still runs on the host transcript
+  void prove_fused2() {
+    param = cs[0]->param;
+    const std::string &label = param->challenge_labels()[0];
+    uint8_t lab[32] = {0};
+    memcpy(lab, label.data(), std::min<size_t>(label.size(), 32));
+    std::vector<uint8_t> in1(planes_size(n1, 3) + 1), com(nb * 3 * 64), chi(nb * 32);
+    const Planes p1 = draw_and_pack(0, n1, in1.data(), 3, i_b1, o_b1, s_b1);
+    circ = param->device_circuit();
+    int rc = bpgpu_r1cs_prove_fs2_begin(d.ctx(), gens, circ, nb, n1, st_entry.data(), lab, n1 ? p1.aL : nullptr, n1 ? p1.aR : nullptr,
+                                        n1 ? p1.aO : nullptr, vkeys || !n1 ? nullptr : p1.sL, vkeys || !n1 ? nullptr : p1.sR,
+                                        vkeys && n1 ? p1.key : nullptr, p1.bl, &ps.h, com.data(), chi.data(), nullptr);
+    if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
+    d.check(rc, "bpgpu_r1cs_prove_fs2_begin");
+    for (size_t p = 0; p < nb; p++) read_points(&com[p * 192], {&proofs[p].A_I1, &proofs[p].A_O1, &proofs[p].S1});
+    lap("prove: fused begin");
+    // the host transcript absorbs A_I1 A_O1 S1 and the gadgets draw their challenge from it: it must be the device's
+    randomize_constraints();
+    const size_t k = log2_exact(padded_n);
+    for (size_t p = 0; p < nb; p++) {
+      if (n != param->n() || cs[p]->chi_drawn.size() != 1 || cs[p]->rows_dropped != param->num_constraints())
+        throw std::invalid_argument("prove_batch: the gadgets built on a prover do not match its ParametricCircuit");
+      uint8_t mine[32];
+      cs[p]->chi_drawn[0].to_bytes_le(mine);
+      if (memcmp(mine, &chi[32 * p], 32)) throw std::logic_error("prove_batch: the device's gadget challenge is not the host transcript's");
+    }
+    std::vector<uint8_t> in2(planes_size(n - n1, 8) + nb * m * 32 + 1);
+    uint8_t *pvb = in2.data() + planes_size(n - n1, 8);
+    const Planes p2 = draw_and_pack(n1, n, in2.data(), 8, i_b2, o_b2, s_b2);
+    parallel_for(nb, [&](size_t p) { pack_range_ark(pvb + p * m * 32, cs[p]->v_blinding.data(), m); });
+    lap("prove: pack planes, draws");
+    const size_t nvar = 11 + 2 * k;
+    std::vector<uint8_t> pts(nb * nvar * 64), sc(nb * 5 * 32), st_out(nb * 32);
+    rc = bpgpu_r1cs_prove_fs2_finish(d.ctx(), gens, circ, &ps.h, p2.aL, p2.aR, p2.aO, vkeys ? nullptr : p2.sL, vkeys ? nullptr : p2.sR,
+                                     vkeys ? p2.key : nullptr, m ? pvb : nullptr, p2.bl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
+    d.check(rc, "bpgpu_r1cs_prove_fs2_finish");
+    for (size_t p = 0; p < nb; p++) {
+      R1CSProof &pr = proofs[p];
+      const uint8_t *pp = &pts[p * nvar * 64], *ps5 = &sc[p * 160];
+      read_points(pp, {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6});
+      append_points(pr.ipp_proof.L_vec, pp + 64 * 11, k);
+      append_points(pr.ipp_proof.R_vec, pp + 64 * (11 + k), k);
+      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
+      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
+      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up
+    }
+    lap("prove: fused finish");
   }
 
   // One phase of commitments, prover.rs:457-494 (lo = 0) / :519-565 (lo = n1): blinding factors, then A_I, A_O, S over
@@ -1798,6 +1854,7 @@ std::vector<R1CSProof> Prover::prove_batch(std::vector<Prover *> &provers, const
   for (size_t p = 0; p < nb; p++) cs[p] = provers[p]->c_.get();
   ProveBatch b(same_gpu(device), bp_gens, std::move(cs), rngs, group && group->size() > 1 ? group : nullptr);
   b.check_and_bind();                                                                     // prover.rs:420-452
+  if (b.fused2) { b.prove_fused2(); return std::move(b.proofs); }
   if (b.fused) { b.prove_fused(); return std::move(b.proofs); }
   b.commit_phase(0, b.n1, 1);                                                             // :457-494
   b.lap("prove: phase-1 commit");

@@ -520,6 +520,52 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_prove_fs_dev(self.ctx, gens, circuit, nb, d_states, d_a_L, d_a_R, d_a_O, d_s_L, d_s_R, d_vector_keys, d_v_blinding,
                                               d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out))
 
+    def r1cs_prove_fs2_begin(self, gens, circuit, nb, n1, states, gadget_label, blindings, a_L=None, a_R=None, a_O=None, s_L=None, s_R=None,
+                             vector_keys=None):
+        """The first of the two calls that prove nb provers of a two-phase circuit (include/bpgpu.h bpgpu_r1cs_prove_fs2_begin): the
+        phase-1 commitments over n1 multipliers and the device transcript up to the gadget's challenge.  Witness and blindings
+        (nb x 3) in ark-ff Montgomery form -> (session, A_I1 A_O1 S1 nb x 3 x 64 B, gadget challenges nb x 32 B, states nb x 32 B)"""
+        h = C.c_void_p()
+        com, chi, so = _out(64 * 3 * nb), _out(32 * nb), _out(32 * nb)
+        lab = (gadget_label + bytes(32))[:32]
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin(self.ctx, gens, circuit, nb, n1, opt(states), _buf(lab), opt(a_L), opt(a_R), opt(a_O), opt(s_L),
+                                                 opt(s_R), opt(vector_keys), opt(blindings), C.byref(h), com, chi, so))
+        return (h if h.value else None), bytes(com)[:64 * 3 * nb], bytes(chi)[:32 * nb], bytes(so)[:32 * nb]
+
+    def r1cs_prove_fs2_begin_dev(self, gens, circuit, nb, n1, d_states, gadget_label, d_blindings, d_a_L=None, d_a_R=None, d_a_O=None,
+                                 d_s_L=None, d_s_R=None, d_vector_keys=None, d_commitments=None, d_chi=None, d_states_out=None):
+        """the same on device pointers, asynchronous on the context's stream -> session; a malformed operand raises input_flag()"""
+        h = C.c_void_p()
+        lab = (gadget_label + bytes(32))[:32]
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin_dev(self.ctx, gens, circuit, nb, n1, d_states, _buf(lab), d_a_L, d_a_R, d_a_O, d_s_L, d_s_R,
+                                                     d_vector_keys, d_blindings, C.byref(h), d_commitments, d_chi, d_states_out))
+        return h if h.value else None
+
+    def r1cs_prove_fs2_finish(self, gens, circuit, session, nb, n, m, a_L, a_R, a_O, blindings, v_blinding=None, s_L=None, s_R=None,
+                              vector_keys=None, want_wire=True):
+        """The second call (bpgpu_r1cs_prove_fs2_finish): the phase-2 witness (nb x n2), blindings nb x 8, on a session of
+        r1cs_prove_fs2_begin for a circuit of n multipliers and m commitments -> (proof_points nb x (11 + 2k) x 64 B, proof_scalars
+        nb x 5 x 32 B, wire nb x proof_len or None, challenges nb x (5 + k) x 32 B, states_out nb x 32 B).  `session` (a c_void_p) is
+        cleared once the call has launched anything; after a refusal it stays open."""
+        k = max(n - 1, 0).bit_length()
+        nvar, plen = 11 + 2 * k, 1 + 14 * 32 + (2 * k + 2) * 32
+        pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
+        wire = _out(nb * plen) if want_wire else None
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_finish(self.ctx, gens, circuit, C.byref(session) if session is not None else None, opt(a_L), opt(a_R),
+                                                  opt(a_O), opt(s_L), opt(s_R), opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc,
+                                                  wire, ch, so))
+        return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
+                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
+
+    def r1cs_prove_fs2_finish_dev(self, gens, circuit, session, d_a_L, d_a_R, d_a_O, d_blindings, d_points, d_scalars, d_v_blinding=None,
+                                  d_s_L=None, d_s_R=None, d_vector_keys=None, d_wire=None, d_ch=None, d_states_out=None):
+        """the same on device pointers, asynchronous; may follow r1cs_prove_fs2_begin_dev without a sync()"""
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_finish_dev(self.ctx, gens, circuit, C.byref(session) if session is not None else None, d_a_L, d_a_R,
+                                                      d_a_O, d_s_L, d_s_R, d_vector_keys, d_v_blinding, d_blindings, d_points, d_scalars,
+                                                      d_wire, d_ch, d_states_out))
+
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
 
@@ -634,6 +680,21 @@ class BpGpu:
 
     def r1cs_verify_batch_wire_dev(self, gens, circuit, nb, n1, proof_len, d_proofs, d_commitments, d_init, d_ok):
         self._ck(_lib.bpgpu_r1cs_verify_batch_wire_dev(self.ctx, gens, circuit, nb, n1, proof_len, d_proofs, d_commitments, d_init, d_ok))
+
+    def r1cs_verify_batch_wire2(self, gens, circuit, nb, n1, proof_len, gadget_label, proofs, commitments, init_states):
+        """the same for a two-phase circuit (circuit_create_param, one gadget challenge drawn under gadget_label)"""
+        if len(proofs) != nb * proof_len or len(init_states) != 32 * nb:
+            raise BpGpuError(E_LEN, "r1cs_verify_batch_wire2: length mismatch")
+        ok = (C.c_int32 * max(nb, 1))()
+        lab = (gadget_label + bytes(32))[:32]
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2(self.ctx, gens, circuit, nb, n1, proof_len, _buf(lab), _buf(proofs), _buf(commitments),
+                                                    _buf(init_states), ok))
+        return list(ok)[:nb]
+
+    def r1cs_verify_batch_wire2_dev(self, gens, circuit, nb, n1, proof_len, gadget_label, d_proofs, d_commitments, d_init, d_ok):
+        lab = (gadget_label + bytes(32))[:32]
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2_dev(self.ctx, gens, circuit, nb, n1, proof_len, _buf(lab), d_proofs, d_commitments, d_init,
+                                                        d_ok))
 
     def r1cs_verify_combined(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, rho):
         nvar = 11 + m + 2 * k
