@@ -152,6 +152,24 @@ int bpgpu_msm_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const uint8_t *scalars,
  * instead of an error code.  For callers that keep points resident between MSMs. */
 int bpgpu_msm_batch_dev(bpgpu_ctx *ctx, size_t nb, size_t n, const void *scalars_dev, const void *points_dev,
                         void *out_dev);
+/* Diagnostic, no context and no device needed: the launch route that the bucket method (k_pip.hip: what bpgpu_msm,
+ * bpgpu_msm_batch(_dev), bpgpu_msm_ark and bpgpu_msm_shared run from BPGPU_OPT_PIPPENGER_MIN terms on, when the window-parallel
+ * launches do not take the call) chooses for nb instances of n terms.  The route depends on (nb, n) alone and never on the data; the
+ * library takes its own decisions from the same function, so the tests can assert which kernels a shape reaches.  Results never
+ * depend on the route.  out[BPGPU_PIP_PLAN_*]; BPGPU_E_ARG for nb == 0 or n < 2, BPGPU_E_LEN for a shape the 32-bit bucket ids
+ * cannot address (the MSM entry points return the same). */
+#define BPGPU_PIP_PLAN_C 0            /* window bits: 8..16 */
+#define BPGPU_PIP_PLAN_W 1            /* windows: 252 / c + 1 */
+#define BPGPU_PIP_PLAN_TWO_LEVEL 2    /* 1: LDS-staged two-level counting sort of the bucket ids, 0: one global atomic per entry */
+#define BPGPU_PIP_PLAN_TASK 3         /* entries of a bucket that one lane adds up: 16 or 64 */
+#define BPGPU_PIP_PLAN_TASK_SEARCH 4  /* task table: 1 = a lane per task and a binary search, 0 = a lane per bucket and a loop */
+#define BPGPU_PIP_PLAN_TASK_SORT 5    /* 1: the tasks are sorted by length before the bucket launch */
+#define BPGPU_PIP_PLAN_SCAN 6         /* launches of a scan over the bucket counts: 2 or 3 */
+#define BPGPU_PIP_PLAN_COARSE_SCAN 7  /* launches of the scan over the two-level sort's coarse histograms: 2 or 3; 0 without that sort */
+#define BPGPU_PIP_PLAN_FINAL_QUAD 8   /* Horner tail: 1 = a quad per instance, 0 = a wave per instance */
+#define BPGPU_PIP_PLAN_CHUNKS 9       /* blocks a window's running sum is cut into: 1..64 */
+#define BPGPU_PIP_PLAN_FIELDS 10
+int bpgpu_pippenger_plan(size_t nb, size_t n, int32_t out[BPGPU_PIP_PLAN_FIELDS]);
 /* sum of n points, no scalars (StarkPoint + StarkPoint): the local reduction of the <= 8 partial results that the GPUs of
  * a node all-gather after a term-range-sharded MSM or a combined batch check -- one launch instead of an
  * MSM with unit scalars (whose 252-doubling chain costs ~1 ms however few the terms). */

@@ -782,6 +782,22 @@ static bool pippenger_addressable(size_t nb, size_t n) {
   const size_t cW = 252 / (size_t)c + 1, chalf = (size_t)1 << (c - 1);
   return n < ((size_t)1 << 31) / nb && nb * cW * chalf < ((size_t)1 << 31) && nb * n * cW < ((size_t)1 << 32);
 }
+int bpgpu_pippenger_plan(size_t nb, size_t n, int32_t out[BPGPU_PIP_PLAN_FIELDS]) {
+  if (!out || !nb || n < 2) return BPGPU_E_ARG;
+  if (!pippenger_addressable(nb, n)) return BPGPU_E_LEN;
+  const PipPlan q = pippenger_plan(nb, n, pippenger_window(n));
+  out[BPGPU_PIP_PLAN_C] = q.c;
+  out[BPGPU_PIP_PLAN_W] = q.W;
+  out[BPGPU_PIP_PLAN_TWO_LEVEL] = q.two_level;
+  out[BPGPU_PIP_PLAN_TASK] = (int32_t)q.task;
+  out[BPGPU_PIP_PLAN_TASK_SEARCH] = q.task_search;
+  out[BPGPU_PIP_PLAN_TASK_SORT] = q.sort_tasks;
+  out[BPGPU_PIP_PLAN_SCAN] = q.scan_launches;
+  out[BPGPU_PIP_PLAN_COARSE_SCAN] = q.coarse_scan_launches;
+  out[BPGPU_PIP_PLAN_FINAL_QUAD] = q.final_quad;
+  out[BPGPU_PIP_PLAN_CHUNKS] = q.window_chunks;
+  return BPGPU_OK;
+}
 // one Straus lane per term of dense instances: term i reads pts[i], sc[i]
 static StrausArgs straus_dense(const AffDev *pts, const uint32_t *sc) {
   StrausArgs a{};

@@ -137,10 +137,12 @@ __global__ void __launch_bounds__(256) k_pip_scan_apply2(const uint32_t *counts,
   }
   if (blockIdx.x + 1 == ntiles && threadIdx.x == 255) offsets[nb] = tile_off + sm[255];   // the total
 }
-static void pip_scan(hipStream_t st, const uint32_t *counts, uint32_t *offsets, uint32_t *cursor, size_t nb, uint32_t *tile_tmp) {
+// launches a scan of nb counts takes (PipPlan): every block adds up the tile sums before its own while they are few
+static int pip_scan_launches(size_t nb) { return (nb + SCAN_TILE - 1) / SCAN_TILE <= 4096 ? 2 : 3; }
+static void pip_scan(hipStream_t st, const uint32_t *counts, uint32_t *offsets, uint32_t *cursor, size_t nb, uint32_t *tile_tmp, int launches) {
   size_t ntiles = (nb + SCAN_TILE - 1) / SCAN_TILE;
   hipLaunchKernelGGL(k_pip_scan_tiles, dim3(ntiles), dim3(256), 0, st, counts, nb, tile_tmp);
-  if (ntiles <= 4096) {
+  if (launches == 2) {
     hipLaunchKernelGGL(k_pip_scan_apply2, dim3(ntiles), dim3(256), 0, st, counts, tile_tmp, nb, ntiles, offsets, cursor);
     return;
   }
@@ -643,12 +645,41 @@ static bool pip_two_level(size_t ninst, size_t n, int c) {
   return c >= 12 && c <= 16 && n >= ((size_t)1 << 15);
 }
 static size_t pip_max_tasks(size_t n, size_t W, size_t nbk) { return n * W / PIP_TASK + nbk + 1; }
+PipPlan pippenger_plan(size_t ninst, size_t n, int c) {
+  PipPlan q{};
+  q.c = c; q.W = 252 / c + 1; q.half = 1 << (c - 1);
+  const size_t W = q.W;
+  q.nbk = ninst * W * (size_t)q.half;
+  q.tot = ninst * n;
+  q.max_tasks = pip_max_tasks(q.tot, W, q.nbk);
+  const int top_bits = 252 - c * (q.W - 1);                 // top digits are in [0, 2^top_bits]
+  q.two_level = pip_two_level(ninst, n, c);
+  if (q.two_level) {
+    q.shift = c - 1 - 8;
+    q.shift_top = top_bits > 8 ? top_bits - 8 : 0;
+    q.tiles = (n + RS_TILE - 1) / RS_TILE;
+    q.ngh = ninst * W * RS_BINS * q.tiles;
+    q.coarse_scan_launches = pip_scan_launches(q.ngh);
+  }
+  // entries per task: a few dozen points per regular bucket AND enough buckets to fill the chip with one lane each (4 waves per
+  // SIMD) -> a bucket is one task, no merge pass for it.  (2^17 terms, 82 k buckets: long tasks leave one wave per SIMD -- 0.92
+  // against 0.83 ms -- so the 16-entry tasks stay there.)
+  q.task = n / (size_t)q.half >= 12 && q.nbk >= ((size_t)1 << 18) ? PIP_TASK_MAX : PIP_TASK;
+  q.task_search = (n >> top_bits) / q.task > 64;            // tasks per top bucket (uniform scalars: n / 2^top_bits entries each)
+  q.sort_tasks = q.tot * W >= ((size_t)1 << 18);            // two short launches: worth it from ~16 k tasks on
+  q.scan_launches = pip_scan_launches(q.nbk);
+  q.window_ab = q.half >= 64;
+  q.window_chunks = q.window_ab ? pip_window_ab_chunks(q.half) : pip_window_chunks(q.half, ninst, q.W);
+  q.final_quad = ninst > 1536;
+  return q;
+}
 size_t pippenger_scratch_bytes_batch(size_t ninst, size_t n, int c) {
-  size_t W = 252 / c + 1, half = (size_t)1 << (c - 1), nbk = ninst * W * half, tot = ninst * n, mt = pip_max_tasks(tot, W, nbk);
+  const PipPlan q = pippenger_plan(ninst, n, c);
+  size_t W = q.W, nbk = q.nbk, tot = q.tot, mt = q.max_tasks;
   size_t base = al(tot * W * 4) * 2 + al((nbk + 1) * 4) * 5 + al(mt * 4) + al(mt * sizeof(JacRaw)) + al(nbk * sizeof(JacRaw)) +
                 al(ninst * W * sizeof(JacRaw)) * 129 + al(mt / PIP_HEAVY * 4 + 8) + al((nbk / SCAN_TILE + 2) * 4) + al(mt * 4) + al(1280);
-  if (pip_two_level(ninst, n, c)) {
-    size_t ngh = ninst * W * RS_BINS * ((n + RS_TILE - 1) / RS_TILE);
+  if (q.two_level) {
+    size_t ngh = q.ngh;
     base += al((ngh + 1) * 4) * 2 + al((ngh / SCAN_TILE + 2) * 4) + al(tot * W * 4) + al(tot * W);
   }
   return base;
@@ -658,11 +689,12 @@ size_t pippenger_scratch_bytes(size_t n, int c) { return pippenger_scratch_bytes
 void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars, size_t ninst, size_t n, int c, JacRaw *out,
                      size_t out_stride, void *scratch) {
   if (!ninst) return;
+  const PipPlan q = pippenger_plan(ninst, n, c);
   PipParams pp;
-  pp.c = c; pp.W = 252 / c + 1; pp.half = 1 << (c - 1);
+  pp.c = q.c; pp.W = q.W; pp.half = q.half;
   for (int j = 0; j < 9; j++) pp.K[j] = 0;
   for (int w = 0; w < pp.W; w++) { int bit = c * w + c - 1; pp.K[bit >> 5] |= 1u << (bit & 31); }
-  size_t W = pp.W, nbk = ninst * W * (size_t)pp.half, tot = ninst * n;
+  size_t W = pp.W, nbk = q.nbk, tot = q.tot;
   uint8_t *p = (uint8_t *)scratch;
   uint32_t *keys = (uint32_t *)p; p += al(tot * W * 4);
   uint32_t *sorted = (uint32_t *)p; p += al(tot * W * 4);
@@ -672,7 +704,7 @@ void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars,
   uint32_t *cursor = (uint32_t *)p; p += al((nbk + 1) * 4);
   uint32_t *tcount = (uint32_t *)p; p += al((nbk + 1) * 4);
   uint32_t *toffsets = (uint32_t *)p; p += al((nbk + 1) * 4);
-  const size_t mt = pip_max_tasks(tot, W, nbk);
+  const size_t mt = q.max_tasks;
   uint32_t *task_bucket = (uint32_t *)p; p += al(mt * 4);
   JacRaw *partial = (JacRaw *)p; p += al(mt * sizeof(JacRaw));
   JacRaw *buckets = (JacRaw *)p; p += al(nbk * sizeof(JacRaw));
@@ -684,15 +716,12 @@ void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars,
   uint32_t *tl_hist = zblk;                                                      // [0, TL_CLASSES) histogram, [TL_CURSOR, ..) cursors (1 024 bytes)
   uint32_t *heavy_cnt = zblk + 256;                                              // count of heavy buckets (heavy[2..] = their ids)
   (void)hipMemsetAsync(counts, 0, al((nbk + 1) * 4) + 1280, st);   // bucket counts (the top windows' buckets beyond 2^top_bits are written by nobody), task-length histogram, heavy count
-  // entries per task: a few dozen points per regular bucket AND enough buckets to fill the chip with one lane each (4 waves per
-  // SIMD) -> a bucket is one task, no merge pass for it.  (2^17 terms, 82 k buckets: long tasks leave one wave per SIMD -- 0.92
-  // against 0.83 ms -- so the 16-entry tasks stay there.)
-  const uint32_t task = n / (size_t)pp.half >= 12 && nbk >= ((size_t)1 << 18) ? PIP_TASK_MAX : PIP_TASK;
-  if (pip_two_level(ninst, n, c)) {
+  const uint32_t task = q.task;
+  if (q.two_level) {
     // LDS-staged two-level counting sort: digits (no atomics) -> coarse histograms per tile -> scan -> coarse scatter ->
     // per-(segment, bin) fine sort, which also produces the bucket counts
-    const int shift = c - 1 - 8, top_bits = 252 - c * (pp.W - 1), shift_top = top_bits > 8 ? top_bits - 8 : 0;   // top digits are in [0, 2^top_bits]
-    const size_t nseg = ninst * W, tiles = (n + RS_TILE - 1) / RS_TILE, ngh = nseg * RS_BINS * tiles;
+    const int shift = q.shift, shift_top = q.shift_top;
+    const size_t nseg = ninst * W, tiles = q.tiles, ngh = q.ngh;
     uint32_t *gh = (uint32_t *)p; p += al((ngh + 1) * 4);
     uint32_t *goff = (uint32_t *)p; p += al((ngh + 1) * 4);
     uint32_t *gtile = (uint32_t *)p; p += al((ngh / SCAN_TILE + 2) * 4);
@@ -700,25 +729,21 @@ void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars,
     uint8_t *cfine = p; p += al(tot * W);
     hipLaunchKernelGGL(k_pip_digits, dim3((tot + 255) / 256), dim3(256), 0, st, pp, scalars, n, ninst, keys, (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_pip_coarse_hist, dim3(tiles, nseg), dim3(RS_TPB), 0, st, keys, n, pp.W, pp.half, shift, shift_top, tiles, gh);
-    pip_scan(st, gh, goff, nullptr, ngh, gtile);
+    pip_scan(st, gh, goff, nullptr, ngh, gtile, q.coarse_scan_launches);
     hipLaunchKernelGGL(k_pip_coarse_scatter, dim3(tiles, nseg), dim3(RS_TPB), 0, st, keys, n, pp.W, pp.half, shift, shift_top, tiles, goff, cval, cfine);
     hipLaunchKernelGGL(k_pip_fine_sort, dim3(RS_BINS, nseg), dim3(RS_TPB), 0, st, goff, tiles, nseg, pp.W, pp.half, shift, shift_top, cval, cfine, counts, sorted);
-    pip_scan(st, counts, offsets, nullptr, nbk, tile_tmp);
+    pip_scan(st, counts, offsets, nullptr, nbk, tile_tmp, q.scan_launches);
   } else {
     if (tot) hipLaunchKernelGGL(k_pip_digits, dim3((tot + 255) / 256), dim3(256), 0, st, pp, scalars, n, ninst, keys, counts);
-    pip_scan(st, counts, offsets, cursor, nbk, tile_tmp);
+    pip_scan(st, counts, offsets, cursor, nbk, tile_tmp, q.scan_launches);
     if (tot) hipLaunchKernelGGL(k_pip_scatter, dim3((tot * W + 255) / 256), dim3(256), 0, st, pp, keys, n, ninst, cursor, sorted);
   }
   hipLaunchKernelGGL(k_pip_taskcount, dim3((nbk + 255) / 256), dim3(256), 0, st, counts, tcount, nbk, task);
-  pip_scan(st, tcount, toffsets, nullptr, nbk, tile_tmp);
-  {
-    const int top_bits = 252 - c * (pp.W - 1);
-    const size_t tasks_per_top_bucket = (n >> top_bits) / task;     // uniform scalars: n / 2^top_bits entries per top bucket
-    if (tasks_per_top_bucket > 64) hipLaunchKernelGGL(k_pip_taskdesc_search, dim3((mt + 255) / 256), dim3(256), 0, st, toffsets, nbk, task_bucket);
-    else hipLaunchKernelGGL(k_pip_taskdesc, dim3((nbk + 255) / 256), dim3(256), 0, st, toffsets, nbk, task_bucket);
-  }
+  pip_scan(st, tcount, toffsets, nullptr, nbk, tile_tmp, q.scan_launches);
+  if (q.task_search) hipLaunchKernelGGL(k_pip_taskdesc_search, dim3((mt + 255) / 256), dim3(256), 0, st, toffsets, nbk, task_bucket);
+  else hipLaunchKernelGGL(k_pip_taskdesc, dim3((nbk + 255) / 256), dim3(256), 0, st, toffsets, nbk, task_bucket);
   // the task count is data dependent: launch the upper bound, excess lanes exit on the device-side count
-  const bool sort_tasks = tot * W >= ((size_t)1 << 18);     // two short launches: worth it from ~16 k tasks on
+  const bool sort_tasks = q.sort_tasks;
   if (sort_tasks) {
     hipLaunchKernelGGL(k_pip_tasklen_hist, dim3((mt + TL_TILE - 1) / TL_TILE), dim3(TL_TPB), 0, st, offsets, toffsets, task_bucket, nbk, tl_hist, task);
     hipLaunchKernelGGL(k_pip_task_scatter, dim3((mt + TL_TILE - 1) / TL_TILE), dim3(TL_TPB), 0, st, offsets, toffsets, task_bucket, nbk,
@@ -728,12 +753,11 @@ void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars,
                      nbk, sort_tasks ? task_perm : (const uint32_t *)nullptr, partial, task, buckets);
   hipLaunchKernelGGL(k_pip_merge, dim3((nbk + 63) / 64), dim3(64), 0, st, toffsets, partial, nbk, buckets, heavy + 2, heavy_cnt);
   hipLaunchKernelGGL(k_pip_merge_heavy, dim3(mt / PIP_HEAVY + 1), dim3(PH_TPB), 0, st, toffsets, partial, heavy + 2, heavy_cnt, buckets);
-  if (pp.half >= 64) {
-    const int chunks = pip_window_ab_chunks(pp.half);
+  const int chunks = q.window_chunks;
+  if (q.window_ab) {
     hipLaunchKernelGGL(k_pip_window_a, dim3(pp.W, ninst, chunks), dim3(64), 0, st, pp, buckets, win_part, chunks);
     hipLaunchKernelGGL(k_pip_window_b, dim3(ninst * W), dim3(256), 0, st, pp, win_part, win, chunks);
   } else {
-    const int chunks = pip_window_chunks(pp.half, ninst, pp.W);
     if (chunks > 1) {
       hipLaunchKernelGGL(k_pip_window, dim3(pp.W, ninst, chunks), dim3(PW_TPB), 0, st, pp, buckets, win_part, chunks);
       segmented_sum(st, win_part, win, ninst * W, chunks);
@@ -741,7 +765,7 @@ void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars,
       hipLaunchKernelGGL(k_pip_window, dim3(pp.W, ninst, 1), dim3(PW_TPB), 0, st, pp, buckets, win, 1);
     }
   }
-  if (ninst <= 1536) hipLaunchKernelGGL(k_pip_final_row, dim3((unsigned)ninst), dim3(64), 0, st, win, pp.W, pp.c, out, out_stride);
+  if (!q.final_quad) hipLaunchKernelGGL(k_pip_final_row, dim3((unsigned)ninst), dim3(64), 0, st, win, pp.W, pp.c, out, out_stride);
   else hipLaunchKernelGGL(k_pip_final, dim3((ninst * 4 + 63) / 64), dim3(64), 0, st, win, pp.W, pp.c, ninst, out, out_stride);
 }
 void pippenger(hipStream_t st, const AffDev *pts, const uint32_t *scalars, size_t n, int c, JacRaw *out, void *scratch) {

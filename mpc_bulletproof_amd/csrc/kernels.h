@@ -102,6 +102,24 @@ void pippenger(hipStream_t st, const AffDev *pts, const uint32_t *scalars, size_
 size_t pippenger_scratch_bytes_batch(size_t ninst, size_t n, int c);
 void pippenger_batch(hipStream_t st, const AffDev *pts, const uint32_t *scalars, size_t ninst, size_t n, int c, JacRaw *out,
                      size_t out_stride, void *scratch);
+// The launch route of pippenger_batch(ninst, n, c): EVERY decision between two launch chains is taken here, once, on the host, from
+// the shape alone; pippenger_batch and pippenger_scratch_bytes_batch read it, and bpgpu_pippenger_plan shows it to the tests.
+struct PipPlan {
+  int c, W, half;               // window bits, windows, buckets per window
+  bool two_level;               // LDS-staged two-level counting sort (k_pip_coarse_* + k_pip_fine_sort) | atomic scatter (k_pip_scatter)
+  int shift, shift_top;         // two-level: fine bits of the bucket id in the regular windows and in the top one
+  size_t tiles, ngh;            // two-level: key tiles per segment, coarse-histogram entries
+  int coarse_scan_launches;     // two-level: launches of the scan of the coarse histograms (2 | 3); 0 without that sort
+  uint32_t task;                // entries per task of k_pip_bucket_bounded (PIP_TASK | PIP_TASK_MAX)
+  bool task_search;             // task table by a lane per task with a binary search (k_pip_taskdesc_search) | by a loop per bucket
+  bool sort_tasks;              // tasks sorted by length before the bucket launch
+  int scan_launches;            // launches of a scan over the nbk bucket (and task) counts: 2 | 3
+  bool window_ab;               // window sums by k_pip_window_a + _b | by k_pip_window (fewer than 64 buckets per window: no c in [8, 16])
+  int window_chunks;            // blocks a window's running sum is cut into
+  bool final_quad;              // Horner tail with a quad per instance (k_pip_final) | a wave per instance (k_pip_final_row)
+  size_t nbk, tot, max_tasks;   // buckets, terms, upper bound of the task count
+};
+PipPlan pippenger_plan(size_t ninst, size_t n, int c);
 // ---- k_pip2.hip: ONE mid-size instance in six launches (+ a front launch from boundary bytes); 2^8 <= n <= 2^18
 int pippenger2_window(size_t n);
 bool pippenger2_supported(size_t n);

@@ -92,6 +92,19 @@ def device_count():
     return _lib.bpgpu_device_count()
 
 
+# bpgpu_pippenger_plan (include/bpgpu.h BPGPU_PIP_PLAN_*)
+PIP_PLAN_FIELDS = ("c", "W", "two_level", "task", "task_search", "task_sort", "scan", "coarse_scan", "final_quad", "chunks")
+
+
+def pippenger_plan(nb, n):
+    """the launch route of the bucket-method MSM for nb instances of n terms, as a dict over PIP_PLAN_FIELDS (needs no device)"""
+    out = (C.c_int32 * len(PIP_PLAN_FIELDS))()
+    rc = _lib.bpgpu_pippenger_plan(nb, n, out)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return dict(zip(PIP_PLAN_FIELDS, out))
+
+
 class BpGpu:
     """One context on one device.  All byte encodings as in include/bpgpu.h."""
 

@@ -4,6 +4,7 @@ import pytest
 
 import bp_helpers as bh
 import oracle_lib as o
+import pip_shapes
 
 pytestmark = pytest.mark.gpu
 H = bytes.fromhex
@@ -1350,12 +1351,13 @@ def test_msm_pippenger_sizes(gpu, opts, n, route):
         assert got == o.msm(sc, Gp, 2)
 
 
-def test_msm_pippenger_two_level_sort_edge_cases(gpu):
-    """n >= 2^15 takes the LDS-staged two-level counting sort (coarse bins per tile, fine sort per bin): skewed and
-    degenerate key distributions -- all scalars equal (one bucket per window holds everything), 0 / 1 / n-1 scalars,
-    bit-valued scalars, identity points, duplicate and opposite points, a ragged last tile -- against the oracle-free
-    identity MSM(s_i, k_i G) = (sum s_i k_i) G."""
-    n = 40000 + 37                                                  # not a multiple of the 2048-key tile
+def test_msm_pippenger_atomic_scatter_skewed_battery(gpu):
+    """40 037 terms get c = 11 and with it the ATOMIC-SCATTER sort (k_pip_scatter; the two-level sort needs c >= 12, which no
+    size below ~58 432 terms gets -- this test once carried its name; test_msm_pippenger_route_c13_two_level_battery runs the
+    same battery there).  Skewed and degenerate key distributions -- all scalars equal (one bucket per window holds
+    everything: heavy merge), 0 / 1 / n-1 scalars, bit-valued scalars, identity points, duplicate and opposite points --
+    against the oracle-free identity MSM(s_i, k_i G) = (sum s_i k_i) G."""
+    _, n = pip_shapes.assert_plan("skewed40037")                    # 40 000 + 37: c = 11, atomic scatter, 16-entry tasks, sorted
     Gp, Gd = o.gens("G", n, dlogs=True)
     G = o.generator()
     ks = o.unscalars(Gd)
@@ -1386,9 +1388,10 @@ def test_msm_pippenger_two_level_sort_edge_cases(gpu):
     check(sc, bytes(pts), dl)
 
 
-def test_msm_batch_pippenger_two_level(gpu):
-    """two instances of 33 000 terms each through the batched entry point (segments = instance x window)"""
-    nb, n = 2, 33000
+def test_msm_batch_pippenger_atomic_scatter_c11(gpu):
+    """two instances of 33 000 terms each through the batched entry point (bucket ids carry the instance): c = 11, so the
+    atomic-scatter sort, not the two-level one this test was once named for (test_msm_pippenger_route_two_level_batch is)"""
+    nb, n = pip_shapes.assert_plan("batch33000")
     Gp, Gd = o.gens("H", n, dlogs=True)
     sc = o.random_scalars(78, nb * n)
     got = gpu.msm_batch(nb, n, sc, Gp * nb)
@@ -1401,6 +1404,257 @@ def test_msm_batch_pippenger(gpu):
     Gp = o.gens("H", n)
     sc = o.random_scalars(77, nb * n)
     assert gpu.msm_batch(nb, n, sc, Gp * nb) == o.msm_batch(sc, Gp * nb, nb, n)
+
+
+# ------------------------------------------------------------------ bucket method: every sort, task and window route
+# tests/pip_shapes.py lists the shapes (A..I) with the route each is aimed at; every test asserts that route first
+# (pip_shapes.assert_plan, bpgpu_pippenger_plan) and then compares bytes with MSM(s_i, k_i G) = (sum s_i k_i) G.  The points are
+# one set of 8 192 k_i G repeated to length -- duplicates are everywhere, so equal scalars also put equal points into one task --
+# with identity points, adjacent duplicates and P / -P pairs patched in.
+@pytest.fixture(scope="module")
+def pip_base():
+    return o.gens("G", 8192, dlogs=True)
+
+
+def _rows(b, width):
+    """a writable n x width byte matrix over a copy of b"""
+    import numpy as np
+    return np.frombuffer(bytearray(b), dtype=np.uint8).reshape(-1, width)
+
+
+def _row(b):
+    import numpy as np
+    return np.frombuffer(b, dtype=np.uint8)
+
+
+def _pip_points(base, n):
+    """-> (n points, their discrete logarithms): the base set repeated, every 13th point the identity, a duplicate of its
+    neighbour behind every 101st and the opposite of its neighbour behind every 211th"""
+    import numpy as np
+    Gp, Gd = base
+    reps = -(-n // (len(Gp) // 64))
+    pts, dl = _rows((Gp * reps)[:64 * n], 64), _rows((Gd * reps)[:32 * n], 32)
+    pts[0::13] = 0
+    dl[0::13] = 0
+    idx = np.arange(5, n - 1, 101)
+    pts[idx + 1], dl[idx + 1] = pts[idx], dl[idx]
+    for i in range(7, n - 1, 211):
+        p = pts[i].tobytes()
+        if p != bytes(64):
+            p = p[:32] + (o.P - int.from_bytes(p[32:], "little")).to_bytes(32, "little")
+        pts[i + 1], dl[i + 1] = _row(p), _row(o.s2b(N - o.b2s(dl[i].tobytes())))
+    return pts.tobytes(), dl.tobytes()
+
+
+def _pip_want(sc, dl):
+    return o.point_mul(o.inner_product(sc, dl), o.generator())
+
+
+def _sc_mix(seed, n):
+    """0, 1, N - 1, 2, N - 2 and a random scalar in turn"""
+    rows = _rows(o.random_scalars(seed, n), 32)
+    for k, v in enumerate((0, 1, N - 1, 2, N - 2)):
+        rows[k::6] = _row(o.s2b(v))
+    return rows.tobytes()
+
+
+def _sc_equal(seed, n):
+    return o.random_scalars(seed, 1) * n
+
+
+def _sc_bits(n):
+    return ((bytes(32) + o.s2b(1)) * (n // 2 + 1))[:32 * n]
+
+
+def _sc_small(seed, n):
+    """random scalars shifted right by 200 bits: the upper windows are empty"""
+    rows = _rows(o.random_scalars(seed, n), 32)
+    rows[:, :7] = rows[:, 25:]
+    rows[:, 7:] = 0
+    return rows.tobytes()
+
+
+def _sc_runs(seed, n):
+    """two runs of equal scalars, a run of 0 / 1 / N - 1 in turn, and random scalars"""
+    rows = _rows(o.random_scalars(seed, n), 32)
+    q = n // 4
+    rows[1:q] = rows[0]
+    rows[q + 1:2 * q] = rows[q]
+    for k, v in enumerate((0, 1, N - 1)):
+        rows[2 * q + k:3 * q:3] = _row(o.s2b(v))
+    return rows.tobytes()
+
+
+def _msm_resident(gpu, nb, n, sc, pts):
+    """bpgpu_msm_batch_dev: operands and result in device memory"""
+    d_sc, d_pts, d_out = gpu.to_device(sc), gpu.to_device(pts), gpu.malloc(64 * nb)
+    try:
+        gpu.msm_batch_dev(nb, n, d_sc, d_pts, d_out)
+        out = gpu.download(d_out, 64 * nb)
+        assert gpu.input_flag() == 0
+        return out
+    finally:
+        for d in (d_sc, d_pts, d_out):
+            gpu.free(d)
+
+
+def test_msm_pippenger_route_c10(gpu, opts, pip_base):
+    """A: 6 000 terms, c = 10 (512 buckets per window in two chunks), tasks unsorted, task table by search"""
+    _, n = pip_shapes.assert_plan("A")
+    opts(msm_wp_max=0)
+    pts, dl = _pip_points(pip_base, n)
+    for sc in (o.random_scalars(6001, n), _sc_mix(6002, n)):
+        assert gpu.msm(sc, pts) == _pip_want(sc, dl)
+
+
+def test_msm_pippenger_route_64_entry_tasks_c8(gpu, opts, pip_base):
+    """B: 64 x 1 536 terms, the fewest at which a call gets 64-entry tasks (n / 128 buckets = 12, 2^18 buckets in all): sorted
+    tasks, atomic scatter.  Instances in turn: random; all scalars equal (one bucket per window holds 1 536 entries: 24
+    partials, the heavy merge); all zero (every task empty, the result is the identity); bits; the 0 / 1 / N - 1 / 2 / N - 2 mix.
+    Host buffers and resident operands."""
+    nb, n = pip_shapes.assert_plan("B")
+    opts(msm_wp_max=0)
+    pts, dl = _pip_points(pip_base, nb * n)
+    kinds = [lambda b: o.random_scalars(700 + b, n), lambda b: _sc_equal(800 + b, n), lambda b: bytes(32 * n),
+             lambda b: _sc_bits(n), lambda b: _sc_mix(900 + b, n)]
+    sc = b"".join(kinds[b % 5](b) for b in range(nb))
+    want = b"".join(_pip_want(sc[32 * n * b:32 * n * (b + 1)], dl[32 * n * b:32 * n * (b + 1)]) for b in range(nb))
+    assert want[64 * 2:64 * 3] == bytes(64) and want[:64] != bytes(64)
+    assert gpu.msm_batch(nb, n, sc, pts) == want
+    assert _msm_resident(gpu, nb, n, sc, pts) == want
+
+
+def test_msm_pippenger_route_c13_two_level_battery(gpu, opts, pip_base):
+    """C: 58 437 terms (7 tiles of 8 192 keys and one of 1 093), c = 13: the two-level sort with 16-entry tasks.  The battery of
+    test_msm_pippenger_atomic_scatter_skewed_battery -- all equal (a coarse bin of 58 437 entries: the unstaged fine sort, heavy
+    merge), bits, the mix, small scalars, random -- over points with identities, duplicates and opposite pairs; and one vector
+    on the edge of the fine sort's LDS stage (FS_CAP = 6 144 entries): a scalar s in 1..4 095 has window-0 digit s and coarse bin
+    (s - 1) >> 4, so 6 144 terms with s in [1, 16] fill bin 0 exactly (staged), 6 145 terms with s in [17, 32] put bin 1 one
+    over (unstaged), and every other term, its low 13 bits cleared, adds nothing to that window."""
+    import numpy as np
+    _, n = pip_shapes.assert_plan("C")
+    opts(msm_wp_max=0)
+    pts, dl = _pip_points(pip_base, n)
+    for sc in (_sc_equal(31337, n), _sc_bits(n), _sc_mix(31338, n), _sc_small(31339, n), o.random_scalars(31340, n)):
+        assert gpu.msm(sc, pts) == _pip_want(sc, dl)
+    rows = _rows(o.random_scalars(31341, n), 32)
+    rows[:, 0] = 0
+    rows[:, 1] &= 0xE0
+    for idx, first in ((np.arange(6144) * 4, 1), (np.arange(6145) * 4 + 1, 17)):      # spread over the first three tiles
+        rows[idx] = 0
+        rows[idx, 0] = first + np.arange(len(idx)) % 16
+    sc = rows.tobytes()
+    vals = o.unscalars(sc)
+    assert sum(1 for v in vals if 1 <= v & 0x1FFF <= 16) == 6144 and sum(1 for v in vals if 17 <= v & 0x1FFF <= 32) == 6145
+    assert all(v & 0x1FFF == 0 or v <= 32 for v in vals)
+    assert gpu.msm(sc, pts) == _pip_want(sc, dl)
+
+
+def test_msm_pippenger_route_two_level_batch(gpu, opts, pip_base):
+    """D: 4 x 58 437 terms: the two-level sort over several instances (segment = instance x window) and 64-entry tasks at
+    c = 13 (327 680 buckets).  Instance 0 random, 1 all equal, 2 bits, 3 the mix."""
+    nb, n = pip_shapes.assert_plan("D")
+    opts(msm_wp_max=0)
+    pts, dl = _pip_points(pip_base, nb * n)
+    sc = o.random_scalars(4001, n) + _sc_equal(4002, n) + _sc_bits(n) + _sc_mix(4003, n)
+    want = b"".join(_pip_want(sc[32 * n * b:32 * n * (b + 1)], dl[32 * n * b:32 * n * (b + 1)]) for b in range(nb))
+    assert gpu.msm_batch(nb, n, sc, pts) == want
+
+
+def test_msm_pippenger_route_c15(gpu, opts, pip_base):
+    """E: 196 700 terms, c = 15: 64 fine buckets per coarse bin (shift 6), the top window's own shift of 4, 64-entry tasks,
+    64 window chunks.  Random scalars through the default route and with the window-parallel launches switched off (both
+    are k_pip.hip at this size); runs of equal scalars, 0 / 1 / N - 1 and random in one vector."""
+    _, n = pip_shapes.assert_plan("E")
+    pts, dl = _pip_points(pip_base, n)
+    sc = o.random_scalars(15001, n)
+    want = _pip_want(sc, dl)
+    assert gpu.msm(sc, pts) == want
+    opts(msm_wp_max=0)
+    assert gpu.msm(sc, pts) == want
+    sc = _sc_runs(15002, n)
+    assert gpu.msm(sc, pts) == _pip_want(sc, dl)
+
+
+def test_msm_pippenger_route_c16(gpu, opts, pip_base):
+    """F: 737 400 terms, c = 16: 128 fine buckets per coarse bin (shift 7, the whole h[128] of k_pip_fine_sort) and the cap of
+    64 window chunks (8 buckets per lane).  Vectors as E; the random one also with resident operands."""
+    _, n = pip_shapes.assert_plan("F")
+    opts(msm_wp_max=0)
+    pts, dl = _pip_points(pip_base, n)
+    sc = o.random_scalars(16001, n)
+    want = _pip_want(sc, dl)
+    assert gpu.msm(sc, pts) == want
+    assert _msm_resident(gpu, 1, n, sc, pts) == want
+    sc = _sc_runs(16002, n)
+    assert gpu.msm(sc, pts) == _pip_want(sc, dl)
+
+
+def _own_context_msm_batch(nb, n, sc, pts, **options):
+    """one call in a context of its own, destroyed afterwards: the module's shared context does not keep the workspace"""
+    import mpc_bulletproof_amd as m
+    g = m.BpGpu(0)
+    try:
+        for k, v in options.items():
+            g.set_option(k, v)
+        return g.msm_batch(nb, n, sc, pts)
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("nb", [1536, 1537, 2049])
+def test_msm_pippenger_route_many_instances(pip_base, nb):
+    """G: nb x 16 terms with pippenger_min = 2.  1 536 instances: the last count whose Horner tail runs a wave per instance;
+    1 537: the first with a quad per instance (k_pip_final); 2 049: 8 392 704 buckets, more than 4 096 scan tiles, so the bucket
+    and task scans take three launches (k_pip_scan_top + k_pip_scan_apply).  Random scalars, one instance all zero, one all
+    equal; instance 0, the last, the two special ones and every 64th are checked, against the oracle's MSM as well."""
+    _, n = pip_shapes.assert_plan("G%d" % nb)
+    pts, dl = _pip_points(pip_base, nb * n)
+    zero, equal = 5, nb - 3
+    rows = _rows(o.random_scalars(2000 + nb, nb * n), 32)
+    rows[zero * n:(zero + 1) * n] = 0
+    rows[equal * n:(equal + 1) * n] = rows[equal * n]
+    sc = rows.tobytes()
+    got = _own_context_msm_batch(nb, n, sc, pts, msm_wp_max=0, pippenger_min=2)
+    assert got[64 * zero:64 * zero + 64] == bytes(64)
+    for b in sorted({0, nb - 1, zero, equal} | set(range(0, nb, 64))):
+        s, p, d = sc[32 * n * b:32 * n * (b + 1)], pts[64 * n * b:64 * n * (b + 1)], dl[32 * n * b:32 * n * (b + 1)]
+        assert got[64 * b:64 * b + 64] == _pip_want(s, d) == o.msm(s, p), b
+
+
+@pytest.mark.parametrize("n", [2, 3, 17, 255])
+def test_msm_pippenger_route_fewer_terms_than_buckets(gpu, opts, pip_base, n):
+    """H: with pippenger_min = 2 the launch chain runs with fewer terms than one window has buckets (128 at c = 8)"""
+    pip_shapes.assert_plan("H%d" % n)
+    opts(msm_wp_max=0, pippenger_min=2)
+    pts, _ = _pip_points(pip_base, 300)
+    pts = pts[64 * 3:64 * (3 + n)]                                                     # from a non-identity point on
+    for sc in (o.random_scalars(50 + n, n), _sc_mix(60 + n, n)):
+        assert gpu.msm(sc, pts) == o.msm(sc, pts)
+
+
+def test_msm_pippenger_route_coarse_scan_in_three_launches(pip_base):
+    """I: 205 x 58 437 terms, the fewest at which the coarse histograms of the two-level sort (205 x 20 segments x 256 bins x 8
+    tiles) fill more than 4 096 scan tiles: their scan takes k_pip_scan_top + k_pip_scan_apply, and the total behind the last
+    offset, which bounds the last bin of the last segment, comes from k_pip_scan_top.  Every instance runs the same points;
+    its scalars are one of four vectors (random, all equal, bits, the mix) with term 1 replaced by the instance number + 1, so
+    that no two instances are alike and each expected point is one of four inner products plus a correction."""
+    import numpy as np
+    nb, n = pip_shapes.assert_plan("I")
+    pts, dl = _pip_points(pip_base, n)
+    vecs = [o.random_scalars(9001, n), _sc_equal(9002, n), _sc_bits(n), _sc_mix(9003, n)]
+    ips = [o.b2s(o.inner_product(v, dl)) for v in vecs]
+    k1 = o.b2s(dl[32:64])
+    assert k1 != 0
+    rows = _rows(b"".join(vecs[b % 4] for b in range(nb)), 32)
+    own = np.zeros((nb, 32), dtype=np.uint8)
+    own[:, 0], own[:, 1] = (np.arange(nb) + 1) & 0xFF, (np.arange(nb) + 1) >> 8
+    rows[1::n] = own
+    got = _own_context_msm_batch(nb, n, rows.tobytes(), pts * nb, msm_wp_max=0)
+    G = o.generator()
+    for b in range(nb):
+        v1 = o.b2s(vecs[b % 4][32:64])
+        assert got[64 * b:64 * b + 64] == o.point_mul(o.s2b(ips[b % 4] + (b + 1 - v1) * k1), G), b
 
 
 # ------------------------------------------------------------------ combined batch check
