@@ -136,7 +136,11 @@ int h29_recode(int c, const uint8_t *s, int *digits) {
   memcpy(sw, s, 32);
   int n = 0;
 #define DO(C) { recode_add_k<C>(sp, sw); n = num_windows<C>(); for (int w = 0; w < n; w++) digits[w] = recode_digit<C>(sp, w); }
-  switch (c) { case 4: DO(4) break; case 8: DO(8) break; case 12: DO(12) break; case 13: DO(13) break; case 16: DO(16) break; default: return -1; }
+  switch (c) {      // every width a kernel instantiates: Straus 4, k_pip2 7..12, k_pip 8..16, the tables 4, 8, 10, 12, 14, 16, 20
+    case 4: DO(4) break; case 7: DO(7) break; case 8: DO(8) break; case 9: DO(9) break; case 10: DO(10) break; case 11: DO(11) break;
+    case 12: DO(12) break; case 13: DO(13) break; case 14: DO(14) break; case 15: DO(15) break; case 16: DO(16) break; case 20: DO(20) break;
+    default: return -1;
+  }
   return n;
 }
 }
