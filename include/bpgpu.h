@@ -100,7 +100,9 @@ int bpgpu_input_flag(bpgpu_ctx *ctx, int *bad);
  * (bpgpu_r1cs_prover_commit), 17 polynomial build, 18 bpgpu_msm_gens (T commitments), 19 IPP session set-up, 20 the IPP round
  * loop, 21 the L / R table-lookup MSM of one round (the prover's dominant kernel, nested inside 20).
  * Kind 22: the launches only bpgpu_r1cs_prove_fs and bpgpu_r1cs_prove_fs2_begin / _finish have (their transcript slices, the scalar
- * links between the stages, proof assembly); the stages they chain keep reporting under 16..21. */
+ * links between the stages, proof assembly); the stages they chain keep reporting under 16..21.
+ * Kind 23: the decode launches of bpgpu_r1cs_verify_mixed_wire_* (ragged unpack + point decompression, and the fold of the reject
+ * bits: two pairs per check); the ragged transcript replay of those calls reports under 5. */
 int bpgpu_profile_enable(bpgpu_ctx *ctx, int on);
 int bpgpu_profile_select(bpgpu_ctx *ctx, uint32_t kind_mask);
 int bpgpu_profile_read(bpgpu_ctx *ctx, double ms_sum[BPGPU_PROF_KINDS], uint64_t launches[BPGPU_PROF_KINDS]);
@@ -713,7 +715,7 @@ int bpgpu_r1cs_verify_screened_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const
  * BPGPU_E_GENS (2^k above the generators' capacity), BPGPU_E_ARG (a null pointer, gadget challenges given to a one-phase circuit or
  * missing for a parametric one, ngroups > BPGPU_MIXED_MAX_GROUPS).  ngroups == 0 or only empty groups: BPGPU_OK, the identity.
  * Device transcripts (init_states) and wire-format proofs are not taken here: challenges come from the host's transcript replay, the
- * route a Rust host already has. */
+ * route a Rust host already has; bpgpu_r1cs_verify_mixed_wire_* below take wire bytes. */
 #define BPGPU_MIXED_MAX_GROUPS 64
 #define BPGPU_MIXED_MAX_SEGMENTS 16
 typedef struct bpgpu_verify_group {
@@ -732,6 +734,45 @@ int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const 
                                      size_t *fallback_batches);
 int bpgpu_r1cs_verify_mixed_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
                                          size_t *fallback_batches);
+
+/* MIXED queues of WIRE-format proofs: the same two checks from what a node receives -- R1CSProof::to_bytes, compressed commitments
+ * and the 32-byte transcript state per proof -- with decoding, point decompression and the Fiat-Shamir replay on the device.  A
+ * group's operands are those of bpgpu_r1cs_verify_batch_wire (bpgpu_r1cs_verify_batch_wire2 with gadget_label for a parametric
+ * circuit with one gadget challenge) plus the weights; proof_len fixes the version and k for the whole group.  Per check a ragged
+ * front of four launches (unpack | ONE decompression over the check's points | transcript replay, a wave per run of one group |
+ * fold of the reject bits) writes the operands of the mixed check above into the lane's workspace; the square-root tables and the
+ * groups' transcript schedules are set up once per call.  Scalars on the wire are read modulo n.
+ *   _screened : ok[] of every group equals what bpgpu_r1cs_verify_batch_wire (_wire2) returns for that group alone, up to the 2^-250
+ *               weight-cancellation chance.  A proof that does not decode (wrong version byte, off-curve or non-canonical x, both
+ *               flag bits set -- in a proof point or a commitment) or whose validated point is the identity gets ok[p] = 0 and sends
+ *               its check to the per-proof path; neither is an error of the call.  Checks are cut and spread as for
+ *               bpgpu_r1cs_verify_mixed_screened; one host-side wait, between the two phases.
+ *   _combined : the point bpgpu_r1cs_verify_mixed_combined returns on the decoded operands and the device's challenges.  An
+ *               undecodable proof, an identity at a validated point or a malformed weight gives the POISON encoding and raises the
+ *               input flag.
+ *   _dev      : every operand pointer, ok[] and partial_xy_dev in HBM; gadget_label stays a HOST pointer.
+ * Shape errors, before anything is launched: BPGPU_E_LEN (proof_len is no proof size, 2^k from it is not the circuit's padded n,
+ * n1 > n), BPGPU_E_GENS (2^k above the generators' capacity), BPGPU_E_ARG (a null required pointer, a parametric circuit without a
+ * label or a label given to a one-phase circuit, more than one gadget challenge, ngroups > BPGPU_MIXED_MAX_GROUPS).  ngroups == 0 or
+ * only empty groups: BPGPU_OK, the identity.  Two groups may share a circuit handle, with different labels or states. */
+typedef struct bpgpu_wire_group {
+  const bpgpu_circuit *circuit;        /* one-phase, or parametric with nchi == 1 */
+  size_t nb, n1, proof_len;            /* proofs in this group, phase-1 multipliers, bytes per proof */
+  const void *proofs;                  /* nb x proof_len */
+  const void *commitments;             /* nb x m x 32 B compressed; may be NULL when m == 0 */
+  const void *init_states;             /* nb x 32 B chain states, as bpgpu_r1cs_verify_batch_fs */
+  const uint8_t *gadget_label;         /* HOST pointer, 32 bytes zero-padded, for a parametric circuit; NULL otherwise */
+  const void *rho;                     /* nb x 32 B random non-zero weights */
+  void *ok;                            /* nb int32 verdicts (screened calls) */
+} bpgpu_wire_group;
+int bpgpu_r1cs_verify_mixed_wire_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                          size_t *fallback_batches);
+int bpgpu_r1cs_verify_mixed_wire_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                              size_t *fallback_batches);
+int bpgpu_r1cs_verify_mixed_wire_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                          uint8_t partial_xy[64]);
+int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                              void *partial_xy_dev);
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,7 @@ enum WsSlot : int {
   WS_MSM,           // window-parallel scratch, fixed-base chunk partials (msm_gens_dev), second Straus scratch, msm_core_locked's terms
   WS_STRAUS,        // Straus tables (straus_ws)
   WS_PIP,           // bucket-method and combined-check pipelines (k_pip.hip, k_pip2.hip, k_mixed.hip)
-  WS_VAUX,          // wire format / decode bits (verify_wire_locked); combined check: final sum
+  WS_VAUX,          // wire format / decode bits (verify_wire_locked, wire_front_locked); combined check: final sum
   WS_FS_STAGE,      // transcript host forms: challenges out, wire verdicts; bpgpu_ipp_run_fs: transcript states
   WS_FS_CH,         // device transcript: challenges; bpgpu_ipp_run_fs: L, R
   WS_PROOF_BAD,     // per-proof rejects: transcript identity points, non-canonical gadget challenges; bpgpu_ipp_run_fs: zero flag
@@ -66,6 +66,7 @@ enum WsSlot : int {
   WS_PFS_PTS,       // ... A_I A_O S and T_1..T_6: sums and boundary bytes
   WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched_key)
   WS_PFS_SCHED2,    // bpgpu_r1cs_prove_fs2_begin / _finish: the two-phase schedule (bpgpu_ctx::psched2_key)
+  WS_WIRE_SCHED,    // bpgpu_r1cs_verify_mixed_wire_*: the transcript schedules of a call's groups (on the calling context; the lanes read it)
   WS_COUNT
 };
 
@@ -112,6 +113,11 @@ struct bpgpu_ctx {
   // ... and the two-phase one (bpgpu_r1cs_prove_fs2_begin / _finish) in WS_PFS_SCHED2, with its four slices
   size_t psched2_key[2] = {(size_t)-1, (size_t)-1};
   int psched2_cut[5] = {0, 0, 0, 0, 0};
+  // bpgpu_r1cs_verify_mixed_wire_*: page-locked staging of a call's schedules and the mark of its upload (the next call waits for
+  // the mark before it refills the staging -- passed long before, except when _dev calls follow each other without a bpgpu_sync)
+  void *wsched_host = nullptr;
+  size_t wsched_cap = 0;
+  hipEvent_t wsched_ev = nullptr;
 };
 struct ProfScope {   // records start/stop events on `st` around a launch when profiling is on (events come from a per-context pool)
   bpgpu_ctx *c; int kind; hipStream_t st;
@@ -484,6 +490,8 @@ void bpgpu_destroy(bpgpu_ctx *ctx) {
   ctx->lanes.clear();
   if (ctx->lane_ev) hipEventDestroy(ctx->lane_ev);
   if (ctx->pinned) hipHostFree(ctx->pinned);
+  if (ctx->wsched_host) hipHostFree(ctx->wsched_host);
+  if (ctx->wsched_ev) hipEventDestroy(ctx->wsched_ev);
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->st);
   hipStreamSynchronize(ctx->st2);
@@ -2017,20 +2025,26 @@ static bool wire_dims(size_t proof_len, int *two_phase, size_t *k) {
   if (el >= 16 && (el - 16) % 2 == 0) { *two_phase = 1; *k = (el - 16) / 2; return *k < 32; }
   return false;
 }
+// the context's square-root tables, built on its stream at first use
+static int sqrt_tab_locked(bpgpu_ctx *ctx) {
+  if (ctx->sqrt_tab) return BPGPU_OK;
+  void *t = nullptr;
+  if (hipMalloc(&t, sqrt_table_bytes()) != hipSuccess) return BPGPU_E_OOM;
+  sqrt_tables_build(ctx->st, t);
+  ctx->sqrt_tab = t;
+  return BPGPU_OK;
+}
+// sqrt_tab: tables another context owns and has built before this one's stream forked from it (a lane of a mixed wire call);
+// null: the context's own
 static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                               size_t proof_len, const void *proofs, const void *commitments, const void *init_states,
-                              void *ok, const uint8_t *gadget_label = nullptr) {
+                              void *ok, const uint8_t *gadget_label = nullptr, const void *sqrt_tab = nullptr) {
   int two_phase = 0;
   size_t k = 0;
   if (!wire_dims(proof_len, &two_phase, &k)) return BPGPU_E_LEN;
   if (!nb) return BPGPU_OK;
   HIPCK(ctx, hipSetDevice(ctx->device));
-  if (!ctx->sqrt_tab) {
-    void *t = nullptr;
-    if (hipMalloc(&t, sqrt_table_bytes()) != hipSuccess) return BPGPU_E_OOM;
-    sqrt_tables_build(ctx->st, t);
-    ctx->sqrt_tab = t;
-  }
+  if (!sqrt_tab) { CK(sqrt_tab_locked(ctx)); sqrt_tab = ctx->sqrt_tab; }
   const size_t m = c->m, nvar = verify_nvar(c, k);
   void *dcomp, *dxy, *dsc, *dfmt;
   CK(ws_get(ctx, WS_ARG0, nb * nvar * 32, &dcomp));
@@ -2040,7 +2054,7 @@ static int verify_wire_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_c
   int32_t *fmt_ok = (int32_t *)dfmt, *dec_ok = fmt_ok + nb;
   wire_unpack(ctx->st, (const uint8_t *)proofs, proof_len, (const uint8_t *)commitments, nb, m, k, two_phase,
               (Words8 *)dcomp, (Words8 *)dsc, fmt_ok);
-  points_decompress(ctx->st, (const Words8 *)dcomp, (Words8 *)dxy, dec_ok, nb * nvar, ctx->sqrt_tab);
+  points_decompress(ctx->st, (const Words8 *)dcomp, (Words8 *)dxy, dec_ok, nb * nvar, sqrt_tab);
   // undecodable points come out as the identity: the transcript / MSM run on them, the verdict is forced to 0 below
   CK(verify_fs_locked(ctx, g, c, nb, n1, k, init_states, dxy, dsc, ok, nullptr, nullptr, gadget_label));
   wire_and_ok(ctx->st, (int32_t *)ok, fmt_ok, dec_ok, nb, nvar);
@@ -2388,6 +2402,7 @@ static void mixed_plan(const bpgpu_verify_group *G, size_t ngroups, size_t max_p
 }
 // ONE ragged combined check on `ln`'s stream: partial_xy (HBM) = sum over the check's proofs of rho_p * mega_check_p.  The caller
 // resets ln's input flag; zero_rho (optional) is raised for a zero weight.
+static int mixed_run_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const MixSegIn *in, size_t nseg, void *partial_xy, int *zero_rho);
 static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group *G, const MixSeg *segs, size_t nseg,
                               void *partial_xy, int *zero_rho) {
   MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
@@ -2405,6 +2420,10 @@ static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_ve
     v.challenges = (const Words8 *)x.challenges + lo * (6 + x.k);
     v.rho = (const Words8 *)x.rho + lo;
   }
+  return mixed_run_locked(ln, g, in, nseg, partial_xy, zero_rho);
+}
+// ... on operands already laid out as segments (the wire calls decode theirs into the lane's workspace)
+static int mixed_run_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const MixSegIn *in, size_t nseg, void *partial_xy, int *zero_rho) {
   void *scr;
   CK(ws_get(ln, WS_PIP, verify_mixed_scratch_bytes(in, nseg, g->c), &scr));
   MixedArgs a{in, nseg, scr, g->table, g->cap, g->c, ln->d_flag, zero_rho, (Words8 *)partial_xy, ln->prof ? &prof_mark_cb : nullptr, ln};
@@ -2546,6 +2565,266 @@ int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const 
   std::vector<bpgpu_verify_group> D;
   CK(mixed_stage_locked(ctx, groups, ngroups, D));
   CK(mixed_screened_locked(ctx, g, D.data(), ngroups, fallback_batches));
+  for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+
+/* ---------------------------------------------------------------- mixed queues of WIRE-format proofs, transcript on the device
+ * The plan is the mixed queue's (mixed_plan).  Per check a ragged front decodes the segments into the lane's workspace in four
+ * launches -- unpack, ONE decompression over the check's points, the transcript replay, a fold of the reject bits -- in the layouts
+ * of MixSegIn, and the ragged combined check runs on them unchanged.  The square-root tables and the groups' transcript schedules
+ * are built / uploaded once per call on the calling context, before the lanes fork; the lanes only read them. */
+namespace {
+struct WireGroupDims { int two_phase; size_t k; };
+struct WireSched { const TrStep *steps; int nsteps; };
+}
+static int wire_validate(const bpgpu_gens *g, const bpgpu_wire_group *G, size_t ngroups, bool screened, WireGroupDims *dims) {
+  if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
+  for (size_t i = 0; i < ngroups; i++) {
+    const bpgpu_wire_group &x = G[i];
+    const bpgpu_circuit *c = x.circuit;
+    if (!c) return BPGPU_E_ARG;
+    if (x.nb && (!x.proofs || !x.init_states || !x.rho || (c->m && !x.commitments) || (screened && !x.ok))) return BPGPU_E_ARG;
+    if (c->nchi > 1 || (c->nchi != 0) != (x.gadget_label != nullptr)) return BPGPU_E_ARG;
+    if (!wire_dims(x.proof_len, &dims[i].two_phase, &dims[i].k)) return BPGPU_E_LEN;
+    CK(verify_shape(c, g, x.n1, dims[i].k));
+  }
+  return BPGPU_OK;
+}
+// what mixed_plan reads of a group
+static void wire_shadow(const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups, std::vector<bpgpu_verify_group> &V) {
+  V.assign(ngroups, bpgpu_verify_group{});
+  for (size_t i = 0; i < ngroups; i++) { V[i].circuit = G[i].circuit; V[i].nb = G[i].nb; V[i].n1 = G[i].n1; V[i].k = dims[i].k; }
+}
+// every non-empty group's schedule, one after the other in WS_WIRE_SCHED of the calling context: ONE upload per call from page-locked
+// staging, no host wait (fs_transcript_locked's one-entry cache would re-upload and wait whenever the shape changes)
+static int wire_schedules_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups, WireSched *out) {
+  size_t cap = 0;
+  for (size_t i = 0; i < ngroups; i++) if (G[i].nb) cap += transcript_schedule_max(G[i].circuit->m, dims[i].k);
+  if (!cap) return BPGPU_OK;
+  if (!ctx->wsched_ev) HIPCK(ctx, hipEventCreateWithFlags(&ctx->wsched_ev, hipEventDisableTiming));
+  else HIPCK(ctx, hipEventSynchronize(ctx->wsched_ev));        // the previous call's upload has read the staging
+  if (ctx->wsched_cap < cap * sizeof(TrStep)) {
+    if (ctx->wsched_host) { (void)hipHostFree(ctx->wsched_host); ctx->wsched_host = nullptr; ctx->wsched_cap = 0; }
+    HIPCK(ctx, hipHostMalloc(&ctx->wsched_host, 2 * cap * sizeof(TrStep), hipHostMallocDefault));
+    ctx->wsched_cap = 2 * cap * sizeof(TrStep);
+  }
+  void *dsteps;
+  CK(ws_get(ctx, WS_WIRE_SCHED, cap * sizeof(TrStep), &dsteps));
+  TrStep *h = (TrStep *)ctx->wsched_host;
+  size_t off = 0;
+  for (size_t i = 0; i < ngroups; i++) {
+    if (!G[i].nb) { out[i] = WireSched{nullptr, 0}; continue; }
+    const bpgpu_circuit *c = G[i].circuit;
+    memset(h + off, 0, transcript_schedule_max(c->m, dims[i].k) * sizeof(TrStep));
+    const int n = transcript_schedule(h + off, c->m, dims[i].k, (size_t)1 << dims[i].k, c->nchi);
+    out[i] = WireSched{(const TrStep *)dsteps + off, n};
+    off += (size_t)n;
+  }
+  HIPCK(ctx, hipMemcpyAsync(dsteps, h, off * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
+  HIPCK(ctx, hipEventRecord(ctx->wsched_ev, ctx->st));
+  return BPGPU_OK;
+}
+// The ragged front of ONE check on `ln`'s stream: fills in[] with the decoded operands (in ln's workspace) and ORs `bit` into ln's
+// input flag when a proof of the check does not decode or fails the transcript's point validation.  The caller has reset the flag.
+static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const WireGroupDims *dims, const WireSched *sched,
+                             const void *sqrt_tab, const MixSeg *segs, size_t nseg, int bit, MixSegIn *in) {
+  size_t tot = 0, nbt = 0, nchs = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    const size_t gi = segs[s].gi;
+    tot += segs[s].cnt * verify_nvar(G[gi].circuit, dims[gi].k);
+    nbt += segs[s].cnt;
+    nchs += segs[s].cnt * (6 + dims[gi].k);
+  }
+  if (tot + 5 * nbt >= ((size_t)1 << 31)) return BPGPU_E_LEN;      // (the front's tables index with 32 bits)
+  void *dcomp, *dxy, *dsc, *dch, *dchi, *dbits, *dbad;
+  CK(ws_get(ln, WS_ARG0, tot * 32, &dcomp));
+  CK(ws_get(ln, WS_ARG1, tot * 64, &dxy));
+  CK(ws_get(ln, WS_ARG2, nbt * 5 * 32, &dsc));
+  CK(ws_get(ln, WS_FS_CH, nchs * 32, &dch));
+  CK(ws_get(ln, WS_CHI, nbt * 32, &dchi));
+  CK(ws_get(ln, WS_VAUX, (2 * nbt + tot) * 4, &dbits));
+  CK(ws_get(ln, WS_PROOF_BAD, nbt * 4, &dbad));
+  int32_t *fmt_ok = (int32_t *)dbits, *tr_bad = fmt_ok + nbt, *dec_ok = tr_bad + nbt;
+  WireSegIn ws[BPGPU_MIXED_MAX_SEGMENTS];
+  TrSegIn ts[BPGPU_MIXED_MAX_SEGMENTS];
+  size_t pt_off = 0, p_off = 0, ch_off = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    const size_t gi = segs[s].gi, lo = segs[s].lo, cnt = segs[s].cnt, k = dims[gi].k;
+    const bpgpu_wire_group &x = G[gi];
+    const bpgpu_circuit *c = x.circuit;
+    const size_t m = c->m, nvar = verify_nvar(c, k);
+    ws[s] = WireSegIn{(const uint8_t *)x.proofs + lo * x.proof_len, m ? (const uint8_t *)x.commitments + lo * m * 32 : nullptr, x.proof_len,
+                      cnt, m, k, dims[gi].two_phase != 0};
+    Words8 *pts = (Words8 *)dxy + pt_off * 2, *sc = (Words8 *)dsc + p_off * 5, *ch = (Words8 *)dch + ch_off, *chi = (Words8 *)dchi + p_off;
+    ts[s] = TrSegIn{sched[gi].steps, sched[gi].nsteps, cnt, m, k, c->nchi, (const Words8 *)x.init_states + lo, pts, sc, ch, chi,
+                    tr_bad + p_off, x.gadget_label};
+    MixSegIn &v = in[s];
+    v.circ = circuit_dev(c);
+    v.d = VerifyDims{cnt, x.n1, c->n, (size_t)1 << k, k, m, c->nchi ? chi : nullptr, (size_t)ln->opt[BPGPU_OPT_VS_LARGE_MIN]};
+    v.nvar = nvar; v.nchi = c->nchi;
+    v.points = pts; v.proof_scalars = sc; v.challenges = ch;
+    v.rho = (const Words8 *)x.rho + lo;
+    pt_off += cnt * nvar; p_off += cnt; ch_off += cnt * (6 + k);
+  }
+  { ProfScope ps(ln, 23, ln->st);
+    wire_unpack_ragged(ln->st, ws, nseg, (Words8 *)dcomp, (Words8 *)dsc, fmt_ok);
+    // undecodable points come out as the identity: the transcript and the MSMs run on them, the fold rejects their proofs
+    points_decompress(ln->st, (const Words8 *)dcomp, (Words8 *)dxy, dec_ok, tot, sqrt_tab); }
+  { ProfScope ps(ln, 5, ln->st);
+    verify_transcript_ragged(ln->st, ts, nseg); }
+  { ProfScope ps(ln, 23, ln->st);
+    wire_fold(ln->st, ws, nseg, fmt_ok, dec_ok, tr_bad, (int32_t *)dbad, ln->d_flag, bit); }
+  return launch_ok(ln);
+}
+static int wire_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups,
+                                void *partial_xy) try {
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_verify_group> V;
+  std::vector<MixSeg> segs;
+  std::vector<MixCheck> checks;
+  wire_shadow(G, dims, ngroups, V);
+  mixed_plan(V.data(), ngroups, (size_t)-1, (size_t)-1, segs, checks);
+  CK(flag_reset(ctx));
+  if (checks.empty()) { HIPCK(ctx, hipMemsetAsync(partial_xy, 0, 64, ctx->st)); return BPGPU_OK; }
+  WireSched sched[BPGPU_MIXED_MAX_GROUPS];
+  CK(sqrt_tab_locked(ctx));
+  CK(wire_schedules_locked(ctx, G, dims, ngroups, sched));
+  void *dpart = partial_xy;
+  if (checks.size() > 1) CK(ws_get(ctx, WS_SCREEN_PART, checks.size() * 64, &dpart));
+  for (size_t ci = 0; ci < checks.size(); ci++) {
+    MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
+    // an undecodable proof or an identity at a validated point is malformed input of the combined call: bit 1, as verify_mixed's own
+    CK(wire_front_locked(ctx, G, dims, sched, ctx->sqrt_tab, segs.data() + checks[ci].first, checks[ci].nseg, 1, in));
+    CK(mixed_run_locked(ctx, g, in, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
+  }
+  int *dbad2;
+  if (checks.size() > 1) {
+    CK(ws_get(ctx, WS_SCREEN_FLAG, 256, (void **)&dbad2));
+    points_sum(ctx->st, (const Words8 *)dpart, checks.size(), (Words8 *)partial_xy, dbad2);
+  }
+  mixed_poison(ctx->st, ctx->d_flag, (Words8 *)partial_xy);
+  return launch_ok(ctx);
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+static int wire_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups,
+                                size_t *fallback_batches) try {
+  if (fallback_batches) *fallback_batches = 0;
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_verify_group> V;
+  std::vector<MixSeg> segs;
+  std::vector<MixCheck> checks;
+  wire_shadow(G, dims, ngroups, V);
+  mixed_plan(V.data(), ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, segs, checks);
+  if (checks.empty()) return BPGPU_OK;
+  WireSched sched[BPGPU_MIXED_MAX_GROUPS];
+  CK(sqrt_tab_locked(ctx));                          // on ctx->st, before screen_locked forks the lanes from it
+  CK(wire_schedules_locked(ctx, G, dims, ngroups, sched));
+  const void *tab = ctx->sqrt_tab;
+  auto check = [&](bpgpu_ctx *ln, size_t ci, void *partial) -> int {
+    MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
+    CK(flag_reset(ln));
+    CK(wire_front_locked(ln, G, dims, sched, tab, segs.data() + checks[ci].first, checks[ci].nseg, 2, in));
+    return mixed_run_locked(ln, g, in, checks[ci].nseg, partial, ln->d_flag);
+  };
+  auto accept = [&](size_t ci) -> int {
+    const MixSeg *sg = segs.data() + checks[ci].first;
+    for (size_t s = 0; s < checks[ci].nseg; s++)
+      if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
+    return BPGPU_OK;
+  };
+  // the per-proof path decodes its segments again, each on its own (the lane's workspace has moved on since the check); it is
+  // the rare path and keeps the one-circuit call's schedule cache
+  auto fallback = [&](bpgpu_ctx *ln, size_t ci) -> int {
+    const MixSeg *sg = segs.data() + checks[ci].first;
+    for (size_t s = 0; s < checks[ci].nseg; s++) {
+      const bpgpu_wire_group &x = G[sg[s].gi];
+      const size_t lo = sg[s].lo, m = x.circuit->m;
+      CK(verify_wire_locked(ln, g, x.circuit, sg[s].cnt, x.n1, x.proof_len, (const uint8_t *)x.proofs + lo * x.proof_len,
+                            m ? (const uint8_t *)x.commitments + lo * m * 32 : nullptr, (const uint8_t *)x.init_states + lo * 32,
+                            (int32_t *)x.ok + lo, x.gadget_label, tab));
+    }
+    return BPGPU_OK;
+  };
+  return screen_locked(ctx, checks.size(), "bpgpu_r1cs_verify_mixed_wire_screened", fallback_batches, check, accept, fallback);
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+// host forms: every group's wire bytes go up once (WS_MIXED_STAGE), the device form runs, the verdicts come back
+static int wire_stage_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, size_t ngroups, std::vector<bpgpu_wire_group> &D) {
+  size_t tot = 0;
+  auto sizes = [](const bpgpu_wire_group &x, size_t *b) {
+    b[0] = x.nb * x.proof_len; b[1] = x.commitments ? x.nb * x.circuit->m * 32 : 0; b[2] = x.nb * 32; b[3] = x.nb * 32; b[4] = x.nb * 4;
+  };
+  for (size_t i = 0; i < ngroups; i++) { size_t b[5]; sizes(G[i], b); for (size_t j : b) tot += (j + 255) / 256 * 256; }
+  void *base;
+  CK(ws_get(ctx, WS_MIXED_STAGE, tot, &base));
+  uint8_t *q = (uint8_t *)base;
+  D.assign(G, G + ngroups);
+  for (size_t i = 0; i < ngroups; i++) {
+    size_t b[5];
+    sizes(G[i], b);
+    const void *src[4] = {G[i].proofs, G[i].commitments, G[i].init_states, G[i].rho};
+    const void **dst[4] = {&D[i].proofs, &D[i].commitments, &D[i].init_states, &D[i].rho};
+    for (int j = 0; j < 4; j++) {
+      if (src[j]) { CK(h2d(ctx, q, src[j], b[j])); *dst[j] = q; }
+      q += (b[j] + 255) / 256 * 256;
+    }
+    D[i].ok = q;
+    q += (b[4] + 255) / 256 * 256;
+  }
+  return BPGPU_OK;
+}
+int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                              void *partial_xy_dev) {
+  if (!ctx || !partial_xy_dev) return BPGPU_E_ARG;
+  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
+  CK(wire_validate(g, groups, ngroups, false, dims));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return wire_combined_locked(ctx, g, groups, dims, ngroups, partial_xy_dev);
+}
+int bpgpu_r1cs_verify_mixed_wire_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                          uint8_t partial_xy[64]) try {
+  if (!ctx || !partial_xy) return BPGPU_E_ARG;
+  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
+  CK(wire_validate(g, groups, ngroups, false, dims));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_wire_group> D;
+  CK(wire_stage_locked(ctx, groups, ngroups, D));
+  void *dout;
+  CK(ws_get(ctx, WS_ARG4, 64, &dout));
+  CK(wire_combined_locked(ctx, g, D.data(), dims, ngroups, dout));
+  CK(d2h(ctx, partial_xy, dout, 64));
+  HIPCK(ctx, hipStreamSynchronize(ctx->st));
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+int bpgpu_r1cs_verify_mixed_wire_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                              size_t *fallback_batches) {
+  if (fallback_batches) *fallback_batches = 0;
+  if (!ctx) return BPGPU_E_ARG;
+  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
+  CK(wire_validate(g, groups, ngroups, true, dims));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return wire_screened_locked(ctx, g, groups, dims, ngroups, fallback_batches);
+}
+int bpgpu_r1cs_verify_mixed_wire_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
+                                          size_t *fallback_batches) try {
+  if (fallback_batches) *fallback_batches = 0;
+  if (!ctx) return BPGPU_E_ARG;
+  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
+  CK(wire_validate(g, groups, ngroups, true, dims));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIPCK(ctx, hipSetDevice(ctx->device));
+  std::vector<bpgpu_wire_group> D;
+  CK(wire_stage_locked(ctx, groups, ngroups, D));
+  CK(wire_screened_locked(ctx, g, D.data(), dims, ngroups, fallback_batches));
   for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
   HIPCK(ctx, hipStreamSynchronize(ctx->st));
   return BPGPU_OK;

@@ -84,13 +84,10 @@ __global__ void __launch_bounds__(256) k_points_compress(const Words8 *xy, Words
 // (A_I1 A_O1 S1 A_I2 A_O2 S2 | V_0..V_{m-1} | T_1 T_3 T_4 T_5 T_6 | L_0.. | R_0..), the five scalars as canonical
 // little-endian words (big-endian on the wire, read modulo n: from_be_bytes_mod_order), fmt_ok[p] = version byte as
 // the length implies.
-__global__ void __launch_bounds__(256) k_wire_unpack(const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
-                                                     size_t nb, size_t m, size_t k, int two_phase, Words8 *comp,
-                                                     Words8 *scalars, int32_t *fmt_ok) {
-  const size_t nvar = 11 + m + 2 * k, per = nvar + 5;
-  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nb * per) return;
-  const size_t p = t / per, s = t - p * per;
+// slot s of proof p (s < nvar: a point, else one of the five scalars)
+__device__ __forceinline__ void wire_unpack_slot(const uint8_t *proofs, size_t proof_len, const uint8_t *commitments, size_t m, size_t k,
+                                                 int two_phase, size_t p, size_t s, Words8 *comp, Words8 *scalars, int32_t *fmt_ok) {
+  const size_t nvar = 11 + m + 2 * k;
   const uint8_t *pr = proofs + p * proof_len;
   const size_t head = two_phase ? 11 : 8;   // compressed points before the three scalars
   if (s == 0) fmt_ok[p] = pr[0] == (two_phase ? 1 : 0) ? 1 : 0;
@@ -124,6 +121,48 @@ __global__ void __launch_bounds__(256) k_wire_unpack(const uint8_t *proofs, size
     for (int j = 0; j < 8; j++) scalars[p * 5 + q].w[j] = o[j];
   }
 }
+__global__ void __launch_bounds__(256) k_wire_unpack(const uint8_t *proofs, size_t proof_len, const uint8_t *commitments,
+                                                     size_t nb, size_t m, size_t k, int two_phase, Words8 *comp,
+                                                     Words8 *scalars, int32_t *fmt_ok) {
+  const size_t per = 16 + m + 2 * k;
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nb * per) return;
+  const size_t p = t / per;
+  wire_unpack_slot(proofs, proof_len, commitments, m, k, two_phase, p, t - p * per, comp, scalars, fmt_ok);
+}
+// The same for the segments of ONE mixed check (bpgpu_r1cs_verify_mixed_wire_*): every segment has its own proof length, m, k and
+// source arrays; the compressed points of all segments land in one buffer (segment after segment, proof-major inside one: the
+// layout k_points_decompress and k_mix_front walk), the scalars and fmt_ok by the check's proof index.  The table travels in the
+// kernel arguments, as k_mix_front's does.
+struct WireRagSeg { const uint8_t *proofs, *commitments; uint32_t proof_len, m, k, two_phase, nb, p_off, pt_off, t_off; };
+struct WireRag { WireRagSeg seg[MIX_SEG_MAX]; uint32_t nseg, nbt, tot_slots; Words8 *comp, *scalars; int32_t *fmt_ok; };
+static_assert(sizeof(WireRag) <= 4096, "k_wire_unpack_ragged's arguments exceed 4 KB");
+__global__ void __launch_bounds__(256) k_wire_unpack_ragged(WireRag a) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.tot_slots) return;
+  uint32_t s = 0;
+  while (s + 1 < a.nseg && t >= a.seg[s + 1].t_off) s++;
+  const WireRagSeg &g = a.seg[s];
+  const size_t per = 16 + (size_t)g.m + 2 * (size_t)g.k, j = t - g.t_off, p = j / per;
+  wire_unpack_slot(g.proofs, g.proof_len, g.commitments, g.m, g.k, (int)g.two_phase, p, j - p * per, a.comp + g.pt_off,
+                   a.scalars + (size_t)g.p_off * 5, a.fmt_ok + g.p_off);
+}
+// bad[p] = !fmt_ok[p] | any !dec_ok[p][*] | tr_bad[p] over the check's proofs; *flag |= bit when any is set (bit 2: k_or_flag's
+// "a proof of this check is rejected before the MSMs", which sends a screened check to the per-proof path)
+struct WireFold { struct { uint32_t p_off, pt_off, nvar; } seg[MIX_SEG_MAX]; uint32_t nseg, nbt; const int32_t *fmt_ok, *dec_ok, *tr_bad;
+                  int32_t *bad; int *flag; int bit; };
+__global__ void __launch_bounds__(256) k_wire_fold(WireFold a) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.nbt) return;
+  uint32_t s = 0;
+  while (s + 1 < a.nseg && p >= a.seg[s + 1].p_off) s++;
+  const size_t nvar = a.seg[s].nvar;
+  const int32_t *dec = a.dec_ok + a.seg[s].pt_off + (p - a.seg[s].p_off) * nvar;
+  int good = a.fmt_ok[p] && !a.tr_bad[p];
+  for (size_t v = 0; v < nvar; v++) good &= dec[v];
+  a.bad[p] = good ? 0 : 1;
+  if (!good) atomicOr(a.flag, a.bit);
+}
 // ok[p] &= fmt_ok[p] & all(dec_ok[p][*])
 __global__ void __launch_bounds__(256) k_wire_and_ok(int32_t *ok, const int32_t *fmt_ok, const int32_t *dec_ok, size_t nb, size_t nvar) {
   size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -138,6 +177,34 @@ void wire_unpack(hipStream_t st, const uint8_t *proofs, size_t proof_len, const 
   if (!tot) return;
   hipLaunchKernelGGL(k_wire_unpack, dim3((tot + 255) / 256), dim3(256), 0, st, proofs, proof_len, commitments, nb, m, k,
                      two_phase, comp, scalars, fmt_ok);
+}
+void wire_unpack_ragged(hipStream_t st, const WireSegIn *seg, size_t nseg, Words8 *comp, Words8 *scalars, int32_t *fmt_ok) {
+  WireRag a{};
+  uint32_t p_off = 0, pt_off = 0, t_off = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    const WireSegIn &g = seg[s];
+    a.seg[s] = WireRagSeg{g.proofs, g.commitments, (uint32_t)g.proof_len, (uint32_t)g.m, (uint32_t)g.k, g.two_phase ? 1u : 0u, (uint32_t)g.nb,
+                          p_off, pt_off, t_off};
+    const uint32_t nvar = (uint32_t)(11 + g.m + 2 * g.k);
+    p_off += (uint32_t)g.nb; pt_off += (uint32_t)g.nb * nvar; t_off += (uint32_t)g.nb * (nvar + 5);
+  }
+  if (!t_off) return;
+  a.nseg = (uint32_t)nseg; a.nbt = p_off; a.tot_slots = t_off;
+  a.comp = comp; a.scalars = scalars; a.fmt_ok = fmt_ok;
+  hipLaunchKernelGGL(k_wire_unpack_ragged, dim3((t_off + 255) / 256), dim3(256), 0, st, a);
+}
+void wire_fold(hipStream_t st, const WireSegIn *seg, size_t nseg, const int32_t *fmt_ok, const int32_t *dec_ok, const int32_t *tr_bad,
+               int32_t *bad, int *flag, int bit) {
+  WireFold a{};
+  uint32_t p_off = 0, pt_off = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    const uint32_t nvar = (uint32_t)(11 + seg[s].m + 2 * seg[s].k);
+    a.seg[s].p_off = p_off; a.seg[s].pt_off = pt_off; a.seg[s].nvar = nvar;
+    p_off += (uint32_t)seg[s].nb; pt_off += (uint32_t)seg[s].nb * nvar;
+  }
+  if (!p_off) return;
+  a.nseg = (uint32_t)nseg; a.nbt = p_off; a.fmt_ok = fmt_ok; a.dec_ok = dec_ok; a.tr_bad = tr_bad; a.bad = bad; a.flag = flag; a.bit = bit;
+  hipLaunchKernelGGL(k_wire_fold, dim3((p_off + 255) / 256), dim3(256), 0, st, a);
 }
 void wire_and_ok(hipStream_t st, int32_t *ok, const int32_t *fmt_ok, const int32_t *dec_ok, size_t nb, size_t nvar) {
   if (!nb) return;

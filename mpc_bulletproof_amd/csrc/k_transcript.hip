@@ -176,15 +176,11 @@ __constant__ Label TR_LABELS[LB_COUNT] = {
 // call Verifier::new (after Transcript::new(label) and any application preamble).
 // challenges out: y z u x w r u_1..u_k ; tr_bad[p] = 1 if a validated point is the identity
 // (TranscriptProtocol::validate_and_append_point -> VerificationError, transcript.rs:101-113).
-__global__ void __launch_bounds__(64) k_verify_transcript(size_t nb, size_t nvar, size_t nch, const TrStep *steps, int nsteps,
-                                                          const Words8 *init_state, const Words8 *points, const Words8 *scalars,
-                                                          Words8 *challenges, int32_t *tr_bad, Label gadget_label, Words8 *chi,
-                                                          size_t nchi) {
-  // (no raised wave priority here, unlike the other short links of a batch's chain: a lone wave of dependent 64-bit operations
-  // issues back to back, so at priority 3 the 16 transcript waves of each of ~20 batches in flight kept their SIMDs to
-  // themselves for 0.7 ms at a time -- measured 3.54 -> 3.95 M verifications/s for the device-transcript leg without it)
-  size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= nb) return;
+// the replay of proof p (the step interpreter of k_verify_transcript and k_verify_transcript_ragged)
+__device__ __forceinline__ void verify_transcript_lane(size_t p, size_t nvar, size_t nch, const TrStep *steps, int nsteps,
+                                                       const Words8 *init_state, const Words8 *points, const Words8 *scalars,
+                                                       Words8 *challenges, int32_t *tr_bad, const Label &gadget_label, Words8 *chi,
+                                                       size_t nchi) {
   const Words8 *pt = points + p * nvar * 2;
   const Words8 *sc = scalars + p * 5;
   Words8 *ch = challenges + p * nch;
@@ -233,6 +229,54 @@ __global__ void __launch_bounds__(64) k_verify_transcript(size_t nb, size_t nvar
     }
   }
   tr_bad[p] = bad ? 1 : 0;
+}
+__global__ void __launch_bounds__(64) k_verify_transcript(size_t nb, size_t nvar, size_t nch, const TrStep *steps, int nsteps,
+                                                          const Words8 *init_state, const Words8 *points, const Words8 *scalars,
+                                                          Words8 *challenges, int32_t *tr_bad, Label gadget_label, Words8 *chi,
+                                                          size_t nchi) {
+  // (no raised wave priority here, unlike the other short links of a batch's chain: a lone wave of dependent 64-bit operations
+  // issues back to back, so at priority 3 the 16 transcript waves of each of ~20 batches in flight kept their SIMDs to
+  // themselves for 0.7 ms at a time -- measured 3.54 -> 3.95 M verifications/s for the device-transcript leg without it)
+  size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  verify_transcript_lane(p, nvar, nch, steps, nsteps, init_state, points, scalars, challenges, tr_bad, gadget_label, chi, nchi);
+}
+// The replay for the segments of ONE mixed check (bpgpu_r1cs_verify_mixed_wire_*), each with its own schedule, gadget label and
+// arrays.  Blocks of 64 lanes map to segments through the table's block prefix (blk0), so every wave runs ONE segment's steps:
+// lanes of a wave in two segments would take different cases of the switch and run the Keccak bodies one after the other.
+// (Priority unraised, as above.)
+struct TrRagSeg {
+  const TrStep *steps; const Words8 *init_state, *points, *scalars; Words8 *challenges, *chi; int32_t *tr_bad;
+  Label gadget_label; uint32_t nsteps, nb, blk0, nvar, nch, nchi;
+};
+struct TrRag { TrRagSeg seg[MIX_SEG_MAX]; uint32_t nseg; };
+static_assert(sizeof(TrRag) <= 4096, "k_verify_transcript_ragged's arguments exceed 4 KB");
+__global__ void __launch_bounds__(64) k_verify_transcript_ragged(TrRag a) {
+  uint32_t s = 0;
+  while (s + 1 < a.nseg && blockIdx.x >= a.seg[s + 1].blk0) s++;
+  const TrRagSeg &g = a.seg[s];
+  const size_t p = (size_t)(blockIdx.x - g.blk0) * 64 + threadIdx.x;
+  if (p >= g.nb) return;
+  verify_transcript_lane(p, g.nvar, g.nch, g.steps, (int)g.nsteps, g.init_state, g.points, g.scalars, g.challenges, g.tr_bad, g.gadget_label,
+                         g.chi, g.nchi);
+}
+void verify_transcript_ragged(hipStream_t st, const TrSegIn *seg, size_t nseg) {
+  TrRag a{};
+  uint32_t blk = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    const TrSegIn &g = seg[s];
+    TrRagSeg &r = a.seg[s];
+    r.steps = g.steps_dev; r.init_state = g.init_state; r.points = g.points; r.scalars = g.scalars; r.challenges = g.challenges; r.chi = g.chi;
+    r.tr_bad = g.tr_bad;
+    r.gadget_label = Label{{0, 0, 0, 0}};
+    if (g.gadget_label) for (int i = 0; i < 32; i++) r.gadget_label.w[i >> 3] |= (uint64_t)g.gadget_label[i] << (8 * (i & 7));
+    r.nsteps = (uint32_t)g.nsteps; r.nb = (uint32_t)g.nb; r.blk0 = blk; r.nvar = (uint32_t)(11 + g.m + 2 * g.k); r.nch = (uint32_t)(6 + g.k);
+    r.nchi = (uint32_t)g.nchi;
+    blk += (uint32_t)((g.nb + 63) / 64);
+  }
+  if (!blk) return;
+  a.nseg = (uint32_t)nseg;
+  hipLaunchKernelGGL(k_verify_transcript_ragged, dim3(blk), dim3(64), 0, st, a);
 }
 // Verifier::verify's transcript order for a circuit without randomized constraints
 int transcript_schedule(TrStep *out, size_t m, size_t k, size_t padded_n, size_t nchi) {

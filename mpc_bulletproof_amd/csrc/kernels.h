@@ -249,6 +249,13 @@ int transcript_schedule(TrStep *out, size_t m, size_t k, size_t padded_n, size_t
 void verify_transcript(hipStream_t st, size_t nb, size_t m, size_t k, const TrStep *steps_dev, int nsteps, const Words8 *init_state,
                        const Words8 *points, const Words8 *scalars, Words8 *challenges, int32_t *tr_bad,
                        const uint8_t *gadget_label = nullptr, Words8 *chi_out = nullptr, size_t nchi = 0);
+// the same for the segments of ONE mixed check in one launch (nseg <= MIX_SEG_MAX, host array): segment s replays nb proofs of
+// (m, k, nchi) on its own schedule (steps_dev, nsteps: resident in HBM), arrays and gadget label (host memory, or null)
+struct TrSegIn {
+  const TrStep *steps_dev; int nsteps; size_t nb, m, k, nchi;
+  const Words8 *init_state, *points, *scalars; Words8 *challenges, *chi; int32_t *tr_bad; const uint8_t *gadget_label;
+};
+void verify_transcript_ragged(hipStream_t st, const TrSegIn *seg, size_t nseg);
 void and_not(hipStream_t st, int32_t *ok, const int32_t *bad, size_t n);
 void or_flag(hipStream_t st, const int32_t *bad, size_t n, int *flag);
 void zero_flag(hipStream_t st, const Words8 *s, size_t n, int *flag);
@@ -426,5 +433,12 @@ void points_compress(hipStream_t st, const Words8 *xy, Words8 *out, size_t n);
 void wire_unpack(hipStream_t st, const uint8_t *proofs, size_t proof_len, const uint8_t *commitments, size_t nb, size_t m,
                  size_t k, int two_phase, Words8 *comp, Words8 *scalars, int32_t *fmt_ok);
 void wire_and_ok(hipStream_t st, int32_t *ok, const int32_t *fmt_ok, const int32_t *dec_ok, size_t nb, size_t nvar);
+// the segments of ONE mixed check (nseg <= MIX_SEG_MAX, host array) in one launch: comp holds the segments' points one after the
+// other (nb x nvar each), scalars / fmt_ok go by the check's proof index
+struct WireSegIn { const uint8_t *proofs, *commitments; size_t proof_len, nb, m, k; bool two_phase; };
+void wire_unpack_ragged(hipStream_t st, const WireSegIn *seg, size_t nseg, Words8 *comp, Words8 *scalars, int32_t *fmt_ok);
+// bad[p] = !fmt_ok[p] | any !dec_ok[p][*] | tr_bad[p] (all indexed as wire_unpack_ragged lays them out); *flag |= bit if any is set
+void wire_fold(hipStream_t st, const WireSegIn *seg, size_t nseg, const int32_t *fmt_ok, const int32_t *dec_ok, const int32_t *tr_bad,
+               int32_t *bad, int *flag, int bit);
 
 }  // namespace bpk

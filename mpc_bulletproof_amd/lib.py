@@ -20,6 +20,13 @@ class VerifyGroup(C.Structure):
                 ("gadget_challenges", C.c_void_p), ("rho", C.c_void_p), ("ok", C.c_void_p)]
 
 
+class WireGroup(C.Structure):
+    """bpgpu_wire_group: one circuit's run of wire-format proofs in a mixed verification call (include/bpgpu.h)"""
+    _fields_ = [("circuit", C.c_void_p), ("nb", C.c_size_t), ("n1", C.c_size_t), ("proof_len", C.c_size_t),
+                ("proofs", C.c_void_p), ("commitments", C.c_void_p), ("init_states", C.c_void_p),
+                ("gadget_label", C.c_void_p), ("rho", C.c_void_p), ("ok", C.c_void_p)]
+
+
 class BpGpuError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
@@ -65,7 +72,7 @@ OPT = {"msm_wp_max": 1, "msm_pip2_single": 2, "verify_no_fuse": 3, "verify_windo
 PROF_NAMES = ["verify_scalars", "fixed_msm", "points_from_boundary", "straus", "verify_finalize", "transcript", "verify_msm",
               "verify_windows", "verify_front", "verify_groups", "verify_back", "verify_verdict", "combined_front_scalars_digits",
               "combined_sort_accum_reduce", "combined_unused", "combined_final", "prover_commit", "prover_polys", "msm_gens", "ipp_begin",
-              "ipp_rounds", "ipp_round_msm", "prove_fs_links", "reserved23"]
+              "ipp_rounds", "ipp_round_msm", "prove_fs_links", "wire_decode"]
 PROF_KINDS = len(PROF_NAMES)
 
 
@@ -772,6 +779,66 @@ class BpGpu:
         arr, _, _ = self._groups(groups, True)
         nf = C.c_size_t(0)
         self._ck(_lib.bpgpu_r1cs_verify_mixed_screened_dev(self.ctx, gens, arr, len(groups), C.byref(nf)))
+        return nf.value
+
+    # ---- mixed queues of wire-format proofs.  A group is a dict with keys circuit, nb, n1, proof_len, proofs, commitments (None
+    # when m == 0), init_states, rho and, for a parametric circuit, gadget_label (bytes, host memory in both forms); the host forms
+    # take bytes, the _dev forms device pointers (and ok: the group's nb int32 verdicts in HBM for the screened call).
+    @staticmethod
+    def _wire_groups(groups, dev):
+        arr = (WireGroup * max(len(groups), 1))()
+        keep, oks = [], []
+        for i, gr in enumerate(groups):
+            g = arr[i]
+            g.circuit = gr["circuit"]
+            g.nb, g.n1, g.proof_len = gr["nb"], gr["n1"], gr["proof_len"]
+            for f in ("proofs", "commitments", "init_states", "rho"):
+                v = gr.get(f)
+                if v is None:
+                    setattr(g, f, None)
+                elif dev:
+                    setattr(g, f, v)
+                else:
+                    b = C.create_string_buffer(bytes(v), max(len(v), 1))
+                    keep.append(b)
+                    setattr(g, f, C.cast(b, C.c_void_p).value)
+            lab = gr.get("gadget_label")
+            if lab is not None:
+                b = C.create_string_buffer((bytes(lab) + bytes(32))[:32], 32)
+                keep.append(b)
+                g.gadget_label = C.cast(b, C.c_void_p).value
+            if dev:
+                g.ok = gr.get("ok")
+            else:
+                ok = (C.c_int32 * max(gr["nb"], 1))()
+                oks.append(ok)
+                g.ok = C.cast(ok, C.c_void_p).value
+        return arr, keep, oks
+
+    def r1cs_verify_mixed_wire_combined(self, gens, groups):
+        """sum over all groups and proofs of rho_p * mega_check_p from wire bytes (64 bytes; all zero: every proof valid; 0xFF x 64:
+        an undecodable proof, an identity at a validated point or a malformed weight)"""
+        arr, keep, _ = self._wire_groups(groups, False)
+        o = _out(64)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_combined(self.ctx, gens, arr, len(groups), o))
+        return bytes(o)[:64]
+
+    def r1cs_verify_mixed_wire_combined_dev(self, gens, groups, d_out):
+        arr, keep, _ = self._wire_groups(groups, True)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_combined_dev(self.ctx, gens, arr, len(groups), d_out))
+
+    def r1cs_verify_mixed_wire_screened(self, gens, groups):
+        """-> ([ok list per group], number of checks that took the per-proof path)"""
+        arr, keep, oks = self._wire_groups(groups, False)
+        nf = C.c_size_t(0)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_screened(self.ctx, gens, arr, len(groups), C.byref(nf)))
+        return [list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value
+
+    def r1cs_verify_mixed_wire_screened_dev(self, gens, groups):
+        """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
+        arr, keep, _ = self._wire_groups(groups, True)
+        nf = C.c_size_t(0)
+        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_screened_dev(self.ctx, gens, arr, len(groups), C.byref(nf)))
         return nf.value
 
     def set_shard(self, rank, world):

@@ -9,7 +9,13 @@ bench.py); M3's 4 098 generators use window 8 on both sides (a window-16 / 20 ta
       one mixed_screened_dev vs one bpgpu_r1cs_verify_screened_dev per circuit in sequence on the same context
   M3  one 2^10-shuffle (parametric) + 4 096 64-bit range proofs: one mixed call vs bpgpu_r1cs_verify_batch_param for the shuffle
       plus a screened call for the ranges
-Prints one JSON line per measurement.  Usage: bench_mixed_verify.py [--only M1,M2,M3] [--pool 2048] [--reps 7] [--m2-sizes 4096,16384,65536] [--window-bits 20]"""
+  W   the M2 mix as WIRE bytes (R1CSProof::to_bytes, compressed commitments, transcript states; sizes of --m2-sizes), three ways on
+      the same queue: (1) one bpgpu_r1cs_verify_mixed_wire_screened_dev; (2) one bpgpu_r1cs_verify_batch_wire_dev per circuit in
+      sequence, all a host can do without (1); (3) bpgpu_r1cs_verify_mixed_screened_dev on operands decoded and challenged
+      beforehand, the floor.  Every accept bit is asserted.
+Prints one JSON line per measurement and appends it to --log (profiles/mixed_verify.log).  --pools-only makes the oracle pools (no
+GPU needed) and exits.
+Usage: bench_mixed_verify.py [--only M1,M2,M3,W] [--pool 2048] [--reps 7] [--m2-sizes 4096,16384,65536] [--window-bits 20]"""
 import argparse
 import json
 import os
@@ -21,6 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import bp_helpers as bh  # noqa: E402
 import oracle_lib as o  # noqa: E402
@@ -93,6 +100,36 @@ def pool_records(name, npool, cache_dir, jobs):
     return out
 
 
+def _wire_of(job):
+    """operands of one pool proof -> (R1CSProof::to_bytes, compressed commitments) through the Python model (a worker process)"""
+    import pymodel as pm
+    pts, sc, k, m_ = job
+    pt = [pm.b2p(pts[64 * i:64 * i + 64]) for i in range(11 + m_ + 2 * k)]
+    p = dict(zip(("A_I1", "A_O1", "S1", "A_I2", "A_O2", "S2"), pt[:6]))
+    p.update(zip(("T_1", "T_3", "T_4", "T_5", "T_6"), pt[6 + m_:11 + m_]))
+    p.update(zip(("t_x", "t_x_blinding", "e_blinding", "a", "b"), (pm.b2s(sc[32 * i:32 * i + 32]) for i in range(5))))
+    p["L_vec"], p["R_vec"] = pt[11 + m_:11 + m_ + k], pt[11 + m_ + k:]
+    return pm.r1cs_proof_to_bytes(p), b"".join(pm.point_compress(v) for v in pt[6:6 + m_])
+
+
+def pool_wire(name, data, npool, cache_dir, jobs):
+    """the wire form of a pool's proofs, made once beside the pool (before any GPU use)"""
+    import multiprocessing as mp
+    import pickle
+    path = os.path.join(cache_dir, f"{name}_{npool}_wire.pkl") if cache_dir else None
+    if path and os.path.exists(path):
+        with open(path, "rb") as f:
+            return pickle.load(f)
+    k, m_ = data["dims"][1], data["dims"][2]
+    with mp.get_context("fork").Pool(jobs) as pool:
+        out = pool.map(_wire_of, [(r[0], r[1], k, m_) for r in data["recs"]], chunksize=32)
+    if path:
+        with open(path + ".tmp", "wb") as f:
+            pickle.dump(out, f)
+        os.replace(path + ".tmp", path)
+    return out
+
+
 class Pool:
     """pool proofs of one circuit, operands in the layouts of bpgpu_r1cs_verify_batch, and the circuit on the device"""
 
@@ -136,6 +173,17 @@ class Pool:
         allocs += [g["rho"], g["ok"]]
         return g, allocs
 
+    def device_wire(self, gpu, name, nb, rho, wires):
+        """the same nb replayed proofs as wire bytes -> bpgpu_wire_group dict of device pointers (the weights are shared with `device`)"""
+        import pymodel as pm
+        reps = [wires[i % len(wires)] for i in range(nb)]
+        g = dict(circuit=self.circ, nb=nb, n1=self.n1, proof_len=len(reps[0][0]), gadget_label=None, rho=rho)
+        g["proofs"] = gpu.to_device(b"".join(r[0] for r in reps))
+        g["commitments"] = gpu.to_device(b"".join(r[1] for r in reps))
+        g["init_states"] = gpu.to_device(pm.Transcript(SPECS[name][2]).state * nb)
+        g["ok"] = gpu.malloc(4 * nb)
+        return g, [g["proofs"], g["commitments"], g["init_states"], g["ok"]]
+
 
 def timed(gpu, fn):
     gpu.sync()
@@ -158,6 +206,21 @@ def ab(gpu, a, b, reps):
     return statistics.median(ta), statistics.median(tb)
 
 
+def abc(gpu, fns, reps):
+    """medians of `reps` interleaved calls of each of fns (rotating the order); every call must report no fallback"""
+    ts = [[] for _ in fns]
+    for _ in range(2):
+        for fn in fns:
+            timed(gpu, fn)
+    for i in range(reps):
+        for j in range(len(fns)):
+            w = (i + j) % len(fns)
+            dt, r = timed(gpu, fns[w])
+            assert not r, ("fallback batches on valid proofs", w, r)
+            ts[w].append(dt)
+    return [statistics.median(t) for t in ts]
+
+
 def all_ok(gpu, groups):
     for g in groups:
         raw = gpu.download(g["ok"], 4 * g["nb"])
@@ -169,9 +232,16 @@ def screened_one(gpu, gens, g):
                                         g["rho"], g["ok"])
 
 
+LOG = None
+
+
 def emit(**kw):
     kw["lib"] = LIB
-    print(json.dumps(kw), flush=True)
+    line = json.dumps(kw)
+    print(line, flush=True)
+    if LOG:
+        with open(LOG, "a") as f:
+            f.write(line + "\n")
 
 
 def main():
@@ -184,11 +254,19 @@ def main():
     ap.add_argument("--pool-cache", default=os.path.join(ROOT, "tools", "_wl", "mixed_pools"),
                     help="directory of the oracle proof pools (made on first use)")
     ap.add_argument("--jobs", type=int, default=min(16, os.cpu_count() or 1), help="processes that make the pools")
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "mixed_verify.log"), help="file the JSON lines are appended to ('' = none)")
+    ap.add_argument("--pools-only", action="store_true", help="make the oracle pools of --only (no GPU needed) and exit")
     args = ap.parse_args()
+    global LOG
+    LOG = args.log or None
     which = set(args.only.split(","))
     t0 = time.perf_counter()
-    names = ["range64"] + (["range16", "multi4x16", "example"] if "M2" in which else []) + (["shuffle1024"] if "M3" in which else [])
+    mix_names = ["range16", "multi4x16", "example"]
+    names = ["range64"] + (mix_names if which & {"M2", "W"} else []) + (["shuffle1024"] if "M3" in which else [])
     data = {n: pool_records(n, args.pool if n != "shuffle1024" else 1, args.pool_cache, args.jobs) for n in names}
+    wires = {n: pool_wire(n, data[n], args.pool, args.pool_cache, args.jobs) for n in ["range64"] + mix_names} if "W" in which else {}
+    if args.pools_only:
+        return
     print(f"# pools ready in {time.perf_counter() - t0:.1f} s ({args.pool} distinct oracle proofs per circuit, replayed; one 2^10-shuffle)",
           file=sys.stderr, flush=True)
     gpu = m.BpGpu(0)
@@ -198,8 +276,8 @@ def main():
     # the generator tables of bench.py (--window-bits, default 20: 130 generators x 13 windows x 2^19 entries = 57 GB at capacity 64)
     gens = gpu.gens_create(o.gens("G", cap), o.gens("H", cap), o.generator(), o.generator(), args.window_bits)
     p64 = Pool(gpu, "range64", data["range64"])
-    if "M2" in which:
-        p16, pm4, pex = (Pool(gpu, n, data[n]) for n in ("range16", "multi4x16", "example"))
+    if which & {"M2", "W"}:
+        p16, pm4, pex = (Pool(gpu, n, data[n]) for n in mix_names)
     if "M1" in which:
         nb = 262144
         g, al = p64.device(gpu, nb, rnd)
@@ -222,6 +300,41 @@ def main():
             ta, tb = ab(gpu, lambda: gpu.r1cs_verify_mixed_screened_dev(gens, groups), per_circuit, args.reps)
             all_ok(gpu, groups)
             emit(metric="M2", proofs=tot, mixed_ms=ta * 1e3, per_circuit_ms=tb * 1e3, speedup=tb / ta, reps=args.reps, window_bits=args.window_bits, pool=args.pool)
+    if "W" in which:
+        for tot in [int(x) for x in args.m2_sizes.split(",")]:
+            parts = [("range64", p64, tot // 2), ("range16", p16, tot // 4), ("multi4x16", pm4, tot * 15 // 100),
+                     ("example", pex, tot - tot // 2 - tot // 4 - tot * 15 // 100)]
+            groups, wgroups = [], []
+            for name, pool, nb in parts:
+                g, al = pool.device(gpu, nb, rnd)
+                wg, wal = pool.device_wire(gpu, name, nb, g["rho"], wires[name])
+                allocs += al + wal
+                groups.append(g)
+                wgroups.append(wg)
+
+            def per_circuit_wire():
+                for wg in wgroups:
+                    gpu.r1cs_verify_batch_wire_dev(gens, wg["circuit"], wg["nb"], wg["n1"], wg["proof_len"], wg["proofs"], wg["commitments"],
+                                                   wg["init_states"], wg["ok"])
+                return 0
+            for wg in wgroups:                                # every leg's accept bits, each from a cleared array
+                gpu.upload(wg["ok"], bytes(4 * wg["nb"]))
+            assert gpu.r1cs_verify_mixed_wire_screened_dev(gens, wgroups) == 0
+            gpu.sync()
+            all_ok(gpu, wgroups)
+            for wg in wgroups:
+                gpu.upload(wg["ok"], bytes(4 * wg["nb"]))
+            per_circuit_wire()
+            gpu.sync()
+            all_ok(gpu, wgroups)
+            t1, t2, t3 = abc(gpu, [lambda: gpu.r1cs_verify_mixed_wire_screened_dev(gens, wgroups), per_circuit_wire,
+                                   lambda: gpu.r1cs_verify_mixed_screened_dev(gens, groups)], args.reps)
+            all_ok(gpu, wgroups)
+            all_ok(gpu, groups)
+            emit(metric="W", proofs=tot, mixed_wire_ms=t1 * 1e3, per_circuit_wire_ms=t2 * 1e3, mixed_decoded_ms=t3 * 1e3,
+                 mixed_wire_per_s=tot / t1, per_circuit_wire_per_s=tot / t2, mixed_decoded_per_s=tot / t3, speedup_over_per_circuit=t2 / t1,
+                 reps=args.reps, window_bits=args.window_bits, pool=args.pool, screen_batch=gpu.get_option("screen_batch"),
+                 stream_lanes=gpu.get_option("stream_lanes"))
     if "M3" in which:
         # 4 098 generators: the largest table window whose table fits the GPU is 8 (1.1 GB; 16 would take 137 GB, 20 1.8 TB), and
         # both sides of M3 use these tables
