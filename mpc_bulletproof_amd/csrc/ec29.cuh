@@ -285,6 +285,114 @@ BP_HD Aff jac_to_aff(const Jac &p) {
   if (jac_is_inf(p)) { Aff a; a.x = fe_zero<FP>(); a.y = fe_zero<FP>(); return a; }
   return jac_to_aff_with_zinv(p, inv(p.Z));
 }
+// ---- affine group law with the inversion left to the caller ----------------------------------------------------------------
+// lambda = num / den; a caller that has many independent operations inverts the product of their denominators once
+// (Montgomery's trick) and pays 3 multiplications per operation for its 1 / den.  A doubling is then 2S + 5M and an addition
+// 1S + 5M with nothing to convert afterwards, against 7M + 4S + ~7M of normalisation for a Jacobian mixed addition.
+// NOT complete: den = 0 (P + P or P - P in the addition, y = 0 in the doubling) is the caller's to exclude.
+// Coordinates are T' (stored normalised, as everywhere); their VALUES grow along a chain, because x3 = lambda^2 - x1 - x2
+// subtracts stored coordinates instead of products: with |lambda^2| <= p and inputs |x|, |y| <= p,
+//   |x(2P)| <= 3p, |x(3P)| <= 5p, |x(4P)| <= 7p, |x(5P)| <= 9p, |x(6P)| <= 11p, |x(7P)| <= 13p, |x(8P)| <= 15p < 2^255,
+//   |y3| <= p + |y of the first operand|: |y(2P)| <= 2p, |y(3P)|, |y(4P)| <= 3p, |y(5P)| .. |y(8P)| <= 4p,
+// inside what a product accepts (|v| < 2^256); every denominator of the {1..8} P chain stays within the 16p of
+// fp_maybe_zero() and canon() (the largest: x(4P) - x(3P), 12p).
+// doubling: lambda = (3 x^2 + a) / (2 y), a = 1
+BP_HD Fp aff_dbl_num(const Aff &p) {
+  Fp xx = fpsqr(p.x);
+  return norm(add_nr(add_nr(add_nr(xx, xx), xx), fe_one<FP>()));   // four tight terms, limbs < 2^31 -> T'
+}
+BP_HD Fp aff_dbl_den(const Aff &p) { return norm(add_nr(p.y, p.y)); }   // T' + T': limbs < 2^30 + 16 -> T'
+// addition p + q: lambda = (y2 - y1) / (x2 - x1); differences of two T' values, limbs in (-2^29 - 16, 2^29 + 16), left
+// un-normalised as in jac_madd_mid (each is one side of products whose other side is tight)
+BP_HD Fp aff_add_num(const Aff &p, const Aff &q) { return sub_nr(q.y, p.y); }
+BP_HD Fp aff_add_den(const Aff &p, const Aff &q) { return sub_nr(q.x, p.x); }
+// x3 = lambda^2 - x1 - x2, y3 = lambda (x1 - x3) - y1; for a doubling x2 = x1.  lambda is a product (tight).
+BP_HD Aff aff_from_lambda(const Fp &lambda, const Aff &p, const Fp &x2) {
+  Aff r;
+  r.x = norm(sub_nr(sub_nr(fpsqr(lambda), p.x), x2));          // tight - T' - T': limbs in (-2^30 - 16, 2^29) -> T'
+  r.y = sub(fpmul(lambda, sub_nr(p.x, r.x)), p.y);             // T' - T' against a tight lambda; product - T' -> T'
+  return r;
+}
+
+// ---- tables {1..8} P of several points, built in affine coordinates ---------------------------------------------------------
+// Entry e holds (e + 1) P.  Every entry past the first is ONE affine operation on earlier entries, in three dependency levels:
+//   level 0: 2P = 2 (P)          level 1: 3P = 2P + P, 4P = 2 (2P)          level 2: 5P = 4P + P, 6P = 4P + 2P, 7P = 4P + 3P, 8P = 2 (4P)
+// (three doublings and four additions per point).  A level inverts the product of the denominators of all its operations over
+// all the points once: T, 2T and 4T operations share an inversion, three inversions per table set.  For P on the curve and not
+// the identity no denominator is zero: the group has prime order, so y(kP) != 0 and x(kP) != x(jP) for 1 <= j < k <= 8.
+// A zero denominator (a caller's point that is not on the curve) is replaced by one and reported, so that the product -- and
+// with it every other point of the set -- stays intact; the entries of the offending point are then meaningless.
+BP_HD int afftab_first(int e) { return e == 1 ? 0 : (e < 4 ? 1 : 3); }                             // first operand's entry
+BP_HD int afftab_second(int e) { return (e == 1 || e == 3 || e == 7) ? -1 : (e == 2 ? 0 : e - 4); }   // second operand's entry, -1: doubling
+BP_COLD void afftab_den_full(Fp *den, int *zero) {
+  *zero = is_zero_exact(*den) ? 1 : 0;
+  if (*zero) *den = fe_one<FP>();
+}
+BP_HD Fp afftab_den_guard(const Fp &den, bool &bad) {
+  if (fp_maybe_zero(den)) {
+    Fp d = fp_hide(den);
+    int zero;
+    afftab_den_full(&d, &zero);
+    if (zero) bad = true;
+    return fp_hide(d);
+  }
+  return den;
+}
+struct AffOp { Aff p; Fp num, den, x2; };
+// Mem: Aff row(j, e) / put(j, e, a) over the entries of point j (entry 0 = P is there on entry), Fp pre(s) / set_pre(s, x)
+// over 4 T slots of staging.  Bit j of `dead`: point j is the identity (its rows are the caller's: all zero) and takes no part.
+// Bit j of `skip` must imply bit j of `dead`; it is the part of `dead` that a whole wave shares (uniform branches on the device).
+// Returns true if a denominator was zero.
+template <int T, class Mem> BP_HD bool afftab_build(const Mem &mem, unsigned skip, unsigned dead) {
+  bool bad = false;
+  auto operation = [&](int j, int e, bool with_num) {
+    AffOp o;
+    o.num = fe_zero<FP>();
+    const int b = afftab_second(e);
+    o.p = mem.row(j, afftab_first(e));
+    if (b < 0) {
+      o.den = aff_dbl_den(o.p);
+      o.x2 = o.p.x;
+      if (with_num) o.num = aff_dbl_num(o.p);
+    } else {
+      const Aff q = mem.row(j, b);
+      o.den = aff_add_den(o.p, q);
+      o.x2 = q.x;
+      if (with_num) o.num = aff_add_num(o.p, q);
+    }
+    o.den = afftab_den_guard(o.den, bad);
+    return o;
+  };
+#pragma unroll 1
+  for (int lvl = 0; lvl < 3; lvl++) {
+    const int lo = 1 << lvl;              // entries [lo, 2 lo)
+    Fp prod = fe_one<FP>();
+#pragma unroll 1
+    for (int j = 0; j < T; j++) {
+      if ((skip >> j) & 1) continue;
+#pragma unroll 1
+      for (int e = lo; e < 2 * lo; e++) {
+        mem.set_pre(j * lo + e - lo, prod);
+        if (!((dead >> j) & 1)) prod = fpmul(prod, operation(j, e, false).den);
+      }
+    }
+    Fp pinv = inv(prod);
+#pragma unroll 1
+    for (int j = T - 1; j >= 0; j--) {
+      if ((skip >> j) & 1) continue;
+#pragma unroll 1
+      for (int e = 2 * lo - 1; e >= lo; e--) {
+        if ((dead >> j) & 1) continue;
+        const AffOp o = operation(j, e, true);
+        const Fp dinv = fpmul(pinv, mem.pre(j * lo + e - lo));
+        pinv = fpmul(pinv, o.den);
+        mem.put(j, e, aff_from_lambda(fpmul(o.num, dinv), o.p, o.x2));
+      }
+    }
+  }
+  return bad;
+}
+
 // y^2 == x^3 + x + b ?
 BP_HD bool aff_on_curve(const Aff &a) {
   Fp B;

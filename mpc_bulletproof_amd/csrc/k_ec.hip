@@ -181,13 +181,17 @@ void segmented_sum(hipStream_t st, const JacRaw *in, JacRaw *out, size_t nb, siz
 // Straus with a doubling chain per lane pays 252 doublings for every 4 points.  Here the phases are split, and every
 // launch carries whatever else of the batch is independent of it, so that one batch is a chain of six launches
 // none of which waits on a serial 16-wave kernel alone:
-//   front    [tables | prep]   tables: lane per TNP points (role-major): {1..8} P_j, normalised to affine with one
-//                              inversion per lane, written as AffRaw rows tab[proof][point][entry]; the points come
-//                              straight from the ABI bytes and are validated here (per-lane verdict in bad_lane).
+//   front    [tables | prep]   tables: lane per TNP points (role-major): {1..8} P_j as AffRaw rows tab[proof][point][entry].
+//                              TNP = 4, 8: built in affine coordinates, three levels of independent doublings / additions with
+//                              one shared inversion per level (afftab_build, ec29.cuh), every entry written straight into its
+//                              row; TNP = 1, 2: a chain of Jacobian mixed additions, normalised with one inversion per lane.
+//                              The points come straight from the ABI bytes and are validated here (per-lane verdict in
+//                              bad_lane); identity and malformed points get all-zero rows.
 //                              prep: the inversion pass of the scalar assembly (vs_prep.cuh), lane per proof.
 //   scalars  k_verify_scalars (k_scalar.hip), wave per proof
 //   windows  one WAVE per proof, lane w = window w (64 signed 4-bit windows): S_w = sum_j d_{j,w} P_j by mixed
-//            additions from the tables -- no doublings
+//            additions from the tables -- no doublings; the scalars are recoded once per point (lane v recodes point v,
+//            the digits travel through LDS) and identity points are skipped by the whole wave
 //   groups   lane per 8 windows: T_g = sum_{i<8} 16^i S_{8g+i}
 //   back     [horner | fixed]  horner: one LANE per proof: sum_g 2^(32 g) T_g (the proof's 224 remaining dependent
 //                              doublings: the longest link of the chain); fixed: the table-lookup MSMs over the
@@ -204,11 +208,93 @@ struct TablesArgs {
   int32_t *bad_lane;        // nb x lanes: 1 = one of the lane's points is malformed (every lane writes its entry)
   int converted;            // points are AffDev rows (validated, Montgomery form) instead of ABI bytes
 };
+// staging per block of 64 lanes, in int32: the Jacobian builder (1 or 2 points per lane) stages whole entries, the affine one
+// (4 or 8) only the prefix products of a level's denominators
+constexpr size_t tables_stage_ints(size_t tnp) { return tnp >= 4 ? 4 * tnp * NL * 64 : tnp * SE * STE * 64; }
+// what afftab_build (ec29.cuh) reads and writes: the rows of the lane's points in `tab`, prefix products in the staging area
+struct AffTabMem {
+  AffRaw *rows;      // the lane's first point, entry 0
+  size_t jstride;    // rows between two points of the lane
+  int32_t *stg;      // the lane's column of the block's staging area
+  __device__ __forceinline__ Aff row(int j, int e) const {
+    const AffRaw *q = rows + j * jstride + e;
+    Aff r;
+#pragma unroll
+    for (int t = 0; t < NL; t++) { r.x.v[t] = q->v[t]; r.y.v[t] = q->v[NL + t]; }
+    return r;
+  }
+  __device__ __forceinline__ void put(int j, int e, const Aff &x) const {
+    AffRaw *q = rows + j * jstride + e;
+#pragma unroll
+    for (int t = 0; t < NL; t++) { q->v[t] = x.x.v[t]; q->v[NL + t] = x.y.v[t]; }
+  }
+  __device__ __forceinline__ Fp pre(int s) const { Fp x; for (int t = 0; t < NL; t++) x.v[t] = stg[(s * NL + t) * 64]; return x; }
+  __device__ __forceinline__ void set_pre(int s, const Fp &x) const { for (int t = 0; t < NL; t++) stg[(s * NL + t) * 64] = x.v[t]; }
+};
+// Lane shapes 4 and 8: {1..8} P_j in affine coordinates, level by level with one inversion per level over all the lane's live
+// points (afftab_build, ec29.cuh: 3 doublings + 4 additions per point, ~7 k instructions, against ~20 k for seven Jacobian
+// mixed additions and their normalisation).  Every entry goes straight into its row of `tab`; later levels read their operands
+// back from there (a lane only ever reads rows it wrote itself: same thread, program order).  Lanes beyond the grid hold
+// identity points only: they compute nothing and touch no row.
 template <int TNP>
-__device__ __forceinline__ void tables_body(const TablesArgs &a, size_t blk) {
+__device__ __forceinline__ void tables_body_aff(const TablesArgs &a, size_t blk) {
   constexpr int TPB = 64;
   const int tid = threadIdx.x;
-  int32_t *stg = a.scratch + blk * (TNP * SE * STE * TPB);
+  size_t i = blk * TPB + tid;
+  const size_t n = a.nb * a.lanes;
+  const bool live = i < n;
+  if (!live) i = n - 1;
+  const size_t r = i / a.nb, p = i - r * a.nb;        // role-major: a wave holds one role of 64 proofs
+  unsigned skip = 0, pinf = 0;   // bit j: wave-uniform / per-lane "point j is the identity (or beyond nvar, or the lane beyond the grid)"
+  bool malformed = false;
+  AffTabMem mem{a.tab + (p * a.nvar + r) * SE, a.lanes * SE, a.scratch + blk * tables_stage_ints(TNP) + tid};
+#pragma unroll 1
+  for (int j = 0; j < TNP; j++) {
+    const size_t v = r + (size_t)j * a.lanes;
+    const bool there = live && v < a.nvar;
+    Aff P;
+    P.x = fe_zero<FP>();
+    P.y = fe_zero<FP>();
+    if (there) {
+      const AffDev *psrc = a.points + p * a.nvar + v;
+      if (a.converted) P = aff_load(psrc);
+      else {
+        uint32_t w[16];
+#pragma unroll
+        for (int t = 0; t < 16; t++) w[t] = psrc->w[t];
+        if (!aff_from_boundary(P, w)) {
+          malformed = true;
+          P.x = fe_zero<FP>();
+          P.y = fe_zero<FP>();
+        }
+      }
+    }
+    const bool inf = aff_is_inf(P);
+    if (inf) pinf |= 1u << j;
+    if (__all(inf)) skip |= 1u << j;
+    if (there) {
+      mem.put(j, 0, P);
+      if (inf) {   // a dead point's rows are all zero: the window sums skip the point on entry 0, the rest is never read
+#pragma unroll 1
+        for (int e = 1; e < SE; e++) mem.put(j, e, P);
+      }
+    }
+  }
+  // A zero denominator needs a point off the curve, and none gets here: ABI bytes pass aff_from_boundary above, converted rows
+  // come from points_from_boundary (which zeroes what fails the curve test) or from the library's own group operations.
+  if (afftab_build<TNP>(mem, skip, pinf)) malformed = true;
+  if (live) {
+    a.bad_lane[p * a.lanes + r] = malformed ? 1 : 0;
+    if (malformed) atomicOr(a.bad, 1);
+  }
+}
+// Lane shapes 1 and 2: a chain of seven Jacobian mixed additions per point, normalised with ONE inversion per lane (three
+// inversions, as the affine form needs them, do not amortise over one or two points)
+template <int TNP>
+__device__ __forceinline__ void tables_body_jac(const TablesArgs &a, size_t blk) {
+  constexpr int TPB = 64;
+  const int tid = threadIdx.x;
+  int32_t *stg = a.scratch + blk * tables_stage_ints(TNP);
   size_t i = blk * TPB + tid;
   const size_t n = a.nb * a.lanes;
   const bool live = i < n;
@@ -294,36 +380,64 @@ __device__ __forceinline__ void tables_body(const TablesArgs &a, size_t blk) {
     }
   }
 }
+template <int TNP>
+__device__ __forceinline__ void tables_body(const TablesArgs &a, size_t blk) {
+  if constexpr (TNP >= 4) tables_body_aff<TNP>(a, blk);
+  else tables_body_jac<TNP>(a, blk);
+}
 // tables (blocks [0, table_blocks)) and the inversion pass of the scalar assembly in one launch
 template <int TNP>
 __global__ void __launch_bounds__(64) k_verify_front(TablesArgs t, unsigned table_blocks, VsPrepArgs prep) {
   if (blockIdx.x < table_blocks) tables_body<TNP>(t, blockIdx.x);
   else vs_prep_body(prep, blockIdx.x - table_blocks);
 }
-// one wave per proof, lane = window
+// one wave per proof, lane = window.  The points are taken in chunks of up to 64: lane v of a chunk loads and recodes the scalar of
+// point v ONCE (every lane used to do that for every point) and leaves the 9 recoded words in LDS, and it looks at entry 0 of the
+// point's table: all zero = the point is the identity (tables_body writes all-zero rows for it), and the whole wave skips the
+// point -- the three identity points of a one-phase proof, the padding of a ragged MSM.  The rows of a live point are never the
+// identity ((e + 1) P != 0 for e < 8 in a group of prime order), so the fetched row needs no test.
 __global__ void __launch_bounds__(64) k_verify_windows(const AffRaw *tab, const uint32_t *scalars /* nb x nvar x 8 words */,
                                                        size_t nvar, JacRaw *winsum) {
+  static_assert(32 % SW == 0 && num_windows<SW>() == 64, "a window lies inside one recoded word; one lane per window");
+  __shared__ uint32_t rec[64 * 9];   // [point of the chunk][recoded word]: stride 9 words, conflict-free on the way in
   const size_t p = blockIdx.x;
   const int w = threadIdx.x;
+  const int wk = (w * SW) >> 5, wsft = (w * SW) & 31;   // recode_digit<SW>(sp, w) = ((sp[wk] >> wsft) & 15) - 8
   Xyzz acc = xyzz_inf();       // additions only: extended-Jacobian accumulator (ec29.cuh)
 #pragma unroll 1
-  for (size_t v = 0; v < nvar; v++) {
-    uint32_t s[8], sp[9];
-    const uint32_t *src = scalars + (p * nvar + v) * 8;
+  for (size_t base = 0; base < nvar; base += 64) {
+    const int cnt = (int)(nvar - base < 64 ? nvar - base : 64);
+    bool alive = false;
+    if (w < cnt) {
+      uint32_t s[8], sp[9];
+      const uint32_t *src = scalars + (p * nvar + base + w) * 8;
 #pragma unroll
-    for (int t = 0; t < 8; t++) s[t] = src[t];
-    recode_add_k<SW>(sp, s);
-    const int dg = recode_digit<SW>(sp, w);
-    if (dg != 0) {
-      const AffRaw *e = tab + (p * nvar + v) * SE + ((dg < 0 ? -dg : dg) - 1);
-      Aff q;
+      for (int t = 0; t < 8; t++) s[t] = src[t];
+      recode_add_k<SW>(sp, s);
 #pragma unroll
-      for (int t = 0; t < NL; t++) { q.x.v[t] = e->v[t]; q.y.v[t] = e->v[NL + t]; }
-      if (!aff_is_inf(q)) {
+      for (int t = 0; t < 9; t++) rec[w * 9 + t] = sp[t];
+      const AffRaw *e0 = tab + (p * nvar + base + w) * SE;
+      int32_t o = 0;
+#pragma unroll
+      for (int t = 0; t < 2 * NL; t++) o |= e0->v[t];
+      alive = o != 0;
+    }
+    const unsigned long long live = __ballot(alive);
+    __syncthreads();           // (the block is one wave)
+#pragma unroll 1
+    for (int v = 0; v < cnt; v++) {
+      if (!((live >> v) & 1)) continue;
+      const int dg = (int)((rec[v * 9 + wk] >> wsft) & ((1u << SW) - 1)) - (1 << (SW - 1));
+      if (dg != 0) {
+        const AffRaw *e = tab + (p * nvar + base + v) * SE + ((dg < 0 ? -dg : dg) - 1);
+        Aff q;
+#pragma unroll
+        for (int t = 0; t < NL; t++) { q.x.v[t] = e->v[t]; q.y.v[t] = e->v[NL + t]; }
         if (dg < 0) q.y = neg(q.y);
         acc = xyzz_madd_nzq(acc, q);
       }
     }
+    __syncthreads();           // the next chunk overwrites rec
   }
   raw_store(&winsum[p * 64 + w], xyzz_to_jac(acc));
 }
@@ -515,9 +629,12 @@ __global__ void __launch_bounds__(64) k_verify_verdict_q(const JacRaw *varsum, c
     for (int j = 0; j < 8; j++) { mega[2 * p].w[j] = w[j]; mega[2 * p + 1].w[j] = w[8 + j]; }
   }
 }
-// points per table lane: 8 = fewest instructions (one inversion per 8 points), 4 (default) = half the dependency chain of
-// the front launch for +1.3 % instructions per batch, 1 (latency mode) = 7 additions + one inversion per lane, the shortest
-// chain (a lone batch: 0.665 ms against 0.715 ms with 2).  VerifyWp::table_np (BPGPU_OPT_TABLE_NP) overrides.
+// points per table lane.  8 = fewest instructions (affine builder: three inversions per 8 points; the front launch 6.68e6 VALU
+// wave-instructions per 1 024-proof step against 9.78e6 at 4), but 48 table waves whose chain is 293 us alone against 96 waves
+// of 215 us: with twenty batches in flight the longer link costs more than the instructions save.  Same machine, same job,
+// five alternating runs each (profiles/affine_tables.log): 2 048 steps 2.957 M/s at 4 against 2.808 at 8 (the Jacobian builder
+// at 4: 2.863), bursts of 20 steps 2.775 against 2.635 (2.701).  So 4 stays the default; 1 (latency mode) = 7 additions + one
+// inversion per lane, the shortest chain for a lone batch.  VerifyWp::table_np (BPGPU_OPT_TABLE_NP) overrides.
 static int wp_tnp(const VerifyWp &v) {
   const int t = v.table_np ? v.table_np : (v.latency_mode ? 1 : 4);
   return t == 8 ? 8 : (t == 2 ? 2 : (t == 1 ? 1 : 4));
@@ -531,7 +648,7 @@ size_t verify_wp_scratch_bytes(size_t nb, size_t nvar) {
   size_t stage = 0, lanes_max = 0;
   for (size_t tnp : {(size_t)1, (size_t)2, (size_t)4, (size_t)8}) {
     const size_t lanes = (nvar + tnp - 1) / tnp, blocks = (nb * lanes + 63) / 64;
-    const size_t b = al256(blocks * tnp * SE * STE * 64 * 4);
+    const size_t b = al256(blocks * tables_stage_ints(tnp) * 4);
     if (b > stage) stage = b;
     if (lanes > lanes_max) lanes_max = lanes;
   }
@@ -548,7 +665,7 @@ static WpLayout wp_layout(const VerifyWp &v) {
   L.t.points = v.points_abi; L.t.converted = v.points_converted ? 1 : 0; L.t.nb = v.nb; L.t.nvar = v.nvar; L.t.lanes = (v.nvar + tnp - 1) / tnp; L.t.bad = v.bad;
   const size_t nblk = (v.nb * L.t.lanes + 63) / 64;
   uint8_t *sp = (uint8_t *)v.scratch;
-  L.t.scratch = (int32_t *)sp; sp += al256(nblk * tnp * SE * STE * 64 * 4);
+  L.t.scratch = (int32_t *)sp; sp += al256(nblk * tables_stage_ints(tnp) * 4);
   L.t.tab = (AffRaw *)sp; sp += al256(v.nb * v.nvar * SE * sizeof(AffRaw));
   L.winsum = (JacRaw *)sp; sp += al256(v.nb * 64 * sizeof(JacRaw));
   L.varsum = (JacRaw *)sp; sp += al256(v.nb * sizeof(JacRaw));
