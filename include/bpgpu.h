@@ -477,6 +477,37 @@ int bpgpu_r1cs_prove_fs2_finish_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const b
                                     const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
                                     const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
                                     void *challenges_out, void *states_out);
+/* Prover::constraints_satisfied (prover.rs:405-409) for nb provers of ONE circuit, where their witnesses lie: the provers above never
+ * read the rows' constants and take a_O from the caller, so a wrong witness yields a well-formed proof that fails only at the verifier;
+ * this call says so before the proof is paid for.  Circuits of bpgpu_circuit_create / _ark and of bpgpu_circuit_create_param (any
+ * nchi <= 8).  With n = ALL the circuit's multipliers (both phases), m its commitments, q its constraints:
+ *   a_L, a_R, a_O  nb x n         ark-ff Montgomery form, as bpgpu_r1cs_prove_fs takes them (one set of device buffers serves the
+ *                                 check and the proof); may be NULL when n == 0
+ *   v              nb x m         the committed VALUES (not the commitments), ark form; may be NULL when m == 0
+ *   gadget_challenges  nb x nchi x 32  canonical LE for a parametric circuit (as bpgpu_r1cs_prover_session_polys_param), else NULL
+ * Row r of prover p evaluates to e[p][r] = sum over the row's terms of coeff * value, the value of a `One` term being 1 and, for a
+ * parametric circuit, coeff = c0 + sum_j chi_j c_j.  The coefficients are taken as the circuit was created with them: the minus that
+ * the flattening puts on w_V and w_c is no part of a row.
+ *   ok             nb x int32     1 iff first_bad_row and first_bad_gate are both -1
+ *   first_bad_row  (optional) nb x int64   the smallest r with e[p][r] != 0, or -1
+ *   first_bad_gate (optional) nb x int64   the smallest i with a_L[i] a_R[i] != a_O[i], or -1.  The reference has no such test: its
+ *                                 Prover::multiply / allocate_multiplier compute a_O themselves.  Here a_O crosses the ABI, so the
+ *                                 check covers it.
+ *   residuals      (optional) nb x q x 32  canonical LE: e itself, for a caller that debugs a gadget; NULL: nothing per row is stored
+ * The row-major view of the circuit that these calls evaluate is built on the device the first time one of them (or
+ * bpgpu_mpc_constraints_eval) sees the handle -- that first call waits for the build, also in the `_dev` form -- and lives in the handle
+ * until bpgpu_circuit_destroy; bpgpu_circuit_create* costs what it did for callers that never ask.  A handle may be checked from
+ * several contexts of its device at once.
+ * Refusals, before anything is launched: BPGPU_E_ARG for a null required pointer, for gadget challenges given to a numeric circuit or
+ * missing for a parametric one; BPGPU_E_LEN for n or m above 2^25 - 1; nb == 0: BPGPU_OK.  A non-canonical limb gives BPGPU_E_ARG in
+ * the host form and raises bpgpu_input_flag in the `_dev` form (every operand and result a device pointer; asynchronous on the
+ * context's stream).  A failed call leaves no pool memory behind. */
+int bpgpu_r1cs_constraints_satisfied(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *a_L, const uint8_t *a_R,
+                                     const uint8_t *a_O, const uint8_t *v, const uint8_t *gadget_challenges, int32_t *ok,
+                                     int64_t *first_bad_row, int64_t *first_bad_gate, uint8_t *residuals);
+int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R,
+                                         const void *a_O, const void *v, const void *gadget_challenges, void *ok, void *first_bad_row,
+                                         void *first_bad_gate, void *residuals);
 /* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
  * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
  * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step
@@ -529,6 +560,15 @@ int bpgpu_mpc_prover_ipp_begin(bpgpu_ctx *ctx, bpgpu_prover *session, const bpgp
                                const uint8_t *u, const uint8_t *w, bpgpu_ipp **out);
 int bpgpu_mpc_ipp_mask(bpgpu_ctx *ctx, bpgpu_ipp *ipp, const uint8_t *triples, uint8_t *masked);
 int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *ipp, const uint8_t *opened, uint8_t *L, uint8_t *R);
+/* bpgpu_mpc_constraints_eval -- one party's local half of MpcProver::constraints_satisfied (mpc_prover.rs:556-568), which evaluates
+ * every row on shares and opens them in one batch: a_L, a_R, a_O nb x 3 x n and v nb x 3 x m (the committed values' planes; NULL when
+ * m == 0) in the plane layout above, gadget_challenges nb x nchi x 32 B canonical LE for a parametric circuit, else NULL ->
+ * residuals nb x 3 x q, ark form: row r on plane k of proof p at [(3 p + k) q + r].  Every plane is evaluated alike; the constant of a
+ * `One` term goes to the modifier plane only (the rule for public constants above).  The host opens the planes (open_batch) and
+ * compares with zero.  The gate identity a_L a_R = a_O is NOT checked: on shares it is a Beaver product, which needs a triple and an
+ * opening of its own -- the fabric's business.  Refusals and the circuit's row-major view: as bpgpu_r1cs_constraints_satisfied. */
+int bpgpu_mpc_constraints_eval(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *a_L, const uint8_t *a_R,
+                               const uint8_t *a_O, const uint8_t *v, const uint8_t *gadget_challenges, uint8_t *residuals);
 
 /* out[i] = scalars[i] * (curve generator) -- GeneratorsChain::next (generators.rs:112-124),
  * Q = w * B (prover.rs:687), PedersenGens::commit with B = B_blinding (generators.rs:41-43,61-70) */

@@ -184,6 +184,13 @@ struct bpgpu_circuit {
   size_t q = 0, n = 0, m = 0, nnz = 0, nchi = 0;   // nchi: gadget challenges the coefficients are affine in (kernels.h CircuitDev)
   uint32_t *col_ptr = nullptr, *row = nullptr;
   Words8 *coeff = nullptr;
+  // the row-major view (kernels.h RowsDev), built by the first bpgpu_r1cs_constraints_satisfied / bpgpu_mpc_constraints_eval that sees
+  // the handle and kept until bpgpu_circuit_destroy.  A handle serves several contexts of a device, each with its own mutex: view_mu
+  // guards the one-time build (taken with the calling context's mutex held, never the other way round).
+  mutable std::mutex view_mu;
+  mutable void *view_mem = nullptr;
+  mutable RowsDev view{};
+  mutable bool view_ready = false;
 };
 
 #define HIPCK(ctx, call)                                                                    \
@@ -1445,6 +1452,7 @@ void bpgpu_circuit_destroy(bpgpu_ctx *ctx, bpgpu_circuit *c) {
   if (!c) return;
   if (ctx) { std::lock_guard<std::mutex> lk(ctx->mu); hipStreamSynchronize(ctx->st); hipStreamSynchronize(ctx->st2); }
   hipFree(c->coeff);     // [coeff | col_ptr | row] is one allocation
+  hipFree(c->view_mem);  // the row-major view, if a call ever asked for it
   delete c;
 }
 static CircuitDev circuit_dev(const bpgpu_circuit *c) {
@@ -1473,6 +1481,132 @@ int bpgpu_flatten_constraints(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb,
   scalars_check(ctx->st, (Words8 *)dz, nb, ctx->d_flag);
   flatten(ctx->st, circuit_dev(c), nb, (Words8 *)dz, 8, dL, dR, dO, dV, dC, (int32_t *)dzp);
   return checked_download(ctx, {{wL, dL, nb * n * 32}, {wR, dR, nb * n * 32}, {wO, dO, nb * n * 32}, {wV, dV, nb * m * 32}, {wc, dC, wc ? nb * 32 : 0}});
+}
+
+/* ---- Prover::constraints_satisfied (prover.rs:405-409) and a party's half of MpcProver::constraints_satisfied (mpc_prover.rs:538-568):
+ * the witnesses of nb provers against the rows of their circuit (k_rows.hip) -------------------------------------------------------- */
+// the row-major view of c, built on first use (ctx->mu held).  The build ends with a wait: the number of long rows sizes every later
+// launch, and a second context must not read a view that the first one's stream is still writing.
+static int circuit_view(bpgpu_ctx *ctx, const bpgpu_circuit *c, RowsDev *out) {
+  std::lock_guard<std::mutex> lk(c->view_mu);
+  if (!c->view_ready) {
+    const CircuitDev cd = circuit_dev(c);
+    if (!rows_view_supported(cd)) return BPGPU_E_LEN;
+    void *mem = nullptr;
+    if (hipMalloc(&mem, rows_view_bytes(cd)) != hipSuccess) { (void)hipGetLastError(); return BPGPU_E_OOM; }
+    RowsDev v{};
+    const uint32_t *nlong_dev = nullptr;
+    uint32_t nlong = 0;
+    rows_view_build(ctx->st, cd, mem, &v, &nlong_dev);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nlong, nlong_dev, 4, hipMemcpyDeviceToHost, ctx->st) != hipSuccess ||
+        hipStreamSynchronize(ctx->st) != hipSuccess) {
+      ctx->err = "building the row-major view of a circuit failed";
+      (void)hipFree(mem);
+      return BPGPU_E_DEVICE;
+    }
+    v.nlong = nlong;
+    c->view_mem = mem; c->view = v; c->view_ready = true;
+  }
+  *out = c->view;
+  return BPGPU_OK;
+}
+// the refusals that depend on arguments alone (BPGPU_OK with nb == 0: nothing to do)
+static int rows_check(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R, const void *a_O, const void *v,
+                      const void *gadget_challenges, const void *out) {
+  if (!ctx || !c) return BPGPU_E_ARG;
+  if ((c->nchi != 0) != (gadget_challenges != nullptr)) return BPGPU_E_ARG;   // challenges for a numeric circuit, or none for a parametric one
+  if (!nb) return BPGPU_OK;
+  if (!out || (c->n && (!a_L || !a_R || !a_O)) || (c->m && !v)) return BPGPU_E_ARG;
+  return BPGPU_OK;
+}
+namespace {
+struct PoolBlock {   // one pool buffer, given back on the way out (stream-ordered reuse)
+  bpgpu_ctx *ctx; void *p = nullptr;
+  explicit PoolBlock(bpgpu_ctx *c) : ctx(c) {}
+  ~PoolBlock() { pool_release(ctx, p); }
+};
+struct RowsIo { const void *a_L, *a_R, *a_O, *v, *chi; void *ok, *first_row, *first_gate, *resid; };   // src_dev: all in HBM
+}  // namespace
+// ctx->mu held, arguments checked, nb > 0.  planes == 1: the check (ok / first_row / first_gate / resid in HBM, the last three optional;
+// resid plain canonical); planes == 3: a party's evaluation (resid only: nb x 3 x q, ark form).  Asynchronous but for the one-time
+// build of the view.
+static int rows_locked(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, int planes, const RowsIo &io, bool src_dev) {
+  RowsDev view;
+  CK(circuit_view(ctx, c, &view));
+  const size_t nv = nb * (size_t)planes, n = c->n, m = c->m, nchi = c->nchi;
+  if (!rows_eval_fits(view, nv)) return BPGPU_E_LEN;
+  hipStream_t st = ctx->st;
+  // staging: [a_L | a_R | a_O | v] (ark in, plain after the conversion), the gadget challenges, the two words per prover
+  const size_t nval = 3 * nv * n + nv * m;
+  PoolBlock blk(ctx);
+  if (!pool_alloc(ctx, &blk.p, (nval + nb * nchi) * 32 + 2 * nv * 4)) return BPGPU_E_OOM;
+  Words8 *dL = (Words8 *)blk.p, *dR = dL + nv * n, *dO = dR + nv * n, *dV = dO + nv * n, *dchi = dV + nv * m;
+  uint32_t *dbad = (uint32_t *)(dchi + nb * nchi);
+  CK(copy_in(ctx, dL, io.a_L, nv * n * 32, src_dev));
+  CK(copy_in(ctx, dR, io.a_R, nv * n * 32, src_dev));
+  CK(copy_in(ctx, dO, io.a_O, nv * n * 32, src_dev));
+  CK(copy_in(ctx, dV, io.v, nv * m * 32, src_dev));
+  CK(copy_in(ctx, dchi, io.chi, nb * nchi * 32, src_dev));
+  scalars_from_ark(st, dL, dL, nval, ctx->d_flag);                     // in place, as the prover's commit does
+  scalars_check(st, dchi, nb * nchi, ctx->d_flag);
+  const Words8 *chi = nchi ? dchi : nullptr;
+  if (planes == 1) {
+    HIPCK(ctx, hipMemsetAsync(dbad, 0xFF, 2 * nb * 4, st));
+    rows_eval(st, view, n, m, nchi, nb, 1, dL, dR, dO, dV, chi, dbad, (Words8 *)io.resid);
+    rows_gates(st, nb, n, dL, dR, dO, dbad + nb);
+    rows_verdict(st, nb, dbad, dbad + nb, (int32_t *)io.ok, (int64_t *)io.first_row, (int64_t *)io.first_gate);
+  } else {
+    rows_eval(st, view, n, m, nchi, nv, 3, dL, dR, dO, dV, chi, nullptr, (Words8 *)io.resid);
+    scalars_to_ark(st, (const Words8 *)io.resid, (Words8 *)io.resid, nv * view.q, ctx->d_flag);
+  }
+  return launch_ok(ctx);
+}
+int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R, const void *a_O,
+                                         const void *v, const void *gadget_challenges, void *ok, void *first_bad_row, void *first_bad_gate,
+                                         void *residuals) {
+  return noexcept_abi([&]() -> int {
+    CK(rows_check(ctx, c, nb, a_L, a_R, a_O, v, gadget_challenges, ok));
+    if (!nb) return BPGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call
+    return rows_locked(ctx, c, nb, 1, {a_L, a_R, a_O, v, gadget_challenges, ok, first_bad_row, first_bad_gate, residuals}, true);
+  });
+}
+int bpgpu_r1cs_constraints_satisfied(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *a_L, const uint8_t *a_R,
+                                     const uint8_t *a_O, const uint8_t *v, const uint8_t *gadget_challenges, int32_t *ok,
+                                     int64_t *first_bad_row, int64_t *first_bad_gate, uint8_t *residuals) {
+  return noexcept_abi([&]() -> int {
+    CK(rows_check(ctx, c, nb, a_L, a_R, a_O, v, gadget_challenges, ok));
+    if (!nb) return BPGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    // the results' staging: ok, then the optional ones
+    const size_t b_ok = (nb * 4 + 255) / 256 * 256, b_idx = (nb * 8 + 255) / 256 * 256, b_res = residuals ? nb * c->q * 32 : 0;
+    PoolBlock out(ctx);
+    if (!pool_alloc(ctx, &out.p, b_ok + 2 * b_idx + b_res)) return BPGPU_E_OOM;
+    uint8_t *dok = (uint8_t *)out.p, *drow = dok + b_ok, *dgate = drow + b_idx, *dres = dgate + b_idx;
+    CK(flag_reset(ctx));
+    CK(rows_locked(ctx, c, nb, 1, {a_L, a_R, a_O, v, gadget_challenges, dok, first_bad_row ? drow : nullptr, first_bad_gate ? dgate : nullptr,
+                                   residuals ? dres : nullptr}, false));
+    return checked_download(ctx, {{ok, dok, nb * 4}, {first_bad_row, drow, first_bad_row ? nb * 8 : 0},
+                                  {first_bad_gate, dgate, first_bad_gate ? nb * 8 : 0}, {residuals, dres, b_res}});
+  });
+}
+int bpgpu_mpc_constraints_eval(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
+                               const uint8_t *v, const uint8_t *gadget_challenges, uint8_t *residuals) {
+  return noexcept_abi([&]() -> int {
+    CK(rows_check(ctx, c, nb, a_L, a_R, a_O, v, gadget_challenges, residuals));
+    if (!nb) return BPGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t b_res = nb * 3 * c->q * 32;
+    PoolBlock out(ctx);
+    if (!pool_alloc(ctx, &out.p, b_res)) return BPGPU_E_OOM;
+    CK(flag_reset(ctx));
+    CK(rows_locked(ctx, c, nb, 3, {a_L, a_R, a_O, v, gadget_challenges, nullptr, nullptr, nullptr, out.p}, false));
+    return checked_download(ctx, {{residuals, out.p, b_res}});
+  });
 }
 
 /* ---------------------------------------------------------------- per-proof verification: shape, plan, one function per launch route */

@@ -6,7 +6,7 @@
 namespace bpk {
 using namespace bp;
 
-__device__ __forceinline__ Fn load_plain(const Words8 *p) {   // plain canonical words -> Montgomery
+BP_HD Fn load_plain(const Words8 *p) {   // plain canonical words -> Montgomery
   uint32_t w[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) w[j] = p->w[j];
@@ -36,7 +36,7 @@ __device__ __forceinline__ Fn fn_pow_u32(Fn base, uint32_t e) {   // base^e, e >
 // Lazy sums keep limbs small but let the VALUE grow (top limb has ~11 spare bits over a 252-bit
 // modulus): fold the value back into (-eps, (1+eps) n) with one Montgomery multiplication by R mod n.
 // Rule used below: never add more than ~64 reduced values (x 64 lanes of a wave sum) without it.
-__device__ __forceinline__ Fn fn_reduce(const Fn &x) { return mul(x, fe_one<FN>()); }
+BP_HD Fn fn_reduce(const Fn &x) { return mul(x, fe_one<FN>()); }
 // raw limb I/O for device scratch (zpow tables, partial sums)
 __device__ __forceinline__ void raw_put(int32_t *d, const Fn &x) {
 #pragma unroll
@@ -49,6 +49,7 @@ __device__ __forceinline__ Fn raw_get(const int32_t *s) {
   return x;
 }
 // wave-level sum of one Fn per lane (shuffle tree); result in every lane
+#if defined(__HIPCC__)
 __device__ __forceinline__ Fn wave_sum(Fn x) {
 #pragma unroll 1
   for (int off = 32; off > 0; off >>= 1) {
@@ -59,6 +60,7 @@ __device__ __forceinline__ Fn wave_sum(Fn x) {
   }
   return x;
 }
+#endif
 
 // one flattened constraint weight: output o of the column-major circuit against a proof's z-power table (flattened_constraints,
 // prover.rs:342-379; w_V and w_c carry the reference's minus sign)
@@ -73,6 +75,28 @@ __device__ __forceinline__ Fn flatten_column(const CircuitDev &c, size_t o, cons
     if ((++cnt & 15) == 0) acc = fn_reduce(acc);
   }
   if (o >= 3 * c.n) acc = neg(acc);
+  return acc;
+}
+// one constraint row of the row-major view against one prover's witness (Prover::constraints_satisfied, prover.rs:405-409, and a
+// party's local half of mpc_prover.rs:556-568): the terms lo, lo + step, .. below hi of sum coeff * chi_j * value.  The values are
+// the prover's plain canonical planes; `one` is what a `One` term reads (1, or 0 on a share or MAC plane); chi: the prover's
+// gadget challenges (plain canonical words; never read when no term has j > 0).  The stored coefficients carry no sign: the minus
+// of w_V and w_c is flatten_column's.  Lazy like flatten_column: the caller reduces the result (fn_reduce) before it sums further.
+BP_HD Fn eval_row(const RowsDev &rv, uint32_t lo, uint32_t hi, uint32_t step, const Words8 *aL, const Words8 *aR, const Words8 *aO,
+                  const Words8 *v, const Fn &one, const Words8 *chi) {
+  Fn acc = fe_zero<FN>();
+  uint32_t cnt = 0;
+  for (uint32_t t = lo; t < hi; t += step) {
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = rv.coeff[t].w[j];
+    Fn cf = unpack<FN>(w);
+    const uint32_t code = rv.var[t], j = code >> ROWS_CHI_SHIFT, kind = (code >> ROWS_KIND_SHIFT) & 7u, idx = code & ROWS_IDX_MASK;
+    if (j) cf = mul(cf, load_plain(chi + (j - 1)));
+    const Words8 *pl = kind == 0 ? aL : (kind == 1 ? aR : (kind == 2 ? aO : v));
+    acc = add(acc, mul(cf, kind == 4 ? one : load_plain(pl + idx)));
+    if ((++cnt & 15) == 0) acc = fn_reduce(acc);
+  }
   return acc;
 }
 

@@ -92,6 +92,7 @@ __global__ void __launch_bounds__(1024) k_csr_scan(uint32_t *cnt, size_t n1) {
     for (size_t i = full; i < hi; i++) { run += cnt[i]; cnt[i] = run; }
   }
 }
+void csr_scan(hipStream_t st, uint32_t *cnt, size_t n1) { hipLaunchKernelGGL(k_csr_scan, dim3(1), dim3(1024), 0, st, cnt, n1); }
 template <bool ARK>
 __global__ void __launch_bounds__(256) k_csr_scatter(size_t q, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
                                                      const Words8 *coeff_in, size_t n_mul, size_t m, const uint32_t *col_ptr, uint32_t *fill,

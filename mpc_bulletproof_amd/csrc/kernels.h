@@ -226,6 +226,41 @@ void circuit_transpose(hipStream_t st, size_t q, const uint32_t *row_ptr, const 
 void flatten(hipStream_t st, const CircuitDev &c, size_t nb, const Words8 *z, size_t z_stride_words,
              Words8 *wL, Words8 *wR, Words8 *wO, Words8 *wV, Words8 *wc, int32_t *zpow_scratch, const Words8 *chi = nullptr);
 
+// ---- constraint rows against witnesses (k_rows.hip): Prover::constraints_satisfied (prover.rs:405-409) -------------------------
+// The row-major view of a resident circuit: constraint r holds the terms row_ptr[r] .. row_ptr[r + 1], in whatever order the
+// scatter left them (the sums are exact in F_n).  Term t: coeff[t] (a COPY of the column-major coefficient, Montgomery form: a row's
+// coefficients lie next to each other) and var[t] = idx | kind << ROWS_KIND_SHIFT | j << ROWS_CHI_SHIFT -- the variable (kind 0..4 =
+// a_L a_R a_O v One, as the CSR of bpgpu_circuit_create) and the gadget challenge chi_j that scales the term (j = 0: none).
+// long_rows: the nlong rows of more than rows_lane_max() terms, which a wave evaluates instead of a lane.
+constexpr uint32_t ROWS_KIND_SHIFT = 25, ROWS_CHI_SHIFT = 28, ROWS_IDX_MASK = (1u << ROWS_KIND_SHIFT) - 1;
+struct RowsDev {
+  const uint32_t *row_ptr;   // q + 1
+  const uint32_t *var;       // nnz
+  const Words8 *coeff;       // nnz
+  const uint32_t *long_rows; // nlong
+  size_t q, nnz, nlong;
+};
+uint32_t rows_lane_max();    // a row of up to this many terms is one lane's, a longer one a wave's
+bool rows_view_supported(const CircuitDev &c);          // n, m below 2^25 (the packing of var)
+size_t rows_view_bytes(const CircuitDev &c);
+// builds the view of c in mem (rows_view_bytes, 256-byte aligned); *nlong_dev: where the number of long rows lands (inside mem):
+// the caller reads it once the stream has drained and sets view->nlong
+void rows_view_build(hipStream_t st, const CircuitDev &c, void *mem, RowsDev *view, const uint32_t **nlong_dev);
+// e[p][r] for nvirt provers (planes == 3: virtual prover 3 p + k is plane k of proof p, and a `One` term reads 1 on plane 2 only).
+// Operands: plain canonical planes nvirt x n (a_*), nvirt x m (v); chi: nvirt / planes x nchi plain words or nullptr.
+// bad_row (optional): nvirt words, atomicMin of the rows with e != 0 (set to 0xFFFFFFFF by the caller); resid (optional): nvirt x q
+// plain canonical words.  rows_eval_fits: the grid is addressable
+bool rows_eval_fits(const RowsDev &v, size_t nvirt);
+void rows_eval(hipStream_t st, const RowsDev &v, size_t n, size_t m, size_t nchi, size_t nvirt, int planes, const Words8 *aL,
+               const Words8 *aR, const Words8 *aO, const Words8 *vv, const Words8 *chi, uint32_t *bad_row, Words8 *resid);
+// bad_gate[p] = atomicMin of the multipliers i with a_L[i] a_R[i] != a_O[i]
+void rows_gates(hipStream_t st, size_t nb, size_t n, const Words8 *aL, const Words8 *aR, const Words8 *aO, uint32_t *bad_gate);
+// ok[p] = both words untouched; first_row / first_gate (optional): the word, or -1
+void rows_verdict(hipStream_t st, size_t nb, const uint32_t *bad_row, const uint32_t *bad_gate, int32_t *ok, int64_t *first_row,
+                  int64_t *first_gate);
+// the scan of circuit_transpose on its own (k_scalar.hip k_csr_scan): cnt[0] = 0, cnt[i + 1] = count of i -> cnt[i + 1] = end of i
+void csr_scan(hipStream_t st, uint32_t *cnt, size_t n1);
+
 // ---- R1CS prover polynomials (r1cs/prover.rs:587-619, 659-672) -----------------------------------
 // polys: raw Montgomery limbs, layout [6][nb][n][9]: l1 l2 l3 r0 r1 r3
 void prover_polys(hipStream_t st, const CircuitDev &c, size_t nb, const Words8 *y, const Words8 *y_inv,

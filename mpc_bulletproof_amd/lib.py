@@ -586,6 +586,25 @@ class BpGpu:
                                                       d_a_O, d_s_L, d_s_R, d_vector_keys, d_v_blinding, d_blindings, d_points, d_scalars,
                                                       d_wire, d_ch, d_states_out))
 
+    def r1cs_constraints_satisfied(self, circuit, nb, q, a_L, a_R, a_O, v=None, gadget_challenges=None, want_residuals=False):
+        """Prover::constraints_satisfied for nb provers of a circuit of q constraints (include/bpgpu.h
+        bpgpu_r1cs_constraints_satisfied): witness planes nb x n and the committed values nb x m in ark-ff Montgomery form, gadget
+        challenges nb x nchi x 32 B canonical LE for a parametric circuit -> (ok, first_bad_row, first_bad_gate as lists of nb
+        integers, -1 = none; residuals nb x q x 32 B canonical LE or None)"""
+        ok, row, gate = (C.c_int32 * max(nb, 1))(), (C.c_int64 * max(nb, 1))(), (C.c_int64 * max(nb, 1))()
+        res = _out(32 * nb * q) if want_residuals else None
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_constraints_satisfied(self.ctx, circuit, nb, opt(a_L), opt(a_R), opt(a_O), opt(v), opt(gadget_challenges), ok,
+                                                       row, gate, res))
+        return list(ok)[:nb], list(row)[:nb], list(gate)[:nb], bytes(res)[:32 * nb * q] if want_residuals else None
+
+    def r1cs_constraints_satisfied_dev(self, circuit, nb, d_a_L, d_a_R, d_a_O, d_ok, d_v=None, d_gadget_challenges=None, d_first_bad_row=None,
+                                       d_first_bad_gate=None, d_residuals=None):
+        """the same on device pointers (ok nb x int32, the indices nb x int64), asynchronous on the context's stream; a malformed
+        operand raises input_flag()"""
+        self._ck(_lib.bpgpu_r1cs_constraints_satisfied_dev(self.ctx, circuit, nb, d_a_L, d_a_R, d_a_O, d_v, d_gadget_challenges, d_ok,
+                                                           d_first_bad_row, d_first_bad_gate, d_residuals))
+
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
 
@@ -599,6 +618,14 @@ class BpGpu:
         self._ck(_lib.bpgpu_mpc_prover_commit(self.ctx, gens, C.byref(h), nb, n_new, opt(a_L), opt(a_R), opt(a_O), opt(s_L), opt(s_R),
                                               _buf(blindings), out))
         return h, bytes(out)[:64 * 9 * nb]
+
+    def mpc_constraints_eval(self, circuit, nb, q, a_L, a_R, a_O, v=None, gadget_challenges=None):
+        """one party's local half of MpcProver::constraints_satisfied (mpc_prover.rs:556-568): operand planes nb x 3 x n, v nb x 3 x m
+        -> the rows' values on the party's planes, nb x 3 x q, for the host to open and compare with zero"""
+        res = _out(32 * nb * 3 * q)
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_mpc_constraints_eval(self.ctx, circuit, nb, opt(a_L), opt(a_R), opt(a_O), opt(v), opt(gadget_challenges), res))
+        return bytes(res)[:32 * nb * 3 * q]
 
     def mpc_prover_polys_mask(self, session, circuit, nb, n, y, z, triples, gadget_challenges=None):
         """mpc_prover.rs:783-829: triples nb x 6 x 3 x 3 x n -> masked d, e (nb x 6 x 2 x 3 x n)"""
