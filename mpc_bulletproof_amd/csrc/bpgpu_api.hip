@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <memory>
 #include <mutex>
@@ -64,8 +65,8 @@ enum WsSlot : int {
   WS_PFS_CH,        // ... chain states, the challenge arrays y z u x w u_1..u_k
   WS_PFS_SC,        // ... blindings and v_blinding (plain), T rows, tb2, t_x t_x_blinding e_blinding
   WS_PFS_PTS,       // ... A_I A_O S and T_1..T_6: sums and boundary bytes
-  WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched_key)
-  WS_PFS_SCHED2,    // bpgpu_r1cs_prove_fs2_begin / _finish: the two-phase schedule (bpgpu_ctx::psched2_key)
+  WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched[0])
+  WS_PFS_SCHED2,    // bpgpu_r1cs_prove_fs2_begin / _finish: the two-phase schedule (bpgpu_ctx::psched[1])
   WS_WIRE_SCHED,    // bpgpu_r1cs_verify_mixed_wire_*: the transcript schedules of a call's groups (on the calling context; the lanes read it)
   WS_COUNT
 };
@@ -107,12 +108,9 @@ struct bpgpu_ctx {
   // device-transcript schedule cache (m, k, padded_n) -> steps already resident in WS_SCHED
   size_t sched_key[3] = {(size_t)-1, (size_t)-1, (size_t)-1};
   int sched_len = 0;
-  // the prover's schedule (bpgpu_r1cs_prove_fs): (m, padded_n) -> steps resident in WS_PFS_SCHED, and its three slices
-  size_t psched_key[2] = {(size_t)-1, (size_t)-1};
-  int psched_cut[4] = {0, 0, 0, 0};
-  // ... and the two-phase one (bpgpu_r1cs_prove_fs2_begin / _finish) in WS_PFS_SCHED2, with its four slices
-  size_t psched2_key[2] = {(size_t)-1, (size_t)-1};
-  int psched2_cut[5] = {0, 0, 0, 0, 0};
+  // the prover's schedules (prover_schedule), [0] of bpgpu_r1cs_prove_fs in WS_PFS_SCHED, [1] of bpgpu_r1cs_prove_fs2_begin / _finish in
+  // WS_PFS_SCHED2: (m, padded_n) -> steps resident, and their three / four slices
+  struct { size_t key[2] = {(size_t)-1, (size_t)-1}; int cut[5] = {0, 0, 0, 0, 0}; } psched[2];
   // bpgpu_r1cs_verify_mixed_wire_*: page-locked staging of a call's schedules and the mark of its upload (the next call waits for
   // the mark before it refills the staging -- passed long before, except when _dev calls follow each other without a bpgpu_sync)
   void *wsched_host = nullptr;
@@ -3681,208 +3679,255 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
   s->n = n; s->m = m;
   return BPGPU_OK;
 }
-/* ---- Prover::prove (r1cs/prover.rs:412-727) in ONE call for nb provers of a circuit without randomized constraints: the phase
- * commitments, the polynomial build, the T commitments, t(x) and the blindings, the IPP session and its rounds chained on the
- * context's stream with the Fiat-Shamir transcript on the device between them (k_prover_transcript in three slices) -- the host
- * neither hashes nor waits until the proofs are complete.  The stages are the cores of the staged entry points above, fed from
- * HBM; what is new are the transcript slices and the links of k_prove_fs.hip. ------------------------------------------------ */
+/* ---- Prover::prove (r1cs/prover.rs:412-727) for nb provers with the Fiat-Shamir transcript on the device: in ONE call for a circuit
+ * without randomized constraints (bpgpu_r1cs_prove_fs), in TWO around the host's gadget for a two-phase circuit with one gadget
+ * challenge (bpgpu_r1cs_prove_fs2_begin = :420-501, the phase-1 commitments and the chain up to that challenge; _finish = :515-727).
+ * From a proof's last commitment phase on both are ONE chain, prove_fs_chain_locked: the commitments, the polynomial build, the T
+ * commitments, t(x) and the blindings, the IPP session and its rounds on the context's stream, with the transcript on the device
+ * between them (k_prover_transcript, a slice of the schedule each time) -- the host neither hashes nor waits until the proofs are
+ * complete.  The stages are the cores of the staged entry points above, fed from HBM; what is new are the transcript slices and the
+ * links of k_prove_fs.hip.  A two-phase session carries the chain state, the challenge, the phase-1 blinding factors and commitments
+ * from _begin to _finish in HBM: _finish_dev may follow _begin_dev on the stream without a wait. ----------------------------------- */
 namespace {
-struct ProveFsIo {   // every pointer in HBM
-  const uint8_t *states_in, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *v_blinding, *blindings;
-  uint8_t *proof_points, *proof_scalars, *wire, *challenges_out, *states_out;
+// The operands and results of an entry point as it was given them -- in host memory, or in HBM (the *_dev forms) -- and, for the
+// _locked functions, always in HBM.  states_in: the one-phase call's and _begin's (the session carries the chain to _finish)
+struct ProveFsIo {
+  const void *states_in, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *v_blinding, *blindings;
+  void *proof_points, *proof_scalars, *wire, *challenges_out, *states_out;
+};
+struct ProveFs2BeginIo {
+  const void *states_in;
+  const uint8_t *gadget_label;   // host memory in every form
+  const void *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *blindings;
+  void *commitments, *chi_out, *states_out;
 };
 struct ProveFsDims { size_t n, m, padded_n, k; };
+struct Fs2Arrays { uint64_t *states; Words8 *chi, *bl1, *A1; };
+struct ProverSched { const TrStep *steps; const int *cut; };   // resident step list; slice j = steps [cut[j], cut[j + 1])
+// what the one-phase call | a two-phase _finish hand the chain
+struct ProveFsPhase {
+  uint64_t *states;               // the chain states: the workspace's | the session's
+  ProverSched sched;              // the one-phase | the two-phase schedule ...
+  int slice;                      // ... and its slice that absorbs this phase's commitments and draws y, z: 0 | 1
+  const Words8 *chi, *bl1, *A1;   // nullptr | the session's gadget challenge, phase-1 blinding factors and phase-1 commitments
+  size_t n_commit, n1;            // multipliers to commit: n | n - n1;  the IPP's G_factors = [1; n1] ++ [u; ..]: n | n1
+};
+struct ProveFsWs {   // the chain's workspace
+  uint64_t *states;                     // WS_PFS_CH: nb chain states (the one-phase call's), ...
+  Words8 *ch, *uch;                     // ... y z u x w: nb each; then u_1..u_k
+  Words8 *bl, *vb, *rows, *tb2, *sc3;   // WS_PFS_SC: nb x 8 blindings, nb x m v_blinding, nb x 10 T rows, nb tb2, nb x 3 t_x t_x_blinding e_blinding
+  Words8 *T;                            // WS_PFS_PTS: nb x 5 T points, ...
+  JacRaw *Tres;                         // ... and their Jacobian sums
+  void *lr, *zero;                      // WS_FS_CH: the rounds' L, R;  WS_PROOF_BAD
+};
 }  // namespace
+static const uint8_t *u8(const void *p) { return (const uint8_t *)p; }
 static ProveFsDims prove_fs_dims(const bpgpu_circuit *c) {
   ProveFsDims d{c->n, c->m, 1, 0};
   while (d.padded_n < d.n) { d.padded_n <<= 1; d.k++; }
   return d;
 }
+static Fs2Arrays fs2_arrays(const bpgpu_prover *s) { return {(uint64_t *)s->fs2, s->fs2 + s->nb, s->fs2 + 2 * s->nb, s->fs2 + 5 * s->nb}; }
+static int prove_fs_workspace(bpgpu_ctx *ctx, size_t nb, const ProveFsDims &d, ProveFsWs *w) {
+  void *dchs, *dscs, *dpts;
+  CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + d.k) * 32, &dchs));
+  CK(ws_get(ctx, WS_PFS_SC, nb * (8 + d.m + 10 + 1 + 3) * 32, &dscs));
+  CK(ws_get(ctx, WS_PFS_PTS, nb * 5 * (64 + sizeof(JacRaw)), &dpts));
+  CK(ws_get(ctx, WS_FS_CH, (d.k ? d.k : 1) * nb * 128, &w->lr));
+  CK(ws_get(ctx, WS_PROOF_BAD, 4, &w->zero));
+  w->states = (uint64_t *)dchs;
+  w->ch = (Words8 *)dchs + nb; w->uch = w->ch + 5 * nb;
+  w->bl = (Words8 *)dscs; w->vb = w->bl + 8 * nb; w->rows = w->vb + nb * d.m; w->tb2 = w->rows + 10 * nb; w->sc3 = w->tb2 + nb;
+  w->T = (Words8 *)dpts; w->Tres = (JacRaw *)(w->T + nb * 5 * 2);
+  return BPGPU_OK;
+}
+// the prover's transcript schedule of (two_phase, m, padded_n) in HBM (ctx->mu held).  Each kind keeps its own resident copy and key:
+// a context that alternates between the two uploads, and waits, only when a kind's shape changes
+static int prover_schedule(bpgpu_ctx *ctx, bool two_phase, size_t m, size_t padded_n, ProverSched *out) {
+  void *dsteps;
+  CK(ws_get(ctx, two_phase ? WS_PFS_SCHED2 : WS_PFS_SCHED, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
+  auto &e = ctx->psched[two_phase];
+  if (e.key[0] != m || e.key[1] != padded_n) {
+    TrStep steps[PROVER_SCHEDULE_MAX];
+    const int len = prover_transcript_schedule(steps, two_phase, m, padded_n, e.cut);
+    static_assert(PROVER_SCHEDULE_MAX >= 24, "the two-phase schedule has 24 steps");
+    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
+    HIPCK(ctx, hipStreamSynchronize(ctx->st));   // `steps` is a local
+    e.key[0] = m; e.key[1] = padded_n;
+  }
+  *out = {(const TrStep *)dsteps, e.cut};
+  return BPGPU_OK;
+}
+// The chain from a proof's last commitment phase to its assembly (ctx->mu held, shapes checked; asynchronous).  `s` holds whatever was
+// committed before (`ph`); the IPP session's buffers go back to the context's pool on the way out (stream-ordered reuse), as do `s`'s
+// with its owner, whatever the outcome.
+static int prove_fs_chain_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover *s, const ProveFsWs &w,
+                                 const ProveFsIo &io, const ProveFsPhase &ph) {
+  const ProveFsDims d = prove_fs_dims(c);
+  const size_t nb = s->nb, m = d.m, k = d.k;
+  hipStream_t st = ctx->st;
+  const OperandSrc dev{true, false};                 // operands in HBM; ONE input flag for the whole chain
+  const uint8_t *cy = (const uint8_t *)w.ch, *cz = (const uint8_t *)(w.ch + nb), *cu = (const uint8_t *)(w.ch + 2 * nb),
+                *cx = (const uint8_t *)(w.ch + 3 * nb), *cw = (const uint8_t *)(w.ch + 4 * nb);
+  auto transcript = [&](int slice, const Words8 *points, size_t npoints, const Words8 *scalars, size_t nscalars) {
+    const int *cut = ph.sched.cut + ph.slice + slice;
+    prover_transcript(st, nb, ph.sched.steps + cut[0], cut[1] - cut[0], ph.states, points, npoints, scalars, nscalars, w.ch);
+  };
+  IppOwner iown(nullptr, IppFree{ctx});
+  {
+    ProfScope link(ctx, 22, st);
+    scalars_from_ark(st, (const Words8 *)io.blindings, w.bl, 8 * nb, ctx->d_flag);
+    scalars_from_ark(st, (const Words8 *)io.v_blinding, w.vb, nb * m, ctx->d_flag);
+  }
+  // prover.rs:457-494 | :515-565: this phase's commitments A_I A_O S over G, H [n - n_commit, n).  Into the transcript: after
+  // append_u64("m") (:420), as A_I1 A_O1 S1 before the 1-phase separator and the identity phase-2 points | as A_I2 A_O2 S2; y, z (:584-585)
+  Words8 *dA;
+  CK(prover_commit_core(ctx, g, s, nb, ph.n_commit, u8(io.a_L), u8(io.a_R), u8(io.a_O), u8(io.s_L), u8(io.s_R), u8(io.vector_keys), u8(io.blindings),
+                        8 * 32, dev, &dA));
+  {
+    ProfScope link(ctx, 22, st);
+    transcript(0, dA, 3, nullptr, 0);
+  }
+  // :587-640: y^-1, the flattened constraints (on the gadget challenge, if any), l / r coefficients, t_1..t_6;
+  // T_i = t_i B + tb_i B_blinding; u, x
+  Words8 *dt, *dwV;
+  CK(session_polys_core(ctx, s, c, cy, cz, (const uint8_t *)ph.chi, dev, &dt, &dwV));
+  s->n = d.n; s->m = m;
+  {
+    ProfScope link(ctx, 22, st);
+    prove_fs_t_rows(st, nb, dt, w.bl, w.rows);
+  }
+  {
+    ProfScope tmsm(ctx, 18, st);
+    CK(msm_gens_dev(ctx, g, nb * 5, 0, (const uint32_t *)w.rows, w.Tres, st));
+    jac_to_boundary(st, w.Tres, w.T, nb * 5);
+  }
+  {
+    // :644-686: tb2 = <wV, v_blinding>, t_x, t_x_blinding, e_blinding (over both phases' blinding factors, if there are two); w; then
+    // innerproduct_domain_sep (inner_product_proof.rs:72)
+    ProfScope link(ctx, 22, st);
+    transcript(1, w.T, 5, nullptr, 0);
+    const bool coop = m > PROVE_FS_DOT_LANE_MAX;
+    if (coop) sc_dot_batched(st, nb, m, dwV, m, w.vb, m, w.tb2, 1);
+    prove_fs_glue(st, nb, m, (const Words8 *)cx, dt, w.bl, dwV, w.vb, coop ? w.tb2 : nullptr, w.sc3, ph.bl1 ? (const Words8 *)cu : nullptr, ph.bl1);
+    transcript(2, nullptr, 0, w.sc3, 3);
+  }
+  // :687-708: l(x), r(x), the G / H factors, Q = w B; the k rounds (u_j kept for challenges_out)
+  CK(prover_ipp_begin_core(ctx, s, g, d.padded_n, ph.n1, cx, cu, nullptr, cw, dev, iown));
+  bpgpu_ipp *ipp = iown.get();
+  CK(ipp_rounds_fs_dev(ctx, ipp, k, ph.states, w.lr, w.uch, w.zero));
+  {
+    ProfScope link(ctx, 22, st);
+    ProveFsAssemble a{nb, k, ph.A1 ? ph.A1 : dA, w.T, (const Words8 *)w.lr, w.sc3, ipp->a[ipp->cur], ipp->b[ipp->cur], w.ch, w.uch, ph.states,
+                      (Words8 *)io.proof_points, (Words8 *)io.proof_scalars, (Words8 *)io.challenges_out, (Words8 *)io.states_out, (uint8_t *)io.wire,
+                      ph.A1 ? dA : nullptr};
+    prove_fs_assemble(st, a);
+  }
+  return launch_ok(ctx);
+}
+/* ---- the host forms' staging (WS_PFS_STAGE) ---- */
+// The operands, back to back in the order given (an absent one, of zero bytes, gets a null device pointer), then the results.  `placed`
+// runs once the staging exists and before anything is enqueued; then the flag is reset and the operands are uploaded.
+static int prove_fs_stage(bpgpu_ctx *ctx, size_t n_in, const void *const *in_host, const size_t *in_bytes, uint8_t **in_dev, size_t n_out,
+                          const size_t *out_bytes, uint8_t **out_dev, const std::function<void()> &placed = nullptr) {
+  size_t total = 0;
+  for (size_t i = 0; i < n_in; i++) total += in_bytes[i];
+  for (size_t i = 0; i < n_out; i++) total += out_bytes[i];
+  void *dstage;
+  CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
+  if (placed) placed();
+  uint8_t *at = (uint8_t *)dstage;
+  for (size_t i = 0; i < n_in; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
+  for (size_t i = 0; i < n_out; i++) { out_dev[i] = at; at += out_bytes[i]; }
+  CK(flag_reset(ctx));
+  for (size_t i = 0; i < n_in; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
+  return BPGPU_OK;
+}
+// A proof call (the one-phase one, or _finish) from host memory: `a`'s nine operands of in_bytes each (states_in: none for _finish) and
+// the five results -- proof_points, proof_scalars, challenges_out, states_out, then the wire form of wire_len bytes per proof, of
+// odd length and therefore last; the optional ones are downloaded only when asked for -- around `run` on the staged Io
+static int prove_fs_staged(bpgpu_ctx *ctx, size_t nb, size_t k, size_t wire_len, const ProveFsIo &a, const size_t (&in_bytes)[9],
+                           const std::function<int(const ProveFsIo &)> &run, const std::function<void()> &placed = nullptr) {
+  const void *in_host[9] = {a.states_in, a.a_L, a.a_R, a.a_O, a.s_L, a.s_R, a.vector_keys, a.v_blinding, a.blindings};
+  const size_t out_bytes[5] = {nb * (11 + 2 * k) * 64, nb * 5 * 32, nb * (5 + k) * 32, nb * 32, a.wire ? nb * wire_len : 0};
+  uint8_t *in[9], *out[5];
+  CK(prove_fs_stage(ctx, 9, in_host, in_bytes, in, 5, out_bytes, out, placed));
+  CK(run(ProveFsIo{in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8], out[0], out[1], a.wire ? out[4] : nullptr, out[2], out[3]}));
+  return checked_download(ctx, {{a.proof_points, out[0], out_bytes[0]}, {a.proof_scalars, out[1], out_bytes[1]},
+                                {a.challenges_out, out[2], a.challenges_out ? out_bytes[2] : 0},
+                                {a.states_out, out[3], a.states_out ? out_bytes[3] : 0}, {a.wire, out[4], out_bytes[4]}});
+}
+/* ---- one phase: bpgpu_r1cs_prove_fs ---- */
 // the refusals that depend on shapes alone, before anything is launched (BPGPU_OK with nb == 0: nothing to do)
-static int prove_fs_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const void *states_in, const void *a_L,
-                          const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys, const void *v_blinding,
-                          const void *blindings, const void *proof_points, const void *proof_scalars) {
+static int prove_fs_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const ProveFsIo &a) {
   if (!ctx || !g || !c) return BPGPU_E_ARG;
   if (c->nchi) return BPGPU_E_ARG;       // a two-phase prover evaluates its gadget on the challenge: that round trip stays on the host
   if (!nb) return BPGPU_OK;
   if (!c->n) return BPGPU_E_LEN;         // (no multipliers: no IPP to speak of; the staged calls serve such circuits)
   if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
-  if (!states_in || !a_L || !a_R || !a_O || !blindings || !proof_points || !proof_scalars || (c->m && !v_blinding)) return BPGPU_E_ARG;
-  if ((!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  if (!a.states_in || !a.a_L || !a.a_R || !a.a_O || !a.blindings || !a.proof_points || !a.proof_scalars || (c->m && !a.v_blinding)) return BPGPU_E_ARG;
+  if ((!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
   return BPGPU_OK;
 }
-// ctx->mu held, shapes checked, nb > 0; asynchronous.  The sessions live until the last launch is enqueued: their buffers go back to
+// ctx->mu held, shapes checked, nb > 0; asynchronous.  The session lives until the last launch is enqueued: its buffers go back to
 // the context's pool on the way out (stream-ordered reuse), whatever the outcome.
 static int prove_fs_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const ProveFsIo &io) {
   if (ctx->shard_world > 1) return BPGPU_E_ARG;      // partial sums cannot be hashed: a sharded proof needs the ranks' exchange
   const ProveFsDims d = prove_fs_dims(c);
-  const size_t n = d.n, m = d.m, k = d.k;
-  hipStream_t st = ctx->st;
-  const OperandSrc dev{true, false};                 // operands in HBM; ONE input flag for the whole chain
-  void *dchs, *dscs, *dpts, *dsteps, *dlr, *dzero;
-  CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + k) * 32, &dchs));
-  CK(ws_get(ctx, WS_PFS_SC, nb * (8 + m + 10 + 1 + 3) * 32, &dscs));
-  CK(ws_get(ctx, WS_PFS_PTS, nb * 5 * (64 + sizeof(JacRaw)), &dpts));
-  CK(ws_get(ctx, WS_PFS_SCHED, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
-  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
-  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
-  uint64_t *dstates = (uint64_t *)dchs;
-  Words8 *dch = (Words8 *)dchs + nb, *duch = dch + 5 * nb;                        // y z u x w: nb each; then u_1..u_k
-  const uint8_t *cy = (const uint8_t *)dch, *cz = (const uint8_t *)(dch + nb), *cu = (const uint8_t *)(dch + 2 * nb),
-                *cx = (const uint8_t *)(dch + 3 * nb), *cw = (const uint8_t *)(dch + 4 * nb);
-  Words8 *dbl = (Words8 *)dscs, *dvb = dbl + 8 * nb, *drows = dvb + nb * m, *dtb2 = drows + 10 * nb, *dsc3 = dtb2 + nb;
-  Words8 *dT = (Words8 *)dpts;
-  JacRaw *dTres = (JacRaw *)(dT + nb * 5 * 2);
-  if (ctx->psched_key[0] != m || ctx->psched_key[1] != d.padded_n) {
-    TrStep steps[PROVER_SCHEDULE_MAX];
-    const int len = prover_transcript_schedule(steps, m, d.padded_n, ctx->psched_cut);
-    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, st));
-    HIPCK(ctx, hipStreamSynchronize(st));   // `steps` is a local
-    ctx->psched_key[0] = m; ctx->psched_key[1] = d.padded_n;
-  }
-  const TrStep *steps = (const TrStep *)dsteps;
-  const int *cut = ctx->psched_cut;
+  ProveFsWs w;
+  ProverSched sched;
+  CK(prove_fs_workspace(ctx, nb, d, &w));
+  CK(prover_schedule(ctx, false, d.m, d.padded_n, &sched));
   bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
   if (!s) return BPGPU_E_OOM;
   ProverOwner pown(s, ProverFree{ctx});
-  IppOwner iown(nullptr, IppFree{ctx});
   s->nb = nb; s->planes = 1; s->g = g;
-  CK(copy_in(ctx, dstates, io.states_in, nb * 32, true));
-  {
-    ProfScope link(ctx, 22, st);
-    scalars_from_ark(st, (const Words8 *)io.blindings, dbl, 8 * nb, ctx->d_flag);
-    scalars_from_ark(st, (const Words8 *)io.v_blinding, dvb, nb * m, ctx->d_flag);
-  }
-  // prover.rs:420-585: append_u64("m"), the phase-1 commitments, the 1-phase separator, the identity phase-2 points; y, z
-  Words8 *dA;
-  CK(prover_commit_core(ctx, g, s, nb, n, io.a_L, io.a_R, io.a_O, io.s_L, io.s_R, io.vector_keys, io.blindings, 8 * 32, dev, &dA));
-  {
-    ProfScope link(ctx, 22, st);
-    prover_transcript(st, nb, steps + cut[0], cut[1] - cut[0], dstates, dA, 3, nullptr, 0, dch);
-  }
-  // :587-640: y^-1, the flattened constraints, l / r coefficients, t_1..t_6; T_i = t_i B + tb_i B_blinding; u, x
-  Words8 *dt, *dwV;
-  CK(session_polys_core(ctx, s, c, cy, cz, nullptr, dev, &dt, &dwV));
-  s->n = n; s->m = m;
-  {
-    ProfScope link(ctx, 22, st);
-    prove_fs_t_rows(st, nb, dt, dbl, drows);
-  }
-  {
-    ProfScope tmsm(ctx, 18, st);
-    CK(msm_gens_dev(ctx, g, nb * 5, 0, (const uint32_t *)drows, dTres, st));
-    jac_to_boundary(st, dTres, dT, nb * 5);
-  }
-  {
-    // :644-686: tb2 = <wV, v_blinding>, t_x, t_x_blinding, e_blinding; w; then innerproduct_domain_sep (inner_product_proof.rs:72)
-    ProfScope link(ctx, 22, st);
-    prover_transcript(st, nb, steps + cut[1], cut[2] - cut[1], dstates, dT, 5, nullptr, 0, dch);
-    const bool coop = m > PROVE_FS_DOT_LANE_MAX;
-    if (coop) sc_dot_batched(st, nb, m, dwV, m, dvb, m, dtb2, 1);
-    prove_fs_glue(st, nb, m, (const Words8 *)cx, dt, dbl, dwV, dvb, coop ? dtb2 : nullptr, dsc3);
-    prover_transcript(st, nb, steps + cut[2], cut[3] - cut[2], dstates, nullptr, 0, dsc3, 3, dch);
-  }
-  // :687-708: l(x), r(x), the G / H factors, Q = w B; the k rounds (u_j kept for challenges_out)
-  CK(prover_ipp_begin_core(ctx, s, g, d.padded_n, n, cx, cu, nullptr, cw, dev, iown));
-  bpgpu_ipp *ipp = iown.get();
-  CK(ipp_rounds_fs_dev(ctx, ipp, k, dstates, dlr, duch, dzero));
-  {
-    ProfScope link(ctx, 22, st);
-    ProveFsAssemble a{nb, k, dA, dT, (const Words8 *)dlr, dsc3, ipp->a[ipp->cur], ipp->b[ipp->cur], dch, duch, dstates,
-                      (Words8 *)io.proof_points, (Words8 *)io.proof_scalars, (Words8 *)io.challenges_out, (Words8 *)io.states_out, io.wire};
-    prove_fs_assemble(st, a);
-  }
-  return launch_ok(ctx);
+  CK(copy_in(ctx, w.states, io.states_in, nb * 32, true));
+  return prove_fs_chain_locked(ctx, g, c, s, w, io, {w.states, sched, 0, nullptr, nullptr, nullptr, d.n, d.n});
+}
+static int prove_fs_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const ProveFsIo &a, bool dev) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs_check(ctx, g, c, nb, a));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if (dev) {
+      CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call
+      return prove_fs_locked(ctx, g, c, nb, a);
+    }
+    const ProveFsDims d = prove_fs_dims(c);
+    const size_t tot = nb * d.n * 32;
+    return prove_fs_staged(ctx, nb, d.k, 1 + 11 * 32 + (2 * d.k + 2) * 32, a,
+                           {nb * 32, tot, tot, tot, a.s_L ? tot : 0, a.s_R ? tot : 0, a.vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32},
+                           [&](const ProveFsIo &io) { return prove_fs_locked(ctx, g, c, nb, io); });
+  });
 }
 int bpgpu_r1cs_prove_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const void *states_in, const void *a_L,
                             const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
                             const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
                             void *challenges_out, void *states_out) {
-  return noexcept_abi([&]() -> int {
-    CK(prove_fs_check(ctx, g, c, nb, states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->shard_world > 1) return BPGPU_E_ARG;
-    if (!nb) return BPGPU_OK;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call
-    const ProveFsIo io{(const uint8_t *)states_in, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O, (const uint8_t *)s_L,
-                       (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)v_blinding, (const uint8_t *)blindings,
-                       (uint8_t *)proof_points, (uint8_t *)proof_scalars, (uint8_t *)wire, (uint8_t *)challenges_out, (uint8_t *)states_out};
-    return prove_fs_locked(ctx, g, c, nb, io);
-  });
+  return prove_fs_entry(ctx, g, c, nb, {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars, wire,
+                                        challenges_out, states_out}, true);
 }
 int bpgpu_r1cs_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const uint8_t *states_in, const uint8_t *a_L,
                         const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
                         const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire,
                         uint8_t *challenges_out, uint8_t *states_out) {
-  return noexcept_abi([&]() -> int {
-    CK(prove_fs_check(ctx, g, c, nb, states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->shard_world > 1) return BPGPU_E_ARG;
-    if (!nb) return BPGPU_OK;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    const ProveFsDims d = prove_fs_dims(c);
-    const size_t tot = nb * d.n * 32, nvar = 11 + 2 * d.k, proof_len = 1 + 11 * 32 + (2 * d.k + 2) * 32;
-    // staging: the operands in the order of the argument list, then the results (the wire form, of odd length, last)
-    const size_t in_bytes[9] = {nb * 32, tot, tot, tot, s_L ? tot : 0, s_R ? tot : 0, vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32};
-    const size_t out_bytes[5] = {nb * nvar * 64, nb * 5 * 32, nb * (5 + d.k) * 32, nb * 32, wire ? nb * proof_len : 0};
-    size_t total = 0;
-    for (size_t b : in_bytes) total += b;
-    for (size_t b : out_bytes) total += b;
-    void *dstage;
-    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
-    const uint8_t *in_host[9] = {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings};
-    uint8_t *in_dev[9], *out_dev[5], *at = (uint8_t *)dstage;
-    for (int i = 0; i < 9; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
-    for (int i = 0; i < 5; i++) { out_dev[i] = at; at += out_bytes[i]; }
-    CK(flag_reset(ctx));
-    for (int i = 0; i < 9; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
-    const ProveFsIo io{in_dev[0], in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7], in_dev[8],
-                       out_dev[0], out_dev[1], wire ? out_dev[4] : nullptr, out_dev[2], out_dev[3]};
-    CK(prove_fs_locked(ctx, g, c, nb, io));
-    return checked_download(ctx, {{proof_points, out_dev[0], out_bytes[0]}, {proof_scalars, out_dev[1], out_bytes[1]},
-                                  {challenges_out, out_dev[2], challenges_out ? out_bytes[2] : 0},
-                                  {states_out, out_dev[3], states_out ? out_bytes[3] : 0}, {wire, out_dev[4], out_bytes[4]}});
-  });
+  return prove_fs_entry(ctx, g, c, nb, {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars, wire,
+                                        challenges_out, states_out}, false);
 }
-/* ---- Prover::prove for a TWO-PHASE circuit (one gadget challenge) in two calls around the host's gadget: _begin = prover.rs:420-501
- * (phase-1 commitments, the chain up to the gadget challenge), _finish = :515-727 (everything else, as prove_fs_locked with a second
- * commitment phase).  The session carries the chain state, the challenge, the phase-1 blinding factors and commitments from the one
- * to the other in HBM: _finish_dev may follow _begin_dev on the stream without a wait. -------------------------------------------- */
-namespace {
-struct ProveFs2BeginIo {   // every pointer in HBM but the label
-  const uint8_t *states_in, *gadget_label, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *blindings;
-  uint8_t *commitments, *chi_out, *states_out;
-};
-struct Fs2Arrays { uint64_t *states; Words8 *chi, *bl1, *A1; };
-}  // namespace
-static Fs2Arrays fs2_arrays(const bpgpu_prover *s) { return {(uint64_t *)s->fs2, s->fs2 + s->nb, s->fs2 + 2 * s->nb, s->fs2 + 5 * s->nb}; }
-// the two-phase schedule of (m, padded_n), resident in WS_PFS_SCHED2 (ctx->mu held)
-static int prove_fs2_schedule(bpgpu_ctx *ctx, size_t m, size_t padded_n, const TrStep **steps_out) {
-  void *dsteps;
-  CK(ws_get(ctx, WS_PFS_SCHED2, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
-  if (ctx->psched2_key[0] != m || ctx->psched2_key[1] != padded_n) {
-    TrStep steps[PROVER_SCHEDULE_MAX];
-    const int len = prover_transcript_schedule2(steps, m, padded_n, ctx->psched2_cut);
-    static_assert(PROVER_SCHEDULE_MAX >= 24, "the two-phase schedule has 24 steps");
-    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
-    HIPCK(ctx, hipStreamSynchronize(ctx->st));   // `steps` is a local
-    ctx->psched2_key[0] = m; ctx->psched2_key[1] = padded_n;
-  }
-  *steps_out = (const TrStep *)dsteps;
-  return BPGPU_OK;
-}
+/* ---- two phases: bpgpu_r1cs_prove_fs2_begin, then _finish on its session ---- */
 // the refusals that depend on shapes and arguments alone (BPGPU_OK with nb == 0: nothing to do)
-static int prove_fs2_begin_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
-                                 const uint8_t *gadget_label, const void *a_L, const void *a_R, const void *a_O, const void *s_L,
-                                 const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session) {
+static int prove_fs2_begin_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const ProveFs2BeginIo &a,
+                                 bpgpu_prover **session) {
   if (!ctx || !g || !c || !session || *session) return BPGPU_E_ARG;
   if (c->nchi != 1) return BPGPU_E_ARG;      // a numeric circuit has no gadget challenge (bpgpu_r1cs_prove_fs); one label per schedule
   if (!nb) return BPGPU_OK;
   if (n1 >= c->n) return BPGPU_E_LEN;        // (no second-phase commitments: the staged calls serve such provers)
   if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
-  if (!states_in || !gadget_label || !blindings) return BPGPU_E_ARG;
-  if (n1 && (!a_L || !a_R || !a_O || (!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr))) return BPGPU_E_ARG;
+  if (!a.states_in || !a.gadget_label || !a.blindings) return BPGPU_E_ARG;
+  if (n1 && (!a.a_L || !a.a_R || !a.a_O || (!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr))) return BPGPU_E_ARG;
   return BPGPU_OK;
 }
 // ctx->mu held, shapes checked, nb > 0; asynchronous.  `own` holds the session, also on failure.
@@ -3891,9 +3936,8 @@ static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   const ProveFsDims d = prove_fs_dims(c);
   hipStream_t st = ctx->st;
   const OperandSrc dev{true, false};                 // operands in HBM; the caller has reset the input flag
-  const TrStep *steps;
-  CK(prove_fs2_schedule(ctx, d.m, d.padded_n, &steps));
-  const int *cut = ctx->psched2_cut;
+  ProverSched sched;
+  CK(prover_schedule(ctx, true, d.m, d.padded_n, &sched));
   bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
   if (!s) return BPGPU_E_OOM;
   own.reset(s);
@@ -3908,11 +3952,12 @@ static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   // prover.rs:420-501: append_u64("m"), the phase-1 commitments, the 2-phase separator, the gadget's challenge
   const bool keys = n1 && !io.s_L;
   Words8 *dA;
-  CK(prover_commit_core(ctx, g, s, nb, n1, io.a_L, io.a_R, io.a_O, n1 ? io.s_L : nullptr, n1 ? io.s_R : nullptr,
-                        keys ? io.vector_keys : nullptr, io.blindings, 3 * 32, dev, &dA));
+  CK(prover_commit_core(ctx, g, s, nb, n1, u8(io.a_L), u8(io.a_R), u8(io.a_O), n1 ? u8(io.s_L) : nullptr, n1 ? u8(io.s_R) : nullptr,
+                        keys ? u8(io.vector_keys) : nullptr, u8(io.blindings), 3 * 32, dev, &dA));
   {
     ProfScope link(ctx, 22, st);
-    prover_transcript(st, nb, steps + cut[0], cut[1] - cut[0], f.states, dA, 3, nullptr, 0, nullptr, io.gadget_label, f.chi);
+    prover_transcript(st, nb, sched.steps + sched.cut[0], sched.cut[1] - sched.cut[0], f.states, dA, 3, nullptr, 0, nullptr, io.gadget_label,
+                      f.chi);
   }
   HIPCK(ctx, hipMemcpyAsync(f.A1, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
   if (io.commitments) HIPCK(ctx, hipMemcpyAsync(io.commitments, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
@@ -3920,197 +3965,103 @@ static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   if (io.states_out) HIPCK(ctx, hipMemcpyAsync(io.states_out, f.states, nb * 32, hipMemcpyDeviceToDevice, st));   // (little-endian words)
   return launch_ok(ctx);
 }
-int bpgpu_r1cs_prove_fs2_begin_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
-                                   const uint8_t gadget_label[32], const void *a_L, const void *a_R, const void *a_O, const void *s_L,
-                                   const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session,
-                                   void *commitments, void *gadget_challenges_out, void *states_out) {
+static int prove_fs2_begin_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const ProveFs2BeginIo &a,
+                                 bpgpu_prover **session, bool dev) {
   return noexcept_abi([&]() -> int {
-    CK(prove_fs2_begin_check(ctx, g, c, nb, n1, states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, session));
+    CK(prove_fs2_begin_check(ctx, g, c, nb, n1, a, session));
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->shard_world > 1) return BPGPU_E_ARG;    // partial sums cannot be hashed
     if (!nb) return BPGPU_OK;
     HIPCK(ctx, hipSetDevice(ctx->device));
-    CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call; _finish_dev adds to it: one flag for the pair
-    const ProveFs2BeginIo io{(const uint8_t *)states_in, gadget_label, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O,
-                             (const uint8_t *)s_L, (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)blindings,
-                             (uint8_t *)commitments, (uint8_t *)gadget_challenges_out, (uint8_t *)states_out};
     ProverOwner own(nullptr, ProverFree{ctx});
-    CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, io, own));
+    if (dev) {
+      CK(flag_reset(ctx));   // the flag reports on the most recent *_dev call; _finish_dev adds to it: one flag for the pair
+      CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, a, own));
+    } else {
+      const size_t tot = nb * n1 * 32;
+      const void *in_host[8] = {a.states_in, a.a_L, a.a_R, a.a_O, a.s_L, a.s_R, a.vector_keys, a.blindings};
+      const size_t in_bytes[8] = {nb * 32, tot, tot, tot, n1 && a.s_L ? tot : 0, n1 && a.s_R ? tot : 0, n1 && a.vector_keys ? nb * 32 : 0,
+                                  nb * 3 * 32};
+      const size_t out_bytes[3] = {nb * 3 * 64, nb * 32, nb * 32};
+      uint8_t *in[8], *out[3];
+      CK(prove_fs_stage(ctx, 8, in_host, in_bytes, in, 3, out_bytes, out));
+      CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, {in[0], a.gadget_label, in[1], in[2], in[3], in[4], in[5], in[6], in[7], out[0], out[1], out[2]},
+                                own));
+      CK(checked_download(ctx, {{a.commitments, out[0], a.commitments ? out_bytes[0] : 0}, {a.chi_out, out[1], a.chi_out ? out_bytes[1] : 0},
+                                {a.states_out, out[2], a.states_out ? out_bytes[2] : 0}}));
+    }
     *session = own.release();
     return BPGPU_OK;
   });
+}
+int bpgpu_r1cs_prove_fs2_begin_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const void *states_in,
+                                   const uint8_t gadget_label[32], const void *a_L, const void *a_R, const void *a_O, const void *s_L,
+                                   const void *s_R, const void *vector_keys, const void *blindings, bpgpu_prover **session,
+                                   void *commitments, void *gadget_challenges_out, void *states_out) {
+  return prove_fs2_begin_entry(ctx, g, c, nb, n1, {states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, commitments,
+                                                   gadget_challenges_out, states_out}, session, true);
 }
 int bpgpu_r1cs_prove_fs2_begin(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const uint8_t *states_in,
                                const uint8_t gadget_label[32], const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
                                const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *blindings,
                                bpgpu_prover **session, uint8_t *commitments, uint8_t *gadget_challenges_out, uint8_t *states_out) {
-  return noexcept_abi([&]() -> int {
-    CK(prove_fs2_begin_check(ctx, g, c, nb, n1, states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, session));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->shard_world > 1) return BPGPU_E_ARG;
-    if (!nb) return BPGPU_OK;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    const size_t tot = nb * n1 * 32;
-    // staging: the operands in the order of the argument list, then the results
-    const size_t in_bytes[8] = {nb * 32, tot, tot, tot, n1 && s_L ? tot : 0, n1 && s_R ? tot : 0, n1 && vector_keys ? nb * 32 : 0, nb * 3 * 32};
-    const size_t out_bytes[3] = {nb * 3 * 64, nb * 32, nb * 32};
-    size_t total = 0;
-    for (size_t b : in_bytes) total += b;
-    for (size_t b : out_bytes) total += b;
-    void *dstage;
-    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
-    const uint8_t *in_host[8] = {states_in, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings};
-    uint8_t *in_dev[8], *out_dev[3], *at = (uint8_t *)dstage;
-    for (int i = 0; i < 8; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
-    for (int i = 0; i < 3; i++) { out_dev[i] = at; at += out_bytes[i]; }
-    CK(flag_reset(ctx));
-    for (int i = 0; i < 8; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
-    const ProveFs2BeginIo io{in_dev[0], gadget_label, in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7],
-                             out_dev[0], out_dev[1], out_dev[2]};
-    ProverOwner own(nullptr, ProverFree{ctx});
-    CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, io, own));
-    CK(checked_download(ctx, {{commitments, out_dev[0], commitments ? out_bytes[0] : 0},
-                              {gadget_challenges_out, out_dev[1], gadget_challenges_out ? out_bytes[1] : 0},
-                              {states_out, out_dev[2], states_out ? out_bytes[2] : 0}}));
-    *session = own.release();
-    return BPGPU_OK;
-  });
+  return prove_fs2_begin_entry(ctx, g, c, nb, n1, {states_in, gadget_label, a_L, a_R, a_O, s_L, s_R, vector_keys, blindings, commitments,
+                                                   gadget_challenges_out, states_out}, session, false);
 }
 // _finish's refusals: they leave the session open
-static int prove_fs2_finish_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const void *a_L,
-                                  const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
-                                  const void *v_blinding, const void *blindings, const void *proof_points, const void *proof_scalars) {
+static int prove_fs2_finish_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const ProveFsIo &a) {
   if (!ctx || !g || !c || !session || !*session) return BPGPU_E_ARG;
   const bpgpu_prover *s = *session;
   if (!s->fs2 || s->fs2_c != c || s->g != g) return BPGPU_E_ARG;   // opened by _begin, on this circuit and these generators
-  if (!a_L || !a_R || !a_O || !blindings || !proof_points || !proof_scalars || (c->m && !v_blinding)) return BPGPU_E_ARG;
-  if ((!s_L) != (!s_R) || (s_L != nullptr) == (vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  if (!a.a_L || !a.a_R || !a.a_O || !a.blindings || !a.proof_points || !a.proof_scalars || (c->m && !a.v_blinding)) return BPGPU_E_ARG;
+  if ((!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
   return BPGPU_OK;
 }
-// ctx->mu held, arguments checked; asynchronous.  The session is `pown`'s: its buffers, and the IPP session's, go back to the
-// context's pool on the way out (stream-ordered reuse), whatever the outcome.
+// ctx->mu held, arguments checked; asynchronous.  The session is `pown`'s: its buffers go back to the context's pool on the way out
+// (stream-ordered reuse), whatever the outcome.
 static int prove_fs2_finish_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, ProverOwner &pown, const ProveFsIo &io) {
   bpgpu_prover *s = pown.get();
   const ProveFsDims d = prove_fs_dims(c);
-  const size_t nb = s->nb, n = d.n, m = d.m, k = d.k, n1 = s->wn, n2 = n - n1;
-  hipStream_t st = ctx->st;
-  const OperandSrc dev{true, false};                 // operands in HBM; ONE input flag for the whole chain
-  const TrStep *steps;
-  CK(prove_fs2_schedule(ctx, m, d.padded_n, &steps));
-  const int *cut = ctx->psched2_cut;
-  void *dchs, *dscs, *dpts, *dlr, *dzero;
-  CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + k) * 32, &dchs));
-  CK(ws_get(ctx, WS_PFS_SC, nb * (8 + m + 10 + 1 + 3) * 32, &dscs));
-  CK(ws_get(ctx, WS_PFS_PTS, nb * 5 * (64 + sizeof(JacRaw)), &dpts));
-  CK(ws_get(ctx, WS_FS_CH, (k ? k : 1) * nb * 128, &dlr));
-  CK(ws_get(ctx, WS_PROOF_BAD, 4, &dzero));
   const Fs2Arrays f = fs2_arrays(s);
-  Words8 *dch = (Words8 *)dchs + nb, *duch = dch + 5 * nb;                        // y z u x w: nb each; then u_1..u_k
-  const uint8_t *cy = (const uint8_t *)dch, *cz = (const uint8_t *)(dch + nb), *cu = (const uint8_t *)(dch + 2 * nb),
-                *cx = (const uint8_t *)(dch + 3 * nb), *cw = (const uint8_t *)(dch + 4 * nb);
-  Words8 *dbl = (Words8 *)dscs, *dvb = dbl + 8 * nb, *drows = dvb + nb * m, *dtb2 = drows + 10 * nb, *dsc3 = dtb2 + nb;
-  Words8 *dT = (Words8 *)dpts;
-  JacRaw *dTres = (JacRaw *)(dT + nb * 5 * 2);
-  IppOwner iown(nullptr, IppFree{ctx});
-  {
-    ProfScope link(ctx, 22, st);
-    scalars_from_ark(st, (const Words8 *)io.blindings, dbl, 8 * nb, ctx->d_flag);
-    scalars_from_ark(st, (const Words8 *)io.v_blinding, dvb, nb * m, ctx->d_flag);
-  }
-  // prover.rs:515-585: the phase-2 commitments over G[n1..n), H[n1..n); A_I2 A_O2 S2; y, z
-  Words8 *dA2;
-  CK(prover_commit_core(ctx, g, s, nb, n2, io.a_L, io.a_R, io.a_O, io.s_L, io.s_R, io.vector_keys, io.blindings, 8 * 32, dev, &dA2));
-  {
-    ProfScope link(ctx, 22, st);
-    prover_transcript(st, nb, steps + cut[1], cut[2] - cut[1], f.states, dA2, 3, nullptr, 0, dch);
-  }
-  // :587-640: the polynomial build on the session's own gadget challenge; T_i = t_i B + tb_i B_blinding; u, x
-  Words8 *dt, *dwV;
-  CK(session_polys_core(ctx, s, c, cy, cz, (const uint8_t *)f.chi, dev, &dt, &dwV));
-  s->n = n; s->m = m;
-  {
-    ProfScope link(ctx, 22, st);
-    prove_fs_t_rows(st, nb, dt, dbl, drows);
-  }
-  {
-    ProfScope tmsm(ctx, 18, st);
-    CK(msm_gens_dev(ctx, g, nb * 5, 0, (const uint32_t *)drows, dTres, st));
-    jac_to_boundary(st, dTres, dT, nb * 5);
-  }
-  {
-    // :644-686: tb2, t_x, t_x_blinding, e_blinding over both phases' blinding factors; w; then innerproduct_domain_sep
-    ProfScope link(ctx, 22, st);
-    prover_transcript(st, nb, steps + cut[2], cut[3] - cut[2], f.states, dT, 5, nullptr, 0, dch);
-    const bool coop = m > PROVE_FS_DOT_LANE_MAX;
-    if (coop) sc_dot_batched(st, nb, m, dwV, m, dvb, m, dtb2, 1);
-    prove_fs_glue(st, nb, m, (const Words8 *)cx, dt, dbl, dwV, dvb, coop ? dtb2 : nullptr, dsc3, (const Words8 *)cu, f.bl1);
-    prover_transcript(st, nb, steps + cut[3], cut[4] - cut[3], f.states, nullptr, 0, dsc3, 3, dch);
-  }
-  // :687-708: l(x), r(x), G_factors = [1; n1] ++ [u; n2 + pad], Q = w B; the k rounds (u_j kept for challenges_out)
-  CK(prover_ipp_begin_core(ctx, s, g, d.padded_n, n1, cx, cu, nullptr, cw, dev, iown));
-  bpgpu_ipp *ipp = iown.get();
-  CK(ipp_rounds_fs_dev(ctx, ipp, k, f.states, dlr, duch, dzero));
-  {
-    ProfScope link(ctx, 22, st);
-    ProveFsAssemble a{nb, k, f.A1, dT, (const Words8 *)dlr, dsc3, ipp->a[ipp->cur], ipp->b[ipp->cur], dch, duch, f.states,
-                      (Words8 *)io.proof_points, (Words8 *)io.proof_scalars, (Words8 *)io.challenges_out, (Words8 *)io.states_out, io.wire,
-                      dA2};
-    prove_fs_assemble(st, a);
-  }
-  return launch_ok(ctx);
+  ProveFsWs w;
+  ProverSched sched;
+  CK(prover_schedule(ctx, true, d.m, d.padded_n, &sched));
+  CK(prove_fs_workspace(ctx, s->nb, d, &w));
+  return prove_fs_chain_locked(ctx, g, c, s, w, io, {f.states, sched, 1, f.chi, f.bl1, f.A1, d.n - s->wn, s->wn});
+}
+static int prove_fs2_finish_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const ProveFsIo &a,
+                                  bool dev) {
+  return noexcept_abi([&]() -> int {
+    CK(prove_fs2_finish_check(ctx, g, c, session, a));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    ProverOwner pown(nullptr, ProverFree{ctx});
+    auto take = [&] { pown.reset(*session); *session = nullptr; };   // from there on the session is consumed
+    if (dev) {
+      take();   // (no flag reset: what _begin_dev's operands raised stays raised -- the flag reports on the pair)
+      return prove_fs2_finish_locked(ctx, g, c, pown, a);
+    }
+    const ProveFsDims d = prove_fs_dims(c);
+    const size_t nb = (*session)->nb, tot = nb * (d.n - (*session)->wn) * 32;
+    return prove_fs_staged(ctx, nb, d.k, 1 + 14 * 32 + (2 * d.k + 2) * 32, a,
+                           {0, tot, tot, tot, a.s_L ? tot : 0, a.s_R ? tot : 0, a.vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32},
+                           [&](const ProveFsIo &io) { return prove_fs2_finish_locked(ctx, g, c, pown, io); }, take);
+  });
 }
 int bpgpu_r1cs_prove_fs2_finish_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const void *a_L,
                                     const void *a_R, const void *a_O, const void *s_L, const void *s_R, const void *vector_keys,
                                     const void *v_blinding, const void *blindings, void *proof_points, void *proof_scalars, void *wire,
                                     void *challenges_out, void *states_out) {
-  return noexcept_abi([&]() -> int {
-    CK(prove_fs2_finish_check(ctx, g, c, session, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->shard_world > 1) return BPGPU_E_ARG;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    ProverOwner pown(*session, ProverFree{ctx});   // from here on the session is consumed
-    *session = nullptr;
-    // (no flag reset: what _begin_dev's operands raised stays raised -- the flag reports on the pair)
-    const ProveFsIo io{nullptr, (const uint8_t *)a_L, (const uint8_t *)a_R, (const uint8_t *)a_O, (const uint8_t *)s_L,
-                       (const uint8_t *)s_R, (const uint8_t *)vector_keys, (const uint8_t *)v_blinding, (const uint8_t *)blindings,
-                       (uint8_t *)proof_points, (uint8_t *)proof_scalars, (uint8_t *)wire, (uint8_t *)challenges_out, (uint8_t *)states_out};
-    return prove_fs2_finish_locked(ctx, g, c, pown, io);
-  });
+  return prove_fs2_finish_entry(ctx, g, c, session, {nullptr, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points,
+                                                     proof_scalars, wire, challenges_out, states_out}, true);
 }
 int bpgpu_r1cs_prove_fs2_finish(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, bpgpu_prover **session, const uint8_t *a_L,
                                 const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys,
                                 const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points, uint8_t *proof_scalars,
                                 uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out) {
-  return noexcept_abi([&]() -> int {
-    CK(prove_fs2_finish_check(ctx, g, c, session, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->shard_world > 1) return BPGPU_E_ARG;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    const ProveFsDims d = prove_fs_dims(c);
-    const size_t nb = (*session)->nb, tot = nb * (d.n - (*session)->wn) * 32, nvar = 11 + 2 * d.k, proof_len = 1 + 14 * 32 + (2 * d.k + 2) * 32;
-    // staging: the operands in the order of the argument list, then the results (the wire form, of odd length, last)
-    const size_t in_bytes[8] = {tot, tot, tot, s_L ? tot : 0, s_R ? tot : 0, vector_keys ? nb * 32 : 0, nb * d.m * 32, nb * 8 * 32};
-    const size_t out_bytes[5] = {nb * nvar * 64, nb * 5 * 32, nb * (5 + d.k) * 32, nb * 32, wire ? nb * proof_len : 0};
-    size_t total = 0;
-    for (size_t b : in_bytes) total += b;
-    for (size_t b : out_bytes) total += b;
-    void *dstage;
-    CK(ws_get(ctx, WS_PFS_STAGE, total, &dstage));
-    ProverOwner pown(*session, ProverFree{ctx});   // from here on the session is consumed
-    *session = nullptr;
-    const uint8_t *in_host[8] = {a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings};
-    uint8_t *in_dev[8], *out_dev[5], *at = (uint8_t *)dstage;
-    for (int i = 0; i < 8; i++) { in_dev[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
-    for (int i = 0; i < 5; i++) { out_dev[i] = at; at += out_bytes[i]; }
-    CK(flag_reset(ctx));
-    for (int i = 0; i < 8; i++) CK(h2d(ctx, in_dev[i], in_host[i], in_bytes[i]));
-    const ProveFsIo io{nullptr, in_dev[0], in_dev[1], in_dev[2], in_dev[3], in_dev[4], in_dev[5], in_dev[6], in_dev[7],
-                       out_dev[0], out_dev[1], wire ? out_dev[4] : nullptr, out_dev[2], out_dev[3]};
-    CK(prove_fs2_finish_locked(ctx, g, c, pown, io));
-    return checked_download(ctx, {{proof_points, out_dev[0], out_bytes[0]}, {proof_scalars, out_dev[1], out_bytes[1]},
-                                  {challenges_out, out_dev[2], challenges_out ? out_bytes[2] : 0},
-                                  {states_out, out_dev[3], states_out ? out_bytes[3] : 0}, {wire, out_dev[4], out_bytes[4]}});
-  });
+  return prove_fs2_finish_entry(ctx, g, c, session, {nullptr, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points,
+                                                     proof_scalars, wire, challenges_out, states_out}, false);
 }
 /* scalars[i] * (curve generator): GeneratorsChain::next (generators.rs:112-124), Q = w * B (prover.rs:687) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out) {

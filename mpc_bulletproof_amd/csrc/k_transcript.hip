@@ -597,7 +597,7 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
   hipLaunchKernelGGL(k_ipp_round_challenge, dim3((nb + 63) / 64), dim3(64), 0, st, nb, states, lr, u_out);
 }
 
-// ---- the PROVER's side of the schedule (r1cs/prover.rs:420-686 for a circuit without randomized constraints), for the one-call
+// ---- the PROVER's side of the schedule (r1cs/prover.rs:420-686), here for a circuit without randomized constraints and the one-call
 // prover (bpgpu_r1cs_prove_fs): the same step table, cut where a challenge has to exist before the next arithmetic stage runs --
 //   slice 0: append_u64("m"), A_I1 A_O1 S1, the 1-phase separator, A_I2 A_O2 S2 (identity), y, z       -> the polynomial build
 //   slice 1: T_1 T_3 T_4 T_5 T_6, u, x                                                                  -> t(x), the blindings
@@ -664,56 +664,39 @@ __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrSte
 #pragma unroll
   for (int i = 0; i < 4; i++) states[p * 4 + i] = st[i];
 }
-// the step list and its three slices: slice j = steps [cut[j], cut[j + 1]).  Points are indexed within the slice's own array
-// (A_I1 A_O1 S1 | T_1 T_3 T_4 T_5 T_6), scalars as t_x t_x_blinding e_blinding, challenges as y z u x w.
-int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4]) {
-  int n = 0;
-  auto add = [&](uint8_t kind, uint8_t label, uint32_t src, uint64_t value) {
-    out[n].kind = kind; out[n].label = label; out[n].validate = 0; out[n].pad = 0; out[n].src = src; out[n].value = value; n++;
-  };
-  cut[0] = 0;
-  add(TS_U64, LB_m, 0, m);                                                                       // prover.rs:420
-  add(TS_POINT, LB_AI1, 0, 0); add(TS_POINT, LB_AO1, 1, 0); add(TS_POINT, LB_S1, 2, 0);          // :496-498
-  add(TS_DOMSEP, LB_1phase, 0, 0);                                                               // :388
-  add(TS_POINT, LB_AI2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_AO2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_S2, TS_SRC_IDENTITY, 0);   // :566-580
-  add(TS_CHALLENGE, LB_y, 0, 0); add(TS_CHALLENGE, LB_z, 1, 0);                                  // :584-585
-  cut[1] = n;
-  const uint8_t tl[5] = {LB_T1, LB_T3, LB_T4, LB_T5, LB_T6};
-  for (int j = 0; j < 5; j++) add(TS_POINT, tl[j], (uint32_t)j, 0);                              // :633-637
-  add(TS_CHALLENGE, LB_u, 2, 0); add(TS_CHALLENGE, LB_x, 3, 0);                                  // :639-640
-  cut[2] = n;
-  add(TS_SCALAR, LB_tx, 0, 0); add(TS_SCALAR, LB_txb, 1, 0); add(TS_SCALAR, LB_eb, 2, 0);        // :680-683
-  add(TS_CHALLENGE, LB_w, 4, 0);                                                                 // :686
-  add(TS_DOMSEP, LB_ipp, 0, 0); add(TS_U64, LB_n, 0, padded_n);                                  // inner_product_proof.rs:72
-  cut[3] = n;
-  return n;
-}
-// The same for a circuit WITH randomized constraints and one gadget challenge (bpgpu_r1cs_prove_fs2_begin / _finish), in four slices:
+// the step list and its slices: slice j = steps [cut[j], cut[j + 1]).  Points are indexed within the slice's own array (A_I1 A_O1 S1 |
+// T_1 T_3 T_4 T_5 T_6), scalars as t_x t_x_blinding e_blinding, challenges as y z u x w.  One phase: the three slices above.  Two phases
+// -- a circuit WITH randomized constraints and one gadget challenge (bpgpu_r1cs_prove_fs2_begin / _finish) -- four:
 //   slice 0: append_u64("m"), A_I1 A_O1 S1, the 2-phase separator, the gadget challenge (into chi[p])   -> the host's gadget
 //   slice 1: A_I2 A_O2 S2 (the second commitment's output, indexed 0..2), y, z                          -> the polynomial build
 //   slice 2, 3: as slices 1, 2 above
-int prover_transcript_schedule2(TrStep *out, size_t m, size_t padded_n, int cut[5]) {
-  int n = 0;
+int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t padded_n, int cut[5]) {
+  int n = 0, nc = 0;
   auto add = [&](uint8_t kind, uint8_t label, uint32_t src, uint64_t value) {
     out[n].kind = kind; out[n].label = label; out[n].validate = 0; out[n].pad = 0; out[n].src = src; out[n].value = value; n++;
   };
-  cut[0] = 0;
+  cut[nc++] = 0;
   add(TS_U64, LB_m, 0, m);                                                                       // prover.rs:420
   add(TS_POINT, LB_AI1, 0, 0); add(TS_POINT, LB_AO1, 1, 0); add(TS_POINT, LB_S1, 2, 0);          // :496-498
-  add(TS_DOMSEP, LB_2phase, 0, 0);                                                               // :391
-  add(TS_GADGET_CHALLENGE, LB_z, 0, 0);                                                          // :393-408 (the label is the launch's)
-  cut[1] = n;
-  add(TS_POINT, LB_AI2, 0, 0); add(TS_POINT, LB_AO2, 1, 0); add(TS_POINT, LB_S2, 2, 0);          // :578-580
+  if (two_phase) {
+    add(TS_DOMSEP, LB_2phase, 0, 0);                                                             // :391
+    add(TS_GADGET_CHALLENGE, LB_z, 0, 0);                                                        // :393-408 (the label is the launch's)
+    cut[nc++] = n;
+    add(TS_POINT, LB_AI2, 0, 0); add(TS_POINT, LB_AO2, 1, 0); add(TS_POINT, LB_S2, 2, 0);        // :578-580
+  } else {
+    add(TS_DOMSEP, LB_1phase, 0, 0);                                                             // :388
+    add(TS_POINT, LB_AI2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_AO2, TS_SRC_IDENTITY, 0); add(TS_POINT, LB_S2, TS_SRC_IDENTITY, 0);   // :566-580
+  }
   add(TS_CHALLENGE, LB_y, 0, 0); add(TS_CHALLENGE, LB_z, 1, 0);                                  // :584-585
-  cut[2] = n;
+  cut[nc++] = n;
   const uint8_t tl[5] = {LB_T1, LB_T3, LB_T4, LB_T5, LB_T6};
   for (int j = 0; j < 5; j++) add(TS_POINT, tl[j], (uint32_t)j, 0);                              // :633-637
   add(TS_CHALLENGE, LB_u, 2, 0); add(TS_CHALLENGE, LB_x, 3, 0);                                  // :639-640
-  cut[3] = n;
+  cut[nc++] = n;
   add(TS_SCALAR, LB_tx, 0, 0); add(TS_SCALAR, LB_txb, 1, 0); add(TS_SCALAR, LB_eb, 2, 0);        // :680-683
   add(TS_CHALLENGE, LB_w, 4, 0);                                                                 // :686
   add(TS_DOMSEP, LB_ipp, 0, 0); add(TS_U64, LB_n, 0, padded_n);                                  // inner_product_proof.rs:72
-  cut[4] = n;
+  cut[nc] = n;
   return n;
 }
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,

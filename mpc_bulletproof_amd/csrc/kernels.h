@@ -382,13 +382,11 @@ void ipp_round_tail(hipStream_t st, size_t nb, const JacRaw *sums, uint64_t *sta
 
 // ---- the one-call prover (bpgpu_r1cs_prove_fs): the prover's transcript slices (k_transcript.hip) and the links between the stages
 // (k_prove_fs.hip) ------------------------------------------------------------------------------------
-// host: the prover's step list for a one-phase circuit (22 steps) and its three slices, slice j = steps [cut[j], cut[j + 1]):
-// up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator
+// host: the prover's step list and its slices, slice j = steps [cut[j], cut[j + 1]).  A one-phase circuit: 22 steps in three slices,
+// up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator.  A two-phase circuit with one gadget challenge: 24
+// steps in four, up to the gadget challenge | A_I2 A_O2 S2, y, z | then the same two
 constexpr int PROVER_SCHEDULE_MAX = 24;
-int prover_transcript_schedule(TrStep *out, size_t m, size_t padded_n, int cut[4]);
-// ... and for a two-phase circuit with one gadget challenge (24 steps), in four slices: up to the gadget challenge | A_I2 A_O2 S2, y, z |
-// T points, u, x | the three scalars, w, the IPP separator
-int prover_transcript_schedule2(TrStep *out, size_t m, size_t padded_n, int cut[5]);
+int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t padded_n, int cut[5]);
 // one slice for nb provers, a lane each; states: 4 x u64 per prover, updated.  A step's src indexes points (pt_stride per prover),
 // scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p].  A TS_GADGET_CHALLENGE step draws under
 // gadget_label (32 bytes, zero-padded, host memory) into chi[p]

@@ -1576,6 +1576,22 @@ struct ProveBatch {
         throw std::invalid_argument("prove_batch: constraint rows differ between provers");
   }
 
+  // What a fused call returned -- proof_points nb x (11 + 2k) x 64 B, proof_scalars nb x 5 x 32 B, states_out nb x 32 B -- into the
+  // proofs; the host transcripts catch up, as after bpgpu_ipp_run_fs
+  void read_fused(size_t k, const std::vector<uint8_t> &pts, const std::vector<uint8_t> &sc, const std::vector<uint8_t> &st_out) {
+    const size_t nvar = 11 + 2 * k;
+    for (size_t p = 0; p < nb; p++) {
+      R1CSProof &pr = proofs[p];
+      const uint8_t *pp = &pts[p * nvar * 64], *ps5 = &sc[p * 160];
+      read_points(pp, {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6});
+      append_points(pr.ipp_proof.L_vec, pp + 64 * 11, k);
+      append_points(pr.ipp_proof.R_vec, pp + 64 * (11 + k), k);
+      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
+      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
+      cs[p]->tr.set_state(&st_out[32 * p]);
+    }
+  }
+
   // BPH_PROVE_FUSED: every draw up front -- with no second phase nothing is drawn between the vectors and the T blindings, so it is
   // the staged route's stream --, then bpgpu_r1cs_prove_fs
   void prove_fused() {
@@ -1598,16 +1614,7 @@ struct ProveBatch {
                                  vkeys ? pl.key : nullptr, m ? pvb : nullptr, pl.bl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
     if (rc == BPGPU_E_GENS) throw R1CSException(R1CSError::InvalidGeneratorsLength);
     d.check(rc, "bpgpu_r1cs_prove_fs");
-    for (size_t p = 0; p < nb; p++) {
-      R1CSProof &pr = proofs[p];
-      const uint8_t *pp = &pts[p * nvar * 64], *ps5 = &sc[p * 160];
-      read_points(pp, {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6});
-      append_points(pr.ipp_proof.L_vec, pp + 64 * 11, k);
-      append_points(pr.ipp_proof.R_vec, pp + 64 * (11 + k), k);
-      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
-      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
-      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up, as after bpgpu_ipp_run_fs
-    }
+    read_fused(k, pts, sc, st_out);
     lap("prove: fused device call");
   }
 
@@ -1648,16 +1655,7 @@ struct ProveBatch {
     rc = bpgpu_r1cs_prove_fs2_finish(d.ctx(), gens, circ, &ps.h, p2.aL, p2.aR, p2.aO, vkeys ? nullptr : p2.sL, vkeys ? nullptr : p2.sR,
                                      vkeys ? p2.key : nullptr, m ? pvb : nullptr, p2.bl, pts.data(), sc.data(), nullptr, nullptr, st_out.data());
     d.check(rc, "bpgpu_r1cs_prove_fs2_finish");
-    for (size_t p = 0; p < nb; p++) {
-      R1CSProof &pr = proofs[p];
-      const uint8_t *pp = &pts[p * nvar * 64], *ps5 = &sc[p * 160];
-      read_points(pp, {&pr.A_I1, &pr.A_O1, &pr.S1, &pr.A_I2, &pr.A_O2, &pr.S2, &pr.T_1, &pr.T_3, &pr.T_4, &pr.T_5, &pr.T_6});
-      append_points(pr.ipp_proof.L_vec, pp + 64 * 11, k);
-      append_points(pr.ipp_proof.R_vec, pp + 64 * (11 + k), k);
-      pr.t_x = Scalar::from_bytes_le(ps5); pr.t_x_blinding = Scalar::from_bytes_le(ps5 + 32); pr.e_blinding = Scalar::from_bytes_le(ps5 + 64);
-      pr.ipp_proof.a = Scalar::from_bytes_le(ps5 + 96); pr.ipp_proof.b = Scalar::from_bytes_le(ps5 + 128);
-      cs[p]->tr.set_state(&st_out[32 * p]);               // the host transcript catches up
-    }
+    read_fused(k, pts, sc, st_out);
     lap("prove: fused finish");
   }
 

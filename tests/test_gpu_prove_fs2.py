@@ -12,6 +12,7 @@ import circuit_gen as cg
 import mpc_dealer as md
 import oracle_lib as o
 import prove_fs2_cases as pc
+import prove_fs_cases as pc1
 
 pm = cg.pm
 N = pm.N
@@ -475,7 +476,77 @@ def test_refusals_and_the_session_lifecycle(gpu, gens, mgens):
             gpu.circuit_destroy(x)
 
 
-# ------------------------------------------------------------------------------------------------ 7: the host mirror
+# ------------------------------------------------------------------------------------------------ 7: both kinds on one context
+# timed launches per profile kind (BpGpu.profile_read) of ONE call with nb = 1: bpgpu_r1cs_prove_fs on circuit A below,
+# bpgpu_r1cs_prove_fs2_begin and _finish on circuit B -- the launch structure of each call
+LAUNCHES_FS = dict(prover_commit=1, prover_polys=1, msm_gens=1, ipp_begin=1, ipp_rounds=1, ipp_round_msm=1, prove_fs_links=5)
+LAUNCHES_BEGIN = dict(prover_commit=1, prove_fs_links=2)
+LAUNCHES_FINISH = LAUNCHES_FS
+
+
+def test_one_and_two_phase_proofs_alternate_on_one_context(gpu, gens, mgens):
+    """the one-phase and the two-phase call share the context's transcript-schedule cache, workspace and chain: a one-phase circuit A
+    (n = 2, m = 1) and a two-phase circuit B (n = 1 + 1, m = 1) have the SAME cache key (m, padded n) = (1, 2), A' (n = 2, m = 0) another.
+    A, B, A again, A', then A between _begin and _finish of B: every call gives the model's bytes, and launches what it always did"""
+    A, A_ = cg.Circuit(521, 2, 0, 1, 3, 0, "sparse"), cg.Circuit(520, 2, 0, 0, 3, 0, "sparse")
+    rA, rA_ = pc1.model_proof(A, mgens, 0, False, 521), pc1.model_proof(A_, mgens, 0, False, 520)
+    shape = pc.SHAPES[2]
+    assert shape == (1, 1, 1, 4, "sparse")
+    B, (rB,) = records(mgens, shape, EXPLICIT, (0,))
+    assert (A.m, pc.lg_padded(A.n)) == (B.m, pc.lg_padded(B.n)) == (1, 1) and (A_.m, pc.lg_padded(A_.n)) == (0, 1)
+    b1, b2 = pc.begin_operands([rB], EXPLICIT, B.n1), pc.finish_operands([rB], EXPLICIT)
+    hA, hA_, hB = gpu.circuit_create(*A.csr(), A.n, A.m), gpu.circuit_create(*A_.csr(), A_.n, A_.m), make(gpu, B)
+    open_ = []
+
+    def launches():
+        got = {name: cnt for name, (_, cnt) in gpu.profile_read().items() if cnt}
+        print(got)
+        return got
+
+    def one_phase(h, circ, r):
+        out = gpu.r1cs_prove_fs(gens, h, 1, circ.n, circ.m, **pc1.operands([r], False))
+        got = launches()
+        for name, g, w in zip(("points", "scalars", "wire", "challenges", "state"), out, expected(r)):
+            assert g == w, name
+        return out, got
+
+    def begin():
+        sess, com, chi, st = gpu.r1cs_prove_fs2_begin(gens, hB, 1, B.n1, gadget_label=cg.CHI_LABEL, **b1)
+        open_.append(sess)
+        return (com, chi, st), launches()
+
+    def finish(first):
+        out = gpu.r1cs_prove_fs2_finish(gens, hB, open_[0], 1, B.n, B.m, **b2)
+        assert not open_.pop().value
+        got = launches()
+        check_against_model(first, out, [rB], pc.lg_padded(B.n))
+        return got
+    gpu.profile_enable(True)
+    try:
+        gpu.profile_read()
+        out1, l1 = one_phase(hA, A, rA)                    # 1
+        first, l2 = begin()                                # 2
+        l3 = finish(first)
+        out4, l4 = one_phase(hA, A, rA)                    # 3
+        assert out4 == out1
+        one_phase(hA_, A_, rA_)                            # 4
+        first, l5 = begin()                                # 5
+        out6, l6 = one_phase(hA, A, rA)                    # 6: B's session is open
+        assert out6 == out1
+        l7 = finish(first)                                 # 7
+        assert l1 == l4 == l6 == LAUNCHES_FS
+        assert l2 == l5 == LAUNCHES_BEGIN
+        assert l3 == l7 == LAUNCHES_FINISH
+    finally:
+        gpu.profile_enable(False)
+        for s in open_:
+            if s is not None and s.value:
+                gpu.prover_destroy(s)
+        for h in (hA, hA_, hB):
+            gpu.circuit_destroy(h)
+
+
+# ------------------------------------------------------------------------------------------------ 8: the host mirror
 def _shuffle_prove_param(host, ks, values, seed, cap):
     arr = (C.c_uint64 * (2 * ks))(*values)
     proof, plen, com, ms3 = (C.c_uint8 * 8192)(), C.c_size_t(0), (C.c_uint8 * (2 * ks * 64))(), (C.c_double * 3)()
