@@ -35,7 +35,11 @@ __device__ __forceinline__ Fn fn_pow_u32(Fn base, uint32_t e) {   // base^e, e >
 }
 // Lazy sums keep limbs small but let the VALUE grow (top limb has ~11 spare bits over a 252-bit
 // modulus): fold the value back into (-eps, (1+eps) n) with one Montgomery multiplication by R mod n.
-// Rule used below: never add more than ~64 reduced values (x 64 lanes of a wave sum) without it.
+// Rule used below: fold every 4, 8 or 16 loop trips (at most 33 lazy terms), once more before a wave_sum, and end the 4-wave add
+// (256 reduced values) with store_plain or fn_reduce.  Measured headroom (tests/test_lazy_sums_cpu.py, heaviest terms -- lazy value
+// n - 1 -- on a UBSan build): 4095 unreduced products may be added before fn_reduce and 4095 reduced values before the last
+// reduction; the 4096th wraps the top limb (4096 * 2^19 = 2^31).  The values then are far past the |v| < 2^256 that mul documents for
+// two general operands: fn_reduce's other operand is R mod n < n, which is what leaves the room.
 BP_HD Fn fn_reduce(const Fn &x) { return mul(x, fe_one<FN>()); }
 // raw limb I/O for device scratch (zpow tables, partial sums)
 __device__ __forceinline__ void raw_put(int32_t *d, const Fn &x) {

@@ -8,6 +8,7 @@ import random
 import re
 
 import circuit_gen as cg
+import lazy_sum_cases as lz
 import mpc_dealer as md
 
 pm = cg.pm
@@ -85,7 +86,8 @@ def csr(rows, nchi=0):
 
 def length_rows(T, n=6, m=2, seed=11):
     """Hand-built rows of every length of row_lengths(T) in ONE circuit -- so both routes run in one launch -- with coefficients and
-    values at 0, 1 and n - 1 beside random ones, then: the all-(n - 1) x (n - 1) row of 257 terms (the largest lazy sums), a row of
+    values at 0, 1 and n - 1 beside random ones, then: a row of 257 of the heaviest products (coefficient x value = -2^-261, each lazily
+    n - 1: tests/lazy_sum_cases.py), the all-(n - 1) x (n - 1) row of 257 terms (each lazily the 251-bit 2^261 mod n), a row of
     explicit zero terms, a row of one variable repeated, rows of `One` terms only (a non-zero constant alone, a zero constant alone,
     two constants that cancel).  -> (rows, witness); the rows are NOT satisfied: the model's residuals are the expectation."""
     rnd = random.Random(seed)
@@ -96,6 +98,7 @@ def length_rows(T, n=6, m=2, seed=11):
     rows = []
     for length in row_lengths(T):
         rows.append([(rnd.choice(variables), rnd.choice((0, 1, N - 1, rnd.randrange(N)))) for _ in range(length)])
+    rows.append([(("L", 3), lz.C * pow(a_L[3], -1, N) % N)] * 257)
     rows.append([(("L", 2), N - 1)] * 257)
     rows.append([(rnd.choice(variables), 0) for _ in range(T + 3)])
     rows.append([(("R", 3), rnd.randrange(N)) for _ in range(40)])

@@ -8,6 +8,7 @@ import pytest
 import circuit_gen as cg
 import mpc_dealer as md
 import oracle_lib as o
+from polys_model import model_polys, padded
 
 pm = cg.pm
 N = pm.N
@@ -75,10 +76,6 @@ def ints(b):
 
 def pack(vals):
     return b"".join(le(v) for v in vals)
-
-
-def padded(n):
-    return 1 if n == 0 else 1 << (n - 1).bit_length()
 
 
 def make(gpu, circ, ark=False):
@@ -187,23 +184,6 @@ def test_malformed_circuits_are_refused_and_the_context_stays_usable(gpu):
 
 
 # ------------------------------------------------------------------------------------------------ prover polynomials
-def model_polys(circ, weights, y, x, wit):
-    """prover.rs:587-619 and 659-672 on integers: t_1..t_6, l_vec, r_vec with the zero / -y^i padding"""
-    wL, wR, wO = weights[:3]
-    n, np_ = circ.n, padded(circ.n)
-    yi = pow(y, -1, N)
-    l1 = [(wit["aL"][i] + pow(yi, i, N) * wR[i]) % N for i in range(n)]
-    l2, l3 = wit["aO"], wit["sL"]
-    r0 = [(wO[i] - pow(y, i, N)) % N for i in range(n)]
-    r1 = [(pow(y, i, N) * wit["aR"][i] + wL[i]) % N for i in range(n)]
-    r3 = [pow(y, i, N) * wit["sR"][i] % N for i in range(n)]
-    ip = lambda a, b: sum(u * v for u, v in zip(a, b)) % N       # noqa: E731
-    t = [ip(l1, r0), (ip(l1, r1) + ip(l2, r0)) % N, (ip(l2, r1) + ip(l3, r0)) % N, (ip(l1, r3) + ip(l3, r1)) % N, ip(l2, r3), ip(l3, r3)]
-    lv = [x * (l1[i] + x * (l2[i] + x * l3[i])) % N for i in range(n)] + [0] * (np_ - n)
-    rv = [(r0[i] + x * (r1[i] + x * x * r3[i])) % N for i in range(n)] + [(-pow(y, i, N)) % N for i in range(n, np_)]
-    return t, lv, rv
-
-
 def random_witness(rnd, n):
     return {k: [rnd.randrange(N) for _ in range(n)] for k in ("aL", "aR", "aO", "sL", "sR")}
 

@@ -117,6 +117,7 @@ def test_hand_built_rows_cover_every_length_and_edge():
     assert es[q - 4] == 5 and es[q - 3] == 0 and es[q - 2] == 0 and es[q - 1] == T + 2      # the rows of constants only
     assert es[lengths.index(0)] == 0                                                        # the empty row
     assert es[q - 7] == 257 * (N - 1) * (N - 1) % N                                         # the all-(n - 1) row
+    assert es[q - 8] == 257 * -pow(1 << 261, -1, N) % N                                     # the row of the heaviest products
     assert es[q - 6] == 0 and any(es)                                                       # explicit zeros; not a satisfied circuit
 
 

@@ -1,13 +1,15 @@
 """The row evaluation of csrc/fn_dev.cuh (eval_row: what every lane of bpgpu_r1cs_constraints_satisfied and
 bpgpu_mpc_constraints_eval runs) compiled for the CPU with -fsanitize=undefined as a stand-alone program
-(tests/csrc/rows_host_test.cpp) and compared with Python integers: rows around the lazy sums' reduction every 16th term, the largest
-sums the accumulation can meet, zero coefficients, a repeated variable and parametric terms at the edges of the field."""
+(tests/csrc/rows_host_test.cpp) and compared with Python integers: rows around the lazy sums' reduction every 16th term, the heaviest
+sums the accumulation can meet (every product lazily n - 1: tests/lazy_sum_cases.py), zero coefficients, a repeated variable and
+parametric terms at the edges of the field."""
 import os
 import random
 import subprocess
 
 import pytest
 
+import lazy_sum_cases as lz
 import satisfied_cases as sc
 
 N = sc.N
@@ -56,7 +58,11 @@ def test_row_evaluation_equals_the_model(exe, tmp_path):
         # random terms over every kind, the constant included
         cases.append(([(rnd.randrange(5), rnd.randrange(len(vals)), 0, rnd.choice((0, 1, N - 1, rnd.randrange(N)))) for _ in range(length)],
                       vals, (), 1))
-        # the largest lazy sums: every product (n - 1) x (n - 1)
+        # the heaviest lazy sums: coefficient x value = -2^-261, every product lazily n - 1, through a plane and through chi
+        cases.append(([(0, 3, 0, lz.C * lz.inv(vals[3]) % N)] * length, vals, (), 1))
+        cases.append(([(k % 4, 3 + k % 9, 0, lz.C * lz.inv(vals[3 + k % 9]) % N) for k in range(length)], vals, (), 1))
+        cases.append(([(1, 4, 2, lz.C * lz.inv(vals[4] * vals[5]) % N)] * length, vals, (1, vals[5], 1), 1))
+        # every product (n - 1) x (n - 1): lazily 2^261 mod n, a 251-bit value
         cases.append(([(0, 2, 0, N - 1)] * length, vals, (), 1))
         # coefficient 0 throughout; one variable repeated
         cases.append(([(rnd.randrange(4), rnd.randrange(len(vals)), 0, 0) for _ in range(length)], vals, (), 1))
