@@ -100,7 +100,8 @@ int bpgpu_input_flag(bpgpu_ctx *ctx, int *bad);
  * (bpgpu_r1cs_prover_commit), 17 polynomial build, 18 bpgpu_msm_gens (T commitments), 19 IPP session set-up, 20 the IPP round
  * loop, 21 the L / R table-lookup MSM of one round (the prover's dominant kernel, nested inside 20).
  * Kind 22: the launches only bpgpu_r1cs_prove_fs and bpgpu_r1cs_prove_fs2_begin / _finish have (their transcript slices, the scalar
- * links between the stages, proof assembly); the stages they chain keep reporting under 16..21.
+ * links between the stages, proof assembly); the stages they chain keep reporting under 16..21.  bpgpu_r1cs_commit_values and
+ * bpgpu_mpc_commit_values report their point launches under 16 and the chain launch under 22.
  * Kind 23: the decode launches of bpgpu_r1cs_verify_mixed_wire_* (ragged unpack + point decompression, and the fold of the reject
  * bits: two pairs per check); the ragged transcript replay of those calls reports under 5. */
 int bpgpu_profile_enable(bpgpu_ctx *ctx, int on);
@@ -423,6 +424,38 @@ int bpgpu_r1cs_prove_fs_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
                             const void *a_L, const void *a_R, const void *a_O, const void *s_L, const void *s_R,
                             const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
                             void *proof_scalars, void *wire, void *challenges_out, void *states_out);
+/* Prover::commit (r1cs/prover.rs:319-329) for the m committed values of each of nb provers -- the step BEFORE the calls above and
+ * below: V = v B + v_blinding B_blinding (PedersenGens::commit, generators.rs:41-43) over g's resident Pedersen pair (table generators
+ * 0 and 1; the pair may be equal, as in the reference's default PedersenGens) and, optionally, the chain from Prover::new to the last
+ * commit.  A host that holds (init_state, v, v_blinding, witness, blindings) on the device enqueues bpgpu_r1cs_commit_values_dev ->
+ * bpgpu_r1cs_constraints_satisfied_dev -> bpgpu_r1cs_prove_fs_dev without a wait or a copy, and gets back what the wire verifiers take.
+ *   v, v_blinding  nb x m         ark-ff Montgomery form: the buffers bpgpu_r1cs_constraints_satisfied takes as v and
+ *                                 bpgpu_r1cs_prove_fs as v_blinding (one set of device buffers serves all three calls); may be NULL
+ *                                 when nb m == 0
+ *   states_in      (optional) nb x 32   the chain state when the host would call Prover::new: the value the _fs / _wire verifiers take
+ *                                 as init_states
+ *   V              (optional) nb x m x 64   boundary form
+ *   V_compressed   (optional) nb x m x 32   the form bpgpu_points_compress writes and bpgpu_r1cs_verify_batch_wire reads as commitments
+ *   states_out     (optional) nb x 32   the chain after r1cs_domain_sep (prover.rs:286) and m x append_point("V", V_j) in order: exactly
+ *                                 the states_in of bpgpu_r1cs_prove_fs / bpgpu_r1cs_prove_fs2_begin
+ * states_in and states_out go together: both, or neither (no transcript).  At least one of V, V_compressed, states_out must be given.
+ * A prover does not validate: an identity commitment (v = v_blinding = 0, or v + v_blinding = 0 mod n over equal bases) is written as
+ * 64 zero bytes, compressed as 00..00 40 (31 zero bytes, then 0x40) and absorbed as 64 zero bytes.  m == 0 is legal: no points, and
+ * states_out is the state after the separator.
+ * Refusals, before anything is launched: BPGPU_E_ARG for a null context or gens, for a null v or v_blinding while nb m > 0, for
+ * exactly one of states_in / states_out, for no output at all and for a context after bpgpu_set_shard(world > 1); BPGPU_E_LEN for
+ * nb m above 2^30 (the launches index commitments and rows of two scalars with room to spare below that; the two-party call counts
+ * its three planes: 3 nb m); nb == 0: BPGPU_OK, no output touched.  A non-canonical ark limb gives BPGPU_E_ARG in the host form and
+ * raises bpgpu_input_flag in the `_dev` form (every operand and result a device pointer; asynchronous on the context's stream).  A
+ * failed call leaves no pool memory behind.  Profiling: the point launches report under kind 16, the chain launch under kind 22.
+ * The chain of ONE prover is serial: a lane absorbs its m points one after the other.  For m in the tens of thousands (the
+ * 2^14-shuffle's 32 768 commitments) the host's hashing is faster than one lane -- DESIGN.md gives 9-13 ms for the host; the device
+ * figure is not measured -- so such a caller passes states_in = states_out = NULL, takes the points from the call and absorbs them on
+ * the host. */
+int bpgpu_r1cs_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const uint8_t *v, const uint8_t *v_blinding,
+                             const uint8_t *states_in, uint8_t *V, uint8_t *V_compressed, uint8_t *states_out);
+int bpgpu_r1cs_commit_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const void *v, const void *v_blinding,
+                                 const void *states_in, void *V, void *V_compressed, void *states_out);
 /* Prover::prove for nb provers of ONE two-phase circuit (bpgpu_circuit_create_param with nchi == 1) in TWO calls around the gadget: the
  * phase-2 witness depends on a challenge the host evaluates its gadget on, and that is the only round trip left.  The Fiat-Shamir hash
  * chain runs on the device in both calls; they replace bpgpu_r1cs_prover_commit (twice), _session_polys_param, bpgpu_msm_gens,
@@ -569,6 +602,13 @@ int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *ipp, const uint8_t *opened, u
  * opening of its own -- the fabric's business.  Refusals and the circuit's row-major view: as bpgpu_r1cs_constraints_satisfied. */
 int bpgpu_mpc_constraints_eval(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const uint8_t *a_L, const uint8_t *a_R,
                                const uint8_t *a_O, const uint8_t *v, const uint8_t *gadget_challenges, uint8_t *residuals);
+/* bpgpu_mpc_commit_values -- one party's local half of MpcProver::commit_preshared / batch_commit_preshared (mpc_prover.rs:402-456;
+ * PedersenGens::commit_shared, generators.rs:52-58): v, v_blinding nb x 3 x m in the plane layout above, ark form -> V nb x 3 x m x 64 B,
+ * V_k = v_k B + v_blinding_k B_blinding on every plane alike over g's resident Pedersen pair; no step needs the party index.  There is
+ * no transcript: the parties open the points over the network first, and the host absorbs the OPENED values.  Shape and limb errors as
+ * bpgpu_r1cs_commit_values (a null V is "no output"; BPGPU_E_LEN for 3 nb m above 2^30). */
+int bpgpu_mpc_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const uint8_t *v, const uint8_t *v_blinding,
+                            uint8_t *V);
 
 /* out[i] = scalars[i] * (curve generator) -- GeneratorsChain::next (generators.rs:112-124),
  * Q = w * B (prover.rs:687), PedersenGens::commit with B = B_blinding (generators.rs:41-43,61-70) */

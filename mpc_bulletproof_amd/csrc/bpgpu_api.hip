@@ -4063,6 +4063,87 @@ int bpgpu_r1cs_prove_fs2_finish(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
   return prove_fs2_finish_entry(ctx, g, c, session, {nullptr, a_L, a_R, a_O, s_L, s_R, vector_keys, v_blinding, blindings, proof_points,
                                                      proof_scalars, wire, challenges_out, states_out}, false);
 }
+/* ---- the step before Prover::prove: Prover::commit for every committed value (prover.rs:319-329) -- V = v B + v_blinding B_blinding
+ * over the resident Pedersen pair and, optionally, the chain from Prover::new up to the last append_point("V") -- and one party's
+ * local half of MpcProver::batch_commit_preshared (mpc_prover.rs:402-456), the same sums over the three planes. ------------------- */
+namespace {
+struct CommitIo { const void *v, *v_blinding, *states_in; void *V, *V_compressed, *states_out; };   // host memory, or HBM (the _dev form, the _locked function)
+constexpr size_t COMMIT_VALUES_MAX = (size_t)1 << 30;   // commitments of one call (include/bpgpu.h)
+}  // namespace
+// the refusals that depend on the pointers alone
+static int commit_values_check(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nv, size_t m, const CommitIo &a) {
+  if (!ctx || !g) return BPGPU_E_ARG;
+  if (nv && m && (!a.v || !a.v_blinding)) return BPGPU_E_ARG;
+  if ((a.states_in != nullptr) != (a.states_out != nullptr)) return BPGPU_E_ARG;   // the chain's two ends go together
+  if (!a.V && !a.V_compressed && !a.states_out) return BPGPU_E_ARG;
+  return BPGPU_OK;
+}
+// ctx->mu held, arguments checked, nv > 0, every pointer in HBM; asynchronous.  nv virtual provers of m commitments each (nv = 3 nb
+// for a party's planes), the chain -- if asked for -- over nchain = nv provers.  The points are the fixed-base launch with zero
+// vector generators over rows of two scalars; the workspace goes back to the pool on the way out (stream-ordered reuse).
+static int commit_values_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nv, size_t m, const CommitIo &io) {
+  const size_t tot = nv * m;
+  hipStream_t st = ctx->st;
+  PoolBlock ws(ctx);
+  Words8 *dV = (Words8 *)io.V;
+  if (tot) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // (rows of two scalars are at most 128 window pairs: fixed_msm_chunks gives 1 at every table width today, so `part` stays null
+    // and the launch sums inside a block or a wave; the scratch follows the function in case its tuning changes)
+    const size_t chunks = fixed_msm_chunks(g->c, 0, tot);
+    const size_t b_rows = tot * 2 * sizeof(Words8), b_res = up(tot * sizeof(JacRaw)), b_part = chunks > 1 ? up(tot * chunks * sizeof(JacRaw)) : 0;
+    if (!pool_alloc(ctx, &ws.p, b_rows + b_res + b_part + (dV ? 0 : tot * 64))) return BPGPU_E_OOM;
+    uint8_t *at = (uint8_t *)ws.p;
+    Words8 *rows = (Words8 *)at; at += b_rows;
+    JacRaw *res = (JacRaw *)at; at += b_res;
+    JacRaw *part = b_part ? (JacRaw *)at : nullptr; at += b_part;
+    if (!dV) dV = (Words8 *)at;
+    ProfScope points(ctx, 16, st);
+    commit_value_rows(st, (const Words8 *)io.v, (const Words8 *)io.v_blinding, rows, tot, ctx->d_flag);
+    fixed_msm(st, g->c, g->table, 0, g->cap, (const uint32_t *)rows, 2 * 8, res, tot, part);
+    jac_to_boundary(st, res, dV, tot);
+    if (io.V_compressed) points_compress(st, dV, (Words8 *)io.V_compressed, tot);
+  }
+  if (io.states_out) {
+    ProfScope chain(ctx, 22, st);
+    commit_transcript(st, nv, m, (const Words8 *)io.states_in, dV, (Words8 *)io.states_out);
+  }
+  return launch_ok(ctx);
+}
+static int commit_values_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, int planes, size_t m, const CommitIo &a, bool dev) {
+  return noexcept_abi([&]() -> int {
+    CK(commit_values_check(ctx, g, nb, m, a));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->shard_world > 1) return BPGPU_E_ARG;      // a commitment is one rank's: nothing of it is sharded
+    if (nb > COMMIT_VALUES_MAX / planes || (m && nb * planes > COMMIT_VALUES_MAX / m)) return BPGPU_E_LEN;
+    if (!nb) return BPGPU_OK;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const size_t nv = nb * planes, tot = nv * m;
+    CK(flag_reset(ctx));   // (the _dev form: the flag reports on the most recent *_dev call)
+    if (dev) return commit_values_locked(ctx, g, nv, m, a);
+    // the host form's staging: v | v_blinding | states_in, then V | V_compressed | states_out, each only when asked for
+    const size_t b_sc = tot * 32, b_st = a.states_in ? nv * 32 : 0, b_V = a.V ? tot * 64 : 0, b_Vc = a.V_compressed ? tot * 32 : 0;
+    PoolBlock stage(ctx);
+    if (!pool_alloc(ctx, &stage.p, 2 * b_sc + 2 * b_st + b_V + b_Vc)) return BPGPU_E_OOM;
+    uint8_t *dv = (uint8_t *)stage.p, *dvb = dv + b_sc, *dsi = dvb + b_sc, *dV = dsi + b_st, *dVc = dV + b_V, *dso = dVc + b_Vc;
+    CK(h2d(ctx, dv, a.v, b_sc));
+    CK(h2d(ctx, dvb, a.v_blinding, b_sc));
+    CK(h2d(ctx, dsi, a.states_in, b_st));
+    CK(commit_values_locked(ctx, g, nv, m, {dv, dvb, b_st ? dsi : nullptr, b_V ? dV : nullptr, b_Vc ? dVc : nullptr, b_st ? dso : nullptr}));
+    return checked_download(ctx, {{a.V, dV, b_V}, {a.V_compressed, dVc, b_Vc}, {a.states_out, dso, b_st}});
+  });
+}
+int bpgpu_r1cs_commit_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const void *v, const void *v_blinding,
+                                 const void *states_in, void *V, void *V_compressed, void *states_out) {
+  return commit_values_entry(ctx, g, nb, 1, m, {v, v_blinding, states_in, V, V_compressed, states_out}, true);
+}
+int bpgpu_r1cs_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const uint8_t *v, const uint8_t *v_blinding,
+                             const uint8_t *states_in, uint8_t *V, uint8_t *V_compressed, uint8_t *states_out) {
+  return commit_values_entry(ctx, g, nb, 1, m, {v, v_blinding, states_in, V, V_compressed, states_out}, false);
+}
+int bpgpu_mpc_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const uint8_t *v, const uint8_t *v_blinding, uint8_t *V) {
+  return commit_values_entry(ctx, g, nb, 3, m, {v, v_blinding, nullptr, V, nullptr, nullptr}, false);
+}
 /* scalars[i] * (curve generator): GeneratorsChain::next (generators.rs:112-124), Q = w * B (prover.rs:687) */
 int bpgpu_generator_mul(bpgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out) {
   if (!ctx || (n && (!scalars || !out))) return BPGPU_E_ARG;

@@ -24,17 +24,31 @@ __device__ __forceinline__ Fn fn_ark_out() { constexpr int32_t C[NL] = FN_ARK_OU
 __device__ __forceinline__ Fp fp_ark_in() { constexpr int32_t C[NL] = FP_ARK_IN; return limbs_const<FP>(C); }
 __device__ __forceinline__ Fp fp_ark_out() { constexpr int32_t C[NL] = FP_ARK_OUT; return limbs_const<FP>(C); }
 
-// ark Montgomery limbs (x 2^256 mod n) -> plain canonical words
+// one scalar, ark Montgomery limbs (x 2^256 mod n) -> plain canonical words; a non-canonical limb set raises *bad and gives zero
+__device__ __forceinline__ void scalar_from_ark(const Words8 *in, Words8 *out, int *bad) {
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) w[j] = in->w[j];
+  if (!words_lt_mod<FN>(w)) {
+    atomicOr(bad, 1);
+#pragma unroll
+    for (int j = 0; j < 8; j++) out->w[j] = 0;
+    return;
+  }
+  pack(w, canon(mul(unpack<FN>(w), fn_ark_in())));
+#pragma unroll
+  for (int j = 0; j < 8; j++) out->w[j] = w[j];
+}
 __global__ void __launch_bounds__(256) k_scalars_from_ark(const Words8 *in, Words8 *out, size_t n, int *bad) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in[i].w[j];
-  if (!words_lt_mod<FN>(w)) { atomicOr(bad, 1); for (int j = 0; j < 8; j++) out[i].w[j] = 0; return; }
-  pack(w, canon(mul(unpack<FN>(w), fn_ark_in())));
-#pragma unroll
-  for (int j = 0; j < 8; j++) out[i].w[j] = w[j];
+  scalar_from_ark(&in[i], &out[i], bad);
+}
+// the same for two arrays into interleaved rows: lane t converts v[t / 2] (t even) or v_blinding[t / 2] (t odd) into rows[t]
+__global__ void __launch_bounds__(256) k_commit_value_rows(const Words8 *v, const Words8 *vb, Words8 *rows, size_t n, int *bad) {
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * n) return;
+  scalar_from_ark(((t & 1) ? vb : v) + (t >> 1), &rows[t], bad);
 }
 // plain canonical words -> ark Montgomery limbs
 __global__ void __launch_bounds__(256) k_scalars_to_ark(const Words8 *in, Words8 *out, size_t n, int *bad) {
@@ -102,6 +116,9 @@ __global__ void __launch_bounds__(256) k_aff_to_jacraw(const AffDev *in, JacRaw 
 
 void scalars_from_ark(hipStream_t st, const Words8 *in, Words8 *out, size_t n, int *bad) {
   if (n) hipLaunchKernelGGL(k_scalars_from_ark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, n, bad);
+}
+void commit_value_rows(hipStream_t st, const Words8 *v, const Words8 *vb, Words8 *rows, size_t n, int *bad) {
+  if (n) hipLaunchKernelGGL(k_commit_value_rows, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, v, vb, rows, n, bad);
 }
 void scalars_to_ark(hipStream_t st, const Words8 *in, Words8 *out, size_t n, int *bad) {
   if (n) hipLaunchKernelGGL(k_scalars_to_ark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, n, bad);

@@ -664,6 +664,38 @@ __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrSte
 #pragma unroll
   for (int i = 0; i < 4; i++) states[p * 4 + i] = st[i];
 }
+// What comes BEFORE that schedule (bpgpu_r1cs_commit_values): Prover::new's r1cs_domain_sep (prover.rs:286), then append_point("V", V_j)
+// for the prover's m commitments in order (Prover::commit, :319-329).  One lane per prover and a loop over its points -- m is a
+// caller's number, up to tens of thousands, so the points are no step list.  states_in: the chain on entry to Prover::new (what the
+// wire verifiers take as init_states); states_out: the chain on entry to Prover::prove; they may be the same array.  Nothing is
+// validated: an identity commitment is absorbed as its 64 zero bytes.
+__global__ void __launch_bounds__(64) k_commit_transcript(size_t nb, size_t m, const Words8 *states_in, const Words8 *points, Words8 *states_out) {
+  // (no raised wave priority: the note in k_verify_transcript)
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nb) return;
+  uint64_t st[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) st[i] = (uint64_t)states_in[p].w[2 * i] | ((uint64_t)states_in[p].w[2 * i + 1] << 32);
+  {
+    constexpr Label DS = mk_label("dom-sep");
+    const Label lab = TR_LABELS[LB_r1cs];
+    uint64_t tail[5] = {32, lab.w[0], lab.w[1], lab.w[2], lab.w[3]};
+    chain_hash<5>(st, 0x00, DS, tail);
+  }
+  const Label labV = TR_LABELS[LB_V];
+  uint64_t tail[9];
+  tail[0] = 64;
+#pragma unroll 1
+  for (size_t j = 0; j < m; j++) {
+    load64(points + (p * m + j) * 2, tail + 1);
+    chain_hash<9>(st, 0x00, labV, tail);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) { states_out[p].w[2 * i] = (uint32_t)st[i]; states_out[p].w[2 * i + 1] = (uint32_t)(st[i] >> 32); }
+}
+void commit_transcript(hipStream_t st, size_t nb, size_t m, const Words8 *states_in, const Words8 *points, Words8 *states_out) {
+  if (nb) hipLaunchKernelGGL(k_commit_transcript, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, nb, m, states_in, points, states_out);
+}
 // the step list and its slices: slice j = steps [cut[j], cut[j + 1]).  Points are indexed within the slice's own array (A_I1 A_O1 S1 |
 // T_1 T_3 T_4 T_5 T_6), scalars as t_x t_x_blinding e_blinding, challenges as y z u x w.  One phase: the three slices above.  Two phases
 // -- a circuit WITH randomized constraints and one gadget challenge (bpgpu_r1cs_prove_fs2_begin / _finish) -- four:

@@ -138,6 +138,9 @@ void segmented_sum(hipStream_t st, const JacRaw *in, JacRaw *out, size_t nb, siz
 // coordinate 4 x u64 limbs of c 2^256 mod p, identity Z = 0
 void scalars_from_ark(hipStream_t st, const Words8 *in, Words8 *out_plain, size_t n, int *bad);
 void scalars_to_ark(hipStream_t st, const Words8 *in_plain, Words8 *out, size_t n, int *bad);
+// rows[2 i] = v[i], rows[2 i + 1] = v_blinding[i], plain canonical words from ark limbs: the (value, blinding) rows of n Pedersen
+// commitments over [B, B_blinding], the operand of fixed_msm with zero vector generators
+void commit_value_rows(hipStream_t st, const Words8 *v, const Words8 *v_blinding, Words8 *rows, size_t n, int *bad);
 void points_from_ark(hipStream_t st, const Words8 *in /* 3 per point */, JacRaw *out, size_t n, int *bad);
 void points_to_ark(hipStream_t st, const JacRaw *in, Words8 *out /* 3 per point */, size_t n);
 void aff_to_jacraw(hipStream_t st, const AffDev *in, JacRaw *out, size_t n);
@@ -393,6 +396,9 @@ int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t pad
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
                        size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges, const uint8_t *gadget_label = nullptr,
                        Words8 *chi = nullptr);
+// the chain before Prover::prove (bpgpu_r1cs_commit_values), a lane per prover: r1cs_domain_sep, then append_point("V", V_j) over the
+// prover's m boundary points (nb x m, prover-major).  states_in / states_out: nb x 32 B, may alias
+void commit_transcript(hipStream_t st, size_t nb, size_t m, const Words8 *states_in, const Words8 *points, Words8 *states_out);
 // rows[(5 p + j) * 2 ..] = (t, t_blinding) of T_1, T_3..T_6 over [B, B_blinding]; t: nb x 6, bl: nb x 8 (i o s blinding, tb1 tb3 tb4 tb5 tb6)
 void prove_fs_t_rows(hipStream_t st, size_t nb, const Words8 *t, const Words8 *bl, Words8 *rows);
 // out[p] = (t_x, t_x_blinding, e_blinding) from x, t, bl and tb2 = <wV, v_blinding>: summed by the proof's lane for m up to

@@ -540,6 +540,22 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_prove_fs_dev(self.ctx, gens, circuit, nb, d_states, d_a_L, d_a_R, d_a_O, d_s_L, d_s_R, d_vector_keys, d_v_blinding,
                                               d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out))
 
+    def r1cs_commit_values(self, gens, nb, m, v, v_blinding, states=None, want_points=True, want_compressed=True):
+        """Prover::commit for the m values of each of nb provers (include/bpgpu.h bpgpu_r1cs_commit_values): v, v_blinding nb x m in
+        ark-ff Montgomery form, states nb x 32 B the chain on entry to Prover::new (or None: no transcript) -> (V nb x m x 64 B,
+        V_compressed nb x m x 32 B, states_out nb x 32 B: the states of r1cs_prove_fs), each None when not asked for"""
+        V = _out(64 * nb * m) if want_points else None
+        Vc = _out(32 * nb * m) if want_compressed else None
+        so = _out(32 * nb) if states is not None else None
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_commit_values(self.ctx, gens, nb, m, opt(v), opt(v_blinding), opt(states), V, Vc, so))
+        return (bytes(V)[:64 * nb * m] if want_points else None, bytes(Vc)[:32 * nb * m] if want_compressed else None,
+                bytes(so)[:32 * nb] if states is not None else None)
+
+    def r1cs_commit_values_dev(self, gens, nb, m, d_v, d_v_blinding, d_states=None, d_V=None, d_V_compressed=None, d_states_out=None):
+        """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
+        self._ck(_lib.bpgpu_r1cs_commit_values_dev(self.ctx, gens, nb, m, d_v, d_v_blinding, d_states, d_V, d_V_compressed, d_states_out))
+
     def r1cs_prove_fs2_begin(self, gens, circuit, nb, n1, states, gadget_label, blindings, a_L=None, a_R=None, a_O=None, s_L=None, s_R=None,
                              vector_keys=None):
         """The first of the two calls that prove nb provers of a two-phase circuit (include/bpgpu.h bpgpu_r1cs_prove_fs2_begin): the
@@ -626,6 +642,14 @@ class BpGpu:
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
         self._ck(_lib.bpgpu_mpc_constraints_eval(self.ctx, circuit, nb, opt(a_L), opt(a_R), opt(a_O), opt(v), opt(gadget_challenges), res))
         return bytes(res)[:32 * nb * 3 * q]
+
+    def mpc_commit_values(self, gens, nb, m, v, v_blinding):
+        """one party's local half of MpcProver::batch_commit_preshared (mpc_prover.rs:402-456): v, v_blinding nb x 3 x m -> the
+        commitments on the party's planes, nb x 3 x m x 64 B, for the host to open"""
+        V = _out(64 * nb * 3 * m)
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_mpc_commit_values(self.ctx, gens, nb, m, opt(v), opt(v_blinding), V))
+        return bytes(V)[:64 * nb * 3 * m]
 
     def mpc_prover_polys_mask(self, session, circuit, nb, n, y, z, triples, gadget_challenges=None):
         """mpc_prover.rs:783-829: triples nb x 6 x 3 x 3 x n -> masked d, e (nb x 6 x 2 x 3 x n)"""
