@@ -40,6 +40,11 @@ __device__ __forceinline__ Fn fn_pow_u32(Fn base, uint32_t e) {   // base^e, e >
 // n - 1 -- on a UBSan build): 4095 unreduced products may be added before fn_reduce and 4095 reduced values before the last
 // reduction; the 4096th wraps the top limb (4096 * 2^19 = 2^31).  The values then are far past the |v| < 2^256 that mul documents for
 // two general operands: fn_reduce's other operand is R mod n < n, which is what leaves the room.
+// The verifier's sites against that headroom (tests/verifier_sum_cases.py drives each across its fold): flatten_column below 1 + 16
+// products, and its callers add at most two more products to the lazy column; the delta and `One`-column loops of
+// k_verify_scalars(_fast) and k_vsl_gh / k_vsl_wc 1 + 16 products per lane, then 64 reduced lanes (2 reduced waves per block of the
+// grid-split route); k_vsl_tail 1 + 8 partials of 2 reduced values each; k_sc_weighted_colsum, comb_colsum_body (k_pip2.hip) and
+// mix_colsum_body (k_mixed.hip) 1 + 16 products per lane, then 256 reduced values.
 BP_HD Fn fn_reduce(const Fn &x) { return mul(x, fe_one<FN>()); }
 // raw limb I/O for device scratch (zpow tables, partial sums)
 __device__ __forceinline__ void raw_put(int32_t *d, const Fn &x) {

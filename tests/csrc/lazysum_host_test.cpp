@@ -17,6 +17,27 @@
 //                           k_inner_product_partial over `grid` blocks and k_inner_product_finish over their partials
 //   finish nparts plen, then plen pairs `a b`
 //                           k_inner_product_finish over nparts partials, partial i = fn_reduce(a * b) of pattern entry i mod plen
+// The verifier's sites (every term list is plen terms `kind a b` as for `block`; element i reads term i mod plen):
+//   wave pre fold L plen, terms
+//                           one wave of 64 lanes over L elements (stride 64), one term each: k_verify_scalars' `One`-column loop
+//                           (pre 0: add, then fold) and its delta loop (pre 1: fold at the head of the trip, then add); fn_reduce,
+//                           the butterfly, fn_reduce, store_plain of the NEGATED sum (w_c's sign; delta's shape is the same up to it)
+//   column fold E negate mult plen, terms
+//                           flatten_column over E entries, serial, the lazy result negated (a V column) or not and multiplied by
+//                           load_plain(mult): V_j = w_V,j r x^2
+//   hexpr fold E x yi b sr plen, terms of the L column, terms of the O column
+//                           h_i = yi (x wL + wO - b sr) - 1 on two lazy columns of E entries each, and on the same line
+//                           g-side delta term (wO yi) wL: the two places a lazy column meets another product
+//   tail fold nparts waves plen, terms
+//                           k_vsl_tail: nparts partials, partial i the unreduced sum of `waves` reduced terms, added with a fold
+//                           after every fold-th; fn_reduce; negated
+//   mix fold nseg len_1 .. len_nseg plen, terms
+//                           mix_colsum_body: 256 lanes over nseg segments, ONE counter per lane across them; a single segment is
+//                           k_sc_weighted_colsum / comb_colsum_body
+//   split pre fold tfold grid L plen, terms
+//                           k_vsl_wc (pre 0) / k_vsl_gh (pre 1: fold at the head of the trip): `grid` blocks of 128 lanes over L
+//                           elements (stride grid * 128), fold in the loop, two waves per block, then k_vsl_tail's sum of the grid
+//                           partials with fold tfold; negated
 //   sumraw count a b        fn_reduce of `count` unreduced products a * b added up, then the canonical value
 //   sumred count a b        `count` reduced products fn_reduce(a * b) added up, then the canonical value with no reduction between
 #include <cstdio>
@@ -85,6 +106,37 @@ Fn finish(const std::vector<Fn> &partials) {
     for (size_t i = l; i < partials.size(); i += 64) lanes[l] = add(lanes[l], partials[i]);
   for (auto &x : lanes) x = fn_reduce(x);
   return wave_sum_host(lanes.data());
+}
+// a term list: kind 0 a * b, 1 a * (0 - b), 2 load_plain(a) alone
+bool read_terms(FILE *f, size_t count, std::vector<Fn> *out) {
+  const Fn zero = fe_zero<FN>();
+  out->resize(count);
+  for (auto &t : *out) {
+    unsigned kind;
+    Fn a, b;
+    if (fscanf(f, "%x", &kind) != 1 || kind > 2 || !read_fn(f, &a) || !read_fn(f, &b)) return false;
+    t = kind == 0 ? mul(a, b) : (kind == 1 ? mul(a, sub(zero, b)) : a);
+  }
+  return true;
+}
+// flatten_column's loop over E entries
+Fn column(const std::vector<Fn> &terms, unsigned E, unsigned fold) {
+  Fn acc = fe_zero<FN>();
+  unsigned cnt = 0;
+  for (unsigned t = 0; t < E; t++) {
+    acc = add(acc, terms[t % terms.size()]);
+    if (++cnt % fold == 0) acc = fn_reduce(acc);
+  }
+  return acc;
+}
+// k_vsl_tail's sum of partials
+Fn tail_sum(const std::vector<Fn> &parts, unsigned fold) {
+  Fn acc = fe_zero<FN>();
+  for (size_t i = 0; i < parts.size(); i++) {
+    acc = add(acc, parts[i]);
+    if (i % fold == fold - 1) acc = fn_reduce(acc);
+  }
+  return fn_reduce(acc);
 }
 }  // namespace
 
@@ -171,6 +223,99 @@ int main(int argc, char **argv) {
       std::vector<Fn> partials(nparts);
       for (unsigned i = 0; i < nparts; i++) partials[i] = terms[i % plen];
       print_plain(finish(partials));
+    } else if (c == "wave") {
+      unsigned pre, fold, L, plen;
+      std::vector<Fn> terms;
+      if (fscanf(f, "%x %x %x %x", &pre, &fold, &L, &plen) != 4 || pre > 1 || !fold || !plen || !read_terms(f, plen, &terms)) return 3;
+      Fn lanes[64];
+      for (unsigned t = 0; t < 64; t++) {
+        Fn acc = zero;
+        unsigned cnt = 0;
+        for (unsigned i = t; i < L; i += 64) {
+          if (pre && ++cnt % fold == 0) acc = fn_reduce(acc);
+          acc = add(acc, terms[i % plen]);
+          if (!pre && ++cnt % fold == 0) acc = fn_reduce(acc);
+        }
+        lanes[t] = fn_reduce(acc);
+      }
+      print_plain(neg(fn_reduce(wave_sum_host(lanes))));
+    } else if (c == "column") {
+      unsigned fold, E, negate, plen;
+      Fn mult;
+      std::vector<Fn> terms;
+      if (fscanf(f, "%x %x %x", &fold, &E, &negate) != 3 || !fold || negate > 1 || !read_fn(f, &mult) || fscanf(f, "%x", &plen) != 1 || !plen ||
+          !read_terms(f, plen, &terms))
+        return 3;
+      Fn acc = column(terms, E, fold);
+      if (negate) acc = neg(acc);
+      print_plain(mul(acc, mult));
+    } else if (c == "hexpr") {
+      unsigned fold, E, plen;
+      Fn x, yi, b, sr;
+      std::vector<Fn> tl, to;
+      if (fscanf(f, "%x %x", &fold, &E) != 2 || !fold || !read_fn(f, &x) || !read_fn(f, &yi) || !read_fn(f, &b) || !read_fn(f, &sr) ||
+          fscanf(f, "%x", &plen) != 1 || !plen || !read_terms(f, plen, &tl) || !read_terms(f, plen, &to))
+        return 3;
+      const Fn wL = column(tl, E, fold), wO = column(to, E, fold);
+      print_plain(sub(mul(yi, sub(add(mul(x, wL), wO), mul(b, sr))), fe_one<FN>()));
+      printf(" ");
+      print_plain(mul(mul(wO, yi), wL));
+    } else if (c == "tail") {
+      unsigned fold, nparts, waves, plen;
+      std::vector<Fn> terms;
+      if (fscanf(f, "%x %x %x %x", &fold, &nparts, &waves, &plen) != 4 || !fold || !waves || !plen || !read_terms(f, plen, &terms)) return 3;
+      std::vector<Fn> parts(nparts);
+      for (unsigned i = 0; i < nparts; i++) {
+        Fn t = fn_reduce(terms[(size_t)i * waves % plen]);
+        for (unsigned w = 1; w < waves; w++) t = add(t, fn_reduce(terms[((size_t)i * waves + w) % plen]));
+        parts[i] = t;
+      }
+      print_plain(neg(tail_sum(parts, fold)));
+    } else if (c == "mix") {
+      unsigned fold, nseg, plen;
+      if (fscanf(f, "%x %x", &fold, &nseg) != 2 || !fold || !nseg || nseg > 16) return 3;
+      std::vector<unsigned> len(nseg);
+      for (auto &l : len)
+        if (fscanf(f, "%x", &l) != 1) return 3;
+      std::vector<Fn> terms;
+      if (fscanf(f, "%x", &plen) != 1 || !plen || !read_terms(f, plen, &terms)) return 3;
+      std::vector<Fn> lanes(TPB, zero);
+      for (unsigned t = 0; t < TPB; t++) {
+        Fn acc = zero;
+        unsigned cnt = 0;
+        size_t base = 0;
+        for (unsigned s = 0; s < nseg; s++) {
+          for (unsigned p = t; p < len[s]; p += TPB) {
+            acc = add(acc, terms[(base + p) % plen]);
+            if (++cnt % fold == 0) acc = fn_reduce(acc);
+          }
+          base += len[s];
+        }
+        lanes[t] = acc;
+      }
+      print_plain(block_tail(lanes));
+    } else if (c == "split") {
+      unsigned pre, fold, tfold, grid, L, plen;
+      std::vector<Fn> terms;
+      if (fscanf(f, "%x %x %x %x %x %x", &pre, &fold, &tfold, &grid, &L, &plen) != 6 || pre > 1 || !fold || !tfold || !grid || grid > 256 || !plen ||
+          !read_terms(f, plen, &terms))
+        return 3;
+      std::vector<Fn> parts(grid);
+      for (unsigned blk = 0; blk < grid; blk++) {
+        Fn lanes[128];
+        for (unsigned t = 0; t < 128; t++) {
+          Fn acc = zero;
+          unsigned cnt = 0;
+          for (size_t i = (size_t)blk * 128 + t; i < L; i += (size_t)grid * 128) {
+            if (pre && ++cnt % fold == 0) acc = fn_reduce(acc);
+            acc = add(acc, terms[i % plen]);
+            if (!pre && ++cnt % fold == 0) acc = fn_reduce(acc);
+          }
+          lanes[t] = fn_reduce(acc);
+        }
+        parts[blk] = add(fn_reduce(wave_sum_host(lanes)), fn_reduce(wave_sum_host(lanes + 64)));
+      }
+      print_plain(neg(tail_sum(parts, tfold)));
     } else if (c == "sumraw" || c == "sumred") {
       unsigned count;
       Fn a, b;

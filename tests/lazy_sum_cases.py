@@ -40,24 +40,46 @@ def worst_pair(rnd):
 
 
 # ---- the kernels' own fold masks, read from the sources so that the budget assertions follow the code
-SITES = {   # site -> (file, kernel, products added per trip at most)
+SITES = {   # site -> (file, function, products added per trip at most[, the accumulator where the function folds two sums])
     "inner_product": ("k_scalar.hip", "k_inner_product_partial", 1),
     "sc_dot_batched": ("k_scalar.hip", "k_sc_dot_batched", 1),
     "prover_tcoeffs": ("k_scalar.hip", "k_prover_tcoeffs", 2),
     # a trip adds <l, r0> and one Beaver term (t2, t3: 1 + 4 products on the modifier plane) or two Beaver terms (t4: 8)
     "mpc_tcoeffs": ("k_mpc.hip", "k_mpc_tcoeffs", 8),
     "mpc_ipp_combine": ("k_mpc.hip", "k_mpc_ipp_combine", 4),
+    # ---- the verifier (tests/verifier_sum_cases.py)
+    "flatten_column": ("fn_dev.cuh", "flatten_column", 1),                       # a device function: one lane, serial over a column
+    "vs_delta": ("k_scalar.hip", "k_verify_scalars", 1, "dpart"),
+    "vs_one": ("k_scalar.hip", "k_verify_scalars", 1, "wcp"),
+    "vsf_one": ("k_scalar.hip", "k_verify_scalars_fast", 1, "wcp"),
+    "vsl_gh": ("k_scalar.hip", "k_vsl_gh", 1, "dpart"),
+    "vsl_wc": ("k_scalar.hip", "k_vsl_wc", 1, "wcp"),
+    # a trip adds one block's partial: the unreduced sum of its waves' reduced sums (VSL_TPB / 64 = 2 reduced values)
+    "vsl_tail_delta": ("k_scalar.hip", "k_vsl_tail", 2, "delta"),
+    "vsl_tail_wc": ("k_scalar.hip", "k_vsl_tail", 2, "wc"),
+    "sc_weighted_colsum": ("k_scalar.hip", "k_sc_weighted_colsum", 1),
+    "comb_colsum": ("k_pip2.hip", "comb_colsum_body", 1),
+    "mix_colsum": ("k_mixed.hip", "mix_colsum_body", 1),
 }
+_HEAD = r"(?:__global__ void __launch_bounds__\(\w+\)|__device__ __forceinline__ (?:Fn|void)) "
+# `if ((++cnt & 15) == 0) acc = fn_reduce(acc)` and k_vsl_tail's `if ((i & 7) == 7) acc = fn_reduce(acc)`
+_FOLD = r"\(\+\+\w+ & (\d+)\) == 0\) (\w+) = fn_reduce\(\2\)|\(\w+ & (\d+)\) == \3\) (\w+) = fn_reduce\(\4\)"
+
+
+def site_body(site):
+    """the text of a site's function, from its head to the closing brace in column 0"""
+    fname, func = SITES[site][:2]
+    src = open(os.path.join(CSRC, fname)).read()
+    body = src[re.search(_HEAD + func + r"\(", src).start():]
+    return body[:body.index("\n}\n")]
 
 
 def fold_trips(site):
     """the number of loop trips between two fn_reduce of a site's accumulator: mask + 1 of its `(++cnt & mask) == 0`"""
-    fname, kernel, _ = SITES[site]
-    src = open(os.path.join(CSRC, fname)).read()
-    body = src[re.search(r"__global__ void __launch_bounds__\(\w+\) " + kernel + r"\(", src).start():]
-    body = body[:body.index("\n}\n")]
-    masks = re.findall(r"\(\+\+\w+ & (\d+)\) == 0\) \w+ = fn_reduce\(", body)
-    assert len(masks) == 1, (site, masks)
+    acc = SITES[site][3] if len(SITES[site]) > 3 else None
+    found = [(m.group(1) or m.group(3), m.group(2) or m.group(4)) for m in re.finditer(_FOLD, site_body(site))]
+    masks = [mask for mask, name in found if acc is None or name == acc]
+    assert len(masks) == 1, (site, found)
     trips = int(masks[0]) + 1
     assert trips & (trips - 1) == 0, (site, trips)
     return trips

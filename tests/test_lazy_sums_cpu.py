@@ -1,7 +1,9 @@
 """The lazy F_n sums of the scalar kernels (the rule of csrc/fn_dev.cuh) on a CPU build with -fsanitize=undefined, as a stand-alone
 program (tests/csrc/lazysum_host_test.cpp) compared with Python integers: what the heaviest product weighs, every site's accumulate
 shape -- K unreduced terms, fn_reduce, the 64-lane butterfly, the 4-wave add, the last reduction -- on the heaviest and on mixed-sign
-terms, the two-level inner_product, and the two headrooms of the rule, found by bisection and held against each kernel's own fold."""
+terms, the two-level inner_product, the verifier's sites (one-wave sums, flatten_column's serial column negated and multiplied, the
+h expression on two lazy columns, k_vsl_tail's partials, the weighted column sums over one and several segments, the grid-split
+in-loop fold), and the two headrooms of the rule, found by bisection and held against each kernel's own fold."""
 import os
 import random
 import re
@@ -180,6 +182,136 @@ def test_two_level_inner_product(exe, tmp_path):
         assert g == w, tag
 
 
+# ------------------------------------------------------------------------------------------------ the verifier's sites
+def flat_patterns(rnd):
+    """name -> a list of single terms: the heaviest; the heaviest on even elements; mixed signs (every other term against a lazily
+    negative factor); lazily negative throughout; random"""
+    return {name: [el[0] for el in pat] for name, pat in patterns(rnd, 1).items()}
+
+
+def repeat_sum(vals, count):
+    reps, rest = divmod(count, len(vals))
+    return reps * sum(vals) + sum(vals[:rest])
+
+
+def terms_text(pat):
+    return "%x " % len(pat) + " ".join("%x %x %x" % t for t in pat)
+
+
+def check_lines(exe, tmp_path, lines, want, what):
+    got = run(exe, tmp_path, lines)
+    for g, w, tag in zip(got, want, what):
+        assert [int(x, 16) for x in g.split()] == ([v % N for v in w] if isinstance(w, list) else [w % N]), tag
+
+
+@pytest.mark.parametrize("site", ["vs_one", "vsf_one", "vs_delta"])
+def test_one_wave_sums_of_the_verifier(exe, tmp_path, site):
+    """64 lanes x fold products, then the butterfly: the `One`-column loops and the delta loop (which folds at the head of a trip)"""
+    fold, stride = lz.fold_trips(site), 64
+    assert fold == 16
+    rnd = random.Random(site)
+    per = stride * fold
+    lines, want, what = [], [], []
+    for name, pat in flat_patterns(rnd).items():
+        vals = [term_value(*t) for t in pat]
+        for L in (0, 1, 63, 65, per - 1, per, per + 1, per + stride + 17, 2 * per, 2 * per + 17, 4 * per):
+            lines.append("wave %x %x %x " % (site == "vs_delta", fold, L) + terms_text(pat))
+            want.append(-repeat_sum(vals, L))
+            what.append((site, name, L))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
+def test_flatten_column_shape_negated_and_multiplied(exe, tmp_path):
+    """a serial run of products, folded every 16, its lazy result negated (a V column) or not, then multiplied"""
+    fold = lz.fold_trips("flatten_column")
+    assert fold == 16
+    rnd = random.Random(16)
+    lines, want, what = [], [], []
+    for name, pat in flat_patterns(rnd).items():
+        vals = [term_value(*t) for t in pat]
+        for E in (0, 1, fold - 1, fold, fold + 1, 2 * fold - 1, 2 * fold, 2 * fold + 1, 257):
+            for negate in (0, 1):
+                for mult in (N - 1, 1, rnd.randrange(N)):
+                    lines.append("column %x %x %x %x " % (fold, E, negate, mult) + terms_text(pat))
+                    want.append((-1 if negate else 1) * repeat_sum(vals, E) * mult)
+                    what.append(("column", name, E, negate))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
+def test_h_expression_on_two_lazy_columns(exe, tmp_path):
+    """h_i = y^-i (x wL + wO - b s) - 1 and delta's (wO y^-i) wL with both columns lazily as heavy as they get (15 unreduced products,
+    and 16 + 15 across a fold), against heavy and random x, y^-i, b, s"""
+    fold = lz.fold_trips("flatten_column")
+    rnd = random.Random(17)
+    lines, want, what = [], [], []
+    pats = flat_patterns(rnd)
+    for name, pat in pats.items():
+        other = pats["worst" if name != "worst" else "mixed_sign"]
+        pl, po = pat[:3], other[:3]
+        vl, vo = [term_value(*t) for t in pl], [term_value(*t) for t in po]
+        for E in (1, fold - 1, fold, 2 * fold - 1, 2 * fold + 1):
+            for x, yi, b, sr in ((N - 1, N - 1, N - 1, N - 1), (N - 1, 1, 1, N - 1), tuple(rnd.randrange(N) for _ in range(4))):
+                lines.append("hexpr %x %x %x %x %x %x " % (fold, E, x, yi, b, sr) + terms_text(pl) + " " + " ".join("%x %x %x" % t for t in po))
+                wL, wO = repeat_sum(vl, E), repeat_sum(vo, E)
+                want.append([yi * (x * wL + wO - b * sr) - 1, wO * yi * wL])
+                what.append(("hexpr", name, E))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
+def test_tail_of_the_grid_split_route(exe, tmp_path):
+    """k_vsl_tail: up to 256 partials, each the unreduced sum of two reduced wave sums, folded every 8"""
+    fold = lz.fold_trips("vsl_tail_delta")
+    assert fold == lz.fold_trips("vsl_tail_wc") == 8 and lz.products_per_trip("vsl_tail_wc") == 2
+    rnd = random.Random(8)
+    lines, want, what = [], [], []
+    for name, pat in flat_patterns(rnd).items():
+        vals = [term_value(*t) for t in pat]
+        for nparts in (0, 1, 7, 8, 9, 16, 17, 32, 255, 256):
+            lines.append("tail %x %x 2 " % (fold, nparts) + terms_text(pat))
+            want.append(-repeat_sum(vals, 2 * nparts))
+            what.append(("tail", name, nparts))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
+@pytest.mark.parametrize("site", ["sc_weighted_colsum", "comb_colsum", "mix_colsum"])
+def test_weighted_column_sum_shapes(exe, tmp_path, site):
+    """256 lanes x 16 trips, then four waves; mix_colsum_body's counter runs on across its segments"""
+    fold = lz.fold_trips(site)
+    assert fold == 16
+    per = lz.TPB * fold
+    rnd = random.Random(site)
+    segs = [[L] for L in (0, 1, per - 1, per, per + 1, 2 * per + 17)]
+    if site == "mix_colsum":
+        segs += [[per // 2 + 1, per // 2 + 2], [per // 2 + 1, 0, per // 2 + 2], [per - 1, 1, 1], [3, per, 5, per + 17], [per] * 3]
+    lines, want, what = [], [], []
+    for name, pat in flat_patterns(rnd).items():
+        vals = [term_value(*t) for t in pat]
+        for lens in segs:
+            lines.append("mix %x %x " % (fold, len(lens)) + " ".join("%x" % v for v in lens) + " " + terms_text(pat))
+            want.append(repeat_sum(vals, sum(lens)))
+            what.append((site, name, lens))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
+@pytest.mark.parametrize("site", ["vsl_gh", "vsl_wc"])
+def test_grid_split_in_loop_fold(exe, tmp_path, site):
+    """128 lanes x 16 trips per block: the in-loop fold of k_vsl_gh / k_vsl_wc, which needs 256 x 128 x 16 = 2^19 elements per proof on
+    the device and is covered here alone; on grids of 1, 3 and 17 blocks, then through k_vsl_tail's sum"""
+    fold, tfold = lz.fold_trips(site), lz.fold_trips("vsl_tail_wc")
+    assert fold == 16
+    rnd = random.Random(site)
+    lines, want, what = [], [], []
+    for name, pat in flat_patterns(rnd).items():
+        vals = [term_value(*t) for t in pat]
+        for grid in (1, 3, 17):
+            per = grid * 128 * fold
+            for L in (per - 1, per, per + 1, 2 * per + 17):
+                lines.append("split %x %x %x %x %x " % (site == "vsl_gh", fold, tfold, grid, L) + terms_text(pat))
+                want.append(-repeat_sum(vals, L))
+                what.append((site, name, grid, L))
+    check_lines(exe, tmp_path, lines, want, what)
+
+
 # ------------------------------------------------------------------------------------------------ the headrooms
 def largest_ok(exe, tmp_path, cmd, cap=1 << 20):
     """the largest count up to which `cmd count x y` on a heaviest pair ends cleanly with the right sum; the first failure is looked
@@ -214,6 +346,10 @@ def test_every_kernel_stays_inside_the_measured_headroom(headroom):
         assert lz.unreduced_terms(site) <= raw_limit, (site, lz.unreduced_terms(site), raw_limit)
     assert lz.FINISH_PER_LANE <= raw_limit                       # k_inner_product_finish: reduced partials added, then fn_reduce
     assert lz.REDUCED_PER_BLOCK <= red_limit and 64 <= red_limit
+    # the verifier: k_vsl_tail holds a reduced restart and a fold of partials of two reduced wave sums each; the h expression adds a
+    # lazy column (at most 15 products before flatten_column's fold, or a reduced value and 15) to two products
+    assert lz.unreduced_terms("vsl_tail_delta") == lz.unreduced_terms("vsl_tail_wc") == 17 <= red_limit
+    assert lz.fold_trips("flatten_column") + 2 <= raw_limit
     # the limits themselves: the top limb of n is 2^19, so the 4096th heaviest term carries the int32 top limb to 2^31
     assert raw_limit == red_limit == (1 << 12) - 1
 
