@@ -25,6 +25,9 @@ __device__ __forceinline__ void fixed_small_body(const AffDev *table, size_t n, 
   uint32_t cur[16];
   int dcur = 0;
   size_t l = lane;
+  // fetch() only ISSUES the row's loads: the row is read for the first time by the addition that consumes it, one pair later, so the
+  // loads are in flight behind the addition in between.  A zero digit loads entry 0 of the same page and the row is ignored (no
+  // branch around the loads: the compiler would drain the load counter behind it).
   auto fetch = [&](size_t ll, uint32_t *dst, int &dg) {
     dg = 0;
     if (ll < total) {
@@ -35,31 +38,34 @@ __device__ __forceinline__ void fixed_small_body(const AffDev *table, size_t n, 
       for (int t = 0; t < 8; t++) s[t] = sc[g * 8 + t];
       recode_add_k<C>(r, s);
       dg = recode_digit<C>(r, w);
-      if (dg != 0) {
-        size_t row = (g < 2 + n ? g : g + hshift) * W + w;
-        const AffDev *e = table + row * HALF + ((dg < 0 ? -dg : dg) - 1);
-        uint32_t any = 0;
+      const int mag = dg < 0 ? -dg : dg;
+      size_t row = (g < 2 + n ? g : g + hshift) * W + w;
+      const AffDev *e = table + row * HALF + (mag ? mag - 1 : 0);
 #pragma unroll
-        for (int t = 0; t < 16; t++) { dst[t] = e->w[t]; any |= dst[t]; }
-        if (any == 0) dg = 0;   // rows of an identity generator (the ABI accepts one) are the identity: nothing to add
-      }
+      for (int t = 0; t < 16; t++) dst[t] = e->w[t];
     }
   };
   // (Measured and NOT kept here: rows two pairs ahead + scalar words three, as k_fixed.hip's block kernels do.  A lone batch's
   // Horner launch went from 0.49 to 0.41 ms, but the kernel grew from 100 to 208 VGPRs -- two waves per SIMD instead of four --
   // and with twenty batches in flight, where other waves cover a lane's wait anyway, the step rate fell by 7 %.)
-  fetch(l, cur, dcur);
-  while (l < total) {
+  // (the first pass only fetches and the last only adds: one place in the loop issues loads and one waits for them)
+  for (;;) {
     uint32_t nxt[16];
     int dnxt;
-    fetch(l + LPM, nxt, dnxt);
+    fetch(l, nxt, dnxt);
     if (dcur != 0) {
-      Aff q;
-      q.x = unpack<FP>(cur);
-      q.y = unpack<FP>(cur + 8);
-      if (dcur < 0) q.y = neg(q.y);
-      acc = xyzz_madd_nzq(acc, q);   // identity rows were dropped in fetch()
+      uint32_t any = 0;
+#pragma unroll
+      for (int t = 0; t < 16; t++) any |= cur[t];
+      if (any != 0) {   // rows of an identity generator (the ABI accepts one) are the identity: nothing to add, whatever the digit
+        Aff q;
+        q.x = unpack<FP>(cur);
+        q.y = unpack<FP>(cur + 8);
+        if (dcur < 0) q.y = neg(q.y);
+        acc = xyzz_madd_nzq(acc, q);
+      }
     }
+    if (l >= total) break;
 #pragma unroll
     for (int t = 0; t < 16; t++) cur[t] = nxt[t];
     dcur = dnxt;
@@ -103,47 +109,64 @@ __device__ __forceinline__ void fixed_chunk_body(const AffDev *table, size_t n, 
   const size_t g0 = (size_t)q * gens_per_chunk;
   const size_t g1 = g0 + gens_per_chunk < ngens ? g0 + gens_per_chunk : ngens;
   Xyzz acc = xyzz_inf();
-  uint32_t r[9];
-  // rows AHEAD pairs ahead of the addition: position `gc, wc` is the next pair to fetch (wave-uniform; only the digit differs between
-  // lanes), r the recoded scalar of its generator
+  uint32_t r[9], snx[8];
+  // Rows AHEAD pairs ahead of the addition: position `gc, wc` is the next pair to fetch (wave-uniform; only the digit differs between
+  // lanes), r the recoded scalar of its generator, snx the scalar words of the generator after it (loaded while this one is walked, so
+  // that the recoding at wc == 0 finds them in registers; the last generator of the run is loaded again instead of one past g1).
+  // step() only ISSUES the row's loads and nothing reads the row before the addition that consumes it, AHEAD additions later: the
+  // identity-generator test is made there.  A lane whose digit is zero loads entry 0 of the same page and ignores it, so the loads need
+  // no per-lane branch (the compiler drains the load counter behind one); a pair whose digit is zero in EVERY lane -- the windows of a
+  // bit vector, k_fixed_msm_m -- loads nothing (a wave-uniform branch).  Past the run's last pair (gc == g1) step() fetches nothing.
   uint32_t row[AHEAD + 1][16];
   int dg[AHEAD + 1];
   size_t gc = g0;
   int wc = 0;
+  if (g0 < g1) {
+#pragma unroll
+    for (int t = 0; t < 8; t++) snx[t] = sc[g0 * 8 + t];
+  }
   auto step = [&](uint32_t *dst, int &d) {
     d = 0;
     if (gc < g1) {
       if (wc == 0) {
-        uint32_t s[8];
+        recode_add_k<C>(r, snx);
+        const size_t gn = gc + 1 < g1 ? gc + 1 : gc;
 #pragma unroll
-        for (int t = 0; t < 8; t++) s[t] = sc[gc * 8 + t];
-        recode_add_k<C>(r, s);
+        for (int t = 0; t < 8; t++) snx[t] = sc[gn * 8 + t];
       }
       d = recode_digit<C>(r, wc);
-      if (d != 0) {
+      if (__ballot(d != 0) != 0) {
+        const int mag = d < 0 ? -d : d;
         const size_t rw = (gc < 2 + n ? gc : gc + hshift) * W + wc;
-        const AffDev *e = table + rw * HALF + ((d < 0 ? -d : d) - 1);
-        uint32_t any = 0;
+        const AffDev *e = table + rw * HALF + (mag ? mag - 1 : 0);
 #pragma unroll
-        for (int t = 0; t < 16; t++) { dst[t] = e->w[t]; any |= dst[t]; }
-        if (any == 0) d = 0;   // rows of an identity generator are the identity
+        for (int t = 0; t < 16; t++) dst[t] = e->w[t];
       }
       if (++wc == W) { wc = 0; gc++; }
     }
   };
+  // The first AHEAD passes of the loop only fetch (their dg[0] is 0) and the last AHEAD only add: the loop then has ONE place that
+  // issues row loads and one that waits for them.  (With the first rows loaded in front of the loop the compiler, which counts the
+  // outstanding loads per code path, makes every addition wait for the loads issued just before it.)
 #pragma unroll
-  for (int a = 0; a < AHEAD; a++) step(row[a], dg[a]);
+  for (int a = 0; a < AHEAD; a++) dg[a] = 0;
   const size_t npairs = (g1 > g0 ? g1 - g0 : 0) * W;
 #pragma unroll 1
-  for (size_t it = 0; it < npairs; it++) {
+  for (size_t it = 0; it < npairs + AHEAD; it++) {
     step(row[AHEAD], dg[AHEAD]);
     if (dg[0] != 0) {
-      Aff a;
-      a.x = unpack<FP>(row[0]);
-      a.y = unpack<FP>(row[0] + 8);
-      if (dg[0] < 0) a.y = neg(a.y);
-      acc = xyzz_madd_nzq(acc, a);
+      uint32_t any = 0;
+#pragma unroll
+      for (int t = 0; t < 16; t++) any |= row[0][t];
+      if (any != 0) {   // rows of an identity generator are the identity: nothing to add, whatever the digit
+        Aff a;
+        a.x = unpack<FP>(row[0]);
+        a.y = unpack<FP>(row[0] + 8);
+        if (dg[0] < 0) a.y = neg(a.y);
+        acc = xyzz_madd_nzq(acc, a);
+      }
     }
+    // (the wait for the rows fetched by this iteration's step() falls here, behind the addition)
 #pragma unroll
     for (int a = 0; a < AHEAD; a++) {
 #pragma unroll

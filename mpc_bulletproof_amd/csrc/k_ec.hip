@@ -424,18 +424,37 @@ __global__ void __launch_bounds__(64) k_verify_windows(const AffRaw *tab, const 
     }
     const unsigned long long live = __ballot(alive);
     __syncthreads();           // (the block is one wave)
+    // The row of the NEXT live point of the chunk is requested before the addition of this one and read for the first time after it
+    // (the copy nxt -> cur at the end of the loop body), so its loads are in flight behind ~1 650 instructions.  A lane whose digit is
+    // zero requests entry 0 of the point's table and ignores it: no branch around the loads.  The pipeline restarts with every chunk:
+    // its first pass only fetches (dcur = 0), so that the loop has ONE place that issues loads and one that waits for them -- with
+    // the first row loaded in front of the loop the compiler, which counts outstanding loads per code path, makes the addition wait.
+    unsigned long long rem = live;
+    int32_t cur[2 * NL], nxt[2 * NL];
+    int dcur = 0, dnxt = 0;
 #pragma unroll 1
-    for (int v = 0; v < cnt; v++) {
-      if (!((live >> v) & 1)) continue;
-      const int dg = (int)((rec[v * 9 + wk] >> wsft) & ((1u << SW) - 1)) - (1 << (SW - 1));
-      if (dg != 0) {
-        const AffRaw *e = tab + (p * nvar + base + v) * SE + ((dg < 0 ? -dg : dg) - 1);
+    for (;;) {
+      const bool more = rem != 0;
+      if (more) {               // the lowest point of `rem`
+        const int v = __builtin_ctzll(rem);
+        rem &= rem - 1;
+        dnxt = (int)((rec[v * 9 + wk] >> wsft) & ((1u << SW) - 1)) - (1 << (SW - 1));
+        const int mag = dnxt < 0 ? -dnxt : dnxt;
+        const AffRaw *e = tab + (p * nvar + base + v) * SE + (mag ? mag - 1 : 0);
+#pragma unroll
+        for (int t = 0; t < 2 * NL; t++) nxt[t] = e->v[t];
+      }
+      if (dcur != 0) {
         Aff q;
 #pragma unroll
-        for (int t = 0; t < NL; t++) { q.x.v[t] = e->v[t]; q.y.v[t] = e->v[NL + t]; }
-        if (dg < 0) q.y = neg(q.y);
+        for (int t = 0; t < NL; t++) { q.x.v[t] = cur[t]; q.y.v[t] = cur[NL + t]; }
+        if (dcur < 0) q.y = neg(q.y);
         acc = xyzz_madd_nzq(acc, q);
       }
+      if (!more) break;
+#pragma unroll
+      for (int t = 0; t < 2 * NL; t++) cur[t] = nxt[t];
+      dcur = dnxt;
     }
     __syncthreads();           // the next chunk overwrites rec
   }
@@ -711,11 +730,17 @@ void verify_wp_groups(hipStream_t st, const VerifyWp &v) {
   else hipLaunchKernelGGL(k_verify_horner_groups, dim3((v.nb * (64 / HG) + 63) / 64), dim3(64), 0, st, L.winsum, v.nb);
 }
 static size_t wp_chunk_gens(const VerifyWp &v);
+#ifndef WP_BACK_AHEAD
+#define WP_BACK_AHEAD 1   // rows fetched this many pairs ahead of their addition in k_verify_back_q (make EXTRA=-DWP_BACK_AHEAD=2 for an A/B)
+#endif
 template <int C>
 static void launch_back(hipStream_t st, const HornerArgs &h, unsigned hb, const FixedSmallArgs &f, bool latency_mode, int lpm_opt) {
   if (f.chunks) {
-    // (rows two and three pairs ahead of the addition instead of one: the same rate, profiles/r04_burst20_sweep2.log)
-    hipLaunchKernelGGL((k_verify_back_q<C, 1>), dim3(hb + (unsigned)((f.nb + 63) / 64) * f.chunks), dim3(64), 0, st, h, hb, f);
+    // Rows ONE pair ahead: the ~1 650 instructions of an addition outlast a loaded-chip HBM round trip.  Two pairs ahead is slower,
+    // 2.994 against 3.019 M/s over 2 048 steps (profiles/table_walk_prefetch.log): the body rotates its row buffers by copies, so the
+    // wait for the newest row falls at the same place and the second buffer only costs registers and copies.  (The earlier finding
+    // that depths 1, 2 and 3 run at the same rate, profiles/r04_burst20_sweep2.log, was of a body that waited for every row at once.)
+    hipLaunchKernelGGL((k_verify_back_q<C, WP_BACK_AHEAD>), dim3(hb + (unsigned)((f.nb + 63) / 64) * f.chunks), dim3(64), 0, st, h, hb, f);
     return;
   }
   // lanes per fixed-base MSM: 16 = fewest instructions (4 butterfly levels), 32 = half the serial additions per lane
