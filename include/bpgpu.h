@@ -854,6 +854,91 @@ int bpgpu_r1cs_verify_mixed_wire_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, c
 int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
                                               void *partial_xy_dev);
 
+/* ---- pools: queues of INDEPENDENT proofs over several GPUs from ONE process ----------------------------------------------------------
+ * NOT a reference API.  A pool is a set of slots; a slot is one bpgpu_ctx on one device plus one persistent host thread that selects
+ * the device once and issues every HIP call of its slot.  A pool call cuts its queue into one contiguous share per slot, every
+ * non-empty slot runs the single-context entry point named below on its share, on its own thread, and the caller's thread blocks until
+ * every slot has finished.  The devices run their kernel chains independently: no collective is on the data path, and the only
+ * exchange is the 64-byte point per slot at the end of a combined check.  A Rust verifier or prover service is one process: this is
+ * what it calls instead of creating a context, tables and a circuit per device and a thread per context by hand.  ONE proof split over
+ * several GPUs is a different matter and stays with bpgpu_set_shard.
+ *   Slots and devices.  devices[s] is the device of slot s; a device may appear in several slots (the list {0, 0} runs two contexts
+ *     and two host threads on one GPU: that is how the pool is exercised on a one-GPU machine).  Generators and circuits are built
+ *     once per DISTINCT device, on the workers of those devices at the same time, and shared by the slots of that device; _get returns
+ *     the handle of the slot's device, so that every single-context entry point can still be used on the borrowed context of a slot.
+ *     Creation is all or nothing: what was made before a failure is released.  Parametric circuits (bpgpu_circuit_create_param) have no
+ *     pool form: a pool serves circuits without randomized constraints only.
+ *   bpgpu_pool_create: BPGPU_E_ARG for a null out, a null devices, nslots == 0 or nslots > BPGPU_POOL_MAX_SLOTS; BPGPU_E_DEVICE without
+ *     a HIP device or for an index outside [0, bpgpu_device_count).  bpgpu_pool_destroy joins the threads; the pool's generators and
+ *     circuits are destroyed BEFORE it.
+ *   bpgpu_pool_ctx lends the context of a slot (NULL for a bad slot) for bpgpu_set_option, profiling, bpgpu_last_error or any other
+ *     call; such calls serialise with the pool's through the context's own mutex.  bpgpu_pool_device: the slot's device, BPGPU_E_ARG for
+ *     a bad slot.
+ *   bpgpu_pool_set_option applies bpgpu_set_option to every slot, all or nothing: a value that one slot refuses leaves every slot as
+ *     it was.
+ *   bpgpu_pool_last_error: the text of the pool's last failure -- the slot, its device and that context's own text (valid until the
+ *     next call on the pool).
+ *   A pool serialises its calls with one mutex: for concurrency make one pool per calling thread.
+ * The split.  bpgpu_pool_shares (a diagnostic that needs no device, like bpgpu_pippenger_plan; the pool calls take their split from
+ *   it and from nothing else, so the split never depends on timing or data) cuts nb items into nslots contiguous shares
+ *   [lo[s], lo[s + 1]): the ceil(nb / granule) granules are dealt as evenly as possible, the earlier slots taking the extra ones, so
+ *   every share but the last non-empty one is a whole multiple of granule; lo[0] = 0, lo[nslots] = nb, lo is monotone, a slot may be
+ *   empty.  BPGPU_E_ARG for nslots == 0, granule == 0 or a null lo (nslots + 1 entries).  The granule is slot 0's
+ *   BPGPU_OPT_STREAM_BATCH for _verify_stream, its BPGPU_OPT_SCREEN_BATCH for _verify_screened and _verify_combined, and 1 for _prove_fs.
+ * The calls.  Operands, results and layouts are those of the single-context host forms, for the whole queue (all arrays are
+ *   proof-major: a share is an offset into each); what is written for a share is exactly what the single-context call writes for it.
+ *   bpgpu_pool_r1cs_verify_stream    bpgpu_r1cs_verify_stream per share; slot_proofs (optional, nslots entries): the size of each share
+ *   bpgpu_pool_r1cs_verify_screened  bpgpu_r1cs_verify_screened per share; fallback_batches (optional): the sum over the slots
+ *   bpgpu_pool_r1cs_verify_combined  bpgpu_r1cs_verify_combined per share, then the partial points of the non-empty slots are added by
+ *                                    bpgpu_points_sum on slot 0: the point that ONE bpgpu_r1cs_verify_combined over the whole queue
+ *                                    returns (64 zero bytes: every proof valid).  Between processes this reduction is the all-gather of
+ *                                    the partials; inside one process it is a 64-byte hand-over per slot.
+ *   bpgpu_pool_r1cs_prove_fs         bpgpu_r1cs_prove_fs per share (operands and results as there, host form)
+ *   Shape and argument errors are found before any worker is woken, with the codes of the single-context call (BPGPU_E_ARG also for
+ *   handles of another pool); nb == 0 returns BPGPU_OK and touches nothing, out_xy and fallback_batches included.  When a slot fails at
+ *   run time the other slots still finish -- nothing is cancelled and nothing is left running when the call returns -- and the call
+ *   returns the error of the LOWEST failing slot.  A malformed proof is no error of a verification call: ok[p] = 0, as on one context.
+ * Page-locked operands (UNMEASURED rule).  bpgpu_r1cs_verify_stream reads page-locked host memory in place from a kernel.  Whether a
+ *   bpgpu_host_alloc buffer is mapped on EVERY device of a node has not been tried, and a device reading memory that is not mapped for
+ *   it is a GPU fault; so a slot of bpgpu_pool_r1cs_verify_stream takes the in-place route only when the runtime reports the slot's own
+ *   device as the owner of its share of each operand and the first and the last byte of each share lie in one allocation.  Every other
+ *   slot takes the staged copies, which are correct for any host memory.  bpgpu_r1cs_verify_stream itself and bpgpu_host_alloc are
+ *   unchanged. */
+#define BPGPU_POOL_MAX_SLOTS 32
+typedef struct bpgpu_pool bpgpu_pool;
+typedef struct bpgpu_pool_gens bpgpu_pool_gens;
+typedef struct bpgpu_pool_circuit bpgpu_pool_circuit;
+int bpgpu_pool_create(const int *devices, size_t nslots, bpgpu_pool **out);
+void bpgpu_pool_destroy(bpgpu_pool *pool);
+size_t bpgpu_pool_slots(const bpgpu_pool *pool);
+int bpgpu_pool_device(const bpgpu_pool *pool, size_t slot);
+bpgpu_ctx *bpgpu_pool_ctx(bpgpu_pool *pool, size_t slot);
+int bpgpu_pool_set_option(bpgpu_pool *pool, int option, int64_t value);
+const char *bpgpu_pool_last_error(bpgpu_pool *pool);
+int bpgpu_pool_gens_create(bpgpu_pool *pool, const uint8_t *G, const uint8_t *H, size_t gens_capacity, const uint8_t B[64],
+                           const uint8_t B_blinding[64], int window_bits, bpgpu_pool_gens **out);
+void bpgpu_pool_gens_destroy(bpgpu_pool *pool, bpgpu_pool_gens *g);
+const bpgpu_gens *bpgpu_pool_gens_get(const bpgpu_pool_gens *g, size_t slot);
+int bpgpu_pool_circuit_create(bpgpu_pool *pool, size_t q, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
+                              const uint8_t *coeff, size_t n_multipliers, size_t m_commitments, bpgpu_pool_circuit **out);
+int bpgpu_pool_circuit_create_ark(bpgpu_pool *pool, size_t q, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
+                                  const uint8_t *coeff_ark, size_t n_multipliers, size_t m_commitments, bpgpu_pool_circuit **out);
+void bpgpu_pool_circuit_destroy(bpgpu_pool *pool, bpgpu_pool_circuit *c);
+const bpgpu_circuit *bpgpu_pool_circuit_get(const bpgpu_pool_circuit *c, size_t slot);
+int bpgpu_pool_shares(size_t nb, size_t nslots, size_t granule, size_t *lo);
+int bpgpu_pool_r1cs_verify_stream(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t nb, size_t n1, size_t k,
+                                  const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, int32_t *ok, size_t *slot_proofs);
+int bpgpu_pool_r1cs_verify_screened(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t nb, size_t n1, size_t k,
+                                    const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *rho, int32_t *ok,
+                                    size_t *fallback_batches);
+int bpgpu_pool_r1cs_verify_combined(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t nb, size_t n1, size_t k,
+                                    const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *rho,
+                                    uint8_t out_xy[64]);
+int bpgpu_pool_r1cs_prove_fs(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t nb, const uint8_t *states_in,
+                             const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
+                             const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points,
+                             uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,4 +6,4 @@ There is no CPU implementation here: importing it raises if the HIP library has 
 BPGPU_E_DEVICE when no GPU is present.
 """
 from . import lib  # noqa: F401
-from .lib import BpGpu, BpGpuError  # noqa: F401
+from .lib import BpGpu, BpGpuError, BpPool  # noqa: F401

@@ -14,6 +14,7 @@
 
 #include "../../include/bpgpu.h"
 #include "kernels.h"
+#include "bpgpu_internal.h"
 #include "fe29.cuh"
 
 using namespace bpk;
@@ -2012,6 +2013,12 @@ int bpgpu_r1cs_verify_stream_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
 }
 int bpgpu_r1cs_verify_stream(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t k,
                              const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, int32_t *ok) {
+  return bpgpu_internal_verify_stream(ctx, g, c, nb, n1, k, points, scalars, challenges, ok, 1);
+}
+// in_place_ok = 0: page-locked operands take the staged copies as well (bpgpu_internal.h: the pool decides per slot)
+__attribute__((visibility("hidden"))) int bpgpu_internal_verify_stream(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb,
+                                                                       size_t n1, size_t k, const uint8_t *points, const uint8_t *scalars,
+                                                                       const uint8_t *challenges, int32_t *ok, int in_place_ok) {
   if (!ctx || !g || !c || (nb && (!points || !scalars || !challenges || !ok))) return BPGPU_E_ARG;
   if (c->nchi) return BPGPU_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2024,7 +2031,7 @@ int bpgpu_r1cs_verify_stream(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_ci
   // (four DMA commands and as many cross-engine dependencies per 1024 proofs) held the host-memory stream at 2-3 M/s against 4.1
   // resident; reading the operands in place from the chain's own kernels put bus latency on its latency-bound links (3.4 M/s).
   // Pageable operands take the staged copies on each lane's stream.
-  const void *dpts = host_device_alias(points), *dsc = host_device_alias(scalars), *dch = host_device_alias(challenges);
+  const void *dpts = in_place_ok ? host_device_alias(points) : nullptr, *dsc = host_device_alias(scalars), *dch = host_device_alias(challenges);
   const void *dok = host_device_alias(ctx->pinned);
   if (dpts && dsc && dch && dok)
     CK(verify_stream_locked(ctx, g, c, nb, n1, k, (const uint8_t *)dpts, (const uint8_t *)dsc, (const uint8_t *)dch, (uint8_t *)dok,

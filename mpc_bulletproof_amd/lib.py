@@ -121,9 +121,17 @@ class BpGpu:
         if rc:
             raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
 
+    @classmethod
+    def borrowed(cls, ctx):
+        """a BpGpu over a context that someone else owns (BpPool.ctx): close() leaves the context alone"""
+        self = cls.__new__(cls)
+        self.ctx, self._borrowed = C.c_void_p(ctx), True
+        return self
+
     def close(self):
         if self.ctx:
-            _lib.bpgpu_destroy(self.ctx)
+            if not getattr(self, "_borrowed", False):
+                _lib.bpgpu_destroy(self.ctx)
             self.ctx = C.c_void_p()
 
     def __del__(self):
@@ -941,3 +949,133 @@ class BpGpu:
     def r1cs_verify_batch_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok, d_mega=None,
                               d_full=None):
         self._ck(_lib.bpgpu_r1cs_verify_batch_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_ok, d_mega, d_full))
+
+
+POOL_MAX_SLOTS = 32         # BPGPU_POOL_MAX_SLOTS
+
+
+def pool_shares(nb, nslots, granule):
+    """the split every pool call uses (bpgpu_pool_shares; needs no device): nslots + 1 bounds, share s = [lo[s], lo[s + 1])"""
+    lo = (C.c_size_t * (nslots + 1))()
+    rc = _lib.bpgpu_pool_shares(nb, nslots, granule, lo)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return list(lo)
+
+
+class BpPool:
+    """Queues of independent proofs over several devices from one process (include/bpgpu.h, bpgpu_pool_*): one slot -- a context
+    and a host thread -- per entry of `devices`; a device may appear several times.  Byte encodings and layouts as in BpGpu."""
+
+    def __init__(self, devices=(0,)):
+        self.pool = C.c_void_p()
+        devs = (C.c_int * max(len(devices), 1))(*devices)
+        rc = _lib.bpgpu_pool_create(devs, len(devices), C.byref(self.pool))
+        if rc:
+            raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+
+    def close(self):
+        """(the pool's generators and circuits are destroyed before it)"""
+        if self.pool:
+            _lib.bpgpu_pool_destroy(self.pool)
+            self.pool = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc:
+            raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode() + " | " + _lib.bpgpu_pool_last_error(self.pool).decode())
+
+    def slots(self):
+        return _lib.bpgpu_pool_slots(self.pool)
+
+    def device(self, slot):
+        return _lib.bpgpu_pool_device(self.pool, slot)
+
+    def ctx(self, slot):
+        """the context of a slot as a BpGpu that does not own it (options, profiling, any single-context call)"""
+        p = _lib.bpgpu_pool_ctx(self.pool, slot)
+        if not p:
+            raise BpGpuError(E_ARG, "bpgpu_pool_ctx: no such slot")
+        return BpGpu.borrowed(p)
+
+    def set_option(self, name, value):
+        """bpgpu_set_option on every slot, all or nothing"""
+        self._ck(_lib.bpgpu_pool_set_option(self.pool, OPT[name], int(value)))
+
+    shares = staticmethod(pool_shares)
+
+    # ---- handles: one per distinct device, shared by that device's slots
+    def gens_create(self, G, H, B, B_blinding, window_bits=8):
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_pool_gens_create(self.pool, _buf(G), _buf(H), len(G) // 64, _buf(B), _buf(B_blinding), window_bits, C.byref(h)))
+        return h
+
+    def gens_destroy(self, h):
+        _lib.bpgpu_pool_gens_destroy(self.pool, h)
+
+    def gens_get(self, h, slot):
+        """the bpgpu_gens of the slot's device (for single-context calls on ctx(slot)), as an address"""
+        return _lib.bpgpu_pool_gens_get(h, slot)
+
+    def circuit_create(self, row_ptr, kind, idx, coeff, n_mul, m, ark=False):
+        q, nnz = len(row_ptr) - 1, len(kind)
+        h = C.c_void_p()
+        rp = (C.c_uint32 * (q + 1))(*row_ptr)
+        kd = (C.c_uint32 * max(nnz, 1))(*kind)
+        ix = (C.c_uint32 * max(nnz, 1))(*idx)
+        fn = _lib.bpgpu_pool_circuit_create_ark if ark else _lib.bpgpu_pool_circuit_create
+        self._ck(fn(self.pool, q, rp, kd, ix, _buf(coeff), n_mul, m, C.byref(h)))
+        return h
+
+    def circuit_destroy(self, h):
+        _lib.bpgpu_pool_circuit_destroy(self.pool, h)
+
+    def circuit_get(self, h, slot):
+        return _lib.bpgpu_pool_circuit_get(h, slot)
+
+    # ---- the four calls: operands for the whole queue as bytes, or c_void_p of page-locked memory
+    @staticmethod
+    def _wrap(b):
+        return b if isinstance(b, C.c_void_p) else _buf(b)
+
+    def r1cs_verify_stream(self, gens, circuit, nb, n1, k, points, scalars, challenges, want_shares=False, raw=False):
+        """bpgpu_r1cs_verify_stream on every slot's share -> [ok] (raw: the nb x int32 verdicts as bytes); want_shares: (ok, proofs per slot)"""
+        ok = (C.c_int32 * max(nb, 1))()
+        per = (C.c_size_t * max(self.slots(), 1))()
+        self._ck(_lib.bpgpu_pool_r1cs_verify_stream(self.pool, gens, circuit, nb, n1, k, self._wrap(points), self._wrap(scalars),
+                                                    self._wrap(challenges), ok, per))
+        out = bytes(ok)[:4 * nb] if raw else ok[:nb]
+        return (out, list(per)) if want_shares else out
+
+    def r1cs_verify_screened(self, gens, circuit, nb, n1, k, points, scalars, challenges, rho):
+        """-> ([ok], fallback batches summed over the slots)"""
+        ok = (C.c_int32 * max(nb, 1))()
+        nf = C.c_size_t(0)
+        self._ck(_lib.bpgpu_pool_r1cs_verify_screened(self.pool, gens, circuit, nb, n1, k, self._wrap(points), self._wrap(scalars),
+                                                      self._wrap(challenges), self._wrap(rho), ok, C.byref(nf)))
+        return list(ok)[:nb], nf.value
+
+    def r1cs_verify_combined(self, gens, circuit, nb, n1, k, points, scalars, challenges, rho):
+        """sum over the whole queue of rho_p * mega_check_p: the slots' partial points added on slot 0 (64 bytes; all zero: every proof valid)"""
+        o = _out(64)
+        self._ck(_lib.bpgpu_pool_r1cs_verify_combined(self.pool, gens, circuit, nb, n1, k, self._wrap(points), self._wrap(scalars),
+                                                      self._wrap(challenges), self._wrap(rho), o))
+        return bytes(o)
+
+    def r1cs_prove_fs(self, gens, circuit, nb, n, m, states, a_L, a_R, a_O, blindings, v_blinding=None, s_L=None, s_R=None,
+                      vector_keys=None, want_wire=True):
+        """BpGpu.r1cs_prove_fs with the provers dealt over the slots: the same operands, the same five results"""
+        k = max(n - 1, 0).bit_length()
+        nvar, plen = 11 + 2 * k, 1 + 11 * 32 + (2 * k + 2) * 32
+        pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
+        wire = _out(nb * plen) if want_wire else None
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_pool_r1cs_prove_fs(self.pool, gens, circuit, nb, opt(states), opt(a_L), opt(a_R), opt(a_O), opt(s_L), opt(s_R),
+                                               opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so))
+        return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
+                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
