@@ -7,6 +7,7 @@
 #include "../../mpc_bulletproof_amd/csrc/ec29.cuh"
 #include "../../mpc_bulletproof_amd/csrc/ec29_quad.cuh"
 #include "../../mpc_bulletproof_amd/csrc/ec29_row.cuh"
+#include "../../mpc_bulletproof_amd/csrc/fe29_sqrt.cuh"
 using namespace bp;
 
 template <class F> __device__ bool d_load(Fe<F> &out, const uint32_t *w) {
@@ -42,6 +43,32 @@ template <class F> __global__ void k_field(int op, const uint32_t *a, const uint
   }
   d_store(out + 8 * i, r);
   rc[i] = 0;
+}
+// ---- square roots (fe29_sqrt.cuh): the tables as k_sqrt_tables (k_codec.hip) builds them, one block per digit position and one lane
+// per digit value, then fp_sqrt one element per lane; rc = its return (1: out is a root, 0: non-residue), -1 for a non-canonical input
+__global__ void __launch_bounds__(256) k_sqrt_tab(int32_t *T, uint8_t *hash) {
+  const int d = threadIdx.x, j = blockIdx.x;
+  Fp e = sqrt_table_entry(j, d);
+  for (int t = 0; t < NL; t++) T[((size_t)j * 256 + d) * NL + t] = e.v[t];
+  if (j == SQ_DIG - 1) hash[sqrt_hash(e)] = (uint8_t)((256 - d) & 255);
+}
+__global__ void __launch_bounds__(64) k_sqrt(const uint32_t *a, uint32_t *out, int *rc, size_t n, const int32_t *T, const uint8_t *hash) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fp x, r;
+  if (!d_load(x, a + 8 * i)) { rc[i] = -1; return; }
+  const bool ok = fp_sqrt(r, x, T, hash);
+  d_store(out + 8 * i, r);
+  rc[i] = ok ? 1 : 0;
+}
+// compress_xy_words on raw boundary words, unvalidated: the sign comparison at values of y that no curve point has
+__global__ void __launch_bounds__(64) k_compress_words(const uint32_t *xy, uint32_t *out, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x[8], y[8];
+  for (int j = 0; j < 8; j++) { x[j] = xy[16 * i + j]; y[j] = xy[16 * i + 8 + j]; }
+  compress_xy_words(x, y);
+  for (int j = 0; j < 8; j++) out[8 * i + j] = x[j];
 }
 // products of RAW limb vectors (9 x int32 each, any representation the multiplication promises to accept):
 // out = canonical bytes of the integer  value(a) * value(b) / 2^261  mod m
@@ -266,6 +293,24 @@ int g29_field(int field, int op, const uint8_t *a, const uint8_t *b, size_t n, u
   else hipLaunchKernelGGL(k_field<FN>, g, t, 0, 0, op, (const uint32_t *)da.p, (const uint32_t *)db.p, (uint32_t *)dout.p, (int *)drc.p, n);
   if (hipDeviceSynchronize() != hipSuccess) return -100;
   return down(out, dout, 32 * n) && down(rc, drc, 4 * n) ? 0 : -100;
+}
+int g29_sqrt(const uint8_t *a, size_t n, uint8_t *out, int *rc) {
+  const size_t tab = (size_t)SQ_DIG * 256 * NL * 4;
+  DevBuf da(32 * n), dout(32 * n), drc(4 * n), dtab(tab + 65536);
+  if (!up(da, a, 32 * n) || !dout.p || !drc.p || !dtab.p) return -100;
+  if (hipMemset((uint8_t *)dtab.p + tab, 0, 65536) != hipSuccess) return -100;
+  hipLaunchKernelGGL(k_sqrt_tab, dim3(SQ_DIG), dim3(256), 0, 0, (int32_t *)dtab.p, (uint8_t *)dtab.p + tab);
+  if (n) hipLaunchKernelGGL(k_sqrt, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const uint32_t *)da.p, (uint32_t *)dout.p, (int *)drc.p, n,
+                            (const int32_t *)dtab.p, (const uint8_t *)dtab.p + tab);
+  if (hipDeviceSynchronize() != hipSuccess) return -100;
+  return down(out, dout, 32 * n) && down(rc, drc, 4 * n) ? 0 : -100;
+}
+int g29_compress_words(const uint8_t *xy, size_t n, uint8_t *out) {
+  DevBuf dxy(64 * n), dout(32 * n);
+  if (!up(dxy, xy, 64 * n) || !dout.p) return -100;
+  hipLaunchKernelGGL(k_compress_words, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const uint32_t *)dxy.p, (uint32_t *)dout.p, n);
+  if (hipDeviceSynchronize() != hipSuccess) return -100;
+  return down(out, dout, 32 * n) ? 0 : -100;
 }
 int g29_rawmul(int field, int sq, const int32_t *a, const int32_t *b, size_t n, uint8_t *out) {
   DevBuf da(36 * n), db(36 * n), dout(32 * n);

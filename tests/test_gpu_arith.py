@@ -2,7 +2,8 @@
 identity operands, out-of-line exact branches) run on the GPU one element per lane (tests/csrc/fe29_gpu_test.hip,
 built by __graft_entry__.build()) and compared with Python big integers / the Python model -- the GPU twin of
 test_device_arith_cpu.py, plus products of adversarial RAW limb vectors (the representation bounds the
-multiplication promises to accept)."""
+multiplication promises to accept) and the point codec's square root and sign flag (csrc/fe29_sqrt.cuh) on the
+crafted arguments of tests/codec_cases.py."""
 import ctypes as C
 import os
 import random
@@ -59,6 +60,58 @@ def test_field_ops_on_device(g, field, m):
     bad = (C.c_uint8 * 32).from_buffer_copy(le(m))
     one = (C.c_uint8 * 32).from_buffer_copy(le(1))
     assert g.g29_field(field, 2, bad, one, C.c_size_t(1), out, rc) == 0 and rc[0] == -1
+
+
+def test_fp_sqrt_on_device(g):
+    """fp_sqrt (csrc/fe29_sqrt.cuh) over tables built on the device as k_sqrt_tables builds them: the residue verdict of the model's
+    Tonelli-Shanks and a root r = +-model with r^2 = a, for a = 0 (decompression never asks: the curve has no point of order two),
+    small values, every argument tests/codec_cases.py crafts (chosen digits of the discrete logarithm, the sign and x boundaries),
+    the whole 2-power tower c^(2^k) (k digits' worth of zeros below a single bit) and random values."""
+    import codec_cases as cc
+    rnd = random.Random(433)
+    c = pow(3, (P - 1) >> 192, P)
+    vals = [0, 1, 4, P - 1, 3] + [a for _, _, a in cc.build().sqrt_args] + [pow(c, 1 << k, P) for k in range(192)] + \
+           [rnd.randrange(P) for _ in range(2000)]
+    n = len(vals)
+    a = (C.c_uint8 * (32 * n)).from_buffer_copy(b"".join(le(x) for x in vals))
+    out, rc = (C.c_uint8 * (32 * n))(), (C.c_int * n)()
+    assert g.g29_sqrt(a, C.c_size_t(n), out, rc) == 0, "no HIP device"
+    ob = bytes(out)
+    n_sq = n_non = 0
+    for i, x in enumerate(vals):
+        want = pm.fp_sqrt(x)
+        if want is None:
+            assert rc[i] == 0, (i, hex(x))
+            n_non += 1
+        else:
+            r = int.from_bytes(ob[32 * i:32 * i + 32], "little")
+            assert rc[i] == 1 and r in (want, (P - want) % P) and r * r % P == x, (i, hex(x), hex(r))
+            n_sq += 1
+    assert n_sq > 1000 and n_non > 900
+    assert rc[0] == 1 and ob[:32] == bytes(32)                  # sqrt(0) = 0
+    assert rc[5 + len(cc.build().sqrt_args)] == 0               # c itself generates the 2-Sylow subgroup: a non-residue
+    bad = (C.c_uint8 * 32).from_buffer_copy(le(P))
+    assert g.g29_sqrt(bad, C.c_size_t(1), out, rc) == 0 and rc[0] == -1
+
+
+def test_sign_flag_at_its_boundary_on_device(g):
+    """compress_xy_words (csrc/fe29_sqrt.cuh) on raw words: the flag is "y > (p - 1) / 2", strictly -- at (p - 1) / 2 itself, which
+    no curve point has and the validated entry points therefore never show, and one word at a time around it"""
+    half = (P - 1) // 2
+    ys = [0, 1, half - 1, half, half + 1, half + 2, P - 2, P - 1]
+    for j in range(8):
+        ys += [half - (1 << (32 * j)), half + (1 << (32 * j))]
+    ys = [y for y in ys if 0 <= y < P]
+    cases = [(5 + i, y) for i, y in enumerate(ys)] + [(0, 0), (0, half), (0, half + 1)]
+    n = len(cases)
+    xy = (C.c_uint8 * (64 * n)).from_buffer_copy(b"".join(le(x) + le(y) for x, y in cases))
+    out = (C.c_uint8 * (32 * n))()
+    assert g.g29_compress_words(xy, C.c_size_t(n), out) == 0, "no HIP device"
+    ob = bytes(out)
+    for i, (x, y) in enumerate(cases):
+        want = pm.point_compress(pm.INF if (x, y) == (0, 0) else (x, y))
+        assert want[31] >> 6 == (1 if (x, y) == (0, 0) else 2 if y > half else 0)
+        assert ob[32 * i:32 * i + 32] == want, (hex(x), hex(y))
 
 
 def _limbs_value(v):

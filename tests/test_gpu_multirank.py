@@ -11,6 +11,7 @@ import pytest
 
 import bp_helpers as bh
 import oracle_lib as o
+from ark_helpers import _ark_point, _ark_point_affine, _ark_scalar
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -143,31 +144,6 @@ def gpu_ctx():
 
 
 # ------------------------------------------------------------------ arkworks in-memory forms (zero-copy hand-over)
-def _ark_scalar(x):
-    return (x * (1 << 256) % o.N).to_bytes(32, "little")
-
-
-def _ark_point(xy, z):
-    """affine boundary bytes -> ark Projective bytes (Jacobian, Montgomery R = 2^256) with the given Z"""
-    P = o.P
-    R = 1 << 256
-    if xy == bytes(64):
-        return (R % P).to_bytes(32, "little") * 2 + bytes(32)          # Projective::zero() = (1 : 1 : 0)
-    x, y = int.from_bytes(xy[:32], "little"), int.from_bytes(xy[32:], "little")
-    X, Y = x * z * z % P, y * z * z * z % P
-    return b"".join((c * R % P).to_bytes(32, "little") for c in (X, Y, z))
-
-
-def _ark_point_affine(b):
-    P = o.P
-    Ri = pow(1 << 256, -1, P)
-    X, Y, Z = (int.from_bytes(b[32 * i:32 * i + 32], "little") * Ri % P for i in range(3))
-    if Z == 0:
-        return bytes(64)
-    zi = pow(Z, -1, P)
-    return (X * zi * zi % P).to_bytes(32, "little") + (Y * zi * zi * zi % P).to_bytes(32, "little")
-
-
 @pytest.mark.parametrize("n", [0, 1, 40, 600, 3000])
 def test_msm_and_conversions_in_arkworks_memory_form(gpu_ctx, n):
     """bpgpu_msm_ark takes Scalars as ark-ff Montgomery limbs (x 2^256 mod n) and StarkPoints as ark-ec Jacobian coordinates in
