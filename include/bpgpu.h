@@ -77,7 +77,8 @@ int bpgpu_set_latency_mode(bpgpu_ctx *ctx, int on);
 #define BPGPU_OPT_GROUPS_FORM 18           /* first Horner stage: 0 = by mode, 1 = a lane, 2 = a DPP quad, 3 = a whole wave per group of 8 windows */
 #define BPGPU_OPT_FIXED_CHUNK_GENS 19      /* generator half of the verification's back launch: 0 = by mode, -1 = FIXED_LPM lanes per proof and a butterfly; g in 1..64 = a proof
                                             * per lane, g generators per wave, the partial sums added in the verdict launch */
-#define BPGPU_OPT_COUNT 20
+#define BPGPU_OPT_WITNESS_ROUTE 20         /* witness synthesis (bpgpu_r1cs_witness_synthesize, bpgpu_r1cs_prove_fs2): 0 = by bpgpu_witness_plan, 1 = a lane per prover, 2 = a block per prover */
+#define BPGPU_OPT_COUNT 21
 int bpgpu_set_option(bpgpu_ctx *ctx, int option, int64_t value);
 int bpgpu_get_option(bpgpu_ctx *ctx, int option, int64_t *value);
 /* synchronise and report whether an operand of the `_dev` (device-resident, asynchronous) calls issued since the last read -- or
@@ -393,8 +394,10 @@ int bpgpu_r1cs_prover_session_polys_param(bpgpu_ctx *ctx, bpgpu_prover *session,
  * blindings, w, the IPP session and its k rounds run back to back on the context's stream; the Fiat-Shamir hash chain is advanced on
  * the device between them.  It replaces the five staged calls (bpgpu_r1cs_prover_commit, _session_polys, bpgpu_msm_gens,
  * bpgpu_r1cs_prover_ipp_begin, bpgpu_ipp_run_fs) and the host hashing, waits and copies between them.  A parametric circuit
- * (bpgpu_circuit_create_param) is refused with BPGPU_E_ARG: the phase-2 witness of a two-phase prover depends on a challenge the host
- * has to evaluate its gadget on, so that round trip is inherent; such provers keep the staged calls.
+ * (bpgpu_circuit_create_param) is refused with BPGPU_E_ARG: the phase-2 witness of a two-phase prover depends on the gadget's
+ * challenge.  A host round trip is inherent only to a gadget that no bpgpu_witness gate program describes: such provers take
+ * bpgpu_r1cs_prove_fs2_begin / _finish (two calls around a gadget that the host evaluates), every other two-phase prover
+ * bpgpu_r1cs_prove_fs2 (one call: the gates evaluated on the device).
  * With n = the circuit's multipliers, m its commitments, padded_n = next_pow2(n), k = lg padded_n:
  *   states_in      nb x 32        the chain state on entry to Prover::prove (prover.rs:412): after Prover::new and every commit(),
  *                                 i.e. the V's are already absorbed by the host
@@ -456,8 +459,9 @@ int bpgpu_r1cs_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, siz
                              const uint8_t *states_in, uint8_t *V, uint8_t *V_compressed, uint8_t *states_out);
 int bpgpu_r1cs_commit_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const void *v, const void *v_blinding,
                                  const void *states_in, void *V, void *V_compressed, void *states_out);
-/* Prover::prove for nb provers of ONE two-phase circuit (bpgpu_circuit_create_param with nchi == 1) in TWO calls around the gadget: the
- * phase-2 witness depends on a challenge the host evaluates its gadget on, and that is the only round trip left.  The Fiat-Shamir hash
+/* Prover::prove for nb provers of ONE two-phase circuit (bpgpu_circuit_create_param with nchi == 1) in TWO calls around the gadget, for a
+ * host that evaluates its gadget on the challenge itself (a gadget that a bpgpu_witness gate program describes needs no round trip:
+ * bpgpu_r1cs_prove_fs2 below issues both chains in one call).  The Fiat-Shamir hash
  * chain runs on the device in both calls; they replace bpgpu_r1cs_prover_commit (twice), _session_polys_param, bpgpu_msm_gens,
  * bpgpu_r1cs_prover_ipp_begin, bpgpu_ipp_run_fs and the host hashing between them.  With n = the circuit's multipliers, n1 those of
  * phase 1, n2 = n - n1 >= 1, m its commitments, padded_n = next_pow2(n), k = lg padded_n:
@@ -541,6 +545,101 @@ int bpgpu_r1cs_constraints_satisfied(bpgpu_ctx *ctx, const bpgpu_circuit *c, siz
 int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R,
                                          const void *a_O, const void *v, const void *gadget_challenges, void *ok, void *first_bad_row,
                                          void *first_bad_gate, void *residuals);
+/* ---- witness synthesis: Prover::multiply (r1cs/prover.rs:99-125) and allocate_multiplier (:148-165) on the device ----------------------
+ * A bpgpu_witness is a resident GATE PROGRAM: how the n multipliers of one prover are assigned, in order, the first n1 of them in
+ * phase 1.  Gate i has an op (op[i]), an argument (arg[i]) and two rows, 2i = `left` and 2i + 1 = `right`, in the CSR of
+ * bpgpu_circuit_create_param: kinds 0..4, (1 + nchi) * 2n stored rows, block j >= 1 holding the chi_j parts (a coefficient is
+ * c0 + sum_j chi_j c_j), coefficients canonical little-endian.
+ *   BPGPU_GATE_MUL    multiply(left, right): a_L[i] = eval(left), a_R[i] = eval(right), a_O[i] = a_L[i] a_R[i].  A term may read a
+ *                     committed value (kind 3), One (kind 4) or a_L / a_R / a_O (kinds 0..2) of a gate < i.
+ *   BPGPU_GATE_INPUT  allocate_multiplier(Some((l, r))), or a pair of allocate calls: (l, r) is the next pair of the caller's `inputs`
+ *                     (nb x n_inputs x 2, ark form), consumed in gate order; a_O = l r.  Both rows must be empty.
+ *   BPGPU_GATE_BIT    the range gadget's assignment (tests/r1cs.rs:629-632): b = bit arg[i] of the canonical integer eval(left);
+ *                     a_L = 1 - b, a_R = b, a_O = a_L a_R.  The right row must be empty.  arg[i] < 252: the reference's u64
+ *                     assignment, generalised to the whole field.
+ * bpgpu_witness_create validates on the host, before anything is uploaded; after it no kernel index can be out of range.
+ * BPGPU_E_ARG: a null pointer, an unknown op or kind, a multiplier term with idx >= i (a self or forward reference), a chi part in a
+ * gate < n1 (the challenge does not exist in phase 1), a committed index >= m, a BIT with arg >= 252, a non-empty row where the op
+ * requires an empty one, row pointers that decrease, a non-canonical coefficient, n1 > n, nchi > 8.  BPGPU_E_LEN: n or m above 2^25 - 1.
+ * It also computes the dependency levels, per phase: a gate's level is 0 if it is an INPUT or its rows read no multiplier of its
+ * own phase, else 1 + the largest level it reads; the gates of a phase are stored sorted by level.
+ * Two launch forms evaluate a phase, one launch each (csrc/k_witness.hip): a LANE per prover walks the gates in program order; a
+ * BLOCK per prover walks the levels, a level's gates strided over 256 threads and a row of more than 64 terms summed by a wave.
+ * The route is a function of the program's shape and nb alone, never of the data: bpgpu_witness_plan (no device needed) reports
+ * what the library takes: the block form where a level holds two gates or more on average, for up to 1024 provers (measured:
+ * profiles/witness_synth.log, DESIGN.md "Witness synthesis"); above that the width asked for grows with nb / 1024, which is an
+ * extrapolation and UNMEASURED.  BPGPU_OPT_WITNESS_ROUTE forces a form; results never depend on it. */
+typedef struct bpgpu_witness bpgpu_witness;
+#define BPGPU_GATE_MUL 0
+#define BPGPU_GATE_INPUT 1
+#define BPGPU_GATE_BIT 2
+int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
+                         const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff, bpgpu_witness **out);
+void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w);
+#define BPGPU_WIT_PLAN_LEVELS1 0      /* dependency levels of phase 1 (0: no gates) */
+#define BPGPU_WIT_PLAN_LEVELS2 1      /* ... of phase 2 */
+#define BPGPU_WIT_PLAN_WIDEST 2       /* gates of the widest level of either phase */
+#define BPGPU_WIT_PLAN_LONG_ROWS 3    /* rows of more than 64 terms (a wave's in the block form) */
+#define BPGPU_WIT_PLAN_INPUTS 4       /* INPUT gates: pairs of `inputs` per prover */
+#define BPGPU_WIT_PLAN_ROUTE1 5       /* launch form of phase 1: 1 = a lane per prover, 2 = a block per prover; 0: no gates */
+#define BPGPU_WIT_PLAN_ROUTE2 6       /* ... of phase 2 */
+#define BPGPU_WIT_PLAN_FIELDS 7
+int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                       const uint32_t *idx, size_t nb, int32_t out[BPGPU_WIT_PLAN_FIELDS]);
+/* The witnesses of nb provers of one gate program, where the provers read them.
+ *   v                  nb x m          the committed values, ark form: the buffer bpgpu_r1cs_commit_values and
+ *                                      bpgpu_r1cs_constraints_satisfied take; may be NULL when m == 0
+ *   inputs             nb x n_inputs x 2   ark form; may be NULL when the program has no INPUT gate (phase 2 of a program consumes the
+ *                                      pairs that follow those of phase 1)
+ *   gadget_challenges  nb x nchi x 32  canonical LE, for a program with nchi > 0 when phase 2 is evaluated (phase 0 or 2), else NULL
+ *   phase              0: all gates; 1: gates [0, n1); 2: gates [n1, n), the planes already holding phase 1
+ *   a_L, a_R, a_O      nb x n          ark form: the layouts bpgpu_r1cs_constraints_satisfied and bpgpu_r1cs_prove_fs take, so one set of
+ *                                      device buffers serves commit -> synthesize -> check -> prove without a host wait.  The host form
+ *                                      of phase 1 or 2 copies the planes in and out whole: the other phase's multipliers come back as
+ *                                      the caller held them.
+ * Refusals, before any launch: BPGPU_E_ARG for a null required pointer, for challenges given to a numeric program or where phase 1
+ * alone is evaluated, for challenges missing where a parametric program's phase 2 is, for a phase other than 0, 1, 2; nb == 0: BPGPU_OK,
+ * nothing touched.  A non-canonical limb gives BPGPU_E_ARG in the host form and raises bpgpu_input_flag in the `_dev` form (every
+ * operand a device pointer; asynchronous on the context's stream).  A failed call leaves no pool memory behind.  Profiling: kind 22.
+ * A gate chain is serial, and a dependent gate costs the device about 10 us (a store, a load and a few dozen dependent
+ * multiplications of one lane): ONE prover's k = 2^14 shuffle, two chains of 16 383 gates, takes 171 ms here (profiles/
+ * witness_synth.log) where even an interpreted host evaluates it in 61 ms, and one 2^10-shuffle prover is proved faster by
+ * bpgpu_r1cs_prove_fs2_begin / _finish around a host gadget than by bpgpu_r1cs_prove_fs2.  The calls pay off for batches: 256 provers
+ * of the 64-shuffle in 0.74 ms, of 16 x 64-bit range values in 0.07 ms.  A caller with few provers and long chains keeps its host's
+ * Prover::multiply.
+ * Out of scope: the host mirror (mpc_bulletproof.hpp: its multiply keeps evaluating on the host), the pool forms (bpgpu_pool_*),
+ * the two-party prover (a product of shares is a Beaver step, not a local product) and bench.py. */
+int bpgpu_r1cs_witness_synthesize(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const uint8_t *v, const uint8_t *inputs,
+                                  const uint8_t *gadget_challenges, uint8_t *a_L, uint8_t *a_R, uint8_t *a_O);
+int bpgpu_r1cs_witness_synthesize_dev(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const void *v, const void *inputs,
+                                      const void *gadget_challenges, void *a_L, void *a_R, void *a_O);
+/* Prover::prove for nb provers of ONE two-phase circuit in ONE call: the phase-1 gates of w, the chain of bpgpu_r1cs_prove_fs2_begin,
+ * the phase-2 gates on the gadget challenge that chain has just drawn (read from the session's device copy), the chain of
+ * bpgpu_r1cs_prove_fs2_finish -- all on the context's stream, no host wait, no session left behind.  The launches of the two chains
+ * are the ones _begin and _finish issue (the same code); outputs are byte-identical to that pair fed the host-evaluated witness.
+ *   states_in, gadget_label   as bpgpu_r1cs_prove_fs2_begin (the label is host memory in both forms)
+ *   v, inputs       as bpgpu_r1cs_witness_synthesize
+ *   s_L, s_R        nb x n, explicit blinding vectors (phase 1: [0, n1), phase 2: [n1, n) of each prover's row), or both NULL with
+ *   vector_keys     nb x 2 x 32: a phase-1 key, then a phase-2 key (exactly one of the two sources)
+ *   v_blinding      nb x m, ark form; may be NULL when m == 0
+ *   blindings       nb x 11, ark form: i1 o1 s1 | i2 o2 s2 tb1 tb3 tb4 tb5 tb6
+ *   proof_points, proof_scalars, wire, challenges_out, states_out   as bpgpu_r1cs_prove_fs2_finish
+ *   gadget_challenges_out   (optional) nb x 32 canonical LE
+ *   a_L_out, a_R_out, a_O_out   (optional, all three or none) nb x n, ark form: the synthesized witness, e.g. for
+ *                                      bpgpu_r1cs_constraints_satisfied afterwards
+ * Refusals, before anything is launched: those of _begin and _finish; BPGPU_E_ARG for a null program, for a program whose
+ * (n, n1, m, nchi) are not the circuit's, for nchi != 1, for a program with INPUT gates and no `inputs`.  A non-canonical ark limb gives
+ * BPGPU_E_ARG in the host form and raises bpgpu_input_flag in the `_dev` form.  A failed call leaves no session or pool memory behind. */
+int bpgpu_r1cs_prove_fs2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                         const uint8_t *states_in, const uint8_t gadget_label[32], const uint8_t *v, const uint8_t *inputs, const uint8_t *s_L,
+                         const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings,
+                         uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out,
+                         uint8_t *gadget_challenges_out, uint8_t *a_L_out, uint8_t *a_R_out, uint8_t *a_O_out);
+int bpgpu_r1cs_prove_fs2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                             const void *states_in, const uint8_t gadget_label[32], const void *v, const void *inputs, const void *s_L,
+                             const void *s_R, const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
+                             void *proof_scalars, void *wire, void *challenges_out, void *states_out, void *gadget_challenges_out,
+                             void *a_L_out, void *a_R_out, void *a_O_out);
 /* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
  * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
  * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step

@@ -438,6 +438,7 @@ static bool opt_valid(int option, int64_t value) {
     case BPGPU_OPT_FIXED_LPM: return value == 0 || value == 16 || value == 32 || value == 64;
     case BPGPU_OPT_GROUPS_FORM: return value >= 0 && value <= 3;
     case BPGPU_OPT_FIXED_CHUNK_GENS: return value >= -1 && value <= 64;
+    case BPGPU_OPT_WITNESS_ROUTE: return value >= 0 && value <= 2;
     default: return value == 0 || value == 1;
   }
 }
@@ -466,7 +467,8 @@ static int ctx_create(int device, bool single, bpgpu_ctx **out) {
         {BPGPU_OPT_SCREEN_BATCH, "BPGPU_SCREEN_BATCH", 2560},         {BPGPU_OPT_HORNER_FORM, "BPGPU_HORNER_FORM", 0},
         {BPGPU_OPT_HORNER_ROW_MAX, "BPGPU_HORNER_ROW_MAX", 1536},     {BPGPU_OPT_PIPPENGER_MIN, "BPGPU_PIPPENGER_MIN", 512},
         {BPGPU_OPT_IPP_PIPPENGER_MIN, "BPGPU_IPP_PIPPENGER_MIN", 257}, {BPGPU_OPT_FIXED_LPM, "BPGPU_FIXED_LPM", 0},
-        {BPGPU_OPT_GROUPS_FORM, "BPGPU_GROUPS_FORM", 0}, {BPGPU_OPT_FIXED_CHUNK_GENS, "BPGPU_FIXED_CHUNK_GENS", 0}};
+        {BPGPU_OPT_GROUPS_FORM, "BPGPU_GROUPS_FORM", 0}, {BPGPU_OPT_FIXED_CHUNK_GENS, "BPGPU_FIXED_CHUNK_GENS", 0},
+        {BPGPU_OPT_WITNESS_ROUTE, "BPGPU_WITNESS_ROUTE", 0}};
     // the environment only SEEDS a new context's options, through the same validation as bpgpu_set_option: a value that the
     // setter would refuse (a batch size of 0, a negative lane count, ...) leaves the default in force
     for (auto &s : seed) {
@@ -4309,4 +4311,47 @@ int bpgpu_mpc_ipp_round(bpgpu_ctx *ctx, bpgpu_ipp *s, const uint8_t *opened, uin
 
 #pragma GCC visibility pop
 }  // extern "C"
+
+/* ---- what bpgpu_witness.hip takes from this file (bpgpu_internal.h) ------------------------------------------------------------------ */
+int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view) {
+  ctx->mu.lock();
+  if (hipSetDevice(ctx->device) != hipSuccess) {
+    ctx->err = "hipSetDevice failed";
+    ctx->mu.unlock();
+    return BPGPU_E_DEVICE;
+  }
+  *view = {ctx->st, ctx->d_flag, ctx->opt[BPGPU_OPT_WITNESS_ROUTE], ctx->shard_world};
+  return BPGPU_OK;
+}
+void bpgpu_internal_leave(bpgpu_ctx *ctx) { ctx->mu.unlock(); }
+void *bpgpu_internal_pool_alloc(bpgpu_ctx *ctx, size_t bytes) {
+  void *p = nullptr;
+  return pool_alloc(ctx, &p, bytes) ? p : nullptr;
+}
+void bpgpu_internal_pool_release(bpgpu_ctx *ctx, void *p) { pool_release(ctx, p); }
+int bpgpu_internal_hip(bpgpu_ctx *ctx, hipError_t e, const char *what) {
+  if (e == hipSuccess) return BPGPU_OK;
+  ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+  return e == hipErrorOutOfMemory ? BPGPU_E_OOM : BPGPU_E_DEVICE;
+}
+void bpgpu_internal_prof_mark(bpgpu_ctx *ctx, int kind) { if (ctx->prof) ProfScope::mark(ctx, kind, ctx->st); }
+int bpgpu_internal_flag_reset(bpgpu_ctx *ctx) { return flag_reset(ctx); }
+int bpgpu_internal_checked_wait(bpgpu_ctx *ctx) { return checked_download(ctx, {}); }
+void bpgpu_internal_circuit_dims(const bpgpu_circuit *c, size_t *n, size_t *m, size_t *nchi) { *n = c->n; *m = c->m; *nchi = c->nchi; }
+int bpgpu_internal_prove_fs2_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1) {
+  if (c->nchi != 1) return BPGPU_E_ARG;
+  if (!nb) return BPGPU_OK;
+  if (n1 >= c->n) return BPGPU_E_LEN;
+  if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
+  return BPGPU_OK;
+}
+int bpgpu_internal_prove_fs2_chains(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                    const bpgpu_internal_fs2 &io, int (*between)(void *user, const void *chi_dev), void *user) {
+  ProverOwner own(nullptr, ProverFree{ctx});   // the session of the call: its buffers go back to the pool on the way out, whatever the outcome
+  CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, {io.states_in, io.gadget_label, io.a_L1, io.a_R1, io.a_O1, io.s_L1, io.s_R1, io.keys1, io.blindings1,
+                                                nullptr, io.gadget_challenges_out, nullptr}, own));
+  CK(between(user, fs2_arrays(own.get()).chi));
+  return prove_fs2_finish_locked(ctx, g, c, own, {nullptr, io.a_L2, io.a_R2, io.a_O2, io.s_L2, io.s_R2, io.keys2, io.v_blinding, io.blindings2,
+                                                  io.proof_points, io.proof_scalars, io.wire, io.challenges_out, io.states_out});
+}
 

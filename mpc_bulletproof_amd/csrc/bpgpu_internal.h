@@ -1,6 +1,7 @@
 // bpgpu_internal.h -- what the translation units of libbpgpu.so share beside the public header: not exported.
 #ifndef BPGPU_INTERNAL_H
 #define BPGPU_INTERNAL_H
+#include <hip/hip_runtime.h>
 #include "../../include/bpgpu.h"
 
 extern "C" {
@@ -11,4 +12,37 @@ __attribute__((visibility("hidden"))) int bpgpu_internal_verify_stream(bpgpu_ctx
                                                                        size_t n1, size_t k, const uint8_t *points, const uint8_t *scalars,
                                                                        const uint8_t *challenges, int32_t *ok, int in_place_ok);
 }
+
+// ---- what bpgpu_witness.hip takes from bpgpu_api.hip, where bpgpu_ctx, its pool and the provers' chains live -------------------------
+#define BPGPU_HIDDEN __attribute__((visibility("hidden")))
+struct bpgpu_internal_view { hipStream_t st; int *d_flag; int64_t witness_route; size_t shard_world; };
+// an entry point's head and tail: the context's mutex taken and its device selected (on failure the mutex is free again) | released
+BPGPU_HIDDEN int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view);
+BPGPU_HIDDEN void bpgpu_internal_leave(bpgpu_ctx *ctx);
+// between the two (mutex held): the context's buffer pool (nullptr: out of memory), the failure text of a HIP call -> BPGPU_E_*, a
+// profile mark of `kind` on the stream (start and stop marks alternate), the input flag cleared, and the end of an entry point that
+// waits: the launch check and the flag (BPGPU_E_ARG when raised), the stream drained
+BPGPU_HIDDEN void *bpgpu_internal_pool_alloc(bpgpu_ctx *ctx, size_t bytes);
+BPGPU_HIDDEN void bpgpu_internal_pool_release(bpgpu_ctx *ctx, void *p);
+BPGPU_HIDDEN int bpgpu_internal_hip(bpgpu_ctx *ctx, hipError_t e, const char *what);
+BPGPU_HIDDEN void bpgpu_internal_prof_mark(bpgpu_ctx *ctx, int kind);
+BPGPU_HIDDEN int bpgpu_internal_flag_reset(bpgpu_ctx *ctx);
+BPGPU_HIDDEN int bpgpu_internal_checked_wait(bpgpu_ctx *ctx);
+// a circuit handle's shape, and the refusals of bpgpu_r1cs_prove_fs2_begin / _finish that depend on the shapes alone (BPGPU_OK with
+// nb == 0: nothing to do)
+BPGPU_HIDDEN void bpgpu_internal_circuit_dims(const bpgpu_circuit *c, size_t *n, size_t *m, size_t *nchi);
+BPGPU_HIDDEN int bpgpu_internal_prove_fs2_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1);
+// The chains of bpgpu_r1cs_prove_fs2_begin and _finish on one session that lives for the call (mutex held, shapes and arguments checked,
+// nb > 0; every pointer but the label is HBM; asynchronous).  `between` runs once _begin's launches are enqueued, with the session's
+// device copy of the gadget challenges (nb x 32, plain): it enqueues whatever produces the phase-2 operands.
+struct bpgpu_internal_fs2 {
+  const void *states_in;
+  const uint8_t *gadget_label;                                                  // host memory
+  const void *a_L1, *a_R1, *a_O1, *s_L1, *s_R1, *keys1, *blindings1;            // nb x n1 | nb x 32 | nb x 3
+  const void *a_L2, *a_R2, *a_O2, *s_L2, *s_R2, *keys2, *blindings2;            // nb x (n - n1) | nb x 32 | nb x 8
+  const void *v_blinding;
+  void *proof_points, *proof_scalars, *wire, *challenges_out, *states_out, *gadget_challenges_out;
+};
+BPGPU_HIDDEN int bpgpu_internal_prove_fs2_chains(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
+                                                 const bpgpu_internal_fs2 &io, int (*between)(void *user, const void *chi_dev), void *user);
 #endif

@@ -1,0 +1,493 @@
+// bpgpu_witness.hip -- the witness-synthesis entry points of include/bpgpu.h: gate programs (bpgpu_witness_create / _plan), their
+// evaluation (bpgpu_r1cs_witness_synthesize) and the one-call two-phase prover (bpgpu_r1cs_prove_fs2) on top of k_witness.hip.  The
+// context, its pool and the provers' chains live in bpgpu_api.hip; what this file takes from there is in bpgpu_internal.h.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/bpgpu.h"
+#include "bpgpu_internal.h"
+#include "witness_dev.cuh"
+
+using namespace bpk;
+using namespace bp;
+
+static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT && BPGPU_GATE_BIT == WIT_OP_BIT, "gate ops of the header");
+
+// (the leading fields are what the refusals on arguments read)
+struct bpgpu_witness {
+  size_t n = 0, n1 = 0, m = 0, nchi = 0, ninp = 0;
+  uint32_t levels[2] = {0, 0};
+  void *mem = nullptr;          // one device allocation: everything dev points to
+  WitDev dev{};
+};
+
+namespace {
+
+// The route of a phase.  Both forms are bound by the latency of one dependent gate after the other (about 10 us each, measured): a
+// lane pays it once per GATE, a block once per LEVEL, so the block form wins as soon as a level holds two gates -- profiles/
+// witness_synth.log: 0.74 against 1.22 ms for 256 shuffles of 63 levels x 2 gates, 0.074 against 7.4 ms for 256 range programs of one
+// level x 1024, 171 against 352 ms for one chain pair of 16 383 levels x 2 (DESIGN.md "Witness synthesis").  Those runs have at most
+// 256 provers, where every block is resident at once.  Beyond WIT_BLOCKS_RESIDENT provers the blocks run in rounds, and the width
+// asked for grows with the rounds: an extrapolation, not a measurement.
+constexpr size_t WIT_BLOCK_MIN_WIDTH = 2, WIT_BLOCKS_RESIDENT = 1024;
+int wit_route(size_t gates, uint32_t levels, size_t nb) {
+  if (!gates) return 0;
+  const size_t rounds = (nb + WIT_BLOCKS_RESIDENT - 1) / WIT_BLOCKS_RESIDENT;
+  if (rounds > gates) return 1;      // (also keeps the product below in range)
+  return gates >= WIT_BLOCK_MIN_WIDTH * (rounds ? rounds : 1) * levels ? 2 : 1;
+}
+
+struct WitShape {
+  std::vector<uint32_t> level;    // per gate, within its phase
+  std::vector<uint32_t> row_len;  // per row 2 i, 2 i + 1: the terms of all 1 + nchi blocks
+  uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0;
+  size_t nnz = 0;
+};
+// what bpgpu_witness_plan and bpgpu_witness_create share: the checks that make the levels well defined, and the levels
+int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
+                WitShape *s) {
+  if (!row_ptr || (n && !op) || n1 > n || nchi > 8) return BPGPU_E_ARG;
+  if (n > ROWS_IDX_MASK) return BPGPU_E_LEN;
+  const size_t rows = 2 * n, stored = (1 + nchi) * rows;
+  for (size_t r = 0; r < stored; r++) if (row_ptr[r + 1] < row_ptr[r]) return BPGPU_E_ARG;
+  s->nnz = row_ptr[stored];
+  if (s->nnz >= 0xFFFFFF00u) return BPGPU_E_LEN;        // (a wave's lane-strided term index t + 64 must not wrap)
+  if (s->nnz && (!kind || !idx)) return BPGPU_E_ARG;
+  s->level.assign(n, 0);
+  s->row_len.assign(rows, 0);
+  std::vector<uint32_t> width;
+  for (size_t i = 0; i < n; i++) {
+    if (op[i] > BPGPU_GATE_BIT) return BPGPU_E_ARG;
+    if (op[i] == BPGPU_GATE_INPUT) s->ninp++;
+    const size_t phase_lo = i < n1 ? 0 : n1;
+    uint32_t lvl = 0;
+    for (size_t side = 0; side < 2; side++)
+      for (size_t j = 0; j <= nchi; j++) {
+        const size_t r = j * rows + 2 * i + side;
+        s->row_len[2 * i + side] += row_ptr[r + 1] - row_ptr[r];
+        for (uint32_t t = row_ptr[r]; t < row_ptr[r + 1]; t++) {
+          if (kind[t] > 4) return BPGPU_E_ARG;
+          if (kind[t] > 2) continue;
+          if (idx[t] >= i) return BPGPU_E_ARG;            // a self or forward reference
+          if (idx[t] >= phase_lo && op[i] != BPGPU_GATE_INPUT) lvl = std::max(lvl, s->level[idx[t]] + 1);
+        }
+      }
+    s->level[i] = lvl;
+    if (i == n1) width.clear();
+    if (width.size() <= lvl) width.resize(lvl + 1, 0);
+    s->widest = std::max(s->widest, ++width[lvl]);
+    s->levels[i < n1 ? 0 : 1] = (uint32_t)width.size();
+  }
+  const uint32_t lane_max = rows_lane_max();
+  for (uint32_t len : s->row_len) if (len > lane_max) s->nlong++;
+  return BPGPU_OK;
+}
+
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+#define WCK(x) do { int rc__ = (x); if (rc__ != BPGPU_OK) return rc__; } while (0)
+#define WHIP(ctx, call) WCK(bpgpu_internal_hip(ctx, (call), #call))
+
+// the context's mutex for the length of an entry point
+struct Entered {
+  bpgpu_ctx *ctx;
+  bool in = false;
+  bpgpu_internal_view view{};
+  explicit Entered(bpgpu_ctx *c) : ctx(c) {}
+  int enter() { const int rc = bpgpu_internal_enter(ctx, &view); in = rc == BPGPU_OK; return rc; }
+  ~Entered() { if (in) bpgpu_internal_leave(ctx); }
+};
+// pool buffers of a call, given back on the way out (stream-ordered reuse); declared AFTER the Entered of its call: released under the mutex
+struct Scratch {
+  bpgpu_ctx *ctx;
+  std::vector<void *> held;
+  explicit Scratch(bpgpu_ctx *c) : ctx(c) { held.reserve(8); }
+  void *take(size_t bytes) {
+    void *p = bpgpu_internal_pool_alloc(ctx, bytes);
+    if (p) held.push_back(p);
+    return p;
+  }
+  ~Scratch() { for (void *p : held) bpgpu_internal_pool_release(ctx, p); }
+};
+struct Prof22 {   // kind 22: the launches only the one-call chains have
+  bpgpu_ctx *ctx;
+  explicit Prof22(bpgpu_ctx *c) : ctx(c) { bpgpu_internal_prof_mark(ctx, 22); }
+  ~Prof22() { bpgpu_internal_prof_mark(ctx, 22); }
+};
+template <class Body> int no_throw(Body body) {
+  try { return body(); } catch (const std::bad_alloc &) { return BPGPU_E_OOM; }
+}
+
+// the grids of k_witness.hip are addressable
+bool wit_fits(const bpgpu_witness *w, size_t nb) {
+  const size_t widest = std::max(std::max(w->n, w->m), 2 * w->ninp);
+  return nb < ((size_t)1 << 31) && (!widest || nb <= ((size_t)1 << 38) / widest);
+}
+
+// The scratch of a run: plain canonical planes nb x n, the values, the input pairs, the challenges
+struct WitRun { Words8 *L, *R, *O, *v, *in, *chi; };
+int wit_begin(const Entered &e, const bpgpu_witness *w, size_t nb, const void *v, const void *inputs, Scratch &sc, WitRun *run) {
+  const size_t plane = nb * w->n;
+  Words8 *base = (Words8 *)sc.take((3 * plane + nb * w->m + 2 * nb * w->ninp + nb * w->nchi) * 32);
+  if (!base) return BPGPU_E_OOM;
+  *run = {base, base + plane, base + 2 * plane, base + 3 * plane, base + 3 * plane + nb * w->m, base + 3 * plane + nb * w->m + 2 * nb * w->ninp};
+  Prof22 prof(e.ctx);
+  witness_convert(e.view.st, false, nb, w->m, (const Words8 *)v, w->m, run->v, w->m, e.view.d_flag);
+  witness_convert(e.view.st, false, nb, 2 * w->ninp, (const Words8 *)inputs, 2 * w->ninp, run->in, 2 * w->ninp, e.view.d_flag);
+  return BPGPU_OK;
+}
+// one launch: the gates of phase ph (1 or 2) on the run's planes; chi: nb x nchi plain words, or nullptr for phase 1
+void wit_phase(const Entered &e, const bpgpu_witness *w, size_t nb, int ph, const WitRun &run, const Words8 *chi) {
+  const uint32_t n1 = (uint32_t)w->n1, n = (uint32_t)w->n;
+  const uint32_t g_lo = ph == 1 ? 0 : n1, g_hi = ph == 1 ? n1 : n, l_lo = ph == 1 ? 0 : w->levels[0], l_hi = l_lo + w->levels[ph - 1];
+  const int route = e.view.witness_route ? (int)e.view.witness_route : wit_route(g_hi - g_lo, w->levels[ph - 1], nb);
+  Prof22 prof(e.ctx);
+  witness_eval(e.view.st, w->dev, nb, route == 2, g_lo, g_hi, l_lo, l_hi, run.L, run.R, run.O, run.v, run.in, chi);
+}
+// the gates [lo, lo + count) of every prover, out of the run's planes into ark planes of `stride` scalars per prover
+void wit_export(const Entered &e, const bpgpu_witness *w, size_t nb, const WitRun &run, size_t lo, size_t count, void *aL, void *aR, void *aO,
+                size_t stride) {
+  Prof22 prof(e.ctx);
+  const Words8 *src[3] = {run.L, run.R, run.O};
+  void *dst[3] = {aL, aR, aO};
+  for (int k = 0; k < 3; k++) witness_convert(e.view.st, true, nb, count, src[k] + lo, w->n, (Words8 *)dst[k], stride, e.view.d_flag);
+}
+
+// ---- bpgpu_r1cs_witness_synthesize ----
+int synth_check(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const void *v, const void *inputs, const void *chi, const void *aL,
+                const void *aR, const void *aO) {
+  if (!ctx || !w || phase < 0 || phase > 2) return BPGPU_E_ARG;
+  const bool want_chi = w->nchi != 0 && phase != 1;
+  if (want_chi != (chi != nullptr)) return BPGPU_E_ARG;
+  if (!nb) return BPGPU_OK;
+  if ((w->n && (!aL || !aR || !aO)) || (w->m && !v) || (w->ninp && !inputs)) return BPGPU_E_ARG;
+  return wit_fits(w, nb) ? BPGPU_OK : BPGPU_E_LEN;
+}
+// mutex held, arguments checked, nb > 0; every pointer HBM; asynchronous
+int synth_locked(const Entered &e, const bpgpu_witness *w, size_t nb, int phase, const void *v, const void *inputs, const void *chi, void *aL,
+                 void *aR, void *aO) {
+  Scratch sc(e.ctx);
+  WitRun run;
+  WCK(wit_begin(e, w, nb, v, inputs, sc, &run));
+  if (chi) {
+    WHIP(e.ctx, hipMemcpyAsync(run.chi, chi, nb * w->nchi * 32, hipMemcpyDeviceToDevice, e.view.st));
+    scalars_check(e.view.st, run.chi, nb * w->nchi, e.view.d_flag);
+  }
+  if (phase == 2) {          // phase 1 as the caller holds it
+    Prof22 prof(e.ctx);
+    const void *src[3] = {aL, aR, aO};
+    Words8 *dst[3] = {run.L, run.R, run.O};
+    for (int k = 0; k < 3; k++) witness_convert(e.view.st, false, nb, w->n1, (const Words8 *)src[k], w->n, dst[k], w->n, e.view.d_flag);
+  }
+  if (phase != 2) wit_phase(e, w, nb, 1, run, nullptr);
+  if (phase != 1) wit_phase(e, w, nb, 2, run, chi ? run.chi : nullptr);
+  const size_t lo = phase == 2 ? w->n1 : 0, hi = phase == 1 ? w->n1 : w->n;
+  wit_export(e, w, nb, run, lo, hi - lo, (Words8 *)aL + lo, (Words8 *)aR + lo, (Words8 *)aO + lo, w->n);
+  return bpgpu_internal_hip(e.ctx, hipGetLastError(), "witness synthesis launch");
+}
+
+// ---- bpgpu_r1cs_prove_fs2 ----
+struct Fs2Io {
+  const void *states_in;
+  const uint8_t *gadget_label;
+  const void *v, *inputs, *s_L, *s_R, *vector_keys, *v_blinding, *blindings;
+  void *proof_points, *proof_scalars, *wire, *challenges_out, *states_out, *chi_out, *aL, *aR, *aO;
+};
+size_t lg_padded(size_t n) {
+  size_t k = 0;
+  while (((size_t)1 << k) < n) k++;
+  return k;
+}
+int fs2_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
+  if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
+  size_t n, m, nchi;
+  bpgpu_internal_circuit_dims(c, &n, &m, &nchi);
+  if (w->n != n || w->m != m || w->nchi != nchi) return BPGPU_E_ARG;     // not this circuit's program
+  WCK(bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1));
+  if (!nb) return BPGPU_OK;
+  if (!a.states_in || !a.gadget_label || !a.blindings || !a.proof_points || !a.proof_scalars || (m && (!a.v || !a.v_blinding)) ||
+      (w->ninp && !a.inputs))
+    return BPGPU_E_ARG;
+  if ((!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
+  if ((!a.aL) != (!a.aR) || (!a.aL) != (!a.aO)) return BPGPU_E_ARG;                                    // the three planes, or none
+  return wit_fits(w, nb) ? BPGPU_OK : BPGPU_E_LEN;
+}
+struct Fs2Between { const Entered *e; const bpgpu_witness *w; size_t nb; const WitRun *run; void *L2, *R2, *O2; };
+int fs2_between(void *user, const void *chi_dev) {
+  const Fs2Between &b = *(const Fs2Between *)user;
+  const size_t n2 = b.w->n - b.w->n1;
+  wit_phase(*b.e, b.w, b.nb, 2, *b.run, (const Words8 *)chi_dev);
+  wit_export(*b.e, b.w, b.nb, *b.run, b.w->n1, n2, b.L2, b.R2, b.O2, n2);
+  return BPGPU_OK;
+}
+// mutex held, arguments checked, nb > 0; every pointer but the label HBM; asynchronous
+int fs2_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const Fs2Io &io) {
+  if (e.view.shard_world > 1) return BPGPU_E_ARG;      // partial sums cannot be hashed
+  const size_t n = w->n, n1 = w->n1, n2 = n - n1;
+  hipStream_t st = e.view.st;
+  Scratch sc(e.ctx);
+  WitRun run;
+  WCK(wit_begin(e, w, nb, io.v, io.inputs, sc, &run));
+  // the operands as the two chains take them, a phase each: witness planes and blinding vectors nb x n1 | nb x n2, keys nb x 32 each,
+  // blinding factors nb x 3 | nb x 8
+  const bool vec = io.s_L != nullptr;
+  const size_t p1 = nb * n1, p2 = nb * n2;
+  Words8 *split = (Words8 *)sc.take(((vec ? 5 : 3) * (p1 + p2) + 2 * nb + 11 * nb) * 32);
+  if (!split) return BPGPU_E_OOM;
+  Words8 *at = split;
+  auto cut = [&](size_t count) { Words8 *p = at; at += count; return p; };
+  Words8 *L1 = cut(p1), *R1 = cut(p1), *O1 = cut(p1), *L2 = cut(p2), *R2 = cut(p2), *O2 = cut(p2);
+  Words8 *sL1 = vec ? cut(p1) : nullptr, *sR1 = vec ? cut(p1) : nullptr, *sL2 = vec ? cut(p2) : nullptr, *sR2 = vec ? cut(p2) : nullptr;
+  Words8 *k1 = cut(nb), *k2 = cut(nb), *bl1 = cut(3 * nb), *bl2 = cut(8 * nb);
+  auto rows = [&](void *dst, size_t dcount, const void *src, size_t scount, size_t off) {   // dcount scalars of each prover's scount, from off
+    if (!dcount) return hipSuccess;
+    return hipMemcpy2DAsync(dst, dcount * 32, (const Words8 *)src + off, scount * 32, dcount * 32, nb, hipMemcpyDeviceToDevice, st);
+  };
+  if (vec) {
+    WHIP(e.ctx, rows(sL1, n1, io.s_L, n, 0));
+    WHIP(e.ctx, rows(sR1, n1, io.s_R, n, 0));
+    WHIP(e.ctx, rows(sL2, n2, io.s_L, n, n1));
+    WHIP(e.ctx, rows(sR2, n2, io.s_R, n, n1));
+  } else {
+    WHIP(e.ctx, rows(k1, 1, io.vector_keys, 2, 0));
+    WHIP(e.ctx, rows(k2, 1, io.vector_keys, 2, 1));
+  }
+  WHIP(e.ctx, rows(bl1, 3, io.blindings, 11, 0));
+  WHIP(e.ctx, rows(bl2, 8, io.blindings, 11, 3));
+  wit_phase(e, w, nb, 1, run, nullptr);
+  wit_export(e, w, nb, run, 0, n1, L1, R1, O1, n1);
+  const Fs2Between b{&e, w, nb, &run, L2, R2, O2};
+  const bpgpu_internal_fs2 ch{io.states_in, io.gadget_label,
+                              n1 ? L1 : nullptr, n1 ? R1 : nullptr, n1 ? O1 : nullptr, sL1, sR1, vec ? nullptr : k1, bl1,
+                              L2, R2, O2, sL2, sR2, vec ? nullptr : k2, bl2,
+                              io.v_blinding, io.proof_points, io.proof_scalars, io.wire, io.challenges_out, io.states_out, io.chi_out};
+  WCK(bpgpu_internal_prove_fs2_chains(e.ctx, g, c, nb, n1, ch, fs2_between, (void *)&b));
+  if (io.aL) wit_export(e, w, nb, run, 0, n, io.aL, io.aR, io.aO, n);
+  return bpgpu_internal_hip(e.ctx, hipGetLastError(), "two-phase prover launch");
+}
+
+}  // namespace
+
+extern "C" {
+#pragma GCC visibility push(default)
+
+int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
+                       size_t nb, int32_t out[BPGPU_WIT_PLAN_FIELDS]) {
+  return no_throw([&]() -> int {
+    if (!out) return BPGPU_E_ARG;
+    WitShape s;
+    WCK(wit_analyse(n, n1, nchi, op, row_ptr, kind, idx, &s));
+    out[BPGPU_WIT_PLAN_LEVELS1] = (int32_t)s.levels[0];
+    out[BPGPU_WIT_PLAN_LEVELS2] = (int32_t)s.levels[1];
+    out[BPGPU_WIT_PLAN_WIDEST] = (int32_t)s.widest;
+    out[BPGPU_WIT_PLAN_LONG_ROWS] = (int32_t)s.nlong;
+    out[BPGPU_WIT_PLAN_INPUTS] = (int32_t)s.ninp;
+    out[BPGPU_WIT_PLAN_ROUTE1] = wit_route(n1, s.levels[0], nb);
+    out[BPGPU_WIT_PLAN_ROUTE2] = wit_route(n - n1, s.levels[1], nb);
+    return BPGPU_OK;
+  });
+}
+
+int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
+                         const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff, bpgpu_witness **out) {
+  return no_throw([&]() -> int {
+    if (!ctx || !out) return BPGPU_E_ARG;
+    *out = nullptr;
+    if (n && !arg) return BPGPU_E_ARG;
+    WitShape s;
+    WCK(wit_analyse(n, n1, nchi, op, row_ptr, kind, idx, &s));
+    if (m > ROWS_IDX_MASK) return BPGPU_E_LEN;
+    if (s.nnz && !coeff) return BPGPU_E_ARG;
+    const size_t rows = 2 * n, nnz = s.nnz, nlev = (size_t)s.levels[0] + s.levels[1];
+    // the rest of the validation: after it no index a kernel forms is out of range
+    for (size_t i = 0; i < n; i++) {
+      if (op[i] == BPGPU_GATE_BIT && arg[i] >= WIT_BIT_MAX) return BPGPU_E_ARG;
+      if (op[i] == BPGPU_GATE_INPUT && (s.row_len[2 * i] || s.row_len[2 * i + 1])) return BPGPU_E_ARG;
+      if (op[i] == BPGPU_GATE_BIT && s.row_len[2 * i + 1]) return BPGPU_E_ARG;
+      for (size_t j = 0; j <= nchi; j++) {
+        const size_t r = j * rows + 2 * i;
+        if (j && i < n1 && row_ptr[r + 2] != row_ptr[r]) return BPGPU_E_ARG;       // the challenge does not exist in phase 1
+        for (uint32_t t = row_ptr[r]; t < row_ptr[r + 2]; t++)
+          if (kind[t] == 3 && idx[t] >= m) return BPGPU_E_ARG;
+      }
+    }
+    // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op], every part 256-byte aligned
+    const size_t o_rp = up256((nnz ? nnz : 1) * 32), o_var = o_rp + up256((rows + 1) * 4), o_arg = o_var + up256((nnz ? nnz : 1) * 4),
+                 o_ord = o_arg + up256((n ? n : 1) * 4), o_lp = o_ord + up256((n ? n : 1) * 4), o_ll = o_lp + up256((nlev + 1) * 4),
+                 o_op = o_ll + up256((nlev ? nlev : 1) * 4), total = o_op + up256(n ? n : 1);
+    std::vector<uint8_t> img(total, 0);
+    Words8 *h_coeff = (Words8 *)img.data();
+    uint32_t *h_rp = (uint32_t *)(img.data() + o_rp), *h_var = (uint32_t *)(img.data() + o_var), *h_arg = (uint32_t *)(img.data() + o_arg),
+             *h_ord = (uint32_t *)(img.data() + o_ord), *h_lp = (uint32_t *)(img.data() + o_lp), *h_ll = (uint32_t *)(img.data() + o_ll);
+    uint8_t *h_op = img.data() + o_op;
+    // one CSR of 2 n rows: a row's blocks one after the other, the block in the term's code; coefficients in Montgomery form
+    uint32_t pos = 0;
+    for (size_t r = 0; r < rows; r++) {
+      h_rp[r] = pos;
+      for (size_t j = 0; j <= nchi; j++)
+        for (uint32_t t = row_ptr[j * rows + r]; t < row_ptr[j * rows + r + 1]; t++, pos++) {
+          uint32_t cw[8];
+          memcpy(cw, coeff + 32 * (size_t)t, 32);
+          if (!words_lt_mod<FN>(cw)) return BPGPU_E_ARG;
+          pack(h_coeff[pos].w, canon(to_mont(unpack<FN>(cw))));
+          h_var[pos] = (kind[t] == 4 ? 0u : idx[t]) | kind[t] << ROWS_KIND_SHIFT | (uint32_t)j << ROWS_CHI_SHIFT;
+        }
+    }
+    h_rp[rows] = pos;
+    // the gates of a phase sorted by level (stable: program order within a level), the ones with a long row last in their level
+    const uint32_t lane_max = rows_lane_max();
+    uint32_t pairs = 0, at = 0, lvl_base = 0;
+    for (size_t i = 0; i < n; i++) {
+      h_op[i] = op[i];
+      h_arg[i] = op[i] == BPGPU_GATE_INPUT ? pairs++ : (op[i] == BPGPU_GATE_BIT ? arg[i] : 0);
+    }
+    for (int ph = 0; ph < 2; ph++) {
+      const size_t lo = ph ? n1 : 0, hi = ph ? n : n1;
+      for (uint32_t l = 0; l < s.levels[ph]; l++) {
+        h_lp[lvl_base + l] = at;
+        for (int want_long = 0; want_long < 2; want_long++) {
+          if (want_long) h_ll[lvl_base + l] = at;
+          for (size_t i = lo; i < hi; i++)
+            if (s.level[i] == l && (int)(s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max) == want_long) h_ord[at++] = (uint32_t)i;
+        }
+      }
+      lvl_base += s.levels[ph];
+    }
+    h_lp[nlev] = at;
+    bpgpu_witness *w = new (std::nothrow) bpgpu_witness();
+    if (!w) return BPGPU_E_OOM;
+    w->n = n; w->n1 = n1; w->m = m; w->nchi = nchi; w->ninp = s.ninp;
+    w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
+    Entered e(ctx);
+    int rc = e.enter();
+    // (a plain allocation, not the context's pool: a program may outlive the context that made it, as a circuit may)
+    if (rc == BPGPU_OK && hipMalloc(&w->mem, total) != hipSuccess) { (void)hipGetLastError(); w->mem = nullptr; rc = BPGPU_E_OOM; }
+    if (rc == BPGPU_OK) rc = bpgpu_internal_hip(ctx, hipMemcpyAsync(w->mem, img.data(), total, hipMemcpyHostToDevice, e.view.st), "witness program upload");
+    if (rc == BPGPU_OK) rc = bpgpu_internal_hip(ctx, hipStreamSynchronize(e.view.st), "witness program upload");     // `img` is a local
+    if (rc != BPGPU_OK) { if (w->mem) (void)hipFree(w->mem); delete w; return rc; }
+    const uint8_t *d = (const uint8_t *)w->mem;
+    w->dev.rows = RowsDev{(const uint32_t *)(d + o_rp), (const uint32_t *)(d + o_var), (const Words8 *)d, nullptr, rows, nnz, 0};
+    w->dev.op = d + o_op;
+    w->dev.arg = (const uint32_t *)(d + o_arg);
+    w->dev.order = (const uint32_t *)(d + o_ord);
+    w->dev.level_ptr = (const uint32_t *)(d + o_lp);
+    w->dev.level_long = (const uint32_t *)(d + o_ll);
+    w->dev.n = (uint32_t)n; w->dev.m = (uint32_t)m; w->dev.nchi = (uint32_t)nchi; w->dev.ninp = s.ninp;
+    *out = w;
+    return BPGPU_OK;
+  });
+}
+void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w) {
+  if (!w) return;
+  if (ctx) (void)bpgpu_sync(ctx);
+  (void)hipFree(w->mem);
+  delete w;
+}
+
+int bpgpu_r1cs_witness_synthesize_dev(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const void *v, const void *inputs,
+                                      const void *gadget_challenges, void *a_L, void *a_R, void *a_O) {
+  return no_throw([&]() -> int {
+    WCK(synth_check(ctx, w, nb, phase, v, inputs, gadget_challenges, a_L, a_R, a_O));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    WCK(bpgpu_internal_flag_reset(ctx));   // the flag reports on the most recent *_dev call
+    return synth_locked(e, w, nb, phase, v, inputs, gadget_challenges, a_L, a_R, a_O);
+  });
+}
+int bpgpu_r1cs_witness_synthesize(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const uint8_t *v, const uint8_t *inputs,
+                                  const uint8_t *gadget_challenges, uint8_t *a_L, uint8_t *a_R, uint8_t *a_O) {
+  return no_throw([&]() -> int {
+    WCK(synth_check(ctx, w, nb, phase, v, inputs, gadget_challenges, a_L, a_R, a_O));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    Scratch sc(ctx);
+    // staging: the three planes, then v, the input pairs, the challenges
+    const size_t plane = nb * w->n, b_v = nb * w->m * 32, b_in = 2 * nb * w->ninp * 32, b_chi = gadget_challenges ? nb * w->nchi * 32 : 0;
+    Words8 *dL = (Words8 *)sc.take(3 * plane * 32 + b_v + b_in + b_chi);
+    if (!dL) return BPGPU_E_OOM;
+    Words8 *dR = dL + plane, *dO = dR + plane;
+    uint8_t *dv = (uint8_t *)(dO + plane), *din = dv + b_v, *dchi = din + b_in;
+    hipStream_t st = e.view.st;
+    WCK(bpgpu_internal_flag_reset(ctx));
+    if (b_v) WHIP(ctx, hipMemcpyAsync(dv, v, b_v, hipMemcpyHostToDevice, st));
+    if (b_in) WHIP(ctx, hipMemcpyAsync(din, inputs, b_in, hipMemcpyHostToDevice, st));
+    if (b_chi) WHIP(ctx, hipMemcpyAsync(dchi, gadget_challenges, b_chi, hipMemcpyHostToDevice, st));
+    uint8_t *host[3] = {a_L, a_R, a_O};
+    Words8 *dev[3] = {dL, dR, dO};
+    // a phase on its own leaves the other phase's multipliers as the caller holds them: the planes travel whole, both ways
+    if (phase != 0 && plane) for (int k = 0; k < 3; k++) WHIP(ctx, hipMemcpyAsync(dev[k], host[k], plane * 32, hipMemcpyHostToDevice, st));
+    WCK(synth_locked(e, w, nb, phase, b_v ? dv : nullptr, b_in ? din : nullptr, b_chi ? dchi : nullptr, dL, dR, dO));
+    WCK(bpgpu_internal_checked_wait(ctx));
+    if (plane) for (int k = 0; k < 3; k++) WHIP(ctx, hipMemcpyAsync(host[k], dev[k], plane * 32, hipMemcpyDeviceToHost, st));
+    WHIP(ctx, hipStreamSynchronize(st));
+    return BPGPU_OK;
+  });
+}
+
+int bpgpu_r1cs_prove_fs2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                             const void *states_in, const uint8_t gadget_label[32], const void *v, const void *inputs, const void *s_L,
+                             const void *s_R, const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
+                             void *proof_scalars, void *wire, void *challenges_out, void *states_out, void *gadget_challenges_out,
+                             void *a_L_out, void *a_R_out, void *a_O_out) {
+  return no_throw([&]() -> int {
+    const Fs2Io io{states_in, gadget_label, v, inputs, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars, wire,
+                   challenges_out, states_out, gadget_challenges_out, a_L_out, a_R_out, a_O_out};
+    WCK(fs2_check(ctx, g, c, w, nb, io));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    WCK(bpgpu_internal_flag_reset(ctx));   // the flag reports on the most recent *_dev call
+    return fs2_locked(e, g, c, w, nb, io);
+  });
+}
+int bpgpu_r1cs_prove_fs2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                         const uint8_t *states_in, const uint8_t gadget_label[32], const uint8_t *v, const uint8_t *inputs, const uint8_t *s_L,
+                         const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings,
+                         uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out,
+                         uint8_t *gadget_challenges_out, uint8_t *a_L_out, uint8_t *a_R_out, uint8_t *a_O_out) {
+  return no_throw([&]() -> int {
+    const Fs2Io a{states_in, gadget_label, v, inputs, s_L, s_R, vector_keys, v_blinding, blindings, proof_points, proof_scalars, wire,
+                  challenges_out, states_out, gadget_challenges_out, a_L_out, a_R_out, a_O_out};
+    WCK(fs2_check(ctx, g, c, w, nb, a));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    if (e.view.shard_world > 1) return BPGPU_E_ARG;
+    Scratch sc(ctx);
+    const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n * 32;
+    // staging: the operands in the order given (an absent one, of zero bytes, gets a null device pointer), then the results -- the
+    // optional ones downloaded only when asked for, the wire form (of odd length) last
+    const void *in_host[8] = {a.states_in, a.v, a.inputs, a.s_L, a.s_R, a.vector_keys, a.v_blinding, a.blindings};
+    const size_t in_bytes[8] = {nb * 32, nb * m * 32, 2 * nb * w->ninp * 32, a.s_L ? plane : 0, a.s_R ? plane : 0, a.vector_keys ? nb * 64 : 0,
+                                nb * m * 32, nb * 11 * 32};
+    void *out_host[9] = {a.proof_points, a.proof_scalars, a.challenges_out, a.states_out, a.chi_out, a.aL, a.aR, a.aO, a.wire};
+    const size_t out_bytes[9] = {nb * (11 + 2 * k) * 64, nb * 5 * 32, a.challenges_out ? nb * (5 + k) * 32 : 0, a.states_out ? nb * 32 : 0,
+                                 a.chi_out ? nb * 32 : 0, a.aL ? plane : 0, a.aL ? plane : 0, a.aL ? plane : 0,
+                                 a.wire ? nb * (1 + 14 * 32 + (2 * k + 2) * 32) : 0};
+    size_t total = 0;
+    for (size_t b : in_bytes) total += b;
+    for (size_t b : out_bytes) total += b;
+    uint8_t *stage = (uint8_t *)sc.take(total);
+    if (!stage) return BPGPU_E_OOM;
+    uint8_t *in[8], *out[9], *at = stage;
+    for (int i = 0; i < 8; i++) { in[i] = in_bytes[i] ? at : nullptr; at += in_bytes[i]; }
+    for (int i = 0; i < 9; i++) { out[i] = out_bytes[i] ? at : nullptr; at += out_bytes[i]; }
+    hipStream_t st = e.view.st;
+    WCK(bpgpu_internal_flag_reset(ctx));
+    for (int i = 0; i < 8; i++) if (in_bytes[i]) WHIP(ctx, hipMemcpyAsync(in[i], in_host[i], in_bytes[i], hipMemcpyHostToDevice, st));
+    WCK(fs2_locked(e, g, c, w, nb, {in[0], a.gadget_label, in[1], in[2], in[3], in[4], in[5], in[6], in[7], out[0], out[1], out[8], out[2],
+                                    out[3], out[4], out[5], out[6], out[7]}));
+    WCK(bpgpu_internal_checked_wait(ctx));
+    for (int i = 0; i < 9; i++) if (out_bytes[i]) WHIP(ctx, hipMemcpyAsync(out_host[i], out[i], out_bytes[i], hipMemcpyDeviceToHost, st));
+    WHIP(ctx, hipStreamSynchronize(st));
+    return BPGPU_OK;
+  });
+}
+
+#pragma GCC visibility pop
+}  // extern "C"

@@ -1,0 +1,106 @@
+// k_witness.hip -- witness synthesis: the gates of a bpgpu_witness program (Prover::multiply, prover.rs:99-125; allocate_multiplier,
+// :148-165) for nb provers, one launch per phase, in two forms.  The gate itself is wit_gate_values of witness_dev.cuh; the rows are
+// eval_row's (fn_dev.cuh).  The planes a launch works on are the library's own scratch, plain canonical words: witness_convert takes
+// the callers' ark planes in and out, prover by prover, so that a phase can land in planes of its own stride.
+#include "fe29_consts.h"
+#include "witness_dev.cuh"
+
+using namespace bp;
+
+namespace bpk {
+
+struct WitArgs {
+  WitDev w;
+  size_t nb;
+  uint32_t g_lo, g_hi, l_lo, l_hi;
+  Words8 *aL, *aR, *aO;
+  const Words8 *v, *inputs, *chi;
+};
+// what one prover reads and writes (chi: never read when no term has j > 0, as in eval_row)
+struct WitProver { Words8 *aL, *aR, *aO; const Words8 *v, *inputs, *chi; };
+__device__ __forceinline__ WitProver wit_prover(const WitArgs &a, size_t p) {
+  return {a.aL + p * a.w.n, a.aR + p * a.w.n, a.aO + p * a.w.n, a.v + p * a.w.m, a.inputs + p * a.w.ninp * 2, a.chi + p * a.w.nchi};
+}
+
+// A lane per prover: the gates in program order, which is topological (a term reads a gate below its own), so a lane only ever
+// reads what it has stored itself.
+__global__ void __launch_bounds__(256) k_witness_lane(WitArgs a) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.nb) return;
+  const WitProver o = wit_prover(a, p);
+  for (uint32_t i = a.g_lo; i < a.g_hi; i++) wit_gate_lane(a.w, i, o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
+}
+// A block per prover: level by level.  The gates of a level read lower levels only (or earlier phases), so they are independent:
+// those without a long row are strided over the 256 threads, the others over the four waves (lane-strided terms, then wave_sum, as
+// k_rows_eval does).  Between two levels the plane stores of the one are made visible to the block (they are global stores that
+// other waves of this block load: a block-scope fence, then the barrier).  Every thread of the block reaches every barrier: the
+// level range is the launch's, and no thread leaves early.
+__global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
+  const WitProver o = wit_prover(a, blockIdx.x);
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (uint32_t l = a.l_lo; l < a.l_hi; l++) {
+    const uint32_t lo = a.w.level_ptr[l], mid = a.w.level_long[l], hi = a.w.level_ptr[l + 1];
+    for (uint32_t t = lo + threadIdx.x; t < mid; t += 256) wit_gate_lane(a.w, a.w.order[t], o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
+    for (uint32_t t = mid + wave; t < hi; t += 4) {                                            // wave-uniform
+      const uint32_t i = a.w.order[t];
+      const uint32_t *rp = a.w.rows.row_ptr + 2 * (size_t)i;
+      const Fn one = fe_one<FN>();
+      const Fn left = wave_sum(fn_reduce(eval_row(a.w.rows, rp[0] + lane, rp[1], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
+      const Fn right = wave_sum(fn_reduce(eval_row(a.w.rows, rp[1] + lane, rp[2], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
+      if (lane == 0) {
+        const WitGate g = wit_gate_values(a.w.op[i], a.w.arg[i], left, right, o.inputs);
+        wit_store(o.aL + i, g.L);
+        wit_store(o.aR + i, g.R);
+        wit_store(o.aO + i, g.O);
+      }
+    }
+    if (l + 1 < a.l_hi) {
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, bool block, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
+                  Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi) {
+  if (!nb || g_lo >= g_hi) return;
+  const WitArgs a{w, nb, g_lo, g_hi, l_lo, l_hi, aL, aR, aO, v, inputs, chi};
+  if (block) hipLaunchKernelGGL(k_witness_block, dim3((unsigned)nb), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_witness_lane, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, a);
+}
+
+// ---- the callers' ark planes in and out: a lane per (prover, scalar) ---------------------------------------------------------------
+__device__ __forceinline__ Fn wit_const(const int32_t (&c)[NL]) {
+  Fn r;
+#pragma unroll
+  for (int j = 0; j < NL; j++) r.v[j] = c[j];
+  return r;
+}
+__global__ void __launch_bounds__(256) k_witness_convert(bool to_ark, size_t nb, size_t count, const Words8 *src, size_t src_stride,
+                                                         Words8 *dst, size_t dst_stride, int *bad) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb * count) return;
+  const size_t p = i / count, k = i % count;
+  const Words8 *in = src + p * src_stride + k;
+  Words8 *out = dst + p * dst_stride + k;
+  constexpr int32_t CIN[NL] = FN_ARK_IN, COUT[NL] = FN_ARK_OUT;
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) w[j] = in->w[j];
+  if (!words_lt_mod<FN>(w)) {
+    atomicOr(bad, 1);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = 0;
+  } else {
+    pack(w, canon(mul(unpack<FN>(w), to_ark ? wit_const(COUT) : wit_const(CIN))));
+  }
+#pragma unroll
+  for (int j = 0; j < 8; j++) out->w[j] = w[j];
+}
+void witness_convert(hipStream_t st, bool to_ark, size_t nb, size_t count, const Words8 *src, size_t src_stride, Words8 *dst,
+                     size_t dst_stride, int *bad) {
+  const size_t tot = nb * count;
+  if (tot) hipLaunchKernelGGL(k_witness_convert, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, to_ark, nb, count, src, src_stride,
+                              dst, dst_stride, bad);
+}
+
+}  // namespace bpk

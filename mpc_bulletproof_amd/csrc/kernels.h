@@ -264,6 +264,31 @@ void rows_verdict(hipStream_t st, size_t nb, const uint32_t *bad_row, const uint
 // the scan of circuit_transpose on its own (k_scalar.hip k_csr_scan): cnt[0] = 0, cnt[i + 1] = count of i -> cnt[i + 1] = end of i
 void csr_scan(hipStream_t st, uint32_t *cnt, size_t n1);
 
+// ---- witness synthesis (k_witness.hip): Prover::multiply / allocate_multiplier (prover.rs:99-125, :148-165) ---------------------
+// A resident gate program (bpgpu_witness): gate i owns rows 2 i (left) and 2 i + 1 (right) of `rows` (terms as in a circuit's row-major
+// view: Montgomery coefficients, var = idx | kind << ROWS_KIND_SHIFT | j << ROWS_CHI_SHIFT; long_rows unused), op[i], arg[i] (the bit of
+// a BIT gate, the pair index of an INPUT gate).  The gates of phase ph are listed level by level in order[]: level l of the program
+// (phase 1's levels first) holds order[level_ptr[l] .. level_ptr[l + 1]), the gates without a long row (witness_dev.cuh) before
+// level_long[l], the others from it.  Validated on the host: every index a kernel forms from these arrays is in range.
+struct WitDev {
+  RowsDev rows;
+  const uint8_t *op;          // n
+  const uint32_t *arg;        // n
+  const uint32_t *order;      // n
+  const uint32_t *level_ptr;  // levels + 1
+  const uint32_t *level_long; // levels
+  uint32_t n, m, nchi, ninp;
+};
+// One launch evaluates the gates [g_lo, g_hi) = the levels [l_lo, l_hi) of nb provers on plain canonical planes nb x n (aL, aR, aO:
+// read for the gates below g_lo, written for the range), v nb x m, inputs nb x ninp x 2, chi nb x nchi (or nullptr), all plain.
+// block == false: a lane per prover, program order; true: a block of 256 threads per prover, level by level.
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, bool block, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
+                  Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
+// rows of `count` scalars, one per prover: src + p * src_stride -> dst + p * dst_stride.  to_ark: plain canonical -> ark Montgomery
+// limbs, else the reverse; a non-canonical source raises *bad and gives zero
+void witness_convert(hipStream_t st, bool to_ark, size_t nb, size_t count, const Words8 *src, size_t src_stride, Words8 *dst,
+                     size_t dst_stride, int *bad);
+
 // ---- R1CS prover polynomials (r1cs/prover.rs:587-619, 659-672) -----------------------------------
 // polys: raw Montgomery limbs, layout [6][nb][n][9]: l1 l2 l3 r0 r1 r3
 void prover_polys(hipStream_t st, const CircuitDev &c, size_t nb, const Words8 *y, const Words8 *y_inv,

@@ -67,7 +67,8 @@ E_ARG, E_LEN, E_DEVICE, E_OOM, E_GENS = -1, -2, -3, -4, -5
 # bpgpu_set_option (include/bpgpu.h BPGPU_OPT_*)
 OPT = {"msm_wp_max": 1, "msm_pip2_single": 2, "verify_no_fuse": 3, "verify_window_parallel": 4, "verify_straus_np": 5,
        "ipp_literal": 6, "vs_large_min": 7, "table_np": 8, "ipp_table_max_n": 9, "stream_lanes": 10, "stream_batch": 11, "screen_batch": 12,
-       "horner_form": 13, "horner_row_max": 14, "pippenger_min": 15, "ipp_pippenger_min": 16, "fixed_lpm": 17, "groups_form": 18, "fixed_chunk_gens": 19}
+       "horner_form": 13, "horner_row_max": 14, "pippenger_min": 15, "ipp_pippenger_min": 16, "fixed_lpm": 17, "groups_form": 18, "fixed_chunk_gens": 19,
+       "witness_route": 20}
 # bpgpu_profile_read kinds (include/bpgpu.h BPGPU_PROF_KINDS)
 PROF_NAMES = ["verify_scalars", "fixed_msm", "points_from_boundary", "straus", "verify_finalize", "transcript", "verify_msm",
               "verify_windows", "verify_front", "verify_groups", "verify_back", "verify_verdict", "combined_front_scalars_digits",
@@ -112,8 +113,29 @@ def pippenger_plan(nb, n):
     return dict(zip(PIP_PLAN_FIELDS, out))
 
 
+# bpgpu_witness_plan (include/bpgpu.h BPGPU_WIT_PLAN_*); gate ops BPGPU_GATE_*
+WIT_PLAN_FIELDS = ("levels1", "levels2", "widest", "long_rows", "inputs", "route1", "route2")
+GATE_MUL, GATE_INPUT, GATE_BIT = 0, 1, 2
+
+
+def _u32s(xs, pad=1):
+    return (C.c_uint32 * max(len(xs), pad))(*xs)
+
+
+def witness_plan(n, n1, nchi, op, row_ptr, kind, idx, nb):
+    """the dependency levels of a gate program and the launch form of each phase for nb provers, as a dict over WIT_PLAN_FIELDS
+    (needs no device)"""
+    out = (C.c_int32 * len(WIT_PLAN_FIELDS))()
+    rc = _lib.bpgpu_witness_plan(n, n1, nchi, _buf(bytes(op)), _u32s(row_ptr), _u32s(kind), _u32s(idx), nb, out)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return dict(zip(WIT_PLAN_FIELDS, out))
+
+
 class BpGpu:
     """One context on one device.  All byte encodings as in include/bpgpu.h."""
+
+    witness_plan = staticmethod(witness_plan)
 
     def __init__(self, device=0):
         self.ctx = C.c_void_p()
@@ -628,6 +650,58 @@ class BpGpu:
         operand raises input_flag()"""
         self._ck(_lib.bpgpu_r1cs_constraints_satisfied_dev(self.ctx, circuit, nb, d_a_L, d_a_R, d_a_O, d_v, d_gadget_challenges, d_ok,
                                                            d_first_bad_row, d_first_bad_gate, d_residuals))
+
+    # ---- witness synthesis (include/bpgpu.h bpgpu_witness)
+    def witness_create(self, n, n1, m, nchi, op, arg, row_ptr, kind, idx, coeff):
+        """a resident gate program: n multipliers (the first n1 in phase 1) over m committed values; op, arg per gate; the rows
+        2 i (left), 2 i + 1 (right) as a CSR of (1 + nchi) * 2 n rows, coefficients canonical LE"""
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_witness_create(self.ctx, n, n1, m, nchi, _buf(bytes(op)), _u32s(arg), _u32s(row_ptr), _u32s(kind), _u32s(idx),
+                                           _buf(coeff), C.byref(h)))
+        return h
+
+    def witness_destroy(self, w):
+        _lib.bpgpu_witness_destroy(self.ctx, w)
+
+    def r1cs_witness_synthesize(self, w, nb, n, phase=0, v=None, inputs=None, gadget_challenges=None, a_L=None, a_R=None, a_O=None):
+        """the witnesses of nb provers of a program of n multipliers (bpgpu_r1cs_witness_synthesize): v nb x m and inputs
+        nb x n_inputs x 2 in ark form, gadget challenges nb x nchi x 32 B canonical LE -> (a_L, a_R, a_O) nb x n, ark form.  phase 1
+        or 2 assigns that phase's gates only: the planes given (phase 2: holding phase 1) come back with the rest untouched"""
+        planes = [_inout(p) if p is not None else _out(32 * nb * n) for p in (a_L, a_R, a_O)]
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_witness_synthesize(self.ctx, w, nb, phase, opt(v), opt(inputs), opt(gadget_challenges), *planes))
+        return tuple(bytes(p)[:32 * nb * n] for p in planes)
+
+    def r1cs_witness_synthesize_dev(self, w, nb, phase, d_a_L, d_a_R, d_a_O, d_v=None, d_inputs=None, d_gadget_challenges=None):
+        """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
+        self._ck(_lib.bpgpu_r1cs_witness_synthesize_dev(self.ctx, w, nb, phase, d_v, d_inputs, d_gadget_challenges, d_a_L, d_a_R, d_a_O))
+
+    def r1cs_prove_fs2(self, gens, circuit, w, nb, n, m, states, gadget_label, blindings, v=None, inputs=None, v_blinding=None, s_L=None,
+                       s_R=None, vector_keys=None, want_wire=True, want_witness=False):
+        """Prover::prove for nb provers of a two-phase circuit of n multipliers and m commitments in one call (bpgpu_r1cs_prove_fs2):
+        the gates of program w on the device around the two transcript chains; blindings nb x 11 -> (proof_points, proof_scalars, wire
+        or None, challenges, states_out, gadget challenges, (a_L, a_R, a_O) or None)"""
+        k = max(n - 1, 0).bit_length()
+        nvar, plen = 11 + 2 * k, 1 + 14 * 32 + (2 * k + 2) * 32
+        pts, sc, ch, so, chi = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb), _out(32 * nb)
+        wire = _out(nb * plen) if want_wire else None
+        planes = [_out(32 * nb * n) if want_witness else None for _ in range(3)]
+        lab = (gadget_label + bytes(32))[:32]
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_r1cs_prove_fs2(self.ctx, gens, circuit, w, nb, opt(states), _buf(lab), opt(v), opt(inputs), opt(s_L), opt(s_R),
+                                           opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so, chi, *planes))
+        return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
+                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb],
+                tuple(bytes(p)[:32 * nb * n] for p in planes) if want_witness else None)
+
+    def r1cs_prove_fs2_dev(self, gens, circuit, w, nb, d_states, gadget_label, d_blindings, d_points, d_scalars, d_v=None, d_inputs=None,
+                           d_v_blinding=None, d_s_L=None, d_s_R=None, d_vector_keys=None, d_wire=None, d_ch=None, d_states_out=None,
+                           d_chi=None, d_a_L=None, d_a_R=None, d_a_O=None):
+        """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
+        lab = (gadget_label + bytes(32))[:32]
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_dev(self.ctx, gens, circuit, w, nb, d_states, _buf(lab), d_v, d_inputs, d_s_L, d_s_R, d_vector_keys,
+                                               d_v_blinding, d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out, d_chi, d_a_L,
+                                               d_a_R, d_a_O))
 
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)

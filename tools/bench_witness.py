@@ -1,0 +1,216 @@
+#!/usr/bin/env python3
+"""Witness synthesis on the device (bpgpu_r1cs_witness_synthesize_dev) and the one-call two-phase prover (bpgpu_r1cs_prove_fs2_dev)
+against the two calls around a host that evaluates the gadget.  Writes profiles/witness_synth.log (the source of the figures in
+DESIGN.md "Witness synthesis").  Shapes: 256 provers x 16 x 64-bit range (one level of 1024 BIT gates), 256 provers x shuffle k = 64
+(two chains of 63 dependent gates), 1 prover x shuffle k = 2^14 (two chains of 16 383).
+
+  synth   the synthesis alone on resident operands, HIP events around the call, on both launch forms (BPGPU_OPT_WITNESS_ROUTE 1 = a
+          lane per prover, 2 = a block per prover) and what bpgpu_witness_plan picks; next to it the HOST's evaluation of the same
+          gates: this tool's Python integers (a Rust host is faster: the figure bounds the host from above);
+  prove   bpgpu_r1cs_prove_fs2_dev (one call) against bpgpu_r1cs_prove_fs2_begin_dev + the host's gadget (download of the challenge,
+          evaluation, Montgomery encoding, upload) + _finish_dev on the same inputs, wall clock from the first call to the drained
+          stream; `chains` is the pair of _dev calls alone on a resident phase-2 witness, the figure tools/bench_prove_fs2.py
+          reports (profiles/prove_fs2.log holds it for the parent commit).  Shapes: 256 x shuffle k = 64 and 1 x shuffle k = 2^10 -- the
+          largest single prover that tool proves through this binding; the k = 2^14 prover (generator tables for 2^15) goes through
+          the host mirror (tools/bench_shuffle.py), which is out of scope here, so that shape has the synthesis line alone.  The
+          range shape is a one-phase prover: bpgpu_r1cs_prove_fs_dev after the synthesis, no second call to save.
+
+A fresh process per line under its own time limit; WARM untimed steps, then STEPS timed ones, medians (min..max) in ms."""
+import ctypes as C
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+WARM, STEPS = 3, 20
+LABEL = b"shuffle challenge"
+STEP_LIMIT = 420          # seconds per child process
+
+
+def fmt(ts):
+    return f"{statistics.median(ts):9.3f} ({min(ts):8.3f}..{max(ts):9.3f})"
+
+
+def shuffle_program(k):
+    """the shuffle's gates (tests/witness_cases.py) and one prover's values"""
+    import witness_cases as wc
+    prog = wc.Program(2 * k, nchi=1)
+    prog.end_phase1()
+    wc._shuffle_gates(prog, k, 0)
+    xs = [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << 64) - 1)) for i in range(k)]
+    return prog, xs + xs[1:] + xs[:1]
+
+
+def range_program(bits, m):
+    import witness_cases as wc
+    case = wc.range_case(bits, m)
+    return case.prog, [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << bits) - 1)) for i in range(m)]
+
+
+class Timer:
+    def __init__(self, gpu):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+        self.ev = [C.c_void_p(), C.c_void_p()]
+        for e in self.ev:
+            assert self.hip.hipEventCreate(C.byref(e)) == 0
+        self.st = C.c_void_p(gpu.stream())
+
+    def events(self, body):
+        assert self.hip.hipEventRecord(self.ev[0], self.st) == 0
+        body()
+        assert self.hip.hipEventRecord(self.ev[1], self.st) == 0 and self.hip.hipEventSynchronize(self.ev[1]) == 0
+        ms = C.c_float()
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.ev[0], self.ev[1]) == 0
+        return ms.value
+
+
+def synth(shape, nb, size):
+    import mpc_dealer as md
+    import mpc_bulletproof_amd as m
+    prog, v = range_program(64, size) if shape == "range" else shuffle_program(size)
+    chi = (0x1234567,) if prog.nchi else ()
+    t0 = time.perf_counter()
+    want = prog.evaluate(v, (), chi)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    gpu = m.BpGpu(0)
+    w = gpu.witness_create(*prog.create_args())
+    plan = m.lib.witness_plan(*prog.plan_args(), nb)
+    d_v = gpu.to_device(b"".join(md.mont(x) for x in v) * nb)
+    d_chi = gpu.to_device(md.le(chi[0]) * nb) if chi else None
+    planes = [gpu.malloc(32 * nb * prog.n) for _ in range(3)]
+    timer = Timer(gpu)
+    out = {}
+    for route in (1, 2):
+        gpu.set_option("witness_route", route)
+        ts = []
+        for step in range(WARM + STEPS):
+            ms = timer.events(lambda: gpu.r1cs_witness_synthesize_dev(w, nb, 0, *planes, d_v=d_v, d_gadget_challenges=d_chi))
+            if step >= WARM:
+                ts.append(ms)
+        assert gpu.input_flag() == 0
+        got = gpu.download(planes[2], 32 * nb * prog.n)
+        assert got[-32 * prog.n:] == b"".join(md.mont(x) for x in want[2]), "the device's witness differs from the host's"
+        out[route] = ts
+    route = plan["route2" if prog.nchi else "route1"]
+    return (f"lane {fmt(out[1])}   block {fmt(out[2])}   plan: {'lane' if route == 1 else 'block'}   levels {plan['levels1'] + plan['levels2']:6d} "
+            f"widest {plan['widest']:5d}   host (Python, ONE prover) {host_ms:9.3f}")
+
+
+def prove(nb, ks, window_bits):
+    import random
+    import mpc_dealer as md
+    import oracle_lib as o
+    import pymodel as pm
+    import witness_cases as wc
+    import mpc_bulletproof_amd as m
+    prog, v = shuffle_program(ks)
+    n, mm = prog.n, prog.m
+    pv = pm.Prover(pm.PedersenGens(), pm.Transcript(b"ShuffleProofTest"))
+    pv.pc_gens.commit = lambda val, b: pm.G           # the commitments play no part here: skip the model's scalar multiplications
+    vars_ = [pv.commit(x, 1)[1] for x in v]
+    pm.shuffle_gadget(pv, vars_[:ks], vars_[ks:])
+    pv._create_randomized_constraints()
+    rp, kd, ix, cf, _ = md.circuit_rows(pv.constraints, param=True)
+    rnd = random.Random(nb)
+    rb = lambda cnt: bytes(rnd.getrandbits(8) for _ in range(cnt))      # noqa: E731
+    scal = lambda cnt: b"".join(md.mont(rnd.randrange(pm.N)) for _ in range(cnt))      # noqa: E731
+    k = (n - 1).bit_length()
+    gpu = m.BpGpu(0)
+    gens = gpu.gens_create(o.gens("G", 1 << k), o.gens("H", 1 << k), o.generator(), o.generator(), window_bits)
+    circ = gpu.circuit_create_param(len(pv.constraints), 1, rp, kd, ix, cf, n, mm)
+    w = gpu.witness_create(*prog.create_args())
+    bl = [scal(11) for _ in range(nb)]
+    d_states, d_v, d_vb = gpu.to_device(rb(32 * nb)), gpu.to_device(b"".join(md.mont(x) for x in v) * nb), gpu.to_device(scal(nb * mm))
+    keys = [rb(64) for _ in range(nb)]
+    d_bl, d_keys = gpu.to_device(b"".join(bl)), gpu.to_device(b"".join(keys))
+    d_bl1, d_bl2 = gpu.to_device(b"".join(b[:96] for b in bl)), gpu.to_device(b"".join(b[96:] for b in bl))
+    d_k2 = gpu.to_device(b"".join(x[32:] for x in keys))
+    plen = 1 + 14 * 32 + (2 * k + 2) * 32
+    d_pts, d_sc, d_wire, d_chi = gpu.malloc(64 * nb * (11 + 2 * k)), gpu.malloc(160 * nb), gpu.malloc(nb * plen), gpu.malloc(32 * nb)
+    planes = [gpu.malloc(32 * nb * n) for _ in range(3)]
+
+    def one_call():
+        gpu.r1cs_prove_fs2_dev(gens, circ, w, nb, d_states, LABEL, d_bl, d_pts, d_sc, d_v=d_v, d_v_blinding=d_vb, d_vector_keys=d_keys,
+                               d_wire=d_wire)
+        gpu.sync()
+
+    def two_calls(host_gadget):
+        sess = gpu.r1cs_prove_fs2_begin_dev(gens, circ, nb, 0, d_states, LABEL, d_bl1, d_chi=d_chi)
+        if host_gadget:
+            chi = gpu.download(d_chi, 32 * nb)                         # the round trip: the challenge down, ...
+            for k_, plane in enumerate(zip(*(prog.evaluate(v, (), (int.from_bytes(chi[32 * p:32 * p + 32], "little"),)) for p in range(nb)))):
+                gpu.upload(planes[k_], b"".join(md.mont(x) for row in plane for x in row))      # ... the witness up
+        gpu.r1cs_prove_fs2_finish_dev(gens, circ, sess, *planes, d_bl2, d_pts, d_sc, d_v_blinding=d_vb, d_vector_keys=d_k2, d_wire=d_wire)
+        gpu.sync()
+    res, wires = {}, {}
+    steps = STEPS if nb * n < 20000 else 5
+    for name, body in (("one call", one_call), ("two calls + host gadget", lambda: two_calls(True)), ("chains", lambda: two_calls(False))):
+        ts = []
+        for step in range(WARM + steps):
+            t0 = time.perf_counter()
+            body()
+            if step >= WARM:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        assert gpu.input_flag() == 0
+        res[name], wires[name] = ts, gpu.download(d_wire, nb * plen)
+    assert wires["one call"] == wires["two calls + host gadget"], "the one call and the two calls disagree on the proof bytes"
+    one, two = statistics.median(res["one call"]), statistics.median(res["two calls + host gadget"])
+    return (f"one call {fmt(res['one call'])}   two calls + host gadget (Python) {fmt(res['two calls + host gadget'])}   ratio {two / one:7.2f}   "
+            f"chains {fmt(res['chains'])}")
+
+
+def child(what, args):
+    if what == "synth":
+        print("RESULT", synth(args[0], int(args[1]), int(args[2])))
+    else:
+        print("RESULT", prove(int(args[0]), int(args[1]), int(args[2])))
+
+
+def main():
+    if len(sys.argv) >= 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2], sys.argv[3:])
+    lines = [f"# tools/bench_witness.py   a fresh process per line (limit {STEP_LIMIT} s), {WARM} warm-up + {STEPS} timed steps per route: median "
+             "(min..max) ms",
+             "# synth: bpgpu_r1cs_witness_synthesize_dev alone, HIP events; host: the same gates of ONE prover on Python integers"]
+
+    def run(*args):
+        try:
+            out = subprocess.run(["timeout", "-k", "10", str(STEP_LIMIT), sys.executable, os.path.abspath(__file__), "--child"] +
+                                 [str(a) for a in args], capture_output=True, text=True)
+        except OSError as e:
+            return f"FAILED to start: {e}", False
+        got = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")]
+        if out.returncode != 0 or not got:
+            return f"FAILED rc={out.returncode}: {(out.stderr or out.stdout)[-400:]!r}", False
+        return got[0][len("RESULT "):], True
+
+    def step(text, *args):
+        res, ok = run(*args)
+        lines.append(text + res)
+        print(lines[-1])
+        sys.stdout.flush()
+        return ok
+    ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16)
+    ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64)
+    ok = ok and step("synth   1 x shuffle k = 2^14       n = 32766   ", "synth", "shuffle", 1, 1 << 14)
+    lines.append("# prove: wall clock from the first call to the drained stream; chains = begin_dev + finish_dev alone (tools/bench_prove_fs2.py's figure)")
+    ok = ok and step("prove   256 x shuffle k = 64       ", "prove", 256, 64, 8)
+    ok = ok and step("prove   1 x shuffle k = 2^10       ", "prove", 1, 1 << 10, 8)
+    if not ok:
+        lines.append("# a step failed: the steps after it were not started")
+    path = os.path.join(ROOT, "profiles", "witness_synth.log")
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("wrote", path)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
