@@ -19,9 +19,11 @@ namespace bp {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(BP_EC_OUTLINE)
 static __device__ __noinline__ Fp fpmul(const Fp &a, const Fp &b) { return mul(a, b); }
 static __device__ __noinline__ Fp fpsqr(const Fp &a) { return sqr(a); }
+static __device__ __noinline__ Fp fpmul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) { return mul2(a, b, c, d); }
 #else
 BP_HD Fp fpmul(const Fp &a, const Fp &b) { return mul(a, b); }
 BP_HD Fp fpsqr(const Fp &a) { return sqr(a); }
+BP_HD Fp fpmul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) { return mul2(a, b, c, d); }   // (a b + c d) / R, one reduction
 #endif
 
 struct Jac { Fp X, Y, Z; };
@@ -106,11 +108,16 @@ BP_HD MaddMid jac_madd_mid(const Jac &p, const Aff &q) {
   m.rr = sub_nr(S2, p.Y);
   return m;
 }
-BP_HD Jac jac_madd_tail(const Jac &p, const MaddMid &m) {
+// FUSED (the inlined hot paths): Y3 = rr (V - X3) + (-Y1) HHH through ONE reduction (fe29.cuh: mul2) -- rr and V - X3 are un-normalised
+// differences, -Y1 a stored coordinate (or a product) negated limb by limb, HHH a product: all within mul2's 2^29 + 8; the result is
+// tight, so the subtraction's carry pass goes as well.  The out-of-line exact cases keep the two products: they set the registers
+// of their kernels, and the wider chain would cost them twelve more.
+template <bool FUSED> BP_HD Jac jac_madd_tail(const Jac &p, const MaddMid &m) {
   Fp HH = fpsqr(m.H), HHH = fpmul(m.H, HH), V = fpmul(p.X, HH);
   Jac r;
   r.X = norm(sub_nr(sub_nr(sub_nr(fpsqr(m.rr), HHH), V), V));
-  r.Y = sub(fpmul(m.rr, sub_nr(V, r.X)), fpmul(p.Y, HHH));
+  if constexpr (FUSED) r.Y = fpmul2(m.rr, sub_nr(V, r.X), neg_nr(p.Y), HHH);
+  else r.Y = sub(fpmul(m.rr, sub_nr(V, r.X)), fpmul(p.Y, HHH));
   r.Z = fpmul(p.Z, m.H);
   return r;
 }
@@ -125,7 +132,7 @@ BP_COLD void jac_madd_full(Jac *out, const Jac *pp, const Aff *qq) {
     *out = jac_inf();
     return;
   }
-  *out = jac_madd_tail(p, m);
+  *out = jac_madd_tail<false>(p, m);
 }
 // Identity operands are resolved by SELECTS after the (then meaningless, but harmless) arithmetic: branch-free, and
 // measured equal to an early return (the addition is bound by its 981 v_mad_i64_i32).
@@ -138,7 +145,7 @@ BP_HD Jac jac_select(bool c, const Jac &a, const Jac &b) {
 BP_HD Jac jac_madd(const Jac &p, const Aff &q) {
   MaddMid m = jac_madd_mid(p, q);
   if (fp_maybe_zero(m.H)) { Jac pc = jac_hide(p), r; Aff qc = aff_hide(q); jac_madd_full(&r, &pc, &qc); return jac_hide(r); }
-  Jac r = jac_madd_tail(p, m);
+  Jac r = jac_madd_tail<true>(p, m);
   Jac qj; qj.X = q.x; qj.Y = q.y; qj.Z = fe_one<FP>();
   r = jac_select(jac_is_inf(p), qj, r);
   return jac_select(aff_is_inf(q), p, r);
@@ -148,7 +155,7 @@ BP_HD Jac jac_madd(const Jac &p, const Aff &q) {
 BP_HD Jac jac_madd_nzq(const Jac &p, const Aff &q) {
   MaddMid m = jac_madd_mid(p, q);
   if (fp_maybe_zero(m.H)) { Jac pc = jac_hide(p), r; Aff qc = aff_hide(q); jac_madd_full(&r, &pc, &qc); return jac_hide(r); }
-  Jac r = jac_madd_tail(p, m);
+  Jac r = jac_madd_tail<true>(p, m);
   Jac qj; qj.X = q.x; qj.Y = q.y; qj.Z = fe_one<FP>();
   return jac_select(jac_is_inf(p), qj, r);
 }
@@ -187,11 +194,12 @@ BP_HD XMid xyzz_madd_mid(const Xyzz &p, const Aff &q) {
   m.R = sub_nr(fpmul(q.y, p.ZZZ), p.Y);
   return m;
 }
-BP_HD Xyzz xyzz_madd_tail(const Xyzz &p, const XMid &m) {
+template <bool FUSED> BP_HD Xyzz xyzz_madd_tail(const Xyzz &p, const XMid &m) {
   Fp PP = fpsqr(m.P), PPP = fpmul(m.P, PP), Q = fpmul(p.X, PP);
   Xyzz r;
   r.X = norm(sub_nr(sub_nr(sub_nr(fpsqr(m.R), PPP), Q), Q));
-  r.Y = sub(fpmul(m.R, sub_nr(Q, r.X)), fpmul(p.Y, PPP));
+  if constexpr (FUSED) r.Y = fpmul2(m.R, sub_nr(Q, r.X), neg_nr(p.Y), PPP);   // R (Q - X3) + (-Y1) PPP, one reduction (jac_madd_tail)
+  else r.Y = sub(fpmul(m.R, sub_nr(Q, r.X)), fpmul(p.Y, PPP));
   r.ZZ = fpmul(p.ZZ, PP);
   r.ZZZ = fpmul(p.ZZZ, PPP);
   return r;
@@ -208,7 +216,7 @@ BP_COLD void xyzz_madd_full(Xyzz *out, const Xyzz *pp, const Aff *qq) {
     *out = xyzz_inf();
     return;
   }
-  *out = xyzz_madd_tail(p, m);
+  *out = xyzz_madd_tail<false>(p, m);
 }
 BP_HD Xyzz xyzz_select(bool c, const Xyzz &a, const Xyzz &b) {
   Xyzz r;
@@ -223,7 +231,7 @@ BP_HD Xyzz xyzz_select(bool c, const Xyzz &a, const Xyzz &b) {
 BP_HD Xyzz xyzz_madd_nzq(const Xyzz &p, const Aff &q) {
   XMid m = xyzz_madd_mid(p, q);
   if (fp_maybe_zero(m.P)) { Xyzz pc = xyzz_hide(p), r; Aff qc = aff_hide(q); xyzz_madd_full(&r, &pc, &qc); return xyzz_hide(r); }
-  Xyzz r = xyzz_madd_tail(p, m);
+  Xyzz r = xyzz_madd_tail<true>(p, m);
   Xyzz qe; qe.X = q.x; qe.Y = q.y; qe.ZZ = fe_one<FP>(); qe.ZZZ = fe_one<FP>();
   return xyzz_select(xyzz_is_inf(p), qe, r);
 }
@@ -245,11 +253,12 @@ BP_HD AddMid jac_add_mid(const Jac &p, const Jac &q) {
   m.rr = sub_nr(S2, m.S1);
   return m;
 }
-BP_HD Jac jac_add_tail(const Jac &p, const Jac &q, const AddMid &m) {
+template <bool FUSED> BP_HD Jac jac_add_tail(const Jac &p, const Jac &q, const AddMid &m) {
   Fp HH = fpsqr(m.H), HHH = fpmul(m.H, HH), V = fpmul(m.U1, HH);
   Jac r;
   r.X = norm(sub_nr(sub_nr(sub_nr(fpsqr(m.rr), HHH), V), V));
-  r.Y = sub(fpmul(m.rr, sub_nr(V, r.X)), fpmul(m.S1, HHH));
+  if constexpr (FUSED) r.Y = fpmul2(m.rr, sub_nr(V, r.X), neg_nr(m.S1), HHH);   // one reduction for both products (jac_madd_tail)
+  else r.Y = sub(fpmul(m.rr, sub_nr(V, r.X)), fpmul(m.S1, HHH));
   r.Z = fpmul(fpmul(p.Z, q.Z), m.H);
   return r;
 }
@@ -263,12 +272,12 @@ BP_COLD void jac_add_full(Jac *out, const Jac *pp, const Jac *qq) {
     *out = jac_inf();
     return;
   }
-  *out = jac_add_tail(p, q, m);
+  *out = jac_add_tail<false>(p, q, m);
 }
 BP_HD Jac jac_add(const Jac &p, const Jac &q) {
   AddMid m = jac_add_mid(p, q);
   if (fp_maybe_zero(m.H)) { Jac pc = jac_hide(p), qc = jac_hide(q), r; jac_add_full(&r, &pc, &qc); return jac_hide(r); }
-  Jac r = jac_add_tail(p, q, m);
+  Jac r = jac_add_tail<true>(p, q, m);
   r = jac_select(jac_is_inf(p), q, r);
   return jac_select(jac_is_inf(q), p, r);
 }

@@ -15,6 +15,13 @@
 // Representation invariants ("T" = tight): lower limbs in [0, 2^29), top limb small signed.
 // "T'" (after norm()): lower limbs in [-8, 2^29 + 8).  mul/sqr accept T' x T' and limbs up to
 // 1.5 * 2^29 against T'; they return T.  Values: every mul input must satisfy |v| < 2^256.
+// mul2(a, b, c, d) = (a*b + c*d) / R (F_p, one reduction for both products) is narrower: ALL FOUR operands must have
+// lower limbs of magnitude <= 2^29 + 8 -- T, T' and the un-normalised differences sub_nr(product, tight) and
+// sub_nr(T, T') of either sign, or any of these negated limb by limb; the 1.5 * 2^29 allowance of mul does NOT carry
+// over.  A column then holds at most 18 products, |sum| <= 18 * (2^29 + 8)^2 < 2^62.17; the two reduction terms add
+// less than 2^29 * (17 * 2^18 + 2^19) < 2^51.2 and the carry of the column before it less than 2^63 / 2^29 = 2^34: the
+// signed 64-bit accumulator keeps 0.8 bit to spare.  With |v| < 2^256 on every operand the value (ab + cd)/R - (0..p)
+// lies in (-2^252 - p, 2^252): inside what every product accepts.  The output is T (no norm needed), like mul's.
 //
 // Replaces (device side) mpc-stark's Scalar / base-field arithmetic used at the call sites listed in
 // SURVEY.md K1-K10; parity is established against oracle/ (tests/).
@@ -90,6 +97,13 @@ template <class F> BP_HD Fe<F> neg(const Fe<F> &a) {
 #pragma unroll
   for (int j = 0; j < NL; j++) r.v[j] = -a.v[j];
   return norm(r);
+}
+// -a limb by limb, no carry pass: an operand of mul2 (magnitudes unchanged)
+template <class F> BP_HD Fe<F> neg_nr(const Fe<F> &a) {
+  Fe<F> r;
+#pragma unroll
+  for (int j = 0; j < NL; j++) r.v[j] = -a.v[j];
+  return r;
 }
 // k * a for small k (|k| <= 16), through int64 so that tight limbs cannot overflow int32
 template <int K, class F> BP_HD Fe<F> mul_small(const Fe<F> &a) {
@@ -381,6 +395,45 @@ template <class F> BP_HD Fe<F> sqr(const Fe<F> &a) {
   if constexpr (F::sparse) return sqr_cols(a);
   else return sqr_rows(a);
 #endif
+}
+
+// (a * b + c * d) / R with ONE reduction and one carry pass (F_p): column k holds the terms of both products, the a*b terms in one
+// chain and the c*d terms with the two reduction terms in a second (9 + 2 = 11 at the most), 162 + 18 MADs against 2 * 99 and a
+// subtraction with its carry pass for two products reduced on their own.  A difference a*b - c*d takes one operand negated limb
+// by limb (no norm).  See the header for the operand contract and the column bound.
+BP_HD Fp mul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) {
+  int32_t m[NL];
+  Fp r;
+  int64_t acc = 0;
+  fence();
+#pragma unroll
+  for (int k = 0; k < 2 * NL - 1; k++) {
+    const int j0 = k >= NL ? k - NL + 1 : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    int32_t x[11], y[11];
+    int n = 0;
+#pragma unroll
+    for (int j = j0; j <= k && j < NL; j++) { x[n] = a.v[j]; y[n] = b.v[k - j]; n++; }
+    madchain(acc, n, x, y);
+    n = 0;
+#pragma unroll
+    for (int j = j0; j <= k && j < NL; j++) { x[n] = c.v[j]; y[n] = d.v[k - j]; n++; }
+    if (k >= 6 && k - 6 < NL) { x[n] = m[k - 6]; y[n] = -4456448; n++; }   // -p[6] = -(17 << 18)
+    if (k >= 8 && k - 8 < NL) { x[n] = m[k - 8]; y[n] = -524288; n++; }    // -p[8] = -(1 << 19)
+    madchain(acc, n, x, y);
+#else
+    for (int j = j0; j <= k && j < NL; j++) acc += (int64_t)a.v[j] * (int64_t)b.v[k - j];
+    for (int j = j0; j <= k && j < NL; j++) acc += (int64_t)c.v[j] * (int64_t)d.v[k - j];
+    if (k >= 6 && k - 6 < NL) acc += (int64_t)m[k - 6] * (int64_t)(-4456448);
+    if (k >= 8 && k - 8 < NL) acc += (int64_t)m[k - 8] * (int64_t)(-524288);
+#endif
+    if (k < NL) m[k] = (int32_t)((uint32_t)acc & (uint32_t)LMASK);
+    else r.v[k - NL] = (int32_t)((uint32_t)acc & (uint32_t)LMASK);
+    acc >>= LB;
+  }
+  r.v[NL - 1] = (int32_t)acc;
+  fence();
+  return r;
 }
 
 // unique representative in [0, m): all limbs in [0, 2^29).  Accepts |value| < 16m.
