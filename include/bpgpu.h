@@ -77,8 +77,9 @@ int bpgpu_set_latency_mode(bpgpu_ctx *ctx, int on);
 #define BPGPU_OPT_GROUPS_FORM 18           /* first Horner stage: 0 = by mode, 1 = a lane, 2 = a DPP quad, 3 = a whole wave per group of 8 windows */
 #define BPGPU_OPT_FIXED_CHUNK_GENS 19      /* generator half of the verification's back launch: 0 = by mode, -1 = FIXED_LPM lanes per proof and a butterfly; g in 1..64 = a proof
                                             * per lane, g generators per wave, the partial sums added in the verdict launch */
-#define BPGPU_OPT_WITNESS_ROUTE 20         /* witness synthesis (bpgpu_r1cs_witness_synthesize, bpgpu_r1cs_prove_fs2): 0 = by bpgpu_witness_plan, 1 = a lane per prover, 2 = a block per prover */
-#define BPGPU_OPT_COUNT 21
+#define BPGPU_OPT_WITNESS_ROUTE 20         /* witness synthesis (bpgpu_r1cs_witness_synthesize, bpgpu_r1cs_prove_fs2): 0 = by bpgpu_witness_plan and BPGPU_OPT_WITNESS_SCAN_MIN, 1 = a lane per prover, 2 = a block per prover */
+#define BPGPU_OPT_WITNESS_SCAN_MIN 21      /* under WITNESS_ROUTE 0, a phase whose longest product chain has this many members or more takes the scan form (default 16; 0 = never; up to 2^25) */
+#define BPGPU_OPT_COUNT 22
 int bpgpu_set_option(bpgpu_ctx *ctx, int option, int64_t value);
 int bpgpu_get_option(bpgpu_ctx *ctx, int option, int64_t *value);
 /* synchronise and report whether an operand of the `_dev` (device-resident, asynchronous) calls issued since the last read -- or
@@ -563,12 +564,29 @@ int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c,
  * requires an empty one, row pointers that decrease, a non-canonical coefficient, n1 > n, nchi > 8.  BPGPU_E_LEN: n or m above 2^25 - 1.
  * It also computes the dependency levels, per phase: a gate's level is 0 if it is an INPUT or its rows read no multiplier of its
  * own phase, else 1 + the largest level it reads; the gates of a phase are stored sorted by level.
- * Two launch forms evaluate a phase, one launch each (csrc/k_witness.hip): a LANE per prover walks the gates in program order; a
- * BLOCK per prover walks the levels, a level's gates strided over 256 threads and a row of more than 64 terms summed by a wave.
+ * Three launch forms evaluate a phase, one launch each (csrc/k_witness.hip): a LANE per prover walks the gates in program order; a
+ * BLOCK per prover walks the levels, a level's gates strided over 256 threads and a row of more than 64 terms summed by a wave; the
+ * SCAN form is the block form over compressed levels, with every product chain evaluated as a prefix product.
+ * A product chain is recognised from the program's shape alone.  Gate i of a phase is a MEMBER with predecessor j when it is a
+ * BPGPU_GATE_MUL, one of its rows (the left is tried first) is the LINK row -- exactly one stored term over all 1 + nchi blocks (an
+ * explicit zero coefficient is a term), of kind 2 on a gate j of the same phase that has no member successor yet (of two gates linking
+ * to one a_O the first in program order is the member) -- and the other, FREE row has no term of kind 0..2 on a gate of the same
+ * phase.  A gate with a successor and no predecessor is the chain's HEAD (any op, any rows).  Along a chain a_O is a prefix product of
+ * factors that read nothing of their phase, and F_n multiplication is exactly associative on canonical values: a 256-thread block
+ * scans all chains headed at one level together (segmented, no inversion: a zero factor zeroes the rest of its chain) in about
+ * 2 ceil(M / 256) + 10 dependent multiplications for M members, and stores the bytes the gates one by one give.  In the compressed
+ * levels a member takes its predecessor's level.  bpgpu_witness_chains reports the chains.  Only chains of pure products stop being
+ * serial: a general dependent chain such as (a_O[i - 1] + v) w is still serial, one level per gate.
  * The route is a function of the program's shape and nb alone, never of the data: bpgpu_witness_plan (no device needed) reports
- * what the library takes: the block form where a level holds two gates or more on average, for up to 1024 provers (measured:
- * profiles/witness_synth.log, DESIGN.md "Witness synthesis"); above that the width asked for grows with nb / 1024, which is an
- * extrapolation and UNMEASURED.  BPGPU_OPT_WITNESS_ROUTE forces a form; results never depend on it. */
+ * what the library takes.  A phase whose longest chain has BPGPU_OPT_WITNESS_SCAN_MIN members or more takes the scan form: the
+ * default, 16, is the smallest power of two >= 16 from which on the scan form's slowest step lay below the block form's fastest for 1
+ * and for 256 provers (profiles/witness_synth.log, chains of 8 .. 16 382 members; at 16 members 0.053 against 0.200 ms and 0.058
+ * against 0.222 ms), and 4096 provers of the 64-shuffle (62 members) take 0.273 ms scanned, 1.273 ms on lanes, 3.217 ms in blocks;
+ * shorter chains above 256 provers, and any chain above 4096 provers, are UNMEASURED.  Otherwise: the block form where a level
+ * holds two gates or more on average, for up to 1024 provers (measured: the same log, DESIGN.md "Witness synthesis"); above that
+ * the width asked for grows with nb / 1024, which is an extrapolation and UNMEASURED.  BPGPU_OPT_WITNESS_ROUTE 1 or 2 forces a form
+ * (the scan form cannot be forced, only enabled: BPGPU_OPT_WITNESS_SCAN_MIN 1 scans every chain, 0 none; the environment seeds of a
+ * new context are BPGPU_WITNESS_ROUTE and BPGPU_WITNESS_SCAN_MIN); results never depend on either. */
 typedef struct bpgpu_witness bpgpu_witness;
 #define BPGPU_GATE_MUL 0
 #define BPGPU_GATE_INPUT 1
@@ -581,11 +599,25 @@ void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w);
 #define BPGPU_WIT_PLAN_WIDEST 2       /* gates of the widest level of either phase */
 #define BPGPU_WIT_PLAN_LONG_ROWS 3    /* rows of more than 64 terms (a wave's in the block form) */
 #define BPGPU_WIT_PLAN_INPUTS 4       /* INPUT gates: pairs of `inputs` per prover */
-#define BPGPU_WIT_PLAN_ROUTE1 5       /* launch form of phase 1: 1 = a lane per prover, 2 = a block per prover; 0: no gates */
+#define BPGPU_WIT_PLAN_ROUTE1 5       /* launch form of phase 1: 1 = a lane per prover, 2 = a block per prover, 3 = a block per prover with
+                                       * the product chains scanned (at the default BPGPU_OPT_WITNESS_SCAN_MIN); 0: no gates */
 #define BPGPU_WIT_PLAN_ROUTE2 6       /* ... of phase 2 */
 #define BPGPU_WIT_PLAN_FIELDS 7
 int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
                        const uint32_t *idx, size_t nb, int32_t out[BPGPU_WIT_PLAN_FIELDS]);
+/* The product chains of a gate program, from its shape alone (no device needed): per phase the number of chains, of their members, the
+ * members of the longest one and the COMPRESSED levels the scan form walks.  Refusals: those of bpgpu_witness_plan. */
+#define BPGPU_WIT_CHAIN_CHAINS1 0
+#define BPGPU_WIT_CHAIN_CHAINS2 1
+#define BPGPU_WIT_CHAIN_MEMBERS1 2
+#define BPGPU_WIT_CHAIN_MEMBERS2 3
+#define BPGPU_WIT_CHAIN_LONGEST1 4
+#define BPGPU_WIT_CHAIN_LONGEST2 5
+#define BPGPU_WIT_CHAIN_LEVELS1 6
+#define BPGPU_WIT_CHAIN_LEVELS2 7
+#define BPGPU_WIT_CHAIN_FIELDS 8
+int bpgpu_witness_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                         const uint32_t *idx, int32_t out[BPGPU_WIT_CHAIN_FIELDS]);
 /* The witnesses of nb provers of one gate program, where the provers read them.
  *   v                  nb x m          the committed values, ark form: the buffer bpgpu_r1cs_commit_values and
  *                                      bpgpu_r1cs_constraints_satisfied take; may be NULL when m == 0
@@ -601,12 +633,13 @@ int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, cons
  * alone is evaluated, for challenges missing where a parametric program's phase 2 is, for a phase other than 0, 1, 2; nb == 0: BPGPU_OK,
  * nothing touched.  A non-canonical limb gives BPGPU_E_ARG in the host form and raises bpgpu_input_flag in the `_dev` form (every
  * operand a device pointer; asynchronous on the context's stream).  A failed call leaves no pool memory behind.  Profiling: kind 22.
- * A gate chain is serial, and a dependent gate costs the device about 10 us (a store, a load and a few dozen dependent
- * multiplications of one lane): ONE prover's k = 2^14 shuffle, two chains of 16 383 gates, takes 171 ms here (profiles/
- * witness_synth.log) where even an interpreted host evaluates it in 61 ms, and one 2^10-shuffle prover is proved faster by
- * bpgpu_r1cs_prove_fs2_begin / _finish around a host gadget than by bpgpu_r1cs_prove_fs2.  The calls pay off for batches: 256 provers
- * of the 64-shuffle in 0.74 ms, of 16 x 64-bit range values in 0.07 ms.  A caller with few provers and long chains keeps its host's
- * Prover::multiply.
+ * A dependent gate costs the device about 10 us (a store, a load and a few dozen dependent multiplications of one lane), but a chain
+ * of pure products is no longer serial: ONE prover's k = 2^14 shuffle, two chains of 16 382 members, takes 1.470 ms scanned
+ * (profiles/witness_synth.log) where the block form takes 186 ms and an interpreted host 54 ms, and one 2^10-shuffle prover is proved
+ * by bpgpu_r1cs_prove_fs2 in 4.7 ms against 10.1 ms for bpgpu_r1cs_prove_fs2_begin / _finish around that host's gadget.  Batches: 256
+ * provers of the 64-shuffle in 0.057 ms, of 16 x 64-bit range values in 0.07 ms.  What is still serial is a general dependent chain
+ * (each gate adding to or otherwise mixing the gate before it): a caller with few provers and long chains of THAT kind keeps its
+ * host's Prover::multiply.
  * Out of scope: the host mirror (mpc_bulletproof.hpp: its multiply keeps evaluating on the host), the pool forms (bpgpu_pool_*),
  * the two-party prover (a product of shares is a Beaver step, not a local product) and bench.py. */
 int bpgpu_r1cs_witness_synthesize(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const uint8_t *v, const uint8_t *inputs,

@@ -439,6 +439,7 @@ static bool opt_valid(int option, int64_t value) {
     case BPGPU_OPT_GROUPS_FORM: return value >= 0 && value <= 3;
     case BPGPU_OPT_FIXED_CHUNK_GENS: return value >= -1 && value <= 64;
     case BPGPU_OPT_WITNESS_ROUTE: return value >= 0 && value <= 2;
+    case BPGPU_OPT_WITNESS_SCAN_MIN: return value >= 0 && value <= ((int64_t)1 << 25);            // 0 = never
     default: return value == 0 || value == 1;
   }
 }
@@ -468,7 +469,7 @@ static int ctx_create(int device, bool single, bpgpu_ctx **out) {
         {BPGPU_OPT_HORNER_ROW_MAX, "BPGPU_HORNER_ROW_MAX", 1536},     {BPGPU_OPT_PIPPENGER_MIN, "BPGPU_PIPPENGER_MIN", 512},
         {BPGPU_OPT_IPP_PIPPENGER_MIN, "BPGPU_IPP_PIPPENGER_MIN", 257}, {BPGPU_OPT_FIXED_LPM, "BPGPU_FIXED_LPM", 0},
         {BPGPU_OPT_GROUPS_FORM, "BPGPU_GROUPS_FORM", 0}, {BPGPU_OPT_FIXED_CHUNK_GENS, "BPGPU_FIXED_CHUNK_GENS", 0},
-        {BPGPU_OPT_WITNESS_ROUTE, "BPGPU_WITNESS_ROUTE", 0}};
+        {BPGPU_OPT_WITNESS_ROUTE, "BPGPU_WITNESS_ROUTE", 0}, {BPGPU_OPT_WITNESS_SCAN_MIN, "BPGPU_WITNESS_SCAN_MIN", WIT_SCAN_MIN_DEFAULT}};
     // the environment only SEEDS a new context's options, through the same validation as bpgpu_set_option: a value that the
     // setter would refuse (a batch size of 0, a negative lane count, ...) leaves the default in force
     for (auto &s : seed) {
@@ -4320,7 +4321,7 @@ int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view) {
     ctx->mu.unlock();
     return BPGPU_E_DEVICE;
   }
-  *view = {ctx->st, ctx->d_flag, ctx->opt[BPGPU_OPT_WITNESS_ROUTE], ctx->shard_world};
+  *view = {ctx->st, ctx->d_flag, ctx->opt[BPGPU_OPT_WITNESS_ROUTE], ctx->opt[BPGPU_OPT_WITNESS_SCAN_MIN], ctx->shard_world};
   return BPGPU_OK;
 }
 void bpgpu_internal_leave(bpgpu_ctx *ctx) { ctx->mu.unlock(); }

@@ -20,6 +20,7 @@ static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT &
 struct bpgpu_witness {
   size_t n = 0, n1 = 0, m = 0, nchi = 0, ninp = 0;
   uint32_t levels[2] = {0, 0};
+  uint32_t scan_levels[2] = {0, 0}, longest[2] = {0, 0};   // the compressed levels and the longest product chain of each phase
   void *mem = nullptr;          // one device allocation: everything dev points to
   WitDev dev{};
 };
@@ -40,13 +41,46 @@ int wit_route(size_t gates, uint32_t levels, size_t nb) {
   return gates >= WIT_BLOCK_MIN_WIDTH * (rounds ? rounds : 1) * levels ? 2 : 1;
 }
 
+// The scan form (bpgpu.h "product chains"): from how many members of a phase's longest chain it is taken when nothing is forced.
+// WIT_SCAN_MIN_DEFAULT (bpgpu_internal.h) is read from the sweep of profiles/witness_synth.log.
+int wit_route_scan(size_t gates, uint32_t levels, uint32_t longest, size_t nb, int64_t scan_min) {
+  if (gates && scan_min > 0 && (int64_t)longest >= scan_min) return 3;
+  return wit_route(gates, levels, nb);
+}
+
+constexpr uint32_t WIT_NONE = 0xFFFFFFFFu;
 struct WitShape {
   std::vector<uint32_t> level;    // per gate, within its phase
   std::vector<uint32_t> row_len;  // per row 2 i, 2 i + 1: the terms of all 1 + nchi blocks
   uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0;
   size_t nnz = 0;
+  // product chains: a member's predecessor (WIT_NONE: an ordinary gate), the side of its link row, a gate's member successor, and
+  // the compressed levels, in which a member takes its predecessor's
+  std::vector<uint32_t> pred, succ, scan_level;
+  std::vector<uint8_t> link_right;
+  uint32_t scan_levels[2] = {0, 0}, chains[2] = {0, 0}, members[2] = {0, 0}, longest[2] = {0, 0};
 };
-// what bpgpu_witness_plan and bpgpu_witness_create share: the checks that make the levels well defined, and the levels
+// Is row `side` of gate i a link row -- one stored term over all blocks, of kind 2, on a gate of the phase that has no member
+// successor yet -- and the other row free of the phase's multipliers?  -> the gate linked to, or WIT_NONE
+uint32_t wit_link_of(size_t i, size_t side, size_t phase_lo, size_t n, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
+                     const uint32_t *idx, const WitShape &s) {
+  if (s.row_len[2 * i + side] != 1) return WIT_NONE;
+  const size_t rows = 2 * n;
+  uint32_t j = WIT_NONE;
+  for (size_t b = 0; b <= nchi; b++) {
+    const size_t r = b * rows + 2 * i + side, f = b * rows + 2 * i + (1 - side);
+    if (row_ptr[r + 1] > row_ptr[r]) {
+      const uint32_t t = row_ptr[r];
+      if (kind[t] != 2 || idx[t] < phase_lo) return WIT_NONE;
+      j = idx[t];
+    }
+    for (uint32_t t = row_ptr[f]; t < row_ptr[f + 1]; t++)
+      if (kind[t] <= 2 && idx[t] >= phase_lo) return WIT_NONE;
+  }
+  return j != WIT_NONE && s.succ[j] == WIT_NONE ? j : WIT_NONE;
+}
+// what bpgpu_witness_plan, bpgpu_witness_chains and bpgpu_witness_create share: the checks that make the levels well defined, the
+// levels, and the product chains with the compressed levels (both from the shape alone: no coefficient is read)
 int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
                 WitShape *s) {
   if (!row_ptr || (n && !op) || n1 > n || nchi > 8) return BPGPU_E_ARG;
@@ -58,12 +92,16 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
   if (s->nnz && (!kind || !idx)) return BPGPU_E_ARG;
   s->level.assign(n, 0);
   s->row_len.assign(rows, 0);
-  std::vector<uint32_t> width;
+  s->pred.assign(n, WIT_NONE);
+  s->succ.assign(n, WIT_NONE);
+  s->scan_level.assign(n, 0);
+  s->link_right.assign(n, 0);
+  std::vector<uint32_t> width, length(n, 0);   // length: of a head, the members of its chain; of a member, its head
   for (size_t i = 0; i < n; i++) {
     if (op[i] > BPGPU_GATE_BIT) return BPGPU_E_ARG;
     if (op[i] == BPGPU_GATE_INPUT) s->ninp++;
     const size_t phase_lo = i < n1 ? 0 : n1;
-    uint32_t lvl = 0;
+    uint32_t lvl = 0, slvl = 0;
     for (size_t side = 0; side < 2; side++)
       for (size_t j = 0; j <= nchi; j++) {
         const size_t r = j * rows + 2 * i + side;
@@ -72,10 +110,29 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
           if (kind[t] > 4) return BPGPU_E_ARG;
           if (kind[t] > 2) continue;
           if (idx[t] >= i) return BPGPU_E_ARG;            // a self or forward reference
-          if (idx[t] >= phase_lo && op[i] != BPGPU_GATE_INPUT) lvl = std::max(lvl, s->level[idx[t]] + 1);
+          if (idx[t] >= phase_lo && op[i] != BPGPU_GATE_INPUT) {
+            lvl = std::max(lvl, s->level[idx[t]] + 1);
+            slvl = std::max(slvl, s->scan_level[idx[t]] + 1);
+          }
         }
       }
     s->level[i] = lvl;
+    const int ph = i < n1 ? 0 : 1;
+    for (size_t side = 0; side < 2 && op[i] == BPGPU_GATE_MUL && s->pred[i] == WIT_NONE; side++) {     // the left row first
+      const uint32_t j = wit_link_of(i, side, phase_lo, n, nchi, row_ptr, kind, idx, *s);
+      if (j == WIT_NONE) continue;
+      s->pred[i] = j;
+      s->succ[j] = (uint32_t)i;
+      s->link_right[i] = (uint8_t)side;
+      const uint32_t head = s->pred[j] == WIT_NONE ? j : length[j];
+      length[i] = head;
+      if (head == j) s->chains[ph]++;
+      s->members[ph]++;
+      s->longest[ph] = std::max(s->longest[ph], ++length[head]);
+      slvl = s->scan_level[j];
+    }
+    s->scan_level[i] = slvl;
+    s->scan_levels[ph] = std::max(s->scan_levels[ph], slvl + 1);
     if (i == n1) width.clear();
     if (width.size() <= lvl) width.resize(lvl + 1, 0);
     s->widest = std::max(s->widest, ++width[lvl]);
@@ -142,10 +199,13 @@ int wit_begin(const Entered &e, const bpgpu_witness *w, size_t nb, const void *v
 // one launch: the gates of phase ph (1 or 2) on the run's planes; chi: nb x nchi plain words, or nullptr for phase 1
 void wit_phase(const Entered &e, const bpgpu_witness *w, size_t nb, int ph, const WitRun &run, const Words8 *chi) {
   const uint32_t n1 = (uint32_t)w->n1, n = (uint32_t)w->n;
-  const uint32_t g_lo = ph == 1 ? 0 : n1, g_hi = ph == 1 ? n1 : n, l_lo = ph == 1 ? 0 : w->levels[0], l_hi = l_lo + w->levels[ph - 1];
-  const int route = e.view.witness_route ? (int)e.view.witness_route : wit_route(g_hi - g_lo, w->levels[ph - 1], nb);
+  const uint32_t g_lo = ph == 1 ? 0 : n1, g_hi = ph == 1 ? n1 : n;
+  const int route = e.view.witness_route ? (int)e.view.witness_route
+                                         : wit_route_scan(g_hi - g_lo, w->levels[ph - 1], w->longest[ph - 1], nb, e.view.witness_scan_min);
+  const uint32_t *levels = route == 3 ? w->scan_levels : w->levels;       // the scan form walks the compressed levels
+  const uint32_t l_lo = ph == 1 ? 0 : levels[0];
   Prof22 prof(e.ctx);
-  witness_eval(e.view.st, w->dev, nb, route == 2, g_lo, g_hi, l_lo, l_hi, run.L, run.R, run.O, run.v, run.in, chi);
+  witness_eval(e.view.st, w->dev, nb, route, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
 }
 // the gates [lo, lo + count) of every prover, out of the run's planes into ark planes of `stride` scalars per prover
 void wit_export(const Entered &e, const bpgpu_witness *w, size_t nb, const WitRun &run, size_t lo, size_t count, void *aL, void *aR, void *aO,
@@ -285,8 +345,23 @@ int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, cons
     out[BPGPU_WIT_PLAN_WIDEST] = (int32_t)s.widest;
     out[BPGPU_WIT_PLAN_LONG_ROWS] = (int32_t)s.nlong;
     out[BPGPU_WIT_PLAN_INPUTS] = (int32_t)s.ninp;
-    out[BPGPU_WIT_PLAN_ROUTE1] = wit_route(n1, s.levels[0], nb);
-    out[BPGPU_WIT_PLAN_ROUTE2] = wit_route(n - n1, s.levels[1], nb);
+    out[BPGPU_WIT_PLAN_ROUTE1] = wit_route_scan(n1, s.levels[0], s.longest[0], nb, WIT_SCAN_MIN_DEFAULT);
+    out[BPGPU_WIT_PLAN_ROUTE2] = wit_route_scan(n - n1, s.levels[1], s.longest[1], nb, WIT_SCAN_MIN_DEFAULT);
+    return BPGPU_OK;
+  });
+}
+int bpgpu_witness_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                         const uint32_t *idx, int32_t out[BPGPU_WIT_CHAIN_FIELDS]) {
+  return no_throw([&]() -> int {
+    if (!out) return BPGPU_E_ARG;
+    WitShape s;
+    WCK(wit_analyse(n, n1, nchi, op, row_ptr, kind, idx, &s));
+    for (int ph = 0; ph < 2; ph++) {
+      out[BPGPU_WIT_CHAIN_CHAINS1 + ph] = (int32_t)s.chains[ph];
+      out[BPGPU_WIT_CHAIN_MEMBERS1 + ph] = (int32_t)s.members[ph];
+      out[BPGPU_WIT_CHAIN_LONGEST1 + ph] = (int32_t)s.longest[ph];
+      out[BPGPU_WIT_CHAIN_LEVELS1 + ph] = (int32_t)s.scan_levels[ph];
+    }
     return BPGPU_OK;
   });
 }
@@ -314,10 +389,14 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
           if (kind[t] == 3 && idx[t] >= m) return BPGPU_E_ARG;
       }
     }
-    // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op], every part 256-byte aligned
+    // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op | scan_order | scan_ptr |
+    // scan_long | chain_elem | chain_ptr], every part 256-byte aligned
+    const size_t nslev = (size_t)s.scan_levels[0] + s.scan_levels[1];
     const size_t o_rp = up256((nnz ? nnz : 1) * 32), o_var = o_rp + up256((rows + 1) * 4), o_arg = o_var + up256((nnz ? nnz : 1) * 4),
                  o_ord = o_arg + up256((n ? n : 1) * 4), o_lp = o_ord + up256((n ? n : 1) * 4), o_ll = o_lp + up256((nlev + 1) * 4),
-                 o_op = o_ll + up256((nlev ? nlev : 1) * 4), total = o_op + up256(n ? n : 1);
+                 o_op = o_ll + up256((nlev ? nlev : 1) * 4), o_so = o_op + up256(n ? n : 1), o_sp = o_so + up256((n ? n : 1) * 4),
+                 o_sl = o_sp + up256((nslev + 1) * 4), o_ce = o_sl + up256((nslev ? nslev : 1) * 4), o_cp = o_ce + up256((n ? n : 1) * 4),
+                 total = o_cp + up256((nslev + 1) * 4);
     std::vector<uint8_t> img(total, 0);
     Words8 *h_coeff = (Words8 *)img.data();
     uint32_t *h_rp = (uint32_t *)(img.data() + o_rp), *h_var = (uint32_t *)(img.data() + o_var), *h_arg = (uint32_t *)(img.data() + o_arg),
@@ -357,10 +436,39 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       lvl_base += s.levels[ph];
     }
     h_lp[nlev] = at;
+    // the same over the compressed levels, members apart: a level's ordinary gates (short rows, then long), and the members of the
+    // chains it heads, chain after chain (heads in program order), each chain from its first member on
+    uint32_t *h_so = (uint32_t *)(img.data() + o_so), *h_sp = (uint32_t *)(img.data() + o_sp), *h_sl = (uint32_t *)(img.data() + o_sl),
+             *h_ce = (uint32_t *)(img.data() + o_ce), *h_cp = (uint32_t *)(img.data() + o_cp);
+    std::vector<uint32_t> fill(3 * nslev + 1, 0);          // per compressed level: short, long, members -> where each list starts
+    const auto slot = [&](size_t i) {
+      const size_t l = (i < n1 ? 0 : s.scan_levels[0]) + s.scan_level[i];
+      return 3 * l + (s.pred[i] != WIT_NONE ? 2 : (s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max ? 1 : 0));
+    };
+    for (size_t i = 0; i < n; i++) fill[slot(i) + 1]++;
+    uint32_t ord_at = 0, mem_at = 0;
+    for (size_t l = 0; l < nslev; l++) {
+      const uint32_t shorts = fill[3 * l + 1], longs = fill[3 * l + 2], mems = fill[3 * l + 3];
+      h_sp[l] = ord_at; h_sl[l] = ord_at + shorts; h_cp[l] = mem_at;
+      fill[3 * l] = ord_at; fill[3 * l + 1] = ord_at + shorts; fill[3 * l + 2] = mem_at;
+      ord_at += shorts + longs;
+      mem_at += mems;
+    }
+    h_sp[nslev] = ord_at; h_cp[nslev] = mem_at;
+    for (size_t i = 0; i < n; i++) {
+      if (s.pred[i] != WIT_NONE) continue;
+      const size_t k = slot(i);
+      h_so[fill[k]++] = (uint32_t)i;
+      if (s.succ[i] == WIT_NONE) continue;
+      uint32_t &m_at = fill[k - k % 3 + 2];                 // a head: its chain, whole, into its level's member list
+      for (uint32_t e = s.succ[i], first = WIT_ELEM_START; e != WIT_NONE; e = s.succ[e], first = 0)
+        h_ce[m_at++] = e | first | (s.link_right[e] ? WIT_ELEM_RIGHT : 0u);
+    }
     bpgpu_witness *w = new (std::nothrow) bpgpu_witness();
     if (!w) return BPGPU_E_OOM;
     w->n = n; w->n1 = n1; w->m = m; w->nchi = nchi; w->ninp = s.ninp;
     w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
+    for (int ph = 0; ph < 2; ph++) { w->scan_levels[ph] = s.scan_levels[ph]; w->longest[ph] = s.longest[ph]; }
     Entered e(ctx);
     int rc = e.enter();
     // (a plain allocation, not the context's pool: a program may outlive the context that made it, as a circuit may)
@@ -375,6 +483,11 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     w->dev.order = (const uint32_t *)(d + o_ord);
     w->dev.level_ptr = (const uint32_t *)(d + o_lp);
     w->dev.level_long = (const uint32_t *)(d + o_ll);
+    w->dev.scan_order = (const uint32_t *)(d + o_so);
+    w->dev.scan_ptr = (const uint32_t *)(d + o_sp);
+    w->dev.scan_long = (const uint32_t *)(d + o_sl);
+    w->dev.chain_elem = (const uint32_t *)(d + o_ce);
+    w->dev.chain_ptr = (const uint32_t *)(d + o_cp);
     w->dev.n = (uint32_t)n; w->dev.m = (uint32_t)m; w->dev.nchi = (uint32_t)nchi; w->dev.ninp = s.ninp;
     *out = w;
     return BPGPU_OK;

@@ -1,9 +1,9 @@
 // k_witness.hip -- witness synthesis: the gates of a bpgpu_witness program (Prover::multiply, prover.rs:99-125; allocate_multiplier,
-// :148-165) for nb provers, one launch per phase, in two forms.  The gate itself is wit_gate_values of witness_dev.cuh; the rows are
+// :148-165) for nb provers, one launch per phase, in three forms.  The gate itself is wit_gate_values of witness_dev.cuh; the rows are
 // eval_row's (fn_dev.cuh).  The planes a launch works on are the library's own scratch, plain canonical words: witness_convert takes
 // the callers' ark planes in and out, prover by prover, so that a phase can land in planes of its own stride.
 #include "fe29_consts.h"
-#include "witness_dev.cuh"
+#include "witness_scan.cuh"
 
 using namespace bp;
 
@@ -34,25 +34,88 @@ __global__ void __launch_bounds__(256) k_witness_lane(WitArgs a) {
 // those without a long row are strided over the 256 threads, the others over the four waves (lane-strided terms, then wave_sum, as
 // k_rows_eval does).  Between two levels the plane stores of the one are made visible to the block (they are global stores that
 // other waves of this block load: a block-scope fence, then the barrier).  Every thread of the block reaches every barrier: the
-// level range is the launch's, and no thread leaves early.
+// level range is the launch's, and no thread leaves early.  wit_level_gates: the gates order[lo .. mid) (short rows) and
+// order[mid .. hi) (a long row) of one level.
+__device__ __forceinline__ void wit_level_gates(const WitArgs &a, const WitProver &o, const uint32_t *order, uint32_t lo, uint32_t mid,
+                                                uint32_t hi) {
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (uint32_t t = lo + threadIdx.x; t < mid; t += 256) wit_gate_lane(a.w, order[t], o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
+  for (uint32_t t = mid + wave; t < hi; t += 4) {                                              // wave-uniform
+    const uint32_t i = order[t];
+    const uint32_t *rp = a.w.rows.row_ptr + 2 * (size_t)i;
+    const Fn one = fe_one<FN>();
+    const Fn left = wave_sum(fn_reduce(eval_row(a.w.rows, rp[0] + lane, rp[1], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
+    const Fn right = wave_sum(fn_reduce(eval_row(a.w.rows, rp[1] + lane, rp[2], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
+    if (lane == 0) {
+      const WitGate g = wit_gate_values(a.w.op[i], a.w.arg[i], left, right, o.inputs);
+      wit_store(o.aL + i, g.L);
+      wit_store(o.aR + i, g.R);
+      wit_store(o.aO + i, g.O);
+    }
+  }
+}
 __global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
   const WitProver o = wit_prover(a, blockIdx.x);
+  for (uint32_t l = a.l_lo; l < a.l_hi; l++) {
+    wit_level_gates(a, o, a.w.order, a.w.level_ptr[l], a.w.level_long[l], a.w.level_ptr[l + 1]);
+    if (l + 1 < a.l_hi) {
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+
+// A block per prover over the COMPRESSED levels (kernels.h WitDev): at each level (A) its ordinary gates as k_witness_block runs
+// them, heads of chains among them; a fence and a barrier; (B) the M members of all chains headed at this level as ONE segmented
+// inclusive prefix product (witness_scan.cuh).  Thread t owns the run [t R, (t + 1) R) of R = ceil(M / 256) elements: a local pass,
+// the scan of the 256 runs' parts -- within a wave by lane shuffles (Kogge-Stone, 6 steps), across the four waves through 4 parts in
+// LDS -- and a second pass that applies the carry: 2 R + 10 dependent multiplications where the gates one by one take M levels.
+// Barriers: M and the level range are the same for every thread of a launch, no thread returns early, and the shuffles run with all
+// 64 lanes active (a thread whose run is empty carries the identity).  The LDS parts of one level are read before that level's
+// closing barrier and written again only after it.
+__device__ __forceinline__ WitPart wit_part_shfl_up(const WitPart &x, uint32_t off) {
+  WitPart r;
+#pragma unroll
+  for (int j = 0; j < NL; j++) r.v.v[j] = __shfl_up(x.v.v[j], off, 64);
+  r.flag = __shfl_up(x.flag, off, 64);
+  return r;
+}
+__device__ __forceinline__ WitPart wit_part_select(bool take, const WitPart &x, const WitPart &y) {
+  WitPart r;
+#pragma unroll
+  for (int j = 0; j < NL; j++) r.v.v[j] = take ? x.v.v[j] : y.v.v[j];
+  r.flag = take ? x.flag : y.flag;
+  return r;
+}
+__global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
+  __shared__ int32_t s_part[4][NL + 1];
+  const WitProver o = wit_prover(a, blockIdx.x);
+  const WitPlanes pl{o.aL, o.aR, o.aO, o.v, o.chi};
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (uint32_t l = a.l_lo; l < a.l_hi; l++) {
-    const uint32_t lo = a.w.level_ptr[l], mid = a.w.level_long[l], hi = a.w.level_ptr[l + 1];
-    for (uint32_t t = lo + threadIdx.x; t < mid; t += 256) wit_gate_lane(a.w, a.w.order[t], o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
-    for (uint32_t t = mid + wave; t < hi; t += 4) {                                            // wave-uniform
-      const uint32_t i = a.w.order[t];
-      const uint32_t *rp = a.w.rows.row_ptr + 2 * (size_t)i;
-      const Fn one = fe_one<FN>();
-      const Fn left = wave_sum(fn_reduce(eval_row(a.w.rows, rp[0] + lane, rp[1], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
-      const Fn right = wave_sum(fn_reduce(eval_row(a.w.rows, rp[1] + lane, rp[2], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
-      if (lane == 0) {
-        const WitGate g = wit_gate_values(a.w.op[i], a.w.arg[i], left, right, o.inputs);
-        wit_store(o.aL + i, g.L);
-        wit_store(o.aR + i, g.R);
-        wit_store(o.aO + i, g.O);
+    wit_level_gates(a, o, a.w.scan_order, a.w.scan_ptr[l], a.w.scan_long[l], a.w.scan_ptr[l + 1]);
+    const uint32_t c_lo = a.w.chain_ptr[l], c_hi = a.w.chain_ptr[l + 1];                       // block-uniform
+    if (c_lo < c_hi) {
+      __threadfence_block();
+      __syncthreads();
+      const uint32_t run = (c_hi - c_lo + 255) / 256;
+      const uint32_t e_lo = min(c_lo + threadIdx.x * run, c_hi), e_hi = min(e_lo + run, c_hi);  // (M < 2^25: no wrap)
+      WitPart x = wit_scan_local(a.w, e_lo, e_hi, pl);
+#pragma unroll 1
+      for (uint32_t off = 1; off < 64; off <<= 1) {
+        const WitPart both = wit_part_combine(wit_part_shfl_up(x, off), x);
+        x = wit_part_select(lane >= off, both, x);
       }
+      if (lane == 63) {
+        raw_put(s_part[wave], x.v);
+        s_part[wave][NL] = (int32_t)x.flag;
+      }
+      const WitPart before = wit_part_select(lane != 0, wit_part_shfl_up(x, 1), wit_part_identity());   // this wave's lanes below
+      __syncthreads();
+      WitPart carry = wit_part_identity();
+      for (uint32_t k = 0; k < wave; k++) carry = wit_part_combine(carry, WitPart{raw_get(s_part[k]), (uint32_t)s_part[k][NL]});
+      carry = wit_part_combine(carry, before);
+      wit_scan_apply(a.w, e_lo, e_hi, carry.v, pl);
     }
     if (l + 1 < a.l_hi) {
       __threadfence_block();
@@ -60,11 +123,12 @@ __global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
     }
   }
 }
-void witness_eval(hipStream_t st, const WitDev &w, size_t nb, bool block, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
                   Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi) {
   if (!nb || g_lo >= g_hi) return;
   const WitArgs a{w, nb, g_lo, g_hi, l_lo, l_hi, aL, aR, aO, v, inputs, chi};
-  if (block) hipLaunchKernelGGL(k_witness_block, dim3((unsigned)nb), dim3(256), 0, st, a);
+  if (form == 3) hipLaunchKernelGGL(k_witness_scan, dim3((unsigned)nb), dim3(256), 0, st, a);
+  else if (form == 2) hipLaunchKernelGGL(k_witness_block, dim3((unsigned)nb), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_witness_lane, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, a);
 }
 

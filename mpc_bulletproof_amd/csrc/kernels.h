@@ -270,6 +270,13 @@ void csr_scan(hipStream_t st, uint32_t *cnt, size_t n1);
 // a BIT gate, the pair index of an INPUT gate).  The gates of phase ph are listed level by level in order[]: level l of the program
 // (phase 1's levels first) holds order[level_ptr[l] .. level_ptr[l + 1]), the gates without a long row (witness_dev.cuh) before
 // level_long[l], the others from it.  Validated on the host: every index a kernel forms from these arrays is in range.
+// The scan form reads a second set of lists over COMPRESSED levels (bpgpu.h "product chains"): a chain member -- a MUL gate with one
+// row that is a single a_O term of its own phase (the link row) and one that reads no multiplier of its phase (the free row) -- takes
+// the level of the gate it links to.  Compressed level l holds the ordinary gates scan_order[scan_ptr[l] .. scan_ptr[l + 1]) (heads
+// of chains among them; short rows before scan_long[l]) and the members chain_elem[chain_ptr[l] .. chain_ptr[l + 1]) of the chains
+// whose head it holds, chain after chain in chain order: gate | WIT_ELEM_START (the first member of a chain) | WIT_ELEM_RIGHT (the
+// link is the right row).  Gate ids are below 2^25 (ROWS_IDX_MASK), so the two flags are free bits.
+constexpr uint32_t WIT_ELEM_START = 1u << 25, WIT_ELEM_RIGHT = 1u << 26;
 struct WitDev {
   RowsDev rows;
   const uint8_t *op;          // n
@@ -277,12 +284,18 @@ struct WitDev {
   const uint32_t *order;      // n
   const uint32_t *level_ptr;  // levels + 1
   const uint32_t *level_long; // levels
+  const uint32_t *scan_order; // n - members
+  const uint32_t *scan_ptr;   // compressed levels + 1
+  const uint32_t *scan_long;  // compressed levels
+  const uint32_t *chain_elem; // members
+  const uint32_t *chain_ptr;  // compressed levels + 1
   uint32_t n, m, nchi, ninp;
 };
 // One launch evaluates the gates [g_lo, g_hi) = the levels [l_lo, l_hi) of nb provers on plain canonical planes nb x n (aL, aR, aO:
 // read for the gates below g_lo, written for the range), v nb x m, inputs nb x ninp x 2, chi nb x nchi (or nullptr), all plain.
-// block == false: a lane per prover, program order; true: a block of 256 threads per prover, level by level.
-void witness_eval(hipStream_t st, const WitDev &w, size_t nb, bool block, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
+// form 1: a lane per prover, program order; 2: a block of 256 threads per prover, level by level; 3: a block per prover over the
+// COMPRESSED levels [l_lo, l_hi), the chains of a level as one segmented prefix product (k_witness_scan).
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
                   Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
 // rows of `count` scalars, one per prover: src + p * src_stride -> dst + p * dst_stride.  to_ark: plain canonical -> ark Montgomery
 // limbs, else the reverse; a non-canonical source raises *bad and gives zero

@@ -68,7 +68,7 @@ E_ARG, E_LEN, E_DEVICE, E_OOM, E_GENS = -1, -2, -3, -4, -5
 OPT = {"msm_wp_max": 1, "msm_pip2_single": 2, "verify_no_fuse": 3, "verify_window_parallel": 4, "verify_straus_np": 5,
        "ipp_literal": 6, "vs_large_min": 7, "table_np": 8, "ipp_table_max_n": 9, "stream_lanes": 10, "stream_batch": 11, "screen_batch": 12,
        "horner_form": 13, "horner_row_max": 14, "pippenger_min": 15, "ipp_pippenger_min": 16, "fixed_lpm": 17, "groups_form": 18, "fixed_chunk_gens": 19,
-       "witness_route": 20}
+       "witness_route": 20, "witness_scan_min": 21}
 # bpgpu_profile_read kinds (include/bpgpu.h BPGPU_PROF_KINDS)
 PROF_NAMES = ["verify_scalars", "fixed_msm", "points_from_boundary", "straus", "verify_finalize", "transcript", "verify_msm",
               "verify_windows", "verify_front", "verify_groups", "verify_back", "verify_verdict", "combined_front_scalars_digits",
@@ -132,10 +132,25 @@ def witness_plan(n, n1, nchi, op, row_ptr, kind, idx, nb):
     return dict(zip(WIT_PLAN_FIELDS, out))
 
 
+# bpgpu_witness_chains (include/bpgpu.h BPGPU_WIT_CHAIN_*)
+WIT_CHAIN_FIELDS = ("chains1", "chains2", "members1", "members2", "longest1", "longest2", "levels1", "levels2")
+
+
+def witness_chains(n, n1, nchi, op, row_ptr, kind, idx):
+    """the product chains of a gate program -- per phase their number, their members, the longest and the compressed levels -- as a
+    dict over WIT_CHAIN_FIELDS (needs no device)"""
+    out = (C.c_int32 * len(WIT_CHAIN_FIELDS))()
+    rc = _lib.bpgpu_witness_chains(n, n1, nchi, _buf(bytes(op)), _u32s(row_ptr), _u32s(kind), _u32s(idx), out)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return dict(zip(WIT_CHAIN_FIELDS, out))
+
+
 class BpGpu:
     """One context on one device.  All byte encodings as in include/bpgpu.h."""
 
     witness_plan = staticmethod(witness_plan)
+    witness_chains = staticmethod(witness_chains)
 
     def __init__(self, device=0):
         self.ctx = C.c_void_p()

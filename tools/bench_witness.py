@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Witness synthesis on the device (bpgpu_r1cs_witness_synthesize_dev) and the one-call two-phase prover (bpgpu_r1cs_prove_fs2_dev)
-against the two calls around a host that evaluates the gadget.  Writes profiles/witness_synth.log (the source of the figures in
-DESIGN.md "Witness synthesis").  Shapes: 256 provers x 16 x 64-bit range (one level of 1024 BIT gates), 256 provers x shuffle k = 64
-(two chains of 63 dependent gates), 1 prover x shuffle k = 2^14 (two chains of 16 383).
+against the two calls around a host that evaluates the gadget.  Appends a run to profiles/witness_synth.log (the source of the figures in
+DESIGN.md "Witness synthesis"; the earlier runs stay).  Shapes: 256 provers x 16 x 64-bit range (one level of 1024 BIT gates), 256
+provers x shuffle k = 64 (two chains of 63 dependent gates: a head and 62 members), 1 prover x shuffle k = 2^14 (two chains of 16 383).
 
-  synth   the synthesis alone on resident operands, HIP events around the call, on both launch forms (BPGPU_OPT_WITNESS_ROUTE 1 = a
-          lane per prover, 2 = a block per prover) and what bpgpu_witness_plan picks; next to it the HOST's evaluation of the same
-          gates: this tool's Python integers (a Rust host is faster: the figure bounds the host from above);
+  synth   the synthesis alone on resident operands, HIP events around the call, on the launch forms (BPGPU_OPT_WITNESS_ROUTE 1 = a
+          lane per prover, 2 = a block per prover; route 0 with BPGPU_OPT_WITNESS_SCAN_MIN 1 = a block per prover with the product
+          chains scanned, for the shapes that have a chain) and what bpgpu_witness_plan picks; next to it the HOST's evaluation of the
+          same gates: this tool's Python integers (a Rust host is faster: the figure bounds the host from above);
+  sweep   the same for ONE shuffle whose two chains have 8 .. 16 382 members, for 1 and 256 provers, block form against scan form:
+          where BPGPU_OPT_WITNESS_SCAN_MIN's default is read from -- the smallest power of two >= 16 from which on the scan's
+          MAXIMUM lies below the block form's MINIMUM for both batch sizes -- and one line of 4096 x shuffle k = 64 on all three
+          forms, beyond the 1024 blocks that are resident at once;
   prove   bpgpu_r1cs_prove_fs2_dev (one call) against bpgpu_r1cs_prove_fs2_begin_dev + the host's gadget (download of the challenge,
           evaluation, Montgomery encoding, upload) + _finish_dev on the same inputs, wall clock from the first call to the drained
           stream; `chains` is the pair of _dev calls alone on a resident phase-2 witness, the figure tools/bench_prove_fs2.py
@@ -17,6 +22,7 @@ DESIGN.md "Witness synthesis").  Shapes: 256 provers x 16 x 64-bit range (one le
 
 A fresh process per line under its own time limit; WARM untimed steps, then STEPS timed ones, medians (min..max) in ms."""
 import ctypes as C
+import json
 import os
 import statistics
 import subprocess
@@ -71,7 +77,12 @@ class Timer:
         return ms.value
 
 
-def synth(shape, nb, size):
+FORMS = {"lane": (1, 0), "block": (2, 0), "scan": (0, 1)}      # form -> (BPGPU_OPT_WITNESS_ROUTE, BPGPU_OPT_WITNESS_SCAN_MIN)
+SWEEP_MEMBERS = (8, 16, 32, 64, 128, 256, 1024, 16382)
+SWEEP_NB = (1, 256)
+
+
+def synth(shape, nb, size, forms=("lane", "block", "scan")):
     import mpc_dealer as md
     import mpc_bulletproof_amd as m
     prog, v = range_program(64, size) if shape == "range" else shuffle_program(size)
@@ -82,13 +93,18 @@ def synth(shape, nb, size):
     gpu = m.BpGpu(0)
     w = gpu.witness_create(*prog.create_args())
     plan = m.lib.witness_plan(*prog.plan_args(), nb)
+    chains = m.lib.witness_chains(*prog.plan_args())
+    longest = max(chains["longest1"], chains["longest2"])
     d_v = gpu.to_device(b"".join(md.mont(x) for x in v) * nb)
     d_chi = gpu.to_device(md.le(chi[0]) * nb) if chi else None
     planes = [gpu.malloc(32 * nb * prog.n) for _ in range(3)]
     timer = Timer(gpu)
     out = {}
-    for route in (1, 2):
-        gpu.set_option("witness_route", route)
+    for form in forms:
+        if form == "scan" and not longest:       # no chain: route 0 would take the width rule
+            continue
+        gpu.set_option("witness_route", FORMS[form][0])
+        gpu.set_option("witness_scan_min", FORMS[form][1])
         ts = []
         for step in range(WARM + STEPS):
             ms = timer.events(lambda: gpu.r1cs_witness_synthesize_dev(w, nb, 0, *planes, d_v=d_v, d_gadget_challenges=d_chi))
@@ -97,10 +113,13 @@ def synth(shape, nb, size):
         assert gpu.input_flag() == 0
         got = gpu.download(planes[2], 32 * nb * prog.n)
         assert got[-32 * prog.n:] == b"".join(md.mont(x) for x in want[2]), "the device's witness differs from the host's"
-        out[route] = ts
+        out[form] = ts
     route = plan["route2" if prog.nchi else "route1"]
-    return (f"lane {fmt(out[1])}   block {fmt(out[2])}   plan: {'lane' if route == 1 else 'block'}   levels {plan['levels1'] + plan['levels2']:6d} "
-            f"widest {plan['widest']:5d}   host (Python, ONE prover) {host_ms:9.3f}")
+    cols = "   ".join(f"{form:5s}{fmt(out[form])}" if form in out else f"{form:5s}{'-':>9s}{'':21s}" for form in forms)
+    text = (f"{cols}   plan: {('lane', 'block', 'scan')[route - 1]:5s}   levels {plan['levels1'] + plan['levels2']:6d} "
+            f"(scan {chains['levels1'] + chains['levels2']:2d})   widest {plan['widest']:5d}   longest chain {longest:6d}   "
+            f"host (Python, ONE prover) {host_ms:9.3f}")
+    return text, {form: (min(ts), max(ts)) for form, ts in out.items()}
 
 
 def prove(nb, ks, window_bits):
@@ -168,14 +187,29 @@ def prove(nb, ks, window_bits):
 
 def child(what, args):
     if what == "synth":
-        print("RESULT", synth(args[0], int(args[1]), int(args[2])))
+        text, spans = synth(args[0], int(args[1]), int(args[2]), tuple(args[3].split(",")))
+        print("SPANS", json.dumps(spans))
+        print("RESULT", text)
     else:
         print("RESULT", prove(int(args[0]), int(args[1]), int(args[2])))
+
+
+def scan_min_line(spans):
+    """the rule of BPGPU_OPT_WITNESS_SCAN_MIN's default on the sweep's (min, max) spans: non-overlap at both batch sizes"""
+    def wins(members):
+        return all(spans[("shuffle", nb, members + 2)]["scan"][1] < spans[("shuffle", nb, members + 2)]["block"][0] for nb in SWEEP_NB)
+    powers = [mm for mm in SWEEP_MEMBERS if mm & (mm - 1) == 0 and mm >= 16]
+    good = [d for d in powers if all(wins(mm) for mm in SWEEP_MEMBERS if mm >= d)]
+    if not good:
+        return "# scan max < block min at both nb from NO measured power of two on: the scan form has missed its purpose"
+    return (f"# scan max < block min at both nb from {good[0]} members on (every longer chain of the sweep included): "
+            f"BPGPU_OPT_WITNESS_SCAN_MIN defaults to {good[0]}")
 
 
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3:])
+    spans = {}
     lines = [f"# tools/bench_witness.py   a fresh process per line (limit {STEP_LIMIT} s), {WARM} warm-up + {STEPS} timed steps per route: median "
              "(min..max) ms",
              "# synth: bpgpu_r1cs_witness_synthesize_dev alone, HIP events; host: the same gates of ONE prover on Python integers"]
@@ -189,6 +223,7 @@ def main():
         got = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT")]
         if out.returncode != 0 or not got:
             return f"FAILED rc={out.returncode}: {(out.stderr or out.stdout)[-400:]!r}", False
+        spans.update({args[1:4]: json.loads(ln[len("SPANS "):]) for ln in out.stdout.splitlines() if ln.startswith("SPANS")})
         return got[0][len("RESULT "):], True
 
     def step(text, *args):
@@ -197,16 +232,23 @@ def main():
         print(lines[-1])
         sys.stdout.flush()
         return ok
-    ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16)
-    ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64)
-    ok = ok and step("synth   1 x shuffle k = 2^14       n = 32766   ", "synth", "shuffle", 1, 1 << 14)
+    ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16, "lane,block,scan")
+    ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64, "lane,block,scan")
+    ok = ok and step("synth   1 x shuffle k = 2^14       n = 32766   ", "synth", "shuffle", 1, 1 << 14, "lane,block,scan")
+    lines.append("# sweep: one shuffle of k = members + 2 per prover (two chains), block form against scan form")
+    for members in SWEEP_MEMBERS:
+        for nb in SWEEP_NB:
+            ok = ok and step(f"sweep   {nb:4d} x {members:5d} members   n = {2 * members + 2:5d}   ", "synth", "shuffle", nb, members + 2, "block,scan")
+    if ok:
+        lines.append(scan_min_line(spans))
+    ok = ok and step("synth   4096 x shuffle k = 64      n = 126     ", "synth", "shuffle", 4096, 64, "lane,block,scan")
     lines.append("# prove: wall clock from the first call to the drained stream; chains = begin_dev + finish_dev alone (tools/bench_prove_fs2.py's figure)")
     ok = ok and step("prove   256 x shuffle k = 64       ", "prove", 256, 64, 8)
     ok = ok and step("prove   1 x shuffle k = 2^10       ", "prove", 1, 1 << 10, 8)
     if not ok:
         lines.append("# a step failed: the steps after it were not started")
     path = os.path.join(ROOT, "profiles", "witness_synth.log")
-    with open(path, "w") as fh:
+    with open(path, "a") as fh:          # a run is appended: the earlier runs stay, the parent commit's among them
         fh.write("\n".join(lines) + "\n")
     print("wrote", path)
     return 0 if ok else 1
