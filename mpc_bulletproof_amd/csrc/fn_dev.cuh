@@ -6,11 +6,18 @@
 namespace bpk {
 using namespace bp;
 
-BP_HD Fn load_plain(const Words8 *p) {   // plain canonical words -> Montgomery
+BP_HD Fn load_words(const Words8 *p) {   // 8 words as they stand (a Montgomery coefficient, ark limbs) -> limbs
   uint32_t w[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) w[j] = p->w[j];
-  return to_mont(unpack<FN>(w));
+  return unpack<FN>(w);
+}
+BP_HD Fn load_plain(const Words8 *p) { return to_mont(load_words(p)); }   // plain canonical words -> Montgomery
+BP_HD bool words_canonical(const Words8 *p) {   // the 8 words are below n
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) w[j] = p->w[j];
+  return words_lt_mod<FN>(w);
 }
 __device__ __forceinline__ void store_plain(Words8 *p, const Fn &x) {   // Montgomery -> plain canonical words
   uint32_t w[8];
@@ -24,7 +31,7 @@ __device__ __forceinline__ Fn fn_from_u32(uint32_t v) {
   t.v[1] = (int32_t)(v >> LB);
   return to_mont(t);
 }
-__device__ __forceinline__ Fn fn_pow_u32(Fn base, uint32_t e) {   // base^e, e >= 0
+BP_HD Fn fn_pow_u32(Fn base, uint32_t e) {   // base^e, e >= 0
   Fn acc = fe_one<FN>();
   while (e) {
     if (e & 1) acc = mul(acc, base);
@@ -69,6 +76,22 @@ __device__ __forceinline__ Fn wave_sum(Fn x) {
   }
   return x;
 }
+// the block tail of every sum: one lazy Fn per lane over a block of TPB lanes -- fn_reduce, wave_sum, the waves' sums (64 reduced values
+// each) through one LDS slot each and added by thread 0, which alone holds the result; it ends the sum with store_plain or fn_reduce.
+// Every thread of the block calls it; the closing barrier frees the slots for another call.
+template <int TPB> __device__ __forceinline__ Fn block_sum(Fn acc) {
+  static_assert(TPB % 64 == 0, "whole waves");
+  acc = wave_sum(fn_reduce(acc));
+  if constexpr (TPB > 64) {
+    __shared__ int32_t sm[NL * (TPB / 64)];
+    if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int w = 1; w < TPB / 64; w++) acc = add(acc, raw_get(sm + w * NL));
+    __syncthreads();
+  }
+  return acc;
+}
 #endif
 
 // one flattened constraint weight: output o of the column-major circuit against a proof's z-power table (flattened_constraints,
@@ -77,10 +100,7 @@ __device__ __forceinline__ Fn flatten_column(const CircuitDev &c, size_t o, cons
   Fn acc = fe_zero<FN>();
   uint32_t cnt = 0;
   for (uint32_t t = c.col_ptr[o]; t < c.col_ptr[o + 1]; t++) {
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
-    acc = add(acc, mul(unpack<FN>(w), raw_get(zp + (size_t)c.row[t] * NL)));
+    acc = add(acc, mul(load_words(&c.coeff[t]), raw_get(zp + (size_t)c.row[t] * NL)));
     if ((++cnt & 15) == 0) acc = fn_reduce(acc);
   }
   if (o >= 3 * c.n) acc = neg(acc);
@@ -96,10 +116,7 @@ BP_HD Fn eval_row(const RowsDev &rv, uint32_t lo, uint32_t hi, uint32_t step, co
   Fn acc = fe_zero<FN>();
   uint32_t cnt = 0;
   for (uint32_t t = lo; t < hi; t += step) {
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = rv.coeff[t].w[j];
-    Fn cf = unpack<FN>(w);
+    Fn cf = load_words(&rv.coeff[t]);
     const uint32_t code = rv.var[t], j = code >> ROWS_CHI_SHIFT, kind = (code >> ROWS_KIND_SHIFT) & 7u, idx = code & ROWS_IDX_MASK;
     if (j) cf = mul(cf, load_plain(chi + (j - 1)));
     const Words8 *pl = kind == 0 ? aL : (kind == 1 ? aR : (kind == 2 ? aO : v));

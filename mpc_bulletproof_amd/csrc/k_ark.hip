@@ -8,6 +8,7 @@
 // on the host.  [The layouts are the published ones of ark-ff / ark-ec 0.4; confirm against the pinned crate versions when a
 // Rust toolchain is available: shim/examples/gen_fixtures.rs.]
 #include "ec_dev.cuh"
+#include "fn_dev.cuh"
 
 using namespace bp;
 
@@ -26,16 +27,14 @@ __device__ __forceinline__ Fp fp_ark_out() { constexpr int32_t C[NL] = FP_ARK_OU
 
 // one scalar, ark Montgomery limbs (x 2^256 mod n) -> plain canonical words; a non-canonical limb set raises *bad and gives zero
 __device__ __forceinline__ void scalar_from_ark(const Words8 *in, Words8 *out, int *bad) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in->w[j];
-  if (!words_lt_mod<FN>(w)) {
+  if (!words_canonical(in)) {
     atomicOr(bad, 1);
 #pragma unroll
     for (int j = 0; j < 8; j++) out->w[j] = 0;
     return;
   }
-  pack(w, canon(mul(unpack<FN>(w), fn_ark_in())));
+  uint32_t w[8];
+  pack(w, canon(mul(load_words(in), fn_ark_in())));
 #pragma unroll
   for (int j = 0; j < 8; j++) out->w[j] = w[j];
 }
@@ -54,11 +53,9 @@ __global__ void __launch_bounds__(256) k_commit_value_rows(const Words8 *v, cons
 __global__ void __launch_bounds__(256) k_scalars_to_ark(const Words8 *in, Words8 *out, size_t n, int *bad) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (!words_canonical(&in[i])) { atomicOr(bad, 1); for (int j = 0; j < 8; j++) out[i].w[j] = 0; return; }
   uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in[i].w[j];
-  if (!words_lt_mod<FN>(w)) { atomicOr(bad, 1); for (int j = 0; j < 8; j++) out[i].w[j] = 0; return; }
-  pack(w, canon(mul(unpack<FN>(w), fn_ark_out())));
+  pack(w, canon(mul(load_words(&in[i]), fn_ark_out())));
 #pragma unroll
   for (int j = 0; j < 8; j++) out[i].w[j] = w[j];
 }

@@ -15,13 +15,6 @@ using namespace bp;
 
 namespace bpk {
 
-__device__ __forceinline__ bool plain_canonical(const Words8 *p) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = p->w[j];
-  return words_lt_mod<FN>(w);
-}
-
 // ---- header: a lane per proof.  hdr[p] = (k + 2) raw field elements: u_j^2 (j < k), a / (u_1 ... u_k), b / (u_1 ... u_k).
 // Writes the scalars of Q (a b, or a b w: Q = w B), of L (-u^2) and of R (-u^-2) where the MSM route reads them.  A zero
 // challenge has no inverse: the proof is marked rejected (reject[p] = 1) and computed with 1 in its place.
@@ -29,13 +22,13 @@ __global__ void __launch_bounds__(64) k_ippv_header(IppvHeader h) {
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= h.nb) return;
   const int k = h.k;
-  bool canonical = plain_canonical(&h.ab[2 * p]) && plain_canonical(&h.ab[2 * p + 1]) && (!h.w || plain_canonical(&h.w[p]));
+  bool canonical = words_canonical(&h.ab[2 * p]) && words_canonical(&h.ab[2 * p + 1]) && (!h.w || words_canonical(&h.w[p]));
   Fn pref[32], val[32];
   Fn acc = fe_one<FN>();
   bool zero = false;
 #pragma unroll 1
   for (int i = 0; i < k; i++) {
-    canonical = canonical && plain_canonical(&h.challenges[p * k + i]);
+    canonical = canonical && words_canonical(&h.challenges[p * k + i]);
     pref[i] = acc;
     val[i] = load_plain(&h.challenges[p * k + i]);
     if (is_zero_exact(val[i])) { zero = true; val[i] = fe_one<FN>(); }
@@ -101,7 +94,7 @@ __global__ void __launch_bounds__(1 << LOG) k_ippv_assemble(size_t n, int k, siz
   if (i >= n) return;
   const size_t mask = ((size_t)1 << r) - 1;
   const Words8 *gf = &Gf[p * n + i], *hf = &Hf[p * n + i];
-  if (!plain_canonical(gf) || !plain_canonical(hf)) atomicOr(bad, 1);
+  if (!words_canonical(gf) || !words_canonical(hf)) atomicOr(bad, 1);
   const Fn sg = mul(raw_get(hi), raw_get(lo + (i & mask) * NL));
   const Fn sh = mul(raw_get(hi + NL), raw_get(lo + ((n - 1 - i) & mask) * NL));
   store_plain(&g_sc[p * sc_stride + i], mul(sg, load_plain(gf)));

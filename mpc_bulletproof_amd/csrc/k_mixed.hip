@@ -62,12 +62,8 @@ __global__ void __launch_bounds__(256) k_mix_front(MixFront a) {
     for (int t = 0; t < 8; t++) { r[t] = g.rho[j].w[t]; any |= r[t]; a.rho_all[p].w[t] = r[t]; }
     if (!words_lt_mod<FN>(r)) atomicOr(a.bad, 1);
     if (!any && a.zero_rho) atomicOr(a.zero_rho, 1);
-    for (uint32_t c = 0; c < g.nchi; c++) {
-      uint32_t x[8];
-#pragma unroll
-      for (int t = 0; t < 8; t++) x[t] = g.chi[j * g.nchi + c].w[t];
-      if (!words_lt_mod<FN>(x)) atomicOr(a.bad, 1);
-    }
+    for (uint32_t c = 0; c < g.nchi; c++)
+      if (!words_canonical(&g.chi[j * g.nchi + c])) atomicOr(a.bad, 1);
   } else if (b < a.pb + a.rb + a.vb) {              // inversion pass of the segments whose assembly takes it here, lane per proof
     const uint32_t v = b - a.pb - a.rb;
     uint32_t s = 0;
@@ -85,7 +81,7 @@ __global__ void __launch_bounds__(256) k_mix_front(MixFront a) {
 // or 2 + np + (j - 2 - N) (H); columns beyond a segment's np take nothing from it
 struct MixColSeg { const Words8 *fixed; uint32_t p_off, nb, np; };
 struct MixColsum { MixColSeg seg[MIX_SEG_MAX]; uint32_t nseg; size_t nmax; const Words8 *rho_all; Words8 *out; };
-__device__ __forceinline__ void mix_colsum_body(const MixColsum &a, size_t j, int32_t *sm /* NL * 4 */) {
+__device__ __forceinline__ void mix_colsum_body(const MixColsum &a, size_t j) {
   Fn acc = fe_zero<FN>();
   int cnt = 0;
   for (uint32_t s = 0; s < a.nseg; s++) {
@@ -100,20 +96,13 @@ __device__ __forceinline__ void mix_colsum_body(const MixColsum &a, size_t j, in
       if ((++cnt & 15) == 0) acc = fn_reduce(acc);
     }
   }
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int wv = 1; wv < 4; wv++) t = add(t, raw_get(sm + wv * NL));
-    store_plain(&a.out[j], t);
-  }
+  const Fn t = block_sum<256>(acc);
+  if (threadIdx.x == 0) store_plain(&a.out[j], t);
 }
 static_assert(sizeof(Pip2) + sizeof(unsigned) + sizeof(MixColsum) + 16 <= 4096, "k_mix_k1's arguments exceed 4 KB");
 __global__ void __launch_bounds__(256) k_mix_k1(Pip2 p, unsigned digit_blocks, MixColsum cs) {
-  __shared__ int32_t sm[NL * 4];
   if (blockIdx.x < digit_blocks) p2_digits_body(p, blockIdx.x);
-  else mix_colsum_body(cs, blockIdx.x - digit_blocks, sm);
+  else mix_colsum_body(cs, blockIdx.x - digit_blocks);
 }
 // generic route: var[i] *= rho_all[pidx[i]]
 __global__ void __launch_bounds__(256) k_mix_scale(Words8 *var, const uint32_t *pidx, const Words8 *rho_all, size_t n) {

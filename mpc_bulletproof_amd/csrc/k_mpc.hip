@@ -26,16 +26,6 @@ __device__ __forceinline__ Fn beaver_term(const Words8 *opened, const Words8 *tr
   if (k == 2) r = add(r, mul(d, e));
   return r;
 }
-// sum of one Fn per lane over a 256-lane block; the result in lane 0
-__device__ __forceinline__ Fn block_sum256(Fn acc) {
-  __shared__ int32_t sm[NL * 4];
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  Fn t = raw_get(sm);
-  for (int w = 1; w < 4; w++) t = add(t, raw_get(sm + w * NL));
-  return t;
-}
 
 // r1cs_mpc/mpc_prover.rs:783-829: the l(x) / r(x) coefficient vectors per plane, layout [6][3 nb][n][9] as k_prover_polys
 // (l1 l2 l3 r0 r1 r3).  Public terms -- y^-i wR in l1, wL in r1 -- land on the modifier plane only; r0 = wO - y^i is PUBLIC and
@@ -106,7 +96,7 @@ __global__ void __launch_bounds__(256) k_mpc_tcoeffs(size_t nb, size_t n, const 
     if (p2 >= 0) acc = add(acc, beaver_term(opened, trip, p, 6, (size_t)p2, k, n, i));
     if ((++cnt & 3) == 0) acc = fn_reduce(acc);
   }
-  const Fn t = block_sum256(acc);
+  const Fn t = block_sum<256>(acc);
   if (threadIdx.x == 0) store_plain(&t_out[v * 6 + which], t);
 }
 void mpc_tcoeffs(hipStream_t st, size_t nb, size_t n, const int32_t *polys, const Words8 *opened, const Words8 *trip, Words8 *t_out) {
@@ -184,7 +174,7 @@ __global__ void __launch_bounds__(256) k_mpc_ipp_combine(size_t h, const Words8 
     acc = add(acc, beaver_term(opened, trip, p, 2, j, k, h, i));
     if ((++cnt & 7) == 0) acc = fn_reduce(acc);
   }
-  const Fn t = block_sum256(acc);
+  const Fn t = block_sum<256>(acc);
   if (threadIdx.x == 0) store_plain(&cLR[2 * v + j], t);
 }
 void mpc_ipp_combine(hipStream_t st, size_t nb, size_t h, const Words8 *opened, const Words8 *trip, Words8 *cLR) {

@@ -171,10 +171,7 @@ __global__ void __launch_bounds__(256) k_p2_front(P2Front a) {
     Aff q;
     if (!aff_from_boundary(q, w)) { atomicOr(a.bad, 1); q.x = fe_zero<FP>(); q.y = fe_zero<FP>(); }
     aff_store(&a.pts[i], q);
-    uint32_t s[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) s[j] = a.sc[i].w[j];
-    if (!words_lt_mod<FN>(s)) atomicOr(a.bad, 1);
+    if (!words_canonical(&a.sc[i])) atomicOr(a.bad, 1);
   } else {
     const size_t i = (size_t)(blockIdx.x - a.pb) * 256 + threadIdx.x;
     if (i < a.ncounts) a.counts[i] = 0;
@@ -238,26 +235,19 @@ __global__ void __launch_bounds__(256) k_comb_front(CombFront a) {
   }
 }
 struct CombColsum { const Words8 *x, *w; size_t nb, cnt; Words8 *out; };
-__device__ __forceinline__ void comb_colsum_body(const CombColsum &a, size_t i, int32_t *sm /* NL * 4 */) {
+__device__ __forceinline__ void comb_colsum_body(const CombColsum &a, size_t i) {
   Fn acc = fe_zero<FN>();
   int c = 0;
   for (size_t p = threadIdx.x; p < a.nb; p += 256) {
     acc = add(acc, mul(load_plain(&a.x[p * a.cnt + i]), load_plain(&a.w[p])));
     if ((++c & 15) == 0) acc = fn_reduce(acc);
   }
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int wv = 1; wv < 4; wv++) t = add(t, raw_get(sm + wv * NL));
-    store_plain(&a.out[i], t);
-  }
+  const Fn t = block_sum<256>(acc);
+  if (threadIdx.x == 0) store_plain(&a.out[i], t);
 }
 __global__ void __launch_bounds__(256) k_comb_k1(Pip2 p, unsigned digit_blocks, CombColsum cs) {
-  __shared__ int32_t sm[NL * 4];
   if (blockIdx.x < digit_blocks) p2_digits_body(p, blockIdx.x);
-  else comb_colsum_body(cs, blockIdx.x - digit_blocks, sm);
+  else comb_colsum_body(cs, blockIdx.x - digit_blocks);
 }
 template <int C>
 __global__ void __launch_bounds__(64) k_comb_k4(Pip2 p, unsigned accum_blocks, FixedSmallArgs f) {

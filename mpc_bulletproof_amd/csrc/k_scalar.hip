@@ -15,19 +15,13 @@ namespace bpk {
 __global__ void __launch_bounds__(256) k_scalars_check(const Words8 *in, size_t n, int *bad) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in[i].w[j];
-  if (!words_lt_mod<FN>(w)) atomicOr(bad, 1);
+  if (!words_canonical(&in[i])) atomicOr(bad, 1);
 }
 // the same with the verdict attributed to a proof: element i belongs to proof i / per; writes 1 only (zero the array first)
 __global__ void __launch_bounds__(256) k_scalars_check_proof(const Words8 *in, size_t n, size_t per, int *bad, int32_t *bad_proof) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in[i].w[j];
-  if (!words_lt_mod<FN>(w)) { if (bad) atomicOr(bad, 1); bad_proof[i / per] = 1; }
+  if (!words_canonical(&in[i])) { if (bad) atomicOr(bad, 1); bad_proof[i / per] = 1; }
 }
 void scalars_check(hipStream_t st, const Words8 *in, size_t n, int *bad) {
   if (!n) return;
@@ -114,18 +108,16 @@ __global__ void __launch_bounds__(256) k_csr_scatter(size_t q, const uint32_t *r
       pos = col_ptr[o] + base + (uint32_t)__popcll(mc & ((1ull << __lane_id()) - 1));
     } else pos = col_ptr[o] + atomicAdd(&fill[o], 1u);
     rows[pos] = (uint32_t)r;
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = coeff_in[t].w[j];
-    if (!words_lt_mod<FN>(w)) { atomicOr(bad, 1); continue; }
+    if (!words_canonical(&coeff_in[t])) { atomicOr(bad, 1); continue; }
     Fn x;
     if (ARK) {       // ark-ff Montgomery limbs (x 2^256 mod n): one multiplication by 2^266 instead of the host's de-Montgomery
       constexpr int32_t C[NL] = FN_ARK_MONT;
       Fn k;
 #pragma unroll
       for (int j = 0; j < NL; j++) k.v[j] = C[j];
-      x = canon(mul(unpack<FN>(w), k));
-    } else x = canon(to_mont(unpack<FN>(w)));
+      x = canon(mul(load_words(&coeff_in[t]), k));
+    } else x = canon(load_plain(&coeff_in[t]));
+    uint32_t w[8];
     pack(w, x);
 #pragma unroll
     for (int j = 0; j < 8; j++) coeff_out[pos].w[j] = w[j];
@@ -229,22 +221,14 @@ void batch_inverse(hipStream_t st, Words8 *io, size_t n, int *bad_zero) {
 // inner_product: grid-stride partial sums, one raw partial per block, then a single-block finish
 constexpr int IP_TPB = 256;
 __global__ void __launch_bounds__(IP_TPB) k_inner_product_partial(const Words8 *a, const Words8 *b, size_t n, int32_t *partials) {
-  __shared__ int32_t sm[NL * (IP_TPB / 64)];
   Fn acc = fe_zero<FN>();
   int cnt = 0;
   for (size_t i = (size_t)blockIdx.x * IP_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * IP_TPB) {
     acc = add(acc, mul(load_plain(&a[i]), load_plain(&b[i])));
     if ((++cnt & 15) == 0) acc = fn_reduce(acc);
   }
-  acc = wave_sum(fn_reduce(acc));
-  int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) raw_put(sm + wv * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int w = 1; w < IP_TPB / 64; w++) t = add(t, raw_get(sm + w * NL));
-    raw_put(partials + (size_t)blockIdx.x * NL, fn_reduce(t));
-  }
+  const Fn t = block_sum<IP_TPB>(acc);
+  if (threadIdx.x == 0) raw_put(partials + (size_t)blockIdx.x * NL, fn_reduce(t));
 }
 __global__ void __launch_bounds__(64) k_inner_product_finish(const int32_t *partials, int nparts, Words8 *out) {
   Fn acc = fe_zero<FN>();
@@ -294,22 +278,15 @@ void sc_mul_strided(hipStream_t st, size_t nb, size_t cnt, const Words8 *x, size
 }
 __global__ void __launch_bounds__(256) k_sc_dot_batched(size_t cnt, const Words8 *x, size_t x_outer, const Words8 *y,
                                                         size_t y_outer, Words8 *out, size_t out_stride) {
-  __shared__ int32_t sm[NL * 4];
-  size_t p = blockIdx.x;
+  const size_t p = blockIdx.x;
   Fn acc = fe_zero<FN>();
   int c = 0;
   for (size_t i = threadIdx.x; i < cnt; i += 256) {
     acc = add(acc, mul(load_plain(&x[p * x_outer + i]), load_plain(&y[p * y_outer + i])));
     if ((++c & 15) == 0) acc = fn_reduce(acc);
   }
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int w = 1; w < 4; w++) t = add(t, raw_get(sm + w * NL));
-    store_plain(&out[p * out_stride], t);
-  }
+  const Fn t = block_sum<256>(acc);
+  if (threadIdx.x == 0) store_plain(&out[p * out_stride], t);
 }
 void sc_dot_batched(hipStream_t st, size_t nb, size_t cnt, const Words8 *x, size_t x_outer, const Words8 *y,
                     size_t y_outer, Words8 *out, size_t out_stride) {
@@ -342,22 +319,15 @@ void sc_scale_rows(hipStream_t st, size_t nb, size_t cnt, Words8 *x, const Words
   hipLaunchKernelGGL(k_sc_scale_rows, dim3((cnt + 255) / 256, nb), dim3(256), 0, st, cnt, x, w);
 }
 __global__ void __launch_bounds__(256) k_sc_weighted_colsum(size_t nb, size_t cnt, const Words8 *x, const Words8 *w, Words8 *out) {
-  __shared__ int32_t sm[NL * 4];
-  size_t i = blockIdx.x;
+  const size_t i = blockIdx.x;
   Fn acc = fe_zero<FN>();
   int c = 0;
   for (size_t p = threadIdx.x; p < nb; p += 256) {
     acc = add(acc, mul(load_plain(&x[p * cnt + i]), load_plain(&w[p])));
     if ((++c & 15) == 0) acc = fn_reduce(acc);
   }
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int wv = 1; wv < 4; wv++) t = add(t, raw_get(sm + wv * NL));
-    store_plain(&out[i], t);
-  }
+  const Fn t = block_sum<256>(acc);
+  if (threadIdx.x == 0) store_plain(&out[i], t);
 }
 void sc_weighted_colsum(hipStream_t st, size_t nb, size_t cnt, const Words8 *x, const Words8 *w, Words8 *out) {
   if (!cnt) return;
@@ -541,7 +511,6 @@ void prover_polys(hipStream_t st, const CircuitDev &c, size_t nb, const Words8 *
 // one block per (proof, coefficient): t1 = <l1,r0>; t2 = <l1,r1> + <l2,r0>; t3 = <l2,r1> + <l3,r0>;
 // t4 = <l1,r3> + <l3,r1>; t5 = <l2,r3>; t6 = <l3,r3>     (planes: 0 l1, 1 l2, 2 l3, 3 r0, 4 r1, 5 r3)
 __global__ void __launch_bounds__(256) k_prover_tcoeffs(size_t nb, size_t n, const int32_t *polys, Words8 *t_out) {
-  __shared__ int32_t sm[NL * 4];
   const size_t p = blockIdx.x, plane = nb * n * NL;
   const int which = blockIdx.y;
   const int A1[6] = {0, 0, 1, 0, 1, 2}, B1[6] = {3, 4, 4, 5, 5, 5}, A2[6] = {-1, 1, 2, 2, -1, -1}, B2[6] = {-1, 3, 3, 4, -1, -1};
@@ -554,14 +523,8 @@ __global__ void __launch_bounds__(256) k_prover_tcoeffs(size_t nb, size_t n, con
     if (a2 >= 0) acc = add(acc, mul(raw_get(e + a2 * plane), raw_get(e + b2 * plane)));
     if ((++c & 7) == 0) acc = fn_reduce(acc);
   }
-  acc = wave_sum(fn_reduce(acc));
-  if ((threadIdx.x & 63) == 0) raw_put(sm + (threadIdx.x >> 6) * NL, acc);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Fn t = raw_get(sm);
-    for (int w = 1; w < 4; w++) t = add(t, raw_get(sm + w * NL));
-    store_plain(&t_out[p * 6 + which], t);
-  }
+  const Fn t = block_sum<256>(acc);
+  if (threadIdx.x == 0) store_plain(&t_out[p * 6 + which], t);
 }
 void prover_tcoeffs(hipStream_t st, size_t nb, size_t n, const int32_t *polys, Words8 *t_out) {
   if (!nb) return;
@@ -593,11 +556,7 @@ void prover_eval(hipStream_t st, size_t nb, size_t n, size_t padded_n, const Wor
 }
 
 // ------------------------------------------------------------------------------------------------
-// Verifier scalar assembly (r1cs/verifier.rs:457-532) in two kernels.
-// k_vs_prep, one LANE per proof: y^-1 and u_j^-1 (verifier.rs:468, inner_product_proof.rs:283) by Montgomery's
-// trick around one binary-GCD inversion, then u_j^2, u_j^-2, prod u_j^-1.  (Run by one lane of a per-proof block
-// this serial chain cost a full wave's issue slots per proof: a quarter of all instructions of a verification.)
-// aux per proof (NL ints each): 0 y_inv, 1 allinv, 2.. u_sq[32], 34.. u_inv_sq[32] (+ partials, large path)
+// Verifier scalar assembly (r1cs/verifier.rs:457-532) in two kernels: the inversion pass (vs_prep.cuh), then the n-wide work.
 __global__ void __launch_bounds__(64) k_vs_prep(VsPrepArgs a) { vs_prep_body(a, blockIdx.x); }
 // x^lane for the 64 lanes of a wave through two 8-entry tables in LDS: lanes 0..7 build x^0..x^7, lanes 8..15
 // (x^8)^0..(x^8)^7 -- three conditional products on per-lane bases --, then every lane multiplies one entry of each.
@@ -618,8 +577,112 @@ __device__ __forceinline__ Fn wave64_powers(const Fn &x, int tid, int32_t *tab) 
   __syncthreads();   // tab may be reused
   return r;
 }
-// k_verify_scalars, one wave per proof: z powers, g_i / h_i, delta, w_c and the remaining scalars.
+// ---- the formulas, once: the block-per-proof kernel and the grid-split kernels below both call these
 constexpr int VS_TPB = 64;
+// one proof's operands and outputs
+struct VsProof {
+  const Words8 *ch, *ps;     // 6 + k challenges (y z u x w r, u_1..u_k), 5 proof scalars (t_x t_x_blinding e_blinding a b)
+  const int32_t *zpow;
+  Words8 *fx, *vs, *full;    // fixed-base scalars [B, B_blinding, g, h], proof-point scalars, all of them in verifier.rs:517-532 order
+};
+__device__ __forceinline__ VsProof vs_proof(const CircuitDev &c, const VerifyDims &d, size_t p, const Words8 *challenges,
+                                            const Words8 *proof_scalars, const int32_t *zpow_all, Words8 *fixed_sc, Words8 *var_sc,
+                                            Words8 *full_sc) {
+  return VsProof{challenges + p * (6 + d.k), proof_scalars + p * 5, zpow_all + p * c.qz * NL, fixed_sc + p * (2 + 2 * d.padded_n),
+                 var_sc ? var_sc + p * (11 + d.m + 2 * d.k) : nullptr, full_sc ? full_sc + p * (13 + d.m + 2 * d.padded_n + 2 * d.k) : nullptr};
+}
+// canonical-encoding check of the proof's 6 + k challenges and 5 scalars by its wave (a block of VS_TPB): *bad is raised, bad_proof[p]
+// written either way (its only writer: no reset needed)
+__device__ __forceinline__ void vs_check_proof(const VsProof &pr, size_t k, size_t p, int *bad, int32_t *bad_proof) {
+  if (!bad && !bad_proof) return;
+  bool mine = false;
+  for (size_t t = threadIdx.x; t < 11 + k; t += VS_TPB)
+    if (!words_canonical(t < 6 + k ? &pr.ch[t] : &pr.ps[t - 6 - k])) mine = true;
+  const bool any = __any(mine);
+  if (threadIdx.x == 0) {
+    if (any && bad) atomicOr(bad, 1);
+    if (bad_proof) bad_proof[p] = any ? 1 : 0;
+  }
+}
+// y^-i (verifier.rs:469-471), s_i and s_{np-1-i} (inner_product_proof.rs:298-307, closed form) for a lane that has no table of them
+__device__ __forceinline__ void vs_powers_at(const Fn &y_inv, const Fn &allinv, const int32_t *usq, size_t k, size_t np, size_t i, Fn &yi,
+                                             Fn &si, Fn &sr) {
+  yi = fn_pow_u32(y_inv, (uint32_t)i);
+  si = allinv; sr = allinv;
+  const size_t ir = np - 1 - i;
+  for (size_t bb = 0; bb < k; bb++) {
+    const Fn us = raw_get(usq + (k - 1 - bb) * NL);
+    if ((i >> bb) & 1) si = mul(si, us);
+    if ((ir >> bb) & 1) sr = mul(sr, us);
+  }
+}
+struct VsGh { Fn u, x, a, b; };
+__device__ __forceinline__ VsGh vs_gh_operands(const VsProof &pr) {
+  return VsGh{load_plain(&pr.ch[2]), load_plain(&pr.ch[3]), load_plain(&pr.ps[3]), load_plain(&pr.ps[4])};
+}
+// index i of verifier.rs:469-501: stores g_i and h_i, returns the term wL_i wR_i y^-i of delta
+__device__ __forceinline__ Fn vs_gh(const CircuitDev &c, const VerifyDims &d, const VsProof &pr, const VsGh &o, size_t i, const Fn &yi,
+                                    const Fn &si, const Fn &sr) {
+  const size_t n = d.n, np = d.padded_n, off_g = 13 + d.m, off_h = off_g + np;
+  Fn wLi = fe_zero<FN>(), wRi = fe_zero<FN>(), wOi = fe_zero<FN>();
+  if (i < n) {
+    wLi = flatten_column(c, i, pr.zpow);
+    wRi = flatten_column(c, n + i, pr.zpow);
+    wOi = flatten_column(c, 2 * n + i, pr.zpow);
+  }
+  const Fn yneg_wR = mul(wRi, yi);                                              // verifier.rs:472-477
+  Fn g = sub(mul(o.x, yneg_wR), mul(o.a, si));                                  // verifier.rs:487-491
+  Fn h = sub(mul(yi, sub(add(mul(o.x, wLi), wOi), mul(o.b, sr))), fe_one<FN>());   // verifier.rs:493-501
+  if (i >= d.n1) { g = mul(o.u, g); h = mul(o.u, h); }
+  store_plain(&pr.fx[2 + i], g);
+  store_plain(&pr.fx[2 + np + i], h);
+  if (pr.full) { store_plain(&pr.full[off_g + i], g); store_plain(&pr.full[off_h + i], h); }
+  return mul(yneg_wR, wLi);                                                     // verifier.rs:479
+}
+// one term of the `One` column before its sign (w_c, verifier.rs:352-354)
+__device__ __forceinline__ Fn vs_one_term(const CircuitDev &c, const int32_t *zpow, size_t t) {
+  return mul(load_words(&c.coeff[t]), raw_get(zpow + (size_t)c.row[t] * NL));
+}
+// what every tail scalar reads: powers of the challenges, and where u_j^2 and u_j^-2 lie (NL ints each): LDS on the block-per-proof
+// route, aux on the grid-split one
+struct VsTail { Fn u, x, r, xx, rxx, xxx; const int32_t *usq, *uinvsq; };
+__device__ __forceinline__ VsTail vs_tail_operands(const VsProof &pr, const Fn &u, const Fn &x, const int32_t *usq, const int32_t *uinvsq) {
+  VsTail t;
+  t.u = u; t.x = x; t.r = load_plain(&pr.ch[5]);
+  t.xx = sqr(t.x); t.rxx = mul(t.r, t.xx); t.xxx = mul(t.x, t.xx);
+  t.usq = usq; t.uinvsq = uinvsq;
+  return t;
+}
+// what the scalar of B alone reads: delta and w_c (with its sign), reduced, and the proof's a and b
+struct VsB { Fn delta, wc, a, b; };
+// scalar v of the remaining 11 + m + 2k + 2 (verifier.rs:508-532): the proof points' in their order, then B and B_blinding
+__device__ __forceinline__ void vs_tail_scalar(const CircuitDev &c, const VerifyDims &d, const VsProof &pr, const VsTail &t, const VsB &bs,
+                                               size_t v) {
+  const size_t k = d.k, m = d.m, nvar = 11 + m + 2 * k, off_l = 13 + m + 2 * d.padded_n;
+  const Fn x = t.x, xx = t.xx, xxx = t.xxx;   // (picked by v below: as members of one object the pick would be an indexed load)
+  Fn val;
+  size_t fpos = v;
+  if (v < 3) val = v == 0 ? x : (v == 1 ? xx : xxx);                                             // A_I1 A_O1 S1
+  else if (v < 6) val = mul(t.u, v == 3 ? x : (v == 4 ? xx : xxx));                              // A_I2 A_O2 S2
+  else if (v < 6 + m) val = mul(flatten_column(c, 3 * d.n + (v - 6), pr.zpow), t.rxx);           // V_j: wV_j r x^2
+  else if (v < 11 + m) {                                                                          // T_1 T_3 T_4 T_5 T_6
+    const size_t ti = v - 6 - m;
+    val = ti == 0 ? mul(t.r, x) : ti == 1 ? mul(t.rxx, x) : ti == 2 ? mul(t.rxx, xx) : ti == 3 ? mul(t.rxx, xxx) : mul(mul(t.rxx, xx), xx);
+  } else if (v < 11 + m + k) { val = raw_get(t.usq + (v - 11 - m) * NL); fpos = off_l + (v - 11 - m); }                // L_j: u_j^2
+  else if (v < nvar) { val = raw_get(t.uinvsq + (v - 11 - m - k) * NL); fpos = off_l + k + (v - 11 - m - k); }         // R_j: u_j^-2
+  else if (v == nvar) {   // B: w (t_x - a b) + r (xx (wc + delta) - t_x)
+    const Fn w_ch = load_plain(&pr.ch[4]), t_x = load_plain(&pr.ps[0]);
+    val = add(mul(w_ch, sub(t_x, mul(bs.a, bs.b))), mul(t.r, sub(mul(xx, add(bs.wc, bs.delta)), t_x)));
+    fpos = 11 + m;
+  } else {                // B_blinding: -e_blinding - r t_x_blinding
+    val = neg(add(load_plain(&pr.ps[2]), mul(t.r, load_plain(&pr.ps[1]))));
+    fpos = 12 + m;
+  }
+  if (v < nvar) store_plain(&pr.vs[v], val);
+  else store_plain(&pr.fx[v - nvar], val);
+  if (pr.full) store_plain(&pr.full[fpos], val);
+}
+// k_verify_scalars, one wave per proof: z powers, g_i / h_i, delta, w_c and the remaining scalars.
 __global__ void __launch_bounds__(VS_TPB) k_verify_scalars(CircuitDev c, VerifyDims d, const Words8 *challenges,
                                                            const Words8 *proof_scalars, Words8 *fixed_sc,
                                                            Words8 *var_sc, Words8 *full_sc, int32_t *zpow_all,
@@ -631,29 +694,13 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars(CircuitDev c, VerifyD
   int32_t *s_usq = sm + 2 * NL, *s_uinvsq = sm + 34 * NL, *s_part = sm + VS_AUX * NL;
   const size_t p = blockIdx.x;
   const int tid = threadIdx.x;
-  const size_t k = d.k, n = d.n, np = d.padded_n, m = d.m, n1 = d.n1;
-  const Words8 *ch = challenges + p * (6 + k);
-  const Words8 *ps = proof_scalars + p * 5;
-  int32_t *zpow = zpow_all + p * c.qz * NL;
-  Fn y = load_plain(&ch[0]), z = load_plain(&ch[1]), u = load_plain(&ch[2]), x = load_plain(&ch[3]);
-  (void)y;
+  const size_t k = d.k, np = d.padded_n;
+  const VsProof pr = vs_proof(c, d, p, challenges, proof_scalars, zpow_all, fixed_sc, var_sc, full_sc);
+  const Fn z = load_plain(&pr.ch[1]);
   for (int t = tid; t < VS_AUX * NL; t += VS_TPB) sm[t] = aux_all[p * VS_AUX * NL + t];
-  if (bad || bad_proof) {   // canonical-encoding check of this proof's 6 + k challenges and 5 scalars (k_scalars_check)
-    bool mine = false;
-    for (size_t t = tid; t < 11 + k; t += VS_TPB) {
-      const Words8 *src = t < 6 + k ? &ch[t] : &ps[t - 6 - k];
-      uint32_t w[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = src->w[j];
-      if (!words_lt_mod<FN>(w)) mine = true;
-    }
-    const bool any = __any(mine);          // VS_TPB == 64: the block is one wave
-    if (tid == 0) {
-      if (any && bad) atomicOr(bad, 1);
-      if (bad_proof) bad_proof[p] = any ? 1 : 0;   // the only writer of this proof's entry: no reset needed
-    }
-  }
+  vs_check_proof(pr, k, p, bad, bad_proof);
   {   // z^(r+1) table (verifier.rs:336,358): lane r starts at z^(r+1) and steps by z^64
+    int32_t *zpow = zpow_all + p * c.qz * NL;                     // (read below as pr.zpow)
     Fn cur = mul(z, wave64_powers(z, tid, tab)), z64 = z;        // z^(tid + 1)
     for (int t = 0; t < 6; t++) z64 = sqr(z64);
     for (size_t r = tid; r < c.q; r += VS_TPB) {
@@ -663,16 +710,8 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars(CircuitDev c, VerifyD
     }
   }
   __syncthreads();
-  Fn y_inv = raw_get(sm + 0 * NL), allinv = raw_get(sm + 1 * NL);
-  Fn a = load_plain(&ps[3]), b = load_plain(&ps[4]);
-  const size_t nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
-  Words8 *fx = fixed_sc + p * (2 + 2 * np);
-  Words8 *vs = var_sc + p * nvar;
-  Words8 *full = full_sc ? full_sc + p * nterms : nullptr;
-  const size_t off_g = 13 + m, off_h = 13 + m + np;   // positions in verifier.rs:517-532 order
-
-  Fn dpart = fe_zero<FN>();
-  int dcnt = 0;
+  const Fn y_inv = raw_get(sm + 0 * NL), allinv = raw_get(sm + 1 * NL);
+  const VsGh gh = vs_gh_operands(pr);
   // one wave = one pass when the padded size is the wave size (the 64-bit range gadget): y^-i and s_i come from
   // two-level tables shared through LDS, s_{63-i} is read back from the table of the s_i (16 of the ~100 wave-level
   // products of this kernel less)
@@ -695,85 +734,32 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars(CircuitDev c, VerifyD
     __syncthreads();
     sr_w = raw_get(stab + (VS_TPB - 1 - tid) * NL);
   }
+  Fn dpart = fe_zero<FN>(), wcp = fe_zero<FN>();
+  int dcnt = 0, cnt = 0;
   for (size_t i = tid; i < np; i += VS_TPB) {
     if ((++dcnt & 15) == 0) dpart = fn_reduce(dpart);
-    Fn yi, si, sr;
-    if (wave_sized) { yi = yi_w; si = si_w; sr = sr_w; }
-    else {
-      yi = fn_pow_u32(y_inv, (uint32_t)i);                   // y^-i (verifier.rs:469-471)
-      // s_i and s_{np-1-i} (inner_product_proof.rs:298-307, closed form)
-      si = allinv; sr = allinv;
-      size_t ir = np - 1 - i;
-      for (size_t bb = 0; bb < k; bb++) {
-        Fn us = raw_get(s_usq + (k - 1 - bb) * NL);
-        if ((i >> bb) & 1) si = mul(si, us);
-        if ((ir >> bb) & 1) sr = mul(sr, us);
-      }
-    }
-    Fn wLi = fe_zero<FN>(), wRi = fe_zero<FN>(), wOi = fe_zero<FN>();
-    if (i < n) {
-      wLi = flatten_column(c, i, zpow);
-      wRi = flatten_column(c, n + i, zpow);
-      wOi = flatten_column(c, 2 * n + i, zpow);
-    }
-    Fn yneg_wR = mul(wRi, yi);                                // verifier.rs:472-477
-    dpart = add(dpart, mul(yneg_wR, wLi));                    // delta, verifier.rs:479
-    Fn g = sub(mul(x, yneg_wR), mul(a, si));                  // verifier.rs:487-491
-    Fn h = sub(mul(yi, sub(add(mul(x, wLi), wOi), mul(b, sr))), fe_one<FN>());   // verifier.rs:493-501
-    if (i >= n1) { g = mul(u, g); h = mul(u, h); }
-    store_plain(&fx[2 + i], g);
-    store_plain(&fx[2 + np + i], h);
-    if (full) { store_plain(&full[off_g + i], g); store_plain(&full[off_h + i], h); }
+    Fn yi = yi_w, si = si_w, sr = sr_w;
+    if (!wave_sized) vs_powers_at(y_inv, allinv, s_usq, k, np, i, yi, si, sr);
+    dpart = add(dpart, vs_gh(c, d, pr, gh, i, yi, si, sr));
   }
-  // w_c: the `One` column, its terms strided over the block (verifier.rs:352-354)
-  Fn wcp = fe_zero<FN>();
-  {
-    const size_t o = 3 * n + m;
-    int cnt = 0;
-    for (uint32_t t = c.col_ptr[o] + tid; t < c.col_ptr[o + 1]; t += VS_TPB) {
-      uint32_t w[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
-      wcp = add(wcp, mul(unpack<FN>(w), raw_get(zpow + (size_t)c.row[t] * NL)));
-      if ((++cnt & 15) == 0) wcp = fn_reduce(wcp);
-    }
+  const size_t o = 3 * d.n + d.m;   // the `One` column, its terms strided over the block
+  for (uint32_t t = c.col_ptr[o] + tid; t < c.col_ptr[o + 1]; t += VS_TPB) {
+    wcp = add(wcp, vs_one_term(c, pr.zpow, t));
+    if ((++cnt & 15) == 0) wcp = fn_reduce(wcp);
   }
-  dpart = wave_sum(fn_reduce(dpart));
-  wcp = wave_sum(fn_reduce(wcp));
+  dpart = block_sum<VS_TPB>(dpart);
+  wcp = block_sum<VS_TPB>(wcp);
   if (tid == 0) {
     raw_put(s_part, fn_reduce(dpart));
     raw_put(s_part + NL, fn_reduce(wcp));
   }
   __syncthreads();
-  // one lane per remaining output scalar (verifier.rs:508-532)
-  if ((size_t)tid < nvar + 2 || m > (size_t)VS_TPB) {
-    Fn delta = raw_get(s_part), wc = raw_get(s_part + NL);
-    wc = neg(wc);
-    Fn r = load_plain(&ch[5]);
-    Fn xx = sqr(x), rxx = mul(r, xx), xxx = mul(x, xx);
-    for (size_t v = tid; v < nvar + 2; v += VS_TPB) {
-      Fn val;
-      size_t fpos = v;
-      if (v < 3) val = v == 0 ? x : (v == 1 ? xx : xxx);                                  // A_I1 A_O1 S1
-      else if (v < 6) val = mul(u, v == 3 ? x : (v == 4 ? xx : xxx));                    // A_I2 A_O2 S2
-      else if (v < 6 + m) val = mul(flatten_column(c, 3 * n + (v - 6), zpow), rxx);      // V_j: wV_j r x^2
-      else if (v < 11 + m) {                                                              // T_1 T_3 T_4 T_5 T_6
-        size_t ti = v - 6 - m;
-        val = ti == 0 ? mul(r, x) : ti == 1 ? mul(rxx, x) : ti == 2 ? mul(rxx, xx) : ti == 3 ? mul(rxx, xxx) : mul(mul(rxx, xx), xx);
-      } else if (v < 11 + m + k) { val = raw_get(s_usq + (v - 11 - m) * NL); fpos = 13 + m + 2 * np + (v - 11 - m); }           // L_j: u_j^2
-      else if (v < nvar) { val = raw_get(s_uinvsq + (v - 11 - m - k) * NL); fpos = 13 + m + 2 * np + k + (v - 11 - m - k); }     // R_j: u_j^-2
-      else if (v == nvar) {   // B: w (t_x - a b) + r (xx (wc + delta) - t_x)
-        Fn w_ch = load_plain(&ch[4]), t_x = load_plain(&ps[0]);
-        val = add(mul(w_ch, sub(t_x, mul(a, b))), mul(r, sub(mul(xx, add(wc, delta)), t_x)));
-        fpos = 11 + m;
-      } else {                // B_blinding: -e_blinding - r t_x_blinding
-        val = neg(add(load_plain(&ps[2]), mul(r, load_plain(&ps[1]))));
-        fpos = 12 + m;
-      }
-      if (v < nvar) store_plain(&vs[v], val);
-      else store_plain(&fx[v - nvar], val);
-      if (full) store_plain(&full[fpos], val);
-    }
+  // one lane per remaining output scalar
+  const size_t ntail = 13 + d.m + 2 * k;
+  if ((size_t)tid < ntail || d.m > (size_t)VS_TPB) {
+    const VsTail tl = vs_tail_operands(pr, gh.u, gh.x, s_usq, s_uinvsq);
+    const VsB bs{raw_get(s_part), neg(raw_get(s_part + NL)), gh.a, gh.b};
+    for (size_t v = tid; v < ntail; v += VS_TPB) vs_tail_scalar(c, d, pr, tl, bs, v);
   }
 }
 // The same for WAVE-SIZED proofs (padded n = 64, k = 6) after the lane-per-proof pass has done everything serial (vs_prep.cuh,
@@ -790,25 +776,10 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars_fast(CircuitDev c, Ve
   const size_t p = blockIdx.x;
   const int tid = threadIdx.x;
   const size_t k = 6, n = d.n, np = 64, m = d.m, n1 = d.n1;
-  const Words8 *ch = challenges + p * (6 + k);
-  const Words8 *ps = proof_scalars + p * 5;
   int32_t *zpow = zpow_all + p * c.qz * NL;
   for (int t = tid; t < VS_AUX * NL; t += VS_TPB) sm[t] = aux_all[p * VS_AUX * NL + t];
-  if (bad || bad_proof) {   // canonical-encoding check of this proof's 6 + k challenges and 5 scalars
-    bool mine = false;
-    for (size_t t = tid; t < 11 + k; t += VS_TPB) {
-      const Words8 *src = t < 6 + k ? &ch[t] : &ps[t - 6 - k];
-      uint32_t w[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = src->w[j];
-      if (!words_lt_mod<FN>(w)) mine = true;
-    }
-    const bool any = __any(mine);
-    if (tid == 0) {
-      if (any && bad) atomicOr(bad, 1);
-      if (bad_proof) bad_proof[p] = any ? 1 : 0;
-    }
-  }
+  const VsProof pr = vs_proof(c, d, p, challenges, proof_scalars, zpow_all, fixed_sc, var_sc, full_sc);
+  vs_check_proof(pr, k, p, bad, bad_proof);
   __syncthreads();
   {   // z^(r+1), plain (verifier.rs:336,358): one table product, then steps of z^64
     Fn cur = mul(raw_get(sm + (VSF_Z1 + (tid & 7)) * NL), raw_get(sm + (VSF_Z2 + (tid >> 3)) * NL));
@@ -824,10 +795,7 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars_fast(CircuitDev c, Ve
   __syncthreads();           // the z-power table (global) and the s table (LDS) are complete
   const Fn sr = raw_get(stab + (VS_TPB - 1 - tid) * NL);
   const Fn xm = raw_get(sm + VSF_X * NL), um = raw_get(sm + VSF_U * NL), am = raw_get(sm + VSF_A * NL), bm = raw_get(sm + VSF_B * NL);
-  const size_t nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
-  Words8 *fx = fixed_sc + p * (2 + 2 * np);
-  Words8 *vs = var_sc + p * nvar;
-  Words8 *full = full_sc ? full_sc + p * nterms : nullptr;
+  Words8 *fx = pr.fx, *vs = pr.vs, *full = pr.full;
   const size_t off_g = 13 + m, off_h = 13 + m + np, i = tid;
   Fn one_p = fe_zero<FN>();
   one_p.v[0] = 1;
@@ -838,28 +806,22 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars_fast(CircuitDev c, Ve
     wOi = flatten_column(c, 2 * n + i, zpow);
   }
   const Fn yneg_wR = mul(wRi, yi);                                                       // P, verifier.rs:472-477
-  Fn dpart = mul(yneg_wR, wLi);                                                          // delta_i / R (two plain factors)
+  const Fn dpart = mul(yneg_wR, wLi);                                                    // delta_i / R (two plain factors)
   Fn g = sub(mul(xm, yneg_wR), mul(am, si));                                             // P, verifier.rs:487-491
   Fn h = sub(mul(yi, sub(add(mul(xm, wLi), wOi), mul(bm, sr))), one_p);                  // P, verifier.rs:493-501
   if (i >= n1) { g = mul(um, g); h = mul(um, h); }
   vs_store_p(&fx[2 + i], g);
   vs_store_p(&fx[2 + np + i], h);
   if (full) { vs_store_p(&full[off_g + i], g); vs_store_p(&full[off_h + i], h); }
-  Fn wcp = fe_zero<FN>();                                                                // w_c (plain): the `One` column, verifier.rs:352-354
-  {
-    const size_t o = 3 * n + m;
-    int cnt = 0;
-    for (uint32_t t = c.col_ptr[o] + tid; t < c.col_ptr[o + 1]; t += VS_TPB) {
-      uint32_t w[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
-      wcp = add(wcp, mul(unpack<FN>(w), raw_get(zpow + (size_t)c.row[t] * NL)));
-      if ((++cnt & 15) == 0) wcp = fn_reduce(wcp);
-    }
+  Fn wcp = fe_zero<FN>();                                                                // w_c (plain): the `One` column
+  int cnt = 0;
+  const size_t o = 3 * n + m;
+  for (uint32_t t = c.col_ptr[o] + tid; t < c.col_ptr[o + 1]; t += VS_TPB) {
+    wcp = add(wcp, vs_one_term(c, zpow, t));
+    if ((++cnt & 15) == 0) wcp = fn_reduce(wcp);
   }
-  dpart = wave_sum(fn_reduce(dpart));
-  wcp = wave_sum(fn_reduce(wcp));
-  if (tid == 0) { raw_put(s_part, fn_reduce(dpart)); raw_put(s_part + NL, fn_reduce(wcp)); }
+  const Fn dsum = block_sum<VS_TPB>(dpart), wsum = block_sum<VS_TPB>(wcp);
+  if (tid == 0) { raw_put(s_part, fn_reduce(dsum)); raw_put(s_part + NL, fn_reduce(wsum)); }
   __syncthreads();
   // V_j (one lane each) and B (verifier.rs:508-532); everything else was written by the lane-per-proof pass
   const Fn c1m = raw_get(sm + VSF_C1 * NL);
@@ -880,134 +842,69 @@ __global__ void __launch_bounds__(VS_TPB) k_verify_scalars_fast(CircuitDev c, Ve
 // aux per proof (NL ints each): 0 y_inv, 1 allinv, 2.. u_sq[32], 34.. u_inv_sq[32], 66.. delta partials[VSL_PARTS],
 // then w_c partials[VSL_PARTS]
 constexpr int VSL_PARTS = 256, VSL_AUX = VS_AUX + 2 * VSL_PARTS, VSL_TPB = 128;
-// g_i, h_i (verifier.rs:469-501) + per-block delta partial; blockIdx.y = proof; grid-stride over i
+// a block's partial of the grid-split sums: every wave's sum REDUCED, then added by thread 0 -- two reduced values, which k_vsl_tail
+// adds up lazily (block_sum would hand it 128)
+__device__ __forceinline__ void vsl_put_partial(const Fn &lane, int32_t *dst) {
+  __shared__ int32_t s_part[NL * (VSL_TPB / 64)];
+  const int tid = threadIdx.x;
+  const Fn w = wave_sum(fn_reduce(lane));
+  if ((tid & 63) == 0) raw_put(s_part + (tid >> 6) * NL, fn_reduce(w));
+  __syncthreads();
+  if (tid == 0) {
+    Fn t = raw_get(s_part);
+    for (int i = 1; i < VSL_TPB / 64; i++) t = add(t, raw_get(s_part + i * NL));
+    raw_put(dst, t);
+  }
+}
+// g_i, h_i + per-block delta partial; blockIdx.y = proof; grid-stride over i
 __global__ void __launch_bounds__(VSL_TPB) k_vsl_gh(CircuitDev c, VerifyDims d, const Words8 *challenges,
                                                     const Words8 *proof_scalars, Words8 *fixed_sc, Words8 *full_sc,
                                                     const int32_t *zpow_all, int32_t *aux_all) {
-  __shared__ int32_t s_part[NL * (VSL_TPB / 64)];
   const size_t p = blockIdx.y;
-  const int tid = threadIdx.x;
-  const size_t k = d.k, n = d.n, np = d.padded_n, m = d.m, n1 = d.n1;
-  const Words8 *ch = challenges + p * (6 + k);
-  const Words8 *ps = proof_scalars + p * 5;
-  const int32_t *zpow = zpow_all + p * c.qz * NL;
+  const VsProof pr = vs_proof(c, d, p, challenges, proof_scalars, zpow_all, fixed_sc, nullptr, full_sc);
   int32_t *aux = aux_all + p * VSL_AUX * NL;
-  const int32_t *s_usq = aux + 2 * NL;
-  Fn u = load_plain(&ch[2]), x = load_plain(&ch[3]);
-  Fn y_inv = raw_get(aux), allinv = raw_get(aux + NL);
-  Fn a = load_plain(&ps[3]), b = load_plain(&ps[4]);
-  const size_t nterms = 13 + m + 2 * np + 2 * k;
-  Words8 *fx = fixed_sc + p * (2 + 2 * np);
-  Words8 *full = full_sc ? full_sc + p * nterms : nullptr;
-  const size_t off_g = 13 + m, off_h = 13 + m + np;
+  const Fn y_inv = raw_get(aux), allinv = raw_get(aux + NL);
+  const VsGh gh = vs_gh_operands(pr);
   Fn dpart = fe_zero<FN>();
   int dcnt = 0;
-  for (size_t i = (size_t)blockIdx.x * VSL_TPB + tid; i < np; i += (size_t)gridDim.x * VSL_TPB) {
+  for (size_t i = (size_t)blockIdx.x * VSL_TPB + threadIdx.x; i < d.padded_n; i += (size_t)gridDim.x * VSL_TPB) {
     if ((++dcnt & 15) == 0) dpart = fn_reduce(dpart);
-    Fn yi = fn_pow_u32(y_inv, (uint32_t)i);
-    Fn si = allinv, sr = allinv;
-    size_t ir = np - 1 - i;
-    for (size_t bb = 0; bb < k; bb++) {
-      Fn us = raw_get(s_usq + (k - 1 - bb) * NL);
-      if ((i >> bb) & 1) si = mul(si, us);
-      if ((ir >> bb) & 1) sr = mul(sr, us);
-    }
-    Fn wLi = fe_zero<FN>(), wRi = fe_zero<FN>(), wOi = fe_zero<FN>();
-    if (i < n) {
-      wLi = flatten_column(c, i, zpow);
-      wRi = flatten_column(c, n + i, zpow);
-      wOi = flatten_column(c, 2 * n + i, zpow);
-    }
-    Fn yneg_wR = mul(wRi, yi);
-    dpart = add(dpart, mul(yneg_wR, wLi));
-    Fn g = sub(mul(x, yneg_wR), mul(a, si));
-    Fn h = sub(mul(yi, sub(add(mul(x, wLi), wOi), mul(b, sr))), fe_one<FN>());
-    if (i >= n1) { g = mul(u, g); h = mul(u, h); }
-    store_plain(&fx[2 + i], g);
-    store_plain(&fx[2 + np + i], h);
-    if (full) { store_plain(&full[off_g + i], g); store_plain(&full[off_h + i], h); }
+    Fn yi, si, sr;
+    vs_powers_at(y_inv, allinv, aux + 2 * NL, d.k, d.padded_n, i, yi, si, sr);
+    dpart = add(dpart, vs_gh(c, d, pr, gh, i, yi, si, sr));
   }
-  dpart = wave_sum(fn_reduce(dpart));
-  if ((tid & 63) == 0) raw_put(s_part + (tid >> 6) * NL, fn_reduce(dpart));
-  __syncthreads();
-  if (tid == 0) {
-    Fn t = raw_get(s_part);
-    for (int w = 1; w < VSL_TPB / 64; w++) t = add(t, raw_get(s_part + w * NL));
-    raw_put(aux + (66 + blockIdx.x) * NL, t);
-  }
+  vsl_put_partial(dpart, aux + (66 + blockIdx.x) * NL);
 }
-// partial sums of the `One` column (w_c before the sign, verifier.rs:352-354)
+// partial sums of the `One` column
 __global__ void __launch_bounds__(VSL_TPB) k_vsl_wc(CircuitDev c, VerifyDims d, const int32_t *zpow_all, int32_t *aux_all) {
-  __shared__ int32_t s_part[NL * (VSL_TPB / 64)];
   const size_t p = blockIdx.y;
-  const int tid = threadIdx.x;
   const int32_t *zpow = zpow_all + p * c.qz * NL;
-  int32_t *aux = aux_all + p * VSL_AUX * NL;
   const size_t o = 3 * d.n + d.m;
   Fn wcp = fe_zero<FN>();
   int cnt = 0;
-  for (size_t t = (size_t)c.col_ptr[o] + (size_t)blockIdx.x * VSL_TPB + tid; t < c.col_ptr[o + 1]; t += (size_t)gridDim.x * VSL_TPB) {
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = c.coeff[t].w[j];
-    wcp = add(wcp, mul(unpack<FN>(w), raw_get(zpow + (size_t)c.row[t] * NL)));
+  for (size_t t = (size_t)c.col_ptr[o] + (size_t)blockIdx.x * VSL_TPB + threadIdx.x; t < c.col_ptr[o + 1]; t += (size_t)gridDim.x * VSL_TPB) {
+    wcp = add(wcp, vs_one_term(c, zpow, t));
     if ((++cnt & 15) == 0) wcp = fn_reduce(wcp);
   }
-  wcp = wave_sum(fn_reduce(wcp));
-  if ((tid & 63) == 0) raw_put(s_part + (tid >> 6) * NL, fn_reduce(wcp));
-  __syncthreads();
-  if (tid == 0) {
-    Fn t = raw_get(s_part);
-    for (int w = 1; w < VSL_TPB / 64; w++) t = add(t, raw_get(s_part + w * NL));
-    raw_put(aux + (66 + VSL_PARTS + blockIdx.x) * NL, t);
-  }
+  vsl_put_partial(wcp, aux_all + (p * VSL_AUX + 66 + VSL_PARTS + blockIdx.x) * NL);
 }
-// the remaining 11 + m + 2k + 2 scalars (verifier.rs:508-532), one lane each
+// the remaining 11 + m + 2k + 2 scalars, one lane each
 __global__ void __launch_bounds__(VSL_TPB) k_vsl_tail(CircuitDev c, VerifyDims d, const Words8 *challenges,
                                                       const Words8 *proof_scalars, Words8 *fixed_sc, Words8 *var_sc,
                                                       Words8 *full_sc, const int32_t *zpow_all, const int32_t *aux_all,
                                                       int gh_parts, int wc_parts) {
-  const size_t p = blockIdx.y;
-  const size_t k = d.k, n = d.n, np = d.padded_n, m = d.m;
-  const size_t nvar = 11 + m + 2 * k, nterms = 13 + m + 2 * np + 2 * k;
-  const size_t v = (size_t)blockIdx.x * VSL_TPB + threadIdx.x;
-  if (v >= nvar + 2) return;
-  const Words8 *ch = challenges + p * (6 + k);
-  const Words8 *ps = proof_scalars + p * 5;
-  const int32_t *zpow = zpow_all + p * c.qz * NL;
+  const size_t p = blockIdx.y, v = (size_t)blockIdx.x * VSL_TPB + threadIdx.x;
+  if (v >= 13 + d.m + 2 * d.k) return;
+  const VsProof pr = vs_proof(c, d, p, challenges, proof_scalars, zpow_all, fixed_sc, var_sc, full_sc);
   const int32_t *aux = aux_all + p * VSL_AUX * NL;
-  Words8 *fx = fixed_sc + p * (2 + 2 * np);
-  Words8 *vs = var_sc + p * nvar;
-  Words8 *full = full_sc ? full_sc + p * nterms : nullptr;
-  Fn u = load_plain(&ch[2]), x = load_plain(&ch[3]), r = load_plain(&ch[5]);
-  Fn xx = sqr(x), rxx = mul(r, xx), xxx = mul(x, xx);
-  Fn val;
-  size_t fpos = v;
-  if (v < 3) val = v == 0 ? x : (v == 1 ? xx : xxx);
-  else if (v < 6) val = mul(u, v == 3 ? x : (v == 4 ? xx : xxx));
-  else if (v < 6 + m) val = mul(flatten_column(c, 3 * n + (v - 6), zpow), rxx);
-  else if (v < 11 + m) {
-    size_t ti = v - 6 - m;
-    val = ti == 0 ? mul(r, x) : ti == 1 ? mul(rxx, x) : ti == 2 ? mul(rxx, xx) : ti == 3 ? mul(rxx, xxx) : mul(mul(rxx, xx), xx);
-  } else if (v < 11 + m + k) { val = raw_get(aux + (2 + v - 11 - m) * NL); fpos = 13 + m + 2 * np + (v - 11 - m); }
-  else if (v < nvar) { val = raw_get(aux + (34 + v - 11 - m - k) * NL); fpos = 13 + m + 2 * np + k + (v - 11 - m - k); }
-  else if (v == nvar) {
+  VsB bs{fe_zero<FN>(), fe_zero<FN>(), fe_zero<FN>(), fe_zero<FN>()};
+  if (v == 11 + d.m + 2 * d.k) {   // B: the blocks' partials
     Fn delta = fe_zero<FN>(), wc = fe_zero<FN>();
     for (int i = 0; i < gh_parts; i++) { delta = add(delta, raw_get(aux + (66 + i) * NL)); if ((i & 7) == 7) delta = fn_reduce(delta); }
     for (int i = 0; i < wc_parts; i++) { wc = add(wc, raw_get(aux + (66 + VSL_PARTS + i) * NL)); if ((i & 7) == 7) wc = fn_reduce(wc); }
-    delta = fn_reduce(delta);
-    wc = neg(fn_reduce(wc));
-    Fn w_ch = load_plain(&ch[4]), t_x = load_plain(&ps[0]);
-    Fn a = load_plain(&ps[3]), b = load_plain(&ps[4]);
-    val = add(mul(w_ch, sub(t_x, mul(a, b))), mul(r, sub(mul(xx, add(wc, delta)), t_x)));
-    fpos = 11 + m;
-  } else {
-    val = neg(add(load_plain(&ps[2]), mul(r, load_plain(&ps[1]))));
-    fpos = 12 + m;
+    bs = VsB{fn_reduce(delta), neg(fn_reduce(wc)), load_plain(&pr.ps[3]), load_plain(&pr.ps[4])};
   }
-  if (v < nvar) store_plain(&vs[v], val);
-  else store_plain(&fx[v - nvar], val);
-  if (full) store_plain(&full[fpos], val);
+  vs_tail_scalar(c, d, pr, vs_tail_operands(pr, load_plain(&pr.ch[2]), load_plain(&pr.ch[3]), aux + 2 * NL, aux + 34 * NL), bs, v);
 }
 
 bool verify_scalars_fast_shape(const CircuitDev &c, const VerifyDims &d) { return vs_fast_shape(d) && c.nchi == 0 && d.m <= 64; }
@@ -1050,8 +947,6 @@ void verify_scalars(hipStream_t st, const CircuitDev &c, const VerifyDims &d, co
     hipLaunchKernelGGL(k_scalars_check_proof, dim3((d.nb * 5 + 255) / 256), dim3(256), 0, st, proof_scalars, d.nb * 5, (size_t)5, bad, bad_proof);
   } else if (bad) { scalars_check(st, challenges, d.nb * (6 + d.k), bad); scalars_check(st, proof_scalars, d.nb * 5, bad); }
   auto parts = [](size_t work) { size_t b = (work + VSL_TPB - 1) / VSL_TPB; return (int)(b < 1 ? 1 : (b > VSL_PARTS ? VSL_PARTS : b)); };
-  const size_t o = 3 * d.n + d.m;
-  (void)o;
   // number of `One` terms is only known on the device (col_ptr); size its grid from the row count
   const int gh_parts = parts(d.padded_n), wc_parts = parts(c.q);
   hipLaunchKernelGGL(k_vs_prep, dim3((d.nb + 63) / 64), dim3(64), 0, st, VsPrepArgs{d, challenges, aux, (size_t)VSL_AUX});

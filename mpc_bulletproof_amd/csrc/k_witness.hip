@@ -147,16 +147,9 @@ __global__ void __launch_bounds__(256) k_witness_convert(bool to_ark, size_t nb,
   const Words8 *in = src + p * src_stride + k;
   Words8 *out = dst + p * dst_stride + k;
   constexpr int32_t CIN[NL] = FN_ARK_IN, COUT[NL] = FN_ARK_OUT;
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = in->w[j];
-  if (!words_lt_mod<FN>(w)) {
-    atomicOr(bad, 1);
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = 0;
-  } else {
-    pack(w, canon(mul(unpack<FN>(w), to_ark ? wit_const(COUT) : wit_const(CIN))));
-  }
+  uint32_t w[8] = {};
+  if (!words_canonical(in)) atomicOr(bad, 1);
+  else pack(w, canon(mul(load_words(in), to_ark ? wit_const(COUT) : wit_const(CIN))));
 #pragma unroll
   for (int j = 0; j < 8; j++) out->w[j] = w[j];
 }

@@ -36,12 +36,7 @@ __device__ __forceinline__ void vs_store_p(Words8 *p, const Fn &x) {   // a PLAI
 #pragma unroll
   for (int j = 0; j < 8; j++) p->w[j] = w[j];
 }
-__device__ __forceinline__ Fn vs_load_p(const Words8 *p) {             // canonical words -> PLAIN limbs (no conversion product)
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) w[j] = p->w[j];
-  return unpack<FN>(w);
-}
+__device__ __forceinline__ Fn vs_load_p(const Words8 *p) { return load_words(p); }   // canonical words -> PLAIN limbs (no conversion product)
 
 // proof p (one lane)
 __device__ __forceinline__ void vs_prep_lane(const VsPrepArgs &a, size_t p) {

@@ -75,15 +75,6 @@ void print_plain(const Fn &x) {   // store_plain's conversion
 void print_limbs(const Fn &x) {
   for (int j = 0; j < NL; j++) printf("%s%d", j ? "," : "", x.v[j]);
 }
-Fn pow_u32(Fn base, uint32_t e) {   // fn_pow_u32 of fn_dev.cuh (device only there)
-  Fn acc = fe_one<FN>();
-  while (e) {
-    if (e & 1) acc = mul(acc, base);
-    e >>= 1;
-    if (e) base = sqr(base);
-  }
-  return acc;
-}
 // wave_sum's butterfly over the 64 lanes of one wave: every lane adds its partner's value, off = 32, 16, .., 1
 Fn wave_sum_host(Fn *x) {
   for (int off = 32; off > 0; off >>= 1) {
@@ -160,8 +151,8 @@ int main(int argc, char **argv) {
       Fn aL, aR, y;
       unsigned i;
       if (!read_fn(f, &aL) || !read_fn(f, &aR) || !read_fn(f, &y) || fscanf(f, "%x", &i) != 1) return 4;
-      const Fn yi = pow_u32(y, i);
-      const Fn l = add(aL, mul(pow_u32(y, i), zero)), r0 = sub(zero, yi), r1 = add(mul(yi, aR), zero);
+      const Fn yi = fn_pow_u32(y, i);
+      const Fn l = add(aL, mul(fn_pow_u32(y, i), zero)), r0 = sub(zero, yi), r1 = add(mul(yi, aR), zero);
       print_limbs(mul(l, r0));
       printf(" ");
       print_limbs(mul(l, r1));

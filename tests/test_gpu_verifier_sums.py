@@ -9,6 +9,8 @@ The expected point: every proof point is a known multiple of the generator B, B_
 generators' discrete logarithms, so sum scalar * point = (sum scalar * dlog) B: one oracle scalar multiplication.  Proof points
 coincide freely; none is the identity.  Every even proof's e_blinding is chosen so that its sum vanishes: those proofs are accepted.
 Run with `-m gpu` on an MI355X."""
+import random
+
 import pytest
 
 import mpc_dealer as md
@@ -93,9 +95,9 @@ def point_choice(p, nvar):
     return [(5 * p + j) % len(POOL_DLOGS) for j in range(nvar)]
 
 
-def prepare(case, gens):
+def prepare(case, gens, accepted=lambda p: p % 2 == 0):
     """the operands and expectations of a case's proofs: (scalars bytes, challenges bytes, point indices, full per proof, total per
-    proof); every even proof's e_blinding makes its total vanish"""
+    proof); every even proof's e_blinding (every proof's that `accepted` names) makes its total vanish"""
     m, k = case.m, case.k
     nvar = 11 + m + 2 * k
     fulls = case.model()
@@ -104,7 +106,7 @@ def prepare(case, gens):
         choice = point_choice(p, nvar)
         dl = gens.dlogs(m, k, [POOL_DLOGS[i] for i in choice])
         ps = list(ps)
-        if p % 2 == 0:
+        if accepted(p):
             rest = sum(s * d for j, (s, d) in enumerate(zip(full, dl)) if j != 12 + m)
             full[12 + m] = -rest % N                                  # B_blinding's scalar -e_blinding - r t_x_blinding
             ps[2] = (rest - chal[5] * ps[1]) % N
@@ -113,7 +115,7 @@ def prepare(case, gens):
         sc.append(b"".join(le(s) for s in ps))
         ch.append(b"".join(le(c) for c in chal))
         idx.append(choice)
-    assert all((t == 0) == (p % 2 == 0) for p, t in enumerate(totals)), case.name
+    assert all((t == 0) == accepted(p) for p, t in enumerate(totals)), case.name
     return b"".join(sc), b"".join(ch), idx, fulls, totals
 
 
@@ -144,6 +146,47 @@ def run_case(gpu, gens, pool, opts, case, routes):
 
 DEFAULT_ROUTES = [(1, False), (0, False)]                  # the window-parallel chain, a Straus route
 ALL_ROUTES = DEFAULT_ROUTES + [(1, True), (0, True)]       # ... and both again through the grid-split kernels
+
+
+# ------------------------------------------------------------------------------------------------ the canonical check
+@pytest.mark.parametrize("shape", ["fast", "general"])
+def test_one_non_canonical_word_rejects_its_proof_on_every_form(gpu, big, pool, opts, shape):
+    """Proof 1 of three gets one non-canonical word -- its first or last challenge (y, u_k), its first or last proof scalar (t_x, b);
+    the value n or 2^256 - 1 -- on all four routes: the per-proof check inside k_verify_scalars_fast (shape fast) and
+    k_verify_scalars (general), and k_scalars_check_proof in front of the grid-split kernels (vs_large_min = 1).  That proof is
+    rejected where the unmodified call accepts all three, the other two keep their ok, mega and full, the call succeeds, and the
+    context's input flag reads 1, then 0."""
+    case = vc.column_case(shape, 1, random.Random("canonical " + shape))
+    case.check()
+    m, k, nb = case.m, case.k, len(case.proofs)
+    assert nb == 3 and case.takes_large_route(1) and not case.takes_large_route()
+    sc, ch, idx, fulls, totals = prepare(case, big, accepted=lambda p: True)
+    pts = b"".join(pool[i] for choice in idx for i in choice)
+    per_full = 32 * len(fulls[0])
+    spots = [("challenge", 0), ("challenge", 5 + k), ("scalar", 0), ("scalar", 4)]
+    h = gpu.circuit_create(*case.csr(), case.n, case.m)
+    try:
+        for wp, large in ALL_ROUTES:
+            opts(verify_window_parallel=wp, vs_large_min=1 if large else VS_LARGE_DEFAULT)
+            ok0, mega0, full0 = gpu.r1cs_verify_batch(big.handle, h, nb, case.n1, k, m, pts, sc, ch, True, True)
+            assert ok0 == [1, 1, 1] and gpu.input_flag() == 0
+            assert full0 == b"".join(le(s) for full in fulls for s in full)
+            for what, j in spots:
+                for value in (N, (1 << 256) - 1):
+                    bad_sc, bad_ch = bytearray(sc), bytearray(ch)
+                    if what == "challenge":
+                        bad_ch[32 * ((6 + k) + j):32 * ((6 + k) + j + 1)] = value.to_bytes(32, "little")
+                    else:
+                        bad_sc[32 * (5 + j):32 * (5 + j + 1)] = value.to_bytes(32, "little")
+                    ok, mega, full = gpu.r1cs_verify_batch(big.handle, h, nb, case.n1, k, m, pts, bytes(bad_sc), bytes(bad_ch), True, True)
+                    tag = (shape, wp, large, what, j, hex(value))
+                    assert ok[1] == 0 and [ok[0], ok[2]] == [ok0[0], ok0[2]], tag
+                    for p_ in (0, 2):
+                        assert mega[64 * p_:64 * p_ + 64] == mega0[64 * p_:64 * p_ + 64], tag
+                        assert full[per_full * p_:per_full * (p_ + 1)] == full0[per_full * p_:per_full * (p_ + 1)], tag
+                    assert gpu.input_flag() == 1 and gpu.input_flag() == 0, tag
+    finally:
+        gpu.circuit_destroy(h)
 
 
 # ------------------------------------------------------------------------------------------------ the `One` column
