@@ -575,10 +575,28 @@ int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c,
  * factors that read nothing of their phase, and F_n multiplication is exactly associative on canonical values: a 256-thread block
  * scans all chains headed at one level together (segmented, no inversion: a zero factor zeroes the rest of its chain) in about
  * 2 ceil(M / 256) + 10 dependent multiplications for M members, and stores the bytes the gates one by one give.  In the compressed
- * levels a member takes its predecessor's level.  bpgpu_witness_chains reports the chains.  Only chains of pure products stop being
- * serial: a general dependent chain such as (a_O[i - 1] + v) w is still serial, one level per gate.
+ * levels a member takes its predecessor's level.  bpgpu_witness_chains reports the chains, and product chains only.
+ * A second pass over the program, once every product member is known, finds the AFFINE chains.  In program order, a BPGPU_GATE_MUL
+ * that pass 1 left without a predecessor is an affine member with predecessor j when one of its rows (the left is tried first) is
+ * an affine LINK row -- it holds exactly ONE stored term, over all 1 + nchi blocks, of kind 0..2 on a gate of the same phase; that
+ * term is of kind 2, on a gate j that has no member successor of either kind yet (a product gate keeps its a_O whatever the order);
+ * beside it the row may hold any number of terms that read nothing of the phase: committed values, One, multipliers of phase 1 in a
+ * phase-2 gate, with or without chi parts -- and the other row is free as above.  An explicit zero coefficient is still a term, and
+ * a link coefficient split over two blocks (c0 + chi c1 on the same a_O[j]) is TWO terms: that gate stays ordinary.  With the link
+ * row c a_O[j] + f and the free row g, a_O[i] = (c g) a_O[j] + f g: the affine map x -> A x + B with A = c g, B = f g, and a product
+ * member is the map with f = 0.  Affine maps compose associatively, (A2, B2) o (A1, B1) = (A2 A1, A2 B1 + B2), so the EXTENDED chains
+ * -- product and affine members in any order; a gate that pass 1 called a head may become a member -- are evaluated by the same scan
+ * as a segmented prefix composition, in the same number of steps, and store the bytes the gates one by one give (a zero g leaves B
+ * alone for the rest of its chain).  This covers Horner evaluation of committed vectors at a challenge, running sums scaled by a
+ * challenge factor, any accumulate-then-multiply loop.  In the extended compressed levels a member of either kind takes its
+ * predecessor's level; a phase that has an affine member is scanned over those.  bpgpu_witness_affine_chains reports them.
+ * What is still serial, one level per gate: a gate both of whose rows read its phase (a squaring, the x^5 of a Poseidon round), a
+ * link through a_L or a_R, and a link coefficient split over blocks.
  * The route is a function of the program's shape and nb alone, never of the data: bpgpu_witness_plan (no device needed) reports
- * what the library takes.  A phase whose longest chain has BPGPU_OPT_WITNESS_SCAN_MIN members or more takes the scan form: the
+ * what the library takes.  A phase takes the scan form when its longest product chain has BPGPU_OPT_WITNESS_SCAN_MIN members or more,
+ * or when its longest extended chain has max(BPGPU_OPT_WITNESS_SCAN_MIN, 16) members or more (the 16 by the rule below on Horner
+ * gadgets of 8 .. 16 382 members, profiles/witness_affine.log: at 16 members 0.053 against 0.176 ms for 1 prover and 0.061 against
+ * 0.215 ms for 256, more provers UNMEASURED; BPGPU_OPT_WITNESS_SCAN_MIN 1 scans every chain of either kind, 0 none).  For product chains the
  * default, 16, is the smallest power of two >= 16 from which on the scan form's slowest step lay below the block form's fastest for 1
  * and for 256 provers (profiles/witness_synth.log, chains of 8 .. 16 382 members; at 16 members 0.053 against 0.200 ms and 0.058
  * against 0.222 ms), and 4096 provers of the 64-shuffle (62 members) take 0.273 ms scanned, 1.273 ms on lanes, 3.217 ms in blocks;
@@ -600,7 +618,7 @@ void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w);
 #define BPGPU_WIT_PLAN_LONG_ROWS 3    /* rows of more than 64 terms (a wave's in the block form) */
 #define BPGPU_WIT_PLAN_INPUTS 4       /* INPUT gates: pairs of `inputs` per prover */
 #define BPGPU_WIT_PLAN_ROUTE1 5       /* launch form of phase 1: 1 = a lane per prover, 2 = a block per prover, 3 = a block per prover with
-                                       * the product chains scanned (at the default BPGPU_OPT_WITNESS_SCAN_MIN); 0: no gates */
+                                       * the product and affine chains scanned (at the default BPGPU_OPT_WITNESS_SCAN_MIN); 0: no gates */
 #define BPGPU_WIT_PLAN_ROUTE2 6       /* ... of phase 2 */
 #define BPGPU_WIT_PLAN_FIELDS 7
 int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
@@ -618,6 +636,23 @@ int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, cons
 #define BPGPU_WIT_CHAIN_FIELDS 8
 int bpgpu_witness_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
                          const uint32_t *idx, int32_t out[BPGPU_WIT_CHAIN_FIELDS]);
+/* The EXTENDED chains of a gate program -- product and affine members together ("affine member" above) -- from its shape alone (no
+ * device needed): per phase the number of chains, of all their members, of the members that pass 2 added (the affine ones), the
+ * members of the longest chain and the extended compressed levels, which the scan form walks.  A program without an affine member
+ * reports the figures of bpgpu_witness_chains.  Refusals: those of bpgpu_witness_plan. */
+#define BPGPU_WIT_AFF_CHAINS1 0
+#define BPGPU_WIT_AFF_CHAINS2 1
+#define BPGPU_WIT_AFF_MEMBERS1 2
+#define BPGPU_WIT_AFF_MEMBERS2 3
+#define BPGPU_WIT_AFF_AFFINE1 4
+#define BPGPU_WIT_AFF_AFFINE2 5
+#define BPGPU_WIT_AFF_LONGEST1 6
+#define BPGPU_WIT_AFF_LONGEST2 7
+#define BPGPU_WIT_AFF_LEVELS1 8
+#define BPGPU_WIT_AFF_LEVELS2 9
+#define BPGPU_WIT_AFF_FIELDS 10
+int bpgpu_witness_affine_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                                const uint32_t *idx, int32_t out[BPGPU_WIT_AFF_FIELDS]);
 /* The witnesses of nb provers of one gate program, where the provers read them.
  *   v                  nb x m          the committed values, ark form: the buffer bpgpu_r1cs_commit_values and
  *                                      bpgpu_r1cs_constraints_satisfied take; may be NULL when m == 0
@@ -637,9 +672,12 @@ int bpgpu_witness_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, co
  * of pure products is no longer serial: ONE prover's k = 2^14 shuffle, two chains of 16 382 members, takes 1.470 ms scanned
  * (profiles/witness_synth.log) where the block form takes 186 ms and an interpreted host 54 ms, and one 2^10-shuffle prover is proved
  * by bpgpu_r1cs_prove_fs2 in 4.7 ms against 10.1 ms for bpgpu_r1cs_prove_fs2_begin / _finish around that host's gadget.  Batches: 256
- * provers of the 64-shuffle in 0.057 ms, of 16 x 64-bit range values in 0.07 ms.  What is still serial is a general dependent chain
- * (each gate adding to or otherwise mixing the gate before it): a caller with few provers and long chains of THAT kind keeps its
- * host's Prover::multiply.
+ * provers of the 64-shuffle in 0.057 ms, of 16 x 64-bit range values in 0.07 ms.  An accumulate-then-multiply chain such as
+ * (a_O[i - 1] + v) w is an affine chain and scanned as well: ONE prover's Horner evaluation of two committed vectors of 2^14 values,
+ * two chains of 16 382 affine members, takes 1.913 ms where the block form takes 165 ms and that host 50 ms
+ * (profiles/witness_affine.log).  What is still serial is a chain of gates both of whose rows read their phase (a squaring, the x^5
+ * of a Poseidon round), a link through a_L or a_R, or a link coefficient split over blocks: a caller with few provers and long chains
+ * of THAT kind keeps its host's Prover::multiply.
  * Out of scope: the host mirror (mpc_bulletproof.hpp: its multiply keeps evaluating on the host), the pool forms (bpgpu_pool_*),
  * the two-party prover (a product of shares is a Beaver step, not a local product) and bench.py. */
 int bpgpu_r1cs_witness_synthesize(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const uint8_t *v, const uint8_t *inputs,

@@ -18,6 +18,9 @@ __attribute__((visibility("hidden"))) int bpgpu_internal_verify_stream(bpgpu_ctx
 struct bpgpu_internal_view { hipStream_t st; int *d_flag; int64_t witness_route, witness_scan_min; size_t shard_world; };
 // BPGPU_OPT_WITNESS_SCAN_MIN as a context starts with it, and as bpgpu_witness_plan (which has no context) reports routes
 constexpr int64_t WIT_SCAN_MIN_DEFAULT = 16;
+// from how many members of a phase's longest EXTENDED chain (product and affine members, bpgpu.h "affine member") the scan form is
+// taken: max(BPGPU_OPT_WITNESS_SCAN_MIN, WIT_AFFINE_MIN).  Read from the sweep of profiles/witness_affine.log by the rule of the constant above
+constexpr int64_t WIT_AFFINE_MIN = 16;
 // an entry point's head and tail: the context's mutex taken and its device selected (on failure the mutex is free again) | released
 BPGPU_HIDDEN int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view);
 BPGPU_HIDDEN void bpgpu_internal_leave(bpgpu_ctx *ctx);

@@ -20,7 +20,10 @@ static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT &
 struct bpgpu_witness {
   size_t n = 0, n1 = 0, m = 0, nchi = 0, ninp = 0;
   uint32_t levels[2] = {0, 0};
-  uint32_t scan_levels[2] = {0, 0}, longest[2] = {0, 0};   // the compressed levels and the longest product chain of each phase
+  // per phase: the extended compressed levels (the scan lists are the extended chains'; without an affine member those are the
+  // product chains'), the longest product chain, the longest extended chain, and whether the phase has an affine member
+  uint32_t scan_levels[2] = {0, 0}, longest[2] = {0, 0}, xlongest[2] = {0, 0};
+  bool affine[2] = {false, false};
   void *mem = nullptr;          // one device allocation: everything dev points to
   WitDev dev{};
 };
@@ -43,8 +46,13 @@ int wit_route(size_t gates, uint32_t levels, size_t nb) {
 
 // The scan form (bpgpu.h "product chains"): from how many members of a phase's longest chain it is taken when nothing is forced.
 // WIT_SCAN_MIN_DEFAULT (bpgpu_internal.h) is read from the sweep of profiles/witness_synth.log.
-int wit_route_scan(size_t gates, uint32_t levels, uint32_t longest, size_t nb, int64_t scan_min) {
-  if (gates && scan_min > 0 && (int64_t)longest >= scan_min) return 3;
+// A phase's longest EXTENDED chain (xlongest: product and affine members) takes it from max(scan_min, WIT_AFFINE_MIN) members on,
+// read from profiles/witness_affine.log -- except that scan_min == 1 keeps its meaning "every chain", of either kind.
+int wit_route_scan(size_t gates, uint32_t levels, uint32_t longest, uint32_t xlongest, size_t nb, int64_t scan_min) {
+  if (gates && scan_min > 0) {
+    if ((int64_t)longest >= scan_min) return 3;
+    if ((int64_t)xlongest >= (scan_min == 1 ? 1 : std::max(scan_min, WIT_AFFINE_MIN))) return 3;
+  }
   return wit_route(gates, levels, nb);
 }
 
@@ -59,7 +67,30 @@ struct WitShape {
   std::vector<uint32_t> pred, succ, scan_level;
   std::vector<uint8_t> link_right;
   uint32_t scan_levels[2] = {0, 0}, chains[2] = {0, 0}, members[2] = {0, 0}, longest[2] = {0, 0};
+  // the EXTENDED chains (pass 2): the same, with the affine members among the members; is_affine: a member that pass 2 added
+  std::vector<uint32_t> xpred, xsucc, xscan_level;
+  std::vector<uint8_t> xlink_right, is_affine;
+  uint32_t xscan_levels[2] = {0, 0}, xchains[2] = {0, 0}, xmembers[2] = {0, 0}, xaffine[2] = {0, 0}, xlongest[2] = {0, 0};
 };
+// Is row `side` of gate i an AFFINE link row -- exactly one stored term over all blocks of kind 0..2 on a gate of the phase, that
+// term of kind 2 on a gate without a member successor of either kind yet, whatever else the row holds -- and the other row free of
+// the phase's multipliers?  -> the gate linked to, or WIT_NONE
+uint32_t wit_affine_link_of(size_t i, size_t side, size_t phase_lo, size_t n, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
+                            const uint32_t *idx, const WitShape &s) {
+  const size_t rows = 2 * n;
+  uint32_t j = WIT_NONE;
+  for (size_t b = 0; b <= nchi; b++) {
+    const size_t r = b * rows + 2 * i + side, f = b * rows + 2 * i + (1 - side);
+    for (uint32_t t = row_ptr[r]; t < row_ptr[r + 1]; t++) {
+      if (kind[t] > 2 || idx[t] < phase_lo) continue;
+      if (kind[t] != 2 || j != WIT_NONE) return WIT_NONE;     // a link through a_L / a_R, or a second term on the phase
+      j = idx[t];
+    }
+    for (uint32_t t = row_ptr[f]; t < row_ptr[f + 1]; t++)
+      if (kind[t] <= 2 && idx[t] >= phase_lo) return WIT_NONE;
+  }
+  return j != WIT_NONE && s.xsucc[j] == WIT_NONE ? j : WIT_NONE;
+}
 // Is row `side` of gate i a link row -- one stored term over all blocks, of kind 2, on a gate of the phase that has no member
 // successor yet -- and the other row free of the phase's multipliers?  -> the gate linked to, or WIT_NONE
 uint32_t wit_link_of(size_t i, size_t side, size_t phase_lo, size_t n, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
@@ -79,8 +110,9 @@ uint32_t wit_link_of(size_t i, size_t side, size_t phase_lo, size_t n, size_t nc
   }
   return j != WIT_NONE && s.succ[j] == WIT_NONE ? j : WIT_NONE;
 }
-// what bpgpu_witness_plan, bpgpu_witness_chains and bpgpu_witness_create share: the checks that make the levels well defined, the
-// levels, and the product chains with the compressed levels (both from the shape alone: no coefficient is read)
+// what bpgpu_witness_plan, bpgpu_witness_chains, bpgpu_witness_affine_chains and bpgpu_witness_create share: the checks that make the
+// levels well defined, the levels, the product chains with the compressed levels (pass 1) and the extended chains with theirs (pass 2)
+// -- all from the shape alone: no coefficient is read
 int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
                 WitShape *s) {
   if (!row_ptr || (n && !op) || n1 > n || nchi > 8) return BPGPU_E_ARG;
@@ -137,6 +169,43 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
     if (width.size() <= lvl) width.resize(lvl + 1, 0);
     s->widest = std::max(s->widest, ++width[lvl]);
     s->levels[i < n1 ? 0 : 1] = (uint32_t)width.size();
+  }
+  // pass 2, in program order, once every product member is known (a product gate keeps its a_O whatever the order): the MUL gates
+  // without a predecessor that are affine members, and with them the extended chains and their compressed levels
+  s->xpred = s->pred;
+  s->xsucc = s->succ;
+  s->xlink_right = s->link_right;
+  s->xscan_level.assign(n, 0);
+  s->is_affine.assign(n, 0);
+  length.assign(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    const size_t phase_lo = i < n1 ? 0 : n1;
+    const int ph = i < n1 ? 0 : 1;
+    for (size_t side = 0; side < 2 && op[i] == BPGPU_GATE_MUL && s->xpred[i] == WIT_NONE; side++) {      // the left row first
+      const uint32_t j = wit_affine_link_of(i, side, phase_lo, n, nchi, row_ptr, kind, idx, *s);
+      if (j == WIT_NONE) continue;
+      s->xpred[i] = j;
+      s->xsucc[j] = (uint32_t)i;
+      s->xlink_right[i] = (uint8_t)side;
+      s->is_affine[i] = 1;
+      s->xaffine[ph]++;
+    }
+    uint32_t slvl = 0;
+    if (s->xpred[i] != WIT_NONE) {
+      const uint32_t j = s->xpred[i], head = s->xpred[j] == WIT_NONE ? j : length[j];
+      length[i] = head;
+      if (head == j) s->xchains[ph]++;
+      s->xmembers[ph]++;
+      s->xlongest[ph] = std::max(s->xlongest[ph], ++length[head]);
+      slvl = s->xscan_level[j];
+    } else if (op[i] != BPGPU_GATE_INPUT) {
+      for (size_t r = 2 * i; r < 2 * i + 2; r++)
+        for (size_t b = 0; b <= nchi; b++)
+          for (uint32_t t = row_ptr[b * rows + r]; t < row_ptr[b * rows + r + 1]; t++)
+            if (kind[t] <= 2 && idx[t] >= phase_lo) slvl = std::max(slvl, s->xscan_level[idx[t]] + 1);
+    }
+    s->xscan_level[i] = slvl;
+    s->xscan_levels[ph] = std::max(s->xscan_levels[ph], slvl + 1);
   }
   const uint32_t lane_max = rows_lane_max();
   for (uint32_t len : s->row_len) if (len > lane_max) s->nlong++;
@@ -201,11 +270,13 @@ void wit_phase(const Entered &e, const bpgpu_witness *w, size_t nb, int ph, cons
   const uint32_t n1 = (uint32_t)w->n1, n = (uint32_t)w->n;
   const uint32_t g_lo = ph == 1 ? 0 : n1, g_hi = ph == 1 ? n1 : n;
   const int route = e.view.witness_route ? (int)e.view.witness_route
-                                         : wit_route_scan(g_hi - g_lo, w->levels[ph - 1], w->longest[ph - 1], nb, e.view.witness_scan_min);
+                                         : wit_route_scan(g_hi - g_lo, w->levels[ph - 1], w->longest[ph - 1], w->xlongest[ph - 1], nb,
+                                                          e.view.witness_scan_min);
   const uint32_t *levels = route == 3 ? w->scan_levels : w->levels;       // the scan form walks the compressed levels
   const uint32_t l_lo = ph == 1 ? 0 : levels[0];
+  const int form = route == 3 && w->affine[ph - 1] ? 4 : route;           // a phase with an affine member: the affine instantiation
   Prof22 prof(e.ctx);
-  witness_eval(e.view.st, w->dev, nb, route, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
+  witness_eval(e.view.st, w->dev, nb, form, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
 }
 // the gates [lo, lo + count) of every prover, out of the run's planes into ark planes of `stride` scalars per prover
 void wit_export(const Entered &e, const bpgpu_witness *w, size_t nb, const WitRun &run, size_t lo, size_t count, void *aL, void *aR, void *aO,
@@ -345,8 +416,24 @@ int bpgpu_witness_plan(size_t n, size_t n1, size_t nchi, const uint8_t *op, cons
     out[BPGPU_WIT_PLAN_WIDEST] = (int32_t)s.widest;
     out[BPGPU_WIT_PLAN_LONG_ROWS] = (int32_t)s.nlong;
     out[BPGPU_WIT_PLAN_INPUTS] = (int32_t)s.ninp;
-    out[BPGPU_WIT_PLAN_ROUTE1] = wit_route_scan(n1, s.levels[0], s.longest[0], nb, WIT_SCAN_MIN_DEFAULT);
-    out[BPGPU_WIT_PLAN_ROUTE2] = wit_route_scan(n - n1, s.levels[1], s.longest[1], nb, WIT_SCAN_MIN_DEFAULT);
+    out[BPGPU_WIT_PLAN_ROUTE1] = wit_route_scan(n1, s.levels[0], s.longest[0], s.xlongest[0], nb, WIT_SCAN_MIN_DEFAULT);
+    out[BPGPU_WIT_PLAN_ROUTE2] = wit_route_scan(n - n1, s.levels[1], s.longest[1], s.xlongest[1], nb, WIT_SCAN_MIN_DEFAULT);
+    return BPGPU_OK;
+  });
+}
+int bpgpu_witness_affine_chains(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                                const uint32_t *idx, int32_t out[BPGPU_WIT_AFF_FIELDS]) {
+  return no_throw([&]() -> int {
+    if (!out) return BPGPU_E_ARG;
+    WitShape s;
+    WCK(wit_analyse(n, n1, nchi, op, row_ptr, kind, idx, &s));
+    for (int ph = 0; ph < 2; ph++) {
+      out[BPGPU_WIT_AFF_CHAINS1 + ph] = (int32_t)s.xchains[ph];
+      out[BPGPU_WIT_AFF_MEMBERS1 + ph] = (int32_t)s.xmembers[ph];
+      out[BPGPU_WIT_AFF_AFFINE1 + ph] = (int32_t)s.xaffine[ph];
+      out[BPGPU_WIT_AFF_LONGEST1 + ph] = (int32_t)s.xlongest[ph];
+      out[BPGPU_WIT_AFF_LEVELS1 + ph] = (int32_t)s.xscan_levels[ph];
+    }
     return BPGPU_OK;
   });
 }
@@ -391,7 +478,7 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     }
     // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op | scan_order | scan_ptr |
     // scan_long | chain_elem | chain_ptr], every part 256-byte aligned
-    const size_t nslev = (size_t)s.scan_levels[0] + s.scan_levels[1];
+    const size_t nslev = (size_t)s.xscan_levels[0] + s.xscan_levels[1];
     const size_t o_rp = up256((nnz ? nnz : 1) * 32), o_var = o_rp + up256((rows + 1) * 4), o_arg = o_var + up256((nnz ? nnz : 1) * 4),
                  o_ord = o_arg + up256((n ? n : 1) * 4), o_lp = o_ord + up256((n ? n : 1) * 4), o_ll = o_lp + up256((nlev + 1) * 4),
                  o_op = o_ll + up256((nlev ? nlev : 1) * 4), o_so = o_op + up256(n ? n : 1), o_sp = o_so + up256((n ? n : 1) * 4),
@@ -416,6 +503,17 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
         }
     }
     h_rp[rows] = pos;
+    // an affine member's link term first in its link row (wit_link reads a row's first term; the sums are exact: the order is free)
+    for (size_t i = 0; i < n; i++) {
+      if (!s.is_affine[i]) continue;
+      const uint32_t lo = h_rp[2 * i + s.xlink_right[i]], hi = h_rp[2 * i + s.xlink_right[i] + 1], phase_lo = i < n1 ? 0 : (uint32_t)n1;
+      for (uint32_t t = lo; t < hi; t++)
+        if (((h_var[t] >> ROWS_KIND_SHIFT) & 7u) <= 2 && (h_var[t] & ROWS_IDX_MASK) >= phase_lo) {
+          std::swap(h_var[t], h_var[lo]);
+          std::swap(h_coeff[t], h_coeff[lo]);
+          break;
+        }
+    }
     // the gates of a phase sorted by level (stable: program order within a level), the ones with a long row last in their level
     const uint32_t lane_max = rows_lane_max();
     uint32_t pairs = 0, at = 0, lvl_base = 0;
@@ -436,14 +534,15 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       lvl_base += s.levels[ph];
     }
     h_lp[nlev] = at;
-    // the same over the compressed levels, members apart: a level's ordinary gates (short rows, then long), and the members of the
-    // chains it heads, chain after chain (heads in program order), each chain from its first member on
+    // the same over the extended compressed levels, members apart: a level's ordinary gates (short rows, then long), and the members
+    // of the extended chains it heads, chain after chain (heads in program order), each chain from its first member on.  A phase
+    // without an affine member has the product chains' lists: pass 2 changed nothing of it
     uint32_t *h_so = (uint32_t *)(img.data() + o_so), *h_sp = (uint32_t *)(img.data() + o_sp), *h_sl = (uint32_t *)(img.data() + o_sl),
              *h_ce = (uint32_t *)(img.data() + o_ce), *h_cp = (uint32_t *)(img.data() + o_cp);
     std::vector<uint32_t> fill(3 * nslev + 1, 0);          // per compressed level: short, long, members -> where each list starts
     const auto slot = [&](size_t i) {
-      const size_t l = (i < n1 ? 0 : s.scan_levels[0]) + s.scan_level[i];
-      return 3 * l + (s.pred[i] != WIT_NONE ? 2 : (s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max ? 1 : 0));
+      const size_t l = (i < n1 ? 0 : s.xscan_levels[0]) + s.xscan_level[i];
+      return 3 * l + (s.xpred[i] != WIT_NONE ? 2 : (s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max ? 1 : 0));
     };
     for (size_t i = 0; i < n; i++) fill[slot(i) + 1]++;
     uint32_t ord_at = 0, mem_at = 0;
@@ -456,19 +555,22 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     }
     h_sp[nslev] = ord_at; h_cp[nslev] = mem_at;
     for (size_t i = 0; i < n; i++) {
-      if (s.pred[i] != WIT_NONE) continue;
+      if (s.xpred[i] != WIT_NONE) continue;
       const size_t k = slot(i);
       h_so[fill[k]++] = (uint32_t)i;
-      if (s.succ[i] == WIT_NONE) continue;
+      if (s.xsucc[i] == WIT_NONE) continue;
       uint32_t &m_at = fill[k - k % 3 + 2];                 // a head: its chain, whole, into its level's member list
-      for (uint32_t e = s.succ[i], first = WIT_ELEM_START; e != WIT_NONE; e = s.succ[e], first = 0)
-        h_ce[m_at++] = e | first | (s.link_right[e] ? WIT_ELEM_RIGHT : 0u);
+      for (uint32_t e = s.xsucc[i], first = WIT_ELEM_START; e != WIT_NONE; e = s.xsucc[e], first = 0)
+        h_ce[m_at++] = e | first | (s.xlink_right[e] ? WIT_ELEM_RIGHT : 0u) | (s.is_affine[e] ? WIT_ELEM_AFFINE : 0u);
     }
     bpgpu_witness *w = new (std::nothrow) bpgpu_witness();
     if (!w) return BPGPU_E_OOM;
     w->n = n; w->n1 = n1; w->m = m; w->nchi = nchi; w->ninp = s.ninp;
     w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
-    for (int ph = 0; ph < 2; ph++) { w->scan_levels[ph] = s.scan_levels[ph]; w->longest[ph] = s.longest[ph]; }
+    for (int ph = 0; ph < 2; ph++) {
+      w->scan_levels[ph] = s.xscan_levels[ph]; w->longest[ph] = s.longest[ph];
+      w->xlongest[ph] = s.xlongest[ph]; w->affine[ph] = s.xaffine[ph] != 0;
+    }
     Entered e(ctx);
     int rc = e.enter();
     // (a plain allocation, not the context's pool: a program may outlive the context that made it, as a circuit may)

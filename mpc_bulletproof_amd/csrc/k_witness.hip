@@ -67,28 +67,66 @@ __global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
 
 // A block per prover over the COMPRESSED levels (kernels.h WitDev): at each level (A) its ordinary gates as k_witness_block runs
 // them, heads of chains among them; a fence and a barrier; (B) the M members of all chains headed at this level as ONE segmented
-// inclusive prefix product (witness_scan.cuh).  Thread t owns the run [t R, (t + 1) R) of R = ceil(M / 256) elements: a local pass,
+// inclusive prefix product -- or, in a phase with an affine member, prefix composition of affine maps (witness_scan.cuh).  Thread t owns the run [t R, (t + 1) R) of R = ceil(M / 256) elements: a local pass,
 // the scan of the 256 runs' parts -- within a wave by lane shuffles (Kogge-Stone, 6 steps), across the four waves through 4 parts in
 // LDS -- and a second pass that applies the carry: 2 R + 10 dependent multiplications where the gates one by one take M levels.
 // Barriers: M and the level range are the same for every thread of a launch, no thread returns early, and the shuffles run with all
 // 64 lanes active (a thread whose run is empty carries the identity).  The LDS parts of one level are read before that level's
 // closing barrier and written again only after it.
-__device__ __forceinline__ WitPart wit_part_shfl_up(const WitPart &x, uint32_t off) {
-  WitPart r;
+// k_witness_scan<AFFINE>: the same skeleton over either monoid -- WitPart under the product, or WitAff under the composition of
+// affine maps for a phase that has an affine member (every level of such a phase runs the affine operator: a product member is the
+// map with f = 0).  WitScanOf<AFFINE> is what the skeleton needs of a monoid; the parts in LDS are WORDS int32 each.
+__device__ __forceinline__ Fn fn_shfl_up(const Fn &x, uint32_t off) {
+  Fn r;
 #pragma unroll
-  for (int j = 0; j < NL; j++) r.v.v[j] = __shfl_up(x.v.v[j], off, 64);
-  r.flag = __shfl_up(x.flag, off, 64);
+  for (int j = 0; j < NL; j++) r.v[j] = __shfl_up(x.v[j], off, 64);
   return r;
 }
-__device__ __forceinline__ WitPart wit_part_select(bool take, const WitPart &x, const WitPart &y) {
-  WitPart r;
+__device__ __forceinline__ Fn fn_select(bool take, const Fn &x, const Fn &y) {
+  Fn r;
 #pragma unroll
-  for (int j = 0; j < NL; j++) r.v.v[j] = take ? x.v.v[j] : y.v.v[j];
-  r.flag = take ? x.flag : y.flag;
+  for (int j = 0; j < NL; j++) r.v[j] = take ? x.v[j] : y.v[j];
   return r;
 }
-__global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
-  __shared__ int32_t s_part[4][NL + 1];
+template <bool AFFINE> struct WitScanOf;
+template <> struct WitScanOf<false> {
+  using Part = WitPart;
+  static constexpr int WORDS = NL + 1;
+  static __device__ __forceinline__ Part identity() { return wit_part_identity(); }
+  static __device__ __forceinline__ Part combine(const Part &a, const Part &b) { return wit_part_combine(a, b); }
+  static __device__ __forceinline__ Part shfl_up(const Part &x, uint32_t off) { return {fn_shfl_up(x.v, off), __shfl_up(x.flag, off, 64)}; }
+  static __device__ __forceinline__ Part select(bool take, const Part &x, const Part &y) {
+    return {fn_select(take, x.v, y.v), take ? x.flag : y.flag};
+  }
+  static __device__ __forceinline__ void put(int32_t *d, const Part &x) { raw_put(d, x.v); d[NL] = (int32_t)x.flag; }
+  static __device__ __forceinline__ Part get(const int32_t *s) { return {raw_get(s), (uint32_t)s[NL]}; }
+  static __device__ __forceinline__ Part local(const WitDev &w, uint32_t lo, uint32_t hi, const WitPlanes &o) { return wit_scan_local(w, lo, hi, o); }
+  static __device__ __forceinline__ void apply(const WitDev &w, uint32_t lo, uint32_t hi, const Part &carry, const WitPlanes &o) {
+    wit_scan_apply(w, lo, hi, carry.v, o);
+  }
+};
+template <> struct WitScanOf<true> {
+  using Part = WitAff;
+  static constexpr int WORDS = 2 * NL + 1;
+  static __device__ __forceinline__ Part identity() { return wit_aff_identity(); }
+  static __device__ __forceinline__ Part combine(const Part &a, const Part &b) { return wit_aff_combine(a, b); }
+  static __device__ __forceinline__ Part shfl_up(const Part &x, uint32_t off) {
+    return {fn_shfl_up(x.a, off), fn_shfl_up(x.b, off), __shfl_up(x.flag, off, 64)};
+  }
+  static __device__ __forceinline__ Part select(bool take, const Part &x, const Part &y) {
+    return {fn_select(take, x.a, y.a), fn_select(take, x.b, y.b), take ? x.flag : y.flag};
+  }
+  static __device__ __forceinline__ void put(int32_t *d, const Part &x) { raw_put(d, x.a); raw_put(d + NL, x.b); d[2 * NL] = (int32_t)x.flag; }
+  static __device__ __forceinline__ Part get(const int32_t *s) { return {raw_get(s), raw_get(s + NL), (uint32_t)s[2 * NL]}; }
+  static __device__ __forceinline__ Part local(const WitDev &w, uint32_t lo, uint32_t hi, const WitPlanes &o) { return wit_aff_local(w, lo, hi, o); }
+  static __device__ __forceinline__ void apply(const WitDev &w, uint32_t lo, uint32_t hi, const Part &carry, const WitPlanes &o) {
+    wit_aff_apply(w, lo, hi, carry.b, o);
+  }
+};
+template <bool AFFINE> __global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
+  using S = WitScanOf<AFFINE>;
+  using Part = typename S::Part;
+  __shared__ int32_t s_part[4][S::WORDS];
   const WitProver o = wit_prover(a, blockIdx.x);
   const WitPlanes pl{o.aL, o.aR, o.aO, o.v, o.chi};
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -100,22 +138,19 @@ __global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
       __syncthreads();
       const uint32_t run = (c_hi - c_lo + 255) / 256;
       const uint32_t e_lo = min(c_lo + threadIdx.x * run, c_hi), e_hi = min(e_lo + run, c_hi);  // (M < 2^25: no wrap)
-      WitPart x = wit_scan_local(a.w, e_lo, e_hi, pl);
+      Part x = S::local(a.w, e_lo, e_hi, pl);
 #pragma unroll 1
       for (uint32_t off = 1; off < 64; off <<= 1) {
-        const WitPart both = wit_part_combine(wit_part_shfl_up(x, off), x);
-        x = wit_part_select(lane >= off, both, x);
+        const Part both = S::combine(S::shfl_up(x, off), x);
+        x = S::select(lane >= off, both, x);
       }
-      if (lane == 63) {
-        raw_put(s_part[wave], x.v);
-        s_part[wave][NL] = (int32_t)x.flag;
-      }
-      const WitPart before = wit_part_select(lane != 0, wit_part_shfl_up(x, 1), wit_part_identity());   // this wave's lanes below
+      if (lane == 63) S::put(s_part[wave], x);
+      const Part before = S::select(lane != 0, S::shfl_up(x, 1), S::identity());               // this wave's lanes below
       __syncthreads();
-      WitPart carry = wit_part_identity();
-      for (uint32_t k = 0; k < wave; k++) carry = wit_part_combine(carry, WitPart{raw_get(s_part[k]), (uint32_t)s_part[k][NL]});
-      carry = wit_part_combine(carry, before);
-      wit_scan_apply(a.w, e_lo, e_hi, carry.v, pl);
+      Part carry = S::identity();
+      for (uint32_t k = 0; k < wave; k++) carry = S::combine(carry, S::get(s_part[k]));
+      carry = S::combine(carry, before);
+      S::apply(a.w, e_lo, e_hi, carry, pl);
     }
     if (l + 1 < a.l_hi) {
       __threadfence_block();
@@ -127,7 +162,8 @@ void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, uint32_t
                   Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi) {
   if (!nb || g_lo >= g_hi) return;
   const WitArgs a{w, nb, g_lo, g_hi, l_lo, l_hi, aL, aR, aO, v, inputs, chi};
-  if (form == 3) hipLaunchKernelGGL(k_witness_scan, dim3((unsigned)nb), dim3(256), 0, st, a);
+  if (form == 4) hipLaunchKernelGGL(k_witness_scan<true>, dim3((unsigned)nb), dim3(256), 0, st, a);
+  else if (form == 3) hipLaunchKernelGGL(k_witness_scan<false>, dim3((unsigned)nb), dim3(256), 0, st, a);
   else if (form == 2) hipLaunchKernelGGL(k_witness_block, dim3((unsigned)nb), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_witness_lane, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, a);
 }

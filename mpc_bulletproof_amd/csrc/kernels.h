@@ -275,8 +275,12 @@ void csr_scan(hipStream_t st, uint32_t *cnt, size_t n1);
 // the level of the gate it links to.  Compressed level l holds the ordinary gates scan_order[scan_ptr[l] .. scan_ptr[l + 1]) (heads
 // of chains among them; short rows before scan_long[l]) and the members chain_elem[chain_ptr[l] .. chain_ptr[l + 1]) of the chains
 // whose head it holds, chain after chain in chain order: gate | WIT_ELEM_START (the first member of a chain) | WIT_ELEM_RIGHT (the
-// link is the right row).  Gate ids are below 2^25 (ROWS_IDX_MASK), so the two flags are free bits.
-constexpr uint32_t WIT_ELEM_START = 1u << 25, WIT_ELEM_RIGHT = 1u << 26;
+// link is the right row).  Gate ids are below 2^25 (ROWS_IDX_MASK), so the flags are free bits.
+// A phase that has AFFINE members (bpgpu.h: the link row holds c a_O[pred] and beside it terms that read nothing of the phase) lists
+// the extended chains, product and affine members alike, over the extended compressed levels; an affine member carries
+// WIT_ELEM_AFFINE, and its link term stands FIRST in the library's copy of its link row, where wit_link reads it.  Such a phase is
+// launched as k_witness_scan<true> (witness_eval's form 4); a phase without one has the lists and the kernel of the product chains alone.
+constexpr uint32_t WIT_ELEM_START = 1u << 25, WIT_ELEM_RIGHT = 1u << 26, WIT_ELEM_AFFINE = 1u << 27;
 struct WitDev {
   RowsDev rows;
   const uint8_t *op;          // n
@@ -294,7 +298,8 @@ struct WitDev {
 // One launch evaluates the gates [g_lo, g_hi) = the levels [l_lo, l_hi) of nb provers on plain canonical planes nb x n (aL, aR, aO:
 // read for the gates below g_lo, written for the range), v nb x m, inputs nb x ninp x 2, chi nb x nchi (or nullptr), all plain.
 // form 1: a lane per prover, program order; 2: a block of 256 threads per prover, level by level; 3: a block per prover over the
-// COMPRESSED levels [l_lo, l_hi), the chains of a level as one segmented prefix product (k_witness_scan).
+// COMPRESSED levels [l_lo, l_hi), the chains of a level as one segmented prefix product (k_witness_scan<false>) or, where the range
+// holds an affine member (form 4), as one segmented prefix composition of affine maps (k_witness_scan<true>).
 void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
                   Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
 // rows of `count` scalars, one per prover: src + p * src_stride -> dst + p * dst_stride.  to_ark: plain canonical -> ark Montgomery

@@ -146,11 +146,26 @@ def witness_chains(n, n1, nchi, op, row_ptr, kind, idx):
     return dict(zip(WIT_CHAIN_FIELDS, out))
 
 
+# bpgpu_witness_affine_chains (include/bpgpu.h BPGPU_WIT_AFF_*)
+WIT_AFF_FIELDS = ("chains1", "chains2", "members1", "members2", "affine1", "affine2", "longest1", "longest2", "levels1", "levels2")
+
+
+def witness_affine_chains(n, n1, nchi, op, row_ptr, kind, idx):
+    """the extended chains of a gate program, product and affine members together -- per phase their number, all their members, the
+    affine ones among them, the longest and the extended compressed levels -- as a dict over WIT_AFF_FIELDS (needs no device)"""
+    out = (C.c_int32 * len(WIT_AFF_FIELDS))()
+    rc = _lib.bpgpu_witness_affine_chains(n, n1, nchi, _buf(bytes(op)), _u32s(row_ptr), _u32s(kind), _u32s(idx), out)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return dict(zip(WIT_AFF_FIELDS, out))
+
+
 class BpGpu:
     """One context on one device.  All byte encodings as in include/bpgpu.h."""
 
     witness_plan = staticmethod(witness_plan)
     witness_chains = staticmethod(witness_chains)
+    witness_affine_chains = staticmethod(witness_affine_chains)
 
     def __init__(self, device=0):
         self.ctx = C.c_void_p()

@@ -20,6 +20,13 @@ provers x shuffle k = 64 (two chains of 63 dependent gates: a head and 62 member
           the host mirror (tools/bench_shuffle.py), which is out of scope here, so that shape has the synthesis line alone.  The
           range shape is a one-phase prover: bpgpu_r1cs_prove_fs_dev after the synthesis, no second call to save.
 
+
+`bench_witness.py affine` measures the affine chains instead and appends to profiles/witness_affine.log: the two shuffle lines again
+(the product kernel is meant to be unchanged: each span is compared with the last run of profiles/witness_synth.log, widened by the
+8 % box spread DESIGN.md gives for that log), then ONE Horner pair per prover (tests/witness_affine_cases.py: two affine chains of
+8 .. 16 382 members) for 1 and 256 provers, block form against scan form.  The block form is the path these programs took before
+there was an affine scan.  WIT_AFFINE_MIN (csrc/bpgpu_internal.h) is read from that sweep by the rule of the shuffle sweep.
+
 A fresh process per line under its own time limit; WARM untimed steps, then STEPS timed ones, medians (min..max) in ms."""
 import ctypes as C
 import json
@@ -51,6 +58,17 @@ def shuffle_program(k):
     wc._shuffle_gates(prog, k, 0)
     xs = [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << 64) - 1)) for i in range(k)]
     return prog, xs + xs[1:] + xs[:1]
+
+
+def horner_program(k):
+    """the Horner gadget's gates (tests/witness_affine_cases.py: two affine chains of k - 2 members) and one prover's values"""
+    import witness_cases as wc
+    import witness_affine_cases as ac
+    prog = wc.Program(2 * k, nchi=1)
+    prog.end_phase1()
+    ac._horner_gates(prog, k, 0)
+    xs = [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << 64) - 1)) for i in range(k)]
+    return prog, xs + xs
 
 
 def range_program(bits, m):
@@ -85,7 +103,7 @@ SWEEP_NB = (1, 256)
 def synth(shape, nb, size, forms=("lane", "block", "scan")):
     import mpc_dealer as md
     import mpc_bulletproof_amd as m
-    prog, v = range_program(64, size) if shape == "range" else shuffle_program(size)
+    prog, v = {"range": lambda: range_program(64, size), "shuffle": lambda: shuffle_program(size), "horner": lambda: horner_program(size)}[shape]()
     chi = (0x1234567,) if prog.nchi else ()
     t0 = time.perf_counter()
     want = prog.evaluate(v, (), chi)
@@ -93,7 +111,7 @@ def synth(shape, nb, size, forms=("lane", "block", "scan")):
     gpu = m.BpGpu(0)
     w = gpu.witness_create(*prog.create_args())
     plan = m.lib.witness_plan(*prog.plan_args(), nb)
-    chains = m.lib.witness_chains(*prog.plan_args())
+    chains = m.lib.witness_affine_chains(*prog.plan_args())          # the extended chains: a program without an affine member has its product chains
     longest = max(chains["longest1"], chains["longest2"])
     d_v = gpu.to_device(b"".join(md.mont(x) for x in v) * nb)
     d_chi = gpu.to_device(md.le(chi[0]) * nb) if chi else None
@@ -194,24 +212,48 @@ def child(what, args):
         print("RESULT", prove(int(args[0]), int(args[1]), int(args[2])))
 
 
-def scan_min_line(spans):
-    """the rule of BPGPU_OPT_WITNESS_SCAN_MIN's default on the sweep's (min, max) spans: non-overlap at both batch sizes"""
+def scan_min_of(spans, shape):
+    """the rule of both thresholds on a sweep's (min, max) spans: the smallest power of two >= 16 from which on the scan's maximum
+    lies below the block form's minimum at both batch sizes -> members, or None"""
     def wins(members):
-        return all(spans[("shuffle", nb, members + 2)]["scan"][1] < spans[("shuffle", nb, members + 2)]["block"][0] for nb in SWEEP_NB)
+        return all(spans[(shape, nb, members + 2)]["scan"][1] < spans[(shape, nb, members + 2)]["block"][0] for nb in SWEEP_NB)
     powers = [mm for mm in SWEEP_MEMBERS if mm & (mm - 1) == 0 and mm >= 16]
     good = [d for d in powers if all(wins(mm) for mm in SWEEP_MEMBERS if mm >= d)]
+    return good[0] if good else None
+
+
+def scan_min_line(spans):
+    """BPGPU_OPT_WITNESS_SCAN_MIN's default from the shuffle sweep"""
+    good = [d for d in (scan_min_of(spans, "shuffle"),) if d]
     if not good:
         return "# scan max < block min at both nb from NO measured power of two on: the scan form has missed its purpose"
     return (f"# scan max < block min at both nb from {good[0]} members on (every longer chain of the sweep included): "
             f"BPGPU_OPT_WITNESS_SCAN_MIN defaults to {good[0]}")
 
 
-def main():
-    if len(sys.argv) >= 3 and sys.argv[1] == "--child":
-        return child(sys.argv[2], sys.argv[3:])
+def affine_min_line(spans):
+    """WIT_AFFINE_MIN from the Horner sweep"""
+    d = scan_min_of(spans, "horner")
+    if d is None:
+        return ("# scan max < block min at both nb from NO measured power of two on: WIT_AFFINE_MIN is set above every chain "
+                "(2^25), the plan never scans for an affine chain's sake")
+    return f"# scan max < block min at both nb from {d} members on (every longer chain of the sweep included): WIT_AFFINE_MIN = {d}"
+
+
+def earlier_span(prefix, form):
+    """(min, max) of `form` on the last line of profiles/witness_synth.log that starts with `prefix`, and the line"""
+    import re
+    with open(os.path.join(ROOT, "profiles", "witness_synth.log")) as fh:
+        line = [ln for ln in fh.read().splitlines() if ln.startswith(prefix)][-1]
+    mm = re.search(form + r"\s+[0-9.]+ \(\s*([0-9.]+)\.\.\s*([0-9.]+)\)", line)
+    return (float(mm.group(1)), float(mm.group(2))), line
+
+
+def runner(title):
+    """-> (lines, spans, step): step(text, *child arguments) runs one child and appends its line"""
     spans = {}
-    lines = [f"# tools/bench_witness.py   a fresh process per line (limit {STEP_LIMIT} s), {WARM} warm-up + {STEPS} timed steps per route: median "
-             "(min..max) ms",
+    lines = [f"# tools/bench_witness.py {title}  a fresh process per line (limit {STEP_LIMIT} s), {WARM} warm-up + {STEPS} timed steps per route: "
+             "median (min..max) ms",
              "# synth: bpgpu_r1cs_witness_synthesize_dev alone, HIP events; host: the same gates of ONE prover on Python integers"]
 
     def run(*args):
@@ -232,6 +274,44 @@ def main():
         print(lines[-1])
         sys.stdout.flush()
         return ok
+    return lines, spans, step
+
+
+def affine_main():
+    lines, spans, step = runner("affine ")
+    lines.append("# the product kernel again (k_witness_scan<false>): each span against the last run of profiles/witness_synth.log +- 8 %")
+    ok = True
+    for text, nb, k in (("synth   256 x shuffle k = 64       n = 126     ", 256, 64), ("synth   1 x shuffle k = 2^14       n = 32766   ", 1, 1 << 14)):
+        ok = ok and step(text, "synth", "shuffle", nb, k, "lane,block,scan")
+        if not ok:
+            break
+        (lo, hi), line = earlier_span(text, "scan")
+        now = spans[("shuffle", nb, k)]["scan"]
+        inside = lo * 0.92 <= now[0] and now[1] <= hi * 1.08
+        lines.append("# earlier " + line[:len(text) + 150].rstrip())
+        lines.append(f"# scan now {now[0]:.3f}..{now[1]:.3f} ms against {lo:.3f}..{hi:.3f} ms -8 % / +8 %: {'inside' if inside else 'OUTSIDE'}")
+    lines.append("# affine: one Horner pair of k = members + 2 per prover (two affine chains), block form against scan form (k_witness_scan<true>)")
+    for members in SWEEP_MEMBERS:
+        for nb in SWEEP_NB:
+            ok = ok and step(f"affine  {nb:4d} x {members:5d} members   n = {2 * members + 2:5d}   ", "synth", "horner", nb, members + 2, "block,scan")
+    if ok:
+        lines.append(affine_min_line(spans))
+    else:
+        lines.append("# a step failed: the steps after it were not started")
+    path = os.path.join(ROOT, "profiles", "witness_affine.log")
+    with open(path, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines[-3:]))
+    print("wrote", path)
+    return 0 if ok else 1
+
+
+def main():
+    if len(sys.argv) >= 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2], sys.argv[3:])
+    if sys.argv[1:] == ["affine"]:
+        return affine_main()
+    lines, spans, step = runner("")
     ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16, "lane,block,scan")
     ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64, "lane,block,scan")
     ok = ok and step("synth   1 x shuffle k = 2^14       n = 32766   ", "synth", "shuffle", 1, 1 << 14, "lane,block,scan")
