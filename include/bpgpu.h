@@ -48,6 +48,22 @@ const char *bpgpu_strerror(int code);
 const char *bpgpu_last_error(bpgpu_ctx *ctx);   /* text of the last HIP failure on this ctx */
 int bpgpu_sync(bpgpu_ctx *ctx);
 void *bpgpu_stream(bpgpu_ctx *ctx);             /* hipStream_t of the ctx (for event timing) */
+/* Hardware queues.  The pipelined entry points (several contexts driven in turn, the stream, screened and mixed calls, the pool,
+ * the host mirror's prover streams) keep ~20 batches in flight on a stream each, and reach their rate only when those streams
+ * land on as many hardware queues.  The HIP runtime takes the number from GPU_MAX_HW_QUEUES when it initialises (default 4), so
+ * libbpgpu.so claims its requirement of 24 when it is LOADED:
+ *   GPU_MAX_HW_QUEUES unset, not a number, or below 24  -> the library exports 24 (an inherited 4 cannot be told from "nobody
+ *                                                          chose", and keeping it costs a third to two thirds of the rate);
+ *   GPU_MAX_HW_QUEUES at or above 24                    -> left alone (never lowered; the library never exports more than 32);
+ *   BPGPU_HW_QUEUES = 1..32                             -> exactly that is exported, over any inherited value;
+ *   BPGPU_HW_QUEUES = 0                                 -> the process's setting is left untouched (a host that limits queues
+ *                                                          on purpose); any other text is ignored.
+ * No other variable of the runtime is read or written.  A process that has initialised HIP before loading the library keeps
+ * what the runtime read then.  The getter reports what happened at load (a C setenv is invisible to a snapshot of the environment
+ * such as Python's os.environ): *inherited = the value the process environment held, *in_force = the value the library left
+ * there; each -1 if unset, -2 if set to something that is not a number (read as the runtime reads it: the leading decimal
+ * integer; a negative one reports as 0).  Either pointer may be NULL.  Returns BPGPU_OK. */
+int bpgpu_hw_queues(int *inherited, int *in_force);
 /* Tuning hint for the batch-verification entry points of this context.  0 (default): fewest instructions -- right for a
  * caller that keeps several batches in flight (several contexts / streams), where throughput is bound by instruction issue.
  * 1: more, shorter lanes in the two longest launches of a batch's kernel chain -- one batch alone completes ~25 % sooner
@@ -817,8 +833,9 @@ int bpgpu_r1cs_verify_batch_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu
  * library cuts them into batches of BPGPU_OPT_STREAM_BATCH proofs (1024) that take turns on a ring of BPGPU_OPT_STREAM_LANES (20)
  * internal streams + workspaces, so that the kernel chains of ~20 batches overlap on the GPU -- the pipelined rate (4 M
  * verifications/s for the 64-bit range gadget) without the caller creating contexts or exporting GPU_MAX_HW_QUEUES (libbpgpu.so
- * sets it to 24 when it is loaded, unless the process has set it; a process that has initialised HIP before loading the library
- * keeps the runtime's 4 queues and about a third of the rate).  This is what a Rust host's loop of Verifier::verify
+ * raises it to 24 when it is loaded, an inherited smaller value included; BPGPU_HW_QUEUES overrides that, 0 = hands off: see
+ * bpgpu_hw_queues above.  A process that has initialised HIP before loading the library, or that sets BPGPU_HW_QUEUES=0 under an
+ * inherited 4, keeps the runtime's 4 queues and a third to two thirds of the rate).  This is what a Rust host's loop of Verifier::verify
  * (verifier.rs:393) becomes: collect the proofs of one circuit, one call.
  *   _dev : operands and ok[] resident in HBM (layouts of bpgpu_r1cs_verify_batch); asynchronous -- the lanes fork from the
  *          context's stream and are joined back into it: bpgpu_sync, or the next call on this context, waits for all of them.

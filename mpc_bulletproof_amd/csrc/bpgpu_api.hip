@@ -1,6 +1,8 @@
 // bpgpu_api.hip -- the C ABI of include/bpgpu.h on top of the HIP kernels.
 // No CPU fallback: every entry point needs a live HIP device and fails with BPGPU_E_DEVICE otherwise.
 #include <hip/hip_runtime.h>
+#include <cerrno>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -415,8 +417,56 @@ const char *bpgpu_strerror(int code) {
 }
 // The pipelined entry points keep ~20 kernels' worth of independent batches in flight, one stream each; the HIP runtime maps
 // streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default: everything beyond serialises).  The runtime reads the variable
-// when it initialises, so it is set here, when the library is loaded, unless the host process has chosen a value itself.
-__attribute__((constructor)) static void bpgpu_runtime_defaults() { setenv("GPU_MAX_HW_QUEUES", "24", 0); }
+// when it initialises, so the library claims its queues here, when it is loaded.  An inherited 4 cannot be told from "nobody
+// chose" (launchers export the runtime's default spelled out), and honouring it costs every pipelined entry point a third to two
+// thirds of its rate: so a value below the requirement is raised, and a host that limits queues on purpose says so with
+// BPGPU_HW_QUEUES (include/bpgpu.h: bpgpu_hw_queues).
+#define HW_QUEUES_REQUIRED 24   // 20 ring lanes need 20; beyond ~22 active queues bursts turn erratic
+#define HW_QUEUES_MAX 32        // never exported above this
+#define HW_QUEUES_UNSET (-1)
+#define HW_QUEUES_NOT_A_NUMBER (-2)
+// the variable's value as the runtime reads it: the leading decimal integer, whatever follows it
+static int hw_queues_parse(const char *s) {
+  if (!s) return HW_QUEUES_UNSET;
+  char *end = nullptr;
+  errno = 0;
+  const long v = strtol(s, &end, 10);
+  if (end == s || errno == ERANGE || v > INT_MAX) return HW_QUEUES_NOT_A_NUMBER;
+  return v < 0 ? 0 : (int)v;
+}
+// The policy, a pure function of the two variables' texts: the number to export, or 0 to leave the process's setting as it is.
+//   own (BPGPU_HW_QUEUES), the library's choice as the host states it: "1".."32" exactly that, over whatever was inherited; "0"
+//   hands the setting back to the host; anything else is ignored.
+//   inherited (GPU_MAX_HW_QUEUES): unset, not a number or below the requirement -> the requirement; at or above it -> untouched
+//   (never lowered, and never raised beyond HW_QUEUES_MAX because only the requirement is ever exported here).
+static int hw_queues_policy(const char *inherited, const char *own) {
+  if (own && *own) {
+    char *end = nullptr;
+    errno = 0;
+    const long v = strtol(own, &end, 10);
+    const bool whole = end != own && *end == '\0' && errno != ERANGE && own[0] >= '0' && own[0] <= '9';
+    if (whole && v == 0) return 0;
+    if (whole && v >= 1 && v <= HW_QUEUES_MAX) return (int)v;
+  }
+  return hw_queues_parse(inherited) >= HW_QUEUES_REQUIRED ? 0 : HW_QUEUES_REQUIRED;
+}
+static int g_hw_queues_inherited = HW_QUEUES_UNSET, g_hw_queues_in_force = HW_QUEUES_UNSET;
+__attribute__((constructor)) static void bpgpu_claim_hw_queues() {
+  const char *inherited = getenv("GPU_MAX_HW_QUEUES");
+  g_hw_queues_inherited = hw_queues_parse(inherited);
+  const int want = hw_queues_policy(inherited, getenv("BPGPU_HW_QUEUES"));
+  if (want > 0) {
+    char text[16];
+    snprintf(text, sizeof text, "%d", want);
+    setenv("GPU_MAX_HW_QUEUES", text, 1);
+  }
+  g_hw_queues_in_force = hw_queues_parse(getenv("GPU_MAX_HW_QUEUES"));
+}
+int bpgpu_hw_queues(int *inherited, int *in_force) {
+  if (inherited) *inherited = g_hw_queues_inherited;
+  if (in_force) *in_force = g_hw_queues_in_force;
+  return BPGPU_OK;
+}
 
 static int ctx_create(int device, bool single_stream, bpgpu_ctx **out);
 // the one validator of option values: bpgpu_set_option and the environment seeding of a new context both go through it

@@ -100,6 +100,16 @@ def device_count():
     return _lib.bpgpu_device_count()
 
 
+def hw_queues():
+    """-> (inherited, in_force): GPU_MAX_HW_QUEUES as the process environment held it when libbpgpu.so was loaded and as the library
+    left it (bpgpu_hw_queues: -1 unset, -2 not a number).  os.environ is a snapshot that does not see the library's setenv."""
+    inherited, in_force = C.c_int(0), C.c_int(0)
+    rc = _lib.bpgpu_hw_queues(C.byref(inherited), C.byref(in_force))
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return inherited.value, in_force.value
+
+
 # bpgpu_pippenger_plan (include/bpgpu.h BPGPU_PIP_PLAN_*)
 PIP_PLAN_FIELDS = ("c", "W", "two_level", "task", "task_search", "task_sort", "scan", "coarse_scan", "final_quad", "chunks")
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Does libbpgpu.so's load-time default of GPU_MAX_HW_QUEUES reach the HIP runtime?  One process: import torch, then the library,
-then ONE bpgpu_r1cs_verify_stream_dev call over 64 x 1024 proofs (bench.py's workload cache), five times.  Run it plain and with
-GPU_MAX_HW_QUEUES=4 exported: the rates differ by ~3x when the default is effective.  Usage: queue_probe.py <workload-cache>.1024"""
+"""Does libbpgpu.so's load-time claim of hardware queues (include/bpgpu.h: bpgpu_hw_queues) reach the HIP runtime?  One process:
+import torch, then the library, then ONE bpgpu_r1cs_verify_stream_dev call over 64 x 1024 proofs (bench.py's workload cache), five
+times.  Run it plain and with BPGPU_HW_QUEUES=0 GPU_MAX_HW_QUEUES=4 exported (the library then keeps the 4): the rates differ by ~3x
+when the claim is effective.  Usage: queue_probe.py <workload-cache>.1024"""
 import os
 import pickle
 import sys
@@ -30,5 +31,5 @@ for _ in range(6):
     ts.append(time.perf_counter() - t0)
 assert gpu.download(dok, 4 * nb * reps) == (1).to_bytes(4, "little") * (nb * reps)
 ts = sorted(ts[1:])
-print(f"GPU_MAX_HW_QUEUES before the imports: {before!r}, after: {os.environ.get('GPU_MAX_HW_QUEUES')!r}; "
+print(f"GPU_MAX_HW_QUEUES in os.environ: {before!r}; (inherited, in force) as the library reports them: {mb.lib.hw_queues()}; "
       f"one call over {nb * reps} proofs: {ts[len(ts) // 2] * 1e3:.2f} ms = {nb * reps / ts[len(ts) // 2] / 1e6:.2f} M verifications/s")
