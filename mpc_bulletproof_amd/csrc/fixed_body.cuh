@@ -73,16 +73,7 @@ __device__ __forceinline__ void fixed_small_body(const AffDev *table, size_t n, 
   }
   Jac accj = xyzz_to_jac(acc);
 #pragma unroll 1
-  for (int off = LPM / 2; off > 0; off >>= 1) {
-    Jac q;
-#pragma unroll
-    for (int t = 0; t < NL; t++) {
-      q.X.v[t] = __shfl_xor(accj.X.v[t], off, 64);
-      q.Y.v[t] = __shfl_xor(accj.Y.v[t], off, 64);
-      q.Z.v[t] = __shfl_xor(accj.Z.v[t], off, 64);
-    }
-    accj = jac_add(accj, q);
-  }
+  for (int off = LPM / 2; off > 0; off >>= 1) accj = jac_add(accj, jac_shfl_xor(accj, off));
   if (lane == 0 && live) raw_store(&out[b], accj);
 }
 // The same MSMs with a PROOF per lane and a run of whole generators per wave (`gens_per_chunk` of the 2 + 2n): the 64 lanes of a wave

@@ -9,8 +9,7 @@
 #include <cstdlib>
 #include "fixed_body.cuh"
 #include "vs_prep.cuh"
-#include "ec29_quad.cuh"
-#include "ec29_row.cuh"
+#include "ec_chain.cuh"
 
 using namespace bp;
 
@@ -465,123 +464,57 @@ __global__ void __launch_bounds__(64) k_verify_windows(const AffRaw *tab, const 
 // sum_g 2^(32 g) T_g (224 doublings, 7 additions).  The dependency chain of a batch loses 49 of its 63 general
 // additions for 8 x 28 extra doublings per proof (+3 % instructions).
 constexpr int HG = 8;   // windows per group
+// The chain itself, its three forms and their invariants: ec_chain.cuh.  Both stages are horner_chain with
+// (count, stride, dbl) = (HG, 1, SW) in place over the nb * 64 / HG groups, then (64 / HG, HG, SW * HG) per proof into varsum.
 __global__ void __launch_bounds__(64) k_verify_horner_groups(JacRaw *winsum, size_t nb) {
   __builtin_amdgcn_s_setprio(2);
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nb * (64 / HG)) return;
-  JacRaw *s = winsum + t * HG;          // = winsum[p * 64 + g * HG]
-  Jac acc = raw_load(&s[HG - 1]);
-#pragma unroll 1
-  for (int i = HG - 2; i >= 0; i--) {
-#pragma unroll 1
-    for (int d = 0; d < SW; d++) acc = jac_dbl(acc);
-    acc = jac_add(acc, raw_load(&s[i]));
-  }
-  raw_store(&s[0], acc);
+  horner_chain<LaneForm>(blockIdx.x, nb * (64 / HG), winsum, HG, HG, 1, SW, winsum, HG);
 }
 // stage 1 with a DPP quad per (proof, group): the 28 doublings and 7 additions at the quad's depth (latency mode: 4x the lanes
 // and ~2.3x the instructions of this small stage for ~40 % of its time)
 __global__ void __launch_bounds__(64) k_verify_horner_groups4(JacRaw *winsum, size_t nb) {
   __builtin_amdgcn_s_setprio(2);
-  const int role = threadIdx.x & 3;
-  size_t t = (size_t)blockIdx.x * 16 + (threadIdx.x >> 2);
-  const size_t units = nb * (64 / HG);
-  const bool live = t < units;
-  if (!live) t = units - 1;            // whole quads stay active
-  JacRaw *s = winsum + t * HG;
-  JacT acc = jact_from_jac(raw_load(&s[HG - 1]));
-#pragma unroll 1
-  for (int i = HG - 2; i >= 0; i--) {
-#pragma unroll 1
-    for (int d = 0; d < SW; d++) acc = q4_dbl(acc, role);
-    acc = q4_add(acc, jact_from_jac(raw_load(&s[i])), role);
-  }
-  // (a clamped quad recomputes the last unit; only live quads store, after every load of the unit's slot 0 is done)
-  if (live && role == 0) raw_store(&s[0], jact_to_jac(acc));
+  horner_chain<QuadForm>(blockIdx.x, nb * (64 / HG), winsum, HG, HG, 1, SW, winsum, HG);
 }
 // stage 1 with a whole WAVE per (proof, group) (ec29_row.cuh): 28 doublings + 7 additions in ~23 us instead of ~65 us on a quad --
 // for the few groups of a small MSM or a handful of proofs, where this stage is a link of a lone chain
 __global__ void __launch_bounds__(64) k_verify_horner_groups_row(JacRaw *winsum) {
   __builtin_amdgcn_s_setprio(2);
-  const RowK K = rowk_init();
-  JacRaw *s = winsum + (size_t)blockIdx.x * HG;
-  JacR acc = jacr_from_limbs(K, s[HG - 1].v);
-#pragma unroll 1
-  for (int i = HG - 2; i >= 0; i--) {
-#pragma unroll 1
-    for (int d = 0; d < SW; d++) acc = rdbl(K, acc);
-    acc = radd(K, acc, jacr_addend_from_limbs(K, s[i].v));
-  }
-  jacr_store(K, s[0].v, acc);      // (slot 0 was this wave's last load)
+  horner_chain<RowForm>(blockIdx.x, gridDim.x, winsum, HG, HG, 1, SW, winsum, HG);
 }
-// one lane per proof over `count` partial sums `stride` slots apart, `dbl` doublings between them
-struct HornerArgs { const JacRaw *winsum; JacRaw *varsum; size_t nb; int count, stride, dbl, quad; };
+// stage 2, a chain per proof over `count` partial sums `stride` slots apart, `dbl` doublings between them.  The forms:
+//   lane: 16 waves carrying the longest link of a batch's chain;
+//   quad (ec29_quad.cuh): a doubling is 3 field multiplications deep instead of 9, a general addition 5 instead of 16 -- that
+//     link shortened ~1.7x for 4x the lanes;
+//   row (ec29_row.cuh: one field multiplication spread over the 16 lanes of a DPP row, the four rows = the four products of
+//     a level): a doubling is ~270 instructions deep instead of 675 -- 0.58 us against 1.35 us -- for 16x the lanes of the
+//     quad form.  The form for a chain that has the chip to itself: a lone batch (latency mode), the MSMs.
+struct HornerArgs { const JacRaw *winsum; JacRaw *varsum; size_t nb; int count, stride, dbl; ChainForm form; };
 __device__ __forceinline__ void horner_body(const HornerArgs &h, size_t blk) {
-  __builtin_amdgcn_s_setprio(2);   // 16 waves carrying the longest link of the chain
-  size_t p = blk * 64 + threadIdx.x;
-  if (p >= h.nb) return;
-  Jac acc = raw_load(&h.winsum[p * 64 + (size_t)(h.count - 1) * h.stride]);
-#pragma unroll 1
-  for (int w = h.count - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < h.dbl; d++) acc = jac_dbl(acc);
-    acc = jac_add(acc, raw_load(&h.winsum[p * 64 + (size_t)w * h.stride]));
-  }
-  raw_store(&h.varsum[p], acc);
-}
-// The same pass with the four lanes of a DPP quad per proof (ec29_quad.cuh): a doubling is 3 field multiplications
-// deep instead of 9, a general addition 5 instead of 16 -- the longest link of a batch's chain shortened ~1.7x for
-// 4x the lanes of a 16-wave kernel.  16 proofs per wave.
-__device__ __forceinline__ void horner4_body(const HornerArgs &h, size_t blk) {
   __builtin_amdgcn_s_setprio(2);
-  const int role = threadIdx.x & 3;
-  size_t p = blk * 16 + (threadIdx.x >> 2);
-  const bool live = p < h.nb;
-  if (!live) p = h.nb - 1;             // whole quads stay active
-  JacT acc = jact_from_jac(raw_load(&h.winsum[p * 64 + (size_t)(h.count - 1) * h.stride]));
-#pragma unroll 1
-  for (int w = h.count - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < h.dbl; d++) acc = q4_dbl(acc, role);
-    acc = q4_add(acc, jact_from_jac(raw_load(&h.winsum[p * 64 + (size_t)w * h.stride])), role);
+  switch (h.form) {
+    case ChainForm::Row: horner_chain<RowForm>(blk, h.nb, h.winsum, 64, h.count, h.stride, h.dbl, h.varsum, 1); break;
+    case ChainForm::Quad: horner_chain<QuadForm>(blk, h.nb, h.winsum, 64, h.count, h.stride, h.dbl, h.varsum, 1); break;
+    default: horner_chain<LaneForm>(blk, h.nb, h.winsum, 64, h.count, h.stride, h.dbl, h.varsum, 1); break;
   }
-  if (live && role == 0) raw_store(&h.varsum[p], jact_to_jac(acc));
-}
-// The same pass with a whole WAVE per proof (ec29_row.cuh: one field multiplication spread over the 16 lanes of a DPP row, the
-// four rows = the four products of a level): a doubling is ~270 instructions deep instead of 675 -- 0.58 us against 1.35 us --
-// for 16x the lanes of the quad form.  The form for a chain that has the chip to itself: a lone batch (latency mode), the MSMs.
-__device__ __forceinline__ void horner_row_body(const HornerArgs &h, size_t blk) {
-  __builtin_amdgcn_s_setprio(2);
-  const RowK K = rowk_init();
-  const size_t p = blk;
-  JacR acc = jacr_from_limbs(K, h.winsum[p * 64 + (size_t)(h.count - 1) * h.stride].v);
-#pragma unroll 1
-  for (int w = h.count - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < h.dbl; d++) acc = rdbl(K, acc);
-    acc = radd(K, acc, jacr_addend_from_limbs(K, h.winsum[p * 64 + (size_t)w * h.stride].v));
-  }
-  jacr_store(K, h.varsum[p].v, acc);
 }
 // the Horner lanes (blocks [0, horner_blocks)) and the small fixed-base MSMs in one launch
 template <int C, int LPM>
 __global__ void __launch_bounds__(64) k_verify_back(HornerArgs h, unsigned horner_blocks, FixedSmallArgs f) {
-  if (blockIdx.x < horner_blocks) {
-    if (h.quad == 2) horner_row_body(h, blockIdx.x);
-    else if (h.quad) horner4_body(h, blockIdx.x);
-    else horner_body(h, blockIdx.x);
-  }
+  if (blockIdx.x < horner_blocks) horner_body(h, blockIdx.x);
   else fixed_small_body<C, LPM>(f.table, f.n, f.cap, f.scalars, f.sc_stride, f.out, f.nb, blockIdx.x - horner_blocks);
 }
 // the same launch with the generator half walked a proof per lane, a run of generators per wave (fixed_chunk_body)
 template <int C, int AHEAD>
 __global__ void __launch_bounds__(64) k_verify_back_q(HornerArgs h, unsigned horner_blocks, FixedSmallArgs f) {
-  if (blockIdx.x < horner_blocks) {
-    if (h.quad == 2) horner_row_body(h, blockIdx.x);
-    else if (h.quad) horner4_body(h, blockIdx.x);
-    else horner_body(h, blockIdx.x);
-  }
+  if (blockIdx.x < horner_blocks) horner_body(h, blockIdx.x);
   else fixed_chunk_body<C, AHEAD>(f.table, f.n, f.cap, f.scalars, f.sc_stride, f.out, f.nb, f.chunks, f.gens_per_chunk, blockIdx.x - horner_blocks);
+}
+// non-zero: a scalar of proof p was not canonical, or a table lane found one of its points malformed
+__device__ __forceinline__ int wp_malformed(const int32_t *bad_lane, size_t lanes, const int32_t *bad_sc, size_t p) {
+  int malformed = bad_sc ? bad_sc[p] : 0;
+  for (size_t l = 0; l < lanes; l++) malformed |= bad_lane[p * lanes + l];
+  return malformed;
 }
 // lane per proof: variable-base sum + fixed-base partial; ok = identity and every input of the proof well-formed
 __global__ void __launch_bounds__(64) k_verify_verdict(const JacRaw *varsum, const JacRaw *fixed, size_t nb, const int32_t *bad_lane,
@@ -589,22 +522,8 @@ __global__ void __launch_bounds__(64) k_verify_verdict(const JacRaw *varsum, con
   __builtin_amdgcn_s_setprio(2);
   size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nb) return;
-  Jac acc = jac_add(raw_load(&varsum[p]), raw_load(&fixed[p]));
-  const bool inf = jac_is_inf(acc) || is_zero_exact(acc.Z);
-  int malformed = bad_sc ? bad_sc[p] : 0;
-  for (size_t l = 0; l < lanes; l++) malformed |= bad_lane[p * lanes + l];
-  ok[p] = (inf && !malformed) ? 1 : 0;
-  if (mega) {
-    uint32_t w[16];
-    if (inf) {
-#pragma unroll
-      for (int j = 0; j < 16; j++) w[j] = 0;
-    } else {
-      aff_to_boundary(w, jac_to_aff(acc));
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) { mega[2 * p].w[j] = w[j]; mega[2 * p + 1].w[j] = w[8 + j]; }
-  }
+  const Jac acc = jac_add(raw_load(&varsum[p]), raw_load(&fixed[p]));
+  verdict_store(acc, wp_malformed(bad_lane, lanes, bad_sc, p), ok, mega, p);
 }
 // the verdict over `chunks` partial sums of the generator half per proof (k_verify_back_q): R lanes per proof add chunks / R partials
 // each, a butterfly over the R lanes, lane 0 of the proof decides
@@ -620,33 +539,10 @@ __global__ void __launch_bounds__(64) k_verify_verdict_q(const JacRaw *varsum, c
 #pragma unroll 1
   for (unsigned q = r + R; q < chunks; q += R) acc = jac_add(acc, raw_load(&part[p * chunks + q]));
 #pragma unroll 1
-  for (unsigned off = R / 2; off > 0; off >>= 1) {
-    Jac o;
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-      o.X.v[j] = __shfl_xor(acc.X.v[j], off, 64);
-      o.Y.v[j] = __shfl_xor(acc.Y.v[j], off, 64);
-      o.Z.v[j] = __shfl_xor(acc.Z.v[j], off, 64);
-    }
-    acc = jac_add(acc, o);
-  }
+  for (unsigned off = R / 2; off > 0; off >>= 1) acc = jac_add(acc, jac_shfl_xor(acc, off));
   if (r != 0 || !live) return;
   acc = jac_add(raw_load(&varsum[p]), acc);
-  const bool inf = jac_is_inf(acc) || is_zero_exact(acc.Z);
-  int malformed = bad_sc ? bad_sc[p] : 0;
-  for (size_t l = 0; l < lanes; l++) malformed |= bad_lane[p * lanes + l];
-  ok[p] = (inf && !malformed) ? 1 : 0;
-  if (mega) {
-    uint32_t w[16];
-    if (inf) {
-#pragma unroll
-      for (int j = 0; j < 16; j++) w[j] = 0;
-    } else {
-      aff_to_boundary(w, jac_to_aff(acc));
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) { mega[2 * p].w[j] = w[j]; mega[2 * p + 1].w[j] = w[8 + j]; }
-  }
+  verdict_store(acc, wp_malformed(bad_lane, lanes, bad_sc, p), ok, mega, p);
 }
 // points per table lane.  8 = fewest instructions (affine builder: three inversions per 8 points; the front launch 6.68e6 VALU
 // wave-instructions per 1 024-proof step against 9.78e6 at 4), but 48 table waves whose chain is 293 us alone against 96 waves
@@ -715,19 +611,27 @@ void verify_wp_windows(hipStream_t st, const VerifyWp &v, const uint32_t *var_sc
   WpLayout L = wp_layout(v);
   hipLaunchKernelGGL(k_verify_windows, dim3(v.nb), dim3(64), 0, st, L.t.tab, var_scalars, v.nvar, L.winsum);
 }
-static bool wp_grouped() { return true; }   // (two-stage Horner: the one-stage pass stays in the code for reference)
+// The form of the two Horner stages.  An option (BPGPU_OPT_GROUPS_FORM, BPGPU_OPT_HORNER_FORM: 1 = lane, 2 = quad, 3 = a wave
+// per chain) decides; 0 = by mode: a wave per chain when the chain has the chip to itself -- latency mode and at most
+// v.row_max chains -- and else, stage 1: a quad in latency mode, a lane otherwise; stage 2: a quad.
+static ChainForm wp_groups_form(const VerifyWp &v, size_t units) {
+  if (v.groups_form) return chain_form_option(v.groups_form, ChainForm::Lane);
+  if (!v.latency_mode) return ChainForm::Lane;
+  return v.horner_form == 0 && units <= v.row_max ? ChainForm::Row : ChainForm::Quad;   // (a forced stage-2 form keeps stage 1 off the rows)
+}
+static ChainForm wp_horner_form(const VerifyWp &v) {
+  if (v.horner_form) return chain_form_option(v.horner_form, ChainForm::Quad);
+  return v.latency_mode && v.nb <= v.row_max ? ChainForm::Row : ChainForm::Quad;
+}
 void verify_wp_groups(hipStream_t st, const VerifyWp &v) {
   static_assert(num_windows<SW>() == 64, "64 window sums per proof");
-  if (!wp_grouped()) return;
   WpLayout L = wp_layout(v);
-  const bool quad = v.groups_form ? v.groups_form == 2 : v.latency_mode;   // BPGPU_OPT_GROUPS_FORM: 0 = by mode, 1 = lane, 2 = quad, 3 = wave per group of 8 windows
   const size_t units = v.nb * (64 / HG);
-  if (v.groups_form == 3 || (v.groups_form == 0 && v.latency_mode && v.horner_form == 0 && units <= v.row_max)) {
-    hipLaunchKernelGGL(k_verify_horner_groups_row, dim3((unsigned)units), dim3(64), 0, st, L.winsum);
-    return;
-  }
-  if (quad) hipLaunchKernelGGL(k_verify_horner_groups4, dim3((v.nb * (64 / HG) + 15) / 16), dim3(64), 0, st, L.winsum, v.nb);
-  else hipLaunchKernelGGL(k_verify_horner_groups, dim3((v.nb * (64 / HG) + 63) / 64), dim3(64), 0, st, L.winsum, v.nb);
+  const ChainForm form = wp_groups_form(v, units);
+  const dim3 grid(chain_blocks(form, units));
+  if (form == ChainForm::Row) hipLaunchKernelGGL(k_verify_horner_groups_row, grid, dim3(64), 0, st, L.winsum);
+  else if (form == ChainForm::Quad) hipLaunchKernelGGL(k_verify_horner_groups4, grid, dim3(64), 0, st, L.winsum, v.nb);
+  else hipLaunchKernelGGL(k_verify_horner_groups, grid, dim3(64), 0, st, L.winsum, v.nb);
 }
 static size_t wp_chunk_gens(const VerifyWp &v);
 #ifndef WP_BACK_AHEAD
@@ -754,13 +658,8 @@ static void launch_back(hipStream_t st, const HornerArgs &h, unsigned hb, const 
 void verify_wp_back(hipStream_t st, const VerifyWp &v, int c, const AffDev *table, size_t n, size_t cap,
                     const uint32_t *fixed_scalars, size_t sc_stride, JacRaw *out_fixed) {
   WpLayout L = wp_layout(v);
-  // v.horner_form: 0 = by mode (a wave per proof when the chain has the chip to itself: latency mode and at most v.row_max
-  // proofs / groups; else a quad per proof), 1 = lane, 2 = quad, 3 = wave (row form)
-  int quad = v.horner_form == 1 ? 0 : (v.horner_form == 3 ? 2 : 1);
-  if (v.horner_form == 0 && v.latency_mode && v.nb <= v.row_max) quad = 2;
-  HornerArgs h{L.winsum, L.varsum, v.nb, 64, 1, SW, quad};
-  if (wp_grouped()) { h.count = 64 / HG; h.stride = HG; h.dbl = SW * HG; }
-  const unsigned hb = (unsigned)(quad == 2 ? v.nb : (quad ? (v.nb + 15) / 16 : (v.nb + 63) / 64));
+  HornerArgs h{L.winsum, L.varsum, v.nb, 64 / HG, HG, SW * HG, wp_horner_form(v)};   // over what verify_wp_groups left
+  const unsigned hb = chain_blocks(h.form, v.nb);
   FixedSmallArgs f{table, n, cap, fixed_scalars, sc_stride, out_fixed, v.nb};
   if (table && verify_wp_fixed_parts(v, n) > 1) { f.chunks = (unsigned)verify_wp_fixed_parts(v, n); f.gens_per_chunk = (unsigned)wp_chunk_gens(v); }
   if (!table) {   // the generator half ran as its own launch: Horner pass only

@@ -20,8 +20,7 @@ __global__ void __launch_bounds__(256) k_points_from_boundary(const Words8 *xy, 
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t w[16];
-#pragma unroll
-  for (int j = 0; j < 8; j++) { w[j] = xy[2 * i].w[j]; w[8 + j] = xy[2 * i + 1].w[j]; }
+  boundary_load(w, xy, i);
   Aff a;
   bool ok = aff_from_boundary(a, w);
   if (!ok) {
@@ -40,12 +39,7 @@ void points_from_boundary(hipStream_t st, const Words8 *xy, AffDev *out, size_t 
 __global__ void __launch_bounds__(64) k_jac_to_boundary(const JacRaw *in, Words8 *xy, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  Jac p = raw_load(&in[i]);
-  if (!jac_is_inf(p) && is_zero_exact(p.Z)) p = jac_inf();
-  uint32_t w[16];
-  aff_to_boundary(w, jac_to_aff(p));
-#pragma unroll
-  for (int j = 0; j < 8; j++) { xy[2 * i].w[j] = w[j]; xy[2 * i + 1].w[j] = w[8 + j]; }
+  jac_store_boundary(xy, i, raw_load(&in[i]));
 }
 void jac_to_boundary(hipStream_t st, const JacRaw *in, Words8 *xy, size_t n) {
   if (!n) return;
@@ -155,31 +149,10 @@ __global__ void __launch_bounds__(64) k_verify_finalize(const JacRaw *var, size_
     acc = jac_add(acc, q);
   }
 #pragma unroll 1
-  for (int off = 16; off > 0; off >>= 1) {
-    Jac q;
-#pragma unroll
-    for (int t = 0; t < NL; t++) {
-      q.X.v[t] = __shfl_xor(acc.X.v[t], off, 64);
-      q.Y.v[t] = __shfl_xor(acc.Y.v[t], off, 64);
-      q.Z.v[t] = __shfl_xor(acc.Z.v[t], off, 64);
-    }
-    acc = jac_add(acc, q);
-  }
+  for (int off = 16; off > 0; off >>= 1) acc = jac_add(acc, jac_shfl_xor(acc, off));
   if (lane == 0 && live) {
-    bool inf = jac_is_inf(acc) || is_zero_exact(acc.Z);
     const bool malformed = (bad_sc && bad_sc[p]) || (bad_pt && bad_pt[p]);
-    ok[p] = (inf && !malformed) ? 1 : 0;
-    if (mega) {
-      uint32_t w[16];
-      if (inf) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) w[j] = 0;
-      } else {
-        aff_to_boundary(w, jac_to_aff(acc));
-      }
-#pragma unroll
-      for (int j = 0; j < 8; j++) { mega[2 * p].w[j] = w[j]; mega[2 * p + 1].w[j] = w[8 + j]; }
-    }
+    verdict_store(acc, malformed, ok, mega, p);
   }
 }
 void verify_finalize(hipStream_t st, const JacRaw *var, size_t nvar, const JacRaw *fixed, size_t nb,
@@ -194,20 +167,13 @@ __global__ void __launch_bounds__(128) k_points_sum(const Words8 *xy, size_t n, 
   Jac acc = jac_inf();
   for (size_t i = threadIdx.x; i < n; i += 128) {
     uint32_t w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { w[j] = xy[2 * i].w[j]; w[8 + j] = xy[2 * i + 1].w[j]; }
+    boundary_load(w, xy, i);
     Aff a;
     if (!aff_from_boundary(a, w)) { atomicOr(bad, 1); continue; }
     acc = jac_madd(acc, a);
   }
   acc = block_sum<128>(acc, smem);
-  if (threadIdx.x == 0) {
-    if (!jac_is_inf(acc) && is_zero_exact(acc.Z)) acc = jac_inf();
-    uint32_t w[16];
-    aff_to_boundary(w, jac_to_aff(acc));
-#pragma unroll
-    for (int j = 0; j < 8; j++) { out_xy[0].w[j] = w[j]; out_xy[1].w[j] = w[8 + j]; }
-  }
+  if (threadIdx.x == 0) jac_store_boundary(out_xy, 0, acc);
 }
 void points_sum(hipStream_t st, const Words8 *xy, size_t n, Words8 *out_xy, int *bad) {
   hipLaunchKernelGGL(k_points_sum, dim3(1), dim3(128), 0, st, xy, n, out_xy, bad);

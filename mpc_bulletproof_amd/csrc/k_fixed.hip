@@ -286,16 +286,7 @@ __global__ void __launch_bounds__(64) k_fixed_msm_ipp_g(const AffDev *table, siz
   }
   Jac accj = xyzz_to_jac(acc);
 #pragma unroll 1
-  for (int off = 8; off < 64; off <<= 1) {               // over the pair-lanes: lanes mj, mj + 8, ... of the wave
-    Jac q;
-#pragma unroll
-    for (int t = 0; t < NL; t++) {
-      q.X.v[t] = __shfl_xor(accj.X.v[t], off, 64);
-      q.Y.v[t] = __shfl_xor(accj.Y.v[t], off, 64);
-      q.Z.v[t] = __shfl_xor(accj.Z.v[t], off, 64);
-    }
-    accj = jac_add(accj, q);
-  }
+  for (int off = 8; off < 64; off <<= 1) accj = jac_add(accj, jac_shfl_xor(accj, off));   // over the pair-lanes: lanes mj, mj + 8, ... of the wave
   if (pl == 0 && live) raw_store(&out[msm * gridDim.x + blockIdx.x], accj);
 }
 static bool ipp_grouped(size_t nmsm) { return nmsm >= 16; }   // (fewer MSMs than lanes of a unit: the block-per-chunk kernel)

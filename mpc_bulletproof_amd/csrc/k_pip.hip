@@ -13,9 +13,7 @@
 //   6 k_pip_final     Horner over the windows: sum_w 2^(c w) S_w (252 doublings, one lane per instance)
 // Integer work only; step 5's doubling chain (<= 252 sequential doublings, ~1 ms) is the latency
 // floor of any variable-base MSM on this machine.
-#include "ec_dev.cuh"
-#include "ec29_quad.cuh"
-#include "ec29_row.cuh"
+#include "ec_chain.cuh"
 
 using namespace bp;
 
@@ -454,16 +452,7 @@ __global__ void __launch_bounds__(PH_TPB) k_pip_merge_heavy(const uint32_t *toff
   for (uint32_t t = lo + threadIdx.x; t < hi; t += PH_TPB) acc = jac_add(acc, raw_load(&partial[t]));
   static_assert(PH_TPB == 64, "one wave: shuffle butterfly, no LDS round trips");
 #pragma unroll 1
-  for (int off = 32; off > 0; off >>= 1) {
-    Jac q;
-#pragma unroll
-    for (int t = 0; t < NL; t++) {
-      q.X.v[t] = __shfl_xor(acc.X.v[t], off, 64);
-      q.Y.v[t] = __shfl_xor(acc.Y.v[t], off, 64);
-      q.Z.v[t] = __shfl_xor(acc.Z.v[t], off, 64);
-    }
-    acc = jac_add(acc, q);
-  }
+  for (int off = 32; off > 0; off >>= 1) acc = jac_add(acc, jac_shfl_xor(acc, off));
   if (threadIdx.x == 0) raw_store(&buckets[b], acc);
 }
 // S_w = sum_{d=1}^{half} d * B_d per (window, instance), split into `chunks` blocks of half / chunks buckets each
@@ -531,16 +520,7 @@ __global__ void __launch_bounds__(64) k_pip_window_a(PipParams pp, const JacRaw 
   for (int i = 1; i < L; i <<= 1) y = jac_dbl(y);
   Jac v = jac_add(ws, y);
 #pragma unroll 1
-  for (int off = 32; off > 0; off >>= 1) {
-    Jac q;
-#pragma unroll
-    for (int t = 0; t < NL; t++) {
-      q.X.v[t] = __shfl_xor(v.X.v[t], off, 64);
-      q.Y.v[t] = __shfl_xor(v.Y.v[t], off, 64);
-      q.Z.v[t] = __shfl_xor(v.Z.v[t], off, 64);
-    }
-    v = jac_add(v, q);
-  }
+  for (int off = 32; off > 0; off >>= 1) v = jac_add(v, jac_shfl_xor(v, off));
   if (l == 0) {
     raw_store(&part[seg * 2 * chunks + ch], v);
     raw_store(&part[seg * 2 * chunks + chunks + ch], suf);
@@ -595,36 +575,16 @@ static int pip_window_chunks(int half, size_t ninst, int W) {
   while (half / (chunks * 2) >= PW_TPB * 4 && ninst * (size_t)W * (size_t)(chunks * 2) <= 8192) chunks *= 2;   // >= 4 buckets per lane
   return chunks;
 }
-// Horner over the windows, one QUAD per instance (ec29_quad.cuh: a doubling is 3 field multiplications deep instead of
-// 9): sum_w 2^(c w) S_w with 252 doublings in all (per-window doubling would cost c W^2 / 2 of them).  One lane per
+// Horner over the windows (ec_chain.cuh), one QUAD per instance (ec29_quad.cuh: a doubling is 3 field multiplications deep
+// instead of 9): sum_w 2^(c w) S_w with 252 doublings in all (per-window doubling would cost c W^2 / 2 of them).  One lane per
 // instance took 0.75 - 0.9 ms however small the MSM: the latency floor of every bucket-method call.
 __global__ void __launch_bounds__(64) k_pip_final(const JacRaw *win, int W, int c, size_t ninst, JacRaw *out, size_t out_stride) {
-  const int role = threadIdx.x & 3;
-  size_t inst = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-  const bool live = inst < ninst;
-  if (!live) inst = ninst - 1;          // whole quads stay active
-  JacT acc = jact_from_jac(raw_load(&win[inst * W + W - 1]));
-#pragma unroll 1
-  for (int w = W - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < c; d++) acc = q4_dbl(acc, role);
-    acc = q4_add(acc, jact_from_jac(raw_load(&win[inst * W + w])), role);
-  }
-  if (live && role == 0) raw_store(&out[inst * out_stride], jact_to_jac(acc));
+  horner_chain<QuadForm>(blockIdx.x, ninst, win, W, W, 1, c, out, out_stride);
 }
 // The same with a WAVE per instance (ec29_row.cuh: a doubling ~270 instructions deep instead of 675): for the few instances of
 // an ordinary call this tail is a lone chain on an idle chip -- 0.15 ms instead of 0.37.
 __global__ void __launch_bounds__(64) k_pip_final_row(const JacRaw *win, int W, int c, JacRaw *out, size_t out_stride) {
-  const RowK K = rowk_init();
-  const size_t inst = blockIdx.x;
-  JacR acc = jacr_from_limbs(K, win[inst * W + W - 1].v);
-#pragma unroll 1
-  for (int w = W - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < c; d++) acc = rdbl(K, acc);
-    acc = radd(K, acc, jacr_addend_from_limbs(K, win[inst * W + w].v));
-  }
-  jacr_store(K, out[inst * out_stride].v, acc);
+  horner_chain<RowForm>(blockIdx.x, gridDim.x, win, W, W, 1, c, out, out_stride);
 }
 
 // window choice: minimise  n * W (bucket adds) + W * 2^(c-1) * ~3 (running sums), c in [8, 16]

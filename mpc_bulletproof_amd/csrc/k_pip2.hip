@@ -11,16 +11,15 @@
 //   K4 accum     lane per task: gathers its points (64-byte rows, next one prefetched) and adds them up
 //   K5 reduce    block per window: bucket totals, S_w = sum_d d * B_d by per-lane running sums, offset multiplication
 //                and an LDS tree
-//   K6 final     ONE quad (ec29_quad.cuh): Horner over the windows, 252 cooperative doublings; optional extra addend
-//                and boundary output
+//   K6 final     ONE wave (ec_chain.cuh, row form): Horner over the windows, 252 cooperative doublings; optional extra
+//                addend and boundary output
 // K1, K4 and K6 take riders for what else a caller has ready at that point (fused launches: see verify_combined2).
 // Replaces StarkPoint::msm_iter for 2^10 <= n <= 2^18 single instances (call sites: r1cs/verifier.rs:516,
 // r1cs/prover.rs:465-564, inner_product_proof.rs:90-172); parity: tests/test_gpu_parity.py::test_msm_pippenger_*.
 #include <cstdlib>
 #include "fixed_body.cuh"
 #include "vs_prep.cuh"
-#include "ec29_quad.cuh"
-#include "ec29_row.cuh"
+#include "ec_chain.cuh"
 #include "pip2.cuh"
 
 using namespace bp;
@@ -128,30 +127,18 @@ __global__ void __launch_bounds__(P2R_TPB) k_p2_reduce(Pip2 p) {
   Jac acc = block_sum<P2R_TPB>(jac_add(ws, sm), smem);
   if (tid == 0) raw_store(&p.win[w], acc);
 }
-// ---- K6: ONE quad.  out_raw and / or out_xy (boundary bytes; costs one inversion)
+// ---- K6: ONE wave.  out_raw and / or out_xy (boundary bytes; costs one inversion)
 struct P2Final { const JacRaw *win; int W, c; const JacRaw *extra; int nextra; JacRaw *out_raw; Words8 *out_xy; };
 __device__ __forceinline__ void p2_final_body(const P2Final &f) {
   // ONE wave, row form (ec29_row.cuh): the 252 doublings at ~270 instructions each instead of the quad's 675
-  const RowK K = rowk_init();
-  JacR acc = jacr_from_limbs(K, f.win[f.W - 1].v);
+  const RowForm row(0, 1);
+  JacR acc = horner_sum(row, f.win, f.W, 1, f.c);
 #pragma unroll 1
-  for (int w = f.W - 2; w >= 0; w--) {
-#pragma unroll 1
-    for (int d = 0; d < f.c; d++) acc = rdbl(K, acc);
-    acc = radd(K, acc, jacr_addend_from_limbs(K, f.win[w].v));
-  }
-#pragma unroll 1
-  for (int e = 0; e < f.nextra; e++) acc = radd(K, acc, jacr_addend_from_limbs(K, f.extra[e].v));
-  Jac r = jacr_gather(K, acc);
+  for (int e = 0; e < f.nextra; e++) acc = row.add(acc, row.addend(&f.extra[e]));
+  const Jac r = jacr_gather(row.K, acc);
   if (threadIdx.x == 0) {
     if (f.out_raw) raw_store(f.out_raw, r);
-    if (f.out_xy) {
-      if (!jac_is_inf(r) && is_zero_exact(r.Z)) r = jac_inf();
-      uint32_t w[16];
-      aff_to_boundary(w, jac_to_aff(r));   // Fermat: the one-lane binary GCD measured 150 us slower (its compare / shift steps are serial too)
-#pragma unroll
-      for (int j = 0; j < 8; j++) { f.out_xy[0].w[j] = w[j]; f.out_xy[1].w[j] = w[8 + j]; }
-    }
+    if (f.out_xy) jac_store_boundary(f.out_xy, 0, r);   // (its inversion is Fermat's: the one-lane binary GCD measured 150 us slower -- its compare / shift steps are serial too)
   }
 }
 __global__ void __launch_bounds__(64) k_p2_final(P2Final f) { p2_final_body(f); }
@@ -166,8 +153,7 @@ __global__ void __launch_bounds__(256) k_p2_front(P2Front a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
     uint32_t w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { w[j] = a.xy[2 * i].w[j]; w[8 + j] = a.xy[2 * i + 1].w[j]; }
+    boundary_load(w, a.xy, i);
     Aff q;
     if (!aff_from_boundary(q, w)) { atomicOr(a.bad, 1); q.x = fe_zero<FP>(); q.y = fe_zero<FP>(); }
     aff_store(&a.pts[i], q);
@@ -222,8 +208,7 @@ __global__ void __launch_bounds__(256) k_comb_front(CombFront a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.npts) return;
     uint32_t w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) { w[j] = a.points[2 * i].w[j]; w[8 + j] = a.points[2 * i + 1].w[j]; }
+    boundary_load(w, a.points, i);
     Aff q;
     if (!aff_from_boundary(q, w)) { atomicOr(a.bad, 1); q.x = fe_zero<FP>(); q.y = fe_zero<FP>(); }
     aff_store(&a.pts[i], q);

@@ -503,16 +503,7 @@ __global__ void __launch_bounds__(64) k_ipp_round_tail(size_t nb, const JacRaw *
 #pragma unroll 1
     for (size_t i = ll; i < chunks; i += 16) tot = jac_add(tot, raw_load(&src[i]));
 #pragma unroll 1
-    for (int off = 8; off > 0; off >>= 1) {
-      Jac o;
-#pragma unroll
-      for (int t = 0; t < NL; t++) {
-        o.X.v[t] = __shfl_xor(tot.X.v[t], off, 64);
-        o.Y.v[t] = __shfl_xor(tot.Y.v[t], off, 64);
-        o.Z.v[t] = __shfl_xor(tot.Z.v[t], off, 64);
-      }
-      tot = jac_add(tot, o);
-    }
+    for (int off = 8; off > 0; off >>= 1) tot = jac_add(tot, jac_shfl_xor(tot, off));
     // lane 1 converts R: it takes lane 16's total
     Jac r16;
 #pragma unroll
@@ -528,12 +519,9 @@ __global__ void __launch_bounds__(64) k_ipp_round_tail(size_t nb, const JacRaw *
     if (!jac_is_inf(q) && is_zero_exact(q.Z)) q = jac_inf();
     uint32_t w[16];
     aff_to_boundary(w, jac_to_aff(q));
+    boundary_store(lr_xy, 2 * p + l, w);
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-      lr_xy[(2 * p + l) * 2].w[j] = w[j];
-      lr_xy[(2 * p + l) * 2 + 1].w[j] = w[8 + j];
-      S[4 + 8 * l + j] = (uint64_t)w[2 * j] | ((uint64_t)w[2 * j + 1] << 32);
-    }
+    for (int j = 0; j < 8; j++) S[4 + 8 * l + j] = (uint64_t)w[2 * j] | ((uint64_t)w[2 * j + 1] << 32);
   }
   if (live && l < 4) S[l] = states[p * 4 + l];
   __syncthreads();

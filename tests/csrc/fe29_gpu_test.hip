@@ -8,6 +8,7 @@
 #include "../../mpc_bulletproof_amd/csrc/ec29_quad.cuh"
 #include "../../mpc_bulletproof_amd/csrc/ec29_row.cuh"
 #include "../../mpc_bulletproof_amd/csrc/fe29_sqrt.cuh"
+#include "../../mpc_bulletproof_amd/csrc/ec_chain.cuh"
 using namespace bp;
 
 template <class F> __device__ bool d_load(Fe<F> &out, const uint32_t *w) {
@@ -273,6 +274,32 @@ __global__ void __launch_bounds__(64) k_chain(int form, int nd, const uint32_t *
   if (threadIdx.x == 0) for (int j = 0; j < 16; j++) out[j] = wo[j];
 }
 
+// ---- the production Horner chain (ec_chain.cuh) over JacRaw slots, as the verification and the MSM tails call it.
+// k_slots writes the slots from boundary points (non-trivial Z), k_horner runs horner_chain in one form -- a launch of its own,
+// so that a run with dst = the slots is in place as in production -- and k_slots_out returns every `pitch`-th slot as boundary bytes.
+__global__ void __launch_bounds__(64) k_slots(const bpk::Words8 *xy, bpk::JacRaw *slots, int *rc, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[16];
+  bpk::boundary_load(w, xy, i);
+  Aff p;
+  if (!aff_from_boundary(p, w)) { rc[i] = -1; return; }
+  Jac pj = jac_from_aff(p);
+  const uint32_t zw[8] = {0x12345, 7, 9 + (uint32_t)(i & 3), 0, 0, 0, 0, 0};
+  const Fp z = to_mont(unpack<FP>(zw)), z2 = sqr(z);
+  if (!jac_is_inf(pj)) { pj.X = mul(pj.X, z2); pj.Y = mul(pj.Y, mul(z2, z)); pj.Z = mul(pj.Z, z); }
+  bpk::raw_store(&slots[i], pj);
+  rc[i] = 0;
+}
+template <class F> __global__ void __launch_bounds__(64) k_horner(size_t units, const bpk::JacRaw *src, size_t src_pitch, int count, int stride,
+                                                                  int dbl, bpk::JacRaw *dst, size_t dst_pitch) {
+  bpk::horner_chain<F>(blockIdx.x, units, src, src_pitch, count, stride, dbl, dst, dst_pitch);
+}
+__global__ void __launch_bounds__(64) k_slots_out(const bpk::JacRaw *slots, size_t pitch, bpk::Words8 *xy, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) bpk::jac_store_boundary(xy, i, bpk::raw_load(&slots[i * pitch]));
+}
+
 namespace {
 struct DevBuf {
   void *p = nullptr;
@@ -369,6 +396,25 @@ double g29_chain(int form, int nd, const uint8_t *a, uint8_t *out) {
   }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return down(out, dout, 64) ? (double)best * 1e3 : -100;
+}
+// `units` chains in form 0 (lane), 1 (quad) or 2 (row): chain u = sum_{w < count} 2^(dbl w) S[u span + w stride] over the
+// units x span boundary points S; in_place: the sum overwrites slot u span, else it goes to an array of its own.  out: units points.
+// -1: a shape whose loads would leave the slots
+int g29_horner(int form, const uint8_t *pts, size_t units, int span, int count, int stride, int dbl, int in_place, uint8_t *out, int *rc) {
+  if (!units || count < 1 || stride < 1 || span < (count - 1) * stride + 1 || form < 0 || form > 2) return -1;
+  const size_t n = units * (size_t)span;
+  DevBuf dpts(64 * n), dslots(sizeof(bpk::JacRaw) * n), dres(sizeof(bpk::JacRaw) * units), dout(64 * units), drc(4 * n);
+  if (!up(dpts, pts, 64 * n) || !dslots.p || !dres.p || !dout.p || !drc.p) return -100;
+  bpk::JacRaw *slots = (bpk::JacRaw *)dslots.p, *dst = in_place ? slots : (bpk::JacRaw *)dres.p;
+  const size_t dst_pitch = in_place ? (size_t)span : 1;
+  hipLaunchKernelGGL(k_slots, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, (const bpk::Words8 *)dpts.p, slots, (int *)drc.p, n);
+  const dim3 grid(bpk::chain_blocks((bpk::ChainForm)form, units));
+  if (form == 0) hipLaunchKernelGGL(k_horner<bpk::LaneForm>, grid, dim3(64), 0, 0, units, slots, (size_t)span, count, stride, dbl, dst, dst_pitch);
+  else if (form == 1) hipLaunchKernelGGL(k_horner<bpk::QuadForm>, grid, dim3(64), 0, 0, units, slots, (size_t)span, count, stride, dbl, dst, dst_pitch);
+  else hipLaunchKernelGGL(k_horner<bpk::RowForm>, grid, dim3(64), 0, 0, units, slots, (size_t)span, count, stride, dbl, dst, dst_pitch);
+  hipLaunchKernelGGL(k_slots_out, dim3((unsigned)((units + 63) / 64)), dim3(64), 0, 0, dst, dst_pitch, (bpk::Words8 *)dout.p, units);
+  if (hipDeviceSynchronize() != hipSuccess) return -100;
+  return down(out, dout, 64 * units) && down(rc, drc, 4 * n) ? 0 : -100;
 }
 int g29_point(int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out, int *rc) {
   DevBuf da(64 * n), db(64 * n), dout(64 * n), drc(4 * n);

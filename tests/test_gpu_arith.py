@@ -321,3 +321,70 @@ def test_doubling_chain_latency_row_against_quad(g, capsys):
     with capsys.disabled():
         print(f"\n[chain] 252 doublings + 7 additions on one wave: quad form {us[0]:.1f} us, row form {us[1]:.1f} us")
     assert us[1] < us[0]
+
+
+# ------------------------------------------------------------------ the Horner chain over partial sums (csrc/ec_chain.cuh)
+_HORNER_UNITS = {0: 65, 1: 17, 2: 3}     # lane form: a partial second block; quad form: a wave of one live and fifteen clamped quads
+
+
+def _horner_rows(rnd, count, dbl, rows):
+    """`rows` rows of `count` scalars k_w (window sum S_w = k_w G), cycling through: all identity | only S_0 | leading (top)
+    identities, then points | the doubled accumulator EQUALS its addend | ... is its addend's OPPOSITE (the chain passes through
+    the identity and goes on) | random multiples of G."""
+    pool = [rnd.randrange(1, N) for _ in range(12)]
+    out = []
+    for r in range(rows):
+        k = [rnd.choice(pool) for _ in range(count)]
+        kind = r % 6
+        if kind == 0:
+            k = [0] * count
+        elif kind == 1:
+            k = k[:1] + [0] * (count - 1)
+        elif kind == 2:
+            for w in range(count // 2, count):
+                k[w] = 0
+        elif kind in (3, 4) and count >= 2:
+            k[count - 2] = k[count - 1] << dbl if kind == 3 else -(k[count - 1] << dbl)
+        out.append([x % N for x in k])
+    return out
+
+
+@pytest.mark.parametrize("count,stride,dbl,in_place", [(8, 1, 4, 1), (8, 8, 32, 0), (1, 1, 4, 1), (16, 1, 16, 0)])
+def test_horner_chain_in_every_form_against_the_model(g, count, stride, dbl, in_place):
+    """horner_chain of csrc/ec_chain.cuh -- the loop of both Horner stages of the verification and of the MSM tails -- in the
+    lane, quad and row form over JacRaw slots written by an earlier launch: sum_w 2^(dbl w) S_w equals the model's for rows of
+    window sums with identities, with a doubled accumulator that meets its own addend or its opposite, and random ones.  The
+    shapes: the first stage's (8, 1, 4) IN PLACE (the sum overwrites slot 0 of its chain, which the clamped quads of the last wave
+    load too), the second stage's (8, 8, 32) with G in the slots between the strides, a single term, and 16 terms."""
+    rnd = random.Random(733 + count * stride)
+    cache = {0: pm.INF}
+
+    def pt(k):
+        if k not in cache:
+            cache[k] = pm.pt_neg(cache[N - k]) if N - k in cache else pm.pt_mul(k, pm.G)
+        return cache[k]
+
+    span = count * stride
+    gb = pm.p2b(pm.G)
+    for form, units in _HORNER_UNITS.items():
+        if (count, stride, dbl) != (8, 1, 4):
+            units = min(units, 17)
+        rows = _horner_rows(rnd, count, dbl, max(units, 6))
+        for lo in range(0, len(rows), units):
+            chunk = rows[lo:lo + units]
+            slots = []
+            for k in chunk:
+                for w in range(count):
+                    slots.append(pm.p2b(pt(k[w])))
+                    slots.extend([gb] * (stride - 1))       # a wrong stride reads these
+            n = len(chunk)
+            a = (C.c_uint8 * (64 * n * span)).from_buffer_copy(b"".join(slots))
+            out, rc = (C.c_uint8 * (64 * n))(), (C.c_int * (n * span))()
+            ret = g.g29_horner(form, a, C.c_size_t(n), span, count, stride, dbl, in_place, out, rc)
+            assert ret != -1, "g29_horner refused the shape: its loads would leave the slots"
+            assert ret == 0, "no HIP device"
+            assert not any(rc)
+            ob = bytes(out)
+            for u, k in enumerate(chunk):
+                want = pt(sum(k[w] << (dbl * w) for w in range(count)) % N)
+                assert pm.b2p(ob[64 * u:64 * u + 64]) == want, (form, lo + u, (lo + u) % 6)
