@@ -795,6 +795,65 @@ int bpgpu_mpc_constraints_eval(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb
  * bpgpu_r1cs_commit_values (a null V is "no output"; BPGPU_E_LEN for 3 nb m above 2^30). */
 int bpgpu_mpc_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const uint8_t *v, const uint8_t *v_blinding,
                             uint8_t *V);
+/* ---- two-party witness synthesis: MpcProver::multiply / allocate_multiplier (r1cs_mpc/mpc_prover.rs:183-282) level by level --------
+ * The two-party prover now has its own calls for the witness: a bpgpu_witness gate program (above) is evaluated on three-plane shares,
+ * one DEPENDENCY LEVEL at a time.  The gates of one level read only lower levels, so they are independent, and the product of every
+ * gate is a Beaver step that needs an opening: one level is one network round.  Per level the host calls _mask, opens d and e of
+ * every gate of the level (the opening and its MAC check are the fabric's), and calls _combine.  The product and affine scans of the
+ * single-party path do not carry over: the level is the unit.
+ *   bpgpu_witness_gate_levels  level[i] of gate i inside its phase (0 for an INPUT gate or a gate whose rows read no multiplier of its
+ *       own phase, else 1 + the largest level read): the definition bpgpu_witness_create already uses.  No device.  Refusals: those of
+ *       bpgpu_witness_plan, and BPGPU_E_ARG for a null `level` with n > 0.  A host learns from it, before a session exists, which gate
+ *       element t of a round belongs to and how many triples each round needs.
+ * Encodings and plane rules are those of "two-party prover" above: every share, MAC, modifier, triple, masked and opened value is in
+ * ark-ff Montgomery form; gadget challenges are canonical little-endian, one set per proof, and public: a coefficient
+ * c0 + sum_j chi_j c_j scales all three planes alike.  Layouts, proof-major, "3" the plane (share, MAC, modifier):
+ *   v                  nb x 3 x m             may be NULL when m == 0
+ *   inputs             nb x 3 x n_inputs x 2  all pairs of the program (phase 2 consumes those after phase 1's); may be NULL when the
+ *                                             program has no INPUT gate
+ *   a_L, a_R, a_O      nb x 3 x n             _begin reads them only for phase == 2, where they hold phase 1 (NULL otherwise); _finish
+ *                                             writes all of them: the other phase's multipliers come back as given, zero if never given
+ *   phase              0, 1 or 2, with the meaning, and the rules for gadget_challenges, of bpgpu_r1cs_witness_synthesize
+ * One level, with G = bpgpu_mpc_witness_level_len (the gates of the level the next _mask evaluates; 0 when none is left):
+ *   triples  nb x 3 (x, y, z) x 3 x G       masked  nb x 2 (d, e) x 3 x G       opened  nb x 2 (d, e) x G
+ * Element t belongs to the t-th gate of that level in ascending gate index.
+ *   _mask     for every gate i of the level and every plane k: a_L[i] = the left row evaluated on plane k -- a `One` term contributes
+ *             its coefficient on the modifier plane only and nothing on the other two, as bpgpu_mpc_constraints_eval does -- and
+ *             a_R[i] likewise from the right row; an INPUT gate takes the next pair's planes.  The results are stored in the
+ *             session, d = a_L - x and e = a_R - y are written per plane, and the session keeps the triples.
+ *   _combine  a_O[i] on plane k = z_k + d y_k + e x_k, plus d e on the modifier plane; then the session advances to the next level.
+ *             Every gate takes a triple, also one whose row happens to be public, because the reference's &l * &r does.
+ * Rounds: one _mask / _combine pair per level, so the number of openings is the phase's level count (BPGPU_WIT_PLAN_LEVELS1 /
+ * BPGPU_WIT_PLAN_LEVELS2, both for phase 0); bpgpu_mpc_witness_levels_left counts them down.  A phase without gates has zero levels:
+ * _begin succeeds and _finish returns the planes unchanged.  The program handle must outlive the session.
+ * Refusals, all before anything is launched.  BPGPU_E_ARG: a null required pointer; a phase other than 0, 1 or 2; challenges given or
+ * missing against the rules of bpgpu_r1cs_witness_synthesize; planes missing for phase 2; a BPGPU_GATE_BIT gate in the evaluated
+ * phase (a bit of a shared value is not a local function: the range gadget on shares takes its bits as INPUT pairs (1 - b, b)); a
+ * context after bpgpu_set_shard(world > 1); _mask twice in a row; _combine without a _mask; _mask with no level left; _finish with a
+ * level left.  BPGPU_E_LEN: 3 nb n or 3 nb m above 2^30.  nb == 0: BPGPU_OK with *out left NULL.  A non-canonical ark limb in any
+ * input, `opened` and `triples` included, gives BPGPU_E_ARG, as the other two-party calls do; the session stays where it was (the
+ * call may be repeated with good operands, or the session destroyed).  A failed call leaves no pool memory behind;
+ * bpgpu_mpc_witness_destroy frees an abandoned session (and a finished one: _finish does not).  Profiling: kind 22.
+ * Launches (csrc/k_mpc_witness.hip): _mask is one launch over (virtual prover 3 p + k, gate of the level), a lane per gate and a wave
+ * per gate with a row of more than 64 stored terms; _combine one launch, a lane per (virtual prover, gate).  Measured
+ * (profiles/mpc_witness.log, tools/bench_mpc_witness.py: the device part of ONE _mask + _combine pair of one party under the
+ * library's own events, kind 22 -- the conversions of triples, masked and opened values included, the host's copies and waits not):
+ * 1.957 ms for 256 proofs of one level of 1 024 INPUT gates, 0.073 ms per level for 256 proofs of the 64-shuffle (63 levels of 2
+ * gates), 0.069 ms for one proof of a 300-gate level.  UNMEASURED: every other shape, levels with long rows, the wall clock of a
+ * round (which the host's opening bounds), and more than 256 proofs.  Out of scope: `_dev` forms (no bpgpu_mpc_* call has one), the pool, the host mirror, bench.py, and
+ * skipping the triple of a gate whose rows are public. */
+int bpgpu_witness_gate_levels(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                              const uint32_t *idx, uint32_t *level);
+typedef struct bpgpu_mpc_witness bpgpu_mpc_witness;
+int bpgpu_mpc_witness_begin(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, const uint8_t *v, const uint8_t *inputs,
+                            const uint8_t *gadget_challenges, const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O,
+                            bpgpu_mpc_witness **out);
+size_t bpgpu_mpc_witness_levels_left(const bpgpu_mpc_witness *s);
+size_t bpgpu_mpc_witness_level_len(const bpgpu_mpc_witness *s);
+int bpgpu_mpc_witness_mask(bpgpu_ctx *ctx, bpgpu_mpc_witness *s, const uint8_t *triples, uint8_t *masked);
+int bpgpu_mpc_witness_combine(bpgpu_ctx *ctx, bpgpu_mpc_witness *s, const uint8_t *opened);
+int bpgpu_mpc_witness_finish(bpgpu_ctx *ctx, bpgpu_mpc_witness *s, uint8_t *a_L, uint8_t *a_R, uint8_t *a_O);
+void bpgpu_mpc_witness_destroy(bpgpu_ctx *ctx, bpgpu_mpc_witness *s);
 
 /* out[i] = scalars[i] * (curve generator) -- GeneratorsChain::next (generators.rs:112-124),
  * Q = w * B (prover.rs:687), PedersenGens::commit with B = B_blinding (generators.rs:41-43,61-70) */

@@ -4375,6 +4375,10 @@ int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view) {
   return BPGPU_OK;
 }
 void bpgpu_internal_leave(bpgpu_ctx *ctx) { ctx->mu.unlock(); }
+size_t bpgpu_internal_shard_world(bpgpu_ctx *ctx) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->shard_world;
+}
 void *bpgpu_internal_pool_alloc(bpgpu_ctx *ctx, size_t bytes) {
   void *p = nullptr;
   return pool_alloc(ctx, &p, bytes) ? p : nullptr;

@@ -24,6 +24,8 @@ constexpr int64_t WIT_AFFINE_MIN = 16;
 // an entry point's head and tail: the context's mutex taken and its device selected (on failure the mutex is free again) | released
 BPGPU_HIDDEN int bpgpu_internal_enter(bpgpu_ctx *ctx, bpgpu_internal_view *view);
 BPGPU_HIDDEN void bpgpu_internal_leave(bpgpu_ctx *ctx);
+// the world of bpgpu_set_shard, for a refusal that must come before the device is selected
+BPGPU_HIDDEN size_t bpgpu_internal_shard_world(bpgpu_ctx *ctx);
 // between the two (mutex held): the context's buffer pool (nullptr: out of memory), the failure text of a HIP call -> BPGPU_E_*, a
 // profile mark of `kind` on the stream (start and stop marks alternate), the input flag cleared, and the end of an entry point that
 // waits: the launch check and the flag (BPGPU_E_ARG when raised), the stream drained

@@ -8,25 +8,13 @@
 #include <vector>
 
 #include "../../include/bpgpu.h"
-#include "bpgpu_internal.h"
+#include "witness_host.h"       // struct bpgpu_witness, the scaffolding of an entry point
 #include "witness_dev.cuh"
 
 using namespace bpk;
 using namespace bp;
 
 static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT && BPGPU_GATE_BIT == WIT_OP_BIT, "gate ops of the header");
-
-// (the leading fields are what the refusals on arguments read)
-struct bpgpu_witness {
-  size_t n = 0, n1 = 0, m = 0, nchi = 0, ninp = 0;
-  uint32_t levels[2] = {0, 0};
-  // per phase: the extended compressed levels (the scan lists are the extended chains'; without an affine member those are the
-  // product chains'), the longest product chain, the longest extended chain, and whether the phase has an affine member
-  uint32_t scan_levels[2] = {0, 0}, longest[2] = {0, 0}, xlongest[2] = {0, 0};
-  bool affine[2] = {false, false};
-  void *mem = nullptr;          // one device allocation: everything dev points to
-  WitDev dev{};
-};
 
 namespace {
 
@@ -214,39 +202,6 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
 
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
-#define WCK(x) do { int rc__ = (x); if (rc__ != BPGPU_OK) return rc__; } while (0)
-#define WHIP(ctx, call) WCK(bpgpu_internal_hip(ctx, (call), #call))
-
-// the context's mutex for the length of an entry point
-struct Entered {
-  bpgpu_ctx *ctx;
-  bool in = false;
-  bpgpu_internal_view view{};
-  explicit Entered(bpgpu_ctx *c) : ctx(c) {}
-  int enter() { const int rc = bpgpu_internal_enter(ctx, &view); in = rc == BPGPU_OK; return rc; }
-  ~Entered() { if (in) bpgpu_internal_leave(ctx); }
-};
-// pool buffers of a call, given back on the way out (stream-ordered reuse); declared AFTER the Entered of its call: released under the mutex
-struct Scratch {
-  bpgpu_ctx *ctx;
-  std::vector<void *> held;
-  explicit Scratch(bpgpu_ctx *c) : ctx(c) { held.reserve(8); }
-  void *take(size_t bytes) {
-    void *p = bpgpu_internal_pool_alloc(ctx, bytes);
-    if (p) held.push_back(p);
-    return p;
-  }
-  ~Scratch() { for (void *p : held) bpgpu_internal_pool_release(ctx, p); }
-};
-struct Prof22 {   // kind 22: the launches only the one-call chains have
-  bpgpu_ctx *ctx;
-  explicit Prof22(bpgpu_ctx *c) : ctx(c) { bpgpu_internal_prof_mark(ctx, 22); }
-  ~Prof22() { bpgpu_internal_prof_mark(ctx, 22); }
-};
-template <class Body> int no_throw(Body body) {
-  try { return body(); } catch (const std::bad_alloc &) { return BPGPU_E_OOM; }
-}
-
 // the grids of k_witness.hip are addressable
 bool wit_fits(const bpgpu_witness *w, size_t nb) {
   const size_t widest = std::max(std::max(w->n, w->m), 2 * w->ninp);
@@ -402,6 +357,14 @@ int fs2_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, co
 
 }  // namespace
 
+int bpgpu_internal_witness_levels(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
+                                  const uint32_t *idx, uint32_t *level) {
+  WitShape s;
+  WCK(wit_analyse(n, n1, nchi, op, row_ptr, kind, idx, &s));
+  std::copy(s.level.begin(), s.level.end(), level);
+  return BPGPU_OK;
+}
+
 extern "C" {
 #pragma GCC visibility push(default)
 
@@ -477,13 +440,13 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       }
     }
     // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op | scan_order | scan_ptr |
-    // scan_long | chain_elem | chain_ptr], every part 256-byte aligned
+    // scan_long | chain_elem | chain_ptr | slot | asc], every part 256-byte aligned
     const size_t nslev = (size_t)s.xscan_levels[0] + s.xscan_levels[1];
     const size_t o_rp = up256((nnz ? nnz : 1) * 32), o_var = o_rp + up256((rows + 1) * 4), o_arg = o_var + up256((nnz ? nnz : 1) * 4),
                  o_ord = o_arg + up256((n ? n : 1) * 4), o_lp = o_ord + up256((n ? n : 1) * 4), o_ll = o_lp + up256((nlev + 1) * 4),
                  o_op = o_ll + up256((nlev ? nlev : 1) * 4), o_so = o_op + up256(n ? n : 1), o_sp = o_so + up256((n ? n : 1) * 4),
                  o_sl = o_sp + up256((nslev + 1) * 4), o_ce = o_sl + up256((nslev ? nslev : 1) * 4), o_cp = o_ce + up256((n ? n : 1) * 4),
-                 total = o_cp + up256((nslev + 1) * 4);
+                 o_slot = o_cp + up256((nslev + 1) * 4), o_asc = o_slot + up256((n ? n : 1) * 4), total = o_asc + up256((n ? n : 1) * 4);
     std::vector<uint8_t> img(total, 0);
     Words8 *h_coeff = (Words8 *)img.data();
     uint32_t *h_rp = (uint32_t *)(img.data() + o_rp), *h_var = (uint32_t *)(img.data() + o_var), *h_arg = (uint32_t *)(img.data() + o_arg),
@@ -534,6 +497,18 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       lvl_base += s.levels[ph];
     }
     h_lp[nlev] = at;
+    // a level's gates numbered by ascending gate index (the slots of the two-party form): each of its two runs in order[] ascends,
+    // so the numbering is their merge
+    uint32_t *h_slot = (uint32_t *)(img.data() + o_slot), *h_asc = (uint32_t *)(img.data() + o_asc);
+    for (size_t l = 0; l < nlev; l++) {
+      uint32_t a = h_lp[l], b = h_ll[l];
+      for (uint32_t t = h_lp[l]; t < h_lp[l + 1]; t++) {
+        const bool from_short = a < h_ll[l] && (b >= h_lp[l + 1] || h_ord[a] < h_ord[b]);
+        const uint32_t u = from_short ? a++ : b++;
+        h_slot[u] = t - h_lp[l];
+        h_asc[t] = h_ord[u];
+      }
+    }
     // the same over the extended compressed levels, members apart: a level's ordinary gates (short rows, then long), and the members
     // of the extended chains it heads, chain after chain (heads in program order), each chain from its first member on.  A phase
     // without an affine member has the product chains' lists: pass 2 changed nothing of it
@@ -567,6 +542,9 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     if (!w) return BPGPU_E_OOM;
     w->n = n; w->n1 = n1; w->m = m; w->nchi = nchi; w->ninp = s.ninp;
     w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
+    for (size_t i = 0; i < n; i++) if (op[i] == BPGPU_GATE_BIT) w->bits[i < n1 ? 0 : 1]++;
+    w->level_ptr.assign(h_lp, h_lp + nlev + 1);
+    w->level_long.assign(h_ll, h_ll + nlev);
     for (int ph = 0; ph < 2; ph++) {
       w->scan_levels[ph] = s.xscan_levels[ph]; w->longest[ph] = s.longest[ph];
       w->xlongest[ph] = s.xlongest[ph]; w->affine[ph] = s.xaffine[ph] != 0;
@@ -590,6 +568,8 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     w->dev.scan_long = (const uint32_t *)(d + o_sl);
     w->dev.chain_elem = (const uint32_t *)(d + o_ce);
     w->dev.chain_ptr = (const uint32_t *)(d + o_cp);
+    w->dev.slot = (const uint32_t *)(d + o_slot);
+    w->dev.asc = (const uint32_t *)(d + o_asc);
     w->dev.n = (uint32_t)n; w->dev.m = (uint32_t)m; w->dev.nchi = (uint32_t)nchi; w->dev.ninp = s.ninp;
     *out = w;
     return BPGPU_OK;

@@ -10,22 +10,11 @@
 // Layouts (plain canonical words on the device; the API converts from / to ark-ff Montgomery form around them):
 //   triples [p][j][t = x, y, z][k][i]      masked [p][j][d, e][k][i]      opened [p][j][d, e][i]
 // with j the product of the step (6 in the polynomial build, 2 -- c_L, c_R -- in an IPP round) and i < len.
-#include "fn_dev.cuh"
+#include "mpc_witness_dev.cuh"   // beaver_term: the Beaver combine, stated once
 
 using namespace bp;
 
 namespace bpk {
-
-// plane k of the Beaver product j of proof p at element i
-__device__ __forceinline__ Fn beaver_term(const Words8 *opened, const Words8 *trip, size_t p, size_t nprod, size_t j, int k, size_t len,
-                                          size_t i) {
-  const Words8 *o = opened + ((p * nprod + j) * 2) * len + i;
-  const Words8 *t = trip + ((p * nprod + j) * 9 + k) * len + i;   // x at t, y at t + 3 len, z at t + 6 len
-  const Fn d = load_plain(o), e = load_plain(o + len);
-  Fn r = add(load_plain(t + 6 * len), add(mul(d, load_plain(t + 3 * len)), mul(e, load_plain(t))));
-  if (k == 2) r = add(r, mul(d, e));
-  return r;
-}
 
 // r1cs_mpc/mpc_prover.rs:783-829: the l(x) / r(x) coefficient vectors per plane, layout [6][3 nb][n][9] as k_prover_polys
 // (l1 l2 l3 r0 r1 r3).  Public terms -- y^-i wR in l1, wL in r1 -- land on the modifier plane only; r0 = wO - y^i is PUBLIC and

@@ -294,6 +294,10 @@ struct WitDev {
   const uint32_t *chain_elem; // members
   const uint32_t *chain_ptr;  // compressed levels + 1
   uint32_t n, m, nchi, ninp;
+  // the two-party form (k_mpc_witness.hip) numbers the gates of a level by ascending gate index: asc[level_ptr[l] + t] is the t-th
+  // of them, slot[u] the t of order[u]
+  const uint32_t *slot;       // n
+  const uint32_t *asc;        // n
 };
 // One launch evaluates the gates [g_lo, g_hi) = the levels [l_lo, l_hi) of nb provers on plain canonical planes nb x n (aL, aR, aO:
 // read for the gates below g_lo, written for the range), v nb x m, inputs nb x ninp x 2, chi nb x nchi (or nullptr), all plain.
@@ -478,6 +482,24 @@ void mpc_eval(hipStream_t st, size_t nb, size_t n, size_t padded_n, const Words8
 // IPP round: masked values of c_L = <a_L, b_R>, c_R = <a_R, b_L> (j = 0, 1; a, b: 3 nb x 2h), then their combine into cLR[2 v + j]
 void mpc_ipp_mask(hipStream_t st, size_t nb, size_t h, const Words8 *a, const Words8 *b, const Words8 *trip, Words8 *masked);
 void mpc_ipp_combine(hipStream_t st, size_t nb, size_t h, const Words8 *opened, const Words8 *trip, Words8 *cLR);
+
+// ---- two-party witness synthesis (k_mpc_witness.hip): MpcProver::multiply / allocate_multiplier (mpc_prover.rs:183-282), one
+// dependency level of a gate program per launch pair.  The level is order[lo .. hi) of w, the gates without a long row before mid; it
+// has G = hi - lo gates, and slot t is the t-th of them in ascending gate index.  Planes of the 3 nb virtual provers, plain canonical
+// words: aL, aR, aO 3 nb x n, v 3 nb x m, inputs 3 nb x ninp x 2; chi nb x nchi (public, per proof; nullptr without);
+// trip [p][x, y, z][k][t], masked [p][d, e][k][t], opened [p][d, e][t]: the layouts above with one product per proof, len = G.
+struct MpcWitLevel {
+  WitDev w;
+  size_t nb;
+  uint32_t lo, mid, hi;
+  Words8 *aL, *aR, *aO;
+  const Words8 *v, *inputs, *chi, *trip;
+  Words8 *masked;
+};
+// a_L, a_R of the level's gates on every plane (a `One` term on the modifier plane only), and masked d = a_L - x, e = a_R - y
+void mpc_witness_mask(hipStream_t st, const MpcWitLevel &a);
+// a_O of the level's gates: z_k + d y_k + e x_k, plus d e on the modifier plane
+void mpc_witness_combine(hipStream_t st, const MpcWitLevel &a, const Words8 *opened);
 
 // ---- InnerProductProof::verify for nb proofs of one length n = 2^k (k_ippv.hip) -------------------
 // header, a lane per proof: hdr[p] = (k + 2) x 9 int32 (u_j^2, a / prod u, b / prod u: what ippv_assemble reads); the scalars of

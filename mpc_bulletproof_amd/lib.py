@@ -170,6 +170,16 @@ def witness_affine_chains(n, n1, nchi, op, row_ptr, kind, idx):
     return dict(zip(WIT_AFF_FIELDS, out))
 
 
+def witness_gate_levels(n, n1, nchi, op, row_ptr, kind, idx):
+    """the dependency level of every gate of a program inside its phase (bpgpu_witness_gate_levels): slot t of a round of the
+    two-party witness sessions is the t-th gate of that level in ascending gate index (needs no device)"""
+    out = (C.c_uint32 * max(n, 1))()
+    rc = _lib.bpgpu_witness_gate_levels(n, n1, nchi, _buf(bytes(op)), _u32s(row_ptr), _u32s(kind), _u32s(idx), out)
+    if rc:
+        raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
+    return list(out)[:n]
+
+
 class BpGpu:
     """One context on one device.  All byte encodings as in include/bpgpu.h."""
 
@@ -772,6 +782,43 @@ class BpGpu:
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
         self._ck(_lib.bpgpu_mpc_commit_values(self.ctx, gens, nb, m, opt(v), opt(v_blinding), V))
         return bytes(V)[:64 * nb * 3 * m]
+
+    # ---- two-party witness synthesis, a dependency level of a gate program per mask / combine pair (bpgpu_mpc_witness_*)
+    def mpc_witness_begin(self, w, nb, phase=0, v=None, inputs=None, gadget_challenges=None, a_L=None, a_R=None, a_O=None):
+        """a session over program w for nb proofs: v nb x 3 x m, inputs nb x 3 x n_inputs x 2, for phase 2 the planes nb x 3 x n
+        holding phase 1 -> the session, or None when nb == 0"""
+        h = C.c_void_p()
+        opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
+        self._ck(_lib.bpgpu_mpc_witness_begin(self.ctx, w, nb, phase, opt(v), opt(inputs), opt(gadget_challenges), opt(a_L), opt(a_R),
+                                              opt(a_O), C.byref(h)))
+        return h if h.value else None
+
+    def mpc_witness_levels_left(self, s):
+        return _lib.bpgpu_mpc_witness_levels_left(s)
+
+    def mpc_witness_level_len(self, s):
+        """the gates G of the level the next mpc_witness_mask evaluates; 0 when none is left"""
+        return _lib.bpgpu_mpc_witness_level_len(s)
+
+    def mpc_witness_mask(self, s, nb, triples):
+        """triples nb x 3 (x, y, z) x 3 x G -> masked nb x 2 (d, e) x 3 x G"""
+        g = self.mpc_witness_level_len(s)
+        out = _out(32 * nb * 6 * g)
+        self._ck(_lib.bpgpu_mpc_witness_mask(self.ctx, s, _buf(triples), out))
+        return bytes(out)[:32 * nb * 6 * g]
+
+    def mpc_witness_combine(self, s, opened):
+        """opened nb x 2 (d, e) x G: a_O of the level's gates; the session advances to the next level"""
+        self._ck(_lib.bpgpu_mpc_witness_combine(self.ctx, s, _buf(opened)))
+
+    def mpc_witness_finish(self, s, nb, n):
+        """-> (a_L, a_R, a_O) nb x 3 x n"""
+        planes = [_out(32 * nb * 3 * n) for _ in range(3)]
+        self._ck(_lib.bpgpu_mpc_witness_finish(self.ctx, s, *planes))
+        return tuple(bytes(p)[:32 * nb * 3 * n] for p in planes)
+
+    def mpc_witness_destroy(self, s):
+        _lib.bpgpu_mpc_witness_destroy(self.ctx, s)
 
     def mpc_prover_polys_mask(self, session, circuit, nb, n, y, z, triples, gadget_challenges=None):
         """mpc_prover.rs:783-829: triples nb x 6 x 3 x 3 x n -> masked d, e (nb x 6 x 2 x 3 x n)"""
