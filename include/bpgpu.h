@@ -80,7 +80,7 @@ int bpgpu_set_latency_mode(bpgpu_ctx *ctx, int on);
 #define BPGPU_OPT_VERIFY_STRAUS_NP 5       /* points per Straus lane on those paths, 1..4 (default 4) */
 #define BPGPU_OPT_IPP_LITERAL 6            /* 1: bpgpu_ipp_begin always runs the reference's literal schedule (generators folded every round) */
 #define BPGPU_OPT_VS_LARGE_MIN 7           /* padded n / m from which the verifier's scalar assembly is split over the grid (default 4096) */
-#define BPGPU_OPT_TABLE_NP 8               /* proof points per table lane of the window-parallel chain: 1, 2, 4, 8; 0 = by latency mode */
+#define BPGPU_OPT_TABLE_NP 8               /* proof points per table lane of the window-parallel chain: 1, 2, 4, 8; 0 = by mode (1 in latency mode; 8 for batches of 256 proofs or more -- fewest instructions, a longer launch: see bpgpu_set_horner_group --, 4 below) */
 #define BPGPU_OPT_IPP_TABLE_MAX_N 9        /* bpgpu_ipp_begin builds per-session generator tables up to this n (default 2^16), literal schedule above */
 #define BPGPU_OPT_STREAM_LANES 10          /* lanes (streams + workspaces) a bpgpu_r1cs_verify_stream call spreads its batches over, 1..64 (default 20) */
 #define BPGPU_OPT_STREAM_BATCH 11          /* proofs per batch of a bpgpu_r1cs_verify_stream call (default 1024) */
@@ -90,7 +90,7 @@ int bpgpu_set_latency_mode(bpgpu_ctx *ctx, int on);
 #define BPGPU_OPT_PIPPENGER_MIN 15         /* terms from which an MSM that is not served by the window-parallel launches takes the bucket method (default 512) */
 #define BPGPU_OPT_IPP_PIPPENGER_MIN 16     /* the same for the L / R MSMs of bpgpu_ipp_round's literal schedule (default 257) */
 #define BPGPU_OPT_FIXED_LPM 17             /* lanes per fixed-base MSM in the verification's back launch: 16, 32, 64; 0 = by mode */
-#define BPGPU_OPT_GROUPS_FORM 18           /* first Horner stage: 0 = by mode, 1 = a lane, 2 = a DPP quad, 3 = a whole wave per group of 8 windows */
+#define BPGPU_OPT_GROUPS_FORM 18           /* first Horner stage: 0 = by mode, 1 = a lane, 2 = a DPP quad, 3 = a whole wave per group of windows (bpgpu_set_horner_group) */
 #define BPGPU_OPT_FIXED_CHUNK_GENS 19      /* generator half of the verification's back launch: 0 = by mode, -1 = FIXED_LPM lanes per proof and a butterfly; g in 1..64 = a proof
                                             * per lane, g generators per wave, the partial sums added in the verdict launch */
 #define BPGPU_OPT_WITNESS_ROUTE 20         /* witness synthesis (bpgpu_r1cs_witness_synthesize, bpgpu_r1cs_prove_fs2): 0 = by bpgpu_witness_plan and BPGPU_OPT_WITNESS_SCAN_MIN, 1 = a lane per prover, 2 = a block per prover */
@@ -98,6 +98,19 @@ int bpgpu_set_latency_mode(bpgpu_ctx *ctx, int on);
 #define BPGPU_OPT_COUNT 22
 int bpgpu_set_option(bpgpu_ctx *ctx, int option, int64_t value);
 int bpgpu_get_option(bpgpu_ctx *ctx, int option, int64_t *value);
+/* Windows per group of the first Horner stage of the window-parallel chain / MSMs (the second stage then takes 64 / this many
+ * partial sums per proof): 8, 16 or 32; 0 (default) = by mode: 32 for batches of 256 proofs or more outside latency mode, 8
+ * otherwise and in the MSMs.  A launch-route setting of ONE context like the options above -- results never depend on it --
+ * with a setter of its own: BPGPU_E_ARG for any other value, which leaves the setting as it was.  The environment variable
+ * BPGPU_HORNER_GROUP seeds a new context through the same validation.  Why not a numbered option: BPGPU_OPT_COUNT is pinned at
+ * 22 by the ABI tests of the witness entry points (tests/test_witness_chains_abi.py, tests/test_witness_affine_abi.py), and the
+ * change that added this setting could not edit them.  A consequence: bpgpu_pool_set_option does not reach it; the slots of a
+ * pool get it from the environment only.
+ * By mode, a batch of 256 proofs or more outside latency mode takes the shapes with the fewest instructions (this, a lane per
+ * proof in the second stage, BPGPU_OPT_TABLE_NP = 8): right for a caller that keeps several batches in flight; ONE such batch
+ * alone on the chip is 0.41 ms longer than with the short shapes (1 024 64-bit range proofs) -- use bpgpu_set_latency_mode there. */
+int bpgpu_set_horner_group(bpgpu_ctx *ctx, int windows);
+int bpgpu_get_horner_group(bpgpu_ctx *ctx, int *windows);
 /* synchronise and report whether an operand of the `_dev` (device-resident, asynchronous) calls issued since the last read -- or
  * since the last synchronous entry point on this context, each of which uses and clears the flag for its own BPGPU_E_ARG -- was
  * malformed (1); reading clears the flag.  A diagnostic: the verification entry points reject a malformed proof on its own

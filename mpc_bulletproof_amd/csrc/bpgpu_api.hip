@@ -89,6 +89,7 @@ struct bpgpu_ctx {
   // optional per-kernel HIP-event timing (bench.py roofline): kind -> list of (start, stop)
   bool prof = false;
   bool latency_mode = false;      // bpgpu_set_latency_mode
+  int horner_group = 0;           // bpgpu_set_horner_group: windows per group of the first Horner stage, 0 = by mode
   size_t shard_rank = 0, shard_world = 1;   // bpgpu_set_shard: this context's share of ONE large proof split over the GPUs of a node
   // bpgpu_set_option: launch-route selectors of THIS context (tests walk every route through them; a multi-tenant host gives
   // each tenant its own context).  The BPGPU_* environment variables of the same names only seed the defaults, once, in bpgpu_create.
@@ -469,6 +470,7 @@ int bpgpu_hw_queues(int *inherited, int *in_force) {
 }
 
 static int ctx_create(int device, bool single_stream, bpgpu_ctx **out);
+static bool horner_group_valid(long long windows) { return windows == 0 || windows == 8 || windows == 16 || windows == 32; }
 // the one validator of option values: bpgpu_set_option and the environment seeding of a new context both go through it
 static bool opt_valid(int option, int64_t value) {
   if (option <= 0 || option >= BPGPU_OPT_COUNT) return false;
@@ -530,6 +532,11 @@ static int ctx_create(int device, bool single, bpgpu_ctx **out) {
         const long long v = strtoll(e, &end, 10);
         if (end && *end == 0 && opt_valid(s.opt, (int64_t)v)) ctx->opt[s.opt] = (int64_t)v;
       }
+    }
+    if (const char *e = getenv("BPGPU_HORNER_GROUP"); e && *e) {   // (bpgpu_set_horner_group: seeded the same way)
+      char *end = nullptr;
+      const long long v = strtoll(e, &end, 10);
+      if (end && *end == 0 && horner_group_valid(v)) ctx->horner_group = (int)v;
     }
   }
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->st, hipStreamNonBlocking) != hipSuccess ||
@@ -602,6 +609,18 @@ int bpgpu_set_option(bpgpu_ctx *ctx, int option, int64_t value) {
   if (!ctx || !opt_valid(option, value)) return BPGPU_E_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   ctx->opt[option] = value;
+  return BPGPU_OK;
+}
+int bpgpu_set_horner_group(bpgpu_ctx *ctx, int windows) {
+  if (!ctx || !horner_group_valid(windows)) return BPGPU_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  ctx->horner_group = windows;
+  return BPGPU_OK;
+}
+int bpgpu_get_horner_group(bpgpu_ctx *ctx, int *windows) {
+  if (!ctx || !windows) return BPGPU_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  *windows = ctx->horner_group;
   return BPGPU_OK;
 }
 int bpgpu_get_option(bpgpu_ctx *ctx, int option, int64_t *value) {
@@ -792,6 +811,7 @@ static void wp_options(const bpgpu_ctx *ctx, VerifyWp &v) {   // the per-context
   v.fixed_lpm = (int)ctx->opt[BPGPU_OPT_FIXED_LPM];
   v.groups_form = (int)ctx->opt[BPGPU_OPT_GROUPS_FORM];
   v.fixed_chunk_gens = (int)ctx->opt[BPGPU_OPT_FIXED_CHUNK_GENS];
+  v.horner_group = ctx->horner_group;
 }
 static int msm_wp_batch(bpgpu_ctx *ctx, size_t nb, size_t n, const void *dsc, const void *points, bool converted, JacRaw *dsum, bool *done,
                         int *bad = nullptr, size_t max_n = 0) {
@@ -1992,6 +2012,7 @@ static int stream_lanes(bpgpu_ctx *ctx, size_t want) {
   for (bpgpu_ctx *l : ctx->lanes) {   // the lanes follow their parent's settings
     for (int i = 0; i < BPGPU_OPT_COUNT; i++) l->opt[i] = ctx->opt[i];
     l->latency_mode = false;          // (a stream call is the pipelined case by definition)
+    l->horner_group = ctx->horner_group;
     l->prof = ctx->prof; l->prof_mask = ctx->prof_mask;
   }
   return BPGPU_OK;

@@ -459,31 +459,56 @@ __global__ void __launch_bounds__(64) k_verify_windows(const AffRaw *tab, const 
   }
   raw_store(&winsum[p * 64 + w], xyzz_to_jac(acc));
 }
-// Horner over the 64 window sums in two stages.  Stage 1, one lane per (proof, group of 8 windows):
-// T_g = sum_{i<8} 16^i S_{8g+i} (28 doublings, 7 additions), written over S_{8g}.  Stage 2, one lane per proof:
+// Horner over the 64 window sums in two stages.  Stage 1, one chain per (proof, group of HG windows), at HG = 8:
+// T_g = sum_{i<8} 16^i S_{8g+i} (28 doublings, 7 additions), written over S_{8g}.  Stage 2, one chain per proof:
 // sum_g 2^(32 g) T_g (224 doublings, 7 additions).  The dependency chain of a batch loses 49 of its 63 general
 // additions for 8 x 28 extra doublings per proof (+3 % instructions).
-constexpr int HG = 8;   // windows per group
+//
+// The group size HG is a launch parameter (wp_hg below: 8, 16 or 32 windows; bpgpu_set_horner_group).  The chain is 252 doublings
+// and 63 additions deep at every HG; HG only moves doublings between the stages, SW (HG - 1) per group in stage 1 against
+// SW HG (64 / HG - 1) per proof in stage 2, and the additions with them (HG - 1 per group, 64 / HG - 1 per proof).  Stage 1
+// has 64 / HG times the chains of stage 2, so a larger HG is more instructions in stage 1 and fewer in stage 2 -- which pays
+// where stage 2 runs in a dearer form than stage 1 (a quad doubling costs 2.16x a lane doubling per chain).
+constexpr int HG_SHORT = 8, HG_CHOICES[] = {8, 16, 32};   // HG_SHORT: the by-mode size of everything but a pipelined caller's batches (shortest stage 1)
+constexpr bool hg_choices_divide(int windows) {
+  for (int hg : HG_CHOICES) if (hg < 2 || windows % hg != 0 || windows / hg < 2) return false;
+  return true;
+}
+static_assert(hg_choices_divide(num_windows<SW>()), "a proof's 64 window sums are whole groups of HG, at least two of them");
+// The lean shapes (wp_lean below): group size, stage-2 form and points per table lane of a pipelined caller's batches.
+// Measured on 24 hardware queues, 1 024-proof batches on 20 contexts, one machine, three alternating runs per shape
+// (profiles/chain_shapes.log; M verifications/s over 2 048 steps | in bursts of 20 steps), 4 points per table lane:
+//     HG  8: quad 5.077 | 4.229 (the shapes until then)   lane 5.200 | 4.028
+//     HG 16: quad 5.128 | 4.319                           lane 5.224 | 4.128
+//     HG 32: quad 5.180 | 4.317                           lane 5.253 | 4.463
+// A larger group wins in either form and the lanes win at every group size; groups of 8 with stage 2 on lanes lose the bursts
+// (224 lane doublings in one 16-wave link), groups of 32 do not: stage 1 then carries 124 of the 252 doublings on 32 waves.
+// Five alternating runs against the parent commit: 5.072 -> 5.266 sustained at 8 points per lane (5.227 at 4), ranges apart.
+constexpr int WP_LEAN_HG = 32;
+constexpr ChainForm WP_LEAN_STAGE2 = ChainForm::Lane;
+constexpr int WP_LEAN_TNP = 8;
 // The chain itself, its three forms and their invariants: ec_chain.cuh.  Both stages are horner_chain with
 // (count, stride, dbl) = (HG, 1, SW) in place over the nb * 64 / HG groups, then (64 / HG, HG, SW * HG) per proof into varsum.
-__global__ void __launch_bounds__(64) k_verify_horner_groups(JacRaw *winsum, size_t nb) {
+// In place at any HG: chain u reads the HG slots from u HG on and stores to slot u HG, its own last term and no other chain's.
+__global__ void __launch_bounds__(64) k_verify_horner_groups(JacRaw *winsum, size_t nb, int hg) {
   __builtin_amdgcn_s_setprio(2);
-  horner_chain<LaneForm>(blockIdx.x, nb * (64 / HG), winsum, HG, HG, 1, SW, winsum, HG);
+  horner_chain<LaneForm>(blockIdx.x, nb * (64 / hg), winsum, hg, hg, 1, SW, winsum, hg);
 }
-// stage 1 with a DPP quad per (proof, group): the 28 doublings and 7 additions at the quad's depth (latency mode: 4x the lanes
-// and ~2.3x the instructions of this small stage for ~40 % of its time)
-__global__ void __launch_bounds__(64) k_verify_horner_groups4(JacRaw *winsum, size_t nb) {
+// stage 1 with a DPP quad per (proof, group): the 28 doublings and 7 additions of a group of 8 at the quad's depth (latency mode:
+// 4x the lanes and ~2.3x the instructions of this small stage for ~40 % of its time)
+__global__ void __launch_bounds__(64) k_verify_horner_groups4(JacRaw *winsum, size_t nb, int hg) {
   __builtin_amdgcn_s_setprio(2);
-  horner_chain<QuadForm>(blockIdx.x, nb * (64 / HG), winsum, HG, HG, 1, SW, winsum, HG);
+  horner_chain<QuadForm>(blockIdx.x, nb * (64 / hg), winsum, hg, hg, 1, SW, winsum, hg);
 }
-// stage 1 with a whole WAVE per (proof, group) (ec29_row.cuh): 28 doublings + 7 additions in ~23 us instead of ~65 us on a quad --
-// for the few groups of a small MSM or a handful of proofs, where this stage is a link of a lone chain
-__global__ void __launch_bounds__(64) k_verify_horner_groups_row(JacRaw *winsum) {
+// stage 1 with a whole WAVE per (proof, group) (ec29_row.cuh): the 28 doublings + 7 additions of a group of 8 in ~23 us instead of
+// ~65 us on a quad -- for the few groups of a small MSM or a handful of proofs, where this stage is a link of a lone chain
+__global__ void __launch_bounds__(64) k_verify_horner_groups_row(JacRaw *winsum, int hg) {
   __builtin_amdgcn_s_setprio(2);
-  horner_chain<RowForm>(blockIdx.x, gridDim.x, winsum, HG, HG, 1, SW, winsum, HG);
+  horner_chain<RowForm>(blockIdx.x, gridDim.x, winsum, hg, hg, 1, SW, winsum, hg);
 }
 // stage 2, a chain per proof over `count` partial sums `stride` slots apart, `dbl` doublings between them.  The forms:
-//   lane: 16 waves carrying the longest link of a batch's chain;
+//   lane: 16 waves; at groups of 8 their 224 doublings are the longest link of a batch's chain, at groups of 32 (128 doublings)
+//     the link is as long as stage 1's, and both are the cheapest per chain -- the form of a pipelined caller's batches;
 //   quad (ec29_quad.cuh): a doubling is 3 field multiplications deep instead of 9, a general addition 5 instead of 16 -- that
 //     link shortened ~1.7x for 4x the lanes;
 //   row (ec29_row.cuh: one field multiplication spread over the 16 lanes of a DPP row, the four rows = the four products of
@@ -544,14 +569,25 @@ __global__ void __launch_bounds__(64) k_verify_verdict_q(const JacRaw *varsum, c
   acc = jac_add(raw_load(&varsum[p]), acc);
   verdict_store(acc, wp_malformed(bad_lane, lanes, bad_sc, p), ok, mega, p);
 }
-// points per table lane.  8 = fewest instructions (affine builder: three inversions per 8 points; the front launch 6.68e6 VALU
-// wave-instructions per 1 024-proof step against 9.78e6 at 4), but 48 table waves whose chain is 293 us alone against 96 waves
-// of 215 us: with twenty batches in flight the longer link costs more than the instructions save.  Same machine, same job,
-// five alternating runs each (profiles/affine_tables.log): 2 048 steps 2.957 M/s at 4 against 2.808 at 8 (the Jacobian builder
-// at 4: 2.863), bursts of 20 steps 2.775 against 2.635 (2.701).  So 4 stays the default; 1 (latency mode) = 7 additions + one
-// inversion per lane, the shortest chain for a lone batch.  VerifyWp::table_np (BPGPU_OPT_TABLE_NP) overrides.
+// The batches of a pipelined caller: not latency mode, and enough proofs to fill their waves (the gate of wp_chunk_gens).  With
+// some 17 steps' launches resident at once (24 hardware queues) a longer link of such a batch's chain delays nothing, and its
+// instructions are what a step costs.  These batches take the lean shapes (WP_LEAN_HG, WP_LEAN_STAGE2, WP_LEAN_TNP above),
+// every other batch the short ones.
+// Measured: 1 024 proofs of the 64-bit range gadget (24 proof points) on 20 contexts, nothing else.  That other circuits and
+// batch sizes from 256 on gain as well is extrapolated from the instruction counts, not measured.
+// The price: one default-mode batch of 1 024 ALONE on the chip is 0.41 ms longer (groups 0.102 -> 0.438 ms, front 0.217 ->
+// 0.295 ms).  A caller that does not pipeline belongs in latency mode, or forces the short shapes by the options.
+static bool wp_lean(const VerifyWp &v) { return !v.latency_mode && v.nb >= 256; }
+// Points per table lane.  8 = fewest instructions (affine builder: three inversions per 8 points; the front launch 6.68e6 VALU
+// wave-instructions per 1 024-proof step against 9.78e6 at 4), in 48 table waves whose chain is 293 us alone against 96 waves
+// of 215 us.  On four hardware queues the longer link cost more than the instructions saved (profiles/affine_tables.log: 2.808
+// against 2.957 M/s).  On 24 queues it does not (profiles/chain_shapes.log, five alternating runs each, with the lean Horner
+// shapes): over 2 048 steps 5.266 M/s at 8 against 5.227 at 4, ranges apart.  In bursts of 20 steps 8 is the slower one: 4.170
+// against 4.357 at 4.  The parent commit's bursts: median 4.166, lowest run 4.033 -- so 8 costs a burst nothing against the
+// parent and gives up what 4 would gain.  A pipelined caller's batches (wp_lean) take 8, every other batch 4; 1 (latency mode)
+// = 7 additions + one inversion per lane, the shortest chain for a lone batch.  VerifyWp::table_np (BPGPU_OPT_TABLE_NP) overrides.
 static int wp_tnp(const VerifyWp &v) {
-  const int t = v.table_np ? v.table_np : (v.latency_mode ? 1 : 4);
+  const int t = v.table_np ? v.table_np : (v.latency_mode ? 1 : (wp_lean(v) ? WP_LEAN_TNP : 4));
   return t == 8 ? 8 : (t == 2 ? 2 : (t == 1 ? 1 : 4));
 }
 struct WpLayout { TablesArgs t; JacRaw *winsum, *varsum; unsigned blocks; size_t bytes; };
@@ -613,7 +649,10 @@ void verify_wp_windows(hipStream_t st, const VerifyWp &v, const uint32_t *var_sc
 }
 // The form of the two Horner stages.  An option (BPGPU_OPT_GROUPS_FORM, BPGPU_OPT_HORNER_FORM: 1 = lane, 2 = quad, 3 = a wave
 // per chain) decides; 0 = by mode: a wave per chain when the chain has the chip to itself -- latency mode and at most
-// v.row_max chains -- and else, stage 1: a quad in latency mode, a lane otherwise; stage 2: a quad.
+// v.row_max chains -- and else, stage 1: a quad in latency mode, a lane otherwise; stage 2: a lane for a pipelined caller's
+// batches (wp_lean: a lane doubling is 1 250 instructions for 64 chains, a quad doubling 675 for 16, and with the launches of
+// 17 steps on the chip the instructions count, not the link's length; the figures are at WP_LEAN_HG above), a quad for every
+// other batch, whose chain is alone on the chip for 1.35 us per doubling instead of 2.5.
 static ChainForm wp_groups_form(const VerifyWp &v, size_t units) {
   if (v.groups_form) return chain_form_option(v.groups_form, ChainForm::Lane);
   if (!v.latency_mode) return ChainForm::Lane;
@@ -621,17 +660,24 @@ static ChainForm wp_groups_form(const VerifyWp &v, size_t units) {
 }
 static ChainForm wp_horner_form(const VerifyWp &v) {
   if (v.horner_form) return chain_form_option(v.horner_form, ChainForm::Quad);
+  if (wp_lean(v)) return WP_LEAN_STAGE2;
   return v.latency_mode && v.nb <= v.row_max ? ChainForm::Row : ChainForm::Quad;
+}
+// windows per group of stage 1 (VerifyWp::horner_group, bpgpu_set_horner_group: 8, 16, 32); 0 = by mode
+static int wp_hg(const VerifyWp &v) {
+  for (int hg : HG_CHOICES) if (v.horner_group == hg) return hg;
+  return wp_lean(v) ? WP_LEAN_HG : HG_SHORT;
 }
 void verify_wp_groups(hipStream_t st, const VerifyWp &v) {
   static_assert(num_windows<SW>() == 64, "64 window sums per proof");
   WpLayout L = wp_layout(v);
-  const size_t units = v.nb * (64 / HG);
+  const int hg = wp_hg(v);
+  const size_t units = v.nb * (64 / hg);
   const ChainForm form = wp_groups_form(v, units);
   const dim3 grid(chain_blocks(form, units));
-  if (form == ChainForm::Row) hipLaunchKernelGGL(k_verify_horner_groups_row, grid, dim3(64), 0, st, L.winsum);
-  else if (form == ChainForm::Quad) hipLaunchKernelGGL(k_verify_horner_groups4, grid, dim3(64), 0, st, L.winsum, v.nb);
-  else hipLaunchKernelGGL(k_verify_horner_groups, grid, dim3(64), 0, st, L.winsum, v.nb);
+  if (form == ChainForm::Row) hipLaunchKernelGGL(k_verify_horner_groups_row, grid, dim3(64), 0, st, L.winsum, hg);
+  else if (form == ChainForm::Quad) hipLaunchKernelGGL(k_verify_horner_groups4, grid, dim3(64), 0, st, L.winsum, v.nb, hg);
+  else hipLaunchKernelGGL(k_verify_horner_groups, grid, dim3(64), 0, st, L.winsum, v.nb, hg);
 }
 static size_t wp_chunk_gens(const VerifyWp &v);
 #ifndef WP_BACK_AHEAD
@@ -658,7 +704,8 @@ static void launch_back(hipStream_t st, const HornerArgs &h, unsigned hb, const 
 void verify_wp_back(hipStream_t st, const VerifyWp &v, int c, const AffDev *table, size_t n, size_t cap,
                     const uint32_t *fixed_scalars, size_t sc_stride, JacRaw *out_fixed) {
   WpLayout L = wp_layout(v);
-  HornerArgs h{L.winsum, L.varsum, v.nb, 64 / HG, HG, SW * HG, wp_horner_form(v)};   // over what verify_wp_groups left
+  const int hg = wp_hg(v);
+  HornerArgs h{L.winsum, L.varsum, v.nb, 64 / hg, hg, SW * hg, wp_horner_form(v)};   // over what verify_wp_groups left
   const unsigned hb = chain_blocks(h.form, v.nb);
   FixedSmallArgs f{table, n, cap, fixed_scalars, sc_stride, out_fixed, v.nb};
   if (table && verify_wp_fixed_parts(v, n) > 1) { f.chunks = (unsigned)verify_wp_fixed_parts(v, n); f.gens_per_chunk = (unsigned)wp_chunk_gens(v); }

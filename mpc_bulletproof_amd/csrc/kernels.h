@@ -60,13 +60,14 @@ bool verify_msm_fused(hipStream_t st, int np, const StrausArgs &a, JacRaw *out_v
 // latency_mode: more, shorter lanes in the two longest launches (1 point per table lane, 32 lanes per fixed-base MSM, a quad per group in the first Horner stage): one batch
 // alone finishes ~25 % sooner, a pipelined stream of batches runs ~5 % slower (more instructions)
 // points_converted: points_abi holds AffDev rows (already validated and in Montgomery form: points_from_boundary) instead of ABI bytes
-// table_np: points per table lane (1, 2, 4, 8; 0 = by mode: 4, or 1 in latency mode) -- BPGPU_OPT_TABLE_NP
+// table_np: points per table lane (1, 2, 4, 8; 0 = by mode: 1 in latency mode, else 8 from 256 proofs on and 4 below) -- BPGPU_OPT_TABLE_NP
 struct VerifyWp { const AffDev *points_abi; size_t nb, nvar; void *scratch /* verify_wp_scratch_bytes */; int *bad; const int32_t *bad_sc; bool latency_mode; bool points_converted = false; int table_np = 0;
-                  int horner_form = 0;   // Horner pass: 0 = by mode, 1 = a lane, 2 = a DPP quad, 3 = a wave (row form, ec29_row.cuh) per proof -- BPGPU_OPT_HORNER_FORM
+                  int horner_form = 0;   // Horner pass: 0 = by mode (k_ec.hip: wp_horner_form), 1 = a lane, 2 = a DPP quad, 3 = a wave (row form, ec29_row.cuh) per proof -- BPGPU_OPT_HORNER_FORM
                   size_t row_max = 1536; // most proofs / groups for which latency mode takes the row form -- BPGPU_OPT_HORNER_ROW_MAX
                   int fixed_lpm = 0;     // lanes per fixed-base MSM in the back launch: 16 / 32 / 64, 0 = by mode -- BPGPU_OPT_FIXED_LPM
-                  int groups_form = 0;   // first Horner stage: 0 = by mode, 1 = a lane, 2 = a quad, 3 = a wave per group of 8 windows -- BPGPU_OPT_GROUPS_FORM
+                  int groups_form = 0;   // first Horner stage: 0 = by mode, 1 = a lane, 2 = a quad, 3 = a wave per group of windows -- BPGPU_OPT_GROUPS_FORM
                   int fixed_chunk_gens = 0;   // generator half of the back launch: 0 = by mode, -1 = fixed_lpm lanes per proof + butterfly; g > 0 = a proof per lane, g generators per wave, partial sums added in the verdict launch -- BPGPU_OPT_FIXED_CHUNK_GENS
+                  int horner_group = 0;  // windows per group of the first Horner stage: 8 / 16 / 32, 0 = by mode -- bpgpu_set_horner_group
 };
 struct VerifyDims { size_t nb, n1, n, padded_n, k, m; const Words8 *chi; /* nb x nchi gadget challenges (plain words) or nullptr */
                     size_t vs_large_min = 0; /* padded_n / m from which the scalar assembly is split over the grid (0 = 4096) -- BPGPU_OPT_VS_LARGE_MIN */ };

@@ -218,12 +218,28 @@ class BpGpu:
 
     # ---- plumbing
     def set_option(self, name, value):
-        """launch-route option of this context (OPT keys; include/bpgpu.h BPGPU_OPT_*)"""
+        """launch-route option of this context (OPT keys; include/bpgpu.h BPGPU_OPT_*), or "horner_group" (bpgpu_set_horner_group)"""
+        if name == "horner_group":
+            return self.set_horner_group(value)
         self._ck(_lib.bpgpu_set_option(self.ctx, OPT[name], int(value)))
 
     def get_option(self, name):
+        if name == "horner_group":
+            return self.get_horner_group()
         v = C.c_int64()
         self._ck(_lib.bpgpu_get_option(self.ctx, OPT[name], C.byref(v)))
+        return v.value
+
+    def set_horner_group(self, windows):
+        """windows per group of the first Horner stage: 8, 16, 32; 0 = by mode (include/bpgpu.h)"""
+        windows = int(windows)
+        if not -(1 << 31) <= windows < (1 << 31):
+            raise BpGpuError(E_ARG, "set_horner_group: not a C int")
+        self._ck(_lib.bpgpu_set_horner_group(self.ctx, windows))
+
+    def get_horner_group(self):
+        v = C.c_int()
+        self._ck(_lib.bpgpu_get_horner_group(self.ctx, C.byref(v)))
         return v.value
 
     def options(self, **kw):
