@@ -21,9 +21,13 @@ static __device__ __noinline__ Fp fpmul(const Fp &a, const Fp &b) { return mul(a
 static __device__ __noinline__ Fp fpsqr(const Fp &a) { return sqr(a); }
 static __device__ __noinline__ Fp fpmul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) { return mul2(a, b, c, d); }
 #else
-BP_HD Fp fpmul(const Fp &a, const Fp &b) { return mul(a, b); }
-BP_HD Fp fpsqr(const Fp &a) { return sqr(a); }
-BP_HD Fp fpmul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) { return mul2(a, b, c, d); }   // (a b + c d) / R, one reduction
+// (a host build of the tests defines BP_FP_OPERANDS to see the operands of every product of the group law: k = 1, 2 or 4 of them)
+#ifndef BP_FP_OPERANDS
+#define BP_FP_OPERANDS(k, a, b, c, d)
+#endif
+BP_HD Fp fpmul(const Fp &a, const Fp &b) { BP_FP_OPERANDS(2, a, b, a, b); return mul(a, b); }
+BP_HD Fp fpsqr(const Fp &a) { BP_FP_OPERANDS(1, a, a, a, a); return sqr(a); }
+BP_HD Fp fpmul2(const Fp &a, const Fp &b, const Fp &c, const Fp &d) { BP_FP_OPERANDS(4, a, b, c, d); return mul2(a, b, c, d); }   // (a b + c d) / R, one reduction
 #endif
 
 struct Jac { Fp X, Y, Z; };
@@ -164,17 +168,25 @@ BP_HD Jac jac_madd_nzq(const Jac &p, const Aff &q) {
 // A mixed addition into such an accumulator is 8M + 2S (madd-2008-s) against 8M + 3S for the Jacobian one: Z^2 and Z^3 are
 // carried instead of recomputed.  Used where a lane only ADDS table entries to its accumulator (fixed-base walks, window sums,
 // bucket accumulation); the lane converts to Jacobian once (3M + 1S) before its result meets doublings or reductions.
-// Identity <=> all limbs of ZZ are literally zero (ZZZ then is, too).
+// Identity <=> all limbs of ZZ are literally zero (ZZZ then is, too).  Every reader decides on ZZ (or, after xyzz_to_jac, on Z) alone.
+//
+// The identity that xyzz_inf() makes has an all-zero X as well, and that is what keeps identity accumulators out of the hot path of
+// xyzz_madd_nzq: P = q.x * ZZ - X is then 0 - 0 with literally zero limbs (a product with an all-zero operand has all-zero limbs:
+// every column of mul_cols is zero, so is every m_k; sub_nr keeps them zero), fp_maybe_zero(P) fires, and the identity is resolved in
+// the guarded branch that P = 0 (mod p) needs anyway -- the straight path carries no test and no select for it.  X is not part of the
+// DEFINITION: xyzz_madd_full and the selects accept any X beside ZZ = 0 (only xyzz_madd_nzq's filter relies on the zero, and
+// the producers of an identity Xyzz are xyzz_inf(), xyzz_madd_full, which returns it, and xyzz_from_jac, which zeroes X).  Y stays one.
 struct Xyzz { Fp X, Y, ZZ, ZZZ; };
 BP_HD Xyzz xyzz_inf() {
   Xyzz r;
-  r.X = fe_one<FP>(); r.Y = fe_one<FP>(); r.ZZ = fe_zero<FP>(); r.ZZZ = fe_zero<FP>();
+  r.X = fe_zero<FP>(); r.Y = fe_one<FP>(); r.ZZ = fe_zero<FP>(); r.ZZZ = fe_zero<FP>();
   return r;
 }
 BP_HD bool xyzz_is_inf(const Xyzz &p) { return is_zero_limbs(p.ZZ); }
 BP_HD Xyzz xyzz_from_jac(const Jac &p) {
   Xyzz r;
   r.X = p.X; r.Y = p.Y; r.ZZ = fpsqr(p.Z); r.ZZZ = fpmul(r.ZZ, p.Z);
+  if (jac_is_inf(p)) r.X = fe_zero<FP>();   // jac_inf() has X = 1: the identity here keeps its zero X (above)
   return r;
 }
 // (X ZZ^2 : Y ZZ^3 : ZZZ) is the same point in Jacobian coordinates (Z = ZZZ: Z^2 = ZZ^3, Z^3 = ZZZ^3 = ZZ^3 ZZZ)
@@ -227,16 +239,50 @@ BP_HD Xyzz xyzz_select(bool c, const Xyzz &a, const Xyzz &b) {
   }
   return r;
 }
-// q must not be the identity (callers skip identity table entries); an identity accumulator is resolved by a select
+// -y limb by limb where the digit d is negative, y where it is not: (v ^ s) + (s & 1) with s = d >> 31 -- one xor-add per limb, no
+// carry pass.  The result is an OPERAND (fe29.cuh: a T / T' value negated limb by limb), not a coordinate to store: xyzz_madd_nzq
+// below takes it as q.y.
+BP_HD Fp fp_sign_nr(const Fp &y, int d) {
+  const uint32_t s = (uint32_t)(d >> 31), one = (uint32_t)d >> 31;
+  Fp r;
+#pragma unroll
+  for (int j = 0; j < NL; j++) r.v[j] = (int32_t)(((uint32_t)y.v[j] ^ s) + one);
+  return r;
+}
+// q must not be the identity (callers skip identity table entries).  q.x is T / T'; q.y is T / T' or such a value negated limb by limb
+// (fp_sign_nr): on the straight path it feeds ONE product, q.y * ZZZ, and nothing else.  An identity accumulator reaches the guarded
+// branch through the filter (see xyzz_inf) and takes q there, inline; only P = 0 (mod p) proper pays the out-of-line call.  Whatever
+// leaves the branch has q.y behind a carry pass, norm(-y limb by limb) = neg(y): coordinates stay T'.
+// The guarded branch comes FIRST and leaves its result in the accumulator; the lanes it did not take then run the tail over the same
+// variable.  Written the other way round (the tail, then the branch) the accumulator has to outlive the tail for the branch's sake,
+// the tail's result lands in 36 registers of its own and every addition ends with 36 copies into the loop-carried ones.  `rare` passes
+// through an empty asm between the two so that the compiler keeps them two tests in this order instead of one if / else.
 BP_HD Xyzz xyzz_madd_nzq(const Xyzz &p, const Aff &q) {
   XMid m = xyzz_madd_mid(p, q);
-  if (fp_maybe_zero(m.P)) { Xyzz pc = xyzz_hide(p), r; Aff qc = aff_hide(q); xyzz_madd_full(&r, &pc, &qc); return xyzz_hide(r); }
+  int rare = fp_maybe_zero(m.P) ? 1 : 0;
+  Xyzz a = p;
+  if (rare) {
+    Aff qn; qn.x = q.x; qn.y = norm(q.y);
+    if (xyzz_is_inf(p)) { a.X = qn.x; a.Y = qn.y; a.ZZ = fe_one<FP>(); a.ZZZ = fe_one<FP>(); }
+    else { Xyzz pc = xyzz_hide(p), r; Aff qc = aff_hide(qn); xyzz_madd_full(&r, &pc, &qc); a = xyzz_hide(r); }
+  }
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(rare));
+#endif
+  if (!rare) a = xyzz_madd_tail<true>(a, m);
+  return a;
+}
+// any q, T / T' in both coordinates.  The kernels that take this form (k_fixed.hip) keep rows two pairs ahead in registers and have none
+// to spare for the shape above (it costs them 24 more, and a wave per SIMD): here the tail runs for every lane and identity operands
+// are resolved by selects after it.  An identity accumulator always trips the filter (see xyzz_inf) and is kept off the out-of-line
+// call by its own test; the tail over its zeros is harmless.
+BP_HD Xyzz xyzz_madd(const Xyzz &p, const Aff &q) {
+  XMid m = xyzz_madd_mid(p, q);
+  const bool pinf = xyzz_is_inf(p);
+  if (fp_maybe_zero(m.P) && !pinf) { Xyzz pc = xyzz_hide(p), r; Aff qc = aff_hide(q); xyzz_madd_full(&r, &pc, &qc); return xyzz_hide(r); }
   Xyzz r = xyzz_madd_tail<true>(p, m);
   Xyzz qe; qe.X = q.x; qe.Y = q.y; qe.ZZ = fe_one<FP>(); qe.ZZZ = fe_one<FP>();
-  return xyzz_select(xyzz_is_inf(p), qe, r);
-}
-BP_HD Xyzz xyzz_madd(const Xyzz &p, const Aff &q) {
-  Xyzz r = xyzz_madd_nzq(p, q);
+  r = xyzz_select(pinf, qe, r);
   return xyzz_select(aff_is_inf(q), p, r);
 }
 

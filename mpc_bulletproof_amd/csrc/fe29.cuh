@@ -15,6 +15,9 @@
 // Representation invariants ("T" = tight): lower limbs in [0, 2^29), top limb small signed.
 // "T'" (after norm()): lower limbs in [-8, 2^29 + 8).  mul/sqr accept T' x T' and limbs up to
 // 1.5 * 2^29 against T'; they return T.  Values: every mul input must satisfy |v| < 2^256.
+// A T / T' operand may also come negated limb by limb, without a carry pass (neg_nr; ec29.cuh: fp_sign_nr): the bounds above are on
+// MAGNITUDES and the MADs are signed, so mul takes it like the value it negates and returns T again.  Such a value is an operand
+// only: a coordinate that is stored goes through norm() first (norm of -x limb by limb is neg(x)).
 // mul2(a, b, c, d) = (a*b + c*d) / R (F_p, one reduction for both products) is narrower: ALL FOUR operands must have
 // lower limbs of magnitude <= 2^29 + 8 -- T, T' and the un-normalised differences sub_nr(product, tight) and
 // sub_nr(T, T') of either sign, or any of these negated limb by limb; the 1.5 * 2^29 allowance of mul does NOT carry

@@ -61,7 +61,7 @@ __device__ __forceinline__ void fixed_small_body(const AffDev *table, size_t n, 
         Aff q;
         q.x = unpack<FP>(cur);
         q.y = unpack<FP>(cur + 8);
-        if (dcur < 0) q.y = neg(q.y);
+        q.y = fp_sign_nr(q.y, dcur);   // an operand of one product (ec29.cuh: xyzz_madd_nzq), no carry pass
         acc = xyzz_madd_nzq(acc, q);
       }
     }
@@ -153,7 +153,7 @@ __device__ __forceinline__ void fixed_chunk_body(const AffDev *table, size_t n, 
         Aff a;
         a.x = unpack<FP>(row[0]);
         a.y = unpack<FP>(row[0] + 8);
-        if (dg[0] < 0) a.y = neg(a.y);
+        a.y = fp_sign_nr(a.y, dg[0]);   // an operand of one product (ec29.cuh: xyzz_madd_nzq), no carry pass
         acc = xyzz_madd_nzq(acc, a);
       }
     }

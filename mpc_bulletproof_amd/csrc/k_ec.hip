@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(64) k_verify_windows(const AffRaw *tab, const 
         Aff q;
 #pragma unroll
         for (int t = 0; t < NL; t++) { q.x.v[t] = cur[t]; q.y.v[t] = cur[NL + t]; }
-        if (dcur < 0) q.y = neg(q.y);
+        q.y = fp_sign_nr(q.y, dcur);   // an operand of one product (ec29.cuh: xyzz_madd_nzq), no carry pass
         acc = xyzz_madd_nzq(acc, q);
       }
       if (!more) break;
