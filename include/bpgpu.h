@@ -587,6 +587,18 @@ int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c,
  *   BPGPU_GATE_BIT    the range gadget's assignment (tests/r1cs.rs:629-632): b = bit arg[i] of the canonical integer eval(left);
  *                     a_L = 1 - b, a_R = b, a_O = a_L a_R.  The right row must be empty.  arg[i] < 252: the reference's u64
  *                     assignment, generalised to the whole field.
+ *   BPGPU_GATE_INV    inverse-or-zero, the allocate_multiplier(Some((x, x^-1))) of an is-zero / equality / not-equal gadget or of a
+ *                     division: a_L[i] = eval(left); a_R[i] = a_L[i]^-1, or 0 when a_L[i] = 0; a_O[i] = a_L[i] a_R[i], so a_O is 1 for
+ *                     a non-zero a_L and 0 for zero.  The zero test is on the canonical integer of eval(left).  The right row must be
+ *                     empty; arg[i] is ignored; the left row may hold whatever a MUL row may.  In the block and scan forms the INV
+ *                     gates of a level share ONE inversion per thread (Montgomery's trick, csrc/witness_dev.cuh); a lane, and a
+ *                     wave that sums a row of more than 64 terms, invert once per gate.  An INV gate has the level of a MUL gate
+ *                     with its left row, is never a chain MEMBER of either kind, may be a chain's head, and a MUL may link to its
+ *                     a_O.  A phase without an INV gate launches the kernels it always did.  Measured (profiles/witness_inv.log,
+ *                     median ms; block form | lane form | the same program with INPUT gates handed the pairs, the host's work
+ *                     left out): 256 provers x one level of 1024 INV gates 0.123 | 45.964 | 0.074; 1 x 1024: 0.093 | 50.777 |
+ *                     0.045; 4096 x 16: 0.634 | 0.743 | 0.055; 256 x a chain of 64, one gate a level, nothing to batch: 3.102 |
+ *                     2.921 | 0.031.  Every other shape is UNMEASURED; the route rule is the one below, unchanged.
  * bpgpu_witness_create validates on the host, before anything is uploaded; after it no kernel index can be out of range.
  * BPGPU_E_ARG: a null pointer, an unknown op or kind, a multiplier term with idx >= i (a self or forward reference), a chi part in a
  * gate < n1 (the challenge does not exist in phase 1), a committed index >= m, a BIT with arg >= 252, a non-empty row where the op
@@ -638,6 +650,7 @@ typedef struct bpgpu_witness bpgpu_witness;
 #define BPGPU_GATE_MUL 0
 #define BPGPU_GATE_INPUT 1
 #define BPGPU_GATE_BIT 2
+#define BPGPU_GATE_INV 4 /* not 3: callers and tests probe 3 as "an unknown op", so 3 stays refused (BPGPU_E_ARG), like every op above 4 */
 int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
                          const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff, bpgpu_witness **out);
 void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w);
@@ -842,6 +855,8 @@ int bpgpu_mpc_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size
  * Refusals, all before anything is launched.  BPGPU_E_ARG: a null required pointer; a phase other than 0, 1 or 2; challenges given or
  * missing against the rules of bpgpu_r1cs_witness_synthesize; planes missing for phase 2; a BPGPU_GATE_BIT gate in the evaluated
  * phase (a bit of a shared value is not a local function: the range gadget on shares takes its bits as INPUT pairs (1 - b, b)); a
+ * BPGPU_GATE_INV gate in the evaluated phase (neither is the inverse of a shared value: on shares the is-zero gadget takes
+ * (x, x^-1) as an INPUT pair; a phase without one is evaluated as before, whatever the other phase holds); a
  * context after bpgpu_set_shard(world > 1); _mask twice in a row; _combine without a _mask; _mask with no level left; _finish with a
  * level left.  BPGPU_E_LEN: 3 nb n or 3 nb m above 2^30.  nb == 0: BPGPU_OK with *out left NULL.  A non-canonical ark limb in any
  * input, `opened` and `triples` included, gives BPGPU_E_ARG, as the other two-party calls do; the session stays where it was (the

@@ -14,7 +14,8 @@
 using namespace bpk;
 using namespace bp;
 
-static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT && BPGPU_GATE_BIT == WIT_OP_BIT, "gate ops of the header");
+static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT && BPGPU_GATE_BIT == WIT_OP_BIT &&
+              BPGPU_GATE_INV == WIT_OP_INV, "gate ops of the header");
 
 namespace {
 
@@ -48,7 +49,7 @@ constexpr uint32_t WIT_NONE = 0xFFFFFFFFu;
 struct WitShape {
   std::vector<uint32_t> level;    // per gate, within its phase
   std::vector<uint32_t> row_len;  // per row 2 i, 2 i + 1: the terms of all 1 + nchi blocks
-  uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0;
+  uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0, ninv[2] = {0, 0};
   size_t nnz = 0;
   // product chains: a member's predecessor (WIT_NONE: an ordinary gate), the side of its link row, a gate's member successor, and
   // the compressed levels, in which a member takes its predecessor's
@@ -118,8 +119,9 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
   s->link_right.assign(n, 0);
   std::vector<uint32_t> width, length(n, 0);   // length: of a head, the members of its chain; of a member, its head
   for (size_t i = 0; i < n; i++) {
-    if (op[i] > BPGPU_GATE_BIT) return BPGPU_E_ARG;
+    if (op[i] > BPGPU_GATE_INV || op[i] == 3) return BPGPU_E_ARG;      // (3 is no op: bpgpu.h)
     if (op[i] == BPGPU_GATE_INPUT) s->ninp++;
+    if (op[i] == BPGPU_GATE_INV) s->ninv[i < n1 ? 0 : 1]++;
     const size_t phase_lo = i < n1 ? 0 : n1;
     uint32_t lvl = 0, slvl = 0;
     for (size_t side = 0; side < 2; side++)
@@ -231,7 +233,7 @@ void wit_phase(const Entered &e, const bpgpu_witness *w, size_t nb, int ph, cons
   const uint32_t l_lo = ph == 1 ? 0 : levels[0];
   const int form = route == 3 && w->affine[ph - 1] ? 4 : route;           // a phase with an affine member: the affine instantiation
   Prof22 prof(e.ctx);
-  witness_eval(e.view.st, w->dev, nb, form, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
+  witness_eval(e.view.st, w->dev, nb, form, w->invs[ph - 1] != 0, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
 }
 // the gates [lo, lo + count) of every prover, out of the run's planes into ark planes of `stride` scalars per prover
 void wit_export(const Entered &e, const bpgpu_witness *w, size_t nb, const WitRun &run, size_t lo, size_t count, void *aL, void *aR, void *aO,
@@ -431,7 +433,7 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     for (size_t i = 0; i < n; i++) {
       if (op[i] == BPGPU_GATE_BIT && arg[i] >= WIT_BIT_MAX) return BPGPU_E_ARG;
       if (op[i] == BPGPU_GATE_INPUT && (s.row_len[2 * i] || s.row_len[2 * i + 1])) return BPGPU_E_ARG;
-      if (op[i] == BPGPU_GATE_BIT && s.row_len[2 * i + 1]) return BPGPU_E_ARG;
+      if ((op[i] == BPGPU_GATE_BIT || op[i] == BPGPU_GATE_INV) && s.row_len[2 * i + 1]) return BPGPU_E_ARG;
       for (size_t j = 0; j <= nchi; j++) {
         const size_t r = j * rows + 2 * i;
         if (j && i < n1 && row_ptr[r + 2] != row_ptr[r]) return BPGPU_E_ARG;       // the challenge does not exist in phase 1
@@ -440,13 +442,14 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       }
     }
     // the image of the device arrays: [coeff | row_ptr | var | arg | order | level_ptr | level_long | op | scan_order | scan_ptr |
-    // scan_long | chain_elem | chain_ptr | slot | asc], every part 256-byte aligned
+    // scan_long | chain_elem | chain_ptr | slot | asc | level_inv | scan_inv], every part 256-byte aligned
     const size_t nslev = (size_t)s.xscan_levels[0] + s.xscan_levels[1];
     const size_t o_rp = up256((nnz ? nnz : 1) * 32), o_var = o_rp + up256((rows + 1) * 4), o_arg = o_var + up256((nnz ? nnz : 1) * 4),
                  o_ord = o_arg + up256((n ? n : 1) * 4), o_lp = o_ord + up256((n ? n : 1) * 4), o_ll = o_lp + up256((nlev + 1) * 4),
                  o_op = o_ll + up256((nlev ? nlev : 1) * 4), o_so = o_op + up256(n ? n : 1), o_sp = o_so + up256((n ? n : 1) * 4),
                  o_sl = o_sp + up256((nslev + 1) * 4), o_ce = o_sl + up256((nslev ? nslev : 1) * 4), o_cp = o_ce + up256((n ? n : 1) * 4),
-                 o_slot = o_cp + up256((nslev + 1) * 4), o_asc = o_slot + up256((n ? n : 1) * 4), total = o_asc + up256((n ? n : 1) * 4);
+                 o_slot = o_cp + up256((nslev + 1) * 4), o_asc = o_slot + up256((n ? n : 1) * 4), o_li = o_asc + up256((n ? n : 1) * 4),
+                 o_si = o_li + up256((nlev ? nlev : 1) * 4), total = o_si + up256((nslev ? nslev : 1) * 4);
     std::vector<uint8_t> img(total, 0);
     Words8 *h_coeff = (Words8 *)img.data();
     uint32_t *h_rp = (uint32_t *)(img.data() + o_rp), *h_var = (uint32_t *)(img.data() + o_var), *h_arg = (uint32_t *)(img.data() + o_arg),
@@ -477,8 +480,15 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
           break;
         }
     }
-    // the gates of a phase sorted by level (stable: program order within a level), the ones with a long row last in their level
+    // the gates of a phase sorted by level (stable: program order within a level): the ones with short rows, the INV gates among
+    // them last (k_witness.hip inverts once per thread for those), then the ones with a long row.  A level without an INV gate has
+    // the order it always had
     const uint32_t lane_max = rows_lane_max();
+    uint32_t *h_li = (uint32_t *)(img.data() + o_li), *h_si = (uint32_t *)(img.data() + o_si);
+    const auto list_of = [&](size_t i) {        // 0: short rows | 1: short rows, INV | 2: a long row
+      if (s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max) return 2;
+      return op[i] == BPGPU_GATE_INV ? 1 : 0;
+    };
     uint32_t pairs = 0, at = 0, lvl_base = 0;
     for (size_t i = 0; i < n; i++) {
       h_op[i] = op[i];
@@ -488,44 +498,48 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       const size_t lo = ph ? n1 : 0, hi = ph ? n : n1;
       for (uint32_t l = 0; l < s.levels[ph]; l++) {
         h_lp[lvl_base + l] = at;
-        for (int want_long = 0; want_long < 2; want_long++) {
-          if (want_long) h_ll[lvl_base + l] = at;
+        for (int list = 0; list < 3; list++) {
+          if (list == 1) h_li[lvl_base + l] = at;
+          if (list == 2) h_ll[lvl_base + l] = at;
           for (size_t i = lo; i < hi; i++)
-            if (s.level[i] == l && (int)(s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max) == want_long) h_ord[at++] = (uint32_t)i;
+            if (s.level[i] == l && list_of(i) == list) h_ord[at++] = (uint32_t)i;
         }
       }
       lvl_base += s.levels[ph];
     }
     h_lp[nlev] = at;
-    // a level's gates numbered by ascending gate index (the slots of the two-party form): each of its two runs in order[] ascends,
-    // so the numbering is their merge
+    // a level's gates numbered by ascending gate index (the slots of the two-party form): each of its three runs in order[]
+    // ascends, so the numbering is their merge
     uint32_t *h_slot = (uint32_t *)(img.data() + o_slot), *h_asc = (uint32_t *)(img.data() + o_asc);
     for (size_t l = 0; l < nlev; l++) {
-      uint32_t a = h_lp[l], b = h_ll[l];
+      uint32_t at3[3] = {h_lp[l], h_li[l], h_ll[l]};
+      const uint32_t end3[3] = {h_li[l], h_ll[l], h_lp[l + 1]};
       for (uint32_t t = h_lp[l]; t < h_lp[l + 1]; t++) {
-        const bool from_short = a < h_ll[l] && (b >= h_lp[l + 1] || h_ord[a] < h_ord[b]);
-        const uint32_t u = from_short ? a++ : b++;
+        int from = -1;
+        for (int k = 0; k < 3; k++)
+          if (at3[k] < end3[k] && (from < 0 || h_ord[at3[k]] < h_ord[at3[from]])) from = k;
+        const uint32_t u = at3[from]++;
         h_slot[u] = t - h_lp[l];
         h_asc[t] = h_ord[u];
       }
     }
-    // the same over the extended compressed levels, members apart: a level's ordinary gates (short rows, then long), and the members
+    // the same over the extended compressed levels, members apart: a level's ordinary gates (short rows, INV last; then long), and the members
     // of the extended chains it heads, chain after chain (heads in program order), each chain from its first member on.  A phase
     // without an affine member has the product chains' lists: pass 2 changed nothing of it
     uint32_t *h_so = (uint32_t *)(img.data() + o_so), *h_sp = (uint32_t *)(img.data() + o_sp), *h_sl = (uint32_t *)(img.data() + o_sl),
              *h_ce = (uint32_t *)(img.data() + o_ce), *h_cp = (uint32_t *)(img.data() + o_cp);
-    std::vector<uint32_t> fill(3 * nslev + 1, 0);          // per compressed level: short, long, members -> where each list starts
+    std::vector<uint32_t> fill(4 * nslev + 1, 0);          // per compressed level: short, INV, long, members -> where each list starts
     const auto slot = [&](size_t i) {
       const size_t l = (i < n1 ? 0 : s.xscan_levels[0]) + s.xscan_level[i];
-      return 3 * l + (s.xpred[i] != WIT_NONE ? 2 : (s.row_len[2 * i] > lane_max || s.row_len[2 * i + 1] > lane_max ? 1 : 0));
+      return 4 * l + (s.xpred[i] != WIT_NONE ? 3 : list_of(i));          // (an INV gate is never a member)
     };
     for (size_t i = 0; i < n; i++) fill[slot(i) + 1]++;
     uint32_t ord_at = 0, mem_at = 0;
     for (size_t l = 0; l < nslev; l++) {
-      const uint32_t shorts = fill[3 * l + 1], longs = fill[3 * l + 2], mems = fill[3 * l + 3];
-      h_sp[l] = ord_at; h_sl[l] = ord_at + shorts; h_cp[l] = mem_at;
-      fill[3 * l] = ord_at; fill[3 * l + 1] = ord_at + shorts; fill[3 * l + 2] = mem_at;
-      ord_at += shorts + longs;
+      const uint32_t shorts = fill[4 * l + 1], invs = fill[4 * l + 2], longs = fill[4 * l + 3], mems = fill[4 * l + 4];
+      h_sp[l] = ord_at; h_si[l] = ord_at + shorts; h_sl[l] = ord_at + shorts + invs; h_cp[l] = mem_at;
+      fill[4 * l] = ord_at; fill[4 * l + 1] = ord_at + shorts; fill[4 * l + 2] = ord_at + shorts + invs; fill[4 * l + 3] = mem_at;
+      ord_at += shorts + invs + longs;
       mem_at += mems;
     }
     h_sp[nslev] = ord_at; h_cp[nslev] = mem_at;
@@ -534,7 +548,7 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
       const size_t k = slot(i);
       h_so[fill[k]++] = (uint32_t)i;
       if (s.xsucc[i] == WIT_NONE) continue;
-      uint32_t &m_at = fill[k - k % 3 + 2];                 // a head: its chain, whole, into its level's member list
+      uint32_t &m_at = fill[k - k % 4 + 3];                 // a head: its chain, whole, into its level's member list
       for (uint32_t e = s.xsucc[i], first = WIT_ELEM_START; e != WIT_NONE; e = s.xsucc[e], first = 0)
         h_ce[m_at++] = e | first | (s.xlink_right[e] ? WIT_ELEM_RIGHT : 0u) | (s.is_affine[e] ? WIT_ELEM_AFFINE : 0u);
     }
@@ -543,6 +557,7 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     w->n = n; w->n1 = n1; w->m = m; w->nchi = nchi; w->ninp = s.ninp;
     w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
     for (size_t i = 0; i < n; i++) if (op[i] == BPGPU_GATE_BIT) w->bits[i < n1 ? 0 : 1]++;
+    w->invs[0] = s.ninv[0]; w->invs[1] = s.ninv[1];
     w->level_ptr.assign(h_lp, h_lp + nlev + 1);
     w->level_long.assign(h_ll, h_ll + nlev);
     for (int ph = 0; ph < 2; ph++) {
@@ -570,6 +585,8 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     w->dev.chain_ptr = (const uint32_t *)(d + o_cp);
     w->dev.slot = (const uint32_t *)(d + o_slot);
     w->dev.asc = (const uint32_t *)(d + o_asc);
+    w->dev.level_inv = (const uint32_t *)(d + o_li);
+    w->dev.scan_inv = (const uint32_t *)(d + o_si);
     w->dev.n = (uint32_t)n; w->dev.m = (uint32_t)m; w->dev.nchi = (uint32_t)nchi; w->dev.ninp = s.ninp;
     *out = w;
     return BPGPU_OK;

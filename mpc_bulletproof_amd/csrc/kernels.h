@@ -299,14 +299,21 @@ struct WitDev {
   // of them, slot[u] the t of order[u]
   const uint32_t *slot;       // n
   const uint32_t *asc;        // n
+  // the INV gates (witness_dev.cuh) without a long row stand LAST among a level's short-row gates: order[level_inv[l] ..
+  // level_long[l]), and scan_order[scan_inv[l] .. scan_long[l]) of a compressed level; a level without one has level_inv[l] ==
+  // level_long[l] and the order it had before the op existed.  Read by the <.., true> instantiations alone.
+  const uint32_t *level_inv;  // levels
+  const uint32_t *scan_inv;   // compressed levels
 };
 // One launch evaluates the gates [g_lo, g_hi) = the levels [l_lo, l_hi) of nb provers on plain canonical planes nb x n (aL, aR, aO:
 // read for the gates below g_lo, written for the range), v nb x m, inputs nb x ninp x 2, chi nb x nchi (or nullptr), all plain.
 // form 1: a lane per prover, program order; 2: a block of 256 threads per prover, level by level; 3: a block per prover over the
 // COMPRESSED levels [l_lo, l_hi), the chains of a level as one segmented prefix product (k_witness_scan<false>) or, where the range
 // holds an affine member (form 4), as one segmented prefix composition of affine maps (k_witness_scan<true>).
-void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo, uint32_t l_hi,
-                  Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
+// inv: the range holds an INV gate -- the <.., true> instantiation of the form's kernel, which carries the field inversion (one per
+// gate in form 1 and for a long row, one per thread and level otherwise); a range without one launches the kernel it always did.
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, bool inv, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo,
+                  uint32_t l_hi, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
 // rows of `count` scalars, one per prover: src + p * src_stride -> dst + p * dst_stride.  to_ark: plain canonical -> ark Montgomery
 // limbs, else the reverse; a non-canonical source raises *bad and gives zero
 void witness_convert(hipStream_t st, bool to_ark, size_t nb, size_t count, const Words8 *src, size_t src_stride, Words8 *dst,

@@ -126,6 +126,7 @@ def pippenger_plan(nb, n):
 # bpgpu_witness_plan (include/bpgpu.h BPGPU_WIT_PLAN_*); gate ops BPGPU_GATE_*
 WIT_PLAN_FIELDS = ("levels1", "levels2", "widest", "long_rows", "inputs", "route1", "route2")
 GATE_MUL, GATE_INPUT, GATE_BIT = 0, 1, 2
+GATE_INV = 4         # (3 is no op: include/bpgpu.h)
 
 
 def _u32s(xs, pad=1):

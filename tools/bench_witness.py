@@ -27,6 +27,13 @@ provers x shuffle k = 64 (two chains of 63 dependent gates: a head and 62 member
 8 .. 16 382 members) for 1 and 256 provers, block form against scan form.  The block form is the path these programs took before
 there was an affine scan.  WIT_AFFINE_MIN (csrc/bpgpu_internal.h) is read from that sweep by the rule of the shuffle sweep.
 
+`bench_witness.py inv` measures the INV gates (BPGPU_GATE_INV) and appends to profiles/witness_inv.log.  Shapes: 256 provers x one
+level of 1024 INV gates, 1 x 1024, 4096 x 16, and 256 x a chain of 64 INV gates each reading the previous a_O (one gate a level:
+nothing to batch).  Per shape three columns: (a) the block form (BPGPU_OPT_WITNESS_ROUTE 2: one inversion per thread and level),
+(b) the lane form (route 1: one inversion per gate) -- the A/B of the batching on one commit --, and (c) the same program with every
+INV gate replaced by an INPUT gate fed the precomputed pairs, on route 2: the only way a library without the op runs it, the host's
+own inversions and the upload of the pairs left out; what the device inversion costs over having been handed the answer is (a) / (c).
+
 A fresh process per line under its own time limit; WARM untimed steps, then STEPS timed ones, medians (min..max) in ms."""
 import ctypes as C
 import json
@@ -75,6 +82,60 @@ def range_program(bits, m):
     import witness_cases as wc
     case = wc.range_case(bits, m)
     return case.prog, [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << bits) - 1)) for i in range(m)]
+
+
+INV_SHAPES = (("level", 256, 1024), ("level", 1, 1024), ("level", 4096, 16), ("chain", 256, 64))
+
+
+def inv_programs(shape, size):
+    """(the program with INV gates, its twin with INPUT gates, one prover's values): `level` = size independent gates inv(v_j + i + 1),
+    `chain` = size gates inv(a_O[i - 1] + v_j)"""
+    import witness_cases as wc
+    import witness_inv_cases as ic
+    m = 4
+    prog, twin = ic.Program(m), ic.Program(m)
+    last = None
+    for i in range(size):
+        if shape == "chain" and last is not None:
+            last = prog.inv([(wc.O, last, 1), (wc.V, i % m, 1)])
+        else:
+            last = prog.inv([(wc.V, i % m, 1), (wc.ONE, 0, i + 1)])
+        twin.input()
+    prog.end_phase1()
+    twin.end_phase1()
+    return prog, twin, [((0x9E3779B97F4A7C15 * (i + 1)) & ((1 << 64) - 1)) for i in range(m)]
+
+
+def inv_synth(shape, nb, size):
+    import mpc_dealer as md
+    import mpc_bulletproof_amd as m
+    prog, twin, v = inv_programs(shape, size)
+    want = prog.evaluate(v)
+    assert all(x for x in want[0]) and want[2] == [1] * size
+    gpu = m.BpGpu(0)
+    d_v = gpu.to_device(b"".join(md.mont(x) for x in v) * nb)
+    d_in = gpu.to_device(b"".join(md.mont(x) for pair in zip(want[0], want[1]) for x in pair) * nb)
+    planes = [gpu.malloc(32 * nb * size) for _ in range(3)]
+    timer = Timer(gpu)
+    out = {}
+    for col, which, route in (("block", prog, 2), ("lane", prog, 1), ("input", twin, 2)):
+        w = gpu.witness_create(*which.create_args())
+        gpu.set_option("witness_route", route)
+        ts = []
+        for step in range(WARM + STEPS):
+            ms = timer.events(lambda: gpu.r1cs_witness_synthesize_dev(w, nb, 0, *planes, d_v=d_v, d_inputs=d_in if which is twin else None))
+            if step >= WARM:
+                ts.append(ms)
+        assert gpu.input_flag() == 0
+        for k in range(3):
+            got = gpu.download(planes[k], 32 * nb * size)
+            assert got[-32 * size:] == b"".join(md.mont(x) for x in want[k]), "the device's witness differs from the host's"
+        gpu.witness_destroy(w)
+        out[col] = ts
+    a, b, c = (statistics.median(out[col]) for col in ("block", "lane", "input"))
+    plan = m.lib.witness_plan(*prog.plan_args(), nb)
+    return (f"(a) block {fmt(out['block'])}   (b) lane {fmt(out['lane'])}   (c) INPUT {fmt(out['input'])}   (b)/(a) {b / a:8.2f}   (a)/(c) {a / c:8.2f}   "
+            f"(b)/(c) {b / c:8.2f}   plan: {('lane', 'block', 'scan')[plan['route1'] - 1]:5s}   levels {plan['levels1']:3d}")
 
 
 class Timer:
@@ -204,7 +265,9 @@ def prove(nb, ks, window_bits):
 
 
 def child(what, args):
-    if what == "synth":
+    if what == "inv":
+        print("RESULT", inv_synth(args[0], int(args[1]), int(args[2])))
+    elif what == "synth":
         text, spans = synth(args[0], int(args[1]), int(args[2]), tuple(args[3].split(",")))
         print("SPANS", json.dumps(spans))
         print("RESULT", text)
@@ -306,11 +369,33 @@ def affine_main():
     return 0 if ok else 1
 
 
+def inv_main():
+    lines, _, step = runner("inv ")
+    lines[-1] = ("# inv: bpgpu_r1cs_witness_synthesize_dev alone, HIP events; (a) route 2, one inversion per thread and level; (b) route 1, "
+                 "one per gate; (c) the INV gates as INPUT gates fed the pairs, route 2")
+    ok = True
+    for shape, nb, size in INV_SHAPES:
+        text = f"inv     {nb:4d} x {'a chain of' if shape == 'chain' else 'one level of'} {size:4d} INV gates   "
+        if ok:
+            ok = step(text, "inv", shape, nb, size)
+        else:
+            lines.append(text + "UNMEASURED")
+    if not ok:
+        lines.append("# a step failed: the steps after it were not started")
+    path = os.path.join(ROOT, "profiles", "witness_inv.log")
+    with open(path, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("wrote", path)
+    return 0 if ok else 1
+
+
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3:])
     if sys.argv[1:] == ["affine"]:
         return affine_main()
+    if sys.argv[1:] == ["inv"]:
+        return inv_main()
     lines, spans, step = runner("")
     ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16, "lane,block,scan")
     ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64, "lane,block,scan")
