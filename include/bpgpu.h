@@ -753,6 +753,64 @@ int bpgpu_r1cs_prove_fs2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_ci
                              const void *s_R, const void *vector_keys, const void *v_blinding, const void *blindings, void *proof_points,
                              void *proof_scalars, void *wire, void *challenges_out, void *states_out, void *gadget_challenges_out,
                              void *a_L_out, void *a_R_out, void *a_O_out);
+/* Prove from COMMITTED VALUES in one call: what a prover has -- the transcript state at Prover::new, the values and their blindings, the
+ * gadget's INPUT pairs, the blinding factors -- in; what it ships -- commitments, proofs and a verdict per prover -- out.  The stages are
+ * the calls above (the same code, handed device pointers), all on the context's stream, no host wait between them, nothing left behind.
+ * Two circuit shapes are accepted, and nothing else:
+ *   ONE-PHASE  c numeric (bpgpu_circuit_create / _ark), w with nchi == 0 and n1 == n, gadget_label == NULL.  Stage order:
+ *              1 bpgpu_r1cs_commit_values with the chain from init_states, 2 bpgpu_r1cs_witness_synthesize phase 0,
+ *              3 bpgpu_r1cs_constraints_satisfied, 4 bpgpu_r1cs_prove_fs on the states that stage 1 produced.
+ *   TWO-PHASE  c parametric with nchi == 1, w with the same (n, n1, m, nchi), gadget_label given (32 bytes, host memory in both forms).
+ *              Stage order: 1 bpgpu_r1cs_commit_values, 2 the bpgpu_r1cs_prove_fs2 chain, which synthesizes both phases and draws the
+ *              gadget challenge, 3 bpgpu_r1cs_constraints_satisfied on the witness and the challenge that stage 2 left on the device.
+ *              The check necessarily runs AFTER the proof here: the phase-2 witness does not exist before the challenge.
+ * The witness planes, the chain states between stage 1 and the prover and the gadget challenge live in the context's pool memory for
+ * the length of the call (in the caller's buffers where a_*_out / gadget_challenges_out are given).  The one host wait is inherited from
+ * bpgpu_r1cs_constraints_satisfied: the first use of a circuit handle builds its row-major view, here before any stage is launched.
+ * REJECTED PROVERS SHIP NOTHING.  After the last stage ONE launch (k_prove_fs.hip, profiling kind 22; the stages keep their kinds)
+ * clears, for every prover with ok[p] == 0, its rows of proof_points, proof_scalars, wire, challenges_out and states_out to zero bytes:
+ * an all-zero wire proof has version byte 0 and undecodable points, and every wire verifier rejects it.  V, V_compressed, ok,
+ * first_bad_row, first_bad_gate, gadget_challenges_out and the witness outputs are left alone: they are the diagnostics.  Accepted
+ * provers' bytes are untouched.  The host form and the `_dev` form behave the same; the `_dev` form never waits for ok.
+ * Every operand has the encoding and layout of the call it is handed to:
+ *   init_states, v, v_blinding, V, V_compressed   as bpgpu_r1cs_commit_values (init_states: its states_in; V, V_compressed optional)
+ *   inputs                                         as bpgpu_r1cs_witness_synthesize
+ *   ok, first_bad_row, first_bad_gate              as bpgpu_r1cs_constraints_satisfied (nb x int32; optional nb x int64 each)
+ *   one-phase: s_L, s_R nb x n or vector_keys nb x 32, blindings nb x 8, proof_points, proof_scalars, wire, challenges_out, states_out
+ *              as bpgpu_r1cs_prove_fs; gadget_challenges_out is not written
+ *   two-phase: s_L, s_R nb x n or vector_keys nb x 2 x 32, blindings nb x 11, the results and gadget_challenges_out as bpgpu_r1cs_prove_fs2
+ *   a_L_out, a_R_out, a_O_out                      (optional, all three or none) nb x n, ark form: the synthesized witness
+ * For accepted provers every output equals, byte for byte, what the chain of the host-form calls returns on the same operands; for
+ * rejected provers ok, first_bad_row, first_bad_gate, V and V_compressed do.  Results never depend on BPGPU_OPT_WITNESS_ROUTE,
+ * BPGPU_OPT_WITNESS_SCAN_MIN or any other route option.
+ * Refusals, all before anything is launched: those of the constituent calls, and BPGPU_E_ARG for a null ok, proof_points or
+ * proof_scalars, for a null program, for a program whose (n, n1, m, nchi) are not the circuit's (a one-phase program has n1 == n), for
+ * nchi > 1, for a label given to a one-phase pair or missing for a two-phase one, for a program with INPUT gates and no `inputs`, for
+ * some but not all of the three witness outputs, for both or neither blinding-vector source and for a context after
+ * bpgpu_set_shard(world > 1); BPGPU_E_LEN for n == 0, or n1 >= n in the two-phase shape; BPGPU_E_GENS for padded_n above the
+ * generators' capacity; nb == 0: BPGPU_OK, nothing touched.  A non-canonical ark limb gives BPGPU_E_ARG in the host form and raises
+ * bpgpu_input_flag in the `_dev` form (every operand and result but the label a device pointer; asynchronous on the context's stream).
+ * A failed or refused call leaves no session and no pool memory behind.
+ * Measured (profiles/prove_values.log: wall clock of a batch in host form on an MI355X, pageable memory, median (min..max) ms, the one
+ * call | the chain of host-form calls it replaces, timed on a build of the parent commit; faster means the one call's maximum lies
+ * below the chain's minimum): 256 provers x 16 x 64-bit range values (n = 1024, m = 16) 14.135 (14.048..14.202) | 15.932
+ * (15.815..16.122), faster by 1.8 ms; 256 x shuffle 64 6.791 (6.774..6.836) | 7.466 (7.428..7.566), faster by 0.7 ms (from
+ * page-locked memory 6.698 (6.666..7.100) | 6.983 (6.965..7.016): the spans overlap, nothing is claimed); ONE shuffle-2^10 prover
+ * 33.272 (30.185..39.759) | 34.947 (30.998..40.040): the spans overlap, nothing is claimed; the range shape on a {0, 0} pool 13.761
+ * (13.607..14.246) against 14.611 (14.353..14.939) for bpgpu_r1cs_witness_synthesize + bpgpu_pool_r1cs_prove_fs, which commit and
+ * check nothing; the clearing launch at 256 provers 0.008 ms.  Every other shape is UNMEASURED. */
+int bpgpu_r1cs_prove_values(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                            const uint8_t *init_states, const uint8_t gadget_label[32], const uint8_t *v, const uint8_t *v_blinding,
+                            const uint8_t *inputs, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *blindings,
+                            uint8_t *V, uint8_t *V_compressed, int32_t *ok, int64_t *first_bad_row, int64_t *first_bad_gate,
+                            uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out,
+                            uint8_t *gadget_challenges_out, uint8_t *a_L_out, uint8_t *a_R_out, uint8_t *a_O_out);
+int bpgpu_r1cs_prove_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                                const void *init_states, const uint8_t gadget_label[32], const void *v, const void *v_blinding,
+                                const void *inputs, const void *s_L, const void *s_R, const void *vector_keys, const void *blindings, void *V,
+                                void *V_compressed, void *ok, void *first_bad_row, void *first_bad_gate, void *proof_points, void *proof_scalars,
+                                void *wire, void *challenges_out, void *states_out, void *gadget_challenges_out, void *a_L_out, void *a_R_out,
+                                void *a_O_out);
 /* ---- two-party prover: ONE party's local arithmetic (src/r1cs_mpc/: the collaborative prover over SPDZ-style shares) ----------------
  * An authenticated scalar held by party p is THREE planes: a share s_p, a MAC share m_p and a public modifier c, identical at both
  * parties.  Invariants: value v = s_0 + s_1 + c; m_0 + m_1 = alpha (s_0 + s_1), alpha = alpha_0 + alpha_1 the MAC key.  No local step
@@ -1140,8 +1198,11 @@ int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *
  *     and two host threads on one GPU: that is how the pool is exercised on a one-GPU machine).  Generators and circuits are built
  *     once per DISTINCT device, on the workers of those devices at the same time, and shared by the slots of that device; _get returns
  *     the handle of the slot's device, so that every single-context entry point can still be used on the borrowed context of a slot.
- *     Creation is all or nothing: what was made before a failure is released.  Parametric circuits (bpgpu_circuit_create_param) have no
- *     pool form: a pool serves circuits without randomized constraints only.
+ *     Creation is all or nothing: what was made before a failure is released.  Parametric circuits (bpgpu_pool_circuit_create_param:
+ *     the arguments of bpgpu_circuit_create_param) serve bpgpu_pool_r1cs_prove_values alone: verification of two-phase proofs has no pool
+ *     form yet, so the _verify_* calls and _prove_fs refuse such a handle with BPGPU_E_ARG before any worker is woken.  A
+ *     bpgpu_pool_witness is one bpgpu_witness gate program per distinct device (bpgpu_pool_witness_create: the arguments, validation and
+ *     error codes of bpgpu_witness_create, all or nothing; _get(w, slot): the program of the slot's device; _destroy before the pool).
  *   bpgpu_pool_create: BPGPU_E_ARG for a null out, a null devices, nslots == 0 or nslots > BPGPU_POOL_MAX_SLOTS; BPGPU_E_DEVICE without
  *     a HIP device or for an index outside [0, bpgpu_device_count).  bpgpu_pool_destroy joins the threads; the pool's generators and
  *     circuits are destroyed BEFORE it.
@@ -1158,7 +1219,8 @@ int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *
  *   [lo[s], lo[s + 1]): the ceil(nb / granule) granules are dealt as evenly as possible, the earlier slots taking the extra ones, so
  *   every share but the last non-empty one is a whole multiple of granule; lo[0] = 0, lo[nslots] = nb, lo is monotone, a slot may be
  *   empty.  BPGPU_E_ARG for nslots == 0, granule == 0 or a null lo (nslots + 1 entries).  The granule is slot 0's
- *   BPGPU_OPT_STREAM_BATCH for _verify_stream, its BPGPU_OPT_SCREEN_BATCH for _verify_screened and _verify_combined, and 1 for _prove_fs.
+ *   BPGPU_OPT_STREAM_BATCH for _verify_stream, its BPGPU_OPT_SCREEN_BATCH for _verify_screened and _verify_combined, and 1 for _prove_fs and
+ *   _prove_values.
  * The calls.  Operands, results and layouts are those of the single-context host forms, for the whole queue (all arrays are
  *   proof-major: a share is an offset into each); what is written for a share is exactly what the single-context call writes for it.
  *   bpgpu_pool_r1cs_verify_stream    bpgpu_r1cs_verify_stream per share; slot_proofs (optional, nslots entries): the size of each share
@@ -1168,6 +1230,9 @@ int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *
  *                                    returns (64 zero bytes: every proof valid).  Between processes this reduction is the all-gather of
  *                                    the partials; inside one process it is a 64-byte hand-over per slot.
  *   bpgpu_pool_r1cs_prove_fs         bpgpu_r1cs_prove_fs per share (operands and results as there, host form)
+ *   bpgpu_pool_r1cs_prove_values     bpgpu_r1cs_prove_values per share, one-phase or two-phase (operands and results as there, host form:
+ *                                    commitments, verdicts and proofs from the provers' values; a rejected prover's proof rows are zero
+ *                                    bytes, whichever slot it fell to); the gadget label is shared by the whole queue
  *   Shape and argument errors are found before any worker is woken, with the codes of the single-context call (BPGPU_E_ARG also for
  *   handles of another pool); nb == 0 returns BPGPU_OK and touches nothing, out_xy and fallback_batches included.  When a slot fails at
  *   run time the other slots still finish -- nothing is cancelled and nothing is left running when the call returns -- and the call
@@ -1182,6 +1247,7 @@ int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *
 typedef struct bpgpu_pool bpgpu_pool;
 typedef struct bpgpu_pool_gens bpgpu_pool_gens;
 typedef struct bpgpu_pool_circuit bpgpu_pool_circuit;
+typedef struct bpgpu_pool_witness bpgpu_pool_witness;
 int bpgpu_pool_create(const int *devices, size_t nslots, bpgpu_pool **out);
 void bpgpu_pool_destroy(bpgpu_pool *pool);
 size_t bpgpu_pool_slots(const bpgpu_pool *pool);
@@ -1197,8 +1263,16 @@ int bpgpu_pool_circuit_create(bpgpu_pool *pool, size_t q, const uint32_t *row_pt
                               const uint8_t *coeff, size_t n_multipliers, size_t m_commitments, bpgpu_pool_circuit **out);
 int bpgpu_pool_circuit_create_ark(bpgpu_pool *pool, size_t q, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
                                   const uint8_t *coeff_ark, size_t n_multipliers, size_t m_commitments, bpgpu_pool_circuit **out);
+int bpgpu_pool_circuit_create_param(bpgpu_pool *pool, size_t q, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
+                                    const uint32_t *idx, const uint8_t *coeff, size_t n_multipliers, size_t m_commitments,
+                                    bpgpu_pool_circuit **out);
 void bpgpu_pool_circuit_destroy(bpgpu_pool *pool, bpgpu_pool_circuit *c);
 const bpgpu_circuit *bpgpu_pool_circuit_get(const bpgpu_pool_circuit *c, size_t slot);
+int bpgpu_pool_witness_create(bpgpu_pool *pool, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
+                              const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff,
+                              bpgpu_pool_witness **out);
+void bpgpu_pool_witness_destroy(bpgpu_pool *pool, bpgpu_pool_witness *w);
+const bpgpu_witness *bpgpu_pool_witness_get(const bpgpu_pool_witness *w, size_t slot);
 int bpgpu_pool_shares(size_t nb, size_t nslots, size_t granule, size_t *lo);
 int bpgpu_pool_r1cs_verify_stream(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t nb, size_t n1, size_t k,
                                   const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, int32_t *ok, size_t *slot_proofs);
@@ -1212,6 +1286,13 @@ int bpgpu_pool_r1cs_prove_fs(bpgpu_pool *pool, const bpgpu_pool_gens *g, const b
                              const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
                              const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points,
                              uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out);
+int bpgpu_pool_r1cs_prove_values(bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, const bpgpu_pool_witness *w,
+                                 size_t nb, const uint8_t *init_states, const uint8_t gadget_label[32], const uint8_t *v,
+                                 const uint8_t *v_blinding, const uint8_t *inputs, const uint8_t *s_L, const uint8_t *s_R,
+                                 const uint8_t *vector_keys, const uint8_t *blindings, uint8_t *V, uint8_t *V_compressed, int32_t *ok,
+                                 int64_t *first_bad_row, int64_t *first_bad_gate, uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire,
+                                 uint8_t *challenges_out, uint8_t *states_out, uint8_t *gadget_challenges_out, uint8_t *a_L_out,
+                                 uint8_t *a_R_out, uint8_t *a_O_out);
 
 #ifdef __cplusplus
 }

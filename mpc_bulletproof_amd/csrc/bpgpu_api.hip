@@ -3942,10 +3942,8 @@ static int prove_fs_staged(bpgpu_ctx *ctx, size_t nb, size_t k, size_t wire_len,
 // the refusals that depend on shapes alone, before anything is launched (BPGPU_OK with nb == 0: nothing to do)
 static int prove_fs_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const ProveFsIo &a) {
   if (!ctx || !g || !c) return BPGPU_E_ARG;
-  if (c->nchi) return BPGPU_E_ARG;       // a two-phase prover evaluates its gadget on the challenge: that round trip stays on the host
+  CK(bpgpu_internal_prove_fs_shape(g, c, nb));
   if (!nb) return BPGPU_OK;
-  if (!c->n) return BPGPU_E_LEN;         // (no multipliers: no IPP to speak of; the staged calls serve such circuits)
-  if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
   if (!a.states_in || !a.a_L || !a.a_R || !a.a_O || !a.blindings || !a.proof_points || !a.proof_scalars || (c->m && !a.v_blinding)) return BPGPU_E_ARG;
   if ((!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
   return BPGPU_OK;
@@ -4429,5 +4427,32 @@ int bpgpu_internal_prove_fs2_chains(bpgpu_ctx *ctx, const bpgpu_gens *g, const b
   CK(between(user, fs2_arrays(own.get()).chi));
   return prove_fs2_finish_locked(ctx, g, c, own, {nullptr, io.a_L2, io.a_R2, io.a_O2, io.s_L2, io.s_R2, io.keys2, io.v_blinding, io.blindings2,
                                                   io.proof_points, io.proof_scalars, io.wire, io.challenges_out, io.states_out});
+}
+// the stages of bpgpu_r1cs_prove_values: the _locked functions of the entry points above, as they stand
+int bpgpu_internal_prove_fs_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb) {
+  if (c->nchi) return BPGPU_E_ARG;       // a two-phase prover evaluates its gadget on the challenge: bpgpu_r1cs_prove_fs2
+  if (!nb) return BPGPU_OK;
+  if (!c->n) return BPGPU_E_LEN;         // (no multipliers: no IPP to speak of; the staged calls serve such circuits)
+  return prove_fs_dims(c).padded_n > g->cap ? BPGPU_E_GENS : BPGPU_OK;
+}
+int bpgpu_internal_commit_values_shape(size_t nb, size_t m) {
+  return nb > COMMIT_VALUES_MAX || (m && nb > COMMIT_VALUES_MAX / m) ? BPGPU_E_LEN : BPGPU_OK;
+}
+int bpgpu_internal_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const void *v, const void *v_blinding,
+                                 const void *states_in, void *V, void *V_compressed, void *states_out) {
+  return commit_values_locked(ctx, g, nb, m, {v, v_blinding, states_in, V, V_compressed, states_out});
+}
+int bpgpu_internal_rows_fit(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb) {
+  RowsDev view;
+  CK(circuit_view(ctx, c, &view));
+  return rows_eval_fits(view, nb) ? BPGPU_OK : BPGPU_E_LEN;
+}
+int bpgpu_internal_constraints_satisfied(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R, const void *a_O,
+                                         const void *v, const void *gadget_challenges, void *ok, void *first_bad_row, void *first_bad_gate) {
+  return rows_locked(ctx, c, nb, 1, {a_L, a_R, a_O, v, gadget_challenges, ok, first_bad_row, first_bad_gate, nullptr}, true);
+}
+int bpgpu_internal_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const bpgpu_internal_fs1 &io) {
+  return prove_fs_locked(ctx, g, c, nb, {io.states_in, io.a_L, io.a_R, io.a_O, io.s_L, io.s_R, io.vector_keys, io.v_blinding, io.blindings,
+                                         io.proof_points, io.proof_scalars, io.wire, io.challenges_out, io.states_out});
 }
 

@@ -52,4 +52,33 @@ struct bpgpu_internal_fs2 {
 };
 BPGPU_HIDDEN int bpgpu_internal_prove_fs2_chains(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                                  const bpgpu_internal_fs2 &io, int (*between)(void *user, const void *chi_dev), void *user);
+// The stages of bpgpu_r1cs_prove_values beside the two above (mutex held, arguments checked, nb > 0, every pointer HBM; asynchronous):
+// the refusals of bpgpu_r1cs_prove_fs and of bpgpu_r1cs_commit_values that depend on shapes alone, and the launches of
+// bpgpu_r1cs_commit_values_dev, bpgpu_r1cs_constraints_satisfied_dev (no residuals) and bpgpu_r1cs_prove_fs_dev.  _rows_fit builds the
+// row-major view of c if it does not exist yet (the one wait of the call) and gives the check's BPGPU_E_LEN before anything else runs.
+struct bpgpu_internal_fs1 {
+  const void *states_in, *a_L, *a_R, *a_O, *s_L, *s_R, *vector_keys, *v_blinding, *blindings;
+  void *proof_points, *proof_scalars, *wire, *challenges_out, *states_out;
+};
+BPGPU_HIDDEN int bpgpu_internal_prove_fs_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb);
+BPGPU_HIDDEN int bpgpu_internal_commit_values_shape(size_t nb, size_t m);
+BPGPU_HIDDEN int bpgpu_internal_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size_t m, const void *v, const void *v_blinding,
+                                              const void *states_in, void *V, void *V_compressed, void *states_out);
+BPGPU_HIDDEN int bpgpu_internal_rows_fit(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb);
+BPGPU_HIDDEN int bpgpu_internal_constraints_satisfied(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t nb, const void *a_L, const void *a_R,
+                                                      const void *a_O, const void *v, const void *gadget_challenges, void *ok,
+                                                      void *first_bad_row, void *first_bad_gate);
+BPGPU_HIDDEN int bpgpu_internal_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, const bpgpu_internal_fs1 &io);
+// The operands of bpgpu_r1cs_prove_values in the header's order, and its refusals that precede a launch (BPGPU_OK with nb == 0:
+// nothing to do): bpgpu_pool.hip asks before it wakes a worker.  Only the handles' shapes and the pointers' presence are read.
+struct bpgpu_internal_pv {
+  const void *init_states;
+  const uint8_t *gadget_label;                                                  // host memory in every form
+  const void *v, *v_blinding, *inputs, *s_L, *s_R, *vector_keys, *blindings;
+  void *V, *V_compressed, *ok, *first_bad_row, *first_bad_gate, *proof_points, *proof_scalars, *wire, *challenges_out, *states_out,
+      *gadget_challenges_out, *a_L_out, *a_R_out, *a_O_out;
+};
+BPGPU_HIDDEN size_t bpgpu_internal_witness_inputs(const bpgpu_witness *w);      // INPUT pairs per prover
+BPGPU_HIDDEN int bpgpu_internal_prove_values_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                                                   const bpgpu_internal_pv &a);
 #endif

@@ -5,53 +5,10 @@
 // end of a combined check.  Written on the public entry points, plus bpgpu_internal_verify_stream (bpgpu_internal.h).
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include <functional>
-#include <mutex>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "bpgpu_internal.h"
-#include "pool_workers.hpp"
-
-struct bpgpu_pool {
-  std::mutex mu;                     // one pool call at a time
-  std::vector<int> device;           // per slot
-  std::vector<bpgpu_ctx *> ctx;      // per slot
-  std::vector<size_t> owner;         // per slot: the lowest slot of the same device, which creates and destroys that device's handles
-  bppool::Workers workers{BPGPU_E_OOM};   // (a job that throws has run out of host memory: nothing else in them throws)
-  std::string err;
-};
-// one handle per distinct device, shared by that device's slots
-struct bpgpu_pool_gens {
-  const bpgpu_pool *pool = nullptr;
-  std::vector<bpgpu_gens *> at;      // per slot (at[s] == at[owner[s]])
-  size_t cap = 0;
-};
-struct bpgpu_pool_circuit {
-  const bpgpu_pool *pool = nullptr;
-  std::vector<bpgpu_circuit *> at;
-  size_t n = 0, m = 0;               // multipliers, commitments: the strides of a proof's operands
-};
+#include "pool_host.h"
 
 namespace {
 
-using Job = bppool::Workers::Job;
-
-// one round on the workers; the error of the lowest failing slot, with its slot, device and context text in pool->err
-int run_slots(bpgpu_pool *pool, const std::vector<Job> &jobs, const char *what) {
-  std::vector<int> codes;
-  const long bad = pool->workers.run(jobs, codes);
-  if (bad < 0) return BPGPU_OK;
-  const size_t s = (size_t)bad;
-  pool->err = std::string(what) + ": slot " + std::to_string(s) + " (device " + std::to_string(pool->device[s]) + "): " +
-              bpgpu_strerror(codes[s]) + " | " + bpgpu_last_error(pool->ctx[s]);
-  return codes[s];
-}
-int refuse(bpgpu_pool *pool, int code, const char *what) {
-  pool->err = std::string(what) + ": " + bpgpu_strerror(code) + " (refused before any slot was woken)";
-  return code;
-}
 // The in-place operand route of bpgpu_r1cs_verify_stream (the chain's fetch kernel reads page-locked host memory over the bus) is
 // taken only when the slice is KNOWN to be mapped for the slot's device: the runtime reports that device as the owner of the first
 // and of the last byte, both are device-mapped host memory at one offset from each other, and both lie in one allocation.
@@ -78,55 +35,6 @@ int verify_shape(const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c, size_t n
   const size_t np = (size_t)1 << k, n = c->n;
   if (n > np || n1 > n || (np > 1 && n <= np / 2 && n != 0)) return BPGPU_E_LEN;
   return np > g->cap ? BPGPU_E_GENS : BPGPU_OK;
-}
-bool handles_ok(const bpgpu_pool *pool, const bpgpu_pool_gens *g, const bpgpu_pool_circuit *c) {
-  return pool && g && c && g->pool == pool && c->pool == pool;
-}
-int shares_of(bpgpu_pool *pool, size_t nb, int option, std::vector<size_t> &lo) {
-  int64_t granule = 1;
-  if (option) {
-    const int rc = bpgpu_get_option(pool->ctx[0], option, &granule);
-    if (rc) return rc;
-  }
-  lo.assign(pool->ctx.size() + 1, 0);
-  return bpgpu_pool_shares(nb, pool->ctx.size(), (size_t)granule, lo.data());
-}
-const uint8_t *at(const uint8_t *p, size_t off) { return p ? p + off : nullptr; }
-uint8_t *at(uint8_t *p, size_t off) { return p ? p + off : nullptr; }
-
-// a handle per distinct device, made on the owners' workers at once; all or nothing
-template <class Handle>
-int make_per_device(bpgpu_pool *pool, std::vector<Handle *> &out, const std::function<int(bpgpu_ctx *, Handle **)> &create,
-                    const std::function<void(bpgpu_ctx *, Handle *)> &destroy, const char *what) {
-  const size_t ns = pool->ctx.size();
-  out.assign(ns, nullptr);
-  std::vector<Job> jobs(ns);
-  for (size_t s = 0; s < ns; s++)
-    if (pool->owner[s] == s) jobs[s] = [&, s]() -> int { return create(pool->ctx[s], &out[s]); };
-  const int rc = run_slots(pool, jobs, what);
-  if (rc) {
-    std::vector<Job> undo(ns);
-    for (size_t s = 0; s < ns; s++)
-      if (out[s]) undo[s] = [&, s]() -> int { destroy(pool->ctx[s], out[s]); return 0; };
-    std::vector<int> codes;
-    pool->workers.run(undo, codes);
-    out.assign(ns, nullptr);
-    return rc;
-  }
-  for (size_t s = 0; s < ns; s++) out[s] = out[pool->owner[s]];
-  return BPGPU_OK;
-}
-template <class Handle>
-void drop_per_device(bpgpu_pool *pool, std::vector<Handle *> &h, const std::function<void(bpgpu_ctx *, Handle *)> &destroy) {
-  const size_t ns = pool->ctx.size();
-  std::vector<Job> jobs(ns);
-  for (size_t s = 0; s < ns && s < h.size(); s++)
-    if (pool->owner[s] == s && h[s]) jobs[s] = [&, s]() -> int { destroy(pool->ctx[s], h[s]); return 0; };
-  std::vector<int> codes;
-  pool->workers.run(jobs, codes);
-}
-template <class Body> int noexcept_abi(Body body) {
-  try { return body(); } catch (const std::bad_alloc &) { return BPGPU_E_OOM; }
 }
 int circuit_create_any(bpgpu_pool *pool, bool ark, size_t q, const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx,
                        const uint8_t *coeff, size_t n_multipliers, size_t m_commitments, bpgpu_pool_circuit **out) {
@@ -282,7 +190,7 @@ const bpgpu_circuit *bpgpu_pool_circuit_get(const bpgpu_pool_circuit *c, size_t 
 
 int bpgpu_pool_r1cs_verify_stream(bpgpu_pool *pool, const bpgpu_pool_gens *pg, const bpgpu_pool_circuit *pc, size_t nb, size_t n1, size_t k,
                                   const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, int32_t *ok, size_t *slot_proofs) {
-  if (!handles_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !ok))) return BPGPU_E_ARG;
+  if (!numeric_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !ok))) return BPGPU_E_ARG;
   return noexcept_abi([&]() -> int {
     std::lock_guard<std::mutex> lk(pool->mu);
     const char *what = "bpgpu_pool_r1cs_verify_stream";
@@ -311,7 +219,7 @@ int bpgpu_pool_r1cs_verify_stream(bpgpu_pool *pool, const bpgpu_pool_gens *pg, c
 int bpgpu_pool_r1cs_verify_screened(bpgpu_pool *pool, const bpgpu_pool_gens *pg, const bpgpu_pool_circuit *pc, size_t nb, size_t n1, size_t k,
                                     const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *rho, int32_t *ok,
                                     size_t *fallback_batches) {
-  if (!handles_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !rho || !ok))) return BPGPU_E_ARG;
+  if (!numeric_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !rho || !ok))) return BPGPU_E_ARG;
   return noexcept_abi([&]() -> int {
     std::lock_guard<std::mutex> lk(pool->mu);
     const char *what = "bpgpu_pool_r1cs_verify_screened";
@@ -343,7 +251,7 @@ int bpgpu_pool_r1cs_verify_screened(bpgpu_pool *pool, const bpgpu_pool_gens *pg,
 int bpgpu_pool_r1cs_verify_combined(bpgpu_pool *pool, const bpgpu_pool_gens *pg, const bpgpu_pool_circuit *pc, size_t nb, size_t n1, size_t k,
                                     const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges, const uint8_t *rho,
                                     uint8_t out_xy[64]) {
-  if (!handles_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !rho)) || !out_xy) return BPGPU_E_ARG;
+  if (!numeric_ok(pool, pg, pc) || (nb && (!points || !scalars || !challenges || !rho)) || !out_xy) return BPGPU_E_ARG;
   return noexcept_abi([&]() -> int {
     std::lock_guard<std::mutex> lk(pool->mu);
     const char *what = "bpgpu_pool_r1cs_verify_combined";
@@ -379,7 +287,7 @@ int bpgpu_pool_r1cs_prove_fs(bpgpu_pool *pool, const bpgpu_pool_gens *pg, const 
                              const uint8_t *a_L, const uint8_t *a_R, const uint8_t *a_O, const uint8_t *s_L, const uint8_t *s_R,
                              const uint8_t *vector_keys, const uint8_t *v_blinding, const uint8_t *blindings, uint8_t *proof_points,
                              uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out) {
-  if (!handles_ok(pool, pg, pc)) return BPGPU_E_ARG;
+  if (!numeric_ok(pool, pg, pc)) return BPGPU_E_ARG;
   return noexcept_abi([&]() -> int {
     std::lock_guard<std::mutex> lk(pool->mu);
     const char *what = "bpgpu_pool_r1cs_prove_fs";

@@ -1,6 +1,7 @@
 // bpgpu_witness.hip -- the witness-synthesis entry points of include/bpgpu.h: gate programs (bpgpu_witness_create / _plan), their
-// evaluation (bpgpu_r1cs_witness_synthesize) and the one-call two-phase prover (bpgpu_r1cs_prove_fs2) on top of k_witness.hip.  The
-// context, its pool and the provers' chains live in bpgpu_api.hip; what this file takes from there is in bpgpu_internal.h.
+// evaluation (bpgpu_r1cs_witness_synthesize), the one-call two-phase prover (bpgpu_r1cs_prove_fs2) on top of k_witness.hip, and the
+// call that chains commitments, synthesis, check and proof from the provers' values (bpgpu_r1cs_prove_values).  The context, its
+// pool and the provers' chains live in bpgpu_api.hip; what this file takes from there is in bpgpu_internal.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -289,19 +290,27 @@ size_t lg_padded(size_t n) {
   while (((size_t)1 << k) < n) k++;
   return k;
 }
-int fs2_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
-  if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
+// what bpgpu_r1cs_prove_fs2 and bpgpu_r1cs_prove_values share: is w the program of c?
+bool wit_program_of(const bpgpu_witness *w, const bpgpu_circuit *c) {
   size_t n, m, nchi;
   bpgpu_internal_circuit_dims(c, &n, &m, &nchi);
-  if (w->n != n || w->m != m || w->nchi != nchi) return BPGPU_E_ARG;     // not this circuit's program
-  WCK(bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1));
-  if (!nb) return BPGPU_OK;
-  if (!a.states_in || !a.gadget_label || !a.blindings || !a.proof_points || !a.proof_scalars || (m && (!a.v || !a.v_blinding)) ||
-      (w->ninp && !a.inputs))
+  return w->n == n && w->m == m && w->nchi == nchi;
+}
+// ... and what a prover on a gate program requires of its pointers, whatever the circuit's shape (nb > 0; the label is the caller's)
+int wit_prover_pointers(const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
+  if (!a.states_in || !a.blindings || !a.proof_points || !a.proof_scalars || (w->m && (!a.v || !a.v_blinding)) || (w->ninp && !a.inputs))
     return BPGPU_E_ARG;
   if ((!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr)) return BPGPU_E_ARG;   // exactly one source of s_L, s_R
   if ((!a.aL) != (!a.aR) || (!a.aL) != (!a.aO)) return BPGPU_E_ARG;                                    // the three planes, or none
   return wit_fits(w, nb) ? BPGPU_OK : BPGPU_E_LEN;
+}
+int fs2_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
+  if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
+  if (!wit_program_of(w, c)) return BPGPU_E_ARG;
+  WCK(bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1));
+  if (!nb) return BPGPU_OK;
+  if (!a.gadget_label) return BPGPU_E_ARG;
+  return wit_prover_pointers(w, nb, a);
 }
 struct Fs2Between { const Entered *e; const bpgpu_witness *w; size_t nb; const WitRun *run; void *L2, *R2, *O2; };
 int fs2_between(void *user, const void *chi_dev) {
@@ -357,7 +366,71 @@ int fs2_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, co
   return bpgpu_internal_hip(e.ctx, hipGetLastError(), "two-phase prover launch");
 }
 
+// ---- bpgpu_r1cs_prove_values ----
+using PvIo = bpgpu_internal_pv;
+int pv_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const PvIo &a) {
+  if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
+  if (!wit_program_of(w, c) || w->nchi > 1) return BPGPU_E_ARG;                       // not this circuit's program, or no shape of the call
+  const bool two = w->nchi == 1;
+  if (!two && w->n1 != w->n) return BPGPU_E_ARG;
+  WCK(two ? bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1) : bpgpu_internal_prove_fs_shape(g, c, nb));
+  WCK(bpgpu_internal_commit_values_shape(nb, w->m));
+  if (!nb) return BPGPU_OK;
+  if (two != (a.gadget_label != nullptr)) return BPGPU_E_ARG;                         // the label goes with the gadget challenge
+  if (bpgpu_internal_shard_world(ctx) > 1) return BPGPU_E_ARG;                        // partial sums cannot be hashed
+  if (!a.ok) return BPGPU_E_ARG;
+  return wit_prover_pointers(w, nb, {a.init_states, a.gadget_label, a.v, a.inputs, a.s_L, a.s_R, a.vector_keys, a.v_blinding, a.blindings,
+                                     a.proof_points, a.proof_scalars, a.wire, a.challenges_out, a.states_out, a.gadget_challenges_out,
+                                     a.a_L_out, a.a_R_out, a.a_O_out});
+}
+// what both forms do between taking the mutex and touching an operand: the shard refusal, and the one-time build of the circuit's
+// row-major view (the one wait of the call) with the check's BPGPU_E_LEN -- before a copy or a launch is enqueued
+int pv_enter(const Entered &e, const bpgpu_circuit *c, size_t nb) {
+  if (e.view.shard_world > 1) return BPGPU_E_ARG;
+  return bpgpu_internal_rows_fit(e.ctx, c, nb);
+}
+// Mutex held, arguments checked, the circuit's row-major view built (pv_enter), nb > 0; every pointer but the label HBM;
+// asynchronous.  The stages are the _locked functions of the calls they replace; between them the chain states
+// after the commitments, the witness planes and the gadget challenge stay in pool memory (or in the caller's buffers, where given).
+int pv_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const PvIo &io) {
+  bpgpu_ctx *ctx = e.ctx;
+  const bool two = w->nchi == 1;
+  const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n;
+  Scratch sc(ctx);
+  Words8 *mid = (Words8 *)sc.take((nb + (two && !io.gadget_challenges_out ? nb : 0) + (io.a_L_out ? 0 : 3 * plane)) * 32);
+  if (!mid) return BPGPU_E_OOM;
+  Words8 *at = mid + nb;
+  void *chi = nullptr, *L = io.a_L_out, *R = io.a_R_out, *O = io.a_O_out;
+  if (two) { chi = io.gadget_challenges_out; if (!chi) { chi = at; at += nb; } }
+  if (!L) { L = at; R = at + plane; O = at + 2 * plane; }
+  WCK(bpgpu_internal_commit_values(ctx, g, nb, m, io.v, io.v_blinding, io.init_states, io.V, io.V_compressed, mid));
+  if (!two) {
+    WCK(synth_locked(e, w, nb, 0, io.v, io.inputs, nullptr, L, R, O));
+    WCK(bpgpu_internal_constraints_satisfied(ctx, c, nb, L, R, O, io.v, nullptr, io.ok, io.first_bad_row, io.first_bad_gate));
+    WCK(bpgpu_internal_prove_fs(ctx, g, c, nb, {mid, L, R, O, io.s_L, io.s_R, io.vector_keys, io.v_blinding, io.blindings, io.proof_points,
+                                                io.proof_scalars, io.wire, io.challenges_out, io.states_out}));
+  } else {
+    // (the phase-2 witness does not exist before the gadget challenge: the check follows the proof)
+    WCK(fs2_locked(e, g, c, w, nb, {mid, io.gadget_label, io.v, io.inputs, io.s_L, io.s_R, io.vector_keys, io.v_blinding, io.blindings,
+                                    io.proof_points, io.proof_scalars, io.wire, io.challenges_out, io.states_out, chi, L, R, O}));
+    WCK(bpgpu_internal_constraints_satisfied(ctx, c, nb, L, R, O, io.v, chi, io.ok, io.first_bad_row, io.first_bad_gate));
+  }
+  {
+    Prof22 prof(ctx);
+    prove_fs_clear_rejected(e.view.st, {nb, (11 + 2 * k) * 64, (5 + k) * 32, 1 + (two ? 14 : 11) * 32 + (2 * k + 2) * 32, (const int32_t *)io.ok,
+                                        (uint8_t *)io.proof_points, (uint8_t *)io.proof_scalars, (uint8_t *)io.challenges_out,
+                                        (uint8_t *)io.states_out, (uint8_t *)io.wire});
+  }
+  return bpgpu_internal_hip(ctx, hipGetLastError(), "prove-from-values launch");
+}
+
 }  // namespace
+
+size_t bpgpu_internal_witness_inputs(const bpgpu_witness *w) { return w->ninp; }
+int bpgpu_internal_prove_values_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                                      const bpgpu_internal_pv &a) {
+  return pv_check(ctx, g, c, w, nb, a);
+}
 
 int bpgpu_internal_witness_levels(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint32_t *row_ptr, const uint32_t *kind,
                                   const uint32_t *idx, uint32_t *level) {
@@ -696,6 +769,75 @@ int bpgpu_r1cs_prove_fs2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circui
                                     out[3], out[4], out[5], out[6], out[7]}));
     WCK(bpgpu_internal_checked_wait(ctx));
     for (int i = 0; i < 9; i++) if (out_bytes[i]) WHIP(ctx, hipMemcpyAsync(out_host[i], out[i], out_bytes[i], hipMemcpyDeviceToHost, st));
+    WHIP(ctx, hipStreamSynchronize(st));
+    return BPGPU_OK;
+  });
+}
+
+int bpgpu_r1cs_prove_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                                const void *init_states, const uint8_t gadget_label[32], const void *v, const void *v_blinding,
+                                const void *inputs, const void *s_L, const void *s_R, const void *vector_keys, const void *blindings, void *V,
+                                void *V_compressed, void *ok, void *first_bad_row, void *first_bad_gate, void *proof_points, void *proof_scalars,
+                                void *wire, void *challenges_out, void *states_out, void *gadget_challenges_out, void *a_L_out, void *a_R_out,
+                                void *a_O_out) {
+  return no_throw([&]() -> int {
+    const PvIo io{init_states, gadget_label, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, V, V_compressed, ok, first_bad_row,
+                  first_bad_gate, proof_points, proof_scalars, wire, challenges_out, states_out, gadget_challenges_out, a_L_out, a_R_out, a_O_out};
+    WCK(pv_check(ctx, g, c, w, nb, io));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    WCK(pv_enter(e, c, nb));
+    WCK(bpgpu_internal_flag_reset(ctx));   // the flag reports on the most recent *_dev call
+    return pv_locked(e, g, c, w, nb, io);
+  });
+}
+int bpgpu_r1cs_prove_values(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb,
+                            const uint8_t *init_states, const uint8_t gadget_label[32], const uint8_t *v, const uint8_t *v_blinding,
+                            const uint8_t *inputs, const uint8_t *s_L, const uint8_t *s_R, const uint8_t *vector_keys, const uint8_t *blindings,
+                            uint8_t *V, uint8_t *V_compressed, int32_t *ok, int64_t *first_bad_row, int64_t *first_bad_gate,
+                            uint8_t *proof_points, uint8_t *proof_scalars, uint8_t *wire, uint8_t *challenges_out, uint8_t *states_out,
+                            uint8_t *gadget_challenges_out, uint8_t *a_L_out, uint8_t *a_R_out, uint8_t *a_O_out) {
+  return no_throw([&]() -> int {
+    const PvIo a{init_states, gadget_label, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, V, V_compressed, ok, first_bad_row,
+                 first_bad_gate, proof_points, proof_scalars, wire, challenges_out, states_out, gadget_challenges_out, a_L_out, a_R_out, a_O_out};
+    WCK(pv_check(ctx, g, c, w, nb, a));
+    if (!nb) return BPGPU_OK;
+    Entered e(ctx);
+    WCK(e.enter());
+    WCK(pv_enter(e, c, nb));
+    Scratch sc(ctx);
+    const bool two = w->nchi == 1;
+    const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n * 32;
+    // staging: the operands in the header's order (an absent one, of zero bytes, gets a null device pointer), then the results -- the
+    // optional ones downloaded only when asked for, every part 256-byte aligned (the verdict words and the wire form are no
+    // multiples of 32 bytes).  What the provers send is a few scalars each; the planes never cross the bus unless asked for.
+    const void *in_host[8] = {a.init_states, a.v, a.v_blinding, a.inputs, a.s_L, a.s_R, a.vector_keys, a.blindings};
+    const size_t in_bytes[8] = {nb * 32, nb * m * 32, nb * m * 32, 2 * nb * w->ninp * 32, a.s_L ? plane : 0, a.s_R ? plane : 0,
+                                a.vector_keys ? nb * (two ? 64 : 32) : 0, nb * (two ? 11 : 8) * 32};
+    void *out_host[14] = {a.V, a.V_compressed, a.ok, a.first_bad_row, a.first_bad_gate, a.proof_points, a.proof_scalars, a.wire, a.challenges_out,
+                          a.states_out, two ? a.gadget_challenges_out : nullptr, a.a_L_out, a.a_R_out, a.a_O_out};
+    const size_t out_all[14] = {nb * m * 64, nb * m * 32, nb * 4, nb * 8, nb * 8, nb * (11 + 2 * k) * 64, nb * 5 * 32,
+                                nb * (1 + (two ? 14 : 11) * 32 + (2 * k + 2) * 32), nb * (5 + k) * 32, nb * 32, nb * 32, plane, plane, plane};
+    size_t out_bytes[14], total = 0;
+    for (size_t b : in_bytes) total += up256(b);
+    for (int i = 0; i < 14; i++) { out_bytes[i] = out_host[i] ? out_all[i] : 0; total += up256(out_bytes[i]); }
+    uint8_t *stage = (uint8_t *)sc.take(total);
+    if (!stage) return BPGPU_E_OOM;
+    uint8_t *in[8], *out[14], *at = stage;
+    for (int i = 0; i < 8; i++) { in[i] = in_bytes[i] ? at : nullptr; at += up256(in_bytes[i]); }
+    for (int i = 0; i < 14; i++) { out[i] = out_bytes[i] ? at : nullptr; at += up256(out_bytes[i]); }
+    hipStream_t st = e.view.st;
+    WCK(bpgpu_internal_flag_reset(ctx));
+    for (int i = 0; i < 8; i++) if (in_bytes[i]) WHIP(ctx, hipMemcpyAsync(in[i], in_host[i], in_bytes[i], hipMemcpyHostToDevice, st));
+    const int rc = pv_locked(e, g, c, w, nb, {in[0], a.gadget_label, in[1], in[2], in[3], in[4], in[5], in[6], in[7], out[0], out[1], out[2], out[3],
+                                              out[4], out[5], out[6], out[7], out[8], out[9], out[10], out[11], out[12], out[13]});
+    if (rc != BPGPU_OK) {      // no copy from the caller's memory is left in flight behind an early return
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    WCK(bpgpu_internal_checked_wait(ctx));
+    for (int i = 0; i < 14; i++) if (out_bytes[i]) WHIP(ctx, hipMemcpyAsync(out_host[i], out[i], out_bytes[i], hipMemcpyDeviceToHost, st));
     WHIP(ctx, hipStreamSynchronize(st));
     return BPGPU_OK;
   });

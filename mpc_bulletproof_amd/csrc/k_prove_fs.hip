@@ -149,4 +149,34 @@ void prove_fs_assemble(hipStream_t st, const ProveFsAssemble &a) {
   hipLaunchKernelGGL(k_pfs_assemble, dim3((tot + 255) / 256), dim3(256), 0, st, a);
 }
 
+// bpgpu_r1cs_prove_values: a prover whose witness failed the check (ok[p] == 0) ships nothing -- its rows of proof_points,
+// proof_scalars, wire, challenges_out and states_out become zero bytes; an accepted prover's rows are not touched.  A thread per 16
+// bytes of a prover's rows (per * nb threads; every store lies inside row p < nb of its array).  The wire rows are of odd length and
+// start at any byte: those are cleared bytewise.
+__global__ void __launch_bounds__(256) k_pfs_clear_rejected(ProveFsClear o) {
+  const size_t c_pts = o.b_points / 16, c_sc = c_pts + 10, c_ch = c_sc + (o.challenges_out ? o.b_chal / 16 : 0),
+               c_st = c_ch + (o.states_out ? 2 : 0), per = c_st + (o.wire ? (o.b_wire + 15) / 16 : 0);
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= o.nb * per) return;
+  const size_t p = t / per, s = t - p * per;
+  if (o.ok[p] != 0) return;
+  if (s >= c_st) {
+    const size_t lo = (s - c_st) * 16, hi = lo + 16 < o.b_wire ? lo + 16 : o.b_wire;
+    uint8_t *row = o.wire + p * o.b_wire;
+    for (size_t i = lo; i < hi; i++) row[i] = 0;
+    return;
+  }
+  uint32_t *dst;
+  if (s < c_pts) dst = (uint32_t *)(o.proof_points + p * o.b_points) + 4 * s;
+  else if (s < c_sc) dst = (uint32_t *)(o.proof_scalars + p * 160) + 4 * (s - c_pts);
+  else if (s < c_ch) dst = (uint32_t *)(o.challenges_out + p * o.b_chal) + 4 * (s - c_sc);
+  else dst = (uint32_t *)(o.states_out + p * 32) + 4 * (s - c_ch);
+  dst[0] = 0u; dst[1] = 0u; dst[2] = 0u; dst[3] = 0u;
+}
+void prove_fs_clear_rejected(hipStream_t st, const ProveFsClear &a) {
+  if (!a.nb) return;
+  const size_t per = a.b_points / 16 + 10 + (a.challenges_out ? a.b_chal / 16 : 0) + (a.states_out ? 2 : 0) + (a.wire ? (a.b_wire + 15) / 16 : 0);
+  hipLaunchKernelGGL(k_pfs_clear_rejected, dim3((a.nb * per + 255) / 256), dim3(256), 0, st, a);
+}
+
 }  // namespace bpk

@@ -473,6 +473,15 @@ struct ProveFsAssemble {
   const Words8 *A2 = nullptr;   // two phases: nb x 3 points A_I2 A_O2 S2 (nullptr: the identity, wire version 0)
 };
 void prove_fs_assemble(hipStream_t st, const ProveFsAssemble &a);
+// the rows of the provers with ok[p] == 0 cleared to zero bytes (bpgpu_r1cs_prove_values: a rejected prover ships nothing).  Per prover:
+// proof_points b_points bytes (a multiple of 64), proof_scalars 160, and the optional challenges_out b_chal (a multiple of 32),
+// states_out 32 and wire b_wire (any length); all but wire 4-byte aligned
+struct ProveFsClear {
+  size_t nb, b_points, b_chal, b_wire;
+  const int32_t *ok;
+  uint8_t *proof_points, *proof_scalars, *challenges_out, *states_out, *wire;
+};
+void prove_fs_clear_rejected(hipStream_t st, const ProveFsClear &a);
 
 // ---- two-party prover, one party's local arithmetic (k_mpc.hip): 3 nb virtual provers v = 3 p + k (k = 0 share, 1 MAC, 2 public
 // modifier); triples [p][j][x, y, z][k][i], masked [p][j][d, e][k][i], opened [p][j][d, e][i] (plain canonical words)

@@ -1,4 +1,5 @@
 """ctypes binding of libbpgpu.so (include/bpgpu.h).  Byte-level, no torch types."""
+import collections
 import ctypes as C
 import os
 
@@ -179,6 +180,31 @@ def witness_gate_levels(n, n1, nchi, op, row_ptr, kind, idx):
     if rc:
         raise BpGpuError(rc, _lib.bpgpu_strerror(rc).decode())
     return list(out)[:n]
+
+
+ProveValues = collections.namedtuple("ProveValues", "ok first_bad_row first_bad_gate V V_compressed points scalars wire challenges states "
+                                                    "chi planes")
+
+
+def _prove_values_host(call, nb, n, m, lab, init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness):
+    """the host form's buffers around `call(nb, operands..., results...)`: bpgpu_r1cs_prove_values, or the pool's -> ProveValues (chi
+    None for a one-phase circuit, wire and planes None unless asked for)"""
+    two = lab is not None
+    k = max(n - 1, 0).bit_length()
+    nvar, plen = 11 + 2 * k, 1 + (14 if two else 11) * 32 + (2 * k + 2) * 32
+    ok, row, gate = (C.c_int32 * max(nb, 1))(), (C.c_int64 * max(nb, 1))(), (C.c_int64 * max(nb, 1))()
+    V, Vc = _out(64 * nb * m), _out(32 * nb * m)
+    pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
+    chi = _out(32 * nb) if two else None
+    wire = _out(nb * plen) if want_wire else None
+    planes = [_out(32 * nb * n) if want_witness else None for _ in range(3)]
+    opt = lambda b: b if b is None or isinstance(b, C.c_void_p) else _buf(b)     # noqa: E731
+    call(nb, opt(init_states), lab, opt(v), opt(v_blinding), opt(inputs), opt(s_L), opt(s_R), opt(vector_keys), opt(blindings), V, Vc, ok, row,
+         gate, pts, sc, wire, ch, so, chi, *planes)
+    return ProveValues(list(ok)[:nb], list(row)[:nb], list(gate)[:nb], bytes(V)[:64 * nb * m], bytes(Vc)[:32 * nb * m],
+                       bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
+                       bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb] if two else None,
+                       tuple(bytes(p)[:32 * nb * n] for p in planes) if want_witness else None)
 
 
 class BpGpu:
@@ -770,6 +796,26 @@ class BpGpu:
                                                d_v_blinding, d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out, d_chi, d_a_L,
                                                d_a_R, d_a_O))
 
+    def r1cs_prove_values(self, gens, circuit, w, nb, n, m, *, init_states, blindings, v=None, v_blinding=None, inputs=None,
+                          gadget_label=None, s_L=None, s_R=None, vector_keys=None, want_wire=True, want_witness=False, dev=False,
+                          d_out=None):
+        """Commitments, verdicts and proofs of nb provers from their committed values in one call (bpgpu_r1cs_prove_values): the stages
+        commit_values -> witness synthesis -> constraints_satisfied -> prove_fs (gadget_label None: a numeric circuit, blindings
+        nb x 8), or commit_values -> the prove_fs2 chain -> constraints_satisfied (a label: a two-phase circuit, blindings nb x 11),
+        resident in between -> ProveValues; the proof rows of a prover with ok == 0 are zero bytes.  Operands are bytes, or c_void_p
+        of page-locked memory.  dev=True: every operand a bpgpu_malloc pointer and d_out a dict of device pointers under ProveValues'
+        field names (a_L, a_R, a_O for the planes; ok, points and scalars required): asynchronous, nothing is returned"""
+        lab = None if gadget_label is None else _buf((gadget_label + bytes(32))[:32])
+        if dev:
+            o = lambda name: d_out.get(name)     # noqa: E731
+            self._ck(_lib.bpgpu_r1cs_prove_values_dev(self.ctx, gens, circuit, w, nb, init_states, lab, v, v_blinding, inputs, s_L, s_R,
+                                                      vector_keys, blindings, o("V"), o("V_compressed"), o("ok"), o("first_bad_row"),
+                                                      o("first_bad_gate"), o("points"), o("scalars"), o("wire"), o("challenges"), o("states"),
+                                                      o("chi"), o("a_L"), o("a_R"), o("a_O")))
+            return None
+        return _prove_values_host(lambda *a: self._ck(_lib.bpgpu_r1cs_prove_values(self.ctx, gens, circuit, w, *a)), nb, n, m, lab, init_states,
+                                  v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness)
+
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
 
@@ -1216,6 +1262,26 @@ class BpPool:
     def circuit_get(self, h, slot):
         return _lib.bpgpu_pool_circuit_get(h, slot)
 
+    def circuit_create_param(self, q, nchi, row_ptr, kind, idx, coeff, n_mul, m):
+        """BpGpu.circuit_create_param per distinct device: a handle that r1cs_prove_values takes (the other pool calls refuse it)"""
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_pool_circuit_create_param(self.pool, q, nchi, _u32s(row_ptr), _u32s(kind), _u32s(idx), _buf(coeff), n_mul, m,
+                                                      C.byref(h)))
+        return h
+
+    def witness_create(self, n, n1, m, nchi, op, arg, row_ptr, kind, idx, coeff):
+        """BpGpu.witness_create per distinct device"""
+        h = C.c_void_p()
+        self._ck(_lib.bpgpu_pool_witness_create(self.pool, n, n1, m, nchi, _buf(bytes(op)), _u32s(arg), _u32s(row_ptr), _u32s(kind), _u32s(idx),
+                                                _buf(coeff), C.byref(h)))
+        return h
+
+    def witness_destroy(self, h):
+        _lib.bpgpu_pool_witness_destroy(self.pool, h)
+
+    def witness_get(self, h, slot):
+        return _lib.bpgpu_pool_witness_get(h, slot)
+
     # ---- the four calls: operands for the whole queue as bytes, or c_void_p of page-locked memory
     @staticmethod
     def _wrap(b):
@@ -1257,3 +1323,10 @@ class BpPool:
                                                opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so))
         return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
                 bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
+
+    def r1cs_prove_values(self, gens, circuit, w, nb, n, m, *, init_states, blindings, v=None, v_blinding=None, inputs=None,
+                          gadget_label=None, s_L=None, s_R=None, vector_keys=None, want_wire=True, want_witness=False):
+        """BpGpu.r1cs_prove_values with the provers dealt over the slots (pool handles): the same operands -> ProveValues"""
+        lab = None if gadget_label is None else _buf((gadget_label + bytes(32))[:32])
+        return _prove_values_host(lambda *a: self._ck(_lib.bpgpu_pool_r1cs_prove_values(self.pool, gens, circuit, w, *a)), nb, n, m, lab,
+                                  init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness)
