@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "bpgpu_internal.h"
 #include "fe29.cuh"
+#include "queue_plan.h"
 
 using namespace bpk;
 
@@ -42,7 +43,7 @@ enum WsSlot : int {
   WS_VFRES,         // verifier: generator-half sums; combined check: the two halves
   WS_MSM,           // window-parallel scratch, fixed-base chunk partials (msm_gens_dev), second Straus scratch, msm_core_locked's terms
   WS_STRAUS,        // Straus tables (straus_ws)
-  WS_PIP,           // bucket-method and combined-check pipelines (k_pip.hip, k_pip2.hip, k_mixed.hip)
+  WS_PIP,           // bucket-method and combined-check pipelines (k_pip.hip, k_pip2.hip; k_mixed.hip: mixed_run_locked)
   WS_VAUX,          // wire format / decode bits (verify_wire_locked, wire_front_locked); combined check: final sum
   WS_FS_STAGE,      // transcript host forms: challenges out, wire verdicts; bpgpu_ipp_run_fs: transcript states
   WS_FS_CH,         // device transcript: challenges; bpgpu_ipp_run_fs: L, R
@@ -54,10 +55,10 @@ enum WsSlot : int {
   WS_MSM2,          // fixed-base chunk partials under a caller that holds WS_MSM (verifier); two-party masked and opened values
   WS_WP_PTS,        // msm_wp_batch: padded points
   WS_WP_SC,         // msm_wp_batch: padded scalars
-  WS_SCREEN_PART,   // screened calls: one partial point per check; mixed combined call: the checks' partials
-  WS_SCREEN_FLAG,   // screened calls: one input flag per check; mixed combined call: the partials' sum flag
+  WS_SCREEN_PART,   // screened calls (screen_locked): one partial point per check; queue_combined_locked: the checks' partials
+  WS_SCREEN_FLAG,   // screened calls (screen_locked): one input flag per check; queue_combined_locked: the partials' sum flag
   WS_WP_RED,        // msm_wp_batch: scratch of the reduced instances
-  WS_MIXED_STAGE,   // mixed host forms: every group's operands
+  WS_MIXED_STAGE,   // mixed host forms (queue_stage_locked): every group's operands and verdicts
   WS_IPPV_STAGE,    // bpgpu_ipp_verify_*: the host forms' operands and results
   WS_IPPV_HDR,      // ... per-proof header values, reject marks
   WS_IPPV_SC,       // ... MSM scalars: dense instances, or the generator half over resident generators
@@ -70,7 +71,7 @@ enum WsSlot : int {
   WS_PFS_PTS,       // ... A_I A_O S and T_1..T_6: sums and boundary bytes
   WS_PFS_SCHED,     // ... the prover's transcript schedule (bpgpu_ctx::psched[0])
   WS_PFS_SCHED2,    // bpgpu_r1cs_prove_fs2_begin / _finish: the two-phase schedule (bpgpu_ctx::psched[1])
-  WS_WIRE_SCHED,    // bpgpu_r1cs_verify_mixed_wire_*: the transcript schedules of a call's groups (on the calling context; the lanes read it)
+  WS_WIRE_SCHED,    // wire_schedules_locked (WireQueue::prepare): the transcript schedules of a call's groups (on the calling context; the lanes read it)
   WS_COUNT
 };
 
@@ -2566,76 +2567,35 @@ int bpgpu_r1cs_verify_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_
 
 /* ---------------------------------------------------------------- mixed queues: proofs of several circuits in one call
  * The groups' proofs are concatenated (group after group) and cut into checks; a check is a list of runs ("segments") of one group's
- * consecutive proofs.  Each check is ONE ragged combined check (k_mixed.hip); the screened call re-verifies a failing check per
- * proof, segment by segment, on each segment's own circuit. */
+ * consecutive proofs (queue_plan.h: mixed_plan, host arithmetic with a CPU test of its own).  Each check is ONE ragged combined check
+ * (k_mixed.hip); the screened call re-verifies a failing check per proof, segment by segment, on each segment's own circuit.
+ * A queue holds decoded operands (bpgpu_verify_group) or wire bytes (bpgpu_wire_group).  The plan, the two drivers, the host staging
+ * and the entry helpers are stated once, over a queue kind (DecodedQueue, WireQueue) that says what differs:
+ *   validate(screened)                 shape checks of every group before anything is launched (the codes of the one-circuit calls;
+ *                                      screened: ok[] must be given); leaves what the plan reads in shape[]
+ *   prepare(ctx)                       once per call on the calling context, when the plan is not empty and before any lane forks
+ *   front(ln, segs, nseg, bit, in)     the segment table of ONE check on lane ln; what it launches ORs `bit` into ln's input flag
+ *   per_proof(ln, seg)                 the per-proof path of one segment on lane ln: verdicts into the group's ok[] (HBM)
+ *   fields(x, d, f)                    host forms: the operand fields of group x, and where their device addresses go in its copy d */
+using bpqueue::MixCheck;
+using bpqueue::MixSeg;
+using bpqueue::QueueShape;
 namespace {
-struct MixSeg { size_t gi, lo, cnt; };
-struct MixCheck { size_t first, nseg; };   // a range of the plan's segment list
+struct StageField { const void *src; const void **dst; size_t bytes; };
 }
-// shape checks of every group before anything is launched (the codes of the one-circuit calls); screened: ok[] must be given
-static int mixed_validate(const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, bool screened) {
-  if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
-  for (size_t i = 0; i < ngroups; i++) {
-    const bpgpu_verify_group &x = G[i];
-    const bpgpu_circuit *c = x.circuit;
-    if (!c) return BPGPU_E_ARG;
-    if (x.nb && (!x.points || !x.scalars || !x.challenges || !x.rho || (screened && !x.ok))) return BPGPU_E_ARG;
-    if ((c->nchi != 0) != (x.gadget_challenges != nullptr)) return BPGPU_E_ARG;
-    if (x.k >= 32) return BPGPU_E_LEN;
-    CK(verify_shape(c, g, x.n1, x.k));
-  }
-  return BPGPU_OK;
-}
-// cut the concatenated queue into checks of at most max_proofs proofs, max_points proof points (a single proof may exceed it) and
-// BPGPU_MIXED_MAX_SEGMENTS segments
-static void mixed_plan(const bpgpu_verify_group *G, size_t ngroups, size_t max_proofs, size_t max_points, std::vector<MixSeg> &segs,
-                       std::vector<MixCheck> &checks) {
-  size_t cp = 0, cpts = 0;
-  auto close = [&]() { if (!checks.empty() && checks.back().nseg) { checks.push_back(MixCheck{segs.size(), 0}); } cp = cpts = 0; };
-  checks.push_back(MixCheck{0, 0});
-  for (size_t gi = 0; gi < ngroups; gi++) {
-    const size_t nvar = verify_nvar(G[gi].circuit, G[gi].k);
-    size_t lo = 0;
-    while (lo < G[gi].nb) {
-      if (checks.back().nseg == BPGPU_MIXED_MAX_SEGMENTS) close();
-      size_t room = max_proofs - cp, fit = cpts < max_points ? (max_points - cpts) / nvar : 0;
-      if (fit < room) room = fit;
-      if (!room) {
-        if (cp) { close(); continue; }
-        room = 1;      // one proof larger than the point budget: a check of its own
-      }
-      const size_t cnt = G[gi].nb - lo < room ? G[gi].nb - lo : room;
-      segs.push_back(MixSeg{gi, lo, cnt});
-      checks.back().nseg++;
-      cp += cnt; cpts += cnt * nvar; lo += cnt;
-      if (cp >= max_proofs || cpts >= max_points) close();
-    }
-  }
-  if (!checks.back().nseg) checks.pop_back();
+// a segment's entry of a check's table: cnt proofs of circuit c from the given operands
+static MixSegIn mixed_seg_in(const bpgpu_ctx *ln, const bpgpu_circuit *c, size_t cnt, size_t n1, size_t k, const Words8 *points,
+                             const Words8 *proof_scalars, const Words8 *challenges, const Words8 *chi, const Words8 *rho) {
+  MixSegIn v;
+  v.circ = circuit_dev(c);
+  v.d = VerifyDims{cnt, n1, c->n, (size_t)1 << k, k, c->m, c->nchi ? chi : nullptr, (size_t)ln->opt[BPGPU_OPT_VS_LARGE_MIN]};
+  v.nvar = verify_nvar(c, k); v.nchi = c->nchi;
+  v.points = points; v.proof_scalars = proof_scalars; v.challenges = challenges;
+  v.rho = rho;
+  return v;
 }
 // ONE ragged combined check on `ln`'s stream: partial_xy (HBM) = sum over the check's proofs of rho_p * mega_check_p.  The caller
 // resets ln's input flag; zero_rho (optional) is raised for a zero weight.
-static int mixed_run_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const MixSegIn *in, size_t nseg, void *partial_xy, int *zero_rho);
-static int mixed_check_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group *G, const MixSeg *segs, size_t nseg,
-                              void *partial_xy, int *zero_rho) {
-  MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
-  for (size_t s = 0; s < nseg; s++) {
-    const bpgpu_verify_group &x = G[segs[s].gi];
-    const bpgpu_circuit *c = x.circuit;
-    const size_t lo = segs[s].lo, nvar = verify_nvar(x.circuit, x.k), np = (size_t)1 << x.k;
-    MixSegIn &v = in[s];
-    v.circ = circuit_dev(c);
-    v.d = VerifyDims{segs[s].cnt, x.n1, c->n, np, x.k, c->m,
-                     c->nchi ? (const Words8 *)x.gadget_challenges + lo * c->nchi : nullptr, (size_t)ln->opt[BPGPU_OPT_VS_LARGE_MIN]};
-    v.nvar = nvar; v.nchi = c->nchi;
-    v.points = (const Words8 *)x.points + lo * nvar * 2;
-    v.proof_scalars = (const Words8 *)x.scalars + lo * 5;
-    v.challenges = (const Words8 *)x.challenges + lo * (6 + x.k);
-    v.rho = (const Words8 *)x.rho + lo;
-  }
-  return mixed_run_locked(ln, g, in, nseg, partial_xy, zero_rho);
-}
-// ... on operands already laid out as segments (the wire calls decode theirs into the lane's workspace)
 static int mixed_run_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const MixSegIn *in, size_t nseg, void *partial_xy, int *zero_rho) {
   void *scr;
   CK(ws_get(ln, WS_PIP, verify_mixed_scratch_bytes(in, nseg, g->c), &scr));
@@ -2643,27 +2603,8 @@ static int mixed_run_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const MixSegIn *
   verify_mixed(ln->st, a);
   return launch_ok(ln);
 }
-static int mixed_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, void *partial_xy) try {
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<MixSeg> segs;
-  std::vector<MixCheck> checks;
-  mixed_plan(G, ngroups, (size_t)-1, (size_t)-1, segs, checks);   // (checks cut at the segment cap only; each picks its own MSM route)
-  CK(flag_reset(ctx));
-  if (checks.empty()) { HIPCK(ctx, hipMemsetAsync(partial_xy, 0, 64, ctx->st)); return BPGPU_OK; }
-  void *dpart = partial_xy;
-  if (checks.size() > 1) CK(ws_get(ctx, WS_SCREEN_PART, checks.size() * 64, &dpart));
-  for (size_t ci = 0; ci < checks.size(); ci++)
-    CK(mixed_check_locked(ctx, g, G, segs.data() + checks[ci].first, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
-  int *dbad2;
-  if (checks.size() > 1) {       // the checks' partials are valid points: their sum cannot raise the flag (a separate one all the same)
-    CK(ws_get(ctx, WS_SCREEN_FLAG, 256, (void **)&dbad2));
-    points_sum(ctx->st, (const Words8 *)dpart, checks.size(), (Words8 *)partial_xy, dbad2);
-  }
-  mixed_poison(ctx->st, ctx->d_flag, (Words8 *)partial_xy);
-  return launch_ok(ctx);
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
-}
+
+/* ---- decoded operands (bpgpu_r1cs_verify_mixed_*): the front is pointer arithmetic on the groups' arrays ---- */
 // the per-proof path for one segment on lane ln: bpgpu_r1cs_verify_batch(_param)'s verdicts into the group's ok[] (HBM)
 static int mixed_per_proof_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgpu_verify_group &x, size_t lo, size_t cnt) {
   const bpgpu_circuit *c = x.circuit;
@@ -2681,136 +2622,59 @@ static int mixed_per_proof_locked(bpgpu_ctx *ln, const bpgpu_gens *g, const bpgp
   if (dchibad) and_not(ln->st, ok, (const int32_t *)dchibad, cnt);
   return launch_ok(ln);
 }
-static int mixed_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *G, size_t ngroups, size_t *fallback_batches) try {
-  if (fallback_batches) *fallback_batches = 0;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<MixSeg> segs;
-  std::vector<MixCheck> checks;
-  // proofs per check: BPGPU_OPT_SCREEN_BATCH, and at most 2^16 proof points (the one-instance bucket pipeline of k_pip2.hip)
-  mixed_plan(G, ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, segs, checks);
-  if (checks.empty()) return BPGPU_OK;
-  // a check's flag holds malformed input and zero weights; a failing check takes the per-proof path segment by segment
-  auto check = [&](bpgpu_ctx *ln, size_t ci, void *partial) -> int {
-    CK(flag_reset(ln));
-    return mixed_check_locked(ln, g, G, segs.data() + checks[ci].first, checks[ci].nseg, partial, ln->d_flag);
-  };
-  auto accept = [&](size_t ci) -> int {
-    const MixSeg *sg = segs.data() + checks[ci].first;
-    for (size_t s = 0; s < checks[ci].nseg; s++)
-      if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
-    return BPGPU_OK;
-  };
-  auto fallback = [&](bpgpu_ctx *ln, size_t ci) -> int {
-    const MixSeg *sg = segs.data() + checks[ci].first;
-    for (size_t s = 0; s < checks[ci].nseg; s++) CK(mixed_per_proof_locked(ln, g, G[sg[s].gi], sg[s].lo, sg[s].cnt));
-    return BPGPU_OK;
-  };
-  return screen_locked(ctx, checks.size(), "bpgpu_r1cs_verify_mixed_screened", fallback_batches, check, accept, fallback);
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
-}
-// host forms: every group's operands go up once (one staging buffer), the device form runs, the verdicts come back
-static int mixed_stage_locked(bpgpu_ctx *ctx, const bpgpu_verify_group *G, size_t ngroups, std::vector<bpgpu_verify_group> &D) {
-  size_t tot = 0;
-  auto sizes = [](const bpgpu_verify_group &x, size_t *b) {
-    const size_t nvar = verify_nvar(x.circuit, x.k);
-    b[0] = x.nb * nvar * 64; b[1] = x.nb * 160; b[2] = x.nb * (6 + x.k) * 32; b[3] = x.gadget_challenges ? x.nb * x.circuit->nchi * 32 : 0;
-    b[4] = x.nb * 32; b[5] = x.nb * 4;
-  };
-  for (size_t i = 0; i < ngroups; i++) { size_t b[6]; sizes(G[i], b); for (size_t j : b) tot += (j + 255) / 256 * 256; }
-  void *base;
-  CK(ws_get(ctx, WS_MIXED_STAGE, tot, &base));
-  uint8_t *q = (uint8_t *)base;
-  D.assign(G, G + ngroups);
-  for (size_t i = 0; i < ngroups; i++) {
-    size_t b[6];
-    sizes(G[i], b);
-    const void *src[5] = {G[i].points, G[i].scalars, G[i].challenges, G[i].gadget_challenges, G[i].rho};
-    const void **dst[5] = {&D[i].points, &D[i].scalars, &D[i].challenges, &D[i].gadget_challenges, &D[i].rho};
-    for (int j = 0; j < 5; j++) {
-      if (src[j]) { CK(h2d(ctx, q, src[j], b[j])); *dst[j] = q; }
-      q += (b[j] + 255) / 256 * 256;
+namespace {
+struct DecodedQueue {
+  using Group = bpgpu_verify_group;
+  static constexpr const char *screened_name = "bpgpu_r1cs_verify_mixed_screened";
+  static constexpr size_t NFIELDS = 5;
+  const bpgpu_gens *g;
+  const Group *G;
+  size_t ngroups;
+  QueueShape shape[BPGPU_MIXED_MAX_GROUPS];
+  int validate(bool screened) {
+    if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
+    for (size_t i = 0; i < ngroups; i++) {
+      const Group &x = G[i];
+      const bpgpu_circuit *c = x.circuit;
+      if (!c) return BPGPU_E_ARG;
+      if (x.nb && (!x.points || !x.scalars || !x.challenges || !x.rho || (screened && !x.ok))) return BPGPU_E_ARG;
+      if ((c->nchi != 0) != (x.gadget_challenges != nullptr)) return BPGPU_E_ARG;
+      if (x.k >= 32) return BPGPU_E_LEN;
+      CK(verify_shape(c, g, x.n1, x.k));
+      shape[i] = QueueShape{x.nb, verify_nvar(c, x.k)};
     }
-    D[i].ok = q;
-    q += (b[5] + 255) / 256 * 256;
+    return BPGPU_OK;
   }
-  return BPGPU_OK;
-}
-int bpgpu_r1cs_verify_mixed_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
-                                         void *partial_xy_dev) {
-  if (!ctx || !partial_xy_dev) return BPGPU_E_ARG;
-  CK(mixed_validate(g, groups, ngroups, false));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return mixed_combined_locked(ctx, g, groups, ngroups, partial_xy_dev);
-}
-int bpgpu_r1cs_verify_mixed_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
-                                     uint8_t partial_xy[64]) try {
-  if (!ctx || !partial_xy) return BPGPU_E_ARG;
-  CK(mixed_validate(g, groups, ngroups, false));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_verify_group> D;
-  CK(mixed_stage_locked(ctx, groups, ngroups, D));
-  void *dout;
-  CK(ws_get(ctx, WS_ARG4, 64, &dout));
-  CK(mixed_combined_locked(ctx, g, D.data(), ngroups, dout));
-  CK(d2h(ctx, partial_xy, dout, 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
-}
-int bpgpu_r1cs_verify_mixed_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
-                                         size_t *fallback_batches) {
-  if (fallback_batches) *fallback_batches = 0;
-  if (!ctx) return BPGPU_E_ARG;
-  CK(mixed_validate(g, groups, ngroups, true));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return mixed_screened_locked(ctx, g, groups, ngroups, fallback_batches);
-}
-int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
-                                     size_t *fallback_batches) try {
-  if (fallback_batches) *fallback_batches = 0;
-  if (!ctx) return BPGPU_E_ARG;
-  CK(mixed_validate(g, groups, ngroups, true));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_verify_group> D;
-  CK(mixed_stage_locked(ctx, groups, ngroups, D));
-  CK(mixed_screened_locked(ctx, g, D.data(), ngroups, fallback_batches));
-  for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
+  int prepare(bpgpu_ctx *) { return BPGPU_OK; }
+  int front(bpgpu_ctx *ln, const MixSeg *segs, size_t nseg, int, MixSegIn *in) const {
+    for (size_t s = 0; s < nseg; s++) {
+      const Group &x = G[segs[s].gi];
+      const size_t lo = segs[s].lo, nvar = shape[segs[s].gi].nvar;
+      in[s] = mixed_seg_in(ln, x.circuit, segs[s].cnt, x.n1, x.k, (const Words8 *)x.points + lo * nvar * 2, (const Words8 *)x.scalars + lo * 5,
+                           (const Words8 *)x.challenges + lo * (6 + x.k), (const Words8 *)x.gadget_challenges + lo * x.circuit->nchi,
+                           (const Words8 *)x.rho + lo);
+    }
+    return BPGPU_OK;
+  }
+  int per_proof(bpgpu_ctx *ln, const MixSeg &sg) const { return mixed_per_proof_locked(ln, g, G[sg.gi], sg.lo, sg.cnt); }
+  static void fields(const Group &x, Group &d, StageField *f) {
+    f[0] = StageField{x.points, &d.points, x.nb * verify_nvar(x.circuit, x.k) * 64};
+    f[1] = StageField{x.scalars, &d.scalars, x.nb * 160};
+    f[2] = StageField{x.challenges, &d.challenges, x.nb * (6 + x.k) * 32};
+    f[3] = StageField{x.gadget_challenges, &d.gadget_challenges, x.gadget_challenges ? x.nb * x.circuit->nchi * 32 : 0};
+    f[4] = StageField{x.rho, &d.rho, x.nb * 32};
+  }
+};
 }
 
-/* ---------------------------------------------------------------- mixed queues of WIRE-format proofs, transcript on the device
- * The plan is the mixed queue's (mixed_plan).  Per check a ragged front decodes the segments into the lane's workspace in four
- * launches -- unpack, ONE decompression over the check's points, the transcript replay, a fold of the reject bits -- in the layouts
- * of MixSegIn, and the ragged combined check runs on them unchanged.  The square-root tables and the groups' transcript schedules
- * are built / uploaded once per call on the calling context, before the lanes fork; the lanes only read them. */
+/* ---- WIRE-format proofs, transcript on the device (bpgpu_r1cs_verify_mixed_wire_*) ----
+ * Per check a ragged front decodes the segments into the lane's workspace in four launches -- unpack, ONE decompression over the
+ * check's points, the transcript replay, a fold of the reject bits -- in the layouts of MixSegIn, and the ragged combined check runs
+ * on them unchanged.  The square-root tables and the groups' transcript schedules are built / uploaded once per call on the calling
+ * context, before the lanes fork; the lanes only read them. */
 namespace {
 struct WireGroupDims { int two_phase; size_t k; };
 struct WireSched { const TrStep *steps; int nsteps; };
-}
-static int wire_validate(const bpgpu_gens *g, const bpgpu_wire_group *G, size_t ngroups, bool screened, WireGroupDims *dims) {
-  if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
-  for (size_t i = 0; i < ngroups; i++) {
-    const bpgpu_wire_group &x = G[i];
-    const bpgpu_circuit *c = x.circuit;
-    if (!c) return BPGPU_E_ARG;
-    if (x.nb && (!x.proofs || !x.init_states || !x.rho || (c->m && !x.commitments) || (screened && !x.ok))) return BPGPU_E_ARG;
-    if (c->nchi > 1 || (c->nchi != 0) != (x.gadget_label != nullptr)) return BPGPU_E_ARG;
-    if (!wire_dims(x.proof_len, &dims[i].two_phase, &dims[i].k)) return BPGPU_E_LEN;
-    CK(verify_shape(c, g, x.n1, dims[i].k));
-  }
-  return BPGPU_OK;
-}
-// what mixed_plan reads of a group
-static void wire_shadow(const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups, std::vector<bpgpu_verify_group> &V) {
-  V.assign(ngroups, bpgpu_verify_group{});
-  for (size_t i = 0; i < ngroups; i++) { V[i].circuit = G[i].circuit; V[i].nb = G[i].nb; V[i].n1 = G[i].n1; V[i].k = dims[i].k; }
 }
 // every non-empty group's schedule, one after the other in WS_WIRE_SCHED of the calling context: ONE upload per call from page-locked
 // staging, no host wait (fs_transcript_locked's one-entry cache would re-upload and wait whenever the shape changes)
@@ -2875,12 +2739,7 @@ static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const Wir
     Words8 *pts = (Words8 *)dxy + pt_off * 2, *sc = (Words8 *)dsc + p_off * 5, *ch = (Words8 *)dch + ch_off, *chi = (Words8 *)dchi + p_off;
     ts[s] = TrSegIn{sched[gi].steps, sched[gi].nsteps, cnt, m, k, c->nchi, (const Words8 *)x.init_states + lo, pts, sc, ch, chi,
                     tr_bad + p_off, x.gadget_label};
-    MixSegIn &v = in[s];
-    v.circ = circuit_dev(c);
-    v.d = VerifyDims{cnt, x.n1, c->n, (size_t)1 << k, k, m, c->nchi ? chi : nullptr, (size_t)ln->opt[BPGPU_OPT_VS_LARGE_MIN]};
-    v.nvar = nvar; v.nchi = c->nchi;
-    v.points = pts; v.proof_scalars = sc; v.challenges = ch;
-    v.rho = (const Words8 *)x.rho + lo;
+    in[s] = mixed_seg_in(ln, c, cnt, x.n1, k, pts, sc, ch, chi, (const Words8 *)x.rho + lo);
     pt_off += cnt * nvar; p_off += cnt; ch_off += cnt * (6 + k);
   }
   { ProfScope ps(ln, 23, ln->st);
@@ -2893,156 +2752,210 @@ static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const Wir
     wire_fold(ln->st, ws, nseg, fmt_ok, dec_ok, tr_bad, (int32_t *)dbad, ln->d_flag, bit); }
   return launch_ok(ln);
 }
-static int wire_combined_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups,
-                                void *partial_xy) try {
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_verify_group> V;
+namespace {
+struct WireQueue {
+  using Group = bpgpu_wire_group;
+  static constexpr const char *screened_name = "bpgpu_r1cs_verify_mixed_wire_screened";
+  static constexpr size_t NFIELDS = 4;
+  const bpgpu_gens *g;
+  const Group *G;
+  size_t ngroups;
+  QueueShape shape[BPGPU_MIXED_MAX_GROUPS];
+  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
+  WireSched sched[BPGPU_MIXED_MAX_GROUPS];
+  const void *sqrt_tab;                      // the calling context's
+  int validate(bool screened) {
+    if (!g || (ngroups && !G) || ngroups > BPGPU_MIXED_MAX_GROUPS) return BPGPU_E_ARG;
+    for (size_t i = 0; i < ngroups; i++) {
+      const Group &x = G[i];
+      const bpgpu_circuit *c = x.circuit;
+      if (!c) return BPGPU_E_ARG;
+      if (x.nb && (!x.proofs || !x.init_states || !x.rho || (c->m && !x.commitments) || (screened && !x.ok))) return BPGPU_E_ARG;
+      if (c->nchi > 1 || (c->nchi != 0) != (x.gadget_label != nullptr)) return BPGPU_E_ARG;
+      if (!wire_dims(x.proof_len, &dims[i].two_phase, &dims[i].k)) return BPGPU_E_LEN;
+      CK(verify_shape(c, g, x.n1, dims[i].k));
+      shape[i] = QueueShape{x.nb, verify_nvar(c, dims[i].k)};
+    }
+    return BPGPU_OK;
+  }
+  int prepare(bpgpu_ctx *ctx) {
+    CK(sqrt_tab_locked(ctx));
+    sqrt_tab = ctx->sqrt_tab;
+    return wire_schedules_locked(ctx, G, dims, ngroups, sched);
+  }
+  // an undecodable proof or an identity at a validated point is malformed input: `bit`
+  int front(bpgpu_ctx *ln, const MixSeg *segs, size_t nseg, int bit, MixSegIn *in) const {
+    return wire_front_locked(ln, G, dims, sched, sqrt_tab, segs, nseg, bit, in);
+  }
+  // decodes the segment again, on its own (the lane's workspace has moved on since the check); it is the rare path and keeps the
+  // one-circuit call's schedule cache
+  int per_proof(bpgpu_ctx *ln, const MixSeg &sg) const {
+    const Group &x = G[sg.gi];
+    const size_t lo = sg.lo, m = x.circuit->m;
+    return verify_wire_locked(ln, g, x.circuit, sg.cnt, x.n1, x.proof_len, (const uint8_t *)x.proofs + lo * x.proof_len,
+                              m ? (const uint8_t *)x.commitments + lo * m * 32 : nullptr, (const uint8_t *)x.init_states + lo * 32,
+                              (int32_t *)x.ok + lo, x.gadget_label, sqrt_tab);
+  }
+  static void fields(const Group &x, Group &d, StageField *f) {
+    f[0] = StageField{x.proofs, &d.proofs, x.nb * x.proof_len};
+    f[1] = StageField{x.commitments, &d.commitments, x.commitments ? x.nb * x.circuit->m * 32 : 0};
+    f[2] = StageField{x.init_states, &d.init_states, x.nb * 32};
+    f[3] = StageField{x.rho, &d.rho, x.nb * 32};
+  }
+};
+}
+
+/* ---- the drivers, the host staging and the entry helpers of both kinds ---- */
+extern "C++" {   // (templates, in the middle of the C ABI)
+// the sum of the checks' points; an empty queue gives the identity
+template <class Kind> static int queue_combined_locked(bpgpu_ctx *ctx, Kind &q, void *partial_xy) {
   std::vector<MixSeg> segs;
   std::vector<MixCheck> checks;
-  wire_shadow(G, dims, ngroups, V);
-  mixed_plan(V.data(), ngroups, (size_t)-1, (size_t)-1, segs, checks);
+  // (checks cut at the segment cap only; each picks its own MSM route)
+  bpqueue::mixed_plan(q.shape, q.ngroups, (size_t)-1, (size_t)-1, BPGPU_MIXED_MAX_SEGMENTS, segs, checks);
   CK(flag_reset(ctx));
   if (checks.empty()) { HIPCK(ctx, hipMemsetAsync(partial_xy, 0, 64, ctx->st)); return BPGPU_OK; }
-  WireSched sched[BPGPU_MIXED_MAX_GROUPS];
-  CK(sqrt_tab_locked(ctx));
-  CK(wire_schedules_locked(ctx, G, dims, ngroups, sched));
+  CK(q.prepare(ctx));
   void *dpart = partial_xy;
   if (checks.size() > 1) CK(ws_get(ctx, WS_SCREEN_PART, checks.size() * 64, &dpart));
   for (size_t ci = 0; ci < checks.size(); ci++) {
     MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
-    // an undecodable proof or an identity at a validated point is malformed input of the combined call: bit 1, as verify_mixed's own
-    CK(wire_front_locked(ctx, G, dims, sched, ctx->sqrt_tab, segs.data() + checks[ci].first, checks[ci].nseg, 1, in));
-    CK(mixed_run_locked(ctx, g, in, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
+    CK(q.front(ctx, segs.data() + checks[ci].first, checks[ci].nseg, 1, in));      // bit 1, as verify_mixed's own malformed input
+    CK(mixed_run_locked(ctx, q.g, in, checks[ci].nseg, (uint8_t *)dpart + 64 * ci, nullptr));
   }
   int *dbad2;
-  if (checks.size() > 1) {
+  if (checks.size() > 1) {       // the checks' partials are valid points: their sum cannot raise the flag (a separate one all the same)
     CK(ws_get(ctx, WS_SCREEN_FLAG, 256, (void **)&dbad2));
     points_sum(ctx->st, (const Words8 *)dpart, checks.size(), (Words8 *)partial_xy, dbad2);
   }
   mixed_poison(ctx->st, ctx->d_flag, (Words8 *)partial_xy);
   return launch_ok(ctx);
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
 }
-static int wire_screened_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups,
-                                size_t *fallback_batches) try {
-  if (fallback_batches) *fallback_batches = 0;
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_verify_group> V;
+// the checks screened over the lanes (screen_locked); a failing check takes the per-proof path segment by segment
+template <class Kind> static int queue_screened_locked(bpgpu_ctx *ctx, Kind &q, size_t *fallback_batches) {
   std::vector<MixSeg> segs;
   std::vector<MixCheck> checks;
-  wire_shadow(G, dims, ngroups, V);
-  mixed_plan(V.data(), ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, segs, checks);
+  // proofs per check: BPGPU_OPT_SCREEN_BATCH, and at most 2^16 proof points (the one-instance bucket pipeline of k_pip2.hip)
+  bpqueue::mixed_plan(q.shape, q.ngroups, (size_t)ctx->opt[BPGPU_OPT_SCREEN_BATCH], (size_t)1 << 16, BPGPU_MIXED_MAX_SEGMENTS, segs, checks);
   if (checks.empty()) return BPGPU_OK;
-  WireSched sched[BPGPU_MIXED_MAX_GROUPS];
-  CK(sqrt_tab_locked(ctx));                          // on ctx->st, before screen_locked forks the lanes from it
-  CK(wire_schedules_locked(ctx, G, dims, ngroups, sched));
-  const void *tab = ctx->sqrt_tab;
+  CK(q.prepare(ctx));                         // on ctx->st, before screen_locked forks the lanes from it
+  // a check's flag holds malformed input (bit 2 from the front) and zero weights
   auto check = [&](bpgpu_ctx *ln, size_t ci, void *partial) -> int {
     MixSegIn in[BPGPU_MIXED_MAX_SEGMENTS];
     CK(flag_reset(ln));
-    CK(wire_front_locked(ln, G, dims, sched, tab, segs.data() + checks[ci].first, checks[ci].nseg, 2, in));
-    return mixed_run_locked(ln, g, in, checks[ci].nseg, partial, ln->d_flag);
+    CK(q.front(ln, segs.data() + checks[ci].first, checks[ci].nseg, 2, in));
+    return mixed_run_locked(ln, q.g, in, checks[ci].nseg, partial, ln->d_flag);
   };
   auto accept = [&](size_t ci) -> int {
     const MixSeg *sg = segs.data() + checks[ci].first;
     for (size_t s = 0; s < checks[ci].nseg; s++)
-      if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
+      if (hipMemsetD32Async((hipDeviceptr_t)((int32_t *)q.G[sg[s].gi].ok + sg[s].lo), 1, sg[s].cnt, ctx->st) != hipSuccess) return BPGPU_E_DEVICE;
     return BPGPU_OK;
   };
-  // the per-proof path decodes its segments again, each on its own (the lane's workspace has moved on since the check); it is
-  // the rare path and keeps the one-circuit call's schedule cache
   auto fallback = [&](bpgpu_ctx *ln, size_t ci) -> int {
     const MixSeg *sg = segs.data() + checks[ci].first;
-    for (size_t s = 0; s < checks[ci].nseg; s++) {
-      const bpgpu_wire_group &x = G[sg[s].gi];
-      const size_t lo = sg[s].lo, m = x.circuit->m;
-      CK(verify_wire_locked(ln, g, x.circuit, sg[s].cnt, x.n1, x.proof_len, (const uint8_t *)x.proofs + lo * x.proof_len,
-                            m ? (const uint8_t *)x.commitments + lo * m * 32 : nullptr, (const uint8_t *)x.init_states + lo * 32,
-                            (int32_t *)x.ok + lo, x.gadget_label, tab));
-    }
+    for (size_t s = 0; s < checks[ci].nseg; s++) CK(q.per_proof(ln, sg[s]));
     return BPGPU_OK;
   };
-  return screen_locked(ctx, checks.size(), "bpgpu_r1cs_verify_mixed_wire_screened", fallback_batches, check, accept, fallback);
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
+  return screen_locked(ctx, checks.size(), Kind::screened_name, fallback_batches, check, accept, fallback);
 }
-// host forms: every group's wire bytes go up once (WS_MIXED_STAGE), the device form runs, the verdicts come back
-static int wire_stage_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, size_t ngroups, std::vector<bpgpu_wire_group> &D) {
-  size_t tot = 0;
-  auto sizes = [](const bpgpu_wire_group &x, size_t *b) {
-    b[0] = x.nb * x.proof_len; b[1] = x.commitments ? x.nb * x.circuit->m * 32 : 0; b[2] = x.nb * 32; b[3] = x.nb * 32; b[4] = x.nb * 4;
+// host forms: every group's operands go up once (WS_MIXED_STAGE; one verdict region per group after its operands), and the queue
+// moves on to the copies D that hold the device addresses
+template <class Kind> static int queue_stage_locked(bpgpu_ctx *ctx, Kind &q, std::vector<typename Kind::Group> &D) {
+  constexpr size_t NF = Kind::NFIELDS;
+  StageField f[NF];
+  size_t bytes[NF + 1], off[NF + 1], tot = 0;
+  D.assign(q.G, q.G + q.ngroups);
+  auto layout = [&](size_t i) {
+    Kind::fields(q.G[i], D[i], f);
+    for (size_t j = 0; j < NF; j++) bytes[j] = f[j].bytes;
+    bytes[NF] = q.G[i].nb * 4;
+    bpqueue::stage_layout(bytes, NF + 1, off, &tot);
   };
-  for (size_t i = 0; i < ngroups; i++) { size_t b[5]; sizes(G[i], b); for (size_t j : b) tot += (j + 255) / 256 * 256; }
+  for (size_t i = 0; i < q.ngroups; i++) layout(i);
   void *base;
   CK(ws_get(ctx, WS_MIXED_STAGE, tot, &base));
-  uint8_t *q = (uint8_t *)base;
-  D.assign(G, G + ngroups);
-  for (size_t i = 0; i < ngroups; i++) {
-    size_t b[5];
-    sizes(G[i], b);
-    const void *src[4] = {G[i].proofs, G[i].commitments, G[i].init_states, G[i].rho};
-    const void **dst[4] = {&D[i].proofs, &D[i].commitments, &D[i].init_states, &D[i].rho};
-    for (int j = 0; j < 4; j++) {
-      if (src[j]) { CK(h2d(ctx, q, src[j], b[j])); *dst[j] = q; }
-      q += (b[j] + 255) / 256 * 256;
-    }
-    D[i].ok = q;
-    q += (b[4] + 255) / 256 * 256;
+  tot = 0;
+  for (size_t i = 0; i < q.ngroups; i++) {
+    layout(i);
+    for (size_t j = 0; j < NF; j++)
+      if (f[j].src) { CK(h2d(ctx, (uint8_t *)base + off[j], f[j].src, f[j].bytes)); *f[j].dst = (uint8_t *)base + off[j]; }
+    D[i].ok = (uint8_t *)base + off[NF];
   }
+  q.G = D.data();
   return BPGPU_OK;
+}
+template <class Kind>
+static int queue_combined_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const typename Kind::Group *groups, size_t ngroups, void *partial_xy,
+                                bool dev) {
+  return noexcept_abi([&]() -> int {
+    if (!ctx || !partial_xy) return BPGPU_E_ARG;
+    Kind q{g, groups, ngroups};
+    CK(q.validate(false));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if (dev) return queue_combined_locked(ctx, q, partial_xy);
+    std::vector<typename Kind::Group> D;
+    CK(queue_stage_locked(ctx, q, D));
+    void *dout;
+    CK(ws_get(ctx, WS_ARG4, 64, &dout));
+    CK(queue_combined_locked(ctx, q, dout));
+    CK(d2h(ctx, partial_xy, dout, 64));
+    HIPCK(ctx, hipStreamSynchronize(ctx->st));
+    return BPGPU_OK;
+  });
+}
+template <class Kind>
+static int queue_screened_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const typename Kind::Group *groups, size_t ngroups,
+                                size_t *fallback_batches, bool dev) {
+  return noexcept_abi([&]() -> int {
+    if (fallback_batches) *fallback_batches = 0;
+    if (!ctx) return BPGPU_E_ARG;
+    Kind q{g, groups, ngroups};
+    CK(q.validate(true));
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if (dev) return queue_screened_locked(ctx, q, fallback_batches);
+    std::vector<typename Kind::Group> D;
+    CK(queue_stage_locked(ctx, q, D));
+    CK(queue_screened_locked(ctx, q, fallback_batches));
+    for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
+    HIPCK(ctx, hipStreamSynchronize(ctx->st));
+    return BPGPU_OK;
+  });
+}
+}  // extern "C++"
+int bpgpu_r1cs_verify_mixed_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         void *partial_xy_dev) {
+  return queue_combined_entry<DecodedQueue>(ctx, g, groups, ngroups, partial_xy_dev, true);
+}
+int bpgpu_r1cs_verify_mixed_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     uint8_t partial_xy[64]) {
+  return queue_combined_entry<DecodedQueue>(ctx, g, groups, ngroups, partial_xy, false);
+}
+int bpgpu_r1cs_verify_mixed_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                         size_t *fallback_batches) {
+  return queue_screened_entry<DecodedQueue>(ctx, g, groups, ngroups, fallback_batches, true);
+}
+int bpgpu_r1cs_verify_mixed_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_verify_group *groups, size_t ngroups,
+                                     size_t *fallback_batches) {
+  return queue_screened_entry<DecodedQueue>(ctx, g, groups, ngroups, fallback_batches, false);
 }
 int bpgpu_r1cs_verify_mixed_wire_combined_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
                                               void *partial_xy_dev) {
-  if (!ctx || !partial_xy_dev) return BPGPU_E_ARG;
-  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
-  CK(wire_validate(g, groups, ngroups, false, dims));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return wire_combined_locked(ctx, g, groups, dims, ngroups, partial_xy_dev);
+  return queue_combined_entry<WireQueue>(ctx, g, groups, ngroups, partial_xy_dev, true);
 }
 int bpgpu_r1cs_verify_mixed_wire_combined(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
-                                          uint8_t partial_xy[64]) try {
-  if (!ctx || !partial_xy) return BPGPU_E_ARG;
-  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
-  CK(wire_validate(g, groups, ngroups, false, dims));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_wire_group> D;
-  CK(wire_stage_locked(ctx, groups, ngroups, D));
-  void *dout;
-  CK(ws_get(ctx, WS_ARG4, 64, &dout));
-  CK(wire_combined_locked(ctx, g, D.data(), dims, ngroups, dout));
-  CK(d2h(ctx, partial_xy, dout, 64));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
+                                          uint8_t partial_xy[64]) {
+  return queue_combined_entry<WireQueue>(ctx, g, groups, ngroups, partial_xy, false);
 }
 int bpgpu_r1cs_verify_mixed_wire_screened_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
                                               size_t *fallback_batches) {
-  if (fallback_batches) *fallback_batches = 0;
-  if (!ctx) return BPGPU_E_ARG;
-  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
-  CK(wire_validate(g, groups, ngroups, true, dims));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return wire_screened_locked(ctx, g, groups, dims, ngroups, fallback_batches);
+  return queue_screened_entry<WireQueue>(ctx, g, groups, ngroups, fallback_batches, true);
 }
 int bpgpu_r1cs_verify_mixed_wire_screened(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_wire_group *groups, size_t ngroups,
-                                          size_t *fallback_batches) try {
-  if (fallback_batches) *fallback_batches = 0;
-  if (!ctx) return BPGPU_E_ARG;
-  WireGroupDims dims[BPGPU_MIXED_MAX_GROUPS];
-  CK(wire_validate(g, groups, ngroups, true, dims));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIPCK(ctx, hipSetDevice(ctx->device));
-  std::vector<bpgpu_wire_group> D;
-  CK(wire_stage_locked(ctx, groups, ngroups, D));
-  CK(wire_screened_locked(ctx, g, D.data(), dims, ngroups, fallback_batches));
-  for (size_t i = 0; i < ngroups; i++) CK(d2h(ctx, groups[i].ok, D[i].ok, groups[i].nb * 4));
-  HIPCK(ctx, hipStreamSynchronize(ctx->st));
-  return BPGPU_OK;
-} catch (const std::bad_alloc &) {
-  return BPGPU_E_OOM;
+                                          size_t *fallback_batches) {
+  return queue_screened_entry<WireQueue>(ctx, g, groups, ngroups, fallback_batches, false);
 }
 
 /* ---------------------------------------------------------------- IPP prover session */

@@ -1010,18 +1010,26 @@ class BpGpu:
     def r1cs_verify_combined_dev(self, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_out):
         self._ck(_lib.bpgpu_r1cs_verify_combined_dev(self.ctx, gens, circuit, nb, n1, k, d_points, d_scalars, d_challenges, d_rho, d_out))
 
-    # ---- mixed queues: groups of proofs of several circuits in one call.  A group is a dict with keys circuit, nb, n1, k, points,
-    # scalars, challenges, rho and, for a parametric circuit, gadget_challenges (the layouts of r1cs_verify_batch); the host forms
-    # take bytes, the _dev forms device pointers (and ok: the group's nb int32 verdicts in HBM for the screened call).
+    # ---- mixed queues: groups of proofs of several circuits in one call.  A group is a dict; the host forms take bytes, the _dev
+    # forms device pointers (and ok: the group's nb int32 verdicts in HBM for the screened call).  Decoded operands: keys circuit, nb,
+    # n1, k, points, scalars, challenges, rho and, for a parametric circuit, gadget_challenges (the layouts of r1cs_verify_batch).
+    # Wire-format proofs: keys circuit, nb, n1, proof_len, proofs, commitments (None when m == 0), init_states, rho and, for a
+    # parametric circuit, gadget_label (bytes, host memory in both forms).
+    # A queue kind: (ctypes struct, its three size fields, its pointer fields, its host label or None)
+    _DECODED = (VerifyGroup, ("nb", "n1", "k"), ("points", "scalars", "challenges", "gadget_challenges", "rho"), None)
+    _WIRE = (WireGroup, ("nb", "n1", "proof_len"), ("proofs", "commitments", "init_states", "rho"), "gadget_label")
+
     @staticmethod
-    def _groups(groups, dev):
-        arr = (VerifyGroup * max(len(groups), 1))()
+    def _queue(kind, groups, dev):
+        struct, sizes, pointers, label = kind
+        arr = (struct * max(len(groups), 1))()
         keep, oks = [], []
         for i, gr in enumerate(groups):
             g = arr[i]
             g.circuit = gr["circuit"]
-            g.nb, g.n1, g.k = gr["nb"], gr["n1"], gr["k"]
-            for f in ("points", "scalars", "challenges", "gadget_challenges", "rho"):
+            for f in sizes:
+                setattr(g, f, gr[f])
+            for f in pointers:
                 v = gr.get(f)
                 if v is None:
                     setattr(g, f, None)
@@ -1031,65 +1039,11 @@ class BpGpu:
                     b = C.create_string_buffer(bytes(v), max(len(v), 1))
                     keep.append(b)
                     setattr(g, f, C.cast(b, C.c_void_p).value)
-            if dev:
-                g.ok = gr.get("ok")
-            else:
-                ok = (C.c_int32 * max(gr["nb"], 1))()
-                oks.append(ok)
-                g.ok = C.cast(ok, C.c_void_p).value
-        return arr, keep, oks
-
-    def r1cs_verify_mixed_combined(self, gens, groups):
-        """sum over all groups and proofs of rho_p * mega_check_p (64 bytes; all zero: every proof valid; 0xFF x 64: malformed input)"""
-        arr, keep, _ = self._groups(groups, False)
-        o = _out(64)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined(self.ctx, gens, arr, len(groups), o))
-        return bytes(o)[:64]
-
-    def r1cs_verify_mixed_combined_dev(self, gens, groups, d_out):
-        arr, _, _ = self._groups(groups, True)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_combined_dev(self.ctx, gens, arr, len(groups), d_out))
-
-    def r1cs_verify_mixed_screened(self, gens, groups):
-        """-> ([ok list per group], number of checks that took the per-proof path)"""
-        arr, keep, oks = self._groups(groups, False)
-        nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened(self.ctx, gens, arr, len(groups), C.byref(nf)))
-        return [list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value
-
-    def r1cs_verify_mixed_screened_dev(self, gens, groups):
-        """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
-        arr, _, _ = self._groups(groups, True)
-        nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_screened_dev(self.ctx, gens, arr, len(groups), C.byref(nf)))
-        return nf.value
-
-    # ---- mixed queues of wire-format proofs.  A group is a dict with keys circuit, nb, n1, proof_len, proofs, commitments (None
-    # when m == 0), init_states, rho and, for a parametric circuit, gadget_label (bytes, host memory in both forms); the host forms
-    # take bytes, the _dev forms device pointers (and ok: the group's nb int32 verdicts in HBM for the screened call).
-    @staticmethod
-    def _wire_groups(groups, dev):
-        arr = (WireGroup * max(len(groups), 1))()
-        keep, oks = [], []
-        for i, gr in enumerate(groups):
-            g = arr[i]
-            g.circuit = gr["circuit"]
-            g.nb, g.n1, g.proof_len = gr["nb"], gr["n1"], gr["proof_len"]
-            for f in ("proofs", "commitments", "init_states", "rho"):
-                v = gr.get(f)
-                if v is None:
-                    setattr(g, f, None)
-                elif dev:
-                    setattr(g, f, v)
-                else:
-                    b = C.create_string_buffer(bytes(v), max(len(v), 1))
-                    keep.append(b)
-                    setattr(g, f, C.cast(b, C.c_void_p).value)
-            lab = gr.get("gadget_label")
+            lab = gr.get(label) if label else None
             if lab is not None:
                 b = C.create_string_buffer((bytes(lab) + bytes(32))[:32], 32)
                 keep.append(b)
-                g.gadget_label = C.cast(b, C.c_void_p).value
+                setattr(g, label, C.cast(b, C.c_void_p).value)
             if dev:
                 g.ok = gr.get("ok")
             else:
@@ -1097,32 +1051,49 @@ class BpGpu:
                 oks.append(ok)
                 g.ok = C.cast(ok, C.c_void_p).value
         return arr, keep, oks
+
+    def _queue_combined(self, fn, kind, gens, groups, d_out=None, dev=False):
+        arr, keep, _ = self._queue(kind, groups, dev)
+        o = d_out if dev else _out(64)
+        self._ck(fn(self.ctx, gens, arr, len(groups), o))
+        return None if dev else bytes(o)[:64]
+
+    def _queue_screened(self, fn, kind, gens, groups, dev=False):
+        arr, keep, oks = self._queue(kind, groups, dev)
+        nf = C.c_size_t(0)
+        self._ck(fn(self.ctx, gens, arr, len(groups), C.byref(nf)))
+        return nf.value if dev else ([list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value)
+
+    def r1cs_verify_mixed_combined(self, gens, groups):
+        """sum over all groups and proofs of rho_p * mega_check_p (64 bytes; all zero: every proof valid; 0xFF x 64: malformed input)"""
+        return self._queue_combined(_lib.bpgpu_r1cs_verify_mixed_combined, self._DECODED, gens, groups)
+
+    def r1cs_verify_mixed_combined_dev(self, gens, groups, d_out):
+        self._queue_combined(_lib.bpgpu_r1cs_verify_mixed_combined_dev, self._DECODED, gens, groups, d_out, True)
+
+    def r1cs_verify_mixed_screened(self, gens, groups):
+        """-> ([ok list per group], number of checks that took the per-proof path)"""
+        return self._queue_screened(_lib.bpgpu_r1cs_verify_mixed_screened, self._DECODED, gens, groups)
+
+    def r1cs_verify_mixed_screened_dev(self, gens, groups):
+        """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
+        return self._queue_screened(_lib.bpgpu_r1cs_verify_mixed_screened_dev, self._DECODED, gens, groups, True)
 
     def r1cs_verify_mixed_wire_combined(self, gens, groups):
         """sum over all groups and proofs of rho_p * mega_check_p from wire bytes (64 bytes; all zero: every proof valid; 0xFF x 64:
         an undecodable proof, an identity at a validated point or a malformed weight)"""
-        arr, keep, _ = self._wire_groups(groups, False)
-        o = _out(64)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_combined(self.ctx, gens, arr, len(groups), o))
-        return bytes(o)[:64]
+        return self._queue_combined(_lib.bpgpu_r1cs_verify_mixed_wire_combined, self._WIRE, gens, groups)
 
     def r1cs_verify_mixed_wire_combined_dev(self, gens, groups, d_out):
-        arr, keep, _ = self._wire_groups(groups, True)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_combined_dev(self.ctx, gens, arr, len(groups), d_out))
+        self._queue_combined(_lib.bpgpu_r1cs_verify_mixed_wire_combined_dev, self._WIRE, gens, groups, d_out, True)
 
     def r1cs_verify_mixed_wire_screened(self, gens, groups):
         """-> ([ok list per group], number of checks that took the per-proof path)"""
-        arr, keep, oks = self._wire_groups(groups, False)
-        nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_screened(self.ctx, gens, arr, len(groups), C.byref(nf)))
-        return [list(ok)[:gr["nb"]] for ok, gr in zip(oks, groups)], nf.value
+        return self._queue_screened(_lib.bpgpu_r1cs_verify_mixed_wire_screened, self._WIRE, gens, groups)
 
     def r1cs_verify_mixed_wire_screened_dev(self, gens, groups):
         """verdicts into each group's device ok array (sync() before reading them) -> fallback checks"""
-        arr, keep, _ = self._wire_groups(groups, True)
-        nf = C.c_size_t(0)
-        self._ck(_lib.bpgpu_r1cs_verify_mixed_wire_screened_dev(self.ctx, gens, arr, len(groups), C.byref(nf)))
-        return nf.value
+        return self._queue_screened(_lib.bpgpu_r1cs_verify_mixed_wire_screened_dev, self._WIRE, gens, groups, True)
 
     def set_shard(self, rank, world):
         """this context's share of ONE large proof split over the GPUs of a node (include/bpgpu.h bpgpu_set_shard)"""

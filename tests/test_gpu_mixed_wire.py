@@ -361,3 +361,51 @@ def test_shape_errors_fail_before_anything_runs(gpu, gens, mix):
     finally:
         gpu.circuit_destroy(two_chi)
         gpu.gens_destroy(small)
+
+
+def test_more_groups_than_one_check_takes(gpu, gens, mix, opts):
+    """20 small groups of wire bytes, more than the 16 group runs one check holds (BPGPU_MIXED_MAX_SEGMENTS): the combined call adds
+    up the points of two checks, each behind its own ragged front, and equals the decoded queue's call on the host-decoded operands
+    of the same records and weights (the identity on valid proofs; an off-curve point in the last group poisons the sum), and the
+    screened call closes a check after 16 groups -- its verdicts equal the oracle's and exactly the check that holds the tampered
+    proof falls back"""
+    import mpc_bulletproof_amd as m
+    assert m.lib.MIXED_MAX_SEGMENTS == 16
+    rnd = random.Random(2020)
+    ng = 20
+    kinds = [mix[i % 5] for i in range(ng)]
+    nxt = {kd.name: 0 for kd in mix}
+
+    def take(kd, nb):
+        idx = list(range(nxt[kd.name], nxt[kd.name] + nb))
+        nxt[kd.name] += nb
+        return idx
+    idxs = [take(kd, 1 + i % 2) for i, kd in enumerate(kinds)]
+    rhos = [_rhos(rnd, len(ix)) for ix in idxs]
+
+    def queues(recs):
+        return ([_wgroup(kd, r, b"".join(w)) for kd, r, w in zip(kinds, recs, rhos)],
+                [_group(kd, r, b"".join(w)) for kd, r, w in zip(kinds, recs, rhos)])
+    valid = [kd.pick(ix) for kd, ix in zip(kinds, idxs)]
+    wire, decoded = queues(valid)
+    got = gpu.r1cs_verify_mixed_wire_combined(gens, wire)
+    assert got == gpu.r1cs_verify_mixed_combined(gens, decoded)
+    assert got == IDENT
+    assert gpu.input_flag() == 0
+    # one tampered proof in group 18: the second check
+    recs = [kd.pick(ix, {ix[0]} if g == 18 else set()) for g, (kd, ix) in enumerate(zip(kinds, idxs))]
+    assert recs[18][0]["ok"] == 0
+    wire, decoded = queues(recs)
+    got = gpu.r1cs_verify_mixed_wire_combined(gens, wire)
+    assert got == gpu.r1cs_verify_mixed_combined(gens, decoded)
+    assert got not in (IDENT, POISON)
+    assert gpu.input_flag() == 0
+    opts(screen_batch=2560, stream_lanes=3)
+    oks, nf = gpu.r1cs_verify_mixed_wire_screened(gens, wire)
+    assert oks == [[x["ok"] for x in r] for r in recs]
+    assert nf == 1
+    # an off-curve point in group 19
+    recs[19] = [_patch(recs[19][0], 1 + 32 * 2, OFF_CURVE, 0)] + recs[19][1:]
+    wire, _ = queues(recs)
+    assert gpu.r1cs_verify_mixed_wire_combined(gens, wire) == POISON
+    assert gpu.input_flag() == 1
