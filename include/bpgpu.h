@@ -362,10 +362,21 @@ int bpgpu_circuit_create_ark(bpgpu_ctx *ctx, size_t q, const uint32_t *row_ptr, 
  * The CSR has (1 + nchi) * q rows: rows [0, q) hold the constant parts c0, rows [j q, (j + 1) q) the chi_j parts (row r of block j
  * belongs to constraint r).  One such circuit serves every proof of the gadget, whatever challenge its transcript produced.
  * Use it with bpgpu_r1cs_verify_batch_param (gadget challenges from the host) or bpgpu_r1cs_verify_batch_fs2 (transcript on the
- * device); the other entry points reject it (BPGPU_E_ARG).  nchi <= 8 (the device transcript supports nchi <= 1). */
+ * device); the other entry points reject it (BPGPU_E_ARG).  nchi <= 8.  The device transcript draws one challenge under the label
+ * an entry point is given, or all nchi under the circuit's own labels (bpgpu_circuit_set_gadget_labels). */
 int bpgpu_circuit_create_param(bpgpu_ctx *ctx, size_t q, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
                                const uint32_t *idx, const uint8_t *coeff, size_t n_multipliers, size_t m_commitments,
                                bpgpu_circuit **out);
+/* The labels of a parametric circuit's gadget challenges: nchi x 32 bytes, each zero-padded as gadget_label.  Label j is the label of
+ * the j-th challenge_scalar call of the randomized phase, in draw order (the closures run one after the other, r1cs/prover.rs:383-408,
+ * r1cs/verifier.rs:366-385) -- the challenge whose parts are block j + 1 of the circuit's rows.  The handle keeps a copy (host memory);
+ * a later call replaces it.  Not to be called while another call uses the handle.  BPGPU_E_ARG: a null pointer, a numeric circuit.
+ * Every entry point with the transcript on the device -- bpgpu_r1cs_prove_fs2_begin / _finish, bpgpu_r1cs_prove_fs2,
+ * bpgpu_r1cs_prove_values, bpgpu_r1cs_verify_batch_fs2, bpgpu_r1cs_verify_batch_wire2, bpgpu_r1cs_verify_mixed_wire_* -- then takes the
+ * circuit with gadget_label == NULL (a label beside attached ones: BPGPU_E_ARG), for any 1 <= nchi <= 8: TS step j hashes under
+ * label j, and every gadget_challenges(_out) array is nb x nchi x 32, prover-major.  A circuit with nothing attached behaves as
+ * described at each entry point: one challenge, under the label given.  Timings of circuits with nchi > 1: UNMEASURED. */
+int bpgpu_circuit_set_gadget_labels(bpgpu_ctx *ctx, bpgpu_circuit *c, const uint8_t *labels);
 /* Prover::prove arithmetic between the y,z and the u,x challenges -- r1cs/prover.rs:587-619:
  * flattened_constraints(z), exp_y / exp_y_inv, the l(x)/r(x) coefficient vectors and
  * t_1..t_6 = VecPoly3::special_inner_product (util.rs:152-170), for nb provers of ONE circuit.
@@ -496,14 +507,15 @@ int bpgpu_r1cs_commit_values_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb,
  * bpgpu_r1cs_prover_ipp_begin, bpgpu_ipp_run_fs and the host hashing between them.  With n = the circuit's multipliers, n1 those of
  * phase 1, n2 = n - n1 >= 1, m its commitments, padded_n = next_pow2(n), k = lg padded_n:
  * _begin (prover.rs:420-501): append_u64("m"), the phase-1 commitments (n1 == 0 commits the blindings alone), A_I1 A_O1 S1 absorbed,
- * the 2-phase separator, challenge_scalar(gadget_label) -- the label zero-padded to 32 bytes as in bpgpu_r1cs_verify_batch_fs2.
+ * the 2-phase separator, challenge_scalar(gadget_label) -- the label zero-padded to 32 bytes as in bpgpu_r1cs_verify_batch_fs2; NULL
+ * for a circuit with attached labels (bpgpu_circuit_set_gadget_labels), which draws its nchi challenges, each under its own.
  *   states_in      nb x 32        the chain state on entry to Prover::prove, as bpgpu_r1cs_prove_fs
  *   a_L, a_R, a_O  nb x n1        ark form; s_L, s_R nb x n1 or vector_keys nb x 32: exactly one source when n1 > 0; all may be NULL
  *                                 when n1 == 0
  *   blindings      nb x 3         ark form: i_blinding1 o_blinding1 s_blinding1 (:457-459)
- *   session        in: *session == NULL; out: the open session.  It keeps on the device the chain state, the gadget challenge, the
+ *   session        in: *session == NULL; out: the open session.  It keeps on the device the chain state, the gadget challenges (nb x nchi x 32 B), the
  *                                 phase-1 blinding factors and commitments and the witness planes
- *   commitments    (optional) nb x 3 x 64: A_I1 A_O1 S1;   gadget_challenges_out (optional) nb x 32 canonical LE;
+ *   commitments    (optional) nb x 3 x 64: A_I1 A_O1 S1;   gadget_challenges_out (optional) nb x nchi x 32 canonical LE;
  *   states_out     (optional) nb x 32: the chain after the gadget challenge
  * _finish (:515-727): the phase-2 commitments over G[n1..n), H[n1..n), A_I2 A_O2 S2 absorbed, y, z, the polynomial build with the
  * parametric weights taken from the session's own gadget challenge, the T commitments, u, x, tb2, t_x, t_x_blinding,
@@ -730,14 +742,14 @@ int bpgpu_r1cs_witness_synthesize_dev(bpgpu_ctx *ctx, const bpgpu_witness *w, si
  * the phase-2 gates on the gadget challenge that chain has just drawn (read from the session's device copy), the chain of
  * bpgpu_r1cs_prove_fs2_finish -- all on the context's stream, no host wait, no session left behind.  The launches of the two chains
  * are the ones _begin and _finish issue (the same code); outputs are byte-identical to that pair fed the host-evaluated witness.
- *   states_in, gadget_label   as bpgpu_r1cs_prove_fs2_begin (the label is host memory in both forms)
+ *   states_in, gadget_label   as bpgpu_r1cs_prove_fs2_begin (the label is host memory in both forms; NULL with attached labels)
  *   v, inputs       as bpgpu_r1cs_witness_synthesize
  *   s_L, s_R        nb x n, explicit blinding vectors (phase 1: [0, n1), phase 2: [n1, n) of each prover's row), or both NULL with
  *   vector_keys     nb x 2 x 32: a phase-1 key, then a phase-2 key (exactly one of the two sources)
  *   v_blinding      nb x m, ark form; may be NULL when m == 0
  *   blindings       nb x 11, ark form: i1 o1 s1 | i2 o2 s2 tb1 tb3 tb4 tb5 tb6
  *   proof_points, proof_scalars, wire, challenges_out, states_out   as bpgpu_r1cs_prove_fs2_finish
- *   gadget_challenges_out   (optional) nb x 32 canonical LE
+ *   gadget_challenges_out   (optional) nb x nchi x 32 canonical LE, prover-major
  *   a_L_out, a_R_out, a_O_out   (optional, all three or none) nb x n, ark form: the synthesized witness, e.g. for
  *                                      bpgpu_r1cs_constraints_satisfied afterwards
  * Refusals, before anything is launched: those of _begin and _finish; BPGPU_E_ARG for a null program, for a program whose
@@ -760,7 +772,8 @@ int bpgpu_r1cs_prove_fs2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_ci
  *   ONE-PHASE  c numeric (bpgpu_circuit_create / _ark), w with nchi == 0 and n1 == n, gadget_label == NULL.  Stage order:
  *              1 bpgpu_r1cs_commit_values with the chain from init_states, 2 bpgpu_r1cs_witness_synthesize phase 0,
  *              3 bpgpu_r1cs_constraints_satisfied, 4 bpgpu_r1cs_prove_fs on the states that stage 1 produced.
- *   TWO-PHASE  c parametric with nchi == 1, w with the same (n, n1, m, nchi), gadget_label given (32 bytes, host memory in both forms).
+ *   TWO-PHASE  c parametric with nchi == 1, w with the same (n, n1, m, nchi), gadget_label given (32 bytes, host memory in both forms);
+ *              or c with attached labels (bpgpu_circuit_set_gadget_labels), any nchi, and gadget_label == NULL.
  *              Stage order: 1 bpgpu_r1cs_commit_values, 2 the bpgpu_r1cs_prove_fs2 chain, which synthesizes both phases and draws the
  *              gadget challenge, 3 bpgpu_r1cs_constraints_satisfied on the witness and the challenge that stage 2 left on the device.
  *              The check necessarily runs AFTER the proof here: the phase-2 witness does not exist before the challenge.
@@ -1034,7 +1047,9 @@ int bpgpu_r1cs_verify_batch_wire2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const
  * gadget challenges (nb x nchi x 32 B, in the order the gadget drew them) beside the usual 6 + k challenges.  _fs2: as
  * bpgpu_r1cs_verify_batch_fs -- the whole transcript replay on the device, including the phase separator and the gadget's
  * challenge_scalar(gadget_label) (label zero-padded to 32 bytes; verifier.rs:373-383), whose value selects the constraint weights;
- * gadget_challenges_out (optional) returns it.  Same per-proof rejection rules as the one-phase entry points. */
+ * gadget_challenges_out (optional) returns it.  A circuit with attached labels (bpgpu_circuit_set_gadget_labels) takes gadget_label ==
+ * NULL and draws its nchi challenges, each under its own label (gadget_challenges_out: nb x nchi x 32); bpgpu_r1cs_verify_batch_wire2
+ * likewise.  Same per-proof rejection rules as the one-phase entry points. */
 int bpgpu_r1cs_verify_batch_param(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                   size_t k, const uint8_t *points, const uint8_t *scalars, const uint8_t *challenges,
                                   const uint8_t *gadget_challenges, int32_t *ok, uint8_t *mega, uint8_t *msm_scalars);
@@ -1173,7 +1188,8 @@ typedef struct bpgpu_wire_group {
   const void *proofs;                  /* nb x proof_len */
   const void *commitments;             /* nb x m x 32 B compressed; may be NULL when m == 0 */
   const void *init_states;             /* nb x 32 B chain states, as bpgpu_r1cs_verify_batch_fs */
-  const uint8_t *gadget_label;         /* HOST pointer, 32 bytes zero-padded, for a parametric circuit; NULL otherwise */
+  const uint8_t *gadget_label;         /* HOST pointer, 32 bytes zero-padded, for a parametric circuit; NULL otherwise, and for a
+                                          circuit with attached labels (bpgpu_circuit_set_gadget_labels) */
   const void *rho;                     /* nb x 32 B random non-zero weights */
   void *ok;                            /* nb int32 verdicts (screened calls) */
 } bpgpu_wire_group;
@@ -1266,6 +1282,8 @@ int bpgpu_pool_circuit_create_ark(bpgpu_pool *pool, size_t q, const uint32_t *ro
 int bpgpu_pool_circuit_create_param(bpgpu_pool *pool, size_t q, size_t nchi, const uint32_t *row_ptr, const uint32_t *kind,
                                     const uint32_t *idx, const uint8_t *coeff, size_t n_multipliers, size_t m_commitments,
                                     bpgpu_pool_circuit **out);
+/* bpgpu_circuit_set_gadget_labels on every slot's handle (for bpgpu_pool_r1cs_prove_values with gadget_label == NULL) */
+int bpgpu_pool_circuit_set_gadget_labels(bpgpu_pool *pool, bpgpu_pool_circuit *c, const uint8_t *labels);
 void bpgpu_pool_circuit_destroy(bpgpu_pool *pool, bpgpu_pool_circuit *c);
 const bpgpu_circuit *bpgpu_pool_circuit_get(const bpgpu_pool_circuit *c, size_t slot);
 int bpgpu_pool_witness_create(bpgpu_pool *pool, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,

@@ -1,6 +1,7 @@
 // bpgpu_api.hip -- the C ABI of include/bpgpu.h on top of the HIP kernels.
 // No CPU fallback: every entry point needs a live HIP device and fails with BPGPU_E_DEVICE otherwise.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cerrno>
 #include <climits>
 #include <cstdio>
@@ -111,11 +112,12 @@ struct bpgpu_ctx {
   void *pinned = nullptr;         // page-locked staging for the verdicts of a host-memory stream or screened call (pinned_verdicts)
   size_t pinned_cap = 0;
   // device-transcript schedule cache (m, k, padded_n) -> steps already resident in WS_SCHED
-  size_t sched_key[3] = {(size_t)-1, (size_t)-1, (size_t)-1};
+  size_t sched_key[4] = {(size_t)-1, (size_t)-1, (size_t)-1, 0};   // m, k, padded n + (nchi << 40), the circuit's labels_id (0: none)
   int sched_len = 0;
   // the prover's schedules (prover_schedule), [0] of bpgpu_r1cs_prove_fs in WS_PFS_SCHED, [1] of bpgpu_r1cs_prove_fs2_begin / _finish in
-  // WS_PFS_SCHED2: (m, padded_n) -> steps resident, and their three / four slices
-  struct { size_t key[2] = {(size_t)-1, (size_t)-1}; int cut[5] = {0, 0, 0, 0, 0}; } psched[2];
+  // WS_PFS_SCHED2: (m, padded_n, nchi, the circuit's labels_id or 0) -> steps resident (and the label table behind them), and their
+  // three / four slices
+  struct { size_t key[4] = {(size_t)-1, (size_t)-1, 0, 0}; int cut[5] = {0, 0, 0, 0, 0}; } psched[2];
   // bpgpu_r1cs_verify_mixed_wire_*: page-locked staging of a call's schedules and the mark of its upload (the next call waits for
   // the mark before it refills the staging -- passed long before, except when _dev calls follow each other without a bpgpu_sync)
   void *wsched_host = nullptr;
@@ -187,6 +189,11 @@ struct bpgpu_circuit {
   size_t q = 0, n = 0, m = 0, nnz = 0, nchi = 0;   // nchi: gadget challenges the coefficients are affine in (kernels.h CircuitDev)
   uint32_t *col_ptr = nullptr, *row = nullptr;
   Words8 *coeff = nullptr;
+  // bpgpu_circuit_set_gadget_labels: the nchi labels of the gadgets' challenge_scalar calls in draw order (nchi x 32 B, host memory;
+  // empty: none attached, the device-transcript calls take the one label as an argument).  labels_id is unique over the process
+  // and changes with every attachment: the contexts' resident schedules (with the label table behind the steps) are keyed by it.
+  std::vector<uint8_t> labels;
+  uint64_t labels_id = 0;
   // the row-major view (kernels.h RowsDev), built by the first bpgpu_r1cs_constraints_satisfied / bpgpu_mpc_constraints_eval that sees
   // the handle and kept until bpgpu_circuit_destroy.  A handle serves several contexts of a device, each with its own mutex: view_mu
   // guards the one-time build (taken with the calling context's mutex held, never the other way round).
@@ -1521,6 +1528,23 @@ int bpgpu_circuit_create_param(bpgpu_ctx *ctx, size_t q, size_t nchi, const uint
   if (nchi > 8) return BPGPU_E_LEN;
   return circuit_create_impl(ctx, q, nchi, row_ptr, kind, idx, coeff, n_mul, m, out);
 }
+int bpgpu_circuit_set_gadget_labels(bpgpu_ctx *ctx, bpgpu_circuit *c, const uint8_t *labels) try {
+  static std::atomic<uint64_t> next_id{1};
+  if (!ctx || !c || !labels || !c->nchi) return BPGPU_E_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  c->labels.assign(labels, labels + c->nchi * GADGET_LABEL_BYTES);
+  c->labels_id = next_id.fetch_add(1);
+  return BPGPU_OK;
+} catch (const std::bad_alloc &) {
+  return BPGPU_E_OOM;
+}
+// What a device-transcript entry point makes of (circuit, gadget_label argument): with labels attached the argument must be null
+// and any nchi goes; without, `unattached_ok` is the entry point's own rule for the one label.  The attached table (host), or null
+static const uint8_t *circuit_labels(const bpgpu_circuit *c) { return c->labels.empty() ? nullptr : c->labels.data(); }
+static int gadget_label_rule(const bpgpu_circuit *c, const uint8_t *gadget_label, bool unattached_ok) {
+  if (circuit_labels(c)) return gadget_label ? BPGPU_E_ARG : BPGPU_OK;
+  return unattached_ok ? BPGPU_OK : BPGPU_E_ARG;
+}
 void bpgpu_circuit_destroy(bpgpu_ctx *ctx, bpgpu_circuit *c) {
   if (!c) return;
   if (ctx) { std::lock_guard<std::mutex> lk(ctx->mu); hipStreamSynchronize(ctx->st); hipStreamSynchronize(ctx->st2); }
@@ -2125,27 +2149,35 @@ static int fs_transcript_locked(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t n
                                 const void *scalars, void *challenges_out, const uint8_t *gadget_label, void *chi_out, Words8 **chp,
                                 void **dbad_out, void **dchi_out) try {
   if (k >= 32) return BPGPU_E_LEN;
-  if (c->nchi > 1 || (c->nchi == 1 && !gadget_label)) return BPGPU_E_ARG;   // one gadget challenge label per schedule
+  // without attached labels: one gadget challenge label per schedule
+  CK(gadget_label_rule(c, gadget_label, !(c->nchi > 1 || (c->nchi == 1 && !gadget_label))));
   HIPCK(ctx, hipSetDevice(ctx->device));
   const size_t m = c->m, np = (size_t)1 << k, nchi = c->nchi;
+  const uint8_t *labels = circuit_labels(c);
+  const size_t label_id = labels ? c->labels_id : 0, cap = transcript_schedule_max(m, k, nchi);
   void *dsteps, *dch, *dbad, *dchi = nullptr;
   if (nchi) { if (chi_out) dchi = chi_out; else CK(ws_get(ctx, WS_CHI, nb * nchi * 32, &dchi)); }
-  CK(ws_get(ctx, WS_SCHED, transcript_schedule_max(m, k) * sizeof(TrStep) + 64, &dsteps));
+  CK(ws_get(ctx, WS_SCHED, (cap + gadget_label_slots(nchi)) * sizeof(TrStep) + 64, &dsteps));
   CK(ws_get(ctx, WS_FS_CH, nb * (6 + k) * 32, &dch));
   CK(ws_get(ctx, WS_PROOF_BAD, nb * 4, &dbad));
-  if (ctx->sched_key[0] != m || ctx->sched_key[1] != k || ctx->sched_key[2] != np + (nchi << 40)) {
-    std::vector<TrStep> steps(transcript_schedule_max(m, k));
+  if (ctx->sched_key[0] != m || ctx->sched_key[1] != k || ctx->sched_key[2] != np + (nchi << 40) || ctx->sched_key[3] != label_id) {
+    // the steps, and behind them (at step `cap`) the circuit's label table, if it has one: ONE upload
+    std::vector<TrStep> steps(cap + gadget_label_slots(nchi));
     ctx->sched_len = transcript_schedule(steps.data(), m, k, np, nchi);
-    HIPCK(ctx, hipMemcpyAsync(dsteps, steps.data(), ctx->sched_len * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
+    size_t up = (size_t)ctx->sched_len;
+    if (labels) { memcpy(steps.data() + cap, labels, nchi * GADGET_LABEL_BYTES); up = steps.size(); }
+    ctx->sched_key[0] = (size_t)-1;              // (nothing resident if the upload fails)
+    HIPCK(ctx, hipMemcpyAsync(dsteps, steps.data(), up * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
     HIPCK(ctx, hipStreamSynchronize(ctx->st));   // `steps` is a local
-    ctx->sched_key[0] = m; ctx->sched_key[1] = k; ctx->sched_key[2] = np + (nchi << 40);
+    ctx->sched_key[0] = m; ctx->sched_key[1] = k; ctx->sched_key[2] = np + (nchi << 40); ctx->sched_key[3] = label_id;
   }
   *chp = challenges_out ? (Words8 *)challenges_out : (Words8 *)dch;
   *dbad_out = dbad;
   *dchi_out = dchi;
   ProfScope ps(ctx, 5, ctx->st);
   verify_transcript(ctx->st, nb, m, k, (const TrStep *)dsteps, ctx->sched_len, (const Words8 *)init_states,
-                    (const Words8 *)points, (const Words8 *)scalars, *chp, (int32_t *)dbad, gadget_label, (Words8 *)dchi, nchi);
+                    (const Words8 *)points, (const Words8 *)scalars, *chp, (int32_t *)dbad, gadget_label, (Words8 *)dchi, nchi,
+                    labels ? (const uint8_t *)((const TrStep *)dsteps + cap) : nullptr);
   return BPGPU_OK;
 } catch (const std::bad_alloc &) {   // host-side staging (std::vector): no exception crosses the C ABI
   return BPGPU_E_OOM;
@@ -2290,7 +2322,7 @@ int bpgpu_r1cs_verify_batch_wire_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const 
 int bpgpu_r1cs_verify_batch_wire2_dev(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                       size_t proof_len, const uint8_t gadget_label[32], const void *proofs_dev,
                                       const void *commitments_dev, const void *init_states_dev, void *ok_dev) {
-  if (!gadget_label) return BPGPU_E_ARG;
+  if (!gadget_label && !(c && circuit_labels(c))) return BPGPU_E_ARG;   // the label: the call's, or the circuit's own
   return verify_wire_dev(ctx, g, c, nb, n1, proof_len, gadget_label, proofs_dev, commitments_dev, init_states_dev, ok_dev);
 }
 static int verify_wire_host(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, size_t proof_len,
@@ -2322,7 +2354,7 @@ int bpgpu_r1cs_verify_batch_wire(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
 int bpgpu_r1cs_verify_batch_wire2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1,
                                   size_t proof_len, const uint8_t gadget_label[32], const uint8_t *proofs, const uint8_t *commitments,
                                   const uint8_t *init_states, int32_t *ok) {
-  if (!gadget_label) return BPGPU_E_ARG;
+  if (!gadget_label && !(c && circuit_labels(c))) return BPGPU_E_ARG;   // the label: the call's, or the circuit's own
   return verify_wire_host(ctx, g, c, nb, n1, proof_len, gadget_label, proofs, commitments, init_states, ok);
 }
 
@@ -2674,13 +2706,14 @@ struct DecodedQueue {
  * context, before the lanes fork; the lanes only read them. */
 namespace {
 struct WireGroupDims { int two_phase; size_t k; };
-struct WireSched { const TrStep *steps; int nsteps; };
+struct WireSched { const TrStep *steps; int nsteps; const uint8_t *labels; };   // labels: the circuit's label table in HBM, or null
 }
-// every non-empty group's schedule, one after the other in WS_WIRE_SCHED of the calling context: ONE upload per call from page-locked
-// staging, no host wait (fs_transcript_locked's one-entry cache would re-upload and wait whenever the shape changes)
+// every non-empty group's schedule (and behind it the label table of a circuit that has one), one after the other in WS_WIRE_SCHED of
+// the calling context: ONE upload per call from page-locked staging, no host wait (fs_transcript_locked's one-entry cache would re-upload and wait whenever the shape changes)
 static int wire_schedules_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, const WireGroupDims *dims, size_t ngroups, WireSched *out) {
   size_t cap = 0;
-  for (size_t i = 0; i < ngroups; i++) if (G[i].nb) cap += transcript_schedule_max(G[i].circuit->m, dims[i].k);
+  auto room = [&](size_t i) { return transcript_schedule_max(G[i].circuit->m, dims[i].k, G[i].circuit->nchi) + gadget_label_slots(G[i].circuit->nchi); };
+  for (size_t i = 0; i < ngroups; i++) if (G[i].nb) cap += room(i);
   if (!cap) return BPGPU_OK;
   if (!ctx->wsched_ev) HIPCK(ctx, hipEventCreateWithFlags(&ctx->wsched_ev, hipEventDisableTiming));
   else HIPCK(ctx, hipEventSynchronize(ctx->wsched_ev));        // the previous call's upload has read the staging
@@ -2694,12 +2727,17 @@ static int wire_schedules_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, cons
   TrStep *h = (TrStep *)ctx->wsched_host;
   size_t off = 0;
   for (size_t i = 0; i < ngroups; i++) {
-    if (!G[i].nb) { out[i] = WireSched{nullptr, 0}; continue; }
+    if (!G[i].nb) { out[i] = WireSched{nullptr, 0, nullptr}; continue; }
     const bpgpu_circuit *c = G[i].circuit;
-    memset(h + off, 0, transcript_schedule_max(c->m, dims[i].k) * sizeof(TrStep));
+    memset(h + off, 0, room(i) * sizeof(TrStep));
     const int n = transcript_schedule(h + off, c->m, dims[i].k, (size_t)1 << dims[i].k, c->nchi);
-    out[i] = WireSched{(const TrStep *)dsteps + off, n};
+    out[i] = WireSched{(const TrStep *)dsteps + off, n, nullptr};
     off += (size_t)n;
+    if (const uint8_t *labels = circuit_labels(c)) {
+      memcpy(h + off, labels, c->nchi * GADGET_LABEL_BYTES);
+      out[i].labels = (const uint8_t *)((const TrStep *)dsteps + off);
+      off += gadget_label_slots(c->nchi);
+    }
   }
   HIPCK(ctx, hipMemcpyAsync(dsteps, h, off * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
   HIPCK(ctx, hipEventRecord(ctx->wsched_ev, ctx->st));
@@ -2709,9 +2747,10 @@ static int wire_schedules_locked(bpgpu_ctx *ctx, const bpgpu_wire_group *G, cons
 // input flag when a proof of the check does not decode or fails the transcript's point validation.  The caller has reset the flag.
 static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const WireGroupDims *dims, const WireSched *sched,
                              const void *sqrt_tab, const MixSeg *segs, size_t nseg, int bit, MixSegIn *in) {
-  size_t tot = 0, nbt = 0, nchs = 0;
+  size_t tot = 0, nbt = 0, nchs = 0, nchis = 0;
   for (size_t s = 0; s < nseg; s++) {
     const size_t gi = segs[s].gi;
+    nchis += segs[s].cnt * G[gi].circuit->nchi;
     tot += segs[s].cnt * verify_nvar(G[gi].circuit, dims[gi].k);
     nbt += segs[s].cnt;
     nchs += segs[s].cnt * (6 + dims[gi].k);
@@ -2722,13 +2761,13 @@ static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const Wir
   CK(ws_get(ln, WS_ARG1, tot * 64, &dxy));
   CK(ws_get(ln, WS_ARG2, nbt * 5 * 32, &dsc));
   CK(ws_get(ln, WS_FS_CH, nchs * 32, &dch));
-  CK(ws_get(ln, WS_CHI, nbt * 32, &dchi));
+  CK(ws_get(ln, WS_CHI, (nchis ? nchis : 1) * 32, &dchi));
   CK(ws_get(ln, WS_VAUX, (2 * nbt + tot) * 4, &dbits));
   CK(ws_get(ln, WS_PROOF_BAD, nbt * 4, &dbad));
   int32_t *fmt_ok = (int32_t *)dbits, *tr_bad = fmt_ok + nbt, *dec_ok = tr_bad + nbt;
   WireSegIn ws[BPGPU_MIXED_MAX_SEGMENTS];
   TrSegIn ts[BPGPU_MIXED_MAX_SEGMENTS];
-  size_t pt_off = 0, p_off = 0, ch_off = 0;
+  size_t pt_off = 0, p_off = 0, ch_off = 0, chi_off = 0;
   for (size_t s = 0; s < nseg; s++) {
     const size_t gi = segs[s].gi, lo = segs[s].lo, cnt = segs[s].cnt, k = dims[gi].k;
     const bpgpu_wire_group &x = G[gi];
@@ -2736,11 +2775,11 @@ static int wire_front_locked(bpgpu_ctx *ln, const bpgpu_wire_group *G, const Wir
     const size_t m = c->m, nvar = verify_nvar(c, k);
     ws[s] = WireSegIn{(const uint8_t *)x.proofs + lo * x.proof_len, m ? (const uint8_t *)x.commitments + lo * m * 32 : nullptr, x.proof_len,
                       cnt, m, k, dims[gi].two_phase != 0};
-    Words8 *pts = (Words8 *)dxy + pt_off * 2, *sc = (Words8 *)dsc + p_off * 5, *ch = (Words8 *)dch + ch_off, *chi = (Words8 *)dchi + p_off;
+    Words8 *pts = (Words8 *)dxy + pt_off * 2, *sc = (Words8 *)dsc + p_off * 5, *ch = (Words8 *)dch + ch_off, *chi = (Words8 *)dchi + chi_off;
     ts[s] = TrSegIn{sched[gi].steps, sched[gi].nsteps, cnt, m, k, c->nchi, (const Words8 *)x.init_states + lo, pts, sc, ch, chi,
-                    tr_bad + p_off, x.gadget_label};
+                    tr_bad + p_off, x.gadget_label, sched[gi].labels};
     in[s] = mixed_seg_in(ln, c, cnt, x.n1, k, pts, sc, ch, chi, (const Words8 *)x.rho + lo);
-    pt_off += cnt * nvar; p_off += cnt; ch_off += cnt * (6 + k);
+    pt_off += cnt * nvar; p_off += cnt; ch_off += cnt * (6 + k); chi_off += cnt * c->nchi;
   }
   { ProfScope ps(ln, 23, ln->st);
     wire_unpack_ragged(ln->st, ws, nseg, (Words8 *)dcomp, (Words8 *)dsc, fmt_ok);
@@ -2771,7 +2810,7 @@ struct WireQueue {
       const bpgpu_circuit *c = x.circuit;
       if (!c) return BPGPU_E_ARG;
       if (x.nb && (!x.proofs || !x.init_states || !x.rho || (c->m && !x.commitments) || (screened && !x.ok))) return BPGPU_E_ARG;
-      if (c->nchi > 1 || (c->nchi != 0) != (x.gadget_label != nullptr)) return BPGPU_E_ARG;
+      CK(gadget_label_rule(c, x.gadget_label, !(c->nchi > 1 || (c->nchi != 0) != (x.gadget_label != nullptr))));
       if (!wire_dims(x.proof_len, &dims[i].two_phase, &dims[i].k)) return BPGPU_E_LEN;
       CK(verify_shape(c, g, x.n1, dims[i].k));
       shape[i] = QueueShape{x.nb, verify_nvar(c, dims[i].k)};
@@ -3675,7 +3714,8 @@ static int prover_session_polys_locked(bpgpu_ctx *ctx, bpgpu_prover *s, const bp
 }
 /* ---- Prover::prove (r1cs/prover.rs:412-727) for nb provers with the Fiat-Shamir transcript on the device: in ONE call for a circuit
  * without randomized constraints (bpgpu_r1cs_prove_fs), in TWO around the host's gadget for a two-phase circuit with one gadget
- * challenge (bpgpu_r1cs_prove_fs2_begin = :420-501, the phase-1 commitments and the chain up to that challenge; _finish = :515-727).
+ * challenge, or with the nchi <= 8 of a circuit that carries its labels (bpgpu_circuit_set_gadget_labels) -- bpgpu_r1cs_prove_fs2_begin =
+ * :420-501, the phase-1 commitments and the chain up to the last gadget challenge; _finish = :515-727.
  * From a proof's last commitment phase on both are ONE chain, prove_fs_chain_locked: the commitments, the polynomial build, the T
  * commitments, t(x) and the blindings, the IPP session and its rounds on the context's stream, with the transcript on the device
  * between them (k_prover_transcript, a slice of the schedule each time) -- the host neither hashes nor waits until the proofs are
@@ -3696,14 +3736,15 @@ struct ProveFs2BeginIo {
   void *commitments, *chi_out, *states_out;
 };
 struct ProveFsDims { size_t n, m, padded_n, k; };
-struct Fs2Arrays { uint64_t *states; Words8 *chi, *bl1, *A1; };
-struct ProverSched { const TrStep *steps; const int *cut; };   // resident step list; slice j = steps [cut[j], cut[j + 1])
+struct Fs2Arrays { uint64_t *states; Words8 *chi, *bl1, *A1; };   // per prover: 1 state, nchi challenges, 3 blinding factors, 3 points
+// resident step list; slice j = steps [cut[j], cut[j + 1]); labels: the circuit's label table behind the steps, or null
+struct ProverSched { const TrStep *steps; const int *cut; const uint8_t *labels; };
 // what the one-phase call | a two-phase _finish hand the chain
 struct ProveFsPhase {
   uint64_t *states;               // the chain states: the workspace's | the session's
   ProverSched sched;              // the one-phase | the two-phase schedule ...
   int slice;                      // ... and its slice that absorbs this phase's commitments and draws y, z: 0 | 1
-  const Words8 *chi, *bl1, *A1;   // nullptr | the session's gadget challenge, phase-1 blinding factors and phase-1 commitments
+  const Words8 *chi, *bl1, *A1;   // nullptr | the session's gadget challenges (nb x nchi), phase-1 blinding factors and phase-1 commitments
   size_t n_commit, n1;            // multipliers to commit: n | n - n1;  the IPP's G_factors = [1; n1] ++ [u; ..]: n | n1
 };
 struct ProveFsWs {   // the chain's workspace
@@ -3721,7 +3762,11 @@ static ProveFsDims prove_fs_dims(const bpgpu_circuit *c) {
   while (d.padded_n < d.n) { d.padded_n <<= 1; d.k++; }
   return d;
 }
-static Fs2Arrays fs2_arrays(const bpgpu_prover *s) { return {(uint64_t *)s->fs2, s->fs2 + s->nb, s->fs2 + 2 * s->nb, s->fs2 + 5 * s->nb}; }
+static size_t fs2_words(size_t nb, size_t nchi) { return nb * (1 + nchi + 3 + 6); }
+static Fs2Arrays fs2_arrays(const bpgpu_prover *s) {
+  const size_t nb = s->nb, nchi = s->fs2_c->nchi;
+  return {(uint64_t *)s->fs2, s->fs2 + nb, s->fs2 + (1 + nchi) * nb, s->fs2 + (4 + nchi) * nb};
+}
 static int prove_fs_workspace(bpgpu_ctx *ctx, size_t nb, const ProveFsDims &d, ProveFsWs *w) {
   void *dchs, *dscs, *dpts;
   CK(ws_get(ctx, WS_PFS_CH, nb * (1 + 5 + d.k) * 32, &dchs));
@@ -3735,21 +3780,30 @@ static int prove_fs_workspace(bpgpu_ctx *ctx, size_t nb, const ProveFsDims &d, P
   w->T = (Words8 *)dpts; w->Tres = (JacRaw *)(w->T + nb * 5 * 2);
   return BPGPU_OK;
 }
-// the prover's transcript schedule of (two_phase, m, padded_n) in HBM (ctx->mu held).  Each kind keeps its own resident copy and key:
-// a context that alternates between the two uploads, and waits, only when a kind's shape changes
-static int prover_schedule(bpgpu_ctx *ctx, bool two_phase, size_t m, size_t padded_n, ProverSched *out) {
+// the prover's transcript schedule of (two_phase, m, padded_n) in HBM (ctx->mu held) -- c: the two-phase circuit (its nchi gadget
+// steps, and its label table behind the steps if it has one), null for one phase.  Each kind keeps its own resident copy and key:
+// a context that alternates between the two uploads, and waits, only when a kind's shape (or the circuit's labels) changes
+static int prover_schedule(bpgpu_ctx *ctx, const bpgpu_circuit *c, size_t m, size_t padded_n, ProverSched *out) {
+  constexpr size_t ROOM = PROVER_SCHEDULE_MAX + gadget_label_slots(8);
+  const bool two_phase = c != nullptr;
+  const size_t nchi = c ? c->nchi : 0;
+  const uint8_t *labels = c ? circuit_labels(c) : nullptr;
+  const size_t label_id = labels ? c->labels_id : 0;
   void *dsteps;
-  CK(ws_get(ctx, two_phase ? WS_PFS_SCHED2 : WS_PFS_SCHED, PROVER_SCHEDULE_MAX * sizeof(TrStep), &dsteps));
+  CK(ws_get(ctx, two_phase ? WS_PFS_SCHED2 : WS_PFS_SCHED, ROOM * sizeof(TrStep), &dsteps));
   auto &e = ctx->psched[two_phase];
-  if (e.key[0] != m || e.key[1] != padded_n) {
-    TrStep steps[PROVER_SCHEDULE_MAX];
-    const int len = prover_transcript_schedule(steps, two_phase, m, padded_n, e.cut);
-    static_assert(PROVER_SCHEDULE_MAX >= 24, "the two-phase schedule has 24 steps");
-    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, len * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
+  if (e.key[0] != m || e.key[1] != padded_n || e.key[2] != nchi || e.key[3] != label_id) {
+    TrStep steps[ROOM];
+    memset(steps, 0, sizeof steps);
+    const int len = prover_transcript_schedule(steps, nchi, m, padded_n, e.cut);
+    static_assert(PROVER_SCHEDULE_MAX >= 23 + 8, "the two-phase schedule has 23 steps and one per gadget challenge");
+    if (labels) memcpy(steps + PROVER_SCHEDULE_MAX, labels, nchi * GADGET_LABEL_BYTES);
+    e.key[0] = (size_t)-1;                       // (nothing resident if the upload fails)
+    HIPCK(ctx, hipMemcpyAsync(dsteps, steps, (labels ? ROOM : (size_t)len) * sizeof(TrStep), hipMemcpyHostToDevice, ctx->st));
     HIPCK(ctx, hipStreamSynchronize(ctx->st));   // `steps` is a local
-    e.key[0] = m; e.key[1] = padded_n;
+    e.key[0] = m; e.key[1] = padded_n; e.key[2] = nchi; e.key[3] = label_id;
   }
-  *out = {(const TrStep *)dsteps, e.cut};
+  *out = {(const TrStep *)dsteps, e.cut, labels ? (const uint8_t *)((const TrStep *)dsteps + PROVER_SCHEDULE_MAX) : nullptr};
   return BPGPU_OK;
 }
 // The chain from a proof's last commitment phase to its assembly (ctx->mu held, shapes checked; asynchronous).  `s` holds whatever was
@@ -3869,7 +3923,7 @@ static int prove_fs_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circ
   ProveFsWs w;
   ProverSched sched;
   CK(prove_fs_workspace(ctx, nb, d, &w));
-  CK(prover_schedule(ctx, false, d.m, d.padded_n, &sched));
+  CK(prover_schedule(ctx, nullptr, d.m, d.padded_n, &sched));
   bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
   if (!s) return BPGPU_E_OOM;
   ProverOwner pown(s, ProverFree{ctx});
@@ -3914,11 +3968,11 @@ int bpgpu_r1cs_prove_fs(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit
 static int prove_fs2_begin_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1, const ProveFs2BeginIo &a,
                                  bpgpu_prover **session) {
   if (!ctx || !g || !c || !session || *session) return BPGPU_E_ARG;
-  if (c->nchi != 1) return BPGPU_E_ARG;      // a numeric circuit has no gadget challenge (bpgpu_r1cs_prove_fs); one label per schedule
+  CK(bpgpu_internal_prove_fs2_labels(c, a.gadget_label, false));
   if (!nb) return BPGPU_OK;
   if (n1 >= c->n) return BPGPU_E_LEN;        // (no second-phase commitments: the staged calls serve such provers)
   if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;
-  if (!a.states_in || !a.gadget_label || !a.blindings) return BPGPU_E_ARG;
+  if (!a.states_in || (!a.gadget_label && !circuit_labels(c)) || !a.blindings) return BPGPU_E_ARG;
   if (n1 && (!a.a_L || !a.a_R || !a.a_O || (!a.s_L) != (!a.s_R) || (a.s_L != nullptr) == (a.vector_keys != nullptr))) return BPGPU_E_ARG;
   return BPGPU_OK;
 }
@@ -3929,12 +3983,12 @@ static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   hipStream_t st = ctx->st;
   const OperandSrc dev{true, false};                 // operands in HBM; the caller has reset the input flag
   ProverSched sched;
-  CK(prover_schedule(ctx, true, d.m, d.padded_n, &sched));
+  CK(prover_schedule(ctx, c, d.m, d.padded_n, &sched));
   bpgpu_prover *s = new (std::nothrow) bpgpu_prover();
   if (!s) return BPGPU_E_OOM;
   own.reset(s);
   s->nb = nb; s->planes = 1; s->g = g; s->fs2_c = c;
-  if (!pool_alloc(ctx, (void **)&s->fs2, nb * 11 * 32)) return BPGPU_E_OOM;
+  if (!pool_alloc(ctx, (void **)&s->fs2, fs2_words(nb, c->nchi) * 32)) return BPGPU_E_OOM;
   const Fs2Arrays f = fs2_arrays(s);
   CK(copy_in(ctx, f.states, io.states_in, nb * 32, true));
   {
@@ -3949,11 +4003,11 @@ static int prove_fs2_begin_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpg
   {
     ProfScope link(ctx, 22, st);
     prover_transcript(st, nb, sched.steps + sched.cut[0], sched.cut[1] - sched.cut[0], f.states, dA, 3, nullptr, 0, nullptr, io.gadget_label,
-                      f.chi);
+                      f.chi, c->nchi, sched.labels);
   }
   HIPCK(ctx, hipMemcpyAsync(f.A1, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
   if (io.commitments) HIPCK(ctx, hipMemcpyAsync(io.commitments, dA, nb * 3 * 64, hipMemcpyDeviceToDevice, st));
-  if (io.chi_out) HIPCK(ctx, hipMemcpyAsync(io.chi_out, f.chi, nb * 32, hipMemcpyDeviceToDevice, st));
+  if (io.chi_out) HIPCK(ctx, hipMemcpyAsync(io.chi_out, f.chi, nb * c->nchi * 32, hipMemcpyDeviceToDevice, st));
   if (io.states_out) HIPCK(ctx, hipMemcpyAsync(io.states_out, f.states, nb * 32, hipMemcpyDeviceToDevice, st));   // (little-endian words)
   return launch_ok(ctx);
 }
@@ -3974,7 +4028,7 @@ static int prove_fs2_begin_entry(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgp
       const void *in_host[8] = {a.states_in, a.a_L, a.a_R, a.a_O, a.s_L, a.s_R, a.vector_keys, a.blindings};
       const size_t in_bytes[8] = {nb * 32, tot, tot, tot, n1 && a.s_L ? tot : 0, n1 && a.s_R ? tot : 0, n1 && a.vector_keys ? nb * 32 : 0,
                                   nb * 3 * 32};
-      const size_t out_bytes[3] = {nb * 3 * 64, nb * 32, nb * 32};
+      const size_t out_bytes[3] = {nb * 3 * 64, nb * c->nchi * 32, nb * 32};
       uint8_t *in[8], *out[3];
       CK(prove_fs_stage(ctx, 8, in_host, in_bytes, in, 3, out_bytes, out));
       CK(prove_fs2_begin_locked(ctx, g, c, nb, n1, {in[0], a.gadget_label, in[1], in[2], in[3], in[4], in[5], in[6], in[7], out[0], out[1], out[2]},
@@ -4017,7 +4071,7 @@ static int prove_fs2_finish_locked(bpgpu_ctx *ctx, const bpgpu_gens *g, const bp
   const Fs2Arrays f = fs2_arrays(s);
   ProveFsWs w;
   ProverSched sched;
-  CK(prover_schedule(ctx, true, d.m, d.padded_n, &sched));
+  CK(prover_schedule(ctx, c, d.m, d.padded_n, &sched));
   CK(prove_fs_workspace(ctx, s->nb, d, &w));
   return prove_fs_chain_locked(ctx, g, c, s, w, io, {f.states, sched, 1, f.chi, f.bl1, f.A1, d.n - s->wn, s->wn});
 }
@@ -4325,8 +4379,14 @@ void bpgpu_internal_prof_mark(bpgpu_ctx *ctx, int kind) { if (ctx->prof) ProfSco
 int bpgpu_internal_flag_reset(bpgpu_ctx *ctx) { return flag_reset(ctx); }
 int bpgpu_internal_checked_wait(bpgpu_ctx *ctx) { return checked_download(ctx, {}); }
 void bpgpu_internal_circuit_dims(const bpgpu_circuit *c, size_t *n, size_t *m, size_t *nchi) { *n = c->n; *m = c->m; *nchi = c->nchi; }
+// a two-phase prover's circuit and label: a numeric circuit has no gadget challenge (bpgpu_r1cs_prove_fs); with labels attached the
+// call's label must be null; without, one label per schedule (required only where the call has work: need_label)
+int bpgpu_internal_prove_fs2_labels(const bpgpu_circuit *c, const uint8_t *gadget_label, bool need_label) {
+  if (!c->nchi) return BPGPU_E_ARG;
+  return gadget_label_rule(c, gadget_label, c->nchi == 1 && (gadget_label || !need_label));
+}
 int bpgpu_internal_prove_fs2_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1) {
-  if (c->nchi != 1) return BPGPU_E_ARG;
+  if (!c->nchi) return BPGPU_E_ARG;
   if (!nb) return BPGPU_OK;
   if (n1 >= c->n) return BPGPU_E_LEN;
   if (prove_fs_dims(c).padded_n > g->cap) return BPGPU_E_GENS;

@@ -39,9 +39,12 @@ BPGPU_HIDDEN int bpgpu_internal_checked_wait(bpgpu_ctx *ctx);
 // nb == 0: nothing to do)
 BPGPU_HIDDEN void bpgpu_internal_circuit_dims(const bpgpu_circuit *c, size_t *n, size_t *m, size_t *nchi);
 BPGPU_HIDDEN int bpgpu_internal_prove_fs2_shape(const bpgpu_gens *g, const bpgpu_circuit *c, size_t nb, size_t n1);
+// ... and on the circuit's labels: BPGPU_E_ARG for a numeric circuit, for a call's label beside attached ones
+// (bpgpu_circuit_set_gadget_labels), and, with none attached, for nchi > 1 or (need_label) a null label
+BPGPU_HIDDEN int bpgpu_internal_prove_fs2_labels(const bpgpu_circuit *c, const uint8_t *gadget_label, bool need_label);
 // The chains of bpgpu_r1cs_prove_fs2_begin and _finish on one session that lives for the call (mutex held, shapes and arguments checked,
 // nb > 0; every pointer but the label is HBM; asynchronous).  `between` runs once _begin's launches are enqueued, with the session's
-// device copy of the gadget challenges (nb x 32, plain): it enqueues whatever produces the phase-2 operands.
+// device copy of the gadget challenges (nb x nchi x 32, plain, prover-major): it enqueues whatever produces the phase-2 operands.
 struct bpgpu_internal_fs2 {
   const void *states_in;
   const uint8_t *gadget_label;                                                  // host memory

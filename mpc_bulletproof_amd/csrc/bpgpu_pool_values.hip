@@ -26,6 +26,17 @@ int bpgpu_pool_circuit_create_param(bpgpu_pool *pool, size_t q, size_t nchi, con
     return BPGPU_OK;
   });
 }
+int bpgpu_pool_circuit_set_gadget_labels(bpgpu_pool *pool, bpgpu_pool_circuit *pc, const uint8_t *labels) {
+  if (!pool || !pc || pc->pool != pool || !labels) return BPGPU_E_ARG;
+  return noexcept_abi([&]() -> int {
+    std::lock_guard<std::mutex> lk(pool->mu);
+    for (size_t s = 0; s < pc->at.size(); s++) {    // (slots of one device share their owner's handle; no pool call runs meanwhile)
+      if (pool->owner[s] != s) continue;
+      if (const int rc = bpgpu_circuit_set_gadget_labels(pool->ctx[s], pc->at[s], labels)) return refuse(pool, rc, "bpgpu_pool_circuit_set_gadget_labels");
+    }
+    return BPGPU_OK;
+  });
+}
 int bpgpu_pool_witness_create(bpgpu_pool *pool, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
                               const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff, bpgpu_pool_witness **out) {
   if (out) *out = nullptr;
@@ -76,7 +87,7 @@ int bpgpu_pool_r1cs_prove_values(bpgpu_pool *pool, const bpgpu_pool_gens *pg, co
       if (lo[s + 1] > lo[s])
         if (const int rc = bpgpu_internal_prove_values_check(pool->ctx[s], pg->at[s], pc->at[s], pw->at[s], lo[s + 1] - lo[s], whole))
           return refuse(pool, rc, what);
-    const bool two = pc->nchi == 1;
+    const bool two = pc->nchi != 0;
     size_t k = 0;
     while (((size_t)1 << k) < pc->n) k++;
     const size_t m = pc->m, bw = pc->n * 32, bin = 2 * pw->ninp * 32, bkey = two ? 64 : 32, bbl = (two ? 11 : 8) * 32, bpts = (11 + 2 * k) * 64,
@@ -91,7 +102,7 @@ int bpgpu_pool_r1cs_prove_values(bpgpu_pool *pool, const bpgpu_pool_gens *pg, co
                                        blindings + a * bbl, at(V, a * m * 64), at(V_compressed, a * m * 32), ok + a,
                                        first_bad_row ? first_bad_row + a : nullptr, first_bad_gate ? first_bad_gate + a : nullptr,
                                        proof_points + a * bpts, proof_scalars + a * 5 * 32, at(wire, a * bwire), at(challenges_out, a * bch),
-                                       at(states_out, a * 32), at(gadget_challenges_out, a * 32), at(a_L_out, a * bw), at(a_R_out, a * bw),
+                                       at(states_out, a * 32), at(gadget_challenges_out, a * pc->nchi * 32), at(a_L_out, a * bw), at(a_R_out, a * bw),
                                        at(a_O_out, a * bw));
       };
     }

@@ -307,9 +307,10 @@ int wit_prover_pointers(const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
 int fs2_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const Fs2Io &a) {
   if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
   if (!wit_program_of(w, c)) return BPGPU_E_ARG;
+  WCK(bpgpu_internal_prove_fs2_labels(c, a.gadget_label, false));
   WCK(bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1));
   if (!nb) return BPGPU_OK;
-  if (!a.gadget_label) return BPGPU_E_ARG;
+  WCK(bpgpu_internal_prove_fs2_labels(c, a.gadget_label, true));   // the call's label, unless the circuit has its own
   return wit_prover_pointers(w, nb, a);
 }
 struct Fs2Between { const Entered *e; const bpgpu_witness *w; size_t nb; const WitRun *run; void *L2, *R2, *O2; };
@@ -370,13 +371,15 @@ int fs2_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, co
 using PvIo = bpgpu_internal_pv;
 int pv_check(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const PvIo &a) {
   if (!ctx || !g || !c || !w) return BPGPU_E_ARG;
-  if (!wit_program_of(w, c) || w->nchi > 1) return BPGPU_E_ARG;                       // not this circuit's program, or no shape of the call
-  const bool two = w->nchi == 1;
+  if (!wit_program_of(w, c)) return BPGPU_E_ARG;                                      // not this circuit's program
+  const bool two = w->nchi != 0;
   if (!two && w->n1 != w->n) return BPGPU_E_ARG;
+  if (two) WCK(bpgpu_internal_prove_fs2_labels(c, a.gadget_label, false));            // several challenges: only with the circuit's own labels
   WCK(two ? bpgpu_internal_prove_fs2_shape(g, c, nb, w->n1) : bpgpu_internal_prove_fs_shape(g, c, nb));
   WCK(bpgpu_internal_commit_values_shape(nb, w->m));
   if (!nb) return BPGPU_OK;
-  if (two != (a.gadget_label != nullptr)) return BPGPU_E_ARG;                         // the label goes with the gadget challenge
+  // the label goes with the gadget challenge: the call's, unless the circuit has its own
+  if (two ? bpgpu_internal_prove_fs2_labels(c, a.gadget_label, true) != BPGPU_OK : a.gadget_label != nullptr) return BPGPU_E_ARG;
   if (bpgpu_internal_shard_world(ctx) > 1) return BPGPU_E_ARG;                        // partial sums cannot be hashed
   if (!a.ok) return BPGPU_E_ARG;
   return wit_prover_pointers(w, nb, {a.init_states, a.gadget_label, a.v, a.inputs, a.s_L, a.s_R, a.vector_keys, a.v_blinding, a.blindings,
@@ -394,14 +397,14 @@ int pv_enter(const Entered &e, const bpgpu_circuit *c, size_t nb) {
 // after the commitments, the witness planes and the gadget challenge stay in pool memory (or in the caller's buffers, where given).
 int pv_locked(const Entered &e, const bpgpu_gens *g, const bpgpu_circuit *c, const bpgpu_witness *w, size_t nb, const PvIo &io) {
   bpgpu_ctx *ctx = e.ctx;
-  const bool two = w->nchi == 1;
-  const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n;
+  const bool two = w->nchi != 0;
+  const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n, nchis = nb * w->nchi;
   Scratch sc(ctx);
-  Words8 *mid = (Words8 *)sc.take((nb + (two && !io.gadget_challenges_out ? nb : 0) + (io.a_L_out ? 0 : 3 * plane)) * 32);
+  Words8 *mid = (Words8 *)sc.take((nb + (two && !io.gadget_challenges_out ? nchis : 0) + (io.a_L_out ? 0 : 3 * plane)) * 32);
   if (!mid) return BPGPU_E_OOM;
   Words8 *at = mid + nb;
   void *chi = nullptr, *L = io.a_L_out, *R = io.a_R_out, *O = io.a_O_out;
-  if (two) { chi = io.gadget_challenges_out; if (!chi) { chi = at; at += nb; } }
+  if (two) { chi = io.gadget_challenges_out; if (!chi) { chi = at; at += nchis; } }
   if (!L) { L = at; R = at + plane; O = at + 2 * plane; }
   WCK(bpgpu_internal_commit_values(ctx, g, nb, m, io.v, io.v_blinding, io.init_states, io.V, io.V_compressed, mid));
   if (!two) {
@@ -752,7 +755,7 @@ int bpgpu_r1cs_prove_fs2(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_circui
                                 nb * m * 32, nb * 11 * 32};
     void *out_host[9] = {a.proof_points, a.proof_scalars, a.challenges_out, a.states_out, a.chi_out, a.aL, a.aR, a.aO, a.wire};
     const size_t out_bytes[9] = {nb * (11 + 2 * k) * 64, nb * 5 * 32, a.challenges_out ? nb * (5 + k) * 32 : 0, a.states_out ? nb * 32 : 0,
-                                 a.chi_out ? nb * 32 : 0, a.aL ? plane : 0, a.aL ? plane : 0, a.aL ? plane : 0,
+                                 a.chi_out ? nb * w->nchi * 32 : 0, a.aL ? plane : 0, a.aL ? plane : 0, a.aL ? plane : 0,
                                  a.wire ? nb * (1 + 14 * 32 + (2 * k + 2) * 32) : 0};
     size_t total = 0;
     for (size_t b : in_bytes) total += b;
@@ -807,7 +810,7 @@ int bpgpu_r1cs_prove_values(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
     WCK(e.enter());
     WCK(pv_enter(e, c, nb));
     Scratch sc(ctx);
-    const bool two = w->nchi == 1;
+    const bool two = w->nchi != 0;
     const size_t n = w->n, m = w->m, k = lg_padded(n), plane = nb * n * 32;
     // staging: the operands in the header's order (an absent one, of zero bytes, gets a null device pointer), then the results -- the
     // optional ones downloaded only when asked for, every part 256-byte aligned (the verdict words and the wire form are no
@@ -818,7 +821,7 @@ int bpgpu_r1cs_prove_values(bpgpu_ctx *ctx, const bpgpu_gens *g, const bpgpu_cir
     void *out_host[14] = {a.V, a.V_compressed, a.ok, a.first_bad_row, a.first_bad_gate, a.proof_points, a.proof_scalars, a.wire, a.challenges_out,
                           a.states_out, two ? a.gadget_challenges_out : nullptr, a.a_L_out, a.a_R_out, a.a_O_out};
     const size_t out_all[14] = {nb * m * 64, nb * m * 32, nb * 4, nb * 8, nb * 8, nb * (11 + 2 * k) * 64, nb * 5 * 32,
-                                nb * (1 + (two ? 14 : 11) * 32 + (2 * k + 2) * 32), nb * (5 + k) * 32, nb * 32, nb * 32, plane, plane, plane};
+                                nb * (1 + (two ? 14 : 11) * 32 + (2 * k + 2) * 32), nb * (5 + k) * 32, nb * 32, nb * w->nchi * 32, plane, plane, plane};
     size_t out_bytes[14], total = 0;
     for (size_t b : in_bytes) total += up256(b);
     for (int i = 0; i < 14; i++) { out_bytes[i] = out_host[i] ? out_all[i] : 0; total += up256(out_bytes[i]); }

@@ -179,8 +179,8 @@ __constant__ Label TR_LABELS[LB_COUNT] = {
 // the replay of proof p (the step interpreter of k_verify_transcript and k_verify_transcript_ragged)
 __device__ __forceinline__ void verify_transcript_lane(size_t p, size_t nvar, size_t nch, const TrStep *steps, int nsteps,
                                                        const Words8 *init_state, const Words8 *points, const Words8 *scalars,
-                                                       Words8 *challenges, int32_t *tr_bad, const Label &gadget_label, Words8 *chi,
-                                                       size_t nchi) {
+                                                       Words8 *challenges, int32_t *tr_bad, const Label &gadget_label,
+                                                       const Label *gadget_labels, Words8 *chi, size_t nchi) {
   const Words8 *pt = points + p * nvar * 2;
   const Words8 *sc = scalars + p * 5;
   Words8 *ch = challenges + p * nch;
@@ -220,9 +220,12 @@ __device__ __forceinline__ void verify_transcript_lane(size_t p, size_t nvar, si
         chain_hash<9>(st, 0x00, lab, tail);
         break;
       }
-      case TS_GADGET_CHALLENGE:   // cs.challenge_scalar(gadget label) inside the randomized-constraints callback (verifier.rs:366-385)
-        tr_challenge_scalar(st, gadget_label, &chi[p * nchi + s.src]);
+      case TS_GADGET_CHALLENGE: {   // cs.challenge_scalar(gadget label) inside the randomized-constraints callback (verifier.rs:366-385):
+        // draw s.src under the circuit's own label s.src (the table behind the steps), or the launch's one label
+        const Label gl = gadget_labels ? gadget_labels[s.src] : gadget_label;
+        tr_challenge_scalar(st, gl, &chi[p * nchi + s.src]);
         break;
+      }
       default:
         tr_challenge_scalar(st, lab, &ch[s.src]);
         break;
@@ -232,14 +235,14 @@ __device__ __forceinline__ void verify_transcript_lane(size_t p, size_t nvar, si
 }
 __global__ void __launch_bounds__(64) k_verify_transcript(size_t nb, size_t nvar, size_t nch, const TrStep *steps, int nsteps,
                                                           const Words8 *init_state, const Words8 *points, const Words8 *scalars,
-                                                          Words8 *challenges, int32_t *tr_bad, Label gadget_label, Words8 *chi,
-                                                          size_t nchi) {
+                                                          Words8 *challenges, int32_t *tr_bad, Label gadget_label,
+                                                          const Label *gadget_labels, Words8 *chi, size_t nchi) {
   // (no raised wave priority here, unlike the other short links of a batch's chain: a lone wave of dependent 64-bit operations
   // issues back to back, so at priority 3 the 16 transcript waves of each of ~20 batches in flight kept their SIMDs to
   // themselves for 0.7 ms at a time -- measured 3.54 -> 3.95 M verifications/s for the device-transcript leg without it)
   size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nb) return;
-  verify_transcript_lane(p, nvar, nch, steps, nsteps, init_state, points, scalars, challenges, tr_bad, gadget_label, chi, nchi);
+  verify_transcript_lane(p, nvar, nch, steps, nsteps, init_state, points, scalars, challenges, tr_bad, gadget_label, gadget_labels, chi, nchi);
 }
 // The replay for the segments of ONE mixed check (bpgpu_r1cs_verify_mixed_wire_*), each with its own schedule, gadget label and
 // arrays.  Blocks of 64 lanes map to segments through the table's block prefix (blk0), so every wave runs ONE segment's steps:
@@ -247,7 +250,7 @@ __global__ void __launch_bounds__(64) k_verify_transcript(size_t nb, size_t nvar
 // (Priority unraised, as above.)
 struct TrRagSeg {
   const TrStep *steps; const Words8 *init_state, *points, *scalars; Words8 *challenges, *chi; int32_t *tr_bad;
-  Label gadget_label; uint32_t nsteps, nb, blk0, nvar, nch, nchi;
+  Label gadget_label; const Label *gadget_labels; uint32_t nsteps, nb, blk0, nvar, nch, nchi;   // gadget_labels: HBM, or null (the one label)
 };
 struct TrRag { TrRagSeg seg[MIX_SEG_MAX]; uint32_t nseg; };
 static_assert(sizeof(TrRag) <= 4096, "k_verify_transcript_ragged's arguments exceed 4 KB");
@@ -258,7 +261,7 @@ __global__ void __launch_bounds__(64) k_verify_transcript_ragged(TrRag a) {
   const size_t p = (size_t)(blockIdx.x - g.blk0) * 64 + threadIdx.x;
   if (p >= g.nb) return;
   verify_transcript_lane(p, g.nvar, g.nch, g.steps, (int)g.nsteps, g.init_state, g.points, g.scalars, g.challenges, g.tr_bad, g.gadget_label,
-                         g.chi, g.nchi);
+                         g.gadget_labels, g.chi, g.nchi);
 }
 void verify_transcript_ragged(hipStream_t st, const TrSegIn *seg, size_t nseg) {
   TrRag a{};
@@ -271,7 +274,7 @@ void verify_transcript_ragged(hipStream_t st, const TrSegIn *seg, size_t nseg) {
     r.gadget_label = Label{{0, 0, 0, 0}};
     if (g.gadget_label) for (int i = 0; i < 32; i++) r.gadget_label.w[i >> 3] |= (uint64_t)g.gadget_label[i] << (8 * (i & 7));
     r.nsteps = (uint32_t)g.nsteps; r.nb = (uint32_t)g.nb; r.blk0 = blk; r.nvar = (uint32_t)(11 + g.m + 2 * g.k); r.nch = (uint32_t)(6 + g.k);
-    r.nchi = (uint32_t)g.nchi;
+    r.nchi = (uint32_t)g.nchi; r.gadget_labels = (const Label *)g.gadget_labels_dev;
     blk += (uint32_t)((g.nb + 63) / 64);
   }
   if (!blk) return;
@@ -309,15 +312,15 @@ int transcript_schedule(TrStep *out, size_t m, size_t k, size_t padded_n, size_t
   add(TS_CHALLENGE, LB_r, 5, 0, 0);                                               // verifier.rs:506
   return n;
 }
-size_t transcript_schedule_max(size_t m, size_t k) { return 48 + m + 3 * k; }
+size_t transcript_schedule_max(size_t m, size_t k, size_t nchi) { return 48 + m + 3 * k + nchi; }
 void verify_transcript(hipStream_t st, size_t nb, size_t m, size_t k, const TrStep *steps_dev, int nsteps, const Words8 *init_state,
                        const Words8 *points, const Words8 *scalars, Words8 *challenges, int32_t *tr_bad,
-                       const uint8_t *gadget_label, Words8 *chi_out, size_t nchi) {
+                       const uint8_t *gadget_label, Words8 *chi_out, size_t nchi, const uint8_t *gadget_labels_dev) {
   if (!nb) return;
   Label gl{{0, 0, 0, 0}};
   if (gadget_label) for (int i = 0; i < 32; i++) gl.w[i >> 3] |= (uint64_t)gadget_label[i] << (8 * (i & 7));
   hipLaunchKernelGGL(k_verify_transcript, dim3((nb + 63) / 64), dim3(64), 0, st, nb, 11 + m + 2 * k, 6 + k, steps_dev, nsteps,
-                     init_state, points, scalars, challenges, tr_bad, gl, chi_out, nchi);
+                     init_state, points, scalars, challenges, tr_bad, gl, (const Label *)gadget_labels_dev, chi_out, nchi);
 }
 // ok[p] &= !tr_bad[p]
 __global__ void k_and_not(int32_t *ok, const int32_t *bad, size_t n) {
@@ -597,7 +600,7 @@ void ipp_round_challenge(hipStream_t st, size_t nb, uint64_t *states, const Word
 constexpr uint32_t TS_SRC_IDENTITY = 0xFFFFFFFFu;
 __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrStep *steps, int nsteps, uint64_t *states, const Words8 *points,
                                                           size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges,
-                                                          Label gadget_label, Words8 *chi) {
+                                                          Label gadget_label, const Label *gadget_labels, Words8 *chi, size_t nchi) {
   // (no raised wave priority: the note in k_verify_transcript holds for a prover batch that runs beside others)
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= nb) return;
@@ -641,9 +644,12 @@ __global__ void __launch_bounds__(64) k_prover_transcript(size_t nb, const TrSte
         chain_hash<9>(st, 0x00, lab, tail);
         break;
       }
-      case TS_GADGET_CHALLENGE:   // cs.challenge_scalar(gadget label) inside the randomized-constraints callback (prover.rs:393-408)
-        tr_challenge_scalar(st, gadget_label, &chi[p]);
+      case TS_GADGET_CHALLENGE: {   // cs.challenge_scalar(gadget label) inside the randomized-constraints callback (prover.rs:393-408):
+        // draw s.src under the circuit's own label s.src, or the launch's one label
+        const Label gl = gadget_labels ? gadget_labels[s.src] : gadget_label;
+        tr_challenge_scalar(st, gl, &chi[p * nchi + s.src]);
         break;
+      }
       default:
         tr_challenge_scalar(st, lab, &challenges[(size_t)s.src * nb + p]);
         break;
@@ -686,11 +692,12 @@ void commit_transcript(hipStream_t st, size_t nb, size_t m, const Words8 *states
 }
 // the step list and its slices: slice j = steps [cut[j], cut[j + 1]).  Points are indexed within the slice's own array (A_I1 A_O1 S1 |
 // T_1 T_3 T_4 T_5 T_6), scalars as t_x t_x_blinding e_blinding, challenges as y z u x w.  One phase: the three slices above.  Two phases
-// -- a circuit WITH randomized constraints and one gadget challenge (bpgpu_r1cs_prove_fs2_begin / _finish) -- four:
-//   slice 0: append_u64("m"), A_I1 A_O1 S1, the 2-phase separator, the gadget challenge (into chi[p])   -> the host's gadget
+// -- a circuit WITH randomized constraints and nchi gadget challenges (bpgpu_r1cs_prove_fs2_begin / _finish) -- four:
+//   slice 0: append_u64("m"), A_I1 A_O1 S1, the 2-phase separator, the gadget challenges (chi[p * nchi + j]) -> the host's gadget
 //   slice 1: A_I2 A_O2 S2 (the second commitment's output, indexed 0..2), y, z                          -> the polynomial build
 //   slice 2, 3: as slices 1, 2 above
-int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t padded_n, int cut[5]) {
+int prover_transcript_schedule(TrStep *out, size_t nchi, size_t m, size_t padded_n, int cut[5]) {
+  const bool two_phase = nchi != 0;
   int n = 0, nc = 0;
   auto add = [&](uint8_t kind, uint8_t label, uint32_t src, uint64_t value) {
     out[n].kind = kind; out[n].label = label; out[n].validate = 0; out[n].pad = 0; out[n].src = src; out[n].value = value; n++;
@@ -700,7 +707,7 @@ int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t pad
   add(TS_POINT, LB_AI1, 0, 0); add(TS_POINT, LB_AO1, 1, 0); add(TS_POINT, LB_S1, 2, 0);          // :496-498
   if (two_phase) {
     add(TS_DOMSEP, LB_2phase, 0, 0);                                                             // :391
-    add(TS_GADGET_CHALLENGE, LB_z, 0, 0);                                                        // :393-408 (the label is the launch's)
+    for (size_t j = 0; j < nchi; j++) add(TS_GADGET_CHALLENGE, LB_z, (uint32_t)j, 0);            // :393-408 (the labels are the launch's)
     cut[nc++] = n;
     add(TS_POINT, LB_AI2, 0, 0); add(TS_POINT, LB_AO2, 1, 0); add(TS_POINT, LB_S2, 2, 0);        // :578-580
   } else {
@@ -721,12 +728,12 @@ int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t pad
 }
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
                        size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges, const uint8_t *gadget_label,
-                       Words8 *chi) {
+                       Words8 *chi, size_t nchi, const uint8_t *gadget_labels_dev) {
   if (!nb || nsteps <= 0) return;
   Label gl{{0, 0, 0, 0}};
   if (gadget_label) for (int i = 0; i < 32; i++) gl.w[i >> 3] |= (uint64_t)gadget_label[i] << (8 * (i & 7));
   hipLaunchKernelGGL(k_prover_transcript, dim3((nb + 63) / 64), dim3(64), 0, st, nb, steps_dev, nsteps, states, points, pt_stride, scalars,
-                     sc_stride, challenges, gl, chi);
+                     sc_stride, challenges, gl, (const Label *)gadget_labels_dev, chi, nchi);
 }
 
 }  // namespace bpk

@@ -335,18 +335,26 @@ void zpow_table(hipStream_t st, size_t nb, size_t q, const Words8 *z, size_t z_s
 
 // ---- device-side verifier transcript (k_transcript.hip) ------------------------------
 struct TrStep { uint8_t kind, label, validate, pad; uint32_t src; uint64_t value; };
-size_t transcript_schedule_max(size_t m, size_t k);
+size_t transcript_schedule_max(size_t m, size_t k, size_t nchi = 0);
 int transcript_schedule(TrStep *out, size_t m, size_t k, size_t padded_n, size_t nchi = 0);   // host: fills the step list, returns its length
                                                                                                 // (nchi > 0: two-phase circuit with nchi gadget challenges)
-// gadget_label (32 bytes, zero-padded) + chi_out (nb x nchi): the challenge of a second-phase gadget (schedule built with nchi = 1)
+// A gadget label is 32 bytes, zero-padded; a label TABLE is nchi of them in draw order, resident in HBM at an 8-byte aligned address
+// (the callers upload it behind the step list, in the same allocation: gadget_label_slots steps' room).
+constexpr size_t GADGET_LABEL_BYTES = 32;
+constexpr size_t gadget_label_slots(size_t nchi) { return nchi * GADGET_LABEL_BYTES / sizeof(TrStep); }
+// chi_out (nb x nchi): the challenges of the second-phase gadgets.  Draw j hashes under gadget_labels_dev[j] (a label table), or, with
+// no table, under gadget_label (host memory; schedule built with nchi = 1)
 void verify_transcript(hipStream_t st, size_t nb, size_t m, size_t k, const TrStep *steps_dev, int nsteps, const Words8 *init_state,
                        const Words8 *points, const Words8 *scalars, Words8 *challenges, int32_t *tr_bad,
-                       const uint8_t *gadget_label = nullptr, Words8 *chi_out = nullptr, size_t nchi = 0);
+                       const uint8_t *gadget_label = nullptr, Words8 *chi_out = nullptr, size_t nchi = 0,
+                       const uint8_t *gadget_labels_dev = nullptr);
 // the same for the segments of ONE mixed check in one launch (nseg <= MIX_SEG_MAX, host array): segment s replays nb proofs of
-// (m, k, nchi) on its own schedule (steps_dev, nsteps: resident in HBM), arrays and gadget label (host memory, or null)
+// (m, k, nchi) on its own schedule (steps_dev, nsteps: resident in HBM), arrays and gadget label (host memory, or null) or label
+// table (HBM, or null)
 struct TrSegIn {
   const TrStep *steps_dev; int nsteps; size_t nb, m, k, nchi;
   const Words8 *init_state, *points, *scalars; Words8 *challenges, *chi; int32_t *tr_bad; const uint8_t *gadget_label;
+  const uint8_t *gadget_labels_dev;
 };
 void verify_transcript_ragged(hipStream_t st, const TrSegIn *seg, size_t nseg);
 void and_not(hipStream_t st, int32_t *ok, const int32_t *bad, size_t n);
@@ -441,16 +449,17 @@ void ipp_round_tail(hipStream_t st, size_t nb, const JacRaw *sums, uint64_t *sta
 // ---- the one-call prover (bpgpu_r1cs_prove_fs): the prover's transcript slices (k_transcript.hip) and the links between the stages
 // (k_prove_fs.hip) ------------------------------------------------------------------------------------
 // host: the prover's step list and its slices, slice j = steps [cut[j], cut[j + 1]).  A one-phase circuit: 22 steps in three slices,
-// up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator.  A two-phase circuit with one gadget challenge: 24
-// steps in four, up to the gadget challenge | A_I2 A_O2 S2, y, z | then the same two
-constexpr int PROVER_SCHEDULE_MAX = 24;
-int prover_transcript_schedule(TrStep *out, bool two_phase, size_t m, size_t padded_n, int cut[5]);
+// up to y, z | T points, u, x | t_x t_x_blinding e_blinding, w, the IPP separator.  A two-phase circuit with nchi <= 8 gadget
+// challenges (nchi = 0: one phase): 23 + nchi steps in four, up to the last gadget challenge | A_I2 A_O2 S2, y, z | then the same two
+constexpr int PROVER_SCHEDULE_MAX = 32;
+int prover_transcript_schedule(TrStep *out, size_t nchi, size_t m, size_t padded_n, int cut[5]);
 // one slice for nb provers, a lane each; states: 4 x u64 per prover, updated.  A step's src indexes points (pt_stride per prover),
-// scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p].  A TS_GADGET_CHALLENGE step draws under
-// gadget_label (32 bytes, zero-padded, host memory) into chi[p]
+// scalars (sc_stride per prover) or the challenge ARRAYS: challenges[src * nb + p].  TS_GADGET_CHALLENGE step j draws into
+// chi[p * nchi + j] under gadget_labels_dev[j] (a label table, as verify_transcript's) or, with no table, under gadget_label (32 bytes,
+// zero-padded, host memory)
 void prover_transcript(hipStream_t st, size_t nb, const TrStep *steps_dev, int nsteps, uint64_t *states, const Words8 *points,
                        size_t pt_stride, const Words8 *scalars, size_t sc_stride, Words8 *challenges, const uint8_t *gadget_label = nullptr,
-                       Words8 *chi = nullptr);
+                       Words8 *chi = nullptr, size_t nchi = 1, const uint8_t *gadget_labels_dev = nullptr);
 // the chain before Prover::prove (bpgpu_r1cs_commit_values), a lane per prover: r1cs_domain_sep, then append_point("V", V_j) over the
 // prover's m boundary points (nb x m, prover-major).  states_in / states_out: nb x 32 B, may alias
 void commit_transcript(hipStream_t st, size_t nb, size_t m, const Words8 *states_in, const Words8 *points, Words8 *states_out);

@@ -134,6 +134,11 @@ def _u32s(xs, pad=1):
     return (C.c_uint32 * max(len(xs), pad))(*xs)
 
 
+def _label(gadget_label):
+    """a gadget label zero-padded to 32 bytes, or None (a circuit with attached labels, circuit_set_gadget_labels)"""
+    return None if gadget_label is None else _buf((bytes(gadget_label) + bytes(32))[:32])
+
+
 def witness_plan(n, n1, nchi, op, row_ptr, kind, idx, nb):
     """the dependency levels of a gate program and the launch form of each phase for nb provers, as a dict over WIT_PLAN_FIELDS
     (needs no device)"""
@@ -186,16 +191,19 @@ ProveValues = collections.namedtuple("ProveValues", "ok first_bad_row first_bad_
                                                     "chi planes")
 
 
-def _prove_values_host(call, nb, n, m, lab, init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness):
+def _prove_values_host(call, nb, n, m, lab, init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness,
+                       nchi=None):
     """the host form's buffers around `call(nb, operands..., results...)`: bpgpu_r1cs_prove_values, or the pool's -> ProveValues (chi
-    None for a one-phase circuit, wire and planes None unless asked for)"""
-    two = lab is not None
+    None for a one-phase circuit, wire and planes None unless asked for).  nchi: the circuit's gadget challenges (None: one with a label,
+    none without)"""
+    nchi = (1 if lab is not None else 0) if nchi is None else nchi
+    two = nchi != 0
     k = max(n - 1, 0).bit_length()
     nvar, plen = 11 + 2 * k, 1 + (14 if two else 11) * 32 + (2 * k + 2) * 32
     ok, row, gate = (C.c_int32 * max(nb, 1))(), (C.c_int64 * max(nb, 1))(), (C.c_int64 * max(nb, 1))()
     V, Vc = _out(64 * nb * m), _out(32 * nb * m)
     pts, sc, ch, so = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb)
-    chi = _out(32 * nb) if two else None
+    chi = _out(32 * nb * nchi) if two else None
     wire = _out(nb * plen) if want_wire else None
     planes = [_out(32 * nb * n) if want_witness else None for _ in range(3)]
     opt = lambda b: b if b is None or isinstance(b, C.c_void_p) else _buf(b)     # noqa: E731
@@ -203,7 +211,7 @@ def _prove_values_host(call, nb, n, m, lab, init_states, v, v_blinding, inputs, 
          gate, pts, sc, wire, ch, so, chi, *planes)
     return ProveValues(list(ok)[:nb], list(row)[:nb], list(gate)[:nb], bytes(V)[:64 * nb * m], bytes(Vc)[:32 * nb * m],
                        bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
-                       bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb] if two else None,
+                       bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb * nchi] if two else None,
                        tuple(bytes(p)[:32 * nb * n] for p in planes) if want_witness else None)
 
 
@@ -680,24 +688,23 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_commit_values_dev(self.ctx, gens, nb, m, d_v, d_v_blinding, d_states, d_V, d_V_compressed, d_states_out))
 
     def r1cs_prove_fs2_begin(self, gens, circuit, nb, n1, states, gadget_label, blindings, a_L=None, a_R=None, a_O=None, s_L=None, s_R=None,
-                             vector_keys=None):
+                             vector_keys=None, nchi=1):
         """The first of the two calls that prove nb provers of a two-phase circuit (include/bpgpu.h bpgpu_r1cs_prove_fs2_begin): the
         phase-1 commitments over n1 multipliers and the device transcript up to the gadget's challenge.  Witness and blindings
-        (nb x 3) in ark-ff Montgomery form -> (session, A_I1 A_O1 S1 nb x 3 x 64 B, gadget challenges nb x 32 B, states nb x 32 B)"""
+        (nb x 3) in ark-ff Montgomery form -> (session, A_I1 A_O1 S1 nb x 3 x 64 B, gadget challenges nb x nchi x 32 B, states nb x 32 B).
+        gadget_label None: the nchi labels attached to the circuit (circuit_set_gadget_labels)"""
         h = C.c_void_p()
-        com, chi, so = _out(64 * 3 * nb), _out(32 * nb), _out(32 * nb)
-        lab = (gadget_label + bytes(32))[:32]
+        com, chi, so = _out(64 * 3 * nb), _out(32 * nb * nchi), _out(32 * nb)
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin(self.ctx, gens, circuit, nb, n1, opt(states), _buf(lab), opt(a_L), opt(a_R), opt(a_O), opt(s_L),
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin(self.ctx, gens, circuit, nb, n1, opt(states), _label(gadget_label), opt(a_L), opt(a_R), opt(a_O), opt(s_L),
                                                  opt(s_R), opt(vector_keys), opt(blindings), C.byref(h), com, chi, so))
-        return (h if h.value else None), bytes(com)[:64 * 3 * nb], bytes(chi)[:32 * nb], bytes(so)[:32 * nb]
+        return (h if h.value else None), bytes(com)[:64 * 3 * nb], bytes(chi)[:32 * nb * nchi], bytes(so)[:32 * nb]
 
     def r1cs_prove_fs2_begin_dev(self, gens, circuit, nb, n1, d_states, gadget_label, d_blindings, d_a_L=None, d_a_R=None, d_a_O=None,
                                  d_s_L=None, d_s_R=None, d_vector_keys=None, d_commitments=None, d_chi=None, d_states_out=None):
         """the same on device pointers, asynchronous on the context's stream -> session; a malformed operand raises input_flag()"""
         h = C.c_void_p()
-        lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin_dev(self.ctx, gens, circuit, nb, n1, d_states, _buf(lab), d_a_L, d_a_R, d_a_O, d_s_L, d_s_R,
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_begin_dev(self.ctx, gens, circuit, nb, n1, d_states, _label(gadget_label), d_a_L, d_a_R, d_a_O, d_s_L, d_s_R,
                                                      d_vector_keys, d_blindings, C.byref(h), d_commitments, d_chi, d_states_out))
         return h if h.value else None
 
@@ -770,42 +777,42 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_witness_synthesize_dev(self.ctx, w, nb, phase, d_v, d_inputs, d_gadget_challenges, d_a_L, d_a_R, d_a_O))
 
     def r1cs_prove_fs2(self, gens, circuit, w, nb, n, m, states, gadget_label, blindings, v=None, inputs=None, v_blinding=None, s_L=None,
-                       s_R=None, vector_keys=None, want_wire=True, want_witness=False):
+                       s_R=None, vector_keys=None, want_wire=True, want_witness=False, nchi=1):
         """Prover::prove for nb provers of a two-phase circuit of n multipliers and m commitments in one call (bpgpu_r1cs_prove_fs2):
         the gates of program w on the device around the two transcript chains; blindings nb x 11 -> (proof_points, proof_scalars, wire
-        or None, challenges, states_out, gadget challenges, (a_L, a_R, a_O) or None)"""
+        or None, challenges, states_out, gadget challenges nb x nchi x 32 B, (a_L, a_R, a_O) or None).  gadget_label None: the nchi
+        labels attached to the circuit (circuit_set_gadget_labels)"""
         k = max(n - 1, 0).bit_length()
         nvar, plen = 11 + 2 * k, 1 + 14 * 32 + (2 * k + 2) * 32
-        pts, sc, ch, so, chi = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb), _out(32 * nb)
+        pts, sc, ch, so, chi = _out(64 * nb * nvar), _out(160 * nb), _out(32 * nb * (5 + k)), _out(32 * nb), _out(32 * nb * nchi)
         wire = _out(nb * plen) if want_wire else None
         planes = [_out(32 * nb * n) if want_witness else None for _ in range(3)]
-        lab = (gadget_label + bytes(32))[:32]
         opt = lambda b: _buf(b) if b is not None else None     # noqa: E731
-        self._ck(_lib.bpgpu_r1cs_prove_fs2(self.ctx, gens, circuit, w, nb, opt(states), _buf(lab), opt(v), opt(inputs), opt(s_L), opt(s_R),
+        self._ck(_lib.bpgpu_r1cs_prove_fs2(self.ctx, gens, circuit, w, nb, opt(states), _label(gadget_label), opt(v), opt(inputs), opt(s_L), opt(s_R),
                                            opt(vector_keys), opt(v_blinding), opt(blindings), pts, sc, wire, ch, so, chi, *planes))
         return (bytes(pts)[:64 * nb * nvar], bytes(sc)[:160 * nb], bytes(wire)[:nb * plen] if want_wire else None,
-                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb],
+                bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb], bytes(chi)[:32 * nb * nchi],
                 tuple(bytes(p)[:32 * nb * n] for p in planes) if want_witness else None)
 
     def r1cs_prove_fs2_dev(self, gens, circuit, w, nb, d_states, gadget_label, d_blindings, d_points, d_scalars, d_v=None, d_inputs=None,
                            d_v_blinding=None, d_s_L=None, d_s_R=None, d_vector_keys=None, d_wire=None, d_ch=None, d_states_out=None,
                            d_chi=None, d_a_L=None, d_a_R=None, d_a_O=None):
         """the same on device pointers, asynchronous on the context's stream; a malformed operand raises input_flag()"""
-        lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_prove_fs2_dev(self.ctx, gens, circuit, w, nb, d_states, _buf(lab), d_v, d_inputs, d_s_L, d_s_R, d_vector_keys,
+        self._ck(_lib.bpgpu_r1cs_prove_fs2_dev(self.ctx, gens, circuit, w, nb, d_states, _label(gadget_label), d_v, d_inputs, d_s_L, d_s_R, d_vector_keys,
                                                d_v_blinding, d_blindings, d_points, d_scalars, d_wire, d_ch, d_states_out, d_chi, d_a_L,
                                                d_a_R, d_a_O))
 
     def r1cs_prove_values(self, gens, circuit, w, nb, n, m, *, init_states, blindings, v=None, v_blinding=None, inputs=None,
                           gadget_label=None, s_L=None, s_R=None, vector_keys=None, want_wire=True, want_witness=False, dev=False,
-                          d_out=None):
+                          d_out=None, nchi=None):
         """Commitments, verdicts and proofs of nb provers from their committed values in one call (bpgpu_r1cs_prove_values): the stages
         commit_values -> witness synthesis -> constraints_satisfied -> prove_fs (gadget_label None: a numeric circuit, blindings
         nb x 8), or commit_values -> the prove_fs2 chain -> constraints_satisfied (a label: a two-phase circuit, blindings nb x 11),
         resident in between -> ProveValues; the proof rows of a prover with ok == 0 are zero bytes.  Operands are bytes, or c_void_p
         of page-locked memory.  dev=True: every operand a bpgpu_malloc pointer and d_out a dict of device pointers under ProveValues'
-        field names (a_L, a_R, a_O for the planes; ok, points and scalars required): asynchronous, nothing is returned"""
-        lab = None if gadget_label is None else _buf((gadget_label + bytes(32))[:32])
+        field names (a_L, a_R, a_O for the planes; ok, points and scalars required): asynchronous, nothing is returned.  nchi (with
+        gadget_label None): a two-phase circuit with that many attached labels (circuit_set_gadget_labels), blindings nb x 11"""
+        lab = _label(gadget_label)
         if dev:
             o = lambda name: d_out.get(name)     # noqa: E731
             self._ck(_lib.bpgpu_r1cs_prove_values_dev(self.ctx, gens, circuit, w, nb, init_states, lab, v, v_blinding, inputs, s_L, s_R,
@@ -814,7 +821,7 @@ class BpGpu:
                                                       o("chi"), o("a_L"), o("a_R"), o("a_O")))
             return None
         return _prove_values_host(lambda *a: self._ck(_lib.bpgpu_r1cs_prove_values(self.ctx, gens, circuit, w, *a)), nb, n, m, lab, init_states,
-                                  v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness)
+                                  v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness, nchi)
 
     def prover_destroy(self, prover):
         _lib.bpgpu_prover_destroy(self.ctx, prover)
@@ -948,6 +955,12 @@ class BpGpu:
         self._ck(_lib.bpgpu_circuit_create_param(self.ctx, q, nchi, rp, kd, ix, _buf(coeff), n_mul, m, C.byref(h)))
         return h
 
+    def circuit_set_gadget_labels(self, circuit, labels):
+        """attach the labels of a parametric circuit's nchi gadget challenges, in draw order (bpgpu_circuit_set_gadget_labels): a list
+        of byte strings, each zero-padded to 32 bytes; the device-transcript calls then take the circuit with gadget_label None"""
+        tab = None if labels is None else _buf(b"".join((bytes(x) + bytes(32))[:32] for x in labels))
+        self._ck(_lib.bpgpu_circuit_set_gadget_labels(self.ctx, circuit, tab))
+
     def r1cs_verify_batch_param(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, gadget_challenges, want_mega=True,
                                 want_scalars=False):
         np_ = 1 << k
@@ -964,8 +977,7 @@ class BpGpu:
         ok = (C.c_int32 * max(nb, 1))()
         mega = _out(64 * nb) if want_mega else None
         ch, chi = _out(32 * nb * (6 + k)), _out(32 * nb * max(nchi, 1))
-        lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_verify_batch_fs2(self.ctx, gens, circuit, nb, n1, k, _buf(init_states), _buf(lab), _buf(points), _buf(scalars), ok,
+        self._ck(_lib.bpgpu_r1cs_verify_batch_fs2(self.ctx, gens, circuit, nb, n1, k, _buf(init_states), _label(gadget_label), _buf(points), _buf(scalars), ok,
                                                   mega, ch, chi))
         return list(ok)[:nb], (bytes(mega)[:64 * nb] if want_mega else None), bytes(ch)[:32 * nb * (6 + k)], bytes(chi)[:32 * nb * nchi]
 
@@ -985,18 +997,17 @@ class BpGpu:
         self._ck(_lib.bpgpu_r1cs_verify_batch_wire_dev(self.ctx, gens, circuit, nb, n1, proof_len, d_proofs, d_commitments, d_init, d_ok))
 
     def r1cs_verify_batch_wire2(self, gens, circuit, nb, n1, proof_len, gadget_label, proofs, commitments, init_states):
-        """the same for a two-phase circuit (circuit_create_param, one gadget challenge drawn under gadget_label)"""
+        """the same for a two-phase circuit (circuit_create_param): one gadget challenge drawn under gadget_label, or, with
+        gadget_label None, the circuit's own under its attached labels (circuit_set_gadget_labels)"""
         if len(proofs) != nb * proof_len or len(init_states) != 32 * nb:
             raise BpGpuError(E_LEN, "r1cs_verify_batch_wire2: length mismatch")
         ok = (C.c_int32 * max(nb, 1))()
-        lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2(self.ctx, gens, circuit, nb, n1, proof_len, _buf(lab), _buf(proofs), _buf(commitments),
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2(self.ctx, gens, circuit, nb, n1, proof_len, _label(gadget_label), _buf(proofs), _buf(commitments),
                                                     _buf(init_states), ok))
         return list(ok)[:nb]
 
     def r1cs_verify_batch_wire2_dev(self, gens, circuit, nb, n1, proof_len, gadget_label, d_proofs, d_commitments, d_init, d_ok):
-        lab = (gadget_label + bytes(32))[:32]
-        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2_dev(self.ctx, gens, circuit, nb, n1, proof_len, _buf(lab), d_proofs, d_commitments, d_init,
+        self._ck(_lib.bpgpu_r1cs_verify_batch_wire2_dev(self.ctx, gens, circuit, nb, n1, proof_len, _label(gadget_label), d_proofs, d_commitments, d_init,
                                                         d_ok))
 
     def r1cs_verify_combined(self, gens, circuit, nb, n1, k, m, points, scalars, challenges, rho):
@@ -1240,6 +1251,11 @@ class BpPool:
                                                       C.byref(h)))
         return h
 
+    def circuit_set_gadget_labels(self, circuit, labels):
+        """BpGpu.circuit_set_gadget_labels on every slot's handle"""
+        tab = None if labels is None else _buf(b"".join((bytes(x) + bytes(32))[:32] for x in labels))
+        self._ck(_lib.bpgpu_pool_circuit_set_gadget_labels(self.pool, circuit, tab))
+
     def witness_create(self, n, n1, m, nchi, op, arg, row_ptr, kind, idx, coeff):
         """BpGpu.witness_create per distinct device"""
         h = C.c_void_p()
@@ -1296,8 +1312,9 @@ class BpPool:
                 bytes(ch)[:32 * nb * (5 + k)], bytes(so)[:32 * nb])
 
     def r1cs_prove_values(self, gens, circuit, w, nb, n, m, *, init_states, blindings, v=None, v_blinding=None, inputs=None,
-                          gadget_label=None, s_L=None, s_R=None, vector_keys=None, want_wire=True, want_witness=False):
+                          gadget_label=None, s_L=None, s_R=None, vector_keys=None, want_wire=True, want_witness=False,
+                          nchi=None):
         """BpGpu.r1cs_prove_values with the provers dealt over the slots (pool handles): the same operands -> ProveValues"""
-        lab = None if gadget_label is None else _buf((gadget_label + bytes(32))[:32])
+        lab = _label(gadget_label)
         return _prove_values_host(lambda *a: self._ck(_lib.bpgpu_pool_r1cs_prove_values(self.pool, gens, circuit, w, *a)), nb, n, m, lab,
-                                  init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness)
+                                  init_states, v, v_blinding, inputs, s_L, s_R, vector_keys, blindings, want_wire, want_witness, nchi)
