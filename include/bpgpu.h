@@ -611,6 +611,24 @@ int bpgpu_r1cs_constraints_satisfied_dev(bpgpu_ctx *ctx, const bpgpu_circuit *c,
  *                     left out): 256 provers x one level of 1024 INV gates 0.123 | 45.964 | 0.074; 1 x 1024: 0.093 | 50.777 |
  *                     0.045; 4096 x 16: 0.634 | 0.743 | 0.055; 256 x a chain of 64, one gate a level, nothing to batch: 3.102 |
  *                     2.921 | 0.031.  Every other shape is UNMEASURED; the route rule is the one below, unchanged.
+ *   BPGPU_GATE_DIVREM the integer quotient and remainder of a div-rem / floor gadget, its allocate(Some(q)) and allocate(Some(r)),
+ *                     which share one multiplier (prover.rs:127-146): with x and y the CANONICAL integers in [0, n) of eval(left)
+ *                     and eval(right), a_L[i] = floor(x / y), a_R[i] = x mod y, a_O[i] = a_L[i] a_R[i] mod n; for y = 0 (an empty
+ *                     right row is one) a_L[i] = 0 and a_R[i] = x.  x = a_L[i] y + a_R[i] holds over the integers for every input:
+ *                     it is the circuit's range check r < y that rejects a zero divisor.  Both rows may hold whatever a MUL row
+ *                     may; arg[i] is ignored; validation is that of a MUL gate with the same rows.  The division is a restoring
+ *                     shift-and-subtract on 8 x 32-bit words (csrc/int_div.cuh), bitlen(x) - bitlen(y) + 1 steps, none for x < y.
+ *                     A DIVREM gate has the level of a MUL gate with its rows, is never a chain MEMBER of either kind, may be a
+ *                     chain's head, and a MUL may link to its a_O; in the block and scan forms it is strided over the threads
+ *                     like any gate of its level (nothing is batched), and for a row of more than 64 terms lane 0 divides what
+ *                     the wave summed.  A phase without a DIVREM gate launches the kernels it always did.
+ *                     Measured (profiles/witness_divrem.log, median ms; block form | lane form | the same program with
+ *                     INPUT gates handed the (q, r) pairs in the block form | in the lane form, the host's work left out; x of 64
+ *                     bits over y of 33 bits, then x of 252 bits over y of 128 bits): 256 provers x one level of 1024 DIVREM
+ *                     gates 0.101 | 12.917 | 0.074 | 5.565, then 0.138 | 21.593 | 0.075 | 5.580; 1 x 1024: 0.072 | 13.449 | 0.045 |
+ *                     5.767, then 0.107 | 22.789 | 0.045 | 5.660; 4096 x 16: 0.079 | 0.225 | 0.055 | 0.116, then 0.117 | 0.360 |
+ *                     0.055 | 0.116; 256 x a chain of 64, one gate a level: 1.061 | 0.861 | 0.031 | 0.371, then 1.810 | 1.402 |
+ *                     0.031 | 0.371.  Every other shape is UNMEASURED; the route rule is the one below, unchanged.
  * bpgpu_witness_create validates on the host, before anything is uploaded; after it no kernel index can be out of range.
  * BPGPU_E_ARG: a null pointer, an unknown op or kind, a multiplier term with idx >= i (a self or forward reference), a chi part in a
  * gate < n1 (the challenge does not exist in phase 1), a committed index >= m, a BIT with arg >= 252, a non-empty row where the op
@@ -662,7 +680,8 @@ typedef struct bpgpu_witness bpgpu_witness;
 #define BPGPU_GATE_MUL 0
 #define BPGPU_GATE_INPUT 1
 #define BPGPU_GATE_BIT 2
-#define BPGPU_GATE_INV 4 /* not 3: callers and tests probe 3 as "an unknown op", so 3 stays refused (BPGPU_E_ARG), like every op above 4 */
+#define BPGPU_GATE_INV 4 /* not 3: callers and tests probe 3 as "an unknown op", so 3 stays refused (BPGPU_E_ARG) */
+#define BPGPU_GATE_DIVREM 6 /* not 5: tests probe 5 as "an unknown op" too, so 5 stays refused, like 3 and every op above 6 */
 int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t nchi, const uint8_t *op, const uint32_t *arg,
                          const uint32_t *row_ptr, const uint32_t *kind, const uint32_t *idx, const uint8_t *coeff, bpgpu_witness **out);
 void bpgpu_witness_destroy(bpgpu_ctx *ctx, bpgpu_witness *w);
@@ -928,6 +947,8 @@ int bpgpu_mpc_commit_values(bpgpu_ctx *ctx, const bpgpu_gens *g, size_t nb, size
  * phase (a bit of a shared value is not a local function: the range gadget on shares takes its bits as INPUT pairs (1 - b, b)); a
  * BPGPU_GATE_INV gate in the evaluated phase (neither is the inverse of a shared value: on shares the is-zero gadget takes
  * (x, x^-1) as an INPUT pair; a phase without one is evaluated as before, whatever the other phase holds); a
+ * BPGPU_GATE_DIVREM gate in the evaluated phase (nor is the integer quotient of a shared value: on shares the div-rem gadget takes
+ * (q, r) as an INPUT pair; again a phase without one is evaluated as before); a
  * context after bpgpu_set_shard(world > 1); _mask twice in a row; _combine without a _mask; _mask with no level left; _finish with a
  * level left.  BPGPU_E_LEN: 3 nb n or 3 nb m above 2^30.  nb == 0: BPGPU_OK with *out left NULL.  A non-canonical ark limb in any
  * input, `opened` and `triples` included, gives BPGPU_E_ARG, as the other two-party calls do; the session stays where it was (the

@@ -51,6 +51,7 @@ int begin_check(bpgpu_ctx *ctx, const bpgpu_witness *w, size_t nb, int phase, co
   if (want_chi != (chi != nullptr)) return BPGPU_E_ARG;
   if ((phase != 2 && w->bits[0]) || (phase != 1 && w->bits[1])) return BPGPU_E_ARG;   // a bit of a shared value is not a local function
   if ((phase != 2 && w->invs[0]) || (phase != 1 && w->invs[1])) return BPGPU_E_ARG;   // ... and neither is its inverse
+  if ((phase != 2 && w->divs[0]) || (phase != 1 && w->divs[1])) return BPGPU_E_ARG;   // ... nor its integer quotient
   if (bpgpu_internal_shard_world(ctx) > 1) return BPGPU_E_ARG;
   if (!nb) return BPGPU_OK;
   if ((w->m && !v) || (w->ninp && !inputs)) return BPGPU_E_ARG;

@@ -16,7 +16,7 @@ using namespace bpk;
 using namespace bp;
 
 static_assert(BPGPU_GATE_MUL == WIT_OP_MUL && BPGPU_GATE_INPUT == WIT_OP_INPUT && BPGPU_GATE_BIT == WIT_OP_BIT &&
-              BPGPU_GATE_INV == WIT_OP_INV, "gate ops of the header");
+              BPGPU_GATE_INV == WIT_OP_INV && BPGPU_GATE_DIVREM == WIT_OP_DIVREM, "gate ops of the header");
 
 namespace {
 
@@ -50,7 +50,7 @@ constexpr uint32_t WIT_NONE = 0xFFFFFFFFu;
 struct WitShape {
   std::vector<uint32_t> level;    // per gate, within its phase
   std::vector<uint32_t> row_len;  // per row 2 i, 2 i + 1: the terms of all 1 + nchi blocks
-  uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0, ninv[2] = {0, 0};
+  uint32_t levels[2] = {0, 0}, widest = 0, nlong = 0, ninp = 0, ninv[2] = {0, 0}, ndiv[2] = {0, 0};
   size_t nnz = 0;
   // product chains: a member's predecessor (WIT_NONE: an ordinary gate), the side of its link row, a gate's member successor, and
   // the compressed levels, in which a member takes its predecessor's
@@ -120,9 +120,10 @@ int wit_analyse(size_t n, size_t n1, size_t nchi, const uint8_t *op, const uint3
   s->link_right.assign(n, 0);
   std::vector<uint32_t> width, length(n, 0);   // length: of a head, the members of its chain; of a member, its head
   for (size_t i = 0; i < n; i++) {
-    if (op[i] > BPGPU_GATE_INV || op[i] == 3) return BPGPU_E_ARG;      // (3 is no op: bpgpu.h)
+    if (op[i] > BPGPU_GATE_DIVREM || op[i] == 3 || op[i] == 5) return BPGPU_E_ARG;      // (3 and 5 are no ops: bpgpu.h)
     if (op[i] == BPGPU_GATE_INPUT) s->ninp++;
     if (op[i] == BPGPU_GATE_INV) s->ninv[i < n1 ? 0 : 1]++;
+    if (op[i] == BPGPU_GATE_DIVREM) s->ndiv[i < n1 ? 0 : 1]++;
     const size_t phase_lo = i < n1 ? 0 : n1;
     uint32_t lvl = 0, slvl = 0;
     for (size_t side = 0; side < 2; side++)
@@ -234,7 +235,7 @@ void wit_phase(const Entered &e, const bpgpu_witness *w, size_t nb, int ph, cons
   const uint32_t l_lo = ph == 1 ? 0 : levels[0];
   const int form = route == 3 && w->affine[ph - 1] ? 4 : route;           // a phase with an affine member: the affine instantiation
   Prof22 prof(e.ctx);
-  witness_eval(e.view.st, w->dev, nb, form, w->invs[ph - 1] != 0, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
+  witness_eval(e.view.st, w->dev, nb, form, w->invs[ph - 1] != 0, w->divs[ph - 1] != 0, g_lo, g_hi, l_lo, l_lo + levels[ph - 1], run.L, run.R, run.O, run.v, run.in, chi);
 }
 // the gates [lo, lo + count) of every prover, out of the run's planes into ark planes of `stride` scalars per prover
 void wit_export(const Entered &e, const bpgpu_witness *w, size_t nb, const WitRun &run, size_t lo, size_t count, void *aL, void *aR, void *aO,
@@ -634,6 +635,7 @@ int bpgpu_witness_create(bpgpu_ctx *ctx, size_t n, size_t n1, size_t m, size_t n
     w->levels[0] = s.levels[0]; w->levels[1] = s.levels[1];
     for (size_t i = 0; i < n; i++) if (op[i] == BPGPU_GATE_BIT) w->bits[i < n1 ? 0 : 1]++;
     w->invs[0] = s.ninv[0]; w->invs[1] = s.ninv[1];
+    w->divs[0] = s.ndiv[0]; w->divs[1] = s.ndiv[1];
     w->level_ptr.assign(h_lp, h_lp + nlev + 1);
     w->level_long.assign(h_ll, h_ll + nlev);
     for (int ph = 0; ph < 2; ph++) {

@@ -25,12 +25,14 @@ __device__ __forceinline__ WitProver wit_prover(const WitArgs &a, size_t p) {
 // A lane per prover: the gates in program order, which is topological (a term reads a gate below its own), so a lane only ever
 // reads what it has stored itself.
 // The three kernels are templated on INV, whether the launch's range holds an INV gate: the <.., false> instantiations are the
-// kernels of a program without one, with no inversion in them and no read of level_inv / scan_inv.
-template <bool INV> __global__ void __launch_bounds__(256) k_witness_lane(WitArgs a) {
+// kernels of a program without one, with no inversion in them and no read of level_inv / scan_inv.  DIV is the same for a DIVREM
+// gate (int_div.cuh): the <.., false> instantiations carry no integer division.  A DIVREM gate is an ordinary gate of its level --
+// strided over the threads with the others, nothing to batch -- and with a long row lane 0 divides.
+template <bool INV, bool DIV> __global__ void __launch_bounds__(256) k_witness_lane(WitArgs a) {
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= a.nb) return;
   const WitProver o = wit_prover(a, p);
-  for (uint32_t i = a.g_lo; i < a.g_hi; i++) wit_gate_lane_of<INV>(a.w, i, o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
+  for (uint32_t i = a.g_lo; i < a.g_hi; i++) wit_gate_lane_of<INV, DIV>(a.w, i, o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
 }
 // A block per prover: level by level.  The gates of a level read lower levels only (or earlier phases), so they are independent:
 // those without a long row are strided over the 256 threads, the others over the four waves (lane-strided terms, then wave_sum, as
@@ -41,10 +43,11 @@ template <bool INV> __global__ void __launch_bounds__(256) k_witness_lane(WitArg
 // like the others, and a thread inverts ONCE per level for all of its own (witness_dev.cuh wit_inv_forward / _backward): it reads
 // back only what it parked itself, so the level needs no fence or barrier of its own; the loop bounds are block-uniform, and a
 // thread without an INV gate inverts 1.  Without INV, inv == mid.  An INV gate with a long row is lane 0's, one inversion each.
-template <bool INV> __device__ __forceinline__ void wit_level_gates(const WitArgs &a, const WitProver &o, const uint32_t *order, uint32_t lo,
-                                                                    uint32_t inv_lo, uint32_t mid, uint32_t hi) {
+template <bool INV, bool DIV>
+__device__ __forceinline__ void wit_level_gates(const WitArgs &a, const WitProver &o, const uint32_t *order, uint32_t lo, uint32_t inv_lo,
+                                                uint32_t mid, uint32_t hi) {
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (uint32_t t = lo + threadIdx.x; t < inv_lo; t += 256) wit_gate_lane_of<false>(a.w, order[t], o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
+  for (uint32_t t = lo + threadIdx.x; t < inv_lo; t += 256) wit_gate_lane_of<false, DIV>(a.w, order[t], o.aL, o.aR, o.aO, o.v, o.inputs, o.chi);
   if (INV && inv_lo < mid) {                                                                   // block-uniform
     const uint32_t first = inv_lo + threadIdx.x;
     const Fn run = wit_inv_forward(a.w, order, first, mid, 256, o.aL, o.aR, o.aO, o.v, o.chi);
@@ -56,7 +59,9 @@ template <bool INV> __device__ __forceinline__ void wit_level_gates(const WitArg
     const Fn one = fe_one<FN>();
     const Fn left = wave_sum(fn_reduce(eval_row(a.w.rows, rp[0] + lane, rp[1], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
     const Fn right = wave_sum(fn_reduce(eval_row(a.w.rows, rp[1] + lane, rp[2], 64, o.aL, o.aR, o.aO, o.v, one, o.chi)));
-    if (lane == 0) {
+    if (DIV) {
+      if (lane == 0) wit_gate_store_of<INV, DIV>(a.w.op[i], a.w.arg[i], left, right, o.inputs, o.aL + i, o.aR + i, o.aO + i);
+    } else if (lane == 0) {
       const WitGate g = wit_gate_values_of<INV>(a.w.op[i], a.w.arg[i], left, right, o.inputs);
       wit_store(o.aL + i, g.L);
       wit_store(o.aR + i, g.R);
@@ -64,11 +69,11 @@ template <bool INV> __device__ __forceinline__ void wit_level_gates(const WitArg
     }
   }
 }
-template <bool INV> __global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
+template <bool INV, bool DIV> __global__ void __launch_bounds__(256) k_witness_block(WitArgs a) {
   const WitProver o = wit_prover(a, blockIdx.x);
   for (uint32_t l = a.l_lo; l < a.l_hi; l++) {
     const uint32_t mid = a.w.level_long[l];
-    wit_level_gates<INV>(a, o, a.w.order, a.w.level_ptr[l], INV ? a.w.level_inv[l] : mid, mid, a.w.level_ptr[l + 1]);
+    wit_level_gates<INV, DIV>(a, o, a.w.order, a.w.level_ptr[l], INV ? a.w.level_inv[l] : mid, mid, a.w.level_ptr[l + 1]);
     if (l + 1 < a.l_hi) {
       __threadfence_block();
       __syncthreads();
@@ -134,7 +139,7 @@ template <> struct WitScanOf<true> {
     wit_aff_apply(w, lo, hi, carry.b, o);
   }
 };
-template <bool AFFINE, bool INV> __global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
+template <bool AFFINE, bool INV, bool DIV> __global__ void __launch_bounds__(256) k_witness_scan(WitArgs a) {
   using S = WitScanOf<AFFINE>;
   using Part = typename S::Part;
   __shared__ int32_t s_part[4][S::WORDS];
@@ -143,7 +148,7 @@ template <bool AFFINE, bool INV> __global__ void __launch_bounds__(256) k_witnes
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (uint32_t l = a.l_lo; l < a.l_hi; l++) {
     const uint32_t mid = a.w.scan_long[l];
-    wit_level_gates<INV>(a, o, a.w.scan_order, a.w.scan_ptr[l], INV ? a.w.scan_inv[l] : mid, mid, a.w.scan_ptr[l + 1]);
+    wit_level_gates<INV, DIV>(a, o, a.w.scan_order, a.w.scan_ptr[l], INV ? a.w.scan_inv[l] : mid, mid, a.w.scan_ptr[l + 1]);
     const uint32_t c_lo = a.w.chain_ptr[l], c_hi = a.w.chain_ptr[l + 1];                       // block-uniform
     if (c_lo < c_hi) {
       __threadfence_block();
@@ -170,16 +175,19 @@ template <bool AFFINE, bool INV> __global__ void __launch_bounds__(256) k_witnes
     }
   }
 }
-void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, bool inv, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo,
+template <bool INV, bool DIV> static void (*wit_kernel_of(int form))(WitArgs) {
+  if (form == 4) return k_witness_scan<true, INV, DIV>;
+  if (form == 3) return k_witness_scan<false, INV, DIV>;
+  if (form == 2) return k_witness_block<INV, DIV>;
+  return k_witness_lane<INV, DIV>;
+}
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, bool inv, bool div, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo,
                   uint32_t l_hi, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi) {
   if (!nb || g_lo >= g_hi) return;
   const WitArgs a{w, nb, g_lo, g_hi, l_lo, l_hi, aL, aR, aO, v, inputs, chi};
   const dim3 blocks((unsigned)nb), lanes((unsigned)((nb + 255) / 256));
-  void (*kernel)(WitArgs);
-  if (form == 4) kernel = inv ? k_witness_scan<true, true> : k_witness_scan<true, false>;
-  else if (form == 3) kernel = inv ? k_witness_scan<false, true> : k_witness_scan<false, false>;
-  else if (form == 2) kernel = inv ? k_witness_block<true> : k_witness_block<false>;
-  else kernel = inv ? k_witness_lane<true> : k_witness_lane<false>;
+  void (*kernel)(WitArgs) = div ? (inv ? wit_kernel_of<true, true>(form) : wit_kernel_of<false, true>(form))
+                                 : (inv ? wit_kernel_of<true, false>(form) : wit_kernel_of<false, false>(form));
   hipLaunchKernelGGL(kernel, form >= 2 ? blocks : lanes, dim3(256), 0, st, a);
 }
 

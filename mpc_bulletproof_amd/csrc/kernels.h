@@ -312,7 +312,8 @@ struct WitDev {
 // holds an affine member (form 4), as one segmented prefix composition of affine maps (k_witness_scan<true>).
 // inv: the range holds an INV gate -- the <.., true> instantiation of the form's kernel, which carries the field inversion (one per
 // gate in form 1 and for a long row, one per thread and level otherwise); a range without one launches the kernel it always did.
-void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, bool inv, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo,
+// div: the range holds a DIVREM gate -- the instantiation that carries the integer division (int_div.cuh), chosen the same way.
+void witness_eval(hipStream_t st, const WitDev &w, size_t nb, int form, bool inv, bool div, uint32_t g_lo, uint32_t g_hi, uint32_t l_lo,
                   uint32_t l_hi, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs, const Words8 *chi);
 // rows of `count` scalars, one per prover: src + p * src_stride -> dst + p * dst_stride.  to_ark: plain canonical -> ark Montgomery
 // limbs, else the reverse; a non-canonical source raises *bad and gives zero

@@ -3,10 +3,12 @@
 // compiles for the CPU.  The row sums are eval_row's (fn_dev.cuh): lazy, reduced here before the gate's product.
 #pragma once
 #include "fn_dev.cuh"
+#include "int_div.cuh"
 
 namespace bpk {
 
 constexpr uint32_t WIT_OP_MUL = 0, WIT_OP_INPUT = 1, WIT_OP_BIT = 2, WIT_OP_INV = 4;   // BPGPU_GATE_* of include/bpgpu.h (3 is no op)
+constexpr uint32_t WIT_OP_DIVREM = 6;                                  // (and neither is 5)
 constexpr uint32_t WIT_BIT_MAX = 252;                                  // a BIT gate reads a bit below this one
 
 struct WitGate { Fn L, R, O; };
@@ -25,13 +27,28 @@ BP_HD bool wit_store_nz(Words8 *p, const Fn &x) {
   for (int j = 0; j < 8; j++) { p->w[j] = w[j]; any |= w[j]; }
   return any != 0;
 }
+// A DIVREM gate's quotient and remainder words from the lazy sums of its two rows: x and y are the CANONICAL integers of the rows
+// (a value left lazily at v + n, or negative, has another quotient), brought there the way the BIT gate brings its integer.
+BP_HD void wit_divrem_words(uint32_t (&q)[8], uint32_t (&r)[8], const Fn &left, const Fn &right) {
+  uint32_t x[8], y[8];
+  pack(x, from_mont(fn_reduce(left)));
+  pack(y, from_mont(fn_reduce(right)));
+  int_divrem(q, r, x, y);
+}
 // The gate's three values from the lazy sums of its two rows.  Both operands of the product are reduced first: mul documents
 // |v| < 2^256 for two general operands, and a lazy sum of 16 products is far above that.  `inputs`: the prover's pairs (plain words);
 // arg: the pair of an INPUT gate, the bit (< WIT_BIT_MAX) of a BIT gate.  INV: whether the caller's program may hold an INV gate (a
-// kernel of a phase without one carries no inversion: k_witness.hip).
-template <bool INV> BP_HD WitGate wit_gate_values_of(uint32_t op, uint32_t arg, const Fn &left, const Fn &right, const Words8 *inputs) {
+// kernel of a phase without one carries no inversion: k_witness.hip); DIV: the same for a DIVREM gate and the integer division.
+template <bool INV, bool DIV = false>
+BP_HD WitGate wit_gate_values_of(uint32_t op, uint32_t arg, const Fn &left, const Fn &right, const Words8 *inputs) {
   WitGate g;
-  if (INV && op == WIT_OP_INV) {
+  if (DIV && op == WIT_OP_DIVREM) {
+    // q and r are canonical integers below n (q <= x, r <= x): unpack gives tight limbs, to_mont the Montgomery form
+    uint32_t q[8], r[8];
+    wit_divrem_words(q, r, left, right);
+    g.L = to_mont(unpack<FN>(q));
+    g.R = to_mont(unpack<FN>(r));
+  } else if (INV && op == WIT_OP_INV) {
     // inverse-or-zero: inv maps 0 to 0, so a zero a_L gives a_R = a_O = 0 with no test (0 in any lazy form is 0 mod n).  inv's
     // result has lazy signed limbs of magnitude below 2^29 and |value| < 2 n < 2^256: an operand mul takes as it stands (fe29.cuh:
     // the bounds are on magnitudes), so it feeds the gate's product, and wit_store's from_mont, without a reduction.
@@ -56,15 +73,38 @@ template <bool INV> BP_HD WitGate wit_gate_values_of(uint32_t op, uint32_t arg, 
   return g;
 }
 BP_HD WitGate wit_gate_values(uint32_t op, uint32_t arg, const Fn &left, const Fn &right, const Words8 *inputs) {
-  return wit_gate_values_of<true>(op, arg, left, right, inputs);
+  return wit_gate_values_of<true, true>(op, arg, left, right, inputs);
+}
+// ... and stored: a_L and a_R of a DIVREM gate as the plain words the division produced, a_O from them; every other gate as
+// wit_gate_values_of has it
+template <bool INV, bool DIV = false>
+BP_HD void wit_gate_store_of(uint32_t op, uint32_t arg, const Fn &left, const Fn &right, const Words8 *inputs, Words8 *pL, Words8 *pR,
+                             Words8 *pO) {
+  if (DIV && op == WIT_OP_DIVREM) {
+    uint32_t q[8], r[8];
+    wit_divrem_words(q, r, left, right);
+#pragma unroll
+    for (int j = 0; j < 8; j++) { pL->w[j] = q[j]; pR->w[j] = r[j]; }
+    wit_store(pO, mul(to_mont(unpack<FN>(q)), to_mont(unpack<FN>(r))));
+    return;
+  }
+  const WitGate g = wit_gate_values_of<INV, false>(op, arg, left, right, inputs);
+  wit_store(pL, g.L);
+  wit_store(pR, g.R);
+  wit_store(pO, g.O);
 }
 // gate i of one prover, both rows by this lane; aL, aR, aO, v, inputs, chi: the prover's own (plain canonical words)
-template <bool INV> BP_HD void wit_gate_lane_of(const WitDev &w, uint32_t i, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v,
-                                                const Words8 *inputs, const Words8 *chi) {
+template <bool INV, bool DIV = false>
+BP_HD void wit_gate_lane_of(const WitDev &w, uint32_t i, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs,
+                            const Words8 *chi) {
   const uint32_t *rp = w.rows.row_ptr + 2 * (size_t)i;
   const Fn one = fe_one<FN>();
   const Fn left = eval_row(w.rows, rp[0], rp[1], 1, aL, aR, aO, v, one, chi);
   const Fn right = eval_row(w.rows, rp[1], rp[2], 1, aL, aR, aO, v, one, chi);
+  if (DIV) {                 // (a kernel without the op keeps the statements it always had)
+    wit_gate_store_of<INV, DIV>(w.op[i], w.arg[i], left, right, inputs, aL + i, aR + i, aO + i);
+    return;
+  }
   const WitGate g = wit_gate_values_of<INV>(w.op[i], w.arg[i], left, right, inputs);
   wit_store(aL + i, g.L);
   wit_store(aR + i, g.R);
@@ -72,7 +112,7 @@ template <bool INV> BP_HD void wit_gate_lane_of(const WitDev &w, uint32_t i, Wor
 }
 BP_HD void wit_gate_lane(const WitDev &w, uint32_t i, Words8 *aL, Words8 *aR, Words8 *aO, const Words8 *v, const Words8 *inputs,
                          const Words8 *chi) {
-  wit_gate_lane_of<true>(w, i, aL, aR, aO, v, inputs, chi);
+  wit_gate_lane_of<true, true>(w, i, aL, aR, aO, v, inputs, chi);
 }
 
 // ---- a level's INV gates with ONE inversion per thread (Montgomery's trick) -----------------------------------------------------------

@@ -13,6 +13,7 @@ struct bpgpu_witness {
   size_t n = 0, n1 = 0, m = 0, nchi = 0, ninp = 0;
   uint32_t bits[2] = {0, 0};    // BIT gates per phase
   uint32_t invs[2] = {0, 0};    // INV gates per phase
+  uint32_t divs[2] = {0, 0};    // DIVREM gates per phase
   uint32_t levels[2] = {0, 0};
   // per phase: the extended compressed levels (the scan lists are the extended chains'; without an affine member those are the
   // product chains'), the longest product chain, the longest extended chain, and whether the phase has an affine member

@@ -128,6 +128,7 @@ def pippenger_plan(nb, n):
 WIT_PLAN_FIELDS = ("levels1", "levels2", "widest", "long_rows", "inputs", "route1", "route2")
 GATE_MUL, GATE_INPUT, GATE_BIT = 0, 1, 2
 GATE_INV = 4         # (3 is no op: include/bpgpu.h)
+GATE_DIVREM = 6      # (and neither is 5)
 
 
 def _u32s(xs, pad=1):

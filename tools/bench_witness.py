@@ -34,6 +34,12 @@ nothing to batch).  Per shape three columns: (a) the block form (BPGPU_OPT_WITNE
 INV gate replaced by an INPUT gate fed the precomputed pairs, on route 2: the only way a library without the op runs it, the host's
 own inversions and the upload of the pairs left out; what the device inversion costs over having been handed the answer is (a) / (c).
 
+`bench_witness.py divrem` measures the DIVREM gates (BPGPU_GATE_DIVREM) and appends to profiles/witness_divrem.log.  The shapes of
+`inv`, each on two kinds of operands: `u64` = x of 64 bits over y of 33 bits, both below 2^64 (a 32.32 fixed-point quotient: 32 steps
+of the division), and `wide` = x of 252 bits over y of 128 bits (125 steps, the long loop).  Per line four columns: (a) the block
+form and (b) the lane form of the program with DIVREM gates, and (c), (d) the same two forms of the same program with every DIVREM
+gate replaced by an INPUT gate handed the (q, r) pairs, the host's divisions and the upload left out: the floor.
+
 A fresh process per line under its own time limit; WARM untimed steps, then STEPS timed ones, medians (min..max) in ms."""
 import ctypes as C
 import json
@@ -136,6 +142,64 @@ def inv_synth(shape, nb, size):
     plan = m.lib.witness_plan(*prog.plan_args(), nb)
     return (f"(a) block {fmt(out['block'])}   (b) lane {fmt(out['lane'])}   (c) INPUT {fmt(out['input'])}   (b)/(a) {b / a:8.2f}   (a)/(c) {a / c:8.2f}   "
             f"(b)/(c) {b / c:8.2f}   plan: {('lane', 'block', 'scan')[plan['route1'] - 1]:5s}   levels {plan['levels1']:3d}")
+
+
+DIVREM_OPERANDS = {"u64": (64, 33), "wide": (252, 128)}      # bit lengths of x and y
+
+
+def divrem_programs(shape, size, kind):
+    """(the program with DIVREM gates, its twin with INPUT gates, one prover's values): `level` = size independent gates
+    divrem(v_x + i + 1, v_y), `chain` = size gates divrem(v_x + a_R[i - 1], v_y), each reading the remainder below it"""
+    import witness_cases as wc
+    import witness_divrem_cases as dc
+    bx, by = DIVREM_OPERANDS[kind]
+    v = [(1 << (bx - 1)) | ((0x9E3779B97F4A7C15 * (j + 1)) & ((1 << (bx - 2)) - 1)) for j in range(2)]
+    v += [(1 << (by - 1)) | ((0xC2B2AE3D27D4EB4F * (j + 1)) & ((1 << (by - 2)) - 1)) for j in range(2)]
+    prog, twin = dc.Program(4), dc.Program(4)
+    last = None
+    for i in range(size):
+        if shape == "chain" and last is not None:
+            last = prog.divrem([(wc.V, i % 2, 1), (wc.R, last, 1)], [(wc.V, 2 + i % 2, 1)])
+        else:
+            last = prog.divrem([(wc.V, i % 2, 1), (wc.ONE, 0, i + 1)], [(wc.V, 2 + i % 2, 1)])
+        twin.input()
+    prog.end_phase1()
+    twin.end_phase1()
+    return prog, twin, v
+
+
+def divrem_synth(shape, nb, size, kind):
+    import mpc_dealer as md
+    import mpc_bulletproof_amd as m
+    prog, twin, v = divrem_programs(shape, size, kind)
+    want = prog.evaluate(v)
+    bx, by = DIVREM_OPERANDS[kind]
+    assert all(q.bit_length() in (bx - by, bx - by + 1) for q in want[0])
+    gpu = m.BpGpu(0)
+    d_v = gpu.to_device(b"".join(md.mont(x) for x in v) * nb)
+    d_in = gpu.to_device(b"".join(md.mont(x) for pair in zip(want[0], want[1]) for x in pair) * nb)
+    planes = [gpu.malloc(32 * nb * size) for _ in range(3)]
+    timer = Timer(gpu)
+    out = {}
+    for col, which, route in (("block", prog, 2), ("lane", prog, 1), ("input block", twin, 2), ("input lane", twin, 1)):
+        w = gpu.witness_create(*which.create_args())
+        gpu.set_option("witness_route", route)
+        ts = []
+        for step in range(WARM + STEPS):
+            ms = timer.events(lambda: gpu.r1cs_witness_synthesize_dev(w, nb, 0, *planes, d_v=d_v, d_inputs=d_in if which is twin else None))
+            if step >= WARM:
+                ts.append(ms)
+        assert gpu.input_flag() == 0
+        for k in range(3):
+            got = gpu.download(planes[k], 32 * nb * size)
+            assert got[-32 * size:] == b"".join(md.mont(x) for x in want[k]), "the device's witness differs from divmod's"
+        gpu.witness_destroy(w)
+        out[col] = ts
+    a, b, c, d = (statistics.median(out[col]) for col in ("block", "lane", "input block", "input lane"))
+    plan = m.lib.witness_plan(*prog.plan_args(), nb)
+    return (f"(a) block {fmt(out['block'])}   (b) lane {fmt(out['lane'])}   (c) INPUT block {fmt(out['input block'])}   "
+            f"(d) INPUT lane {fmt(out['input lane'])}   (a)/(c) {a / c:8.2f}   (b)/(d) {b / d:8.2f}   "
+            f"plan: {('lane', 'block', 'scan')[plan['route1'] - 1]:5s}   levels {plan['levels1']:3d}")
 
 
 class Timer:
@@ -267,6 +331,8 @@ def prove(nb, ks, window_bits):
 def child(what, args):
     if what == "inv":
         print("RESULT", inv_synth(args[0], int(args[1]), int(args[2])))
+    elif what == "divrem":
+        print("RESULT", divrem_synth(args[0], int(args[1]), int(args[2]), args[3]))
     elif what == "synth":
         text, spans = synth(args[0], int(args[1]), int(args[2]), tuple(args[3].split(",")))
         print("SPANS", json.dumps(spans))
@@ -389,6 +455,27 @@ def inv_main():
     return 0 if ok else 1
 
 
+def divrem_main():
+    lines, _, step = runner("divrem ")
+    lines[-1] = ("# divrem: bpgpu_r1cs_witness_synthesize_dev alone, HIP events; (a) route 2 and (b) route 1 on DIVREM gates; (c), (d) the same "
+                 "routes with the DIVREM gates as INPUT gates handed the (q, r) pairs; u64: x of 64 bits / y of 33 bits, wide: 252 / 128")
+    ok = True
+    for shape, nb, size in INV_SHAPES:
+        for kind in DIVREM_OPERANDS:
+            text = f"divrem  {nb:4d} x {'a chain of' if shape == 'chain' else 'one level of'} {size:4d} DIVREM gates  {kind:4s}   "
+            if ok:
+                ok = step(text, "divrem", shape, nb, size, kind)
+            else:
+                lines.append(text + "UNMEASURED")
+    if not ok:
+        lines.append("# a step failed: the steps after it were not started")
+    path = os.path.join(ROOT, "profiles", "witness_divrem.log")
+    with open(path, "a") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("wrote", path)
+    return 0 if ok else 1
+
+
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3:])
@@ -396,6 +483,8 @@ def main():
         return affine_main()
     if sys.argv[1:] == ["inv"]:
         return inv_main()
+    if sys.argv[1:] == ["divrem"]:
+        return divrem_main()
     lines, spans, step = runner("")
     ok = step("synth   256 x 16 x 64-bit range    n = 1024    ", "synth", "range", 256, 16, "lane,block,scan")
     ok = ok and step("synth   256 x shuffle k = 64       n = 126     ", "synth", "shuffle", 256, 64, "lane,block,scan")
